@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the tidypopgen genotype-matrix hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the whole hot path over one synthetic SNP panel that is already resident in HBM as FBM
 bytes (5 000 individuals x 1 000 000 SNPs, 51 populations, 2 % missing kept as imputed bytes -- BASELINE.json
@@ -18,6 +18,10 @@ xGMI, csrc/comm.hip); torch.distributed (gloo) is only the control plane that ca
   --scaling strong (default): the panel is FIXED (5 000 x 1 000 000, what BASELINE configs 3-5 say) and cut N ways;
   --scaling weak:             every rank owns --snps loci of a panel N times longer.
 Rank 0 prints ONE JSON line.  `value` = N_indiv * M_total genotypes / wall second of the whole step.
+A plain run sets up, warms up, times the K steps (HIP events only around the MFMA kernels `roofline` prices) and prints the
+line.  --full adds what takes runs of its own: the per-kernel table pass, `standalone`, `end_to_end` with `dropin`, and
+`cpu_baseline` with its `parity` against the oracle.  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs) so that two builds can be compared output for output on the same seeded panel.
 """
 import argparse
 import ctypes as C
@@ -51,7 +55,15 @@ def parse():
     ap.add_argument("--no-dropin", action="store_true", help="skip the R-shim block-loop measurement (part of end_to_end)")
     ap.add_argument("--no-standalone", action="store_true", help="skip the stand-alone pairwise_grm / snp_king / snp_ibs timings")
     ap.add_argument("--digest", default=None, help="rank 0 writes a small JSON digest of the results (tests)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs (per-kernel table pass, standalone, end_to_end + dropin, cpu_baseline with "
+                         "parity); without it the run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, a fixed sample of the large outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Step:
@@ -266,6 +278,77 @@ def digest(st):
     chk(st.lib.tpg_dev_to_host(st.ctx.h, st.api._ptr(u), st.d_pca["u"], C.c_size_t(8 * n * k)))
     out["pca_u_abs_colsum"] = np.abs(u).sum(axis=0).tolist()
     return out
+
+
+DUMP_INDIV, DUMP_LOCI, DUMP_BYTES = 512, 16384, 64 << 20
+
+
+def dump_outputs(st, outdir):
+    """What the last step computed, as a caller of the path receives it, into outdir/<name>.npy (float64): the Fst ratios
+    and the PCA's d, u and square Frobenius norm whole; IBS / KING / GRM on a sample of individuals (rows and columns);
+    alt_freq, grouped_alt_freq and the PCA's v, center, scale on a sample of loci (NaN: a locus the PCA dropped).  The
+    samples are seeded and so the same for the same arguments (sample_individuals / sample_loci: their 0-based indices);
+    23 MB at the bench size, at most DUMP_BYTES.  Every rank takes part (the N x N bands and the loci are spread over the
+    ranks, each element is written by exactly one); rank 0 writes the files."""
+    from tidypopgen_amd import sharding
+
+    n, k, G = st.args.n, st.args.k, st.args.pops
+    chk, api, lib, ctx = st.tpg._lib.check, st.api, st.lib, st.ctx
+    rng = np.random.default_rng(20240601)
+    ii = np.sort(rng.choice(n, min(n, DUMP_INDIV), replace=False))
+    fixed = 8 * (3 * len(ii) ** 2 + n * k + 2 * st.P + k + 1 + len(ii))
+    per_locus = 8 * (2 + 2 * G + k + 2 + 1)
+    L = int(min(st.m_total, DUMP_LOCI, max(1, (DUMP_BYTES - fixed) // per_locus)))
+    gl = np.sort(rng.choice(st.m_total, L, replace=False))
+
+    def down(dptr, shape):
+        h = np.empty(shape, order="F")
+        chk(lib.tpg_dev_to_host(ctx.h, api._ptr(h), dptr, C.c_size_t(h.nbytes)))
+        return h
+
+    def over_ranks(val, own):
+        """the entries every rank owns (own) put together; NaN travels as a mask of its own"""
+        if st.world == 1:
+            return val
+        nan = own & np.isnan(val)
+        full = sharding.all_reduce_numpy(np.ascontiguousarray(np.where(own & ~nan, val, 0.0)))
+        nans = sharding.all_reduce_numpy(np.ascontiguousarray(nan.astype(np.float64)))
+        return np.where(nans > 0, np.nan, full)
+
+    fst_results(st)
+    out = {"fst_hudson": st.fst["Hudson"], "fst_wc84": st.fst["WC84"],
+           "sample_individuals": ii.astype(np.float64), "sample_loci": gl.astype(np.float64)}
+    own_nn = sharding.band_mask(n, st.world, st.rank)[np.ix_(ii, ii)]
+    for name, dptr in zip(("ibs", "king", "grm"), st.d_nn):
+        out[name] = over_ranks(down(dptr, (n, n))[np.ix_(ii, ii)], own_nn)
+    # per-locus outputs: this rank holds loci j0 .. j0 + m - 1 of the panel
+    mine = (gl >= st.j0) & (gl < st.j0 + st.m)
+    li = gl[mine] - st.j0
+    for name, dptr, cols in (("alt_freq", st.d_freq, 2), ("grouped_alt_freq", st.d_gfreq, 2 * G)):
+        v = np.zeros((L, cols))
+        v[mine] = down(dptr, (st.m, cols))[li]
+        out[name] = over_ranks(v, np.repeat(mine[:, None], cols, axis=1))
+    if st.has_pca:
+        out["pca_d"] = st.pca_d.copy()
+        out["pca_square_frobenius"] = np.array([st.pca_fro.value])
+        out["pca_u"] = down(st.d_pca["u"], (n, k))
+        # the PCA's rows are this rank's polymorphic loci (pca_cols, 1-based) or all of them
+        if st.pca_cols is None:
+            row, hit = li, np.ones(len(li), dtype=bool)
+        else:
+            cols0 = st.pca_cols.astype(np.int64) - 1
+            row = np.minimum(np.searchsorted(cols0, li), max(0, len(cols0) - 1))
+            hit = (cols0[row] == li) if len(cols0) else np.zeros(len(li), dtype=bool)
+        for name, shape in (("pca_v", (st.m_pca, k)), ("pca_center", (st.m_pca,)), ("pca_scale", (st.m_pca,))):
+            h = down(st.d_pca[name[4:]], shape)
+            v = np.full((L,) + shape[1:], np.nan)
+            sel = np.where(mine)[0][hit]
+            v[sel] = h[row[hit]]
+            out[name] = over_ranks(v, np.broadcast_to(mine.reshape((L,) + (1,) * (len(shape) - 1)), v.shape))
+    if st.rank == 0:
+        os.makedirs(outdir, exist_ok=True)
+        for name, arr in out.items():
+            np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def _e2e_file(st):
@@ -927,10 +1010,11 @@ def main():
         st.run()
     # The timed region brackets only the MFMA kernels the roofline prices with HIP events (on the stream they run on): two
     # event records around a launch cost ~5 us of idle GPU each, and a step has 70 - 170 launches.  The per-kernel table
-    # (kernel_ms_per_step, roofline_other_kernels) comes from a second, untimed pass with every launch bracketed.
+    # (kernel_ms_per_step, roofline_other_kernels) comes from a second, untimed pass with every launch bracketed (--full).
+    # With several ranks the class exchange's all-to-all is bracketed too: config.pca_gram_path names the path by it.
     ROOF_KEYS = ["pairwise_mfma", "pca_gram_mfma", "pca_gram_classes"]
     st.ctx.prof_enable(True)
-    st.ctx.prof_only(ROOF_KEYS)
+    st.ctx.prof_only(ROOF_KEYS + (["gclx_alltoall"] if world > 1 else []))
     st.ctx.prof_reset()
     st.barrier_sync()
     t0 = time.perf_counter()
@@ -941,20 +1025,25 @@ def main():
     if world > 1:
         dt = float(sharding.all_reduce_numpy(np.array([dt]), op="max")[0])
     prof_timed = st.ctx.prof_dump()
-    table_steps = max(2, min(args.steps, 10))
-    st.ctx.prof_only(None)
-    st.ctx.prof_reset()
-    st.barrier_sync()
-    t1 = time.perf_counter()
-    for _ in range(table_steps):
-        st.run()
-    st.barrier_sync()
-    ms_per_step_all_events = (time.perf_counter() - t1) / table_steps * 1e3
-    prof_table = st.ctx.prof_dump()
+    if args.dump_outputs:
+        dump_outputs(st, args.dump_outputs)
+    prof = dict(prof_timed)
+    table_steps = ms_per_step_all_events = None
+    if args.full:
+        table_steps = max(2, min(args.steps, 10))
+        st.ctx.prof_only(None)
+        st.ctx.prof_reset()
+        st.barrier_sync()
+        t1 = time.perf_counter()
+        for _ in range(table_steps):
+            st.run()
+        st.barrier_sync()
+        ms_per_step_all_events = (time.perf_counter() - t1) / table_steps * 1e3
+        prof_table = st.ctx.prof_dump()
+        # one dictionary, per `args.steps` steps: the roofline kernels from the timed region, the others scaled from the table pass
+        prof = {k_: (v_[0] * args.steps / table_steps, v_[1] * args.steps / table_steps) for k_, v_ in prof_table.items()}
+        prof.update(prof_timed)
     st.ctx.prof_enable(False)
-    # one dictionary, per `args.steps` steps: the roofline kernels from the timed region, the others scaled from the table pass
-    prof = {k_: (v_[0] * args.steps / table_steps, v_[1] * args.steps / table_steps) for k_, v_ in prof_table.items()}
-    prof.update(prof_timed)
     dig = digest(st) if args.digest else None
     if rank == 0 and args.digest:
         with open(args.digest, "w") as f:
@@ -1103,17 +1192,19 @@ def main():
             "roofline_other_kernels": roofs[1:] + [r for r in others if r],
             "kernel_ms_from": (f"HIP events; {', '.join(k_ for k_ in ROOF_KEYS if k_ in prof_timed)} inside the timed region, the other "
                                f"kernels in a second pass of {table_steps} steps with every launch bracketed "
-                               f"({ms_per_step_all_events:.3f} ms per step with all the events in the stream)"),
+                               f"({ms_per_step_all_events:.3f} ms per step with all the events in the stream)" if args.full else
+                               f"HIP events; {', '.join(k_ for k_ in ROOF_KEYS if k_ in prof_timed)} inside the timed region "
+                               f"(the other kernels: --full)"),
             "kernel_ms_per_step": {k_: round(v_[1] / args.steps, 4) for k_, v_ in sorted(prof.items())},
             "kernel_launches_per_step": {k_: v_[0] / args.steps for k_, v_ in sorted(prof.items())},
         }
-        # the secondary legs must not take the contract line down with them
-        if world == 1 and not args.no_standalone:
+        # the secondary legs (--full) must not take the contract line down with them
+        if world == 1 and args.full and not args.no_standalone:
             try:
                 out["standalone"] = standalone(st)
             except Exception as e:  # noqa: BLE001
                 out["standalone"] = {"failed": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_end_to_end:
+        if world == 1 and args.full and not args.no_end_to_end:
             try:
                 out["end_to_end"] = end_to_end(st)
             except Exception as e:  # noqa: BLE001
@@ -1125,7 +1216,7 @@ def main():
         # (the driver runs N = 1, 2, 4, 8 back to back), else the committed figure of an earlier round -- labelled as such, never
         # re-timed beside RCCL ranks that own the cores.
         cache = os.path.join(tempfile.gettempdir(), f"tpg_cpu_baseline_{args.n}x{args.m}_G{args.pops}_k{args.k}.json")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, st)
             except Exception as e:  # noqa: BLE001 -- (its parity block already guards itself; this is for the CPU timing)
@@ -1135,7 +1226,7 @@ def main():
                     json.dump({"measured_unix_time": time.time(), "host": os.uname().nodename, "cpu_baseline": out["cpu_baseline"]}, f)
             except OSError:
                 pass
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             cb = None
             try:
                 with open(cache) as f:

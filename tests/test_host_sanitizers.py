@@ -57,9 +57,21 @@ def test_host_pieces_under_address_and_undefined_sanitizers(pieces, what):
     assert r.stdout.strip() == f"ok {what}"
 
 
+def _without_aslr():
+    """GCC's ThreadSanitizer keeps its shadow at fixed addresses; a kernel with high-entropy ASLR (vm.mmap_rnd_bits above
+    28) can map the executable outside the ranges it expects ("FATAL: ThreadSanitizer: unexpected memory mapping").  The
+    binary runs with address-space randomisation off for its own process (setarch -R) wherever the host lets it."""
+    cmd = [shutil.which("setarch") or "setarch", os.uname().machine, "-R"]
+    try:
+        ok = subprocess.run(cmd + ["true"], capture_output=True, timeout=60).returncode == 0
+    except OSError:
+        ok = False
+    return cmd if ok else []
+
+
 @pytest.mark.parametrize("args", [["inproc", "2"], ["inproc", "8"], ["inproc_mismatch"]])
 def test_in_process_transport_under_thread_sanitizer(pieces, args):
-    r = subprocess.run([pieces["tsan"], *args], capture_output=True, text=True, timeout=600, env=ENV)
+    r = subprocess.run(_without_aslr() + [pieces["tsan"], *args], capture_output=True, text=True, timeout=600, env=ENV)
     if r.returncode != 0 and "FATAL: ThreadSanitizer" in r.stderr and "memory layout" in r.stderr:
         pytest.skip("ThreadSanitizer cannot map its shadow in this container")
     assert r.returncode == 0 and "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-4000:]

@@ -22,7 +22,7 @@ n, m, G, R = 5000, 1_000_000, 51, 8
 out = {"workload": f"{n} x {m}, {G} populations, k = 20, {R} ranks (strong scaling: 125 000 loci per rank)"}
 
 # shard-local kernels
-r = subprocess.run([sys.executable, "bench.py", "--snps", str(m // R), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+r = subprocess.run([sys.executable, "bench.py", "--full", "--snps", str(m // R), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
                     "--no-end-to-end"], capture_output=True, text=True, env=dict(os.environ, TPG_GRAM_NO_EXCHANGE="1"))
 line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]
 b = json.loads(line)
