@@ -39,6 +39,16 @@
 
 static inline int is_na(double x) { return isnan(x); } /* NumericVector::is_na == R_isnancpp */
 
+/* R's NA_REAL: the NaN whose low word is 1954 (R's arithmetic.c).  Written where the reference writes NA_REAL; a plain
+ * 0/0 NaN stays where the reference divides by zero.  x86 arithmetic keeps the payload of a NaN operand, so the values
+ * the reference derives from an NA_REAL are NA here as they are there. */
+static double na_real(void) {
+  const uint64_t bits = 0x7FF00000000007A2ull;
+  double d;
+  memcpy(&d, &bits, sizeof d);
+  return d;
+}
+
 /* ------------------------------------------------------------------------- */
 /* bigparallelr::split_len (third-party, recalled; used by CutBySize,
  * R/local_reimplementations.R:13-15).  Fills lower/upper (1-based, inclusive)
@@ -163,7 +173,7 @@ void orc_alt_freq_dip_pseudo(const uint8_t* fbm, int64_t nrow, const int32_t* ro
   if (!as_counts)                                                               /* :48-54 */
     for (int j = 0; j < m; j++) {
       if (out[(size_t)m + j] > 0) out[j] = out[j] / out[(size_t)m + j];
-      else out[j] = NAN; /* NA_REAL */
+      else out[j] = na_real();
     }
   free(mult);
 }
@@ -259,7 +269,7 @@ void orc_gt_pi_diploid(const uint8_t* fbm, int64_t nrow, const int32_t* rowInd, 
       double x = code256[FBM(i, j)];
       if (x > -1) { cnt += x; valid += 2; }
     }
-    pi[j] = (valid > 0) ? (cnt * (valid - cnt) / (valid * (valid - 1) / 2)) : NAN;
+    pi[j] = (valid > 0) ? (cnt * (valid - cnt) / (valid * (valid - 1) / 2)) : na_real();
   }
 }
 
@@ -371,7 +381,7 @@ void orc_pairwise_fst_nei87_loop(const int32_t* pairs1, int P, int m, const doub
       for (int j = 0; j < 2; j++)
         if (!is_na(n_pair[j])) { valid++; ho_sum += sHo[j]; nsum += 1.0; inv_nsum += 1.0 / n_pair[j]; }
       double np = valid;
-      double mn = (inv_nsum > 0) ? nsum / inv_nsum : NAN;
+      double mn = (inv_nsum > 0) ? nsum / inv_nsum : na_real();
       double mHo = ho_sum / valid;
       double sp2a = pow(fA[0], 2) + pow(fA[1], 2);
       double sp2r = pow(fR[0], 2) + pow(fR[1], 2);

@@ -7,9 +7,16 @@
  *
  * STATUS: written against R's documented C API.  R is not installed in the build image, so what is checked there is:
  * (1) the file compiles with -Wall -Wextra -Werror against tests/rmock/ (declarations of the ~35 R API functions it
- * uses, written from R's documentation -- a syntax and signature guard, NOT R), and (2) linked against the small mock
- * runtime of tests/rmock/rmock.c it is driven on the GPU by tests/test_gpu_rshim.py exactly as the R drivers drive it
- * (block loop of R/snp_ibs.R:69-82 on FBM objects whose fields are read through Rf_eval).  See INTEGRATION.md.
+ * uses, written from R's documentation -- a syntax and signature guard, NOT R), and (2) linked against the mock runtime
+ * of tests/rmock/rmock.c (protect stack counted on every call; GC torture, failing allocation and strict arguments as
+ * opt-in modes) every registered symbol runs on the GPU: the increment_* through the block loops of the R drivers
+ * (tests/test_gpu_rshim.py), the per-locus, Fst-loop and fbm256 symbols against the oracle under GC torture and strict
+ * arguments (tests/test_gpu_rshim_entries.py); the 14 reference symbols also run under ASan/UBSan with every allocation
+ * failing in turn (tests/test_host_sanitizers.py).  See INTEGRATION.md.
+ *
+ * R's rules the shim keeps: every R allocation of an entry point comes before its device view exists (an allocation
+ * that fails is a longjmp past tpg_view_free); index vectors are coerced to integer as Rcpp's IntegerVector does; NA_REAL
+ * is written where the reference writes it (alt_freq's freq, gt_pi_diploid), a plain NaN where it divides 0 by 0.
  *
  * Where it goes: tidypopgen/src/tpg_rshim.c, replacing the `[[Rcpp::export]]` bodies of the functions listed in
  * tpg_rshim_entries[] (INTEGRATION.md section 2 says how the registration tables are merged), or the package
@@ -22,6 +29,8 @@
  */
 #define _POSIX_C_SOURCE 200809L /* strdup, mmap */
 #include <fcntl.h>
+#include <limits.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,6 +43,25 @@
 #include <R_ext/Rdynload.h>
 
 #include "tpg.h"
+
+/* R's missing values come from R_ext/Arith.h, which R.h includes.  A build against stand-in R headers that declare only
+ * the API functions (a syntax and signature guard) gets the same values here: NA_real_ is the NaN whose low word is
+ * 1954, NA_integer_ is INT_MIN. */
+#ifndef NA_INTEGER
+#define NA_INTEGER INT_MIN
+#endif
+#ifndef ISNAN
+#define ISNAN(x) (isnan(x))
+#endif
+#ifndef NA_REAL
+static double tpg_na_real(void) {
+  const uint64_t bits = 0x7FF00000000007A2ull;
+  double d;
+  memcpy(&d, &bits, sizeof d);
+  return d;
+}
+#define NA_REAL tpg_na_real()
+#endif
 
 /* ---- session state -------------------------------------------------------------------------------------------- */
 
@@ -256,31 +284,51 @@ static void after_increment(void) {
   if (!deferred()) release_accumulators(0);
 }
 
+/* An index vector as Rcpp's `const IntegerVector&` takes it: a double vector (vctrs::vec_data(.x) rows, ind.row = c(1, 3),
+ * .group_ids(x) - 1) is coerced, as R's as.integer() does it -- the caller PROTECTs the result. */
+static SEXP as_int(SEXP x) { return TYPEOF(x) == INTSXP ? x : Rf_coerceVector(x, INTSXP); }
+static SEXP as_real(SEXP x) { return TYPEOF(x) == REALSXP ? x : Rf_coerceVector(x, REALSXP); }
+
+/* every entry of a 1-based index vector (INTSXP) in [1, hi]: NA (or a NaN coerced to it) is an R error too */
+static const int* checked_index(SEXP ind, int64_t hi, const char* what) {
+  const int* p = INTEGER(ind);
+  for (R_xlen_t k = 0; k < XLENGTH(ind); k++)
+    if (p[k] == NA_INTEGER || p[k] < 1 || p[k] > hi)
+      Rf_error("tidypopgen (GPU): %s[%lld] = %s out of [1,%lld]", what, (long long)k, p[k] == NA_INTEGER ? "NA" : "a value",
+               (long long)hi);
+  return p;
+}
+
 /* the packed (rowInd, colInd, code256) view a per-locus entry point works on.  Default: the columns colInd covers are
  * uploaded for this call alone (the contiguous blocks of the R drivers: their covering range; a scattered colInd: gathered
- * on the host first) and released with it; TPG_RSHIM_CACHE=1: packed from the cached HBM copy of the whole FBM. */
+ * on the host first) and released with it; TPG_RSHIM_CACHE=1: packed from the cached HBM copy of the whole FBM.
+ * rowInd / colInd are INTSXP (as_int).  Every R allocation of the entry point comes BEFORE this: an allocation that fails
+ * is a longjmp that would jump past tpg_view_free. */
 static tpg_view* view_of(SEXP BM, SEXP rowInd, SEXP colInd, int raw_bytes) {
-  if (TYPEOF(rowInd) != INTSXP || TYPEOF(colInd) != INTSXP) Rf_error("rowInd / colInd must be integer vectors");
   const int64_t n = (int64_t)XLENGTH(rowInd), m = (int64_t)XLENGTH(colInd);
   const double* code = raw_bytes ? NULL : code256_of(BM);
+  if (m < 1) Rf_error("tidypopgen (GPU): empty colInd");
+  int* cols = (int*)R_alloc((size_t)m, sizeof(int)); /* R's transient storage: freed when .Call returns or errors */
   tpg_view* v = NULL;
   if (cache_on()) {
-    TPG_R(tpg_view_create(ctx(), genotype_fbm_dev(BM), INTEGER(rowInd), n, INTEGER(colInd), m, code, &v));
+    tpg_fbm* d = genotype_fbm_dev(BM);
+    mapped_file* f = genotype_fbm(BM);
+    checked_index(rowInd, f->nrow, "rowInd");
+    checked_index(colInd, f->ncol, "colInd");
+    TPG_R(tpg_view_create(ctx(), d, INTEGER(rowInd), n, INTEGER(colInd), m, code, &v));
     return v;
   }
   mapped_file* f = genotype_fbm(BM);
   const uint8_t* bytes = (const uint8_t*)f->map;
-  const int64_t nrow = f->nrow, ncol = f->ncol;
-  if (m < 1) Rf_error("tidypopgen (GPU): empty colInd");
-  const int* ci = INTEGER(colInd);
+  const int64_t nrow = f->nrow;
+  checked_index(rowInd, nrow, "rowInd");
+  const int* ci = checked_index(colInd, f->ncol, "colInd");
   int lo = ci[0], hi = ci[0];
   for (int64_t j = 0; j < m; j++) {
-    if (ci[j] < 1 || ci[j] > ncol) Rf_error("tidypopgen (GPU): colInd[%lld] = %d out of [1,%lld]", (long long)j, ci[j], (long long)ncol);
     if (ci[j] < lo) lo = ci[j];
     if (ci[j] > hi) hi = ci[j];
   }
   const int64_t span = (int64_t)hi - lo + 1;
-  int* cols = (int*)R_alloc((size_t)m, sizeof(int)); /* R's transient storage: freed when .Call returns or errors */
   /* tpg_view_create_from_host: upload for this ONE code table (2 bits per genotype over PCIe where table and bytes allow it),
      pack, release the uploaded columns -- nothing of the FBM outlives the call */
   if (span <= 2 * m + 64) {
@@ -323,6 +371,13 @@ static void set_colnames2(SEXP mat, const char* a, const char* b) {
   UNPROTECT(2);
 }
 
+/* ngroups as Rcpp's `int` takes it (an integer or a double); NA or < 1 is an R error, not a matrix of -2^31 columns */
+static int ngroups_of(SEXP ngroups) {
+  const int G = Rf_asInteger(ngroups);
+  if (G == NA_INTEGER || G < 1) Rf_error("tidypopgen (GPU): ngroups must be a positive integer");
+  return G;
+}
+
 /* views are released even when the library call fails (Rf_error does not return) */
 #define TPG_R_VIEW(v, call)          \
   do {                               \
@@ -337,12 +392,18 @@ static void set_colnames2(SEXP mat, const char* a, const char* b) {
 SEXP _tidypopgen_alt_freq_dip_pseudo_cpp(SEXP BM, SEXP rowInd, SEXP colInd, SEXP ploidy, SEXP ncores, SEXP as_counts) {
   (void)ncores;
   const int counts = Rf_asLogical(as_counts);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   SEXP pl = PROTECT(Rf_coerceVector(ploidy, REALSXP));
-  tpg_view* v = view_of(BM, rowInd, colInd, 0);
-  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(colInd), 2));
-  TPG_R_VIEW(v, tpg_alt_freq_dip_pseudo(ctx(), v, REAL(pl), counts, REAL(out)));
+  const int m = (int)XLENGTH(ci);
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 2));
   set_colnames2(out, counts ? "n_alt" : "freq", "n_valid"); /* :44, :56 */
-  UNPROTECT(2);
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_alt_freq_dip_pseudo(ctx(), v, REAL(pl), counts, REAL(out)));
+  double* f = REAL(out);
+  if (!counts)
+    for (int j = 0; j < m; j++)
+      if (!(f[m + j] > 0)) f[j] = NA_REAL; /* :49-53: NA_real_, not the device's NaN */
+  UNPROTECT(4);
   return out;
 }
 
@@ -351,25 +412,28 @@ SEXP _tidypopgen_alt_freq_dip_pseudo_cpp(SEXP BM, SEXP rowInd, SEXP colInd, SEXP
 SEXP _tidypopgen_grouped_alt_freq_dip_pseudo_cpp(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups,
                                                  SEXP ploidy, SEXP ncores, SEXP as_counts) {
   (void)ncores;
-  const int G = Rf_asInteger(ngroups);
+  const int G = ngroups_of(ngroups);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   SEXP pl = PROTECT(Rf_coerceVector(ploidy, REALSXP));
   SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
-  tpg_view* v = view_of(BM, rowInd, colInd, 0);
-  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(colInd), 2 * G));
-  TPG_R_VIEW(v, tpg_grouped_alt_freq_dip_pseudo(ctx(), v, INTEGER(gid), G, REAL(pl), Rf_asLogical(as_counts), REAL(out)));
-  UNPROTECT(3);
+  const int counts = Rf_asLogical(as_counts);
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(ci), 2 * G));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_grouped_alt_freq_dip_pseudo(ctx(), v, INTEGER(gid), G, REAL(pl), counts, REAL(out)));
+  UNPROTECT(5);
   return out;
 }
 
 /* grouped_missingness_cpp(BM, rowInd, colInd, groupIds, ngroups, ncores)   src/grouped_missingness_cpp.cpp:8-33 */
 SEXP _tidypopgen_grouped_missingness_cpp(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP ncores) {
   (void)ncores;
-  const int G = Rf_asInteger(ngroups);
+  const int G = ngroups_of(ngroups);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
-  tpg_view* v = view_of(BM, rowInd, colInd, 0);
-  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(colInd), G));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(ci), G));
+  tpg_view* v = view_of(BM, ri, ci, 0);
   TPG_R_VIEW(v, tpg_grouped_missingness(ctx(), v, INTEGER(gid), G, REAL(out)));
-  UNPROTECT(2);
+  UNPROTECT(4);
   return out;
 }
 
@@ -378,87 +442,112 @@ SEXP _tidypopgen_grouped_missingness_cpp(SEXP BM, SEXP rowInd, SEXP colInd, SEXP
 SEXP _tidypopgen_grouped_summaries_dip_pseudo_cpp(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups,
                                                   SEXP ploidy, SEXP ncores) {
   (void)ncores;
-  const int G = Rf_asInteger(ngroups);
+  const int G = ngroups_of(ngroups);
   const int m = (int)XLENGTH(colInd);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   SEXP pl = PROTECT(Rf_coerceVector(ploidy, REALSXP));
   SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
-  tpg_view* v = view_of(BM, rowInd, colInd, 0);
   SEXP mats[4];
   for (int k = 0; k < 4; k++) mats[k] = PROTECT(Rf_allocMatrix(REALSXP, m, G));
+  static const char* names[4] = {"freq_alt", "freq_ref", "n", "het_obs"}; /* :59-62 */
+  SEXP out = PROTECT(named_list(4, names, mats));
+  tpg_view* v = view_of(BM, ri, ci, 0);
   TPG_R_VIEW(v, tpg_grouped_summaries_dip_pseudo(ctx(), v, INTEGER(gid), G, REAL(pl), REAL(mats[0]), REAL(mats[1]),
                                                  REAL(mats[2]), REAL(mats[3])));
-  static const char* names[4] = {"freq_alt", "freq_ref", "n", "het_obs"}; /* :59-62 */
-  SEXP out = named_list(4, names, mats);
-  UNPROTECT(6);
+  UNPROTECT(9);
   return out;
 }
 
 /* gt_ind_hetero(BM, rowInd, colInd, ncores)   src/gt_ind_hetero.cpp:11-42 -> integer 2 x n {n_het; n_na} */
 SEXP _tidypopgen_gt_ind_hetero(SEXP BM, SEXP rowInd, SEXP colInd, SEXP ncores) {
   (void)ncores;
-  tpg_view* v = view_of(BM, rowInd, colInd, 0);
-  SEXP out = PROTECT(Rf_allocMatrix(INTSXP, 2, (int)XLENGTH(rowInd)));
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP out = PROTECT(Rf_allocMatrix(INTSXP, 2, (int)XLENGTH(ri)));
+  tpg_view* v = view_of(BM, ri, ci, 0);
   TPG_R_VIEW(v, tpg_gt_ind_hetero(ctx(), v, INTEGER(out)));
-  UNPROTECT(1);
+  UNPROTECT(3);
   return out;
 }
 
 /* gt_pi_diploid(BM, rowInd, colInd, ncores)   src/gt_pi_diploid.cpp:7-38 */
 SEXP _tidypopgen_gt_pi_diploid(SEXP BM, SEXP rowInd, SEXP colInd, SEXP ncores) {
   (void)ncores;
-  tpg_view* v = view_of(BM, rowInd, colInd, 0);
-  SEXP out = PROTECT(Rf_allocVector(REALSXP, XLENGTH(colInd)));
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, XLENGTH(ci)));
+  tpg_view* v = view_of(BM, ri, ci, 0);
   TPG_R_VIEW(v, tpg_gt_pi_diploid(ctx(), v, REAL(out)));
-  UNPROTECT(1);
+  /* :35-36: a locus without a valid genotype is NA_real_ (the only NaN pi can be: valid > 0 means valid >= 2) */
+  double* pi = REAL(out);
+  for (R_xlen_t j = 0; j < XLENGTH(out); j++)
+    if (ISNAN(pi[j])) pi[j] = NA_REAL;
+  UNPROTECT(3);
   return out;
 }
 
 /* gt_grouped_pi_diploid(BM, rowInd, colInd, groupIds, ngroups, ncores)   src/gt_grouped_pi_diploid.cpp:7-42 */
 SEXP _tidypopgen_gt_grouped_pi_diploid(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP ncores) {
   (void)ncores;
-  const int G = Rf_asInteger(ngroups);
+  const int G = ngroups_of(ngroups);
   const int m = (int)XLENGTH(colInd);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
-  tpg_view* v = view_of(BM, rowInd, colInd, 0);
   SEXP mats[2];
   for (int k = 0; k < 2; k++) mats[k] = PROTECT(Rf_allocMatrix(REALSXP, m, G));
-  TPG_R_VIEW(v, tpg_gt_grouped_pi_diploid(ctx(), v, INTEGER(gid), G, REAL(mats[0]), REAL(mats[1])));
   static const char* names[2] = {"pi", "n"};
-  SEXP out = named_list(2, names, mats);
-  UNPROTECT(3);
+  SEXP out = PROTECT(named_list(2, names, mats));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_gt_grouped_pi_diploid(ctx(), v, INTEGER(gid), G, REAL(mats[0]), REAL(mats[1])));
+  UNPROTECT(6);
   return out;
 }
 
 /* ---- pairwise population Fst loops --------------------------------------------------------------------------- */
 
-/* common body of the three loop functions.  pairwise_combn arrives as a 2 x P double matrix (NumericMatrix). */
+/* common body of the three loop functions.  pairwise_combn arrives as a 2 x P matrix (NumericMatrix: utils::combn gives an
+   integer one, which Rcpp coerces); so do the m x G matrices, and an integer matrix is coerced as Rcpp coerces it. */
+static SEXP fst_matrix(SEXP x, int m, int G, const char* what) {
+  SEXP dim = Rf_getAttrib(x, R_DimSymbol);
+  if ((TYPEOF(x) != REALSXP && TYPEOF(x) != INTSXP && TYPEOF(x) != LGLSXP) || Rf_length(dim) != 2)
+    Rf_error("%s must be a numeric matrix", what);
+  if (m >= 0 && (INTEGER(dim)[0] != m || INTEGER(dim)[1] != G)) Rf_error("%s is not %d x %d", what, m, G);
+  return as_real(x);
+}
+
 static SEXP fst_loop(int method, SEXP pairwise_combn, SEXP n, SEXP freq_alt, SEXP freq_ref, SEXP het_obs, SEXP by_locus,
                      SEXP return_num_dem) {
-  SEXP dim = Rf_getAttrib(n, R_DimSymbol);
-  if (TYPEOF(n) != REALSXP || Rf_length(dim) != 2) Rf_error("n must be a numeric matrix");
+  SEXP nr = PROTECT(fst_matrix(n, -1, 0, "n"));
+  SEXP dim = Rf_getAttrib(nr, R_DimSymbol);
   const int m = INTEGER(dim)[0], G = INTEGER(dim)[1];
+  SEXP fa = PROTECT(fst_matrix(freq_alt, m, G, "freq_alt"));
+  SEXP fr = PROTECT(freq_ref == R_NilValue ? R_NilValue : fst_matrix(freq_ref, m, G, "freq_ref"));
+  SEXP ho = PROTECT(het_obs == R_NilValue ? R_NilValue : fst_matrix(het_obs, m, G, "het_obs"));
+  SEXP pdim = Rf_getAttrib(pairwise_combn, R_DimSymbol);
+  if (Rf_length(pdim) != 2 || INTEGER(pdim)[0] != 2) Rf_error("pairwise_combn must be a 2-row matrix");
   SEXP pc = PROTECT(Rf_coerceVector(pairwise_combn, INTSXP));
+  checked_index(pc, G, "pairwise_combn");
   const int P = (int)(XLENGTH(pc) / 2);
-  int byl = Rf_asLogical(by_locus);
-  const int rnd = Rf_asLogical(return_num_dem);
-  const int want_a = byl || rnd;
+  const int byl = Rf_asLogical(by_locus) != 0, rnd = Rf_asLogical(return_num_dem) != 0;
   SEXP tot = PROTECT(Rf_allocVector(REALSXP, P));
-  SEXP a = PROTECT(Rf_allocMatrix(REALSXP, want_a ? m : 0, want_a ? P : 0)); /* empty 0 x 0 when not asked, :17-21 */
+  /* :17-21: fst_locus is m x P only under by_locus, fst_locus_dem only under return_num_dem, 0 x 0 otherwise; both are
+     filled under by_locus alone (:35-42), so return_num_dem without by_locus gives a 0 x 0 numerator and a zero
+     denominator, as Rcpp's zero-initialised NumericMatrix leaves it */
+  SEXP a = PROTECT(Rf_allocMatrix(REALSXP, byl ? m : 0, byl ? P : 0));
   SEXP b = PROTECT(Rf_allocMatrix(REALSXP, rnd ? m : 0, rnd ? P : 0));
-  TPG_R(tpg_pairwise_fst_loop(ctx(), method, INTEGER(pc), P, m, G, REAL(n), REAL(freq_alt),
-                              freq_ref == R_NilValue ? NULL : REAL(freq_ref), het_obs == R_NilValue ? NULL : REAL(het_obs),
-                              byl, rnd, REAL(tot), want_a ? REAL(a) : NULL, rnd ? REAL(b) : NULL));
+  if (rnd) memset(REAL(b), 0, sizeof(double) * (size_t)m * (size_t)P);
   SEXP out;
   if (!rnd) { /* :54-60 */
     static const char* names[2] = {"fst_locus", "fst_tot"};
     SEXP vals[2] = {a, tot};
-    out = named_list(2, names, vals);
+    out = PROTECT(named_list(2, names, vals));
   } else {
     static const char* names[2] = {"Fst_by_locus_num", "Fst_by_locus_den"};
     SEXP vals[2] = {a, b};
-    out = named_list(2, names, vals);
+    out = PROTECT(named_list(2, names, vals));
   }
-  UNPROTECT(4);
+  TPG_R(tpg_pairwise_fst_loop(ctx(), method, INTEGER(pc), P, m, G, REAL(nr), REAL(fa), fr == R_NilValue ? NULL : REAL(fr),
+                              ho == R_NilValue ? NULL : REAL(ho), byl, byl && rnd, REAL(tot), byl ? REAL(a) : NULL,
+                              byl && rnd ? REAL(b) : NULL));
+  UNPROTECT(9);
   return out;
 }
 
@@ -494,11 +583,14 @@ SEXP _tidypopgen_pairwise_fst_nei87_loop(SEXP pairwise_combn, SEXP n, SEXP het_o
 SEXP _tidypopgen_increment_ibs_counts(SEXP k, SEXP k2, SEXP g0, SEXP g1, SEXP g2, SEXP BM, SEXP rowInd, SEXP colInd) {
   (void)g0; (void)g1; (void)g2;
   g_call++;
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   mapped_file* f = genotype_fbm(BM);
-  const int64_t n = (int64_t)XLENGTH(rowInd);
-  TPG_R(tpg_increment_ibs_counts(ctx(), double_fbm(k, n), double_fbm(k2, n), (const uint8_t*)f->map, f->nrow, f->ncol,
-                                 INTEGER(rowInd), n, INTEGER(colInd), (int64_t)XLENGTH(colInd)));
+  const int64_t n = (int64_t)XLENGTH(ri);
+  const int *r1 = checked_index(ri, f->nrow, "rowInd"), *c1 = checked_index(ci, f->ncol, "colInd");
+  TPG_R(tpg_increment_ibs_counts(ctx(), double_fbm(k, n), double_fbm(k2, n), (const uint8_t*)f->map, f->nrow, f->ncol, r1,
+                                 n, c1, (int64_t)XLENGTH(ci)));
   after_increment();
+  UNPROTECT(2);
   return R_NilValue;
 }
 
@@ -508,11 +600,14 @@ SEXP _tidypopgen_increment_king_numerator(SEXP k, SEXP n_Aa_i, SEXP g0, SEXP g1,
                                           SEXP colInd) {
   (void)g0; (void)g1; (void)g2; (void)gv;
   g_call++;
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   mapped_file* f = genotype_fbm(BM);
-  const int64_t n = (int64_t)XLENGTH(rowInd);
+  const int64_t n = (int64_t)XLENGTH(ri);
+  const int *r1 = checked_index(ri, f->nrow, "rowInd"), *c1 = checked_index(ci, f->ncol, "colInd");
   TPG_R(tpg_increment_king_numerator(ctx(), double_fbm(k, n), double_fbm(n_Aa_i, n), (const uint8_t*)f->map, f->nrow,
-                                     f->ncol, INTEGER(rowInd), n, INTEGER(colInd), (int64_t)XLENGTH(colInd)));
+                                     f->ncol, r1, n, c1, (int64_t)XLENGTH(ci)));
   after_increment();
+  UNPROTECT(2);
   return R_NilValue;
 }
 
@@ -523,17 +618,19 @@ SEXP _tidypopgen_increment_king_numerator(SEXP k, SEXP n_Aa_i, SEXP g0, SEXP g1,
 SEXP _tidypopgen_increment_as_counts(SEXP k, SEXP k2, SEXP na_mat, SEXP dos_mat, SEXP BM, SEXP rowInd, SEXP colInd) {
   (void)na_mat;
   g_call++;
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   mapped_file* f = genotype_fbm(BM);
-  const int64_t n = (int64_t)XLENGTH(rowInd), m = (int64_t)XLENGTH(colInd);
+  const int64_t n = (int64_t)XLENGTH(ri), m = (int64_t)XLENGTH(ci);
+  const int *r1 = checked_index(ri, f->nrow, "rowInd"), *c1 = checked_index(ci, f->ncol, "colInd");
   double* K = double_fbm(k, n);
-  TPG_R(tpg_increment_as_counts(ctx(), K, double_fbm(k2, n), (const uint8_t*)f->map, f->nrow, f->ncol, INTEGER(rowInd),
-                                n, INTEGER(colInd), m));
+  TPG_R(tpg_increment_as_counts(ctx(), K, double_fbm(k2, n), (const uint8_t*)f->map, f->nrow, f->ncol, r1, n, c1, m));
   const char* q = getenv("TPG_EMULATE_AS_PAD_QUIRK");
   if (q && q[0] == '1') {
     SEXP dim = Rf_getAttrib(dos_mat, R_DimSymbol);
     if (Rf_length(dim) == 2 && (int64_t)INTEGER(dim)[1] == m + 1) TPG_R(tpg_increment_as_note_narrow_block(ctx(), K, n));
   }
   after_increment();
+  UNPROTECT(2);
   return R_NilValue;
 }
 
@@ -577,19 +674,23 @@ SEXP _tidypopgen_tpg_invalidate(SEXP BM) {
    -> list(XV n x K, rowSumsSq n), unnamed as in the reference (:46) */
 SEXP _tidypopgen_fbm256_prod_and_rowSumsSq(SEXP BM, SEXP ind_row, SEXP ind_col, SEXP center, SEXP scale, SEXP V) {
   SEXP dim = Rf_getAttrib(V, R_DimSymbol);
-  if (TYPEOF(V) != REALSXP || Rf_length(dim) != 2) Rf_error("V must be a numeric matrix");
+  if ((TYPEOF(V) != REALSXP && TYPEOF(V) != INTSXP) || Rf_length(dim) != 2) Rf_error("V must be a numeric matrix");
   const int K = INTEGER(dim)[1];
   if ((R_xlen_t)INTEGER(dim)[0] != XLENGTH(ind_col)) Rf_error("Incompatibility between dimensions."); /* myassert_size, :23 */
+  const R_xlen_t m = XLENGTH(ind_col);
+  if (XLENGTH(center) != m || XLENGTH(scale) != m) Rf_error("Incompatibility between dimensions.");
+  SEXP ri = PROTECT(as_int(ind_row)), ci = PROTECT(as_int(ind_col));
+  SEXP Vr = PROTECT(as_real(V));
   SEXP ce = PROTECT(Rf_coerceVector(center, REALSXP));
   SEXP sc = PROTECT(Rf_coerceVector(scale, REALSXP));
-  tpg_view* v = view_of(BM, ind_row, ind_col, 0);
-  SEXP XV = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(ind_row), K));
-  SEXP rss = PROTECT(Rf_allocVector(REALSXP, XLENGTH(ind_row)));
-  TPG_R_VIEW(v, tpg_fbm256_prod_and_rowSumsSq(ctx(), v, REAL(ce), REAL(sc), REAL(V), K, REAL(XV), REAL(rss)));
+  SEXP XV = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(ri), K));
+  SEXP rss = PROTECT(Rf_allocVector(REALSXP, XLENGTH(ri)));
   SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
   SET_VECTOR_ELT(out, 0, XV);
   SET_VECTOR_ELT(out, 1, rss);
-  UNPROTECT(5);
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_fbm256_prod_and_rowSumsSq(ctx(), v, REAL(ce), REAL(sc), REAL(Vr), K, REAL(XV), REAL(rss)));
+  UNPROTECT(8);
   return out;
 }
 
@@ -615,15 +716,13 @@ static tpg_multi* multi(void) {
   return g_multi;
 }
 
-static void check_ind(SEXP rowInd, SEXP colInd) {
-  if (TYPEOF(rowInd) != INTSXP || TYPEOF(colInd) != INTSXP) Rf_error("rowInd / colInd must be integer vectors");
-}
 
 /* tpg_snp_pairwise(BM, rowInd, colInd, adjusted_counts, which) -> list(ibs, king, allele_sharing, grm), each n x n or NULL.
  * which: integer mask of the matrices wanted (1 ibs, 2 king, 4 allele_sharing, 8 grm; NULL = all four).  Only the
  * cross-products those need are accumulated (tpg_multi_pairwise): 2 of 5 for the GRM alone, 4 for KING + GRM. */
 SEXP _tidypopgen_tpg_snp_pairwise(SEXP BM, SEXP rowInd, SEXP colInd, SEXP adjusted_counts, SEXP which) {
-  check_ind(rowInd, colInd);
+  rowInd = PROTECT(as_int(rowInd));
+  colInd = PROTECT(as_int(colInd));
   mapped_file* f = genotype_fbm(BM);
   const uint8_t* bytes = (const uint8_t*)f->map;
   const int64_t nrow = f->nrow, ncol = f->ncol;
@@ -638,14 +737,15 @@ SEXP _tidypopgen_tpg_snp_pairwise(SEXP BM, SEXP rowInd, SEXP colInd, SEXP adjust
                            mats[2] != R_NilValue ? REAL(mats[2]) : NULL, mats[3] != R_NilValue ? REAL(mats[3]) : NULL));
   static const char* names[4] = {"ibs", "king", "allele_sharing", "grm"};
   SEXP out = named_list(4, names, mats);
-  UNPROTECT(4);
+  UNPROTECT(6);
   return out;
 }
 
 /* tpg_grouped_alt_freq(BM, rowInd, colInd, groupIds, ngroups, ploidy, as_counts) -> m x 2G (groupIds NULL: m x 2) */
 SEXP _tidypopgen_tpg_grouped_alt_freq(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP ploidy,
                                       SEXP as_counts) {
-  check_ind(rowInd, colInd);
+  rowInd = PROTECT(as_int(rowInd));
+  colInd = PROTECT(as_int(colInd));
   mapped_file* f = genotype_fbm(BM);
   const int grouped = groupIds != R_NilValue;
   const int G = grouped ? Rf_asInteger(ngroups) : 0;
@@ -655,7 +755,7 @@ SEXP _tidypopgen_tpg_grouped_alt_freq(SEXP BM, SEXP rowInd, SEXP colInd, SEXP gr
   TPG_R(tpg_multi_grouped_alt_freq(multi(), (const uint8_t*)f->map, f->nrow, f->ncol, INTEGER(rowInd), (int64_t)XLENGTH(rowInd),
                                    INTEGER(colInd), (int64_t)XLENGTH(colInd), code256_of(BM), grouped ? INTEGER(gid) : NULL, G,
                                    REAL(pl), Rf_asLogical(as_counts), REAL(out)));
-  UNPROTECT(3);
+  UNPROTECT(5);
   return out;
 }
 
@@ -663,7 +763,8 @@ SEXP _tidypopgen_tpg_grouped_alt_freq(SEXP BM, SEXP rowInd, SEXP colInd, SEXP gr
  * method: 0 Hudson, 1 Nei87, 2 WC84.  Same list as the three loop functions return. */
 SEXP _tidypopgen_tpg_pairwise_pop_fst(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP ploidy, SEXP method,
                                       SEXP pairwise_combn, SEXP by_locus, SEXP return_num_dem) {
-  check_ind(rowInd, colInd);
+  rowInd = PROTECT(as_int(rowInd));
+  colInd = PROTECT(as_int(colInd));
   mapped_file* f = genotype_fbm(BM);
   const int G = Rf_asInteger(ngroups), m = (int)XLENGTH(colInd);
   SEXP pl = PROTECT(Rf_coerceVector(ploidy, REALSXP));
@@ -686,14 +787,15 @@ SEXP _tidypopgen_tpg_pairwise_pop_fst(SEXP BM, SEXP rowInd, SEXP colInd, SEXP gr
     SEXP vals[2] = {a, b};
     out = named_list(2, names, vals);
   }
-  UNPROTECT(6);
+  UNPROTECT(8);
   return out;
 }
 
 /* tpg_pca_partial_svd(BM, rowInd, colInd, k) -> list(d, u, v, center, scale, square_frobenius): what big_SVD returns to
  * gt_pca_partialSVD (R/gt_pca_partialSVD.R:82-105) plus the squared Frobenius norm of R/square_frobenius.R */
 SEXP _tidypopgen_tpg_pca_partial_svd(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k) {
-  check_ind(rowInd, colInd);
+  rowInd = PROTECT(as_int(rowInd));
+  colInd = PROTECT(as_int(colInd));
   mapped_file* f = genotype_fbm(BM);
   const int n = (int)XLENGTH(rowInd), m = (int)XLENGTH(colInd), K = Rf_asInteger(k);
   SEXP vals[6];
@@ -708,7 +810,7 @@ SEXP _tidypopgen_tpg_pca_partial_svd(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k) 
                                   REAL(vals[5])));
   static const char* names[6] = {"d", "u", "v", "center", "scale", "square_frobenius"};
   SEXP out = named_list(6, names, vals);
-  UNPROTECT(6);
+  UNPROTECT(8);
   return out;
 }
 

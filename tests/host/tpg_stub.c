@@ -2,8 +2,9 @@
  * calls, so that the shim's own logic (the table of mapped files, the opt-in HBM cache and its invalidation, the per-call
  * column uploads with their index rebasing, accumulator mappings kept across a block loop, the `which` mask) can run
  * under -fsanitize=address,undefined without a GPU (tests/test_host_sanitizers.py).  Views are plain n x m code
- * matrices; alt_freq is computed for real (diploids), so the test can compare what comes back through the shim with
- * numpy; the increment_* stand-ins add block sizes to K / K2 and touch every element of both. */
+ * matrices; the per-locus entry points and the Fst loops are the CPU oracle's on those codes, so the test can compare
+ * what comes back through the shim with numpy; the increment_* stand-ins add block sizes to K / K2 and touch every
+ * element of both. */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -98,21 +99,6 @@ void tpg_view_free(tpg_view* v) {
   g_stub_view_alive--;
 }
 
-/* src/alt_freq_dip_pseudo_cpp.cpp:21-57 for diploids */
-int tpg_alt_freq_dip_pseudo(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int as_counts, double* out) {
-  (void)ctx; (void)ploidy;
-  for (int64_t j = 0; j < v->m; j++) {
-    double alt = 0, valid = 0;
-    for (int64_t i = 0; i < v->n; i++) {
-      const uint8_t c = v->codes[(size_t)i + (size_t)j * (size_t)v->n];
-      if (c < 3) { alt += c; valid += 2; }
-    }
-    out[j] = as_counts ? alt : alt / valid;
-    out[j + v->m] = valid;
-  }
-  return TPG_OK;
-}
-
 static int increment(double* K, double* K2, int64_t n, int64_t m) {
   for (int64_t k = 0; k < n * n; k++) { K[k] += 0.0; K2[k] += 0.0; } /* both mappings are n x n doubles, writable */
   K[0] += (double)m;
@@ -153,16 +139,116 @@ int tpg_multi_pairwise(tpg_multi* mg, const uint8_t* fbm_bytes, int64_t nrow, in
   return TPG_OK;
 }
 
+/* The per-locus entry points and the Fst loops: the CPU oracle (oracle/tpg_oracle.c, linked into the same test library) on
+ * the view's codes, so that every reference symbol runs through the shim under the sanitizers with deterministic
+ * numbers.  Group ids and pairs are range-checked first, as the library does: the oracle would index out of bounds. */
+void orc_grouped_alt_freq_dip_pseudo(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*,
+                                     const int32_t*, int, const double*, int, double*);
+void orc_grouped_missingness(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*, const int32_t*,
+                             int, double*);
+void orc_grouped_summaries_dip_pseudo(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*,
+                                      const int32_t*, int, const double*, double*, double*, double*, double*);
+void orc_gt_ind_hetero(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*, int32_t*);
+void orc_gt_pi_diploid(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*, double*);
+void orc_gt_grouped_pi_diploid(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*,
+                               const int32_t*, int, double*, double*);
+void orc_pairwise_fst_hudson_loop(const int32_t*, int, int, const double*, const double*, const double*, int, int, double*,
+                                  double*, double*);
+void orc_pairwise_fst_wc84_loop(const int32_t*, int, int, const double*, const double*, const double*, int, int, double*,
+                                double*, double*);
+void orc_pairwise_fst_nei87_loop(const int32_t*, int, int, const double*, const double*, const double*, const double*, int,
+                                 int, double*, double*, double*);
+void orc_fbm256_prod_and_rowSumsSq(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*,
+                                   const double*, const double*, const double*, int, double*, double*);
+
+typedef struct { int32_t *r, *c; double code[256]; } seq_ind; /* the view's codes read as an n x m FBM with code 3 = NA */
+static int seq_of(const tpg_view* v, seq_ind* s) {
+  s->r = (int32_t*)malloc(sizeof(int32_t) * (size_t)(v->n > 0 ? v->n : 1));
+  s->c = (int32_t*)malloc(sizeof(int32_t) * (size_t)(v->m > 0 ? v->m : 1));
+  for (int64_t i = 0; i < v->n; i++) s->r[i] = (int32_t)(i + 1);
+  for (int64_t j = 0; j < v->m; j++) s->c[j] = (int32_t)(j + 1);
+  for (int k = 0; k < 256; k++) s->code[k] = k < 3 ? (double)k : NAN;
+  return TPG_OK;
+}
+static void seq_free(seq_ind* s) { free(s->r); free(s->c); }
+static int groups_ok(const tpg_view* v, const int32_t* g, int G) {
+  if (G < 1) { snprintf(g_err, sizeof(g_err), "ngroups must be positive"); return 0; }
+  for (int64_t i = 0; i < v->n; i++)
+    if (g[i] < 0 || g[i] >= G) { snprintf(g_err, sizeof(g_err), "groupIds[%lld] = %d out of [0,%d)", (long long)i, g[i], G); return 0; }
+  return 1;
+}
+#define ORC_ARGS v->codes, v->n, s.r, (int)v->n, s.c, (int)v->m, s.code
+
+void orc_alt_freq_dip_pseudo(const uint8_t*, int64_t, const int32_t*, int, const int32_t*, int, const double*, const double*,
+                             int, double*);
+int tpg_alt_freq_dip_pseudo(tpg_ctx* c, const tpg_view* v, const double* ploidy, int as_counts, double* out) {
+  (void)c; seq_ind s;
+  seq_of(v, &s); orc_alt_freq_dip_pseudo(ORC_ARGS, ploidy, as_counts, out); seq_free(&s);
+  for (int64_t j = 0; j < v->m; j++) if (out[j] != out[j]) out[j] = NAN; /* the library's NaN, not the oracle's NA */
+  return TPG_OK;
+}
+int tpg_grouped_alt_freq_dip_pseudo(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, const double* p, int a, double* o) {
+  (void)c; seq_ind s;
+  if (!groups_ok(v, g, G)) return TPG_EINVAL;
+  seq_of(v, &s); orc_grouped_alt_freq_dip_pseudo(ORC_ARGS, g, G, p, a, o); seq_free(&s);
+  return TPG_OK;
+}
+int tpg_grouped_missingness(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, double* o) {
+  (void)c; seq_ind s;
+  if (!groups_ok(v, g, G)) return TPG_EINVAL;
+  seq_of(v, &s); orc_grouped_missingness(ORC_ARGS, g, G, o); seq_free(&s);
+  return TPG_OK;
+}
+int tpg_grouped_summaries_dip_pseudo(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, const double* p, double* a, double* b, double* n, double* h) {
+  (void)c; seq_ind s;
+  if (!groups_ok(v, g, G)) return TPG_EINVAL;
+  seq_of(v, &s); orc_grouped_summaries_dip_pseudo(ORC_ARGS, g, G, p, a, b, n, h); seq_free(&s);
+  return TPG_OK;
+}
+int tpg_gt_ind_hetero(tpg_ctx* c, const tpg_view* v, int32_t* o) {
+  (void)c; seq_ind s;
+  seq_of(v, &s); orc_gt_ind_hetero(ORC_ARGS, o); seq_free(&s);
+  return TPG_OK;
+}
+int tpg_gt_pi_diploid(tpg_ctx* c, const tpg_view* v, double* o) {
+  (void)c; seq_ind s;
+  seq_of(v, &s); orc_gt_pi_diploid(ORC_ARGS, o); seq_free(&s);
+  for (int64_t j = 0; j < v->m; j++) if (o[j] != o[j]) o[j] = NAN; /* the library's NaN, not the oracle's NA */
+  return TPG_OK;
+}
+int tpg_gt_grouped_pi_diploid(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, double* a, double* b) {
+  (void)c; seq_ind s;
+  if (!groups_ok(v, g, G)) return TPG_EINVAL;
+  seq_of(v, &s); orc_gt_grouped_pi_diploid(ORC_ARGS, g, G, a, b); seq_free(&s);
+  return TPG_OK;
+}
+int tpg_pairwise_fst_loop(tpg_ctx* c, int me, const int32_t* p, int P, int64_t m, int G, const double* n, const double* fa, const double* fr, const double* h, int bl, int nd, double* t, double* a, double* b) {
+  (void)c;
+  if (m < 1 || G < 1) { snprintf(g_err, sizeof(g_err), "empty input"); return TPG_EINVAL; }
+  if (me != TPG_FST_HUDSON && !h) { snprintf(g_err, sizeof(g_err), "het_obs is required for WC84 / Nei87"); return TPG_EINVAL; }
+  for (int k = 0; k < 2 * P; k++)
+    if (p[k] < 1 || p[k] > G) { snprintf(g_err, sizeof(g_err), "pairwise_combn[%d] = %d out of [1,%d]", k, p[k], G); return TPG_EINVAL; }
+  if (fr && me != TPG_FST_WC84)
+    for (int64_t k = 0; k < m * G; k++)
+      if (!(1 - fa[k] == fr[k] || (fa[k] != fa[k] && fr[k] != fr[k]))) { snprintf(g_err, sizeof(g_err), "freq_ref is not 1 - freq_alt"); return TPG_EINVAL; }
+  double* oa = bl || nd ? a : NULL;
+  if (me == TPG_FST_HUDSON) orc_pairwise_fst_hudson_loop(p, P, (int)m, n, fa, fr, bl || nd, nd, t, oa, b);
+  else if (me == TPG_FST_WC84) orc_pairwise_fst_wc84_loop(p, P, (int)m, n, fa, h, bl || nd, nd, t, oa, b);
+  else orc_pairwise_fst_nei87_loop(p, P, (int)m, n, h, fa, fr, bl || nd, nd, t, oa, b);
+  for (int64_t k = 0; k < m * (int64_t)P; k++) { /* the library's NaN, not the oracle's NA */
+    if (oa && oa[k] != oa[k]) oa[k] = NAN;
+    if (nd && b[k] != b[k]) b[k] = NAN;
+  }
+  return TPG_OK;
+}
+int tpg_fbm256_prod_and_rowSumsSq(tpg_ctx* c, const tpg_view* v, const double* ce, const double* sc, const double* V, int K, double* XV, double* rss) {
+  (void)c; seq_ind s;
+  seq_of(v, &s); orc_fbm256_prod_and_rowSumsSq(ORC_ARGS, ce, sc, V, K, XV, rss); seq_free(&s);
+  return TPG_OK;
+}
+
 /* not exercised by the sanitizer test: present so that the shim links */
 #define NOT_HERE(name) snprintf(g_err, sizeof(g_err), "tests/host/tpg_stub.c has no " name); return TPG_EUNSUPPORTED
-int tpg_grouped_alt_freq_dip_pseudo(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, const double* p, int a, double* o) { (void)c; (void)v; (void)g; (void)G; (void)p; (void)a; (void)o; NOT_HERE("grouped_alt_freq"); }
-int tpg_grouped_missingness(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, double* o) { (void)c; (void)v; (void)g; (void)G; (void)o; NOT_HERE("grouped_missingness"); }
-int tpg_grouped_summaries_dip_pseudo(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, const double* p, double* a, double* b, double* n, double* h) { (void)c; (void)v; (void)g; (void)G; (void)p; (void)a; (void)b; (void)n; (void)h; NOT_HERE("grouped_summaries"); }
-int tpg_gt_ind_hetero(tpg_ctx* c, const tpg_view* v, int32_t* o) { (void)c; (void)v; (void)o; NOT_HERE("gt_ind_hetero"); }
-int tpg_gt_pi_diploid(tpg_ctx* c, const tpg_view* v, double* o) { (void)c; (void)v; (void)o; NOT_HERE("gt_pi_diploid"); }
-int tpg_gt_grouped_pi_diploid(tpg_ctx* c, const tpg_view* v, const int32_t* g, int G, double* a, double* b) { (void)c; (void)v; (void)g; (void)G; (void)a; (void)b; NOT_HERE("gt_grouped_pi_diploid"); }
-int tpg_pairwise_fst_loop(tpg_ctx* c, int me, const int32_t* p, int P, int64_t m, int G, const double* n, const double* fa, const double* fr, const double* h, int bl, int nd, double* t, double* a, double* b) { (void)c; (void)me; (void)p; (void)P; (void)m; (void)G; (void)n; (void)fa; (void)fr; (void)h; (void)bl; (void)nd; (void)t; (void)a; (void)b; NOT_HERE("pairwise_fst_loop"); }
-int tpg_fbm256_prod_and_rowSumsSq(tpg_ctx* c, const tpg_view* v, const double* ce, const double* sc, const double* V, int K, double* XV, double* rss) { (void)c; (void)v; (void)ce; (void)sc; (void)V; (void)K; (void)XV; (void)rss; NOT_HERE("fbm256_prod_and_rowSumsSq"); }
 int tpg_multi_grouped_alt_freq(tpg_multi* mg, const uint8_t* f, int64_t nr, int64_t nc, const int32_t* r, int64_t n, const int32_t* c, int64_t m, const double* code, const int32_t* g, int G, const double* p, int a, double* o) { (void)mg; (void)f; (void)nr; (void)nc; (void)r; (void)n; (void)c; (void)m; (void)code; (void)g; (void)G; (void)p; (void)a; (void)o; NOT_HERE("multi_grouped_alt_freq"); }
 int tpg_multi_pop_fst(tpg_multi* mg, const uint8_t* f, int64_t nr, int64_t nc, const int32_t* r, int64_t n, const int32_t* c, int64_t m, const double* code, const int32_t* g, int G, const double* p, int me, const int32_t* pr, int P, int bl, int nd, double* t, double* a, double* b) { (void)mg; (void)f; (void)nr; (void)nc; (void)r; (void)n; (void)c; (void)m; (void)code; (void)g; (void)G; (void)p; (void)me; (void)pr; (void)P; (void)bl; (void)nd; (void)t; (void)a; (void)b; NOT_HERE("multi_pop_fst"); }
 int tpg_multi_pca_partial_svd(tpg_multi* mg, const uint8_t* f, int64_t nr, int64_t nc, const int32_t* r, int64_t n, const int32_t* c, int64_t m, const double* code, int k, double* d, double* u, double* v, double* ce, double* sc, double* fro) { (void)mg; (void)f; (void)nr; (void)nc; (void)r; (void)n; (void)c; (void)m; (void)code; (void)k; (void)d; (void)u; (void)v; (void)ce; (void)sc; (void)fro; NOT_HERE("multi_pca_partial_svd"); }

@@ -31,6 +31,16 @@ typedef enum { FALSE = 0, TRUE } Rboolean;
 
 extern SEXP R_NilValue, R_UnboundValue, R_NamesSymbol, R_DimSymbol, R_DimNamesSymbol;
 
+/* R's missing values (R_ext/Arith.h): NA_real_ is the NaN whose low word is 1954; is.na() is ISNAN, R_IsNA tells NA_real_
+   from any other NaN */
+extern double R_NaReal;
+#define NA_REAL R_NaReal
+#define NA_INTEGER (-2147483647 - 1)
+#define NA_LOGICAL NA_INTEGER
+int R_IsNA(double x);
+#define ISNAN(x) (__builtin_isnan(x))
+#define ISNA(x) R_IsNA(x)
+
 int TYPEOF(SEXP x);
 R_xlen_t XLENGTH(SEXP x);
 R_len_t Rf_length(SEXP x);

@@ -9,7 +9,9 @@ a session table of mapped files and caches live:
     with -fsanitize=address,undefined and, for the transport, -fsanitize=thread;
   * oracle/tpg_oracle.c with -fsanitize=address,undefined under its golden-vector tests;
   * shim/tpg_rshim.c + tests/rmock/rmock.c with -fsanitize=address,undefined against a host stand-in for the library
-    (tests/host/tpg_stub.c), driven like the R drivers drive it (tests/host/drive_shim_san.py)."""
+    (tests/host/tpg_stub.c, the CPU oracle behind its per-locus entry points), driven like the R drivers drive it and then
+    through all 14 reference symbols under GC torture, strict arguments and failing allocations
+    (tests/host/drive_shim_san.py)."""
 import os
 import shutil
 import subprocess
@@ -92,7 +94,8 @@ def test_shim_table_cache_and_uploads_under_sanitizers(tmp_path):
     so = str(tmp_path / "libshim_san.so")
     _sh(["gcc", "-std=c11", *SAN, "-Wall", "-Wextra", "-Werror", "-Wno-cast-function-type", "-shared", "-fPIC",
          "-I" + os.path.join(ROOT, "tests", "rmock"), "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "shim", "tpg_rshim.c"),
-         os.path.join(ROOT, "tests", "rmock", "rmock.c"), os.path.join(HOST, "tpg_stub.c"), "-o", so])
+         os.path.join(ROOT, "tests", "rmock", "rmock.c"), os.path.join(HOST, "tpg_stub.c"), os.path.join(ROOT, "oracle", "tpg_oracle.c"),
+         "-Wno-unknown-pragmas", "-o", so, "-lm"])
     env = dict(ENV, LD_PRELOAD=_asan_runtime())
     r = subprocess.run([sys.executable, os.path.join(HOST, "drive_shim_san.py"), so, str(tmp_path)], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=600)
