@@ -112,6 +112,42 @@ int tpg_fbm_upload_bed_snps(tpg_ctx* ctx, tpg_fbm* fbm, const uint8_t* host_snps
 int tpg_fbm_to_host(tpg_ctx* ctx, const tpg_fbm* fbm, uint8_t* bytes);
 void tpg_fbm_free(tpg_fbm* fbm);
 
+/* ---- simple imputation (gt_impute_simple, R/gt_impute_simple.R:54-93 around bigsnpr::snp_fastImputeSimple) -----------
+ * Per locus j, over the n individuals of the object being imputed: c0, c1, c2 = entries that are 0, 1, 2; t = c0 + c1 + c2,
+ * s = c1 + 2 c2; an entry is missing when it is 3 (CODE_012[3] = NA).  Only missing entries change:
+ *   TPG_IMPUTE_MODE    the most frequent of 0, 1, 2, on a tie the smaller genotype (which.max);
+ *   TPG_IMPUTE_MEAN0   round(s / t), half to even as R's round(): 0 if 2 s <= t, 1 if 2 s < 3 t, else 2 (no floating point);
+ *   TPG_IMPUTE_RANDOM  every missing entry on its own Binomial(2, s / (2 t)), a pure function of (seed, i, j), the 0-based
+ *                      position of the entry in the object being imputed (store row / column for a store; kept row / kept
+ *                      column for a view and for the selection of a streamed job) -- so it does not depend on block plan,
+ *                      launch shape or device.  With M = tpg_mix64 of csrc/synth_common.h (the splitmix64 finaliser:
+ *                      x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) *
+ *                      0x94D049BB133111EB; x ^ x >> 31) and 64-bit unsigned arithmetic throughout:
+ *                        key = M(seed ^ M(j));  h = M(key ^ M(i));  u1 = h >> 32;  u2 = h & 0xFFFFFFFF;
+ *                        thr = (s << 31) / t;   v = (u1 < thr) + (u2 < thr).
+ * A locus nobody is typed at (t = 0) stays missing under every method and is counted in the report; the PCA entry points
+ * go on refusing it (TPG_ENUMERIC).
+ * A store receives the fill v as byte 4 + v, which CODE_IMPUTE_PRED reads as v and which the raw-byte consumers
+ * (increment_*_counts, code256 == NULL) go on treating as missing: the raw / imputed switch of R/gt_has_imputed.R:101-106.
+ * A store byte above 3 means "already imputed, or not a CODE_012 store": TPG_EUNSUPPORTED ("object x is already imputed"),
+ * store unchanged.  A .bed-form store (tpg_fbm_open_bed) has no byte to hold 4 + v: TPG_EUNSUPPORTED, use tpg_view_impute.
+ * A view is imputed into a NEW view of the same geometry that holds v itself (no code 3 left except at t = 0 loci): what the
+ * CODE_IMPUTE_PRED view of the imputed store would be.  `raw` is a view through code256 == NULL or CODE_012. */
+#define TPG_IMPUTE_NONE 0
+#define TPG_IMPUTE_MODE 1
+#define TPG_IMPUTE_MEAN0 2
+#define TPG_IMPUTE_RANDOM 3
+typedef struct tpg_impute_report {
+  int64_t imputed;          /* entries filled */
+  int64_t loci_all_missing; /* loci left missing because nobody is typed at them */
+} tpg_impute_report;
+/* in place on a byte store; rep may be NULL */
+int tpg_fbm_impute_simple(tpg_ctx* ctx, tpg_fbm* fbm, int method, uint64_t seed, tpg_impute_report* rep);
+/* the same for a store that holds columns [col0, col0 + ncol) of a larger one (an FBM that is imputed block of columns by block
+ * of columns: the R shim): `random` is keyed by col0 + the column, so the blocks together get the fill of one call */
+int tpg_fbm_impute_simple_at(tpg_ctx* ctx, tpg_fbm* fbm, int64_t col0, int method, uint64_t seed, tpg_impute_report* rep);
+int tpg_view_impute(tpg_ctx* ctx, const tpg_view* raw, int method, uint64_t seed, tpg_view** out, tpg_impute_report* rep);
+
 /* The (rowInd, colInd) view every reference kernel receives, packed once:
  * rowInd NULL = all rows, colInd NULL = all columns. */
 int tpg_view_create(tpg_ctx* ctx, const tpg_fbm* fbm, const int32_t* rowInd1, int64_t n,
@@ -442,7 +478,8 @@ void tpg_stream_close(tpg_stream* s);
  * the resident entry point of the same name lays it out.  One (rowInd, colInd) selection serves all of them. */
 #define TPG_STREAM_MAX_FST 3
 typedef struct tpg_stream_job {
-  size_t struct_size;     /* sizeof(tpg_stream_job) of the caller's header */
+  size_t struct_size;     /* sizeof(tpg_stream_job) of the caller's header: this one's, or TPG_STREAM_JOB_SIZE_V1 (a caller
+                             built before impute_method existed: the fields behind that size are not read and count as 0) */
   const int32_t* rowInd1; /* NULL = all rows */
   int64_t n;
   const int32_t* colInd1; /* NULL = all columns */
@@ -478,7 +515,14 @@ typedef struct tpg_stream_job {
   int k;
   double pca_tol;
   double *d, *u, *v, *center, *scale, *square_frobenius;
+  /* TPG_IMPUTE_*: with k > 0 the PCA of every block runs on the imputed raw view (tpg_view_impute; `random` keyed by the
+   * position in this job's selection, so every block plan gives the same fill).  code256_pca must then be NULL or CODE_012
+   * (TPG_EINVAL otherwise).  The other outputs go on reading the store as it is.  tpg_multi_stream_run: TPG_EUNSUPPORTED. */
+  int impute_method;
+  uint64_t impute_seed;
 } tpg_stream_job;
+/* the struct up to and including square_frobenius */
+#define TPG_STREAM_JOB_SIZE_V1 (offsetof(tpg_stream_job, square_frobenius) + sizeof(double*))
 
 typedef struct tpg_stream_report {
   int64_t blocks;          /* blocks of the first sweep */

@@ -668,6 +668,67 @@ SEXP _tidypopgen_tpg_invalidate(SEXP BM) {
   return R_NilValue;
 }
 
+/* tpg_impute_simple(BM, method, seed): gt_impute_simple's write to the FBM (bigsnpr::snp_fastImputeSimple behind
+ * R/gt_impute_simple.R:86), in place on the backing file: column blocks go up, are imputed (tpg_fbm_impute_simple_at: `random`
+ * keyed by the FBM's own row / column) and only the columns that changed are written back; then what tpg_invalidate does.
+ * method 1 = mode, 2 = mean0, 3 = random (TPG_IMPUTE_*).  A byte above 3 anywhere: the R error "object x is already imputed",
+ * file unchanged.  -> c(imputed, loci_all_missing) as doubles.
+ * The two library symbols are referenced weakly: the shim still links and loads against a library built before they existed
+ * (and against the host-only stand-in of the sanitizer jobs); the call then is an R error. */
+#pragma weak tpg_fbm_impute_simple_at
+#pragma weak tpg_fbm_to_host
+SEXP _tidypopgen_tpg_impute_simple(SEXP BM, SEXP method, SEXP seed) {
+  if (!tpg_fbm_impute_simple_at || !tpg_fbm_to_host) Rf_error("tidypopgen (GPU): this libtpg_hip has no tpg_fbm_impute_simple");
+  const int meth = Rf_asInteger(method);
+  SEXP sdx = PROTECT(as_real(seed));
+  const double sd = XLENGTH(sdx) == 1 ? REAL(sdx)[0] : -1.0;
+  UNPROTECT(1);
+  if (!(sd >= 0 && sd < 18446744073709551616.0)) Rf_error("seed must be a non-negative number below 2^64");
+  const uint64_t sd64 = (uint64_t)sd;
+  const int64_t nrow = field_i64(BM, "nrow"), ncol = field_i64(BM, "ncol");
+  if (nrow <= 0 || ncol <= 0) Rf_error("empty FBM");
+  mapped_file* f = map_file(field_path(BM, "backingfile"), (size_t)nrow * (size_t)ncol, 1, nrow, ncol);
+  uint8_t* bytes = (uint8_t*)f->map;
+  int64_t per = ((int64_t)256 << 20) / nrow;
+  if (per < 1) per = 1;
+  if (per > ncol) per = ncol;
+  uint8_t* back = (uint8_t*)malloc((size_t)per * (size_t)nrow);
+  if (!back) Rf_error("tidypopgen (GPU): out of memory");
+  double imputed = 0, all_missing = 0;
+  int rc = TPG_OK;
+  int64_t j0 = 0;
+  for (; j0 < ncol && rc == TPG_OK; j0 += per) {
+    const int64_t nb = ncol - j0 < per ? ncol - j0 : per;
+    uint8_t* at = bytes + (size_t)j0 * (size_t)nrow;
+    tpg_fbm* d = NULL;
+    tpg_impute_report rep = {0, 0};
+    rc = tpg_fbm_from_host(ctx(), at, nrow, nb, &d);
+    if (rc == TPG_OK) rc = tpg_fbm_impute_simple_at(ctx(), d, j0, meth, sd64, &rep);
+    if (rc == TPG_OK) rc = tpg_fbm_to_host(ctx(), d, back);
+    tpg_fbm_free(d);
+    if (rc != TPG_OK) break;
+    for (int64_t j = 0; j < nb; j++) /* only the columns that changed are written: the others' pages stay clean */
+      if (memcmp(at + (size_t)j * (size_t)nrow, back + (size_t)j * (size_t)nrow, (size_t)nrow) != 0)
+        memcpy(at + (size_t)j * (size_t)nrow, back + (size_t)j * (size_t)nrow, (size_t)nrow);
+    imputed += (double)rep.imputed;
+    all_missing += (double)rep.loci_all_missing;
+  }
+  free(back);
+  if (rc != TPG_OK) {
+    /* the blocks in front of the failing one were free of bytes above 3 before this call: their 4..6 are its fills */
+    const size_t done = (size_t)j0 * (size_t)nrow;
+    for (size_t i = 0; i < done; i++)
+      if (bytes[i] >= 4 && bytes[i] <= 6) bytes[i] = 3;
+  }
+  _tidypopgen_tpg_invalidate(BM);
+  if (rc != TPG_OK) Rf_error("tidypopgen (GPU): %s", tpg_last_error());
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, 2));
+  REAL(out)[0] = imputed;
+  REAL(out)[1] = all_missing;
+  UNPROTECT(1);
+  return out;
+}
+
 /* ---- PCA projection -------------------------------------------------------------------------------------------- */
 
 /* fbm256_prod_and_rowSumsSq(BM, ind_row, ind_col, center, scale, V)   src/fbm_prod_and_rowSumSq.cpp:10-47
@@ -843,11 +904,28 @@ const R_CallMethodDef tpg_rshim_entries[] = {
     {"_tidypopgen_tpg_pca_partial_svd", (DL_FUNC)&_tidypopgen_tpg_pca_partial_svd, 4},
     {NULL, NULL, 0}};
 
+/* The entry points that WRITE to the genotype FBM, in a table of their own.  Everything in tpg_rshim_entries[] leaves the
+ * caller's FBM as it found it (tests/test_gpu_rshim_entries.py runs every row of it on one shared backing file); a row here
+ * rewrites the backing file.  Both tables are registered (R_init_tpgshim below; INTEGRATION.md section 2 for the in-package
+ * route), so `.Call` finds these like the others. */
+const R_CallMethodDef tpg_rshim_entries_write[] = {
+    {"_tidypopgen_tpg_impute_simple", (DL_FUNC)&_tidypopgen_tpg_impute_simple, 3},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  R_registerRoutines(dll, NULL, tpg_rshim_entries, NULL, NULL);
+  /* R_registerRoutines takes ONE .Call table per DLL: the two tables end to end (the array must outlive the call) */
+  static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
+                             sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0])];
+  size_t k = 0;
+  for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
+  all[k].name = NULL;
+  all[k].fun = NULL;
+  all[k].numArgs = 0;
+  R_registerRoutines(dll, NULL, all, NULL, NULL);
   R_useDynamicSymbols(dll, FALSE);
 }
 #endif

@@ -44,6 +44,32 @@ tpg_release <- function() invisible(.Call(`_tidypopgen_tpg_release`))
 # only needed under TPG_RSHIM_CACHE=1 (an HBM copy of the whole FBM kept between calls): after anything that writes to X
 tpg_invalidate <- function(X) invisible(.Call(`_tidypopgen_tpg_invalidate`, X))
 
+# gt_impute_simple on the GPU: what R/gt_impute_simple.R does around bigsnpr::snp_fastImputeSimple, with the write to the
+# FBM done by the library in place (missing byte 3 -> 4 + fill).  method "mode" | "mean0" | "random"; `seed` keys the random
+# draws (R's generator is not used).  x is a gen_tibble; the result is x, imputed, with the imputed codes switched off.
+tpg_gt_impute_simple <- function(x, method = c("mode", "mean0", "random"), seed = 0) {
+  method <- match.arg(method)
+  X <- attr(x$genotypes, "fbm")
+  if (nrow(attr(x$genotypes, "loci")) != ncol(X)) {
+    stop("The number of SNPs in the gen_tibble does not match the number of columns in the file backing matrix. ",
+         "Before imputing, use gt_update_backingfile to update your file backing matrix.")
+  }
+  if (!is.null(attr(x$genotypes, "imputed"))) stop("object x is already imputed; use `gt_set_imputed(x, set = TRUE)`")
+  if (!identical(X$code256, bigsnpr::CODE_012)) {
+    if (identical(X$code256, bigsnpr::CODE_IMPUTE_PRED) || identical(X$code256, bigsnpr::CODE_DOSAGE)) {
+      stop("object x is already imputed, but attr(x, 'imputed') is null")
+    }
+    stop("object x uses a code256 that is not compatible with imputation")
+  }
+  report <- .Call(`_tidypopgen_tpg_impute_simple`, X, match(method, c("mode", "mean0", "random")), as.numeric(seed))
+  X$code256 <- bigsnpr::CODE_IMPUTE_PRED
+  attr(x$genotypes, "fbm") <- X
+  attr(x$genotypes, "imputed") <- "simple"
+  attr(x$genotypes, "tpg_impute_report") <- c(imputed = report[1], loci_all_missing = report[2])
+  tidypopgen::gt_set_imputed(x, set = FALSE)
+  x
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

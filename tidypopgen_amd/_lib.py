@@ -98,7 +98,7 @@ SYMBOLS = [
     "tpg_multi_grouped_alt_freq", "tpg_multi_pop_fst", "tpg_multi_pca_partial_svd",
     "tpg_pairwise_accumulate_products", "tpg_pairwise_products", "tpg_pairwise_reduce_begin", "tpg_pairwise_reduce_end",
     "tpg_stream_open_host", "tpg_stream_open_bk", "tpg_stream_open_bed", "tpg_stream_open_bed_host", "tpg_stream_open_synth",
-    "tpg_stream_close", "tpg_stream_run", "tpg_multi_stream_run",
+    "tpg_stream_close", "tpg_stream_run", "tpg_multi_stream_run", "tpg_fbm_impute_simple", "tpg_fbm_impute_simple_at", "tpg_view_impute",
 ]
 
 
@@ -113,7 +113,17 @@ class StreamJob(C.Structure):
         ("fst_tot", vp * 3), ("fst_by_locus", vp * 3), ("fst_by_locus_den", vp * 3),
         ("code256_pca", vp), ("k", C.c_int), ("pca_tol", C.c_double),
         ("d", vp), ("u", vp), ("v", vp), ("center", vp), ("scale", vp), ("square_frobenius", vp),
+        ("impute_method", C.c_int), ("impute_seed", C.c_uint64),
     ]
+
+
+# TPG_STREAM_JOB_SIZE_V1: the struct before impute_method existed (tpg_stream_run accepts that size too)
+STREAM_JOB_SIZE_V1 = StreamJob.square_frobenius.offset + C.sizeof(vp)
+
+
+class ImputeReport(C.Structure):
+    """tpg_impute_report of include/tpg.h"""
+    _fields_ = [("imputed", C.c_int64), ("loci_all_missing", C.c_int64)]
 
 
 class StreamReport(C.Structure):
@@ -126,6 +136,10 @@ class StreamReport(C.Structure):
     ]
 
 
+if hasattr(lib, "tpg_fbm_impute_simple"):  # (a library built before the entry points existed: build() reports it)
+    lib.tpg_fbm_impute_simple.argtypes = [vp, vp, C.c_int, C.c_uint64, C.POINTER(ImputeReport)]
+    lib.tpg_fbm_impute_simple_at.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_uint64, C.POINTER(ImputeReport)]
+    lib.tpg_view_impute.argtypes = [vp, vp, C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(ImputeReport)]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

@@ -34,6 +34,14 @@ CODE_IMPUTE_PRED[:3] = [0.0, 1.0, 2.0]
 CODE_IMPUTE_PRED[4:7] = [0.0, 1.0, 2.0]
 
 FST_METHODS = {"Hudson": 0, "Nei87": 1, "WC84": 2}
+# include/tpg.h: TPG_IMPUTE_* (gt_impute_simple's methods; "mean2" needs fractional dosages: out of scope)
+IMPUTE_METHODS = {"mode": 1, "mean0": 2, "random": 3}
+
+
+def _impute_method(method) -> int:
+    if method not in IMPUTE_METHODS:
+        raise ValueError(f"impute method must be one of {sorted(IMPUTE_METHODS)}, not {method!r}")
+    return IMPUTE_METHODS[method]
 # cross-products of the pairwise accumulators (include/tpg.h: TPG_PW_*)
 PW_V, PW_D, PW_H, PW_A = 1, 2, 4, 8
 PW_FOR_AS, PW_FOR_IBS, PW_FOR_KING, PW_ALL = PW_V | PW_D, PW_V | PW_D | PW_H, PW_V | PW_D | PW_A, 15
@@ -219,6 +227,14 @@ class FBM:
                                 C.c_int(npop), C.c_uint32(thr), C.c_int(int(imputed_bytes)), C.byref(h)))
         return cls(ctx, h, nrow, ncol, code256)
 
+    def impute_simple(self, method: str = "mode", seed: int = 0) -> dict:
+        """gt_impute_simple on the bytes in HBM, in place (tpg_fbm_impute_simple): a missing genotype (byte 3) becomes
+        byte 4 + fill, which CODE_IMPUTE_PRED reads and the raw-byte analyses go on treating as missing.  Returns the
+        report {"imputed", "loci_all_missing"}.  The FBM's code256 is left as it is (gt_impute_simple below switches it)."""
+        rep = _lib.ImputeReport()
+        check(lib.tpg_fbm_impute_simple(self.ctx.h, self.h, C.c_int(_impute_method(method)), C.c_uint64(seed), C.byref(rep)))
+        return {"imputed": int(rep.imputed), "loci_all_missing": int(rep.loci_all_missing)}
+
     def to_numpy(self) -> np.ndarray:
         out = np.zeros((self.nrow, self.ncol), dtype=np.uint8, order="F")
         check(lib.tpg_fbm_to_host(self.ctx.h, self.h, _ptr(out)))
@@ -270,6 +286,18 @@ class View:
             v.n, v.m = int(lib.tpg_view_n(h)), int(lib.tpg_view_m(h))
             out.append(v)
         return out[0], out[1]
+
+    def impute(self, method: str = "mode", seed: int = 0) -> "View":
+        """a new view of the same rows / columns with the missing genotypes of this (raw) view filled from the kept rows
+        (tpg_view_impute): the only route for a .bed-form store.  The report is left in `.impute_report` of the result."""
+        h = C.c_void_p()
+        rep = _lib.ImputeReport()
+        check(lib.tpg_view_impute(self.ctx.h, self.h, C.c_int(_impute_method(method)), C.c_uint64(seed), C.byref(h), C.byref(rep)))
+        v = View.__new__(View)
+        v.X, v.ctx, v.h = self.X, self.ctx, h
+        v.n, v.m = int(lib.tpg_view_n(h)), int(lib.tpg_view_m(h))
+        v.impute_report = {"imputed": int(rep.imputed), "loci_all_missing": int(rep.loci_all_missing)}
+        return v
 
     def unpack(self) -> np.ndarray:
         out = np.zeros((self.n, self.m), dtype=np.uint8, order="F")
@@ -652,11 +680,13 @@ class Stream:
             groupIds=None, ngroups: int = 0, as_counts: bool = False, alt_freq: bool = False, grouped_alt_freq: bool = False,
             grouped_missingness: bool = False, loci_counts: bool = False, fst=(), fst_by_locus: bool = False,
             fst_return_num_dem: bool = False, pairwise_combn=None, k: int = 0, pca_tol: float = 0.0, code256_pca=CODE_IMPUTE_PRED, total_var: bool = True,
-            multi: Optional["Multi"] = None) -> dict:
+            multi: Optional["Multi"] = None, impute: Optional[str] = None, impute_seed: int = 0) -> dict:
         """One streamed pass for everything asked for (tpg_stream_run; with `multi`, tpg_multi_stream_run: the loci
         sharded over its devices).  pairwise: any of "ibs", "king", "allele_sharing", "grm"; fst: up to three of
         "Hudson", "Nei87", "WC84"; k > 0: gt_pca_partialSVD (pca_tol > 0: gt_pca_randomSVD's tolerance).  Returns the
-        results under the names of the resident functions, plus "report" (blocks, bytes moved, peak HBM)."""
+        results under the names of the resident functions, plus "report" (blocks, bytes moved, peak HBM).
+        impute = "mode" | "mean0" | "random": the PCA of every block runs on the imputed raw view (View.impute, keyed by
+        the position in the selection: every block plan gives the same fill); code256_pca is then CODE_012."""
         r, c = _i32(ind_row), _i32(ind_col)
         n = self.nrow if r is None else len(r)
         m = self.ncol if c is None else len(c)
@@ -713,8 +743,10 @@ class Stream:
             if not fst_return_num_dem:
                 del out["fst_locus_den"]
         fro = C.c_double()
+        if impute is not None:
+            job.impute_method, job.impute_seed = _impute_method(impute), int(impute_seed)
         if k > 0:
-            cp = _f64(code256_pca)
+            cp = _f64(CODE_012 if impute is not None else code256_pca)
             keep.append(cp)
             out.update(d=np.zeros(k), u=np.empty((n, k), order="F"), v=np.empty((m, k), order="F"), center=np.empty(m),
                        scale=np.empty(m), method="partialSVD" if pca_tol == 0 else "randomSVD")
@@ -1358,11 +1390,19 @@ def pca_loadings(v: View, center, scale, U, d) -> np.ndarray:
     return out
 
 
+def _pca_view(X: FBM, ind_row, ind_col, code256, impute, impute_seed) -> View:
+    """the view a PCA reads: through code256, or -- impute = "mode" | "mean0" | "random" -- the raw view with its missing
+    genotypes filled from the kept rows (View.impute; the store itself is not changed)"""
+    if impute is None:
+        return View(X, ind_row, ind_col, code256=code256)
+    return View(X, ind_row, ind_col, code256=CODE_012).impute(impute, impute_seed)
+
+
 def gt_pca_partialSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, total_var: bool = True,
-                      code256=CODE_IMPUTE_PRED) -> dict:
+                      code256=CODE_IMPUTE_PRED, impute: Optional[str] = None, impute_seed: int = 0) -> dict:
     """R/gt_pca_partialSVD.R:67-108: the imputed code table is switched on (:74-77), then
     bigstatsr::big_SVD with bigsnpr::snp_scaleBinom."""
-    v = View(X, ind_row, ind_col, code256=code256)
+    v = _pca_view(X, ind_row, ind_col, code256, impute, impute_seed)
     d = np.zeros(k)
     u = np.zeros((v.n, k), order="F")
     vl = np.zeros((v.m, k), order="F")
@@ -1376,15 +1416,25 @@ def gt_pca_partialSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, total_var
     return out
 
 
+def gt_impute_simple(X: FBM, method: str = "mode", seed: int = 0) -> FBM:
+    """R/gt_impute_simple.R:54-93: the missing genotypes of X are filled in place (FBM.impute_simple) and X then reads
+    through CODE_IMPUTE_PRED, as the reference leaves the gen_tibble's FBM; the report is left in `X.impute_report`.
+    An error where the reference stops: "object x is already imputed" (a store byte above 3), and a .bed-form store,
+    which cannot hold an imputed byte (impute a View of it)."""
+    X.impute_report = X.impute_simple(method, seed)
+    X.code256 = CODE_IMPUTE_PRED.copy()
+    return X
+
+
 def gt_pca_randomSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, tol: float = 1e-4, total_var: bool = True,
-                     code256=CODE_IMPUTE_PRED) -> dict:
+                     code256=CODE_IMPUTE_PRED, impute: Optional[str] = None, impute_seed: int = 0) -> dict:
     """R/gt_pca_randomSVD.R:77-135.  The reference reaches the truncated SVD of the scaled matrix through
     bigstatsr::big_randomSVD (RSpectra::svds on the implicit operator), which accepts a singular triplet at the
     relative residual `tol`; the device path runs the same Gram + subspace iteration as gt_pca_partialSVD and stops
     at that tolerance: |K u_j - d_j^2 u_j| <= tol * d_1^2."""
     if not (0 < tol < 1):
         raise ValueError("tol must be in (0, 1)")
-    v = View(X, ind_row, ind_col, code256=code256)
+    v = _pca_view(X, ind_row, ind_col, code256, impute, impute_seed)
     d = np.zeros(k)
     u = np.zeros((v.n, k), order="F")
     vl = np.zeros((v.m, k), order="F")

@@ -322,6 +322,9 @@ int tpg_launch_pack(tpg_ctx* ctx, const tpg_fbm* fbm, const int32_t* d_rows, con
 int tpg_launch_unpack(tpg_ctx* ctx, const tpg_view* v, uint8_t* d_codes, int from_L);
 // the T layout of a view that was packed without it (from L; a no-op when it is there)
 int tpg_view_need_T(tpg_ctx* ctx, const tpg_view* v);
+// impute.hip: tpg_view_impute with the view's first locus at position col0 of the object being imputed (a streamed block)
+int tpg_view_impute_at(tpg_ctx* ctx, const tpg_view* raw, int method, uint64_t seed, int64_t col0, tpg_view** out,
+                       tpg_impute_report* rep);
 int tpg_launch_synth(tpg_ctx* ctx, uint8_t* d_bytes, uint64_t seed, int64_t nrow, int64_t ncol, int64_t j0,
                      int npop, uint32_t miss_thresh, int imputed_bytes);
 

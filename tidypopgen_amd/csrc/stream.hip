@@ -128,6 +128,7 @@ struct StreamRun {
   const StreamSource* src = nullptr;
   const tpg_stream_job* job = nullptr;
   size_t budget = 0;
+  int impute = TPG_IMPUTE_NONE;  // the PCA runs on tpg_view_impute of its view (job->impute_method with k > 0)
   int64_t n = 0, m = 0;      // the selection (m = all loci of the job, not only this device's)
   int64_t P0 = 0, P1 = 0;    // this device's positions of colInd
   tpg_ctx *up_ctx = nullptr, *down_ctx = nullptr;
@@ -238,6 +239,14 @@ struct StreamRun {
       TPG_REQUIRE(j->d && j->u && j->v && j->center && j->scale, TPG_EINVAL, "the PCA needs d, u, v, center and scale");
       TPG_REQUIRE(j->k <= n && j->k <= m, TPG_EINVAL, "k = %d out of range", j->k);
       TPG_REQUIRE(j->pca_tol >= 0 && j->pca_tol < 1, TPG_EINVAL, "pca_tol = %g out of [0, 1)", j->pca_tol);
+      if (j->impute_method != TPG_IMPUTE_NONE) {
+        // the PCA's view of a block is the imputed RAW view: the table must read bytes 0, 1, 2 as themselves and nothing else
+        uint8_t l[256], raw[256];
+        lut_of(j->code256_pca, l);
+        lut_of(nullptr, raw);
+        TPG_REQUIRE(memcmp(l, raw, 256) == 0, TPG_EINVAL, "with impute_method the PCA reads the raw store: code256_pca must be NULL or CODE_012");
+        impute = j->impute_method;
+      }
     }
     // which views a block needs: tables that map every byte alike are one view
     code_pw = nullptr;
@@ -282,6 +291,7 @@ struct StreamRun {
       if (j->fst_by_locus[i]) outp += 8 * (size_t)j->P * (j->fst_return_num_dem ? 2 : 1);
     if (want_pca) outp += 16 + 8 * (size_t)j->k;
     per += 2 * outp;
+    if (impute) per += npad / 4;  // the imputed view's L beside the raw one
     if (want_pca) per += 16 + 24 + npad / 4 + (npad / 4) * 5 / 4;  // counts, weights, the class path's locus-major copy + sorted operands
     per += per / 8;                                                  // slack: row / column index vectors, padding to whole tiles, pool rounding
     const size_t keep_all = want_pca ? (size_t)mloc * (npad / 4 + 16) : 0;  // imputed L views + center / scale for the loadings
@@ -684,6 +694,14 @@ struct StreamRun {
       if (want_pw) TPG_TRY(tpg_pairwise_accumulate_products(ctx, pw, v[view_of_pw], 0, -1, products));
       if (want_pca) {
         tpg_view* vp = v[view_of_pca];
+        struct Imputed {
+          tpg_view* v = nullptr;
+          ~Imputed() { tpg_view_free(v); }
+        } imp;
+        if (impute) {  // keyed by position in the selection: q0 + the locus of the block
+          TPG_TRY(tpg_view_impute_at(ctx, vp, impute, j->impute_seed, q0, &imp.v, nullptr));
+          vp = imp.v;
+        }
         double *dc = o.dc.as<double>(), *ds = o.ds.as<double>();
         Kept* kp = nullptr;
         if (keep_views) {
@@ -714,7 +732,8 @@ struct StreamRun {
         TPG_TRY(rows_out(j->scale, 8, m, q0, ds, mb, 1, ev, keep_views ? -1 : slot));
         if (kp) {
           kp->v = vp;  // the imputed view stays for the loadings
-          v[view_of_pca] = nullptr;
+          if (imp.v) imp.v = nullptr;
+          else v[view_of_pca] = nullptr;
           // what the loadings read is L; the other layouts go back to the pool now
           if (kp->v->T) { tpg_pfree(kp->v->T); kp->v->T = nullptr; }
           if (kp->v->T4) { tpg_pfree(kp->v->T4); kp->v->T4 = nullptr; }
@@ -879,6 +898,13 @@ struct StreamRun {
       const tpg_fbm f = block_fbm(slot, mb);
       tpg_view* vp = nullptr;
       TPG_TRY(tpg_view_create(ctx, &f, j->rowInd1, n, nullptr, 0, block_table(slot, code_pca), &vp));
+      if (impute) {
+        tpg_view* vi = nullptr;
+        const int rci = tpg_view_impute_at(ctx, vp, impute, j->impute_seed, q0, &vi, nullptr);
+        tpg_view_free(vp);
+        TPG_TRY(rci);
+        vp = vi;
+      }
       release_block(b);
       OutSlot& o = out[slot];
       int rc = wait_slot(slot);
@@ -949,10 +975,25 @@ struct StreamRun {
   }
 };
 
+// The caller's job as this library's struct: a caller built against the header before impute_method existed passes the
+// shorter struct; nothing behind its struct_size is read and the newer fields are 0.  Any other size is refused.
+static int read_job(const tpg_stream_job* job, tpg_stream_job* full) {
+  TPG_REQUIRE(job, TPG_EINVAL, "null argument");
+  TPG_REQUIRE(job->struct_size == sizeof(tpg_stream_job) || job->struct_size == TPG_STREAM_JOB_SIZE_V1, TPG_EINVAL,
+              "tpg_stream_job of %zu bytes, this library's has %zu (or %zu without impute_method)", job->struct_size,
+              sizeof(tpg_stream_job), (size_t)TPG_STREAM_JOB_SIZE_V1);
+  memset(full, 0, sizeof(*full));
+  memcpy(full, job, job->struct_size);
+  full->struct_size = sizeof(*full);
+  return TPG_OK;
+}
+
 static int check_job(const tpg_stream* s, const tpg_stream_job* job, int64_t* n, int64_t* m) {
   TPG_REQUIRE(s && job, TPG_EINVAL, "null argument");
   TPG_REQUIRE(job->struct_size == sizeof(tpg_stream_job), TPG_EINVAL, "tpg_stream_job of %zu bytes, this library's has %zu",
               job->struct_size, sizeof(tpg_stream_job));
+  TPG_REQUIRE(job->impute_method >= TPG_IMPUTE_NONE && job->impute_method <= TPG_IMPUTE_RANDOM, TPG_EINVAL,
+              "impute_method %d is not a TPG_IMPUTE_* value", job->impute_method);
   *n = job->rowInd1 ? job->n : s->src.nrow;
   *m = job->colInd1 ? job->m : s->src.ncol;
   TPG_REQUIRE(*n > 0 && *m > 0, TPG_EINVAL, "empty selection (%lld x %lld)", (long long)*n, (long long)*m);
@@ -1087,9 +1128,12 @@ extern "C" void tpg_stream_close(tpg_stream* s) {
   delete s;
 }
 
-extern "C" int tpg_stream_run(tpg_ctx* ctx, tpg_stream* s, const tpg_stream_job* job, tpg_stream_report* report) {
+extern "C" int tpg_stream_run(tpg_ctx* ctx, tpg_stream* s, const tpg_stream_job* caller_job, tpg_stream_report* report) {
   TpgEnter _enter(ctx);
-  TPG_REQUIRE(ctx && s && job, TPG_EINVAL, "null argument");
+  TPG_REQUIRE(ctx && s && caller_job, TPG_EINVAL, "null argument");
+  tpg_stream_job full;
+  TPG_TRY(read_job(caller_job, &full));
+  const tpg_stream_job* job = &full;
   TPG_REQUIRE(s->ctx == ctx, TPG_EINVAL, "the stream was opened on another context");
   int64_t n = 0, m = 0;
   TPG_TRY(check_job(s, job, &n, &m));
@@ -1135,10 +1179,15 @@ int tpg_multi_stream_host(tpg_multi* mg, const uint8_t* fbm_bytes, int64_t nrow,
 // Several devices (one process): every device streams its contiguous share of colInd (tpg_shard_loci), then the exchanges.
 // Phases are separate thread teams, as in comm.hip: a failure in a rank-local phase is known to all before anyone enters a
 // collective.
-extern "C" int tpg_multi_stream_run(tpg_multi* mg, tpg_stream* s, const tpg_stream_job* job, tpg_stream_report* report) {
-  TPG_REQUIRE(mg && s && job, TPG_EINVAL, "null argument");
+extern "C" int tpg_multi_stream_run(tpg_multi* mg, tpg_stream* s, const tpg_stream_job* caller_job, tpg_stream_report* report) {
+  TPG_REQUIRE(mg && s && caller_job, TPG_EINVAL, "null argument");
+  tpg_stream_job full;
+  TPG_TRY(read_job(caller_job, &full));
+  const tpg_stream_job* job = &full;
   int64_t n = 0, m = 0;
   TPG_TRY(check_job(s, job, &n, &m));
+  TPG_REQUIRE(job->impute_method == TPG_IMPUTE_NONE, TPG_EUNSUPPORTED,
+              "tpg_multi_stream_run does not impute: run the job on one device (tpg_stream_run), or impute the store first");
   const int ndev = tpg_multi_ndev(mg);
   void* outs[] = {job->ibs, job->king, job->allele_sharing, job->grm, job->alt_freq, job->grouped_alt_freq, job->grouped_missingness,
                   job->loci_counts, job->d, job->u, job->v, job->center, job->scale};
