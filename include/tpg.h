@@ -185,10 +185,28 @@ int tpg_gt_pi_diploid(tpg_ctx* ctx, const tpg_view* v, double* pi);
 int tpg_gt_grouped_pi_diploid(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, double* pi,
                               double* n);
 /* genotype counts per locus x group, the 3 x ngroups table gt_grouped_hwe fills before each exact test
- * (src/hwe.cpp:238-250; the test itself, PLINK's SNPHWE2, is out of scope): out = three m x G int32 matrices
- * (column-major), k = 0, 1, 2 alternate alleles */
+ * (src/hwe.cpp:238-250; the test on that table, without the download: tpg_gt_grouped_hwe below): out = three m x G int32
+ * matrices (column-major), k = 0, 1, 2 alternate alleles */
 int tpg_grouped_genotype_counts(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups,
                                 int32_t* out);
+/* ---- Hardy-Weinberg exact tests (loci_hwe, R/loci_hwe.R; the reference's .Call rows SNPHWE2_R, hwe_on_matrix,
+ * gt_grouped_hwe) ----
+ * For a table (hom1, het, hom2) of n individuals with r = 2 min(hom1, hom2) + het copies of the rarer allele, the
+ * heterozygote count x runs over r mod 2, r mod 2 + 2, ..., r with w(x + 2) / w(x) = (r - x)(2n - r - x) / ((x + 2)(x + 1))
+ * (Wigginton, Cutler, Abecasis 2005).  With eps = 2^-44, T = {x : w(x) < w(het)(1 + eps)} and ties = the members of T with
+ * w(x) > w(het)(1 - eps): p = sum_T w / sum w; with midp (Graffelman, Moreno 2013) half of ties w(het) is taken off the
+ * numerator.  n = 0 gives 1 (mid-p 0.5); a p below 1e-300 may come back as 0.  FP64 recurrence from the observed count,
+ * within 8 max(n, 8) 2^-53 of the exact value (relative); tables of n < 2^26.  midp is 0 or 1.  The tests run on the
+ * device behind the count sweeps: no count table crosses PCIe. */
+/* p[count]; counts3 = 3 x count int32, column-major {hom1, het, hom2} per test (rows 1..3 of bigstatsr::big_counts, what
+ * hwe_on_matrix takes); host or device memory both sides */
+int tpg_hwe_exact_counts(tpg_ctx* ctx, const int32_t* counts3, int64_t count, int midp, double* p);
+/* loci_hwe of an ungrouped object (R/loci_hwe.R:64-95: big_counts + hwe_on_matrix per block): p[m] */
+int tpg_loci_hwe(tpg_ctx* ctx, const tpg_view* v, int midp, double* p);
+/* gt_grouped_hwe (src/hwe.cpp:220-253): p is m x G column-major; a group nobody belongs to or is typed in gives the
+ * n = 0 value */
+int tpg_gt_grouped_hwe(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, int midp, double* p);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

@@ -43,6 +43,7 @@
 #include <R_ext/Rdynload.h>
 
 #include "tpg.h"
+#include "../tidypopgen_amd/csrc/host/host_hwe.h" /* SNPHWE2_R: one table, on the host */
 
 /* R's missing values come from R_ext/Arith.h, which R.h includes.  A build against stand-in R headers that declare only
  * the API functions (a syntax and signature guard) gets the same values here: NA_real_ is the NaN whose low word is
@@ -875,10 +876,92 @@ SEXP _tidypopgen_tpg_pca_partial_svd(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k) 
   return out;
 }
 
+/* ---- Hardy-Weinberg exact tests ------------------------------------------------------------------------------ */
+
+/* The three library symbols are referenced weakly, as those of tpg_impute_simple are: the shim still links and loads
+ * against a library built before they existed (and against the host-only stand-in of the sanitizer jobs); the call then is
+ * an R error. */
+#pragma weak tpg_hwe_exact_counts
+#pragma weak tpg_loci_hwe
+#pragma weak tpg_gt_grouped_hwe
+#define HWE_NEEDS(sym) \
+  do { \
+    if (!(sym)) Rf_error("tidypopgen (GPU): this libtpg_hip has no " #sym); \
+  } while (0)
+
+static int midp_of(SEXP midp) { /* Rcpp's uint32_t midp: TRUE / FALSE / a number; the test only asks whether it is set */
+  const int v = Rf_asLogical(midp);
+  if (v == NA_INTEGER) Rf_error("tidypopgen (GPU): midp must be TRUE or FALSE");
+  return v != 0;
+}
+
+/* SNPHWE2_R(obs_hets, obs_hom1, obs_hom2, midp)   src/hwe.cpp:193-200: one table, heterozygotes first.  No device call. */
+SEXP _tidypopgen_SNPHWE2_R(SEXP obs_hets, SEXP obs_hom1, SEXP obs_hom2, SEXP midp) {
+  const int het = Rf_asInteger(obs_hets), hom1 = Rf_asInteger(obs_hom1), hom2 = Rf_asInteger(obs_hom2), mid = midp_of(midp);
+  if (het == NA_INTEGER || hom1 == NA_INTEGER || hom2 == NA_INTEGER || het < 0 || hom1 < 0 || hom2 < 0)
+    Rf_error("tidypopgen (GPU): genotype counts must be non-negative integers");
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, 1));
+  REAL(out)[0] = tpg_hwe_exact(hom1, het, hom2, mid);
+  UNPROTECT(1);
+  return out;
+}
+
+/* hwe_on_matrix(geno_counts, midp)   src/hwe.cpp:203-213: rows 1..3 of a big_counts matrix (hom1, het, hom2; its fourth
+   row, the NA count, is not read) -> one p-value per column */
+SEXP _tidypopgen_hwe_on_matrix(SEXP geno_counts, SEXP midp) {
+  HWE_NEEDS(tpg_hwe_exact_counts);
+  const int mid = midp_of(midp);
+  SEXP gc = PROTECT(as_int(geno_counts));
+  SEXP dim = Rf_getAttrib(gc, R_DimSymbol);
+  if (dim == R_NilValue || XLENGTH(dim) != 2 || INTEGER(dim)[0] < 3) Rf_error("tidypopgen (GPU): geno_counts must be a matrix of at least 3 rows");
+  const int nr = INTEGER(dim)[0], m = INTEGER(dim)[1];
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, m));
+  const int* tab = INTEGER(gc);
+  if (nr != 3 && m > 0) {
+    int* t3 = (int*)R_alloc((size_t)3 * (size_t)m, sizeof(int));
+    for (int j = 0; j < m; j++)
+      for (int k = 0; k < 3; k++) t3[3 * (size_t)j + k] = tab[(size_t)nr * (size_t)j + k];
+    tab = t3;
+  }
+  for (R_xlen_t k = 0; k < (R_xlen_t)3 * m; k++)
+    if (tab[k] == NA_INTEGER) Rf_error("tidypopgen (GPU): NA in geno_counts");
+  TPG_R(tpg_hwe_exact_counts(ctx(), tab, m, mid, REAL(out)));
+  UNPROTECT(2);
+  return out;
+}
+
+/* gt_grouped_hwe(BM, rowInd, colInd, groupIds, ngroups, midp)   src/hwe.cpp:220-253 -> m x G */
+SEXP _tidypopgen_gt_grouped_hwe(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP midp) {
+  HWE_NEEDS(tpg_gt_grouped_hwe);
+  const int G = ngroups_of(ngroups), mid = midp_of(midp);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
+  if (XLENGTH(gid) != XLENGTH(ri)) Rf_error("tidypopgen (GPU): groupIds and rowInd differ in length");
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)XLENGTH(ci), G));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_gt_grouped_hwe(ctx(), v, INTEGER(gid), G, mid, REAL(out)));
+  UNPROTECT(4);
+  return out;
+}
+
+/* tpg_loci_hwe(BM, rowInd, colInd, midp): the whole of R/loci_hwe.R:74-89 (big_counts + hwe_on_matrix per block) in one
+   call -> one p-value per locus */
+SEXP _tidypopgen_tpg_loci_hwe(SEXP BM, SEXP rowInd, SEXP colInd, SEXP midp) {
+  HWE_NEEDS(tpg_loci_hwe);
+  const int mid = midp_of(midp);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  if (XLENGTH(ri) < 2) Rf_error("Not implemented for a single individual"); /* R/loci_hwe.R:92 */
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, XLENGTH(ci)));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_loci_hwe(ctx(), v, mid, REAL(out)));
+  UNPROTECT(3);
+  return out;
+}
+
 /* ---- registration ------------------------------------------------------------------------------------------------
  * Same names and arities as the reference's table (src/RcppExports.cpp:348-371).  These rows replace the rows of the
- * same name there; the other rows of that table (compute_np_mn, the HWE functions, the VCF / packedancestry readers,
- * write_to_FBM) keep pointing at the reference's own C++. */
+ * same name there, and so do the three HWE rows of tpg_rshim_entries_hwe[] below; the other rows of that table
+ * (compute_np_mn, the VCF / packedancestry readers, write_to_FBM) keep pointing at the reference's own C++. */
 const R_CallMethodDef tpg_rshim_entries[] = {
     {"_tidypopgen_alt_freq_dip_pseudo_cpp", (DL_FUNC)&_tidypopgen_alt_freq_dip_pseudo_cpp, 6},
     {"_tidypopgen_fbm256_prod_and_rowSumsSq", (DL_FUNC)&_tidypopgen_fbm256_prod_and_rowSumsSq, 6},
@@ -912,16 +995,27 @@ const R_CallMethodDef tpg_rshim_entries_write[] = {
     {"_tidypopgen_tpg_impute_simple", (DL_FUNC)&_tidypopgen_tpg_impute_simple, 3},
     {NULL, NULL, 0}};
 
+/* The Hardy-Weinberg exact tests, in a table of their own: the three rows of the reference's table (src/RcppExports.cpp:358-360)
+ * and the whole of loci_hwe's block loop in one call.  Registered with the other two tables. */
+const R_CallMethodDef tpg_rshim_entries_hwe[] = {
+    {"_tidypopgen_SNPHWE2_R", (DL_FUNC)&_tidypopgen_SNPHWE2_R, 4},
+    {"_tidypopgen_hwe_on_matrix", (DL_FUNC)&_tidypopgen_hwe_on_matrix, 2},
+    {"_tidypopgen_gt_grouped_hwe", (DL_FUNC)&_tidypopgen_gt_grouped_hwe, 6},
+    {"_tidypopgen_tpg_loci_hwe", (DL_FUNC)&_tidypopgen_tpg_loci_hwe, 4},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the two tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the three tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
-                             sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0])];
+                             sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
+                             sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_hwe; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

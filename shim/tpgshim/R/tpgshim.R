@@ -11,14 +11,17 @@
   increment_as_counts = 7L, increment_ibs_counts = 8L, increment_king_numerator = 9L
 )
 .tpg_saved <- new.env()
+# the Hardy-Weinberg wrappers (tpg_rshim_entries_hwe[] of the shim), rebound like the others
+.tpg_routines_hwe <- c(SNPHWE2_R = 4L, hwe_on_matrix = 2L, gt_grouped_hwe = 6L)
 
 tpg_enable <- function() {
   ns <- asNamespace("tidypopgen")
-  for (name in names(.tpg_routines)) {
+  routines <- c(.tpg_routines, .tpg_routines_hwe)
+  for (name in names(routines)) {
     original <- get(name, envir = ns)
     if (is.null(.tpg_saved[[name]])) assign(name, original, envir = .tpg_saved)
     sym <- getNativeSymbolInfo(paste0("_tidypopgen_", name), PACKAGE = "tpgshim")
-    stopifnot(length(formals(original)) == .tpg_routines[[name]])
+    stopifnot(length(formals(original)) == routines[[name]])
     replacement <- original
     body(replacement) <- bquote(.Call(.(sym), ..(lapply(names(formals(original)), as.name))), splice = TRUE)
     unlockBinding(name, ns)
@@ -68,6 +71,13 @@ tpg_gt_impute_simple <- function(x, method = c("mode", "mean0", "random"), seed 
   attr(x$genotypes, "tpg_impute_report") <- c(imputed = report[1], loci_all_missing = report[2])
   tidypopgen::gt_set_imputed(x, set = FALSE)
   x
+}
+
+# loci_hwe of an ungrouped gen_tibble column in one call (R/loci_hwe.R:74-89: big_counts + hwe_on_matrix per block); X is
+# the FBM.code256, ind.row / ind.col the kept individuals and loci.  gt_grouped_hwe, hwe_on_matrix and SNPHWE2_R keep their
+# names and arguments: the shim registers them under the reference's own symbols (tpg_rshim_entries_hwe[]).
+tpg_loci_hwe <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), mid_p = TRUE) {
+  .Call(`_tidypopgen_tpg_loci_hwe`, X, as.integer(ind.row), as.integer(ind.col), isTRUE(mid_p))
 }
 
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))

@@ -99,6 +99,7 @@ SYMBOLS = [
     "tpg_pairwise_accumulate_products", "tpg_pairwise_products", "tpg_pairwise_reduce_begin", "tpg_pairwise_reduce_end",
     "tpg_stream_open_host", "tpg_stream_open_bk", "tpg_stream_open_bed", "tpg_stream_open_bed_host", "tpg_stream_open_synth",
     "tpg_stream_close", "tpg_stream_run", "tpg_multi_stream_run", "tpg_fbm_impute_simple", "tpg_fbm_impute_simple_at", "tpg_view_impute",
+    "tpg_hwe_exact_counts", "tpg_loci_hwe", "tpg_gt_grouped_hwe",
 ]
 
 
@@ -140,6 +141,10 @@ if hasattr(lib, "tpg_fbm_impute_simple"):  # (a library built before the entry p
     lib.tpg_fbm_impute_simple.argtypes = [vp, vp, C.c_int, C.c_uint64, C.POINTER(ImputeReport)]
     lib.tpg_fbm_impute_simple_at.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_uint64, C.POINTER(ImputeReport)]
     lib.tpg_view_impute.argtypes = [vp, vp, C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(ImputeReport)]
+if hasattr(lib, "tpg_loci_hwe"):
+    lib.tpg_hwe_exact_counts.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
+    lib.tpg_loci_hwe.argtypes = [vp, vp, C.c_int, vp]
+    lib.tpg_gt_grouped_hwe.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

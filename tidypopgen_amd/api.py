@@ -1008,6 +1008,42 @@ def grouped_genotype_counts(v: View, groupIds, ngroups: int) -> np.ndarray:
     return np.ascontiguousarray(out.transpose(0, 2, 1))
 
 
+def hwe_on_matrix(geno_counts, midp, ctx: Optional[Context] = None) -> np.ndarray:
+    """src/hwe.cpp:203-213: the exact test on every column of a 3 x m count matrix, rows hom1 / het / hom2 as
+    bigstatsr::big_counts gives them (tpg_hwe_exact_counts)"""
+    ctx = ctx or default_context()
+    g = np.asarray(geno_counts)
+    if g.ndim != 2 or g.shape[0] < 3:
+        raise ValueError("geno_counts must have the rows hom1, het, hom2")
+    counts = np.ascontiguousarray(g[:3].T, dtype=np.int32)  # column-major 3 x m
+    out = np.zeros(counts.shape[0])
+    check(lib.tpg_hwe_exact_counts(ctx.h, _ptr(counts), C.c_int64(counts.shape[0]), C.c_int(int(bool(midp))), _ptr(out)))
+    return out
+
+
+def SNPHWE2_R(obs_hets, obs_hom1, obs_hom2, midp, ctx: Optional[Context] = None) -> float:
+    """src/hwe.cpp:193-200: one table; the heterozygotes come first"""
+    return float(hwe_on_matrix(np.array([[obs_hom1], [obs_hets], [obs_hom2]]), midp, ctx)[0])
+
+
+def gt_grouped_hwe(v: View, groupIds, ngroups: int, mid_p: bool = True) -> np.ndarray:
+    """src/hwe.cpp:220-253 -> (m, G) p-values; counts and tests both on the device (tpg_gt_grouped_hwe)"""
+    out = np.zeros((v.m, ngroups), order="F")
+    gid = _i32(groupIds)
+    check(lib.tpg_gt_grouped_hwe(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), C.c_int(int(bool(mid_p))), _ptr(out)))
+    return out
+
+
+def loci_hwe(X: FBM, ind_row=None, ind_col=None, mid_p: bool = True) -> np.ndarray:
+    """R/loci_hwe.R:64-95 (ungrouped) -> (m,) p-values"""
+    if (X.nrow if ind_row is None else len(ind_row)) < 2:
+        raise ValueError("Not implemented for a single individual")
+    v = View(X, ind_row, ind_col)
+    out = np.zeros(v.m)
+    check(lib.tpg_loci_hwe(v.ctx.h, v.h, C.c_int(int(bool(mid_p))), _ptr(out)))
+    return out
+
+
 GLOBAL_STATS_COLUMNS = ("Ho", "Hs", "Ht", "Dst", "Htp", "Dstp", "Fst", "Fstp", "Fis", "Dest")
 
 
