@@ -378,7 +378,7 @@ bool tpg_comm_alltoall_usable(tpg_comm* comm) {
   tpg_pfree(ds);
   tpg_pfree(dr);
   comm->a2a_state = rc == TPG_OK ? 1 : -1;
-  if (rc != TPG_OK && getenv("TPG_DEBUG")) fprintf(stderr, "[tpg] all-to-all self-test failed on this communicator: no class exchange\n");
+  if (rc != TPG_OK && tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] all-to-all self-test failed on this communicator: no class exchange\n");
   return rc == TPG_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <map>
 #include <set>
@@ -214,6 +215,14 @@ static inline int tpg_pw_products_for(bool ibs, bool king, bool as_or_grm) {
 }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The TPG_* environment switches (INTEGRATION.md "Environment" has the list; tests/test_env_switches.py keeps it true).  Both
+// read the environment on every call: a site that wants one read per process keeps the result in a static.
+static inline bool tpg_env_set(const char* name) { return getenv(name) != nullptr; }
+static inline int tpg_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // Size-bucketed cache of device allocations (hipMalloc / hipFree cost milliseconds and synchronise
 // the device; a step of the hot path needs ~40 scratch buffers).  One pool PER CONTEXT: a context issues

@@ -256,18 +256,17 @@ __global__ __launch_bounds__(256) void tpg_fst_reduce_kernel(const double* __res
 // statement): the totals agree to ~1e-14 relative.
 #define FSTG_T 64   // populations per tile side
 #define FSTG_LB 16  // loci per staged chunk (32 KiB of LDS: four workgroups per CU hide one another's staging)
-// MF: the three products on the FP64 matrix cores (v_mfma_f64_16x16x4_f64: 16 x 16 pairs x 4 loci in 32 cycles, twice the
-// FP64 VALU rate, and a lane feeds it ONE double per operand where the VALU form reads 16 doubles for 48 FMAs -- that form
-// is bound by LDS bandwidth: 27 M ds_read_b128 + 40 M conflict cycles against 1.32 M cycles per launch at 51 populations).
+// The three products run on the FP64 matrix cores (v_mfma_f64_16x16x4_f64: 16 x 16 pairs x 4 loci in 32 cycles, twice the
+// FP64 VALU rate, and a lane feeds it ONE double per operand where a VALU form read 16 doubles for 48 FMAs -- that form
+// was bound by LDS bandwidth: 27 M ds_read_b128 + 40 M conflict cycles against 1.32 M cycles per launch at 51 populations).
 // A wave owns 16 row populations x all 64 column populations: 4 column tiles x 3 products = 12 accumulators, per 4 loci
 // 2 + 8 ds_read_b64 and 12 MFMAs.  Rows of the staged arrays are FSTG_RS = 80 doubles apart (32 dwords modulo the 64
 // banks), so that the four loci a wave instruction reads fall on disjoint banks.
 #define FSTG_RS_MFMA 80
-template <bool MF>
 __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, int64_t m, int G, int ntile, int kmax,
                                                                   double* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  constexpr int RS = MF ? FSTG_RS_MFMA : FSTG_T;  // row stride of the staged arrays
+  constexpr int RS = FSTG_RS_MFMA;  // row stride of the staged arrays
   double* ra = sh;                      // [l][RS] a of the row populations
   double* rc = sh + FSTG_LB * RS;       // c of the row populations
   double* cb = sh + 2 * FSTG_LB * RS;   // b of the column populations
@@ -279,13 +278,7 @@ __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, in
   // by-locus path, which must be bit-identical to the reference, divides)
   double* inv = sh + 4 * FSTG_LB * RS;
   for (int A = threadIdx.x; A <= kmax; A += 256) { inv[2 * A] = 1.0 / (double)A; inv[2 * A + 1] = 1.0 / ((double)A - 1.0); }
-  // thread grid TG x TG of 4 x 4 blocks, TG = populations of this tile / 4 rounded up: with 51 populations 13 x 13 = 169
-  // threads work (three waves) instead of 256 on a padded 64 x 64 tile
-  const int gR = min(FSTG_T, G - tR * FSTG_T), gC = min(FSTG_T, G - tC * FSTG_T);
-  const int TGy = (gR + 3) / 4, TGx = (gC + 3) / 4;
-  const bool work = MF || (int)threadIdx.x < TGy * TGx;
-  const int ty = work ? threadIdx.x / TGx : 0, tx = work ? threadIdx.x % TGx : 0;
-  double AB[4][4], CB[4][4], CC[4][4];  // VALU form: a 4 x 4 block of pairs; MFMA form: [column tile][C/D register]
+  double AB[4][4], CB[4][4], CC[4][4];  // [column tile][C/D register]
 #pragma unroll
   for (int r = 0; r < 4; r++)
 #pragma unroll
@@ -361,58 +354,29 @@ __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, in
     }
     __syncthreads();
     if (kmax > 0) fetch(ch + gridDim.x);
-    if constexpr (MF) {
-      // A = x[locus l + kq][row population 16 wv + r16], B = y[locus l + kq][column population 16 ct + r16]
+    // A = x[locus l + kq][row population 16 wv + r16], B = y[locus l + kq][column population 16 ct + r16]
 #pragma unroll
-      for (int l = 0; l < FSTG_LB; l += 4) {
-        const double av = ra[(l + kq) * RS + 16 * wv + r16], cv = rc[(l + kq) * RS + 16 * wv + r16];
+    for (int l = 0; l < FSTG_LB; l += 4) {
+      const double av = ra[(l + kq) * RS + 16 * wv + r16], cv = rc[(l + kq) * RS + 16 * wv + r16];
 #pragma unroll
-        for (int ct = 0; ct < 4; ct++) {
-          const double bv = cb[(l + kq) * RS + 16 * ct + r16], dv = cc[(l + kq) * RS + 16 * ct + r16];
-          *(v4d*)AB[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, *(v4d*)AB[ct], 0, 0, 0);
-          *(v4d*)CB[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, bv, *(v4d*)CB[ct], 0, 0, 0);
-          *(v4d*)CC[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, dv, *(v4d*)CC[ct], 0, 0, 0);
-        }
-      }
-    } else if (work) {
-#pragma unroll 2
-      for (int l = 0; l < FSTG_LB; l++) {
-        const v4d a4 = *(const v4d*)&ra[l * FSTG_T + 4 * ty], c4 = *(const v4d*)&rc[l * FSTG_T + 4 * ty];
-        const v4d b4 = *(const v4d*)&cb[l * FSTG_T + 4 * tx], d4 = *(const v4d*)&cc[l * FSTG_T + 4 * tx];
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-          for (int c = 0; c < 4; c++) {
-            AB[r][c] = fma(a4[r], b4[c], AB[r][c]);
-            CB[r][c] = fma(c4[r], b4[c], CB[r][c]);
-            CC[r][c] = fma(c4[r], d4[c], CC[r][c]);
-          }
+      for (int ct = 0; ct < 4; ct++) {
+        const double bv = cb[(l + kq) * RS + 16 * ct + r16], dv = cc[(l + kq) * RS + 16 * ct + r16];
+        *(v4d*)AB[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, *(v4d*)AB[ct], 0, 0, 0);
+        *(v4d*)CB[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, bv, *(v4d*)CB[ct], 0, 0, 0);
+        *(v4d*)CC[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, dv, *(v4d*)CC[ct], 0, 0, 0);
       }
     }
   }
-  // partial sums of this workgroup: [block x][tile][product][row][col]
-  if (!work) return;
+  // partial sums of this workgroup: [block x][tile][product][row][col]; C/D: column = lane & 15, row = (lane >> 4) + 4 reg
   double* o = part + (((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * 3) * FSTG_T * FSTG_T;
-  if constexpr (MF) {  // C/D: column = lane & 15, row = (lane >> 4) + 4 reg
 #pragma unroll
-    for (int ct = 0; ct < 4; ct++)
+  for (int ct = 0; ct < 4; ct++)
 #pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        const int q = (16 * wv + kq + 4 * reg) * FSTG_T + 16 * ct + r16;
-        o[q] = AB[ct][reg];
-        o[FSTG_T * FSTG_T + q] = CB[ct][reg];
-        o[2 * FSTG_T * FSTG_T + q] = CC[ct][reg];
-      }
-    return;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r++)
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int q = (4 * ty + r) * FSTG_T + 4 * tx + c;
-      o[q] = AB[r][c];
-      o[FSTG_T * FSTG_T + q] = CB[r][c];
-      o[2 * FSTG_T * FSTG_T + q] = CC[r][c];
+    for (int reg = 0; reg < 4; reg++) {
+      const int q = (16 * wv + kq + 4 * reg) * FSTG_T + 16 * ct + r16;
+      o[q] = AB[ct][reg];
+      o[FSTG_T * FSTG_T + q] = CB[ct][reg];
+      o[2 * FSTG_T * FSTG_T + q] = CC[ct][reg];
     }
 }
 
@@ -790,18 +754,10 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
     double* d_full = d_gp + (size_t)cells * (size_t)nbx;
     // reciprocals by table when the source is the class counts of diploids and the table fits (kmax valid alleles at most)
     const int kq = (src.cnt && !src.has_hap && kmax > 0 && kmax <= 4096) ? kmax : 0;
-    // TPG_FST_HUDSON_VALU=1: the three products on the FP64 VALU (A/B; rounds 3 and 4)
-    static const bool valu = getenv("TPG_FST_HUDSON_VALU") && atoi(getenv("TPG_FST_HUDSON_VALU")) != 0;
-    const size_t shg = sizeof(double) * (4 * FSTG_LB * (valu ? FSTG_T : FSTG_RS_MFMA) + 2 * ((size_t)kq + 1));
-    if (valu) {
-      (void)hipFuncSetAttribute((const void*)tpg_fst_hudson_gemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shg);
-      TPG_LAUNCH(ctx, "fst_hudson", tpg_fst_hudson_gemm_kernel<false>, dim3((unsigned)nbx, (unsigned)(ntile * ntile)), dim3(256), shg,
-                 src, m, G, ntile, kq, d_gp);
-    } else {
-      (void)hipFuncSetAttribute((const void*)tpg_fst_hudson_gemm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shg);
-      TPG_LAUNCH(ctx, "fst_hudson", tpg_fst_hudson_gemm_kernel<true>, dim3((unsigned)nbx, (unsigned)(ntile * ntile)), dim3(256), shg,
-                 src, m, G, ntile, kq, d_gp);
-    }
+    const size_t shg = sizeof(double) * (4 * FSTG_LB * FSTG_RS_MFMA + 2 * ((size_t)kq + 1));
+    (void)hipFuncSetAttribute((const void*)tpg_fst_hudson_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shg);
+    TPG_LAUNCH(ctx, "fst_hudson", tpg_fst_hudson_gemm_kernel, dim3((unsigned)nbx, (unsigned)(ntile * ntile)), dim3(256), shg,
+               src, m, G, ntile, kq, d_gp);
     TPG_LAUNCH(ctx, "fst_reduce", tpg_fst_hudson_gemm_reduce_kernel, dim3((unsigned)ceil_div(cells, 256), FSTG_SL), dim3(256), 0,
                (const double*)d_gp, nbx, cells, d_full);
     TPG_LAUNCH(ctx, "fst_reduce", tpg_fst_hudson_gemm_final_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, (const double*)d_full,
@@ -837,7 +793,7 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
     const int nbt = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (int64_t)nblocks));
     dim3 grid((unsigned)nbt, (unsigned)ypass);
     // many pairs: a thread takes a tile of populations (tpg_fst_wc84_tile_kernel); TPG_FST_TILES=0: 8 unrelated pairs (A/B)
-    static const bool no_tiles = getenv("TPG_FST_TILES") && atoi(getenv("TPG_FST_TILES")) == 0;
+    static const bool no_tiles = tpg_env_int("TPG_FST_TILES", 1) == 0;
     InBuf tb;
     int ntask = 0;
     const bool tiles = ppt == 8 && !no_tiles && G <= 64 && kmax <= FSTT_KMAX && lb_tab == FSTT_LB;

@@ -85,55 +85,6 @@ __device__ __forceinline__ int tpg_gcls_find_run(const uint32_t* __restrict__ st
   return lo;
 }
 
-// Groups of neighbouring classes (the mixed-precision fold, see tpg_gcls_block_table2_kernel) for the one-wave-per-SIMD
-// kernel: a group must END on a multiple of `body` blocks, so that its FP64 fold only ever falls between two bodies of the
-// kernel's unrolled loop.  Group ends are a property of the classes alone (key prefix, position in the run of classes), so
-// every group starts on a multiple of `body` if all before it do, and the padding of a group is its own size rounded up:
-// the last class of every group gets the extra (empty) blocks.  sblk[r] = blocks reserved for class r, ge[r] = last of its group.
-__global__ void tpg_gcls_group_pad_kernel(const unsigned long long* __restrict__ ukeys, const int* __restrict__ nruns, int64_t m,
-                                          const uint32_t* __restrict__ nblk, int gmax, int gq, int body,
-                                          uint32_t* __restrict__ sblk, uint8_t* __restrict__ ge) {
-  const int nr = nruns[0];
-  auto group_end = [&](int r) {
-    return r == nr - 1 || (ukeys[r] >> (52 - gq)) != (ukeys[r + 1] >> (52 - gq)) || (r % gmax) == gmax - 1;
-  };
-  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < m; r += (int64_t)gridDim.x * blockDim.x) {
-    if (r >= nr) { sblk[r] = 0; ge[r] = 0; continue; }
-    const bool e = group_end((int)r);
-    uint32_t tot = nblk[r];
-    if (e && body > 1) {
-      for (int q = (int)r - 1; q >= 0 && !group_end(q); q--) tot += nblk[q];  // at most gmax classes
-      sblk[r] = nblk[r] + (uint32_t)((body - (int)(tot % (uint32_t)body)) % body);
-    } else {
-      sblk[r] = nblk[r];
-    }
-    ge[r] = e ? 1 : 0;
-  }
-}
-
-// Block table of tpg_gcls_gram1w_kernel over the padded layout: entry as in tpg_gcls_block_table2_kernel (x = weight | flags,
-// y = bits of (float)(w_c - w_{c+1})); flag 1 = last block of a class that is not the last of its group; flag 2 = FP64 fold
-// after this block -- the last (possibly empty) block of a group, or a block whose index is GCLS3_GRUN - 1 modulo GCLS3_GRUN
-// (integer sums stay exact: 4 * 64 * 16 320 < 2^23): always the last block of a body, GCLS3_GRUN being a multiple of 8, 10, 12.
-#define GCLS3_GRUN 16320
-__global__ void tpg_gcls_block_table3_kernel(const unsigned long long* __restrict__ ukeys, const uint32_t* __restrict__ blk_start,
-                                             const uint32_t* __restrict__ nblk, const uint32_t* __restrict__ sblk,
-                                             const uint8_t* __restrict__ ge, int nr, int64_t nblocks, ulonglong2* __restrict__ wblk) {
-  for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < nblocks; b += (int64_t)gridDim.x * blockDim.x) {
-    const int r = tpg_gcls_find_run(blk_start, nr, (uint32_t)b);
-    const uint32_t o = (uint32_t)b - blk_start[r];
-    const bool full = (ge[r] && o + 1 == sblk[r]) || (b % GCLS3_GRUN) == GCLS3_GRUN - 1;
-    const bool class_end = !ge[r] && o + 1 == nblk[r];
-    ulonglong2 e;
-    e.x = ukeys[r] | (full ? 2ull : class_end ? 1ull : 0ull);
-    e.y = 0;
-    if (class_end && !full)
-      e.y = (unsigned long long)__float_as_uint(
-          (float)(__longlong_as_double((long long)ukeys[r]) - __longlong_as_double((long long)ukeys[r + 1])));
-    wblk[b] = e;
-  }
-}
-
 __global__ void tpg_gcls_totals_kernel(const int* __restrict__ nruns, const uint32_t* __restrict__ blk_start,
                                        const uint32_t* __restrict__ nblk, long long* __restrict__ totals) {
   const int nr = nruns[0];
@@ -222,7 +173,7 @@ struct GclsSrc {
   int64_t sb, sq, sh1;
 };
 
-// CEN (tpg_gcls_gram2_kernel<VT, true> only): a source dword packs the codes of BOTH blocks of the pair -- low two bits of
+// CEN (tpg_gcls_gram2_kernel<true> only): a source dword packs the codes of BOTH blocks of the pair -- low two bits of
 // a nibble: the dosage code of a locus of block 2 bp, as before (P & 0x33333333 = FP4 dosage / 2); high two bits: a locus
 // of block 2 bp + 1 as its CENTRED dosage g - 1, coded 3 / 0 / 1 so that P & 0xCCCCCCCC is the FP4 value -2 / 0 / +2 -- and
 // the kernel makes an operand word with ONE v_and_b32 instead of a shift and an AND (4 instead of 6 VALU per MFMA).  A
@@ -532,7 +483,8 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 #ifndef GCLS2_D
 #define GCLS2_D 2
 #endif
-// VT: the block table through one vector load per loop body + v_readlane_b32 instead of one scalar load per block (see 3c)
+// The block table comes through one vector load per loop body + v_readlane_b32, not one scalar load per block (scalar loads
+// return out of order, so each use is an s_waitcnt lgkmcnt(0)).
 // The scalar stream of the loop is kept LEAN on purpose.  Two experiments (operand loads removed: 10.4 -> 8.75 ms; class-end
 // and fold flags ignored: 10.3 -> 7.8 ms; neither leaves less than 2.4 x the MFMA time) said that what the waves wait for is
 // mostly their OWN instruction stream: a wave issues one instruction per four cycles, whatever its kind, and per block (4 MFMAs
@@ -548,7 +500,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // pair takes the high halves of the nibbles, values +-2, with the block scales 2^-1 where the even block has 2^+1)
 #define MFMA_G4S2_ODD(a, b, c) \
   __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(tpg_g8(a), tpg_g8(b), (c), 4, 4, 0, (int)0x7E7E7E7E, 0, (int)0x7E7E7E7E)
-template <bool VT, bool CEN = false>
+template <bool CEN>
 __global__ __launch_bounds__(256, 2) void tpg_gcls_gram2_kernel(const uint4* __restrict__ T2g, int64_t nblocks, int64_t rs2, int nrtv,
                                                                 const ulonglong2* __restrict__ wblk,
                                                                 const int2* __restrict__ order, int64_t nun, int S,
@@ -613,28 +565,24 @@ __global__ __launch_bounds__(256, 2) void tpg_gcls_gram2_kernel(const uint4* __r
       });
       int st = 0;  // 2: the class end before this block is still to be folded
       float pdelta = 0.f;
-      ulonglong2 wf_next = wblk[2 * p0];
       const unsigned long long wlast = wblk[bl].x;  // for the fold after the loop
       typedef uint32_t v3u __attribute__((ext_vector_type(3)));
       auto LDT = [&](int first_block) {  // lane l: the table entry of block first_block + l (three dwords: x, low half of y)
         const int bb = first_block + lane;
         return *(const v3u*)(wblk + (bb < bl ? bb : bl));
       };
-      v3u TB = {0, 0, 0};
-      if constexpr (VT) TB = LDT(2 * p0);
+      v3u TB = LDT(2 * p0);
       uint32_t tx0[2 * GCLS2_D], tx1[2 * GCLS2_D], ty0[2 * GCLS2_D];
       for (int pp = p0; pp < p1; pp += GCLS2_D) {
-        if constexpr (VT) {
 #pragma unroll
-          for (int k = 0; k < 2 * GCLS2_D; k++) {
-            tx0[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[0], k);
-            tx1[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[1], k);
-            ty0[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[2], k);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          TB = LDT(2 * (pp + GCLS2_D));
-          __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < 2 * GCLS2_D; k++) {
+          tx0[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[0], k);
+          tx1[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[1], k);
+          ty0[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[2], k);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        TB = LDT(2 * (pp + GCLS2_D));
+        __builtin_amdgcn_sched_barrier(0);
         tpg_static_for<GCLS2_D>([&](auto cc) {
           constexpr int C = decltype(cc)::value, M = (C + GCLS2_D - 1) % GCLS2_D;
           const int pr = pp + C;
@@ -643,16 +591,10 @@ __global__ __launch_bounds__(256, 2) void tpg_gcls_gram2_kernel(const uint4* __r
           if (pr < p1) {
 #pragma unroll
             for (int hb = 0; hb < 2; hb++) {
-              const int b = 2 * pr + hb;
               {
                 ulonglong2 wf;
-                if constexpr (VT) {
-                  wf.x = ((unsigned long long)tx1[2 * C + hb] << 32) | tx0[2 * C + hb];
-                  wf.y = ty0[2 * C + hb];
-                } else {
-                  wf = wf_next;
-                  wf_next = wblk[b < bl ? b + 1 : bl];
-                }
+                wf.x = ((unsigned long long)tx1[2 * C + hb] << 32) | tx0[2 * C + hb];
+                wf.y = ty0[2 * C + hb];
                 v4u X[GA + GB];
 #pragma unroll
                 for (int t = 0; t < GA + GB; t++) {
@@ -752,205 +694,6 @@ __global__ __launch_bounds__(256, 2) void tpg_gcls_gram2_kernel(const uint4* __r
   }
 }
 
-// 3c. the mixed-precision fold at ONE wave per SIMD (TPG_GRAM_KERNEL=14 / 34; the A/B of DESIGN.md 3.2, not a path anything
-// takes): what two waves per SIMD buy the kernel above is that one wave's loads and folds hide behind the other's MFMAs.
-// Here a wave has the whole register file of its SIMD and nobody to hide behind, so everything is explicit:
-//   * operands go through NS rotating register slots (one 16-byte load per lane = a PAIR of blocks), fetched NS - 1 pairs
-//     ahead of their use; the prologue issues them slot by slot (sched_barrier) so that hipcc's wait-count pass, which merges
-//     the loop entry with the back edge, does not put a vmcnt(0) at the top of every loop body (pairwise.hip);
-//   * group ends fall between two bodies of the unrolled loop by construction (tpg_gcls_group_pad_kernel pads every group to
-//     a multiple of 2 NS blocks), so the FP64 fold exists once, not in every step;
-//   * the FP64 result lives in LDS (32 KiB per wave, 128 KiB per workgroup, one workgroup per CU): touched at group
-//     ends only, and an LDS read-modify-write is cheaper than moving 128 registers through AGPRs;
-//   * the block table comes through ONE vector load per body, issued a body ahead and taken apart into SGPRs
-//     (v_readlane_b32) at the top of the body.  (Scalar loads return out of order, so each use is an s_waitcnt lgkmcnt(0):
-//     with one wave per SIMD a full scalar-load latency per block -- 1 750 cycles per block, 44 ms, measured; a load under a
-//     condition, or a loaded register copied into another, makes hipcc drain every load in flight.)
-//   * the lean scalar stream of the two-waves kernel: 32-bit indices, fixed tile bases in SGPRs + one lane offset that
-//     advances by a pair, no range tests (the padded layout ends on a whole body, T2g has a slack of NS pairs behind it),
-//     flags and class differences in SGPRs; the centred operand layout (CEN);
-//   * IL: a step written tile by tile -- MFMA of tile p, then the operand words of fragment p of the NEXT block (4 v_and_b32)
-//     -- and pinned in that order (sched_barrier + an empty asm on the words: left alone hipcc makes them in the next block,
-//     in front of its four MFMAs, and the pipe idles while the wave issues VALU); the class end of the block before
-//     (32 v_pk_fma_f32) sits in front of the step behind ONE scalar branch, and only `dev` changes behind it -- with the
-//     MFMAs inside two variants of the step hipcc gave each variant its own accumulators, ran BOTH sets of MFMAs and merged
-//     them with 32 v_mov_b64 per block (20.7 ms, 1.65 x the MFMAs by SQ_INSTS_MFMA).
-// Measured at 5 000 x 1 000 000 in one job with the two-waves kernel (9.13 ms): 9.36 ms interleaved, 9.93 ms not, whatever
-// the slots (3 / 4 / 5) and the K split (4 ... 24); round 3's first form of it (100 instructions per block) 12.8 - 13.4.
-// PMC: 7.9 VALU-class instructions per MFMA, the wave issues VALU 55 % of its cycles, waits (vmcnt) 26 %, everything else
-// 19 %; MFMA pipe 42 % busy -- the figure of the two-waves kernel -- L2 hit rate 77 % against 85 % (22.8 GB HBM-side).
-// (The same pipelined kernel at TWO waves per SIMD, its FP64 result half in LDS and half read-modify-written in the unit's
-// slab: 13.9 ms, 60 GB of slab traffic; DESIGN.md 3.2.  Two lessons from it live on as comments in the kernels: an address
-// that went through an integer is FLAT to hipcc unless cast to address_space(1), and ONE flat access in a loop turns every
-// vmcnt wait of the loop into vmcnt(0); 64-bit per-lane addresses get hoisted out of loops and spill.)
-// Slabs and the assemble pass are those of the kernel above; K ranges start on multiples of NS pairs.
-#define GCLS3_LDS_BYTES (4 * GP * 16 * 64 * 8)
-template <int NS, bool CEN, bool IL>
-__global__ __launch_bounds__(256, 1) void tpg_gcls_gram1w_kernel(const uint4* __restrict__ T2g, int64_t nblocks, int64_t rs2, int nrtv,
-                                                                  const ulonglong2* __restrict__ wblk,
-                                                                  const int2* __restrict__ order, int64_t nun, int S,
-                                                                  double* __restrict__ slabs) {
-  extern __shared__ double olds_raw[];  // [wave][tile][register][lane]
-  constexpr int NT = GA + GB, BODY = 2 * NS;
-  static_assert(NT == GP, "a step expands fragment p beside the MFMA of tile p");
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  double* olds = olds_raw + (size_t)wv * (GP * 16 * 64) + lane;
-  const int bx = (int)blockIdx.x, xcd = bx & 7, cidx = bx >> 3, cpx = (int)gridDim.x >> 3;
-  const int nbodies = (int)(nblocks / BODY);  // (the padded layout: every group, so the whole list, ends on a body)
-  typedef __attribute__((address_space(1))) const char gchar;
-  typedef __attribute__((address_space(1))) const v4u gv4u;
-  for (int64_t round = 0;; round++) {
-    const int64_t un = ((round * 8 + xcd) * cpx + cidx) * 4 + wv;
-    if (un >= nun * S) break;
-    const int ks = (int)(un / nun);
-    const int64_t u = un % nun;
-    const int2 ijv = order[u];
-    const int2 ij = make_int2(__builtin_amdgcn_readfirstlane(ijv.x), __builtin_amdgcn_readfirstlane(ijv.y));
-    const int p0 = __builtin_amdgcn_readfirstlane(NS * (int)(((int64_t)nbodies * ks) / S));
-    const int p1 = __builtin_amdgcn_readfirstlane(NS * (int)(((int64_t)nbodies * (ks + 1)) / S));
-    gchar* pt[NT];  // the unit's four row tiles at pair p0
-#pragma unroll
-    for (int t = 0; t < GA; t++) pt[t] = (gchar*)tpg_uniform64((int64_t)(T2g + ((int64_t)min(GA * ij.x + t, nrtv - 1) * rs2 + p0) * 64));
-#pragma unroll
-    for (int t = 0; t < GB; t++) pt[GA + t] = (gchar*)tpg_uniform64((int64_t)(T2g + ((int64_t)min(GB * ij.y + t, nrtv - 1) * rs2 + p0) * 64));
-    v2f dev[GP][8];
-    v16f acc[GP];
-#pragma unroll
-    for (int p = 0; p < GP; p++) {
-#pragma unroll
-      for (int i = 0; i < 16; i++) { acc[p][i] = 0.f; olds[(p * 16 + i) * 64] = 0.0; }
-#pragma unroll
-      for (int i = 0; i < 8; i++) dev[p][i] = v2f{0.f, 0.f};
-    }
-    // out += w * sums + dev; sums and dev start again from zero (four elements at a time: few temporaries)
-    auto fold = [&](double w) {
-#pragma unroll
-      for (int p = 0; p < GP; p++)
-        tpg_static_for<4>([&](auto qq) {
-          constexpr int q = decltype(qq)::value;
-          double t[4];
-#pragma unroll
-          for (int e = 0; e < 4; e++) t[e] = olds[(p * 16 + 4 * q + e) * 64];
-#pragma unroll
-          for (int e = 0; e < 4; e++) {
-            const int i = 4 * q + e;
-            olds[(p * 16 + i) * 64] = __builtin_fma((double)acc[p][i], w, t[e]) + (double)dev[p][i >> 1][i & 1];
-            acc[p][i] = 0.f;
-          }
-          dev[p][2 * q] = v2f{0.f, 0.f};
-          dev[p][2 * q + 1] = v2f{0.f, 0.f};
-          __builtin_amdgcn_sched_barrier(0);
-        });
-    };
-    if (p0 < p1) {
-      v4u R[NS][NT];
-      uint32_t voff = (uint32_t)lane * 16u;  // this lane's 16 bytes of the NEXT pair to fetch, relative to pair p0
-      auto LDP = [&](v4u (&slot)[NT]) {
-#pragma unroll
-        for (int t = 0; t < NT; t++) slot[t] = *(gv4u*)(pt[t] + voff);
-        voff += 1024u;
-      };
-      // lane l: the table entry of block first + l (three dwords: with a fourth, dead, register in the tuple hipcc parks the loads' lane offset in it and waits for the table load)
-      typedef uint32_t v3u __attribute__((ext_vector_type(3)));
-      typedef __attribute__((address_space(1))) const v3u gv3u;
-      const uint32_t blast = (uint32_t)(nblocks - 1);
-      gchar* const wb = (gchar*)tpg_uniform64((int64_t)wblk);
-      auto LDT = [&](int first_block) {
-        uint32_t bb = (uint32_t)first_block + (uint32_t)lane;
-        bb = (bb < blast ? bb : blast) * 16u;
-        return *(gv3u*)(wb + bb);
-      };
-      v3u TB = LDT(2 * p0);
-      __builtin_amdgcn_sched_barrier(0);
-      tpg_static_for<NS - 1>([&](auto dd) {
-        LDP(R[decltype(dd)::value]);
-        __builtin_amdgcn_sched_barrier(0);  // slot by slot (see above)
-      });
-      // operand words of one block: half hb of a slot
-      auto expand = [&](const v4u& r, auto Hh) {
-        constexpr int hb = decltype(Hh)::value;
-        if constexpr (CEN) {
-          return r & (hb == 0 ? 0x33333333u : 0xCCCCCCCCu);
-        } else {
-          const uint32_t w0 = r[2 * hb], w1 = r[2 * hb + 1];
-          return v4u{w0 & 0x33333333u, (w0 >> 2) & 0x33333333u, w1 & 0x33333333u, (w1 >> 2) & 0x33333333u};
-        }
-      };
-      v4u X[2][NT];
-#pragma unroll
-      for (int t = 0; t < NT; t++) X[0][t] = expand(R[0][t], std::integral_constant<int, 0>{});
-      bool pend = false;   // the block before ended a class inside its group: dev += pdelta * sums before this block's MFMAs
-      float pdelta = 0.f;  // w_c - w_{c+1}
-      uint32_t fl[BODY], dl[BODY], wlo = 0, whi = 0;  // this body's table entries, in SGPRs
-
-      auto step = [&](auto Cc, auto Hh) {
-        constexpr int C = decltype(Cc)::value, hb = decltype(Hh)::value, cur = hb, nx = hb ^ 1;
-        constexpr int M = (C + NS - 1) % NS;                        // the slot the pair before this one left
-        constexpr int SN = hb == 0 ? C : (C + 1) % NS, HN = hb ^ 1;  // slot and half of the NEXT block
-        if constexpr (hb == 0) LDP(R[M]);
-        __builtin_amdgcn_sched_barrier(0);
-        if (pend) {  // (one branch per block, and only `dev` changes behind it: with the MFMAs inside two variants of the step
-                     // hipcc gave each variant its own accumulators and merged them with 32 v_mov_b64 per block)
-          const v2f dlt = v2f{pdelta, pdelta};
-#pragma unroll
-          for (int p = 0; p < GP; p++)
-            tpg_static_for<8>([&](auto ii) {
-              constexpr int i = decltype(ii)::value;
-              dev[p][i] = __builtin_elementwise_fma(dlt, __builtin_shufflevector(acc[p], acc[p], 2 * i, 2 * i + 1), dev[p][i]);
-            });
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        tpg_static_for<GP>([&](auto pp_) {
-          constexpr int p = decltype(pp_)::value;
-          if constexpr (CEN && hb == 1) acc[p] = MFMA_G4S2_ODD(X[cur][p / GB], X[cur][GA + p % GB], acc[p]);
-          else acc[p] = MFMA_G4S2(X[cur][p / GB], X[cur][GA + p % GB], acc[p]);
-          X[nx][p] = expand(R[SN][p], std::integral_constant<int, HN>{});
-          if constexpr (IL) {
-            asm volatile("" : "+v"(X[nx][p]));  // HERE, in the shadow of the MFMA (left alone, the words are made in the next block, where they are used)
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        });
-        pend = (fl[2 * C + hb] & 1u) != 0;
-        pdelta = __uint_as_float(dl[2 * C + hb]);
-      };
-      for (int pp = p0; pp < p1; pp += NS) {
-        // this body's table entries -> SGPRs, then the load of the next body's into the same register
-#pragma unroll
-        for (int k = 0; k < BODY; k++) {
-          fl[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[0], k);
-          dl[k] = (uint32_t)__builtin_amdgcn_readlane((int)TB[2], k);
-        }
-        wlo = fl[BODY - 1];
-        whi = (uint32_t)__builtin_amdgcn_readlane((int)TB[1], BODY - 1);
-        __builtin_amdgcn_sched_barrier(0);
-        TB = LDT(2 * (pp + NS));
-        __builtin_amdgcn_sched_barrier(0);
-        tpg_static_for<NS>([&](auto cc) {
-          step(cc, std::integral_constant<int, 0>{});
-          step(cc, std::integral_constant<int, 1>{});
-        });
-        // a group (or GCLS3_GRUN blocks) ends with this body's last block: the FP64 fold, here and nowhere else
-        if (__builtin_expect((wlo & 2u) != 0 && pp + NS < p1, 0)) {
-          fold(__longlong_as_double((long long)(((uint64_t)whi << 32) | (wlo & ~3u))));
-          pend = false;
-        }
-      }
-      // the end of the range: whatever the sums hold belongs to the class of the last block (a class end pending there is
-      // part of it: with w_c itself no difference is needed)
-      {
-        const ulonglong2 e = wblk[2 * (int64_t)p1 - 1];
-        fold(__longlong_as_double((long long)(e.x & ~3ull)));
-      }
-    }
-    double* slab = slabs + ((int64_t)ks * nun + u) * GCLS_SLAB + lane;
-#pragma unroll
-    for (int p = 0; p < GP; p++)
-#pragma unroll
-      for (int i = 0; i < 16; i++) slab[(p * 16 + i) * 64] = olds[(p * 16 + i) * 64];
-  }
-}
-
 // 4. the S slabs of every unit, added in split order, into both triangles of K (n x n, column-major).  A wave takes one
 // 32 x 32 tile of the unit: it sums the slabs in MFMA register order (512 contiguous bytes per wave and slab), turns the
 // tile through LDS, and writes it twice with 32 lanes on 256 contiguous bytes -- K[i, k] along i and K[k, i] along k.
@@ -1014,8 +757,7 @@ struct GclsBufs {
 // 0.28 against 0.35 ms at 1 000 x 650 000 (949 classes, 10 634 blocks), 12.1 against 11.3 ms at 5 000 x 1 000 000 (4 728
 // classes, 17 888 blocks) -- or when TPG_GRAM_FOLD64 asks for it (TPG_GRAM_FOLD64=0: never).
 static bool gcls_fold64(int64_t nruns, int64_t nblocks) {
-  const char* e = getenv("TPG_GRAM_FOLD64");
-  if (e) return atoi(e) != 0;
+  if (tpg_env_set("TPG_GRAM_FOLD64")) return tpg_env_int("TPG_GRAM_FOLD64", 0) != 0;
   return (double)nruns < 0.15 * (double)nblocks;
 }
 
@@ -1037,7 +779,7 @@ static double gcls_cost_classes(int64_t nunits, int64_t nruns, int64_t nblocks, 
 static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, const GclsSrc& src, const double* d_w, double* d_what,
                              double* d_K, bool force, bool* done, bool centred_ok) {
   *done = false;
-  if (m >= (1ll << 31) - 64 || (getenv("TPG_GRAM_DIGITS") && !force)) return TPG_OK;
+  if (m >= (1ll << 31) - 64 || (tpg_env_set("TPG_GRAM_DIGITS") && !force)) return TPG_OK;
   GclsBufs B;
   unsigned long long *d_key = nullptr, *d_key2 = nullptr, *d_ukeys = nullptr;
   uint32_t *d_idx = nullptr, *d_idx2 = nullptr, *d_counts = nullptr, *d_cnt = nullptr, *d_nblk = nullptr, *d_estart = nullptr,
@@ -1056,18 +798,6 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
   const size_t t_bytes = std::max(t_sort, std::max(t_rle, t_scan));
   TPG_HIP(B.get((uint8_t**)&d_tmp, t_bytes));
   long long totals[2] = {0, 0};
-  // TPG_GRAM_KERNEL=14 / 34: the one-wave-per-SIMD form of the mixed fold (tpg_gcls_gram1w_kernel, four operand slots; 34 =
-  // steps interleaved tile by tile; a measured A/B: 9.9 / 9.4 ms against 9.1): every group of classes is padded to whole bodies
-  // of its unrolled loop.  TPG_GRAM_KERNEL=1: the two-waves kernel with its block table by scalar loads.
-  const int kern3 = getenv("TPG_GRAM_KERNEL") ? atoi(getenv("TPG_GRAM_KERNEL")) : 0;
-  const bool lean_il = kern3 == 34, lean1 = kern3 == 14 || lean_il;
-  const int body = lean1 ? 8 : 0;
-  const bool one_wave = lean1;
-  const int gmax = getenv("TPG_GRAM_GMAX") ? std::max(1, atoi(getenv("TPG_GRAM_GMAX"))) : GCLS_GMAX;
-  const int gq = getenv("TPG_GRAM_GQ") ? std::min(40, std::max(1, atoi(getenv("TPG_GRAM_GQ")))) : GCLS_GQ;
-  uint32_t* d_sblk = nullptr;
-  uint8_t* d_ge = nullptr;
-  TPG_HIP(B.get(&d_sblk, (size_t)m)); TPG_HIP(B.get(&d_ge, (size_t)m));
   {
     ProfScope ps(ctx, "gcls_classes");
     hipLaunchKernelGGL(tpg_gcls_keys_kernel, dim3(1024), dim3(256), 0, ctx->stream, d_w, m, d_key, d_idx);
@@ -1079,13 +809,10 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
                        (const int*)d_nruns, m, d_cnt, d_nblk);
     t = t_bytes;
     TPG_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, t, d_cnt, d_estart, (int)m, ctx->stream));
-    // blocks reserved per class: its own, plus (one-wave kernel) the padding that ends its group on a whole body
-    hipLaunchKernelGGL(tpg_gcls_group_pad_kernel, dim3(1024), dim3(256), 0, ctx->stream, (const unsigned long long*)d_ukeys,
-                       (const int*)d_nruns, m, (const uint32_t*)d_nblk, gmax, gq, body, d_sblk, d_ge);
     t = t_bytes;
-    TPG_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, t, d_sblk, d_bstart, (int)m, ctx->stream));
+    TPG_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, t, d_nblk, d_bstart, (int)m, ctx->stream));
     hipLaunchKernelGGL(tpg_gcls_totals_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int*)d_nruns,
-                       (const uint32_t*)d_bstart, (const uint32_t*)d_sblk, d_totals);
+                       (const uint32_t*)d_bstart, (const uint32_t*)d_nblk, d_totals);
   }
   TPG_HIP(tpg_fetch_small(ctx, totals, d_totals, sizeof(totals)));
   const int64_t nruns = totals[0], nblocks = totals[1];
@@ -1106,12 +833,12 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
   const int64_t nun = (int64_t)order.size();
   int ncu8 = ctx->num_cu / 8 * 8;
   if (ncu8 < 8) ncu8 = 8;
-  const bool f64 = body ? false : gcls_fold64(nruns, nblocks);
-  // the centred operand layout (tpg_gcls_gather_kernel<true>): the default two-waves mixed-fold kernel only, and only where
-  // the caller double-centres the result (the omitted terms are r_i + r_k + const); TPG_GRAM_CENTER=0: never (A/B)
-  static const bool no_cen = getenv("TPG_GRAM_CENTER") && atoi(getenv("TPG_GRAM_CENTER")) == 0;
-  const bool cen = centred_ok && !no_cen && !f64 && (!body || lean1) && kern3 != 1;
-  const int nblk_grid = one_wave ? ncu8 : 2 * ncu8;  // two workgroups per CU = two waves per SIMD
+  const bool f64 = gcls_fold64(nruns, nblocks);
+  // the centred operand layout (tpg_gcls_gather_kernel<true>): the mixed-fold kernel only, and only where the caller
+  // double-centres the result (the omitted terms are r_i + r_k + const); TPG_GRAM_CENTER=0: never (A/B)
+  static const bool no_cen = tpg_env_int("TPG_GRAM_CENTER", 1) == 0;
+  const bool cen = centred_ok && !no_cen && !f64;
+  const int nblk_grid = 2 * ncu8;  // two workgroups per CU = two waves per SIMD
   const int nwaves = 4 * nblk_grid;
   int S = 2;
   // + the sort, the locus-major copy and the gather (1.25 us per 1000 loci at n = 5 000: they scale with n m)
@@ -1121,12 +848,11 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
   // (1.0 us is its four digits of a weight kept to 22 fractional bits; a caller that asks for more bits, pca.hip, pays per digit)
   const int t_dig = std::max(4, ((int)ceil(log2(2.0 * (double)n + 1.0)) + ctx->pca_digit_fbits + 7) / 7);
   const double cost_dig = (double)ceil_div(nun_dig, (int64_t)(4 * ncu8)) * ((double)ceil_div(m, 128) * 0.25 * t_dig) + 65.0;
-  if (getenv("TPG_GRAM_S")) S = std::max(2, atoi(getenv("TPG_GRAM_S")) & ~1);  // (experiments)
   while ((nblocks / 2 + S) / S + 2 >= (1 << 21)) S += 2;  // a K range stays below 2^21 block pairs (32-bit lane offsets)
-  if (getenv("TPG_DEBUG"))
+  if (tpg_env_set("TPG_DEBUG"))
     fprintf(stderr, "[tpg] gram classes: %lld classes, %lld blocks for %lld loci, S = %d, model %.0f us (digits %.0f us)\n",
             (long long)nruns, (long long)nblocks, (long long)m, S, cost_cls, cost_dig);
-  if (cost_cls > cost_dig && !force && !getenv("TPG_GRAM_CLASSES")) return TPG_OK;
+  if (cost_cls > cost_dig && !force && !tpg_env_set("TPG_GRAM_CLASSES")) return TPG_OK;
 
   int32_t* d_src = nullptr;
   double* d_slabs = nullptr;
@@ -1138,7 +864,7 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
   if (f64) TPG_HIP(B.get(&d_wblk, (size_t)nblocks));
   else TPG_HIP(B.get(&d_wblk2, (size_t)nblocks + 4));
   const int64_t rs2 = (nblocks + 1) / 2;  // row-tile stride of T2g: a uint4 per lane and PAIR of blocks
-  TPG_HIP(B.get(&d_T2g, (size_t)(4 * Q) * (size_t)rs2 * 64 + 8 * 64));  // (+ 8 pairs: tpg_gcls_gram1w_kernel fetches NS - 1 pairs past a range)
+  TPG_HIP(B.get(&d_T2g, (size_t)(4 * Q) * (size_t)rs2 * 64));
   TPG_HIP(B.get(&d_order, (size_t)nun));
   TPG_HIP(B.get(&d_slabs, (size_t)S * (size_t)nun * GCLS_SLAB));
   TPG_HIP(tpg_h2d_async(ctx, d_order, order.data(), sizeof(int2) * (size_t)nun));
@@ -1151,13 +877,9 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
     if (f64)
       hipLaunchKernelGGL(tpg_gcls_block_table_kernel, dim3(256), dim3(256), 0, ctx->stream, (const unsigned long long*)d_ukeys,
                          (const uint32_t*)d_bstart, (const uint32_t*)d_nblk, (int)nruns, nblocks, d_wblk);
-    else if (body)
-      hipLaunchKernelGGL(tpg_gcls_block_table3_kernel, dim3(256), dim3(256), 0, ctx->stream, (const unsigned long long*)d_ukeys,
-                         (const uint32_t*)d_bstart, (const uint32_t*)d_nblk, (const uint32_t*)d_sblk, (const uint8_t*)d_ge,
-                         (int)nruns, nblocks, d_wblk2);
     else
       hipLaunchKernelGGL(tpg_gcls_block_table2_kernel, dim3(256), dim3(256), 0, ctx->stream, (const unsigned long long*)d_ukeys,
-                         (const uint32_t*)d_bstart, (const uint32_t*)d_nblk, (int)nruns, nblocks, gmax, gq, d_wblk2);
+                         (const uint32_t*)d_bstart, (const uint32_t*)d_nblk, (int)nruns, nblocks, GCLS_GMAX, GCLS_GQ, d_wblk2);
   }
   {
     const int64_t tasks = Q * rs2;
@@ -1165,7 +887,7 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(tasks, 4), (int64_t)ctx->num_cu * 16);
     // chunks of 128 individuals per task: a lane reads 32 QW contiguous bytes of its locus (0.69 / 0.61 / 0.60 ms for 1 / 2 / 4
     // at 5 000 x 1 000 000: fewer, longer random reads); TPG_GATHER_QW for the comparison
-    const int qw = getenv("TPG_GATHER_QW") ? atoi(getenv("TPG_GATHER_QW")) : Q >= 4 ? 4 : Q >= 2 ? 2 : 1;
+    const int qw = tpg_env_int("TPG_GATHER_QW", Q >= 4 ? 4 : Q >= 2 ? 2 : 1);
 #define GATHER_GO(C, W) TPG_LAUNCH(ctx, "gcls_gather", (tpg_gcls_gather_kernel<C, W>), dim3(grid), dim3(256), 0, src, Q, (const int32_t*)d_src, nblocks, rs2, d_T2g)
     if (cen) { if (qw == 4) GATHER_GO(true, 4); else if (qw == 2) GATHER_GO(true, 2); else GATHER_GO(true, 1); }
     else { if (qw == 4) GATHER_GO(false, 4); else if (qw == 2) GATHER_GO(false, 2); else GATHER_GO(false, 1); }
@@ -1174,33 +896,14 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
   if (f64)
     TPG_LAUNCH(ctx, "pca_gram_classes", tpg_gcls_gram_kernel, dim3((unsigned)nblk_grid), dim3(256), 0, (const uint4*)d_T2g, nblocks,
                rs2, nrtv, (const unsigned long long*)d_wblk, (const int2*)d_order, nun, S, d_slabs);
-  else if (body) {
-    auto launch1 = [&](auto ns, auto cn, auto il) {
-      constexpr int NS = decltype(ns)::value;
-      constexpr bool CN = decltype(cn)::value, IL = decltype(il)::value;
-      (void)hipFuncSetAttribute((const void*)tpg_gcls_gram1w_kernel<NS, CN, IL>, hipFuncAttributeMaxDynamicSharedMemorySize, GCLS3_LDS_BYTES);
-      TPG_LAUNCH(ctx, "pca_gram_classes", (tpg_gcls_gram1w_kernel<NS, CN, IL>), dim3((unsigned)nblk_grid), dim3(256), GCLS3_LDS_BYTES,
-                 (const uint4*)d_T2g, nblocks, rs2, nrtv, (const ulonglong2*)d_wblk2, (const int2*)d_order, nun, S, d_slabs);
-    };
-    TPG_REQUIRE(nblocks % body == 0, TPG_EHIP, "class layout does not end on a body");
-    const std::integral_constant<int, 4> ns;
-    if (cen) { if (lean_il) launch1(ns, std::true_type{}, std::true_type{}); else launch1(ns, std::true_type{}, std::false_type{}); }
-    else { if (lean_il) launch1(ns, std::false_type{}, std::true_type{}); else launch1(ns, std::false_type{}, std::false_type{}); }
+  else if (cen) {
+    (void)hipFuncSetAttribute((const void*)tpg_gcls_gram2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GCLS2_LDS_BYTES);
+    TPG_LAUNCH(ctx, "pca_gram_classes", tpg_gcls_gram2_kernel<true>, dim3((unsigned)nblk_grid), dim3(256), GCLS2_LDS_BYTES,
+               (const uint4*)d_T2g, nblocks, rs2, nrtv, (const ulonglong2*)d_wblk2, (const int2*)d_order, nun, S, d_slabs);
   } else {
-    // TPG_GRAM_KERNEL=1: the block table by scalar loads, one per block (rounds 2 and 3; A/B)
-    if (kern3 == 1) {
-      (void)hipFuncSetAttribute((const void*)tpg_gcls_gram2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GCLS2_LDS_BYTES);
-      TPG_LAUNCH(ctx, "pca_gram_classes", tpg_gcls_gram2_kernel<false>, dim3((unsigned)nblk_grid), dim3(256), GCLS2_LDS_BYTES,
-                 (const uint4*)d_T2g, nblocks, rs2, nrtv, (const ulonglong2*)d_wblk2, (const int2*)d_order, nun, S, d_slabs);
-    } else if (cen) {
-      (void)hipFuncSetAttribute((const void*)tpg_gcls_gram2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GCLS2_LDS_BYTES);
-      TPG_LAUNCH(ctx, "pca_gram_classes", (tpg_gcls_gram2_kernel<true, true>), dim3((unsigned)nblk_grid), dim3(256), GCLS2_LDS_BYTES,
-                 (const uint4*)d_T2g, nblocks, rs2, nrtv, (const ulonglong2*)d_wblk2, (const int2*)d_order, nun, S, d_slabs);
-    } else {
-      (void)hipFuncSetAttribute((const void*)tpg_gcls_gram2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GCLS2_LDS_BYTES);
-      TPG_LAUNCH(ctx, "pca_gram_classes", tpg_gcls_gram2_kernel<true>, dim3((unsigned)nblk_grid), dim3(256), GCLS2_LDS_BYTES,
-                 (const uint4*)d_T2g, nblocks, rs2, nrtv, (const ulonglong2*)d_wblk2, (const int2*)d_order, nun, S, d_slabs);
-    }
+    (void)hipFuncSetAttribute((const void*)tpg_gcls_gram2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GCLS2_LDS_BYTES);
+    TPG_LAUNCH(ctx, "pca_gram_classes", tpg_gcls_gram2_kernel<false>, dim3((unsigned)nblk_grid), dim3(256), GCLS2_LDS_BYTES,
+               (const uint4*)d_T2g, nblocks, rs2, nrtv, (const ulonglong2*)d_wblk2, (const int2*)d_order, nun, S, d_slabs);
   }
   TPG_LAUNCH(ctx, "gcls_assemble", tpg_gcls_assemble_kernel, dim3((unsigned)std::min<int64_t>(nun, 4096)), dim3(256), 0,
              (const double*)d_slabs, (const int2*)d_order, nun, S, (int)n, d_K);
@@ -1233,7 +936,7 @@ __global__ __launch_bounds__(256) void tpg_gcls_l2lm_kernel(const uint4* __restr
 int tpg_gram_classes(tpg_ctx* ctx, const tpg_view* v, const double* d_w, double* d_what, double* d_K, bool* done,
                      bool centred_ok) {
   *done = false;
-  if (getenv("TPG_GRAM_DIGITS")) return TPG_OK;
+  if (tpg_env_set("TPG_GRAM_DIGITS")) return TPG_OK;
   const int64_t n_lt = 4 * v->KG;
   uint4* d_LM = nullptr;
   TPG_HIP(tpg_pmalloc((void**)&d_LM, sizeof(uint4) * (size_t)n_lt * 32 * (size_t)v->Q * 2));
@@ -1313,7 +1016,7 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
   *done = false;
   const int R = comm->nranks, me = comm->rank;
   const int64_t n = v->n, m = v->m, Q = v->Q;
-  if (R < 2 || R > 255 || n >= (1 << 30) || getenv("TPG_GRAM_NO_EXCHANGE")) return TPG_OK;
+  if (R < 2 || R > 255 || n >= (1 << 30) || tpg_env_set("TPG_GRAM_NO_EXCHANGE")) return TPG_OK;
   GclsBufs B;
   int32_t *d_key = nullptr, *d_hist = nullptr, *d_perdest = nullptr;
   uint8_t* d_owner = nullptr;
@@ -1363,10 +1066,10 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
   const double shard_blocks = (double)blocks_all / R + (double)runs_all;  // a shard pads every class to a block of its own
   const double t_cls_local = units / waves * 4.0 * ((double)runs_all * 0.136 + shard_blocks * 0.079) + 650.0;
   const double t_dig_local = ((double)nrtv * nrtv / 8.0 + nrtv) / (waves / 2.0) * ((double)m_all / R / 128.0) + 65.0;
-  if (getenv("TPG_DEBUG") && me == 0)
+  if (tpg_env_set("TPG_DEBUG") && me == 0)
     fprintf(stderr, "[tpg] gram exchange: %lld loci, %lld classes, %lld blocks over %d ranks: model %.0f us (local classes %.0f, digits %.0f)\n",
             (long long)m_all, (long long)runs_all, (long long)blocks_all, R, t_exch, t_cls_local, t_dig_local);
-  if (t_exch > std::min(t_cls_local, t_dig_local) && !getenv("TPG_GRAM_EXCHANGE")) return TPG_OK;
+  if (t_exch > std::min(t_cls_local, t_dig_local) && !tpg_env_set("TPG_GRAM_EXCHANGE")) return TPG_OK;
 
   // contiguous key ranges of (nearly) equal cost
   std::vector<uint8_t> owner((size_t)n + 1, (uint8_t)(R - 1));

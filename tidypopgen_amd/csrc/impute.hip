@@ -257,10 +257,8 @@ extern "C" int tpg_fbm_impute_simple_at(tpg_ctx* ctx, tpg_fbm* fbm, int64_t col0
   // TPG_IMPUTE_WPL = 1 | 4 | 16 forces the shape (tools/impute_only.py measures the crossover)
   const int64_t pieces = (fbm->nrow + 30) / 16;
   int wpl = pieces <= IMP_PMAX * 64 ? 1 : pieces <= IMP_PMAX * 256 ? 4 : 16;
-  if (const char* e = getenv("TPG_IMPUTE_WPL")) {
-    const int w = atoi(e);
-    if (w == 1 || w == 4 || w == 16) wpl = w;
-  }
+  const int w = tpg_env_int("TPG_IMPUTE_WPL", 0);
+  if (w == 1 || w == 4 || w == 16) wpl = w;
   const bool res = pieces <= (int64_t)IMP_PMAX * 64 * wpl;
   int32_t* d_stat = nullptr;  // per locus: entries filled, or IMP_ALL_MISSING / IMP_REFUSED; then the report's three sums
   const size_t stat_bytes = (4 * (size_t)fbm->ncol + 31) & ~(size_t)31;

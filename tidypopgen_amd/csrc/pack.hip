@@ -437,13 +437,13 @@ int tpg_launch_pack(tpg_ctx* ctx, const tpg_fbm* fbm, const int32_t* d_rows, con
   TPG_REQUIRE(v->KG < 2147483647ll && v->Q <= 65535, TPG_EINVAL, "view too large for the pack grid");
   dim3 grid((unsigned)v->KG, (unsigned)v->Q);
   const bool fast_bytes = fbm->bed_bpl == 0 && (fbm->nrow & 7) == 0 && (((uintptr_t)fbm->d_bytes) & 7) == 0;
-  const bool fast_bed = fbm->bed_bpl > 0 && !(getenv("TPG_PACK_BED_GENERIC") && atoi(getenv("TPG_PACK_BED_GENERIC")) != 0);  // (A/B)
-  if ((fast_bytes || fast_bed) && d_rows == nullptr && !getenv("TPG_PACK_GENERIC")) {
+  const bool fast_bed = fbm->bed_bpl > 0 && tpg_env_int("TPG_PACK_BED_GENERIC", 0) == 0;  // (A/B)
+  if ((fast_bytes || fast_bed) && d_rows == nullptr && !tpg_env_set("TPG_PACK_GENERIC")) {
     TPG_REQUIRE((v->KG + 8) * v->Q < 2147483647ll, TPG_EINVAL, "view too large for the pack grid");
-    const int xmap = getenv("TPG_PACK_XCD") ? atoi(getenv("TPG_PACK_XCD")) : 1;
+    const int xmap = tpg_env_int("TPG_PACK_XCD", 1);
     const dim3 g1((unsigned)((xmap ? (v->KG + 7) / 8 * 8 : v->KG) * ((v->Q + PACK_NSUB - 1) / PACK_NSUB)));
     // per-chunk genotype counts beside the layouts (tpg_view::lc_part; TPG_PACK_COUNTS=0: not, the counts kernel reads L)
-    static const bool counts_on = !(getenv("TPG_PACK_COUNTS") && atoi(getenv("TPG_PACK_COUNTS")) == 0);
+    static const bool counts_on = tpg_env_int("TPG_PACK_COUNTS", 1) != 0;
     const int64_t qb = (v->Q + PACK_NSUB - 1) / PACK_NSUB;
     static_assert(PACK_NSUB * 8 * 16 < 1024, "a 10-bit field holds the counts of a chunk: NSUB x 8 threads x 16 individuals");
     if (counts_on)

@@ -336,9 +336,7 @@ __device__ __forceinline__ void tpg_unrolled_steps(F& step, int kb, std::integer
   (step(std::integral_constant<int, Ss>{}, kb + Ss), ...);
 }
 
-// DBG (timing experiments only, wrong sums; TPG_PW_VARIANT=21 / 22): 1 = the loads of the loop removed (the slots keep what the
-// prologue fetched), 2 = the plane masks of the loop removed as well (the MFMAs run on the first block's planes)
-template <int RA, int RB, int MASK, int NS, int DBG = 0>
+template <int RA, int RB, int MASK, int NS>
 __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* __restrict__ T4, int64_t KG,
                                                                      int64_t kb_begin, int64_t kb_end, int nst, int nct,
                                                                      const int2* __restrict__ order, int64_t nun, int S,
@@ -399,20 +397,17 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
       }
       Frag3 P[2][NT];
 #pragma unroll
-      for (int t = 0; t < NT; t++) {
-        P[0][t] = tpg_planes_of<MASK>(R[0][t], TPG_NIB_V, TPG_NIB_D, TPG_NIB_H);
-        if constexpr (DBG == 2) P[1][t] = tpg_planes_of<MASK>(R[1][t], TPG_NIB_V, TPG_NIB_D, TPG_NIB_H);
-      }
+      for (int t = 0; t < NT; t++) P[0][t] = tpg_planes_of<MASK>(R[0][t], TPG_NIB_V, TPG_NIB_D, TPG_NIB_H);
       auto step = [&](auto Sc, int kb) {
         constexpr int s = decltype(Sc)::value, cur = s & 1, nx = cur ^ 1, sl = (s + 1) % NS, ld = (s + NS - 1) % NS;
         // the slot whose planes were taken in the previous step is free: block kb + NS - 1
-        if constexpr (DBG == 0) LDB(R[ld], kb + NS - 1 < kb1 ? kb + NS - 1 : kl);
+        LDB(R[ld], kb + NS - 1 < kb1 ? kb + NS - 1 : kl);
         // planes of the next block (zero A planes past the K range: the tail of the last unrolled body adds nothing)
         const bool live1 = kb + 1 < kb1;
 #pragma unroll
         for (int t = 0; t < NT; t++) {
           const bool keep = t >= RA || live1;
-          if constexpr (DBG < 2) P[nx][t] = tpg_planes_of<MASK>(R[sl][t], keep ? TPG_NIB_V : 0u, keep ? TPG_NIB_D : 0u, keep ? TPG_NIB_H : 0u);
+          P[nx][t] = tpg_planes_of<MASK>(R[sl][t], keep ? TPG_NIB_V : 0u, keep ? TPG_NIB_D : 0u, keep ? TPG_NIB_H : 0u);
         }
 #pragma unroll
         for (int a = 0; a < RA; a++)
@@ -489,9 +484,7 @@ __device__ __forceinline__ void tpg_static_for(F&& f) {
 constexpr int tpg_waitcnt_vm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | (((n >> 4) & 3) << 14); }
 #define SGB_DS_READ 0x100
 
-// DBGW (timing experiments only, wrong sums; TPG_PW_VARIANT=24 / 25 / 26): 1 = no barrier inside the steps, 2 = neither the barrier
-// nor the LDS-DMA of the steps (the ring keeps what the prologue fetched), 3 = the barrier kept, the LDS-DMA of the steps removed
-template <int RA, int RB, int MASK, int NST, int DBGW = 0>
+template <int RA, int RB, int MASK, int NST>
 __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __restrict__ T4, int64_t KG, int64_t kb_begin,
                                                                     int64_t kb_end, int nst, int nct, const int2* __restrict__ order,
                                                                     int64_t nun, int S, const int64_t* __restrict__ rowpad,
@@ -594,9 +587,9 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
         constexpr int s = decltype(Sc)::value, cur = decltype(Cc)::value, nx = cur ^ 1, s2 = (s + 2) % NST;
         // my pieces of block kb + 2 have landed (younger DMAs: blocks kb + 3 .. kb + NST - 1); behind the barrier everybody's
         // have, and everybody has read block kb (two steps ago): its stage takes block kb + NST
-        if constexpr (DBGW == 0 || DBGW == 1) __builtin_amdgcn_s_waitcnt(tpg_waitcnt_vm(NLD * (NST - 3)));
-        if constexpr (DBGW == 0 || DBGW == 3) __builtin_amdgcn_s_barrier();
-        if constexpr (DBGW == 0 || DBGW == 1) DMA(Sc, kb + NST < kb1 ? kb + NST : kl);
+        __builtin_amdgcn_s_waitcnt(tpg_waitcnt_vm(NLD * (NST - 3)));
+        __builtin_amdgcn_s_barrier();
+        DMA(Sc, kb + NST < kb1 ? kb + NST : kl);
         const bool live1 = kb + 1 < kb1;  // past the K range: zero A planes, the tail of the last unrolled body adds nothing
 #pragma unroll
         for (int t = 0; t < NT; t++) {
@@ -942,7 +935,7 @@ static int pw_ksplit(int64_t nun, int64_t steps, int64_t min_steps_per_unit, int
   return bestS;
 }
 
-template <int RA, int RB, int MASK, int NS, int DBG = 0>
+template <int RA, int RB, int MASK, int NS>
 static int pw_launch_set(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1, const char* name) {
   const int2* d_order = nullptr;
   int64_t nun = 0;
@@ -957,17 +950,16 @@ static int pw_launch_set(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int6
     const int64_t kgs = c1 - c0;
     // per 64-locus block: NM MFMAs at ~18 ns; flush: 16 atomic wave-instructions per accumulator tile (12 us for 15)
     int S = pw_ksplit(nun, 2 * kgs, 16, ceil_div(kgs, max_groups), nwaves, 0.0183 * NM, 0.8 * NM);
-    if (const char* e = getenv("TPG_PW_KSPLIT")) S = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(kgs, max_groups), atoi(e)), std::max<int64_t>(1, 2 * kgs));  // (experiments; any S in range gives the same sums)
-    if (getenv("TPG_DEBUG")) fprintf(stderr, "[tpg] %s: %d x %d tiles, %lld units, S = %d\n", name, RA, RB, (long long)nun, S);
-    TPG_LAUNCH(ctx, name, (tpg_pairwise_set_kernel<RA, RB, MASK, NS, DBG>), dim3((unsigned)nblk), dim3(256), 0,
+    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] %s: %d x %d tiles, %lld units, S = %d\n", name, RA, RB, (long long)nun, S);
+    TPG_LAUNCH(ctx, name, (tpg_pairwise_set_kernel<RA, RB, MASK, NS>), dim3((unsigned)nblk), dim3(256), 0,
                (const uint4*)v->T4, v->KG, 2 * c0, 2 * c1, (int)pw->nst, (int)ceil_div(pw->n, 32), d_order, nun, S,
                (const int64_t*)pw->rowpad, pw->acc);
   }
   return TPG_OK;
 }
 
-// the workgroup form: units are (64 RA) x (64 RB) blocks of pairs, one per workgroup; TPG_PW_KSPLIT=<S> overrides the K split
-template <int RA, int RB, int MASK, int NST, int DBGW = 0>
+// the workgroup form: units are (64 RA) x (64 RB) blocks of pairs, one per workgroup
+template <int RA, int RB, int MASK, int NST>
 static int pw_launch_wg(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1, const char* name) {
   const int2* d_order = nullptr;
   int64_t nun = 0;
@@ -980,9 +972,8 @@ static int pw_launch_wg(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64
     const int64_t c1 = std::min(kg1, c0 + 8 * max_groups);
     const int64_t kgs = c1 - c0;
     int S = pw_ksplit(nun, 2 * kgs, 16, ceil_div(kgs, max_groups), nblk, 0.0183 * NM, 0.8 * NM);
-    if (const char* e = getenv("TPG_PW_KSPLIT")) S = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(kgs, max_groups), atoi(e)), std::max<int64_t>(1, 2 * kgs));
-    if (getenv("TPG_DEBUG")) fprintf(stderr, "[tpg] %s: workgroups of %d x %d tiles, %lld units, S = %d\n", name, 2 * RA, 2 * RB, (long long)nun, S);
-    TPG_LAUNCH(ctx, name, (tpg_pairwise_wg_kernel<RA, RB, MASK, NST, DBGW>), dim3((unsigned)nblk), dim3(256), 0,
+    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] %s: workgroups of %d x %d tiles, %lld units, S = %d\n", name, 2 * RA, 2 * RB, (long long)nun, S);
+    TPG_LAUNCH(ctx, name, (tpg_pairwise_wg_kernel<RA, RB, MASK, NST>), dim3((unsigned)nblk), dim3(256), 0,
                (const uint4*)v->T4, v->KG, 2 * c0, 2 * c1, (int)pw->nst, (int)ceil_div(pw->n, 32), d_order, nun, S,
                (const int64_t*)pw->rowpad, pw->acc);
   }
@@ -991,8 +982,7 @@ static int pw_launch_wg(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64
 
 // wave tile and slot count per product set; TPG_PW_VARIANT=<k> picks another instantiation (A/B runs, tools/pw_only.py)
 static int pw_variant() {
-  const char* e = getenv("TPG_PW_VARIANT");
-  return e ? atoi(e) : 0;
+  return tpg_env_int("TPG_PW_VARIANT", 0);
 }
 
 static int pw_launch_all(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1) {
@@ -1011,9 +1001,7 @@ static int pw_launch_all(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int6
     const int64_t c1 = std::min(kg1, c0 + 8 * max_groups);
     const int64_t kgs = c1 - c0;
     int bestS = pw_ksplit(pw->nun, kgs, 8, ceil_div(kgs, max_groups), nwaves, 0.55, 12.0);
-    // (experiments, tools/pw_ksplit_probe.py: any S in range gives the same sums)
-    if (const char* e = getenv("TPG_PW_KSPLIT")) bestS = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(kgs, max_groups), atoi(e)), std::max<int64_t>(1, kgs));
-    if (getenv("TPG_DEBUG")) fprintf(stderr, "[tpg] pairwise: %lld units, S = %d\n", (long long)pw->nun, bestS);
+    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] pairwise: %lld units, S = %d\n", (long long)pw->nun, bestS);
     if (pw_variant() == 2)  // A/B: three groups of prefetch
       TPG_LAUNCH(ctx, "pairwise_mfma", tpg_pairwise_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, (const uint4*)v->T4, v->KG,
                  c0, c1, (int)pw->nst, (int)ceil_div(pw->n, 32), (const int2*)pw->order, pw->nun, bestS,
@@ -1071,9 +1059,8 @@ extern "C" int tpg_pairwise_accumulate_products(tpg_ctx* ctx, tpg_pairwise* pw, 
   // {V, D, A} 64 x 64 with 5 / 4 / 3 / 6 slots 16.2 / 16.5 / 23.5 / 16.4, 128 x 32 17.9, 96 x 32 17.8; all five through
   // this template (96 x 32, 4 ... 7 slots) 20.2 - 21.8 against 19.5 for the kernel above with its two-block groups
 #define PW_WG(RA, RB, MASK, NST, name) TPG_TRY((pw_launch_wg<RA, RB, MASK, NST>(ctx, pw, v, kg0, kg1, name)))
-  if (set == TPG_PW_FOR_AS && var >= 10 && var < 20) {  // operands shared through LDS (round 5): 14 / 15 / 16 = 4 / 5 / 6 stages
-    if (var == 15) PW_WG(4, 2, TPG_PW_FOR_AS, 5, "pairwise_mfma_as");
-    else if (var == 16) PW_WG(4, 2, TPG_PW_FOR_AS, 6, "pairwise_mfma_as");
+  if (set == TPG_PW_FOR_AS && var >= 10 && var < 20) {  // operands shared through LDS (round 5): 16 = six stages, else four
+    if (var == 16) PW_WG(4, 2, TPG_PW_FOR_AS, 6, "pairwise_mfma_as");
     else PW_WG(4, 2, TPG_PW_FOR_AS, 4, "pairwise_mfma_as");
   } else if (set == TPG_PW_FOR_IBS && var >= 10 && var < 20) {
     if (var == 16) PW_WG(2, 2, TPG_PW_FOR_IBS, 6, "pairwise_mfma_ibs");
@@ -1082,21 +1069,7 @@ extern "C" int tpg_pairwise_accumulate_products(tpg_ctx* ctx, tpg_pairwise* pw, 
     if (var == 16) PW_WG(2, 2, TPG_PW_FOR_KING, 6, "pairwise_mfma_king");
     else PW_WG(2, 2, TPG_PW_FOR_KING, 4, "pairwise_mfma_king");
   } else if (set == TPG_PW_FOR_AS) {
-    // 21 ... 26: timing-only instantiations that give WRONG sums (loads / barriers / LDS-DMA removed: DESIGN.md 3.1 "Round 5").
-    // They exist only in a library built with -DTPG_PW_EXPERIMENTS (tools/build_variants.sh); the shipped one refuses them.
-    if (var >= 21 && var <= 26) {
-#ifdef TPG_PW_EXPERIMENTS
-      if (var == 24) TPG_TRY((pw_launch_wg<4, 2, TPG_PW_FOR_AS, 4, 1>(ctx, pw, v, kg0, kg1, "pairwise_mfma_as")));
-      else if (var == 25) TPG_TRY((pw_launch_wg<4, 2, TPG_PW_FOR_AS, 4, 2>(ctx, pw, v, kg0, kg1, "pairwise_mfma_as")));
-      else if (var == 26) TPG_TRY((pw_launch_wg<4, 2, TPG_PW_FOR_AS, 4, 3>(ctx, pw, v, kg0, kg1, "pairwise_mfma_as")));
-      else if (var == 21) TPG_TRY((pw_launch_set<4, 2, TPG_PW_FOR_AS, 5, 1>(ctx, pw, v, kg0, kg1, "pairwise_mfma_as")));
-      else if (var == 22) TPG_TRY((pw_launch_set<4, 2, TPG_PW_FOR_AS, 5, 2>(ctx, pw, v, kg0, kg1, "pairwise_mfma_as")));
-      else TPG_REQUIRE(false, TPG_EUNSUPPORTED, "TPG_PW_VARIANT=%d does not exist", var);
-#else
-      TPG_REQUIRE(false, TPG_EUNSUPPORTED, "TPG_PW_VARIANT=%d is a timing experiment with wrong sums: build with -DTPG_PW_EXPERIMENTS", var);
-#endif
-    }
-    else if (var == 1) PW_SET(4, 2, TPG_PW_FOR_AS, 5, "pairwise_mfma_as");
+    if (var == 1) PW_SET(4, 2, TPG_PW_FOR_AS, 5, "pairwise_mfma_as");
     else if (var == 2) PW_SET(3, 2, TPG_PW_FOR_AS, 5, "pairwise_mfma_as");
     // (96 x 96 = 18 accumulator tiles, 32 of their registers VGPRs: 15.0 ms with three slots, 21.7 with four -- 54 spills --
     // against 8.1; instantiations removed again)
@@ -1106,10 +1079,6 @@ extern "C" int tpg_pairwise_accumulate_products(tpg_ctx* ctx, tpg_pairwise* pw, 
     // with 4 / 5 slots 11.2 / 11.2, 64 x 64 11.9; the {V, D, H} kernel (three sums per pair, 64 x 64) 12.2
     if (var == 1) PW_SET(4, 2, TPG_PW_FOR_IBS_ALONE, 4, "pairwise_mfma_ibs1");
     else if (var == 2) PW_SET(3, 2, TPG_PW_FOR_IBS_ALONE, 4, "pairwise_mfma_ibs1");
-    else if (var == 3) PW_SET(3, 2, TPG_PW_FOR_IBS_ALONE, 5, "pairwise_mfma_ibs1");
-    else if (var == 4) PW_SET(2, 2, TPG_PW_FOR_IBS_ALONE, 5, "pairwise_mfma_ibs1");
-    else if (var == 5) PW_SET(4, 2, TPG_PW_FOR_IBS_ALONE, 5, "pairwise_mfma_ibs1");
-    else if (var == 6) PW_SET(4, 2, TPG_PW_FOR_IBS_ALONE, 3, "pairwise_mfma_ibs1");
     // (96 x 96, 27 MFMAs per 6 fragments: 17.9 ms with three slots, 21.2 with four -- 86 spills; removed again)
     else PW_SET(4, 2, TPG_PW_FOR_IBS_ALONE, 4, "pairwise_mfma_ibs1");
   } else if (set == TPG_PW_FOR_IBS) {
@@ -1734,8 +1703,7 @@ __global__ __launch_bounds__(256) void tpg_pairwise_counts2_i32_kernel(const int
 // 400 MB of fresh pages per block), and a team of threads adds the first to K while the second is still on its way.
 // TPG_INCREMENT_TRACE=1: one line per call of an increment_* mirror with the milliseconds of its phases (stderr)
 static bool increment_trace() {
-  const char* e = getenv("TPG_INCREMENT_TRACE");
-  return e && atoi(e) != 0;
+  return tpg_env_int("TPG_INCREMENT_TRACE", 0) != 0;
 }
 static double inc_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e3; }
 
@@ -1765,7 +1733,7 @@ static int add_counts_to_caller(tpg_ctx* ctx, int which, const tpg_pairwise* pw,
   }
   TPG_TRY(pw_need(pw, which == 0 ? TPG_PW_FOR_IBS_ALONE : which == 1 ? TPG_PW_FOR_KING : TPG_PW_FOR_AS, "increment"));
   // widths on the wire: 16 bits where the block's bounds allow it (see the kernel); TPG_INCREMENT_I32=1: always int32 (A/B)
-  static const bool wide = getenv("TPG_INCREMENT_I32") && atoi(getenv("TPG_INCREMENT_I32")) != 0;
+  static const bool wide = tpg_env_int("TPG_INCREMENT_I32", 0) != 0;
   const int64_t bound = 2 * pw->loci + pw->as_pad_quirk;  // of |IBS|, |valid|, |KING numerator|; N_Aa, |D|, V <= loci + quirk
   const bool a16 = !wide && (which == 0 ? bound <= 65535 : which == 2 ? pw->loci + pw->as_pad_quirk <= 32767 : false);
   const bool b16 = !wide && (which == 0 ? bound <= 65535 : pw->loci <= 65535);

@@ -1221,12 +1221,11 @@ struct EigWork {
   int init() {
     // K splits: ONE round of workgroups (two fit a CU: 66 KiB of LDS each) -- at n = 5 000, 79 row blocks x 6 splits = 474
     // of 512 places, 89.5 us per product; 16 splits (2.5 rounds, the last half empty) 94.6, 13 splits (two rounds and three
-    // workgroups) 108 (tools/eig_s_scan.py)
+    // workgroups) 108
     const int row_blocks = (n + 63) / 64;
     S = 1;
     while (row_blocks * S < 4 * ctx->num_cu && S < 32 && n / (S * 2) >= 64) S *= 2;  // (short ranges: 1 000 rows take 4)
     S = std::max(1, std::min((int)S, 2 * ctx->num_cu / row_blocks));
-    if (getenv("TPG_EIG_S")) S = std::max(1, atoi(getenv("TPG_EIG_S")));  // (experiments)
     // A'B over chunks of rows: a workgroup per 32 (64) rows, so that a product on a few thousand rows is one short round
     // of many workgroups instead of a long loop in a few
     rows_per_chunk = n <= 4096 ? 32 : 64;
@@ -1320,7 +1319,7 @@ struct EigWork {
 struct StageTimer {
   tpg_ctx* ctx; const char* tag; bool on; double t0;
   static double now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
-  StageTimer(tpg_ctx* c, const char* t) : ctx(c), tag(t), on(getenv("TPG_DEBUG") != nullptr), t0(0) { if (on) { (void)hipStreamSynchronize(ctx->stream); t0 = now(); } }
+  StageTimer(tpg_ctx* c, const char* t) : ctx(c), tag(t), on(tpg_env_set("TPG_DEBUG")), t0(0) { if (on) { (void)hipStreamSynchronize(ctx->stream); t0 = now(); } }
   void mark(const char* what) {
     if (!on) return;
     (void)hipStreamSynchronize(ctx->stream);
@@ -1335,7 +1334,7 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
   // reading K, so extra columns are nearly free, and a block that reaches past the k wanted values into the
   // bulk of the spectrum converges in far fewer filter / Rayleigh-Ritz rounds than k + 12 columns do
   int b = 2 * k + 12;
-  if (getenv("TPG_EIG_BLOCK")) b = atoi(getenv("TPG_EIG_BLOCK"));
+  b = tpg_env_int("TPG_EIG_BLOCK", b);
   if (b > 64) b = 64;
   if (b > n) b = n;
   TPG_REQUIRE(k <= b, TPG_EINVAL, "k = %d too large (at most %d components)", k, b);
@@ -1381,7 +1380,7 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
         // orthogonality to rounding.
         std::vector<double> lamg, Vg;
         host_sym_eig(Gsave, act, lamg, Vg);  // tridiagonal QL: ~0.1 ms at 52 x 52 where cyclic Jacobi took over a millisecond
-        if (getenv("TPG_DEBUG")) fprintf(stderr, "[eig] CholQR fell back to the eigen-decomposition of the block Gram matrix\n");
+        if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[eig] CholQR fell back to the eigen-decomposition of the block Gram matrix\n");
         const double floor_ = std::max(lamg[0], 1e-300) * 1e-14;
         Ri.assign((size_t)act * act, 0.0);
         for (int j = 0; j < act; j++) {
@@ -1459,7 +1458,7 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
       const double dmax = log(2 * AMP) / acosh(x0);
       deg = dmax < 2 ? 2 : (dmax > 20 ? 20 : (int)dmax);
     }
-    if (getenv("TPG_DEBUG"))
+    if (tpg_env_set("TPG_DEBUG"))
       fprintf(stderr, "[eig] it %d act %d locked %d (+%d) deg %d theta_first %.4g theta_last %.4g lam1 %.4g res0 %.3g\n", it,
               act, nl, newly, deg, theta[(size_t)newly], theta[(size_t)act - 1], lam1,
               first ? -1.0 : sqrt(std::max(0.0, RR[(size_t)newly])) / lam1);

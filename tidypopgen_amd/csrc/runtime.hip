@@ -508,7 +508,7 @@ static hipError_t mail_wait(tpg_ctx* ctx, const volatile uint32_t* flag, uint32_
 
 hipError_t tpg_fetch_small(tpg_ctx* ctx, void* host_dst, const void* d_src, size_t bytes) {
   if (bytes == 0) return hipSuccess;
-  static const bool off = getenv("TPG_NO_MAILBOX") != nullptr;  // (A/B: the copy engine + a stream synchronisation)
+  static const bool off = tpg_env_set("TPG_NO_MAILBOX");  // (A/B: the copy engine + a stream synchronisation)
   if (off || bytes > tpg_ctx::MAIL_FETCH_BYTES || (bytes & 3) || ((uintptr_t)d_src & 3) || mail_init(ctx) != hipSuccess) {
     hipError_t e = hipMemcpyAsync(host_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream);
     return e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
@@ -526,7 +526,7 @@ hipError_t tpg_fetch_small(tpg_ctx* ctx, void* host_dst, const void* d_src, size
 
 hipError_t tpg_push_small(tpg_ctx* ctx, void* d_dst, const void* host_src, size_t bytes) {
   if (bytes == 0) return hipSuccess;
-  static const bool off = getenv("TPG_NO_MAILBOX") != nullptr;
+  static const bool off = tpg_env_set("TPG_NO_MAILBOX");
   if (off || bytes > tpg_ctx::MAIL_PUSH_MAX || (bytes & 3) || ((uintptr_t)d_dst & 3) || mail_init(ctx) != hipSuccess)
     return h2d_engine(ctx, d_dst, host_src, bytes);
   const size_t need = (bytes + 63) & ~(size_t)63;
@@ -620,7 +620,7 @@ static hipError_t tpg_download_pinned(tpg_ctx* ctx, uint8_t* dst, const uint8_t*
                                       size_t width = 0, size_t dpitch = 0) {
   *done = false;
   if (width == 0 || width >= bytes) { width = bytes; dpitch = bytes; }
-  static const bool off = getenv("TPG_DOWNLOAD_PINNED") && atoi(getenv("TPG_DOWNLOAD_PINNED")) == 0;
+  static const bool off = tpg_env_int("TPG_DOWNLOAD_PINNED", 1) == 0;
   // (a copy below 64 MiB takes the staging buffer only if the process already has one: pinning 256 MiB costs 35 - 40 ms)
   uint8_t* const pinned = off ? nullptr : nib_stage_acquire(bytes >= XFER_BIG);
   if (!pinned) return hipSuccess;
@@ -668,7 +668,7 @@ static hipError_t tpg_download_pinned(tpg_ctx* ctx, uint8_t* dst, const uint8_t*
 // TPG_DOWNLOAD_THP=0: do not ask (A/B).
 static void advise_huge_pages(void* dst, size_t extent) {
 #ifdef MADV_HUGEPAGE
-  static const bool off = getenv("TPG_DOWNLOAD_THP") && atoi(getenv("TPG_DOWNLOAD_THP")) == 0;
+  static const bool off = tpg_env_int("TPG_DOWNLOAD_THP", 1) == 0;
   const uintptr_t H = 2u << 20, lo = ((uintptr_t)dst + H - 1) & ~(H - 1), hi = ((uintptr_t)dst + extent) & ~(H - 1);
   if (!off && extent >= (4u << 20) && hi > lo) (void)madvise((void*)lo, hi - lo, MADV_HUGEPAGE);
 #else
@@ -786,7 +786,7 @@ void tpg_stage_keep(int buffers) {
 static void nib_stage_release(uint8_t* p) {
   {
     std::lock_guard<std::mutex> lk(g_nib_mu);
-    static const size_t env_keep = getenv("TPG_PINNED_KEEP") ? (size_t)atoi(getenv("TPG_PINNED_KEEP")) : 0;
+    static const size_t env_keep = (size_t)tpg_env_int("TPG_PINNED_KEEP", 0);
     if (g_nib_free.size() < std::max(g_nib_keep, env_keep)) { g_nib_free.push_back(p); return; }
   }
   (void)hipHostFree(p);  // (device-synchronising: only a burst beyond what the process keeps gets here)
@@ -930,7 +930,7 @@ hipError_t tpg_upload_bedpacked(tpg_ctx* ctx, uint8_t* dst, const uint8_t* src, 
 // into one half of the pinned buffer while chunk c leaves the other half at the rate of pinned memory (55 - 57 GB/s).
 // TPG_UPLOAD_PINNED=0: the plain chunked copy (A/B).
 static hipError_t tpg_upload_pinned(tpg_ctx* ctx, uint8_t* dst, const uint8_t* src, size_t bytes) {
-  static const bool off = getenv("TPG_UPLOAD_PINNED") && atoi(getenv("TPG_UPLOAD_PINNED")) == 0;
+  static const bool off = tpg_env_int("TPG_UPLOAD_PINNED", 1) == 0;
   uint8_t* const pinned = off ? nullptr : nib_stage_acquire();
   if (!pinned) return tpg_upload(ctx, dst, src, bytes);
   struct Back { uint8_t* p; ~Back() { nib_stage_release(p); } } back{pinned};
@@ -959,7 +959,7 @@ static hipError_t tpg_upload_pinned(tpg_ctx* ctx, uint8_t* dst, const uint8_t* s
 
 // bulk FBM bytes: packed on the way when that can pay (large, 16-byte aligned destination) and is not switched off
 static hipError_t tpg_upload_fbm_bytes(tpg_ctx* ctx, uint8_t* dst, const uint8_t* src, size_t bytes) {
-  static const bool off = getenv("TPG_UPLOAD_PACKED") && atoi(getenv("TPG_UPLOAD_PACKED")) == 0;
+  static const bool off = tpg_env_int("TPG_UPLOAD_PACKED", 1) == 0;
   if (!off && bytes >= XFER_BIG && (((uintptr_t)dst) & 15) == 0) {
     ProfScope ps(ctx, "upload_packed");
     return tpg_upload_packed(ctx, dst, src, bytes);
@@ -994,11 +994,10 @@ static void make_lut(const double* code256, uint8_t* lut);
 int tpg_fbm_from_host_for_table(tpg_ctx* ctx, const uint8_t* bytes, int64_t nrow, int64_t ncol, const double* code256, tpg_fbm** out,
                                 const double** view_table) {
   *view_table = code256;
-  const char* sw = getenv("TPG_UPLOAD_BEDPACK");
   uint8_t lut[256], l16[16];
   make_lut(code256, lut);
   static const uint8_t bedcode[4] = {3, 2, 0, 1};  // code 0, 1, 2, missing -> .bed 11, 10, 00, 01 = bigsnpr's bytes 0, 1, 2, 3
-  bool can = !(sw && atoi(sw) == 0) && nrow > 0 && ncol > 0 && (size_t)nrow * (size_t)ncol >= (64u << 10);
+  bool can = tpg_env_int("TPG_UPLOAD_BEDPACK", 1) != 0 && nrow > 0 && ncol > 0 && (size_t)nrow * (size_t)ncol >= (64u << 10);
   for (int b = 0; b < 16 && can; b++) {
     if (lut[b] > 3) can = false;
     else l16[b] = bedcode[lut[b]];

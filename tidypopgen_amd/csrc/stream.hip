@@ -208,7 +208,7 @@ struct StreamRun {
 
   static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   // TPG_STREAM_TRACE=1: a timeline of the run on stderr (milliseconds since its start; who waited for whom)
-  bool trace = getenv("TPG_STREAM_TRACE") != nullptr;  // (read per run)
+  bool trace = tpg_env_set("TPG_STREAM_TRACE");  // (read per run)
   void stamp(const char* what, long long b = -1) const {
     if (trace) fprintf(stderr, "[stream] %8.2f ms  %s %lld\n", 1e3 * (now() - t_start), what, b);
   }
@@ -305,7 +305,7 @@ struct StreamRun {
       // no bound: the pipeline's own optimum -- a handful of blocks (per-block fixed costs against overlap: 8 blocks of a
       // byte store, 4 of a .bed payload measured best at 5 000 x 1 000 000), views kept
       target_blocks = src->kind == SRC_BED ? 4 : 8;
-      if (const char* e = getenv("TPG_STREAM_BLOCKS")) target_blocks = std::max(1, atoi(e));
+      if (tpg_env_set("TPG_STREAM_BLOCKS")) target_blocks = std::max(1, tpg_env_int("TPG_STREAM_BLOCKS", 0));
       B = ceil_div(ceil_div(mloc, target_blocks), 128) * 128;
       keep_views = want_pca;
     } else {
@@ -334,8 +334,8 @@ struct StreamRun {
   // the 2-bit host pack serves a byte store and ONE table whose every entry below 16 is a code (TPG_STREAM_BEDPACK=0: off)
   void set_bedpack(const double* table) {
     bedpack = false;
-    const char* e = getenv("TPG_STREAM_BEDPACK");  // (read per run: the tests switch it)
-    if ((e && atoi(e) == 0) || src->kind != SRC_BYTES) return;
+    // (TPG_STREAM_BEDPACK is read per run: the tests switch it)
+    if (tpg_env_int("TPG_STREAM_BEDPACK", 1) == 0 || src->kind != SRC_BYTES) return;
     uint8_t l[256];
     lut_of(table, l);
     static const uint8_t bedcode[4] = {3, 2, 0, 1};  // code 0, 1, 2, missing -> .bed 11, 10, 00, 01 (the bytes 0, 1, 2, 3 of bigsnpr's reading)
@@ -608,9 +608,8 @@ struct StreamRun {
       if (budget) ctx->pca_digit_fbits = 30;
       // the Gram in batches of blocks (see `batch_gram`): a run without a budget that keeps its views and has more than two
       // blocks (with one or two the batches ARE the blocks).  TPG_STREAM_GRAM_BATCH=0: block by block (A/B)
-      const char* gb = getenv("TPG_STREAM_GRAM_BATCH");
       big_views = budget == 0 && keep_views && nblocks > 1;
-      batch_gram = big_views && nblocks > 2 && src->kind != SRC_BYTES && !(gb && atoi(gb) == 0);
+      batch_gram = big_views && nblocks > 2 && src->kind != SRC_BYTES && tpg_env_int("TPG_STREAM_GRAM_BATCH", 1) != 0;
       gram_from = 0;
       if (big_views) {
         const size_t per128 = (size_t)ceil_div(n, 128) * 4096;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which FP4 magnitude each operand plane of the pairwise kernels carries (TPG_T4_ENC, devfrag.h) changes no sum -- the block
 scales undo it -- only the bit patterns the matrix cores multiply, and with them the clock the chip holds under the MFMAs.
-Every encoding is a build of the library (tools/build_variants.sh encK "-DTPG_T4_ENC=K"); this script runs tools/pw_only.py
+Every encoding is a build of the library with -DTPG_T4_ENC=K into abvar/libtpg_encK.so (tools/README.md); this script runs tools/pw_only.py
 for each of them as a child process, round after round (the boxes drift), inside one GPU job.   tools/enc_ab.py [rounds]"""
 import os
 import re

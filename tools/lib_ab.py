@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Run one probe script under every library build in abvar/ (tools/build_variants.sh), round after round, inside one GPU job:
+"""Run one probe script under every library build in abvar/ (tools/README.md), round after round, inside one GPU job:
 tools/lib_ab.py <rounds> <probe.py> [probe args...]   -- prints the probe's last output line per build."""
 import os
 import subprocess

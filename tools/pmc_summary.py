@@ -37,7 +37,7 @@ for f in glob.glob(os.path.join(src, "trace", "*", "*_kernel_stats.csv")):
 # kernel belongs here since round 4 (commit 6dde6ae: 16-byte loads on its 8-byte-aligned columns; round 4's file still had it
 # at 1.0 and reported half of its 5.0 GB)
 WIDE = ("tpg_pairwise_kernel", "tpg_pairwise_set_kernel", "tpg_pairwise_wg_kernel", "tpg_pca_gram_kernel", "tpg_gcls_gram_kernel",
-        "tpg_gcls_gram2_kernel", "tpg_gcls_gram1w_kernel", "tpg_pack_fast_kernel")
+        "tpg_gcls_gram2_kernel", "tpg_pack_fast_kernel")
 out, traffic = {}, {}
 for k, c in sorted(acc.items()):
     d = disp[k]
