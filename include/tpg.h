@@ -565,6 +565,35 @@ int tpg_stream_run(tpg_ctx* ctx, tpg_stream* s, const tpg_stream_job* job, tpg_s
  * share.  Outputs must be host memory (device threads write disjoint pieces).  `s` supplies the store and the budget. */
 int tpg_multi_stream_run(tpg_multi* mg, tpg_stream* s, const tpg_stream_job* job, tpg_stream_report* report);
 
+/* The QC pass of a store that stays on the host: what qc_report_loci (R/qc_report_loci.R:50-57, 96-107: MAF and missingness
+ * from the genotype counts, loci_hwe) and qc_report_indiv (R/qc_report_indiv.R:77-84 over indiv_het_obs,
+ * src/gt_ind_hetero.cpp:11-42) need, from ONE sweep with the block plan, the budget accounting, the uploader and downloader
+ * threads and the report of tpg_stream_run.  A pass of its own: its result decides the rows and columns of every later
+ * pass, and it sets up none of the N x N state.  Every output pointer is optional (NULL = not asked for), host or device
+ * memory, laid out as the resident entry point named beside it; integer counts and p-values are those entry points' bit
+ * for bit (the exact tests run on the device behind the counts of each block: no count table crosses PCIe on the way).
+ * The per-locus outputs leave block by block.  indiv_counts is the one output that is additive over blocks: every block
+ * adds its {n1, n2, nNA} per individual to an n x 4 int32 table that stays in HBM (report: state_bytes; sweeps = 1), n0
+ * follows from m at the end; m >= 2^31 loci: TPG_EUNSUPPORTED for that output.  A job that asks for nothing, asks for a
+ * grouped output without groupIds0 / ngroups >= 1, or has another struct_size: TPG_EINVAL. */
+typedef struct tpg_stream_qc_job {
+  size_t struct_size;     /* sizeof(tpg_stream_qc_job); any other value: TPG_EINVAL */
+  const int32_t* rowInd1; /* NULL = all rows */
+  int64_t n;
+  const int32_t* colInd1; /* NULL = all columns (a synthetic store: contiguous, as in tpg_stream_run) */
+  int64_t m;
+  const double* code256;     /* NULL = raw bytes, as in tpg_stream_job */
+  const int32_t* groupIds0;  /* needed by the grouped outputs only */
+  int ngroups;
+  int midp;                /* 0 or 1 */
+  int32_t* loci_counts;    /* m x 4 row-major           (tpg_loci_counts) */
+  double* hwe_p;           /* m                         (tpg_loci_hwe) */
+  int32_t* grouped_counts; /* three m x G, column-major (tpg_grouped_genotype_counts) */
+  double* grouped_hwe_p;   /* m x G column-major        (tpg_gt_grouped_hwe) */
+  int32_t* indiv_counts;   /* n x 4 row-major {n0,n1,n2,nNA} over the m selected loci (tpg_indiv_counts) */
+} tpg_stream_qc_job;
+int tpg_stream_qc(tpg_ctx* ctx, tpg_stream* s, const tpg_stream_qc_job* job, tpg_stream_report* report);
+
 /* ---- PCA (gt_pca_partialSVD) ---------------------------------------------- */
 /* center / scale of bigsnpr::snp_scaleBinom; TPG_ENUMERIC on a missing value or zero scale */
 int tpg_pca_center_scale(tpg_ctx* ctx, const tpg_view* v, double* center, double* scale);

@@ -99,7 +99,7 @@ SYMBOLS = [
     "tpg_pairwise_accumulate_products", "tpg_pairwise_products", "tpg_pairwise_reduce_begin", "tpg_pairwise_reduce_end",
     "tpg_stream_open_host", "tpg_stream_open_bk", "tpg_stream_open_bed", "tpg_stream_open_bed_host", "tpg_stream_open_synth",
     "tpg_stream_close", "tpg_stream_run", "tpg_multi_stream_run", "tpg_fbm_impute_simple", "tpg_fbm_impute_simple_at", "tpg_view_impute",
-    "tpg_hwe_exact_counts", "tpg_loci_hwe", "tpg_gt_grouped_hwe",
+    "tpg_hwe_exact_counts", "tpg_loci_hwe", "tpg_gt_grouped_hwe", "tpg_stream_qc",
 ]
 
 
@@ -120,6 +120,15 @@ class StreamJob(C.Structure):
 
 # TPG_STREAM_JOB_SIZE_V1: the struct before impute_method existed (tpg_stream_run accepts that size too)
 STREAM_JOB_SIZE_V1 = StreamJob.square_frobenius.offset + C.sizeof(vp)
+
+
+class StreamQcJob(C.Structure):
+    """tpg_stream_qc_job of include/tpg.h, field for field"""
+    _fields_ = [
+        ("struct_size", C.c_size_t), ("rowInd1", vp), ("n", C.c_int64), ("colInd1", vp), ("m", C.c_int64),
+        ("code256", vp), ("groupIds0", vp), ("ngroups", C.c_int), ("midp", C.c_int),
+        ("loci_counts", vp), ("hwe_p", vp), ("grouped_counts", vp), ("grouped_hwe_p", vp), ("indiv_counts", vp),
+    ]
 
 
 class ImputeReport(C.Structure):
@@ -145,6 +154,8 @@ if hasattr(lib, "tpg_loci_hwe"):
     lib.tpg_hwe_exact_counts.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
     lib.tpg_loci_hwe.argtypes = [vp, vp, C.c_int, vp]
     lib.tpg_gt_grouped_hwe.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
+if hasattr(lib, "tpg_stream_qc"):
+    lib.tpg_stream_qc.argtypes = [vp, vp, C.POINTER(StreamQcJob), C.POINTER(StreamReport)]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

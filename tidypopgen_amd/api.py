@@ -766,6 +766,47 @@ class Stream:
         out["report"] = self.report
         return out
 
+    def qc(self, ind_row=None, ind_col=None, code256=CODE_012, groupIds=None, ngroups: int = 0, mid_p: bool = True,
+           loci_counts: bool = False, hwe: bool = False, grouped_counts: bool = False, grouped_hwe: bool = False,
+           indiv_counts: bool = False) -> dict:
+        """The QC pass (tpg_stream_qc): one streamed sweep for the counts and exact tests behind qc_report_loci and
+        qc_report_indiv.  Returns what was asked for under the names of the resident functions -- "loci_counts" (m, 4),
+        "loci_hwe" (m,), "grouped_genotype_counts" (3, m, G), "gt_grouped_hwe" (m, G), "indiv_counts" (n, 4) -- bit for bit
+        what those give on a resident View of the same selection, plus "report"."""
+        r, c = _i32(ind_row), _i32(ind_col)
+        n = self.nrow if r is None else len(r)
+        m = self.ncol if c is None else len(c)
+        G = int(ngroups)
+        job = _lib.StreamQcJob()
+        job.struct_size = C.sizeof(_lib.StreamQcJob)
+        code, gid = _f64(code256), _i32(groupIds)
+        job.rowInd1, job.n, job.colInd1, job.m = _ptr(r), n, _ptr(c), m
+        job.code256, job.groupIds0, job.ngroups, job.midp = _ptr(code), _ptr(gid), G, int(bool(mid_p))
+        out = {}
+        if loci_counts:
+            out["loci_counts"] = np.empty((m, 4), dtype=np.int32)
+            job.loci_counts = _ptr(out["loci_counts"])
+        if hwe:
+            out["loci_hwe"] = np.empty(m)
+            job.hwe_p = _ptr(out["loci_hwe"])
+        gc = None
+        if grouped_counts:
+            gc = np.empty((3, max(G, 0), m), dtype=np.int32)  # three column-major m x G matrices
+            job.grouped_counts = _ptr(gc)
+        if grouped_hwe:
+            out["gt_grouped_hwe"] = np.empty((m, max(G, 0)), order="F")
+            job.grouped_hwe_p = _ptr(out["gt_grouped_hwe"])
+        if indiv_counts:
+            out["indiv_counts"] = np.empty((n, 4), dtype=np.int32)
+            job.indiv_counts = _ptr(out["indiv_counts"])
+        rep = _lib.StreamReport()
+        check(lib.tpg_stream_qc(self.ctx.h, self.h, C.byref(job), C.byref(rep)))
+        if gc is not None:
+            out["grouped_genotype_counts"] = np.ascontiguousarray(gc.transpose(0, 2, 1))
+        self.report = {f: getattr(rep, f) for f, _ in _lib.StreamReport._fields_}
+        out["report"] = self.report
+        return out
+
     def close(self):
         if self.h:
             lib.tpg_stream_close(self.h)
@@ -1042,6 +1083,59 @@ def loci_hwe(X: FBM, ind_row=None, ind_col=None, mid_p: bool = True) -> np.ndarr
     out = np.zeros(v.m)
     check(lib.tpg_loci_hwe(v.ctx.h, v.h, C.c_int(int(bool(mid_p))), _ptr(out)))
     return out
+
+
+def qc_loci_from_counts(loci_counts) -> dict:
+    """maf and missingness of qc_report_loci from the (m, 4) genotype counts {n0, n1, n2, nNA}: f = (n1 + 2 n2) /
+    (2 (n - nNA)), maf = min(f, 1 - f) (R/loci_maf.R over loci_alt_freq: NaN at a locus nobody is typed at), missingness =
+    nNA / n (R/loci_missingness.R)"""
+    c = np.asarray(loci_counts, dtype=np.int64)
+    n = c.sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = (c[:, 1] + 2 * c[:, 2]) / (2.0 * (n - c[:, 3]))
+        return dict(maf=np.minimum(f, 1.0 - f), missingness=c[:, 3] / n.astype(float))
+
+
+def qc_indiv_from_counts(indiv_counts, store_ncol: int) -> dict:
+    """the columns of qc_report_indiv from the (n, 4) per-individual counts {n0, n1, n2, nNA} over the m selected loci.
+    het_obs follows R/indiv_het_obs.R:69 literally: het_n / (ncol(store) - na_n) -- the STORE's column count, not m; the
+    two agree when every locus of the store is selected.  missingness = na_n / m."""
+    c = np.asarray(indiv_counts, dtype=np.int64)
+    m = c.sum(axis=1)
+    het_n, na_n = c[:, 1].astype(np.int32), c[:, 3].astype(np.int32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(het_obs=het_n / (float(store_ncol) - na_n), missingness=na_n / m.astype(float), het_n=het_n, na_n=na_n)
+
+
+def qc_report_loci(S, ind_row=None, ind_col=None, groupIds=None, ngroups: int = 0, mid_p: bool = True) -> dict:
+    """qc_report_loci -> {"maf", "missingness", "hwe_p"}, each (m,).  Ungrouped (R/qc_report_loci.R:50-57): hwe_p as loci_hwe.
+    With groupIds (R/qc_report_loci.R:96-107): the smallest of the locus's per-group p-values times ngroups; maf and
+    missingness stay those of all selected individuals.  S is a Stream (one streamed pass, Stream.qc, through CODE_012) or an
+    FBM (the resident functions through its own table): the report does not depend on where the store lives."""
+    grouped = groupIds is not None
+    if isinstance(S, Stream):
+        q = S.qc(ind_row, ind_col, groupIds=groupIds, ngroups=ngroups, mid_p=mid_p, loci_counts=True, hwe=not grouped,
+                 grouped_hwe=grouped)
+        counts, p = q["loci_counts"], q["gt_grouped_hwe"] if grouped else q["loci_hwe"]
+    else:
+        v = View(S, ind_row, ind_col)
+        counts = loci_counts(v)
+        p = gt_grouped_hwe(v, groupIds, ngroups, mid_p) if grouped else loci_hwe(S, ind_row, ind_col, mid_p)
+    out = qc_loci_from_counts(counts)
+    out["hwe_p"] = p.min(axis=1) * ngroups if grouped else p
+    return out
+
+
+def qc_report_indiv(S, ind_row=None, ind_col=None) -> dict:
+    """qc_report_indiv without its KING column (R/qc_report_indiv.R:77-84; Stream.run(pairwise=("king",)) gives that one) ->
+    {"het_obs", "missingness", "het_n", "na_n"}, each (n,): het_n / na_n are the two rows of gt_ind_hetero, the other two as
+    qc_indiv_from_counts states them (het_obs divides by the store's column count, as R/indiv_het_obs.R:69 does).  S is a
+    Stream (one streamed pass) or an FBM (the resident functions)."""
+    if isinstance(S, Stream):
+        counts = S.qc(ind_row, ind_col, indiv_counts=True)["indiv_counts"]
+    else:
+        counts = indiv_counts(View(S, ind_row, ind_col))
+    return qc_indiv_from_counts(counts, S.ncol)
 
 
 GLOBAL_STATS_COLUMNS = ("Ho", "Hs", "Ht", "Dst", "Htp", "Dstp", "Fst", "Fstp", "Fis", "Dest")

@@ -340,3 +340,7 @@ int tpg_launch_synth(tpg_ctx* ctx, uint8_t* d_bytes, uint64_t seed, int64_t nrow
 // per-locus
 int tpg_launch_loci_counts(tpg_ctx* ctx, const tpg_view* v, int32_t* d_counts /* m x 4 */);
 int tpg_grouped_counts(tpg_ctx* ctx, const tpg_view* v, const int32_t* h_cls, int nclass, GroupedCounts* out);
+// per-individual counts that add up over views (loci.hip): d_acc (n x 4 int32, zero before the first view) += the view's loci,
+// read from L; tpg_launch_indiv_finish turns the sums over m loci into {n0, n1, n2, nNA} (d_out may be d_acc)
+int tpg_launch_indiv_accumulate(tpg_ctx* ctx, const tpg_view* v, int32_t* d_acc);
+int tpg_launch_indiv_finish(tpg_ctx* ctx, const int32_t* d_acc, int64_t n, int64_t m, int32_t* d_out);

@@ -111,6 +111,132 @@ extern "C" int tpg_indiv_counts(tpg_ctx* ctx, const tpg_view* v, int32_t* out) {
   return o.commit(ctx);
 }
 
+// Per-individual counts of a view ADDED to a table that outlives the view (the streamed QC pass, stream.hip: the one
+// output of that pass that is additive over blocks), from the locus-tiled layout L every block already has -- no T, no
+// transpose per block.  In L a dword of lane (r, h) holds the codes of 16 individuals at ONE locus (32 lt + r), so the
+// counters live in the lanes as packed fields and grow by widening (no popcount can help: the sum runs ACROSS dwords):
+//   per locus       lo = w & 0x5555..., hi = (w >> 1) & 0x5555..., lo & hi: three planes of 16 two-bit fields of 0 / 1;
+//   3 loci          added in the two-bit fields (<= 3), then split into even / odd fields of four bits;
+//   15 loci         added in the four-bit fields (<= 15), then split into bytes: byte b of accumulator k is element
+//                   4 k + b of the dword (the operand order of common.h, read backwards);
+//   <= 255 loci     added in the bytes: a wave's share of locus tiles is at most 255 (tiles).
+// About 13 integer operations per dword and locus, against 16 B per lane and tile from HBM: n / 4 bytes per locus read
+// once.  A wave owns a 128-individual group q and the locus tiles [blockIdx.y tiles, + tiles); the four waves of a
+// workgroup take four consecutive groups, so a step of the workgroup reads 4 KiB in one piece.  At the end the 32 lanes
+// that share h hold counters of the same 64 individuals at different loci: they go through LDS (row stride 49 dwords:
+// odd, conflict-free both ways), 96 items (h, accumulator) are summed over r in 16-bit fields (<= 32 x 255), and the
+// sums are ADDED to acc with integer atomics -- several workgroups (the splits of the locus axis) add to one
+// individual, integers make the order irrelevant, and a launch adds 3 n gridDim.y dwords, nothing beside the n / 4
+// bytes per locus it reads.  acc is n x 4 int32, row i = {unused, codes with bit 0 set, with bit 1 set, with both} summed
+// over the loci so far (tpg_indiv_finish_kernel turns it into {n0, n1, n2, nNA}).  Padded loci (>= m) are not loaded and
+// padded individuals (>= n) are not written: the table needs no correction of the kind npad is above.
+#define TPG_IA_STRIDE 49
+__global__ __launch_bounds__(256) void tpg_indiv_accumulate_kernel(const uint4* __restrict__ L, int64_t n_lt, int64_t Q,
+                                                                   int64_t n, int64_t m, int tiles,
+                                                                   int32_t* __restrict__ acc) {
+  __shared__ uint32_t red[4][64 * TPG_IA_STRIDE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t q = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t lt0 = (int64_t)blockIdx.y * tiles, lt1 = lt0 + tiles < n_lt ? lt0 + tiles : n_lt;
+  uint32_t a8[4][3][4] = {};  // [dword s][plane][k]: byte b = element 4 k + b
+  if (q < Q) {
+    const uint4* p = L + q * 64 + lane;
+    const int64_t r = lane & 31;
+    for (int64_t base = lt0; base < lt1; base += 15) {
+      uint32_t a4[4][3][2] = {};
+#pragma unroll
+      for (int g = 0; g < 5; g++) {
+        uint32_t a2[4][3] = {};
+#pragma unroll
+        for (int u = 0; u < 3; u++) {
+          const int64_t lt = base + 3 * g + u;
+          uint4 w = make_uint4(0, 0, 0, 0);
+          if (lt < lt1 && lt * 32 + r < m) w = p[lt * Q * 64];
+          const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+          for (int s = 0; s < 4; s++) {
+            const uint32_t lo = ws[s] & 0x55555555u, hi = (ws[s] >> 1) & 0x55555555u;
+            a2[s][0] += lo;
+            a2[s][1] += hi;
+            a2[s][2] += lo & hi;
+          }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+#pragma unroll
+          for (int pl = 0; pl < 3; pl++) {
+            a4[s][pl][0] += a2[s][pl] & 0x33333333u;
+            a4[s][pl][1] += (a2[s][pl] >> 2) & 0x33333333u;
+          }
+      }
+#pragma unroll
+      for (int s = 0; s < 4; s++)
+#pragma unroll
+        for (int pl = 0; pl < 3; pl++)
+#pragma unroll
+          for (int e = 0; e < 2; e++) {
+            a8[s][pl][e] += a4[s][pl][e] & 0x0F0F0F0Fu;
+            a8[s][pl][2 + e] += (a4[s][pl][e] >> 4) & 0x0F0F0F0Fu;
+          }
+    }
+  }
+  uint32_t* my = red[wave];
+#pragma unroll
+  for (int s = 0; s < 4; s++)
+#pragma unroll
+    for (int pl = 0; pl < 3; pl++)
+#pragma unroll
+      for (int k = 0; k < 4; k++) my[lane * TPG_IA_STRIDE + (s * 3 + pl) * 4 + k] = a8[s][pl][k];
+  __syncthreads();
+  if (q >= Q) return;
+  for (int item = lane; item < 96; item += 64) {
+    const int h = item / 48, j = item % 48;
+    uint32_t ev = 0, od = 0;  // bytes 0, 2 and bytes 1, 3 in 16-bit fields
+    for (int r = 0; r < 32; r++) {
+      const uint32_t x = my[(32 * h + r) * TPG_IA_STRIDE + j];
+      ev += x & 0x00FF00FFu;
+      od += (x >> 8) & 0x00FF00FFu;
+    }
+    const int k = j & 3, pl = (j >> 2) % 3, s = j / 12;
+    const int64_t i0 = q * 128 + 32 * s + 16 * h + 4 * k;
+    const uint32_t c[4] = {ev & 0xFFFFu, od & 0xFFFFu, ev >> 16, od >> 16};
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      if (c[b] && i0 + b < n) atomicAdd(acc + (i0 + b) * 4 + 1 + pl, (int32_t)c[b]);
+  }
+}
+
+// acc as tpg_indiv_accumulate_kernel leaves it after m loci -> {n0, n1, n2, nNA} (in place, or into out)
+__global__ void tpg_indiv_finish_kernel(const int4* acc, int64_t n, int32_t m, int4* out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int4 a = acc[i];
+    const int n1 = a.y - a.w, n2 = a.z - a.w;
+    out[i] = make_int4(m - n1 - n2 - a.w, n1, n2, a.w);
+  }
+}
+
+int tpg_launch_indiv_accumulate(tpg_ctx* ctx, const tpg_view* v, int32_t* d_acc) {
+  const int64_t n_lt = ceil_div(v->m, 32), gx = ceil_div(v->Q, 4);
+  // the locus axis in enough pieces to fill the device a few times over; a wave's piece is whole groups of 15 tiles, at least
+  // 30 (its reduction costs about what ten tiles cost) and at most 255 (the byte fields)
+  int64_t tiles = ceil_div(ceil_div(n_lt, ceil_div(4 * (int64_t)ctx->num_cu, gx)), 15) * 15;
+  tiles = tiles < 30 ? 30 : tiles > 255 ? 255 : tiles;
+  const int64_t gy = ceil_div(n_lt, tiles);
+  TPG_REQUIRE(gy <= 65535 && gx <= 0x7FFFFFFF, TPG_EUNSUPPORTED, "per-individual counts of a view of %lld x %lld", (long long)v->n,
+              (long long)v->m);
+  TPG_LAUNCH(ctx, "indiv_accumulate", tpg_indiv_accumulate_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0,
+             (const uint4*)v->L, n_lt, v->Q, v->n, v->m, (int)tiles, d_acc);
+  TPG_CHECK_LAUNCH();
+  return TPG_OK;
+}
+
+int tpg_launch_indiv_finish(tpg_ctx* ctx, const int32_t* d_acc, int64_t n, int64_t m, int32_t* d_out) {
+  TPG_LAUNCH(ctx, "indiv_finish", tpg_indiv_finish_kernel, dim3((unsigned)(ceil_div(n, 256) < 1024 ? ceil_div(n, 256) : 1024)),
+             dim3(256), 0, (const int4*)d_acc, n, (int32_t)m, (int4*)d_out);
+  TPG_CHECK_LAUNCH();
+  return TPG_OK;
+}
+
 // src/gt_ind_hetero.cpp:11-42: row 0 = heterozygous loci, row 1 = missing loci, per individual
 __global__ void tpg_ind_hetero_kernel(const int4* __restrict__ counts, int64_t n, int32_t* __restrict__ out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {

@@ -15,7 +15,8 @@
 // budget.  After the sweep: epilogues (N x N results go down beside the eigen step), eigen step, and the loadings -- from
 // the imputed views if the budget let them stay, from a second sweep over the store otherwise.
 // tpg_multi_stream_run runs the same loop on every device of a tpg_multi over its share of colInd and exchanges what is
-// additive.
+// additive.  tpg_stream_qc is the same pipeline for the QC pass: counts and Hardy-Weinberg tests per locus leave
+// block by block, the per-individual counts add up in an n x 4 table (loci.hip: tpg_launch_indiv_accumulate).
 //
 // Everything here is orchestration over the library's own entry points: no kernel of the hot path lives in this file.
 #include <fcntl.h>
@@ -127,6 +128,7 @@ struct StreamRun {
   tpg_comm* comm = nullptr;  // NULL: a single device
   const StreamSource* src = nullptr;
   const tpg_stream_job* job = nullptr;
+  const tpg_stream_qc_job* qc = nullptr;  // tpg_stream_qc: `job` then carries the selection, the table and the groups only
   size_t budget = 0;
   int impute = TPG_IMPUTE_NONE;  // the PCA runs on tpg_view_impute of its view (job->impute_method with k > 0)
   int64_t n = 0, m = 0;      // the selection (m = all loci of the job, not only this device's)
@@ -164,6 +166,7 @@ struct StreamRun {
   // per-block outputs (two slots) and the downloader
   struct OutSlot {
     DevBuf af, gaf, gm, lc, fl[TPG_STREAM_MAX_FST], fd[TPG_STREAM_MAX_FST], dc, ds, dv;
+    DevBuf hw, gcn, ghw;  // the QC pass: p-values, genotype counts per group, p-values per group
     hipEvent_t ev = nullptr, ev2 = nullptr;  // behind the per-locus kernels / behind the PCA's center and scale of the block
     int pending = 0;  // download tasks of this slot not finished yet
   } out[2];
@@ -176,6 +179,7 @@ struct StreamRun {
   // additive state
   tpg_pairwise* pw = nullptr;
   DevBuf d_K, d_fsum, d_fpart;
+  DevBuf d_icnt;  // the QC pass: n x 4 int32, the per-individual sums of the blocks so far (tpg_launch_indiv_accumulate)
   bool have_K = false;
   double fro = 0.0;
   struct Kept { tpg_view* v = nullptr; DevBuf dc, ds; int64_t q0 = 0, mb = 0; bool L_borrowed = false; };
@@ -290,6 +294,11 @@ struct StreamRun {
     for (int i = 0; i < j->nfst; i++)
       if (j->fst_by_locus[i]) outp += 8 * (size_t)j->P * (j->fst_return_num_dem ? 2 : 1);
     if (want_pca) outp += 16 + 8 * (size_t)j->k;
+    if (qc) {
+      if (qc->hwe_p) { outp += 8; per += 16; }  // (and the counts tpg_loci_hwe tests)
+      if (qc->grouped_counts) outp += 12 * (size_t)G;
+      if (qc->grouped_hwe_p) outp += 8 * (size_t)G;
+    }
     per += 2 * outp;
     if (impute) per += npad / 4;  // the imputed view's L beside the raw one
     if (want_pca) per += 16 + 24 + npad / 4 + (npad / 4) * 5 / 4;  // counts, weights, the class path's locus-major copy + sorted operands
@@ -300,6 +309,7 @@ struct StreamRun {
     if (want_pw) state += tpg_pairwise_buffer_bytes(n) + 8 * (size_t)n * (size_t)n * (size_t)((j->ibs ? 1 : 0) + (j->king ? 1 : 0) + (j->allele_sharing ? 1 : 0) + (j->grm ? 1 : 0));
     if (want_pca) state += 3 * 8 * (size_t)n * (size_t)n + 8 * (size_t)n * 64 * 6;  // K, a block's Gram, the class path's slabs; eigen blocks
     if (want_fst) state += 8 * 4 * (size_t)j->P * (size_t)j->nfst;
+    if (qc && qc->indiv_counts) state += 16 * (size_t)n;
     int64_t target_blocks;
     if (budget == 0) {
       // no bound: the pipeline's own optimum -- a handful of blocks (per-block fixed costs against overlap: 8 blocks of a
@@ -777,6 +787,102 @@ struct StreamRun {
     return TPG_OK;
   }
 
+  // ------------------------------------------------------------------ the QC pass (tpg_stream_qc)
+  // One view per block through the job's table; every per-locus output is the resident entry point's on that view (the exact
+  // tests run behind the counts on the device) and leaves with the block; the per-individual sums stay.
+  int setup_qc() {
+    const tpg_stream_qc_job* c = qc;
+    TPG_REQUIRE(c->loci_counts || c->hwe_p || c->grouped_counts || c->grouped_hwe_p || c->indiv_counts, TPG_EINVAL,
+                "the job asks for nothing");
+    TPG_REQUIRE(c->midp == 0 || c->midp == 1, TPG_EINVAL, "midp must be 0 or 1");
+    if (c->grouped_counts || c->grouped_hwe_p) {
+      TPG_REQUIRE(c->groupIds0 && c->ngroups >= 1, TPG_EINVAL, "grouped outputs need groupIds and ngroups");
+      for (int64_t i = 0; i < n; i++)
+        TPG_REQUIRE(c->groupIds0[i] >= 0 && c->groupIds0[i] < c->ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)", (long long)i,
+                    c->groupIds0[i], c->ngroups);
+    }
+    TPG_REQUIRE(!c->indiv_counts || m < (1ll << 31), TPG_EUNSUPPORTED, "per-individual counts of 2^31 loci or more do not fit int32");
+    want_loc = true;
+    code_loc = c->code256;
+    tab[0] = c->code256;
+    ntab = 1;
+    view_of_loc = 0;
+    return TPG_OK;
+  }
+
+  int sweep_qc() {
+    const tpg_stream_qc_job* c = qc;
+    TpgEnter _enter(ctx);
+    t_start = now();
+    base_used = device_used();
+    peak_used = base_used;
+    TPG_TRY(alloc_common());
+    const int G = c->ngroups;
+    const int64_t bmax = std::min<int64_t>(B, P1 - P0);
+    if (c->indiv_counts) {
+      TPG_TRY(d_icnt.alloc(16 * (size_t)n));
+      TPG_HIP(hipMemsetAsync(d_icnt.p, 0, 16 * (size_t)n, ctx->stream));
+    }
+    for (int s = 0; s < 2 && s < nblocks; s++) {
+      OutSlot& o = out[s];
+      if (c->loci_counts) TPG_TRY(o.lc.alloc(16 * (size_t)bmax));
+      if (c->hwe_p) TPG_TRY(o.hw.alloc(8 * (size_t)bmax));
+      if (c->grouped_counts) TPG_TRY(o.gcn.alloc(12 * (size_t)G * (size_t)bmax));
+      if (c->grouped_hwe_p) TPG_TRY(o.ghw.alloc(8 * (size_t)G * (size_t)bmax));
+    }
+    set_bedpack(tab[0]);
+    TPG_TRY(start_uploader());
+    for (int64_t b = 0; b < nblocks; b++) {
+      int64_t q0, q1;
+      block_range(b, &q0, &q1);
+      const int64_t mb = q1 - q0;
+      const int slot = (int)(b & 1);
+      stamp("wait for block", b);
+      TPG_TRY(wait_block(b));
+      const tpg_fbm f = block_fbm(slot, mb);
+      tpg_view* v[3];
+      struct Views {
+        tpg_view** v;
+        ~Views() { for (int t = 0; t < 3; t++) tpg_view_free(v[t]); }
+      } views{v};
+      TPG_TRY(make_views(&f, slot, v));
+      release_block(b);
+      stamp("packed", b);
+      OutSlot& o = out[slot];
+      TPG_TRY(wait_slot(slot));
+      const tpg_view* vl = v[0];
+      if (c->loci_counts) TPG_TRY(tpg_loci_counts(ctx, vl, o.lc.as<int32_t>()));
+      if (c->hwe_p) TPG_TRY(tpg_loci_hwe(ctx, vl, c->midp, o.hw.as<double>()));
+      if (c->grouped_counts) TPG_TRY(tpg_grouped_genotype_counts(ctx, vl, c->groupIds0, G, o.gcn.as<int32_t>()));
+      if (c->grouped_hwe_p) TPG_TRY(tpg_gt_grouped_hwe(ctx, vl, c->groupIds0, G, c->midp, o.ghw.as<double>()));
+      if (c->indiv_counts) TPG_TRY(tpg_launch_indiv_accumulate(ctx, vl, d_icnt.as<int32_t>()));
+      TPG_HIP(hipEventRecord(o.ev, ctx->stream));
+      // m x 4 int32 ROW-major: the block's rows are one contiguous piece; the three m x G count matrices are one m x 3G
+      if (c->loci_counts) TPG_TRY(rows_out(c->loci_counts, 16, 1, q0, o.lc.p, mb, 1, o.ev, slot));
+      TPG_TRY(rows_out(c->hwe_p, 8, m, q0, o.hw.p, mb, 1, o.ev, slot));
+      TPG_TRY(rows_out(c->grouped_counts, 4, m, q0, o.gcn.p, mb, 3 * (int64_t)G, o.ev, slot));
+      TPG_TRY(rows_out(c->grouped_hwe_p, 8, m, q0, o.ghw.p, mb, G, o.ev, slot));
+      stamp("per-locus enqueued", b);
+      sample();
+    }
+    up_th.join();
+    if (sh.failed) { tpg_set_error("%s", sh.msg.c_str()); return sh.code; }
+    if (c->indiv_counts) {  // n0 from the number of loci swept
+      OutBuf o;
+      TPG_TRY(o.init(c->indiv_counts, 16 * (size_t)n));
+      TPG_TRY(tpg_launch_indiv_finish(ctx, d_icnt.as<int32_t>(), n, P1 - P0, o.dev<int32_t>()));
+      TPG_HIP(hipStreamSynchronize(ctx->stream));
+      TPG_TRY(o.commit(ctx));
+      if (o.owned) {
+        std::lock_guard<std::mutex> lk(sh.mu);
+        bytes_down += 16 * (size_t)n;
+      }
+    }
+    t_sweep1 = now() - t_start;
+    stamp("sweep enqueued");
+    return TPG_OK;
+  }
+
   // ------------------------------------------------------------------ after the sweep
   // phase A (rank-local + exchanges): pairwise epilogues, Fst ratios, Gram all-reduce; phase B: eigen step, loadings
   int finish() {
@@ -956,6 +1062,7 @@ struct StreamRun {
         if (d_blk[k]) { tpg_pfree(d_blk[k]); d_blk[k] = nullptr; }
         OutSlot& o = out[k];
         o.af.free(); o.gaf.free(); o.gm.free(); o.lc.free(); o.dc.free(); o.ds.free(); o.dv.free();
+      o.hw.free(); o.gcn.free(); o.ghw.free();
         for (int i = 0; i < TPG_STREAM_MAX_FST; i++) { o.fl[i].free(); o.fd[i].free(); }
         if (o.ev) { (void)hipEventDestroy(o.ev); o.ev = nullptr; }
         if (o.ev2) { (void)hipEventDestroy(o.ev2); o.ev2 = nullptr; }
@@ -964,7 +1071,7 @@ struct StreamRun {
         d_nn[k].free();
         if (ev_fin[k]) { (void)hipEventDestroy(ev_fin[k]); ev_fin[k] = nullptr; }
       }
-      d_K.free(); d_fsum.free(); d_fpart.free(); d_u.free();
+      d_K.free(); d_fsum.free(); d_fpart.free(); d_u.free(); d_icnt.free();
     }
     if (own_workers) {
       if (up_ctx) tpg_ctx_destroy(up_ctx);
@@ -1154,6 +1261,55 @@ extern "C" int tpg_stream_run(tpg_ctx* ctx, tpg_stream* s, const tpg_stream_job*
   TPG_TRY(run.plan());
   int rc = run.sweep1();
   if (rc == TPG_OK) rc = run.finish();
+  const int rc2 = run.end();
+  if (rc == TPG_OK) rc = rc2;
+  std::string err = rc == TPG_OK ? "" : tpg_last_error();
+  fill_report(run, s->budget, report);
+  run.cleanup();
+  if (rc != TPG_OK) tpg_set_error("%s", err.c_str());
+  return rc;
+}
+
+// The QC pass: the same run object with the job's selection, table and groups, and the QC outputs beside it.
+extern "C" int tpg_stream_qc(tpg_ctx* ctx, tpg_stream* s, const tpg_stream_qc_job* qc, tpg_stream_report* report) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && s && qc, TPG_EINVAL, "null argument");
+  TPG_REQUIRE(qc->struct_size == sizeof(tpg_stream_qc_job), TPG_EINVAL, "tpg_stream_qc_job of %zu bytes, this library's has %zu",
+              qc->struct_size, sizeof(tpg_stream_qc_job));
+  TPG_REQUIRE(s->ctx == ctx, TPG_EINVAL, "the stream was opened on another context");
+  tpg_stream_job base;
+  memset(&base, 0, sizeof(base));
+  base.struct_size = sizeof(base);
+  base.rowInd1 = qc->rowInd1;
+  base.n = qc->n;
+  base.colInd1 = qc->colInd1;
+  base.m = qc->m;
+  base.code256 = qc->code256;
+  if (qc->grouped_counts || qc->grouped_hwe_p) {  // (the plan counts the per-class tables of a block when there are groups)
+    base.groupIds0 = qc->groupIds0;
+    base.ngroups = qc->ngroups;
+  }
+  base.loci_counts = qc->loci_counts;
+  int64_t n = 0, m = 0;
+  TPG_TRY(check_job(s, &base, &n, &m));
+  StreamRun run;
+  run.ctx = ctx;
+  run.src = &s->src;
+  run.job = &base;
+  run.qc = qc;
+  run.budget = s->budget;
+  run.n = n;
+  run.m = m;
+  run.P0 = 0;
+  run.P1 = m;
+  TPG_TRY(run.setup_qc());
+  if (!s->up_ctx) TPG_TRY(tpg_ctx_create(ctx->device, &s->up_ctx));
+  if (!s->down_ctx) TPG_TRY(tpg_ctx_create(ctx->device, &s->down_ctx));
+  run.up_ctx = s->up_ctx;
+  run.down_ctx = s->down_ctx;
+  run.own_workers = false;
+  TPG_TRY(run.plan());
+  int rc = run.sweep_qc();
   const int rc2 = run.end();
   if (rc == TPG_OK) rc = rc2;
   std::string err = rc == TPG_OK ? "" : tpg_last_error();
