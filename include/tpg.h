@@ -207,6 +207,42 @@ int tpg_loci_hwe(tpg_ctx* ctx, const tpg_view* v, int midp, double* p);
  * n = 0 value */
 int tpg_gt_grouped_hwe(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, int midp, double* p);
 
+/* ---- LD clumping (loci_ld_clump, R/loci_ld_clump.R:84-184 around bigsnpr::snp_clumping) --------------------------------
+ * bigsnpr's function is not part of the reference checkout, so the definition below is this project's own.
+ * Input: a view of n individuals x m loci in which every code is 0, 1 or 2.  A missing genotype: TPG_ENUMERIC, no output
+ *   written (the reference stops on it; impute the view first).  n >= 2^22: TPG_EUNSUPPORTED.
+ * Window: hi[m], int64, 0-based inclusive, hi[j] >= j, hi[j] < m, non-decreasing in j (anything else: TPG_EINVAL).  Loci
+ *   j < k are NEIGHBOURS iff k <= hi[j]; the host layers derive hi from (chromosome, position, size).
+ * Edge: with the int64 sums Sx = sum x, Sxx = sum x^2 over the individuals of a locus, Sxy = sum x_j x_k,
+ *   num = n Sxy - Sx_j Sx_k and d_j = n Sxx_j - Sx_j^2, neighbours j and k are LINKED iff
+ *       (double)num * (double)num > thr_r2 * ((double)d_j * (double)d_k)
+ *   evaluated in exactly this order in IEEE double, no FMA contraction (r^2 > thr_r2 without a division).  A monomorphic
+ *   locus (d = 0) is linked to nothing.  thr_r2 in [0, 1].
+ * Priority: the larger key is the more important locus: the caller's S (m doubles; a NaN: TPG_EINVAL), or with S == NULL
+ *   the minor allele count min(Sx, 2 n - Sx) as an integer (the order of the MAF, without rounding).  Ties go to the
+ *   smaller locus index (R's stable order(S, decreasing = TRUE)).
+ * Exclusion: exclude (m bytes, may be NULL): an excluded locus is never kept and removes nobody.
+ * Result: the sequential greedy set -- walk the loci by priority; a locus still standing is kept and every locus linked
+ *   to it falls.  Equivalently the unique set in which a non-excluded locus is kept iff no linked locus of higher priority
+ *   is kept.  keep[m] bytes (0 / 1); deterministic, independent of blocking and launch geometry.
+ * hi, S and exclude may be host or device memory, bits and keep too; an output must not overlap an input. */
+/* the link relation as a bit band: row j = stride_words uint32, bit b of the row (bit b & 31 of word b >> 5) <-> locus
+ * j + 1 + b; stride_words >= ceil(max_j(hi[j] - j) / 32); bits outside the window are 0.  *n_links (host, may be NULL) =
+ * number of linked pairs. */
+int tpg_ld_band_links(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, double thr_r2, uint32_t* bits,
+                      int64_t stride_words, int64_t* n_links);
+typedef struct tpg_ld_report {
+  int64_t links;       /* linked pairs found */
+  int64_t kept;        /* loci kept */
+  int64_t rounds;      /* parallel resolution rounds run (at most 32; every round decides at least one locus) */
+  int64_t finish_loci; /* loci the bounded rounds left undecided: decided by one wave walking them in priority order */
+  int64_t band_bytes;  /* HBM held by the band (both orientations) during the call */
+} tpg_ld_report;
+/* band, priority order and greedy resolution on the device: only keep comes down (no r^2 value and no part of the band
+ * crosses PCIe).  report may be NULL. */
+int tpg_ld_clump(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, double thr_r2, const double* S,
+                 const uint8_t* exclude, uint8_t* keep, tpg_ld_report* report);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

@@ -884,7 +884,7 @@ SEXP _tidypopgen_tpg_pca_partial_svd(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k) 
 #pragma weak tpg_hwe_exact_counts
 #pragma weak tpg_loci_hwe
 #pragma weak tpg_gt_grouped_hwe
-#define HWE_NEEDS(sym) \
+#define TPG_NEEDS(sym) \
   do { \
     if (!(sym)) Rf_error("tidypopgen (GPU): this libtpg_hip has no " #sym); \
   } while (0)
@@ -909,7 +909,7 @@ SEXP _tidypopgen_SNPHWE2_R(SEXP obs_hets, SEXP obs_hom1, SEXP obs_hom2, SEXP mid
 /* hwe_on_matrix(geno_counts, midp)   src/hwe.cpp:203-213: rows 1..3 of a big_counts matrix (hom1, het, hom2; its fourth
    row, the NA count, is not read) -> one p-value per column */
 SEXP _tidypopgen_hwe_on_matrix(SEXP geno_counts, SEXP midp) {
-  HWE_NEEDS(tpg_hwe_exact_counts);
+  TPG_NEEDS(tpg_hwe_exact_counts);
   const int mid = midp_of(midp);
   SEXP gc = PROTECT(as_int(geno_counts));
   SEXP dim = Rf_getAttrib(gc, R_DimSymbol);
@@ -932,7 +932,7 @@ SEXP _tidypopgen_hwe_on_matrix(SEXP geno_counts, SEXP midp) {
 
 /* gt_grouped_hwe(BM, rowInd, colInd, groupIds, ngroups, midp)   src/hwe.cpp:220-253 -> m x G */
 SEXP _tidypopgen_gt_grouped_hwe(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP midp) {
-  HWE_NEEDS(tpg_gt_grouped_hwe);
+  TPG_NEEDS(tpg_gt_grouped_hwe);
   const int G = ngroups_of(ngroups), mid = midp_of(midp);
   SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
@@ -947,7 +947,7 @@ SEXP _tidypopgen_gt_grouped_hwe(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds
 /* tpg_loci_hwe(BM, rowInd, colInd, midp): the whole of R/loci_hwe.R:74-89 (big_counts + hwe_on_matrix per block) in one
    call -> one p-value per locus */
 SEXP _tidypopgen_tpg_loci_hwe(SEXP BM, SEXP rowInd, SEXP colInd, SEXP midp) {
-  HWE_NEEDS(tpg_loci_hwe);
+  TPG_NEEDS(tpg_loci_hwe);
   const int mid = midp_of(midp);
   SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
   if (XLENGTH(ri) < 2) Rf_error("Not implemented for a single individual"); /* R/loci_hwe.R:92 */
@@ -955,6 +955,47 @@ SEXP _tidypopgen_tpg_loci_hwe(SEXP BM, SEXP rowInd, SEXP colInd, SEXP midp) {
   tpg_view* v = view_of(BM, ri, ci, 0);
   TPG_R_VIEW(v, tpg_loci_hwe(ctx(), v, mid, REAL(out)));
   UNPROTECT(3);
+  return out;
+}
+
+/* ---- LD clumping ---------------------------------------------------------------------------------------------- */
+
+#pragma weak tpg_ld_clump
+
+/* tpg_ld_clump(BM, rowInd, colInd, hi, thr_r2, S, exclude): the bigsnpr::snp_clumping call of R/loci_ld_clump.R:161-174 on
+ * the loci of colInd, in one call -> a logical per locus of colInd (include/tpg.h "LD clumping" is the definition).  hi[j] =
+ * the 1-based position in colInd of the last neighbour of locus j (>= j, non-decreasing), integer or double; S = NULL or one
+ * double per locus; exclude = NULL or one logical per locus.  A missing genotype is an R error, as in the reference. */
+SEXP _tidypopgen_tpg_ld_clump(SEXP BM, SEXP rowInd, SEXP colInd, SEXP hi, SEXP thr_r2, SEXP S, SEXP exclude) {
+  TPG_NEEDS(tpg_ld_clump);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP hr = PROTECT(as_real(hi)), tr = PROTECT(as_real(thr_r2));
+  if (XLENGTH(tr) != 1) Rf_error("tidypopgen (GPU): thr_r2 must be one number");
+  const double thr = REAL(tr)[0];
+  SEXP sr = PROTECT(S == R_NilValue ? R_NilValue : as_real(S));
+  SEXP ex = PROTECT(exclude == R_NilValue ? R_NilValue : Rf_coerceVector(exclude, LGLSXP));
+  const R_xlen_t m = XLENGTH(ci);
+  if (XLENGTH(hr) != m) Rf_error("tidypopgen (GPU): hi and colInd differ in length");
+  if (sr != R_NilValue && XLENGTH(sr) != m) Rf_error("tidypopgen (GPU): S and colInd differ in length");
+  if (ex != R_NilValue && XLENGTH(ex) != m) Rf_error("tidypopgen (GPU): exclude and colInd differ in length");
+  SEXP out = PROTECT(Rf_allocVector(LGLSXP, m));
+  int64_t* h0 = (int64_t*)R_alloc((size_t)(m > 0 ? m : 1), sizeof(int64_t));
+  uint8_t* x8 = (uint8_t*)R_alloc((size_t)(m > 0 ? m : 1), 1); /* exclude */
+  uint8_t* k8 = (uint8_t*)R_alloc((size_t)(m > 0 ? m : 1), 1); /* keep */
+  for (R_xlen_t j = 0; j < m; j++) {
+    const double v = REAL(hr)[j];
+    if (!(v >= 1 && v <= (double)m)) Rf_error("tidypopgen (GPU): hi[%lld] is NA or out of [1,%lld]", (long long)j + 1, (long long)m);
+    h0[j] = (int64_t)v - 1;
+    x8[j] = 0;
+    if (ex != R_NilValue) {
+      if (LOGICAL(ex)[j] == NA_LOGICAL) Rf_error("tidypopgen (GPU): NA in exclude");
+      x8[j] = LOGICAL(ex)[j] != 0;
+    }
+  }
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_ld_clump(ctx(), v, h0, thr, sr == R_NilValue ? NULL : REAL(sr), ex == R_NilValue ? NULL : x8, k8, NULL));
+  for (R_xlen_t j = 0; j < m; j++) LOGICAL(out)[j] = k8[j] != 0;
+  UNPROTECT(7);
   return out;
 }
 
@@ -1004,18 +1045,25 @@ const R_CallMethodDef tpg_rshim_entries_hwe[] = {
     {"_tidypopgen_tpg_loci_hwe", (DL_FUNC)&_tidypopgen_tpg_loci_hwe, 4},
     {NULL, NULL, 0}};
 
+/* LD clumping, in a table of its own as well: the reference has no native row for it (its clumping is bigsnpr's). */
+const R_CallMethodDef tpg_rshim_entries_ld[] = {
+    {"_tidypopgen_tpg_ld_clump", (DL_FUNC)&_tidypopgen_tpg_ld_clump, 7},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the three tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the four tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
-                             sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0])];
+                             sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
+                             sizeof(tpg_rshim_entries_ld) / sizeof(tpg_rshim_entries_ld[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_hwe; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_ld; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

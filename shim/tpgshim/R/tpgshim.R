@@ -80,6 +80,32 @@ tpg_loci_hwe <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigsta
   .Call(`_tidypopgen_tpg_loci_hwe`, X, as.integer(ind.row), as.integer(ind.col), isTRUE(mid_p))
 }
 
+# LD clumping of the loci ind.col in one call (the bigsnpr::snp_clumping call of R/loci_ld_clump.R:161-174; include/tpg.h
+# "LD clumping" is the definition).  infos.chr / infos.pos describe the loci of ind.col, which must be ordered; exclude =
+# positions in ind.col never to keep.  Returns a logical per locus of ind.col.  A missing genotype is an error.
+tpg_ld_clump <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), infos.chr,
+                         infos.pos = NULL, S = NULL, thr.r2 = 0.2, size = 100 / thr.r2, exclude = NULL) {
+  m <- length(ind.col)
+  hi <- integer(m)
+  for (idx in split(seq_len(m), infos.chr)) {
+    if (any(diff(idx) != 1L)) stop("loci are not ordered: a chromosome appears in more than one run")
+    if (is.null(infos.pos)) {
+      hi[idx] <- pmin(idx + floor(size), idx[length(idx)])
+    } else {
+      p <- infos.pos[idx]
+      if (is.unsorted(p)) stop("loci are not ordered: positions decrease inside a chromosome")
+      hi[idx] <- idx[1] - 1L + findInterval(p + size * 1000, p)
+    }
+  }
+  ex <- NULL
+  if (length(exclude) > 0) {
+    ex <- logical(m)
+    ex[exclude] <- TRUE
+  }
+  .Call(`_tidypopgen_tpg_ld_clump`, X, as.integer(ind.row), as.integer(ind.col), hi, as.numeric(thr.r2),
+        if (is.null(S)) NULL else as.numeric(S), ex)
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

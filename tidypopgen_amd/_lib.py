@@ -100,6 +100,7 @@ SYMBOLS = [
     "tpg_stream_open_host", "tpg_stream_open_bk", "tpg_stream_open_bed", "tpg_stream_open_bed_host", "tpg_stream_open_synth",
     "tpg_stream_close", "tpg_stream_run", "tpg_multi_stream_run", "tpg_fbm_impute_simple", "tpg_fbm_impute_simple_at", "tpg_view_impute",
     "tpg_hwe_exact_counts", "tpg_loci_hwe", "tpg_gt_grouped_hwe", "tpg_stream_qc",
+    "tpg_ld_band_links", "tpg_ld_clump",
 ]
 
 
@@ -136,6 +137,12 @@ class ImputeReport(C.Structure):
     _fields_ = [("imputed", C.c_int64), ("loci_all_missing", C.c_int64)]
 
 
+class LdReport(C.Structure):
+    """tpg_ld_report of include/tpg.h"""
+    _fields_ = [("links", C.c_int64), ("kept", C.c_int64), ("rounds", C.c_int64), ("finish_loci", C.c_int64),
+                ("band_bytes", C.c_int64)]
+
+
 class StreamReport(C.Structure):
     """tpg_stream_report of include/tpg.h"""
     _fields_ = [
@@ -156,6 +163,9 @@ if hasattr(lib, "tpg_loci_hwe"):
     lib.tpg_gt_grouped_hwe.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
 if hasattr(lib, "tpg_stream_qc"):
     lib.tpg_stream_qc.argtypes = [vp, vp, C.POINTER(StreamQcJob), C.POINTER(StreamReport)]
+if hasattr(lib, "tpg_ld_clump"):
+    lib.tpg_ld_band_links.argtypes = [vp, vp, vp, C.c_double, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.tpg_ld_clump.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp, C.POINTER(LdReport)]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

@@ -1546,6 +1546,101 @@ def gt_pca_partialSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, total_var
     return out
 
 
+def ld_window_hi(chromosome, position=None, size=500.0, use_positions: bool = True, m: Optional[int] = None) -> np.ndarray:
+    """the window of include/tpg.h "LD clumping": hi[j] = last locus (0-based) that is a neighbour of j.  With positions,
+    neighbours are loci of the same chromosome with |position difference| <= size * 1000; without, loci of the same
+    chromosome with |index difference| <= size.  Loci must be ordered: every chromosome one contiguous run, positions
+    non-decreasing inside it (is_loci_table_ordered stops the reference otherwise).  chromosome = None: one chromosome."""
+    if chromosome is None:
+        if m is None:
+            m = len(position)
+        chrom = np.zeros(m, dtype=np.int64)
+    else:
+        chrom = np.unique(np.asarray(chromosome), return_inverse=True)[1].astype(np.int64).ravel()
+    m = len(chrom)
+    starts = np.r_[0, np.flatnonzero(chrom[1:] != chrom[:-1]) + 1, m] if m else np.array([0, 0])
+    if len(np.unique(chrom[starts[:-1]])) != len(starts) - 1:
+        raise ValueError("loci are not ordered: a chromosome appears in more than one run")
+    hi = np.empty(m, dtype=np.int64)
+    if use_positions:
+        if position is None:
+            raise ValueError("use_positions = True needs the positions of the loci")
+        pos = np.asarray(position, dtype=np.float64)
+        if len(pos) != m:
+            raise ValueError("chromosome and position differ in length")
+    for a, b in zip(starts[:-1], starts[1:]):
+        if use_positions:
+            p = pos[a:b]
+            if np.any(p[1:] < p[:-1]):
+                raise ValueError("loci are not ordered: positions decrease inside a chromosome")
+            hi[a:b] = a + np.searchsorted(p, p + float(size) * 1000.0, side="right") - 1
+        else:
+            hi[a:b] = np.minimum(np.arange(a, b) + int(math.floor(size)), b - 1)
+    return hi
+
+
+def _ld_hi(v: View, hi) -> np.ndarray:
+    hi = np.ascontiguousarray(hi, dtype=np.int64)
+    if hi.shape != (v.m,):
+        raise ValueError("hi must have one entry per locus of the view")
+    return hi
+
+
+def ld_band_links(v: View, hi, thr_r2: float = 0.2, return_links: bool = False):
+    """tpg_ld_band_links: the link relation of neighbouring loci as a bit band, (m, stride) uint32: bit b of row j <->
+    locus j + 1 + b is linked to j (include/tpg.h "LD clumping")"""
+    hi = _ld_hi(v, hi)
+    width = int((hi - np.arange(v.m)).max(initial=0))
+    bits = np.zeros((v.m, max(1, -(-width // 32))), dtype=np.uint32)
+    links = C.c_int64()
+    check(lib.tpg_ld_band_links(v.ctx.h, v.h, _ptr(hi), C.c_double(thr_r2), _ptr(bits), C.c_int64(bits.shape[1]), C.byref(links)))
+    return (bits, int(links.value)) if return_links else bits
+
+
+def ld_clump(v: View, hi, thr_r2: float = 0.2, S=None, exclude=None, return_report: bool = False):
+    """tpg_ld_clump on a view without missing genotypes: keep (m,) bool; exclude = (m,) 0 / 1"""
+    hi = _ld_hi(v, hi)
+    s = _f64(S)
+    ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint8)
+    if (s is not None and s.shape != (v.m,)) or (ex is not None and ex.shape != (v.m,)):
+        raise ValueError("S and exclude must have one entry per locus of the view")
+    keep = np.zeros(v.m, dtype=np.uint8)
+    rep = _lib.LdReport()
+    check(lib.tpg_ld_clump(v.ctx.h, v.h, _ptr(hi), C.c_double(thr_r2), _ptr(s), _ptr(ex), _ptr(keep), C.byref(rep)))
+    keep = keep.astype(bool)
+    if return_report:
+        return keep, {f: int(getattr(rep, f)) for f, _ in _lib.LdReport._fields_}
+    return keep
+
+
+def loci_ld_clump(X: FBM, ind_row=None, ind_col=None, S=None, thr_r2: float = 0.2, size=None, chromosome=None,
+                  position=None, use_positions: bool = True, exclude=None, return_id: bool = False,
+                  impute: Optional[str] = None, impute_seed: int = 0):
+    """R/loci_ld_clump.R:84-184 (around bigsnpr::snp_clumping; the definition is include/tpg.h "LD clumping"): loci are
+    walked by decreasing S (default: minor allele frequency), a locus still standing is kept and removes its neighbours with
+    r^2 > thr_r2.  chromosome / position describe the loci of ind_col, in order; without positions pass
+    use_positions = False.  exclude = 1-based indices of loci never to keep.  A missing genotype is an error, as in the
+    reference, unless impute = "mode" | "mean0" | "random" fills the view first (as for the PCA).  Returns a boolean per
+    locus, or with return_id the 1-based indices of the kept loci."""
+    if size is None:
+        size = 100.0 / thr_r2
+    v = _pca_view(X, ind_row, ind_col, "fbm", impute, impute_seed)
+    if use_positions and position is None:
+        raise ValueError("use_positions = TRUE needs positions; pass use_positions=False to count in loci")
+    hi = ld_window_hi(chromosome, position, size, use_positions, m=v.m)
+    if len(hi) != v.m:
+        raise ValueError("chromosome / position must describe every locus of ind_col")
+    ex = None
+    if exclude is not None and len(exclude) > 0:
+        e = np.asarray(exclude, dtype=np.int64)
+        if e.min() < 1 or e.max() > v.m:
+            raise ValueError("exclude out of range")
+        ex = np.zeros(v.m, dtype=np.uint8)
+        ex[e - 1] = 1
+    keep = ld_clump(v, hi, thr_r2, S, ex)
+    return np.flatnonzero(keep) + 1 if return_id else keep
+
+
 def gt_impute_simple(X: FBM, method: str = "mode", seed: int = 0) -> FBM:
     """R/gt_impute_simple.R:54-93: the missing genotypes of X are filled in place (FBM.impute_simple) and X then reads
     through CODE_IMPUTE_PRED, as the reference leaves the gen_tibble's FBM; the report is left in `X.impute_report`.
