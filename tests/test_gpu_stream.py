@@ -474,3 +474,36 @@ def test_stream_api_from_c(tpg, tmp_path):
     assert np.allclose([float(x) for x in got["d"]], s["d"], rtol=1e-12)
     assert float(got["fro"][0]) == pytest.approx(s["square_frobenius"], rel=1e-14)
     assert float(got["center_sum"][0]) == pytest.approx(s["center"].sum(), rel=1e-14)
+
+
+def test_stream_batched_digit_gram_returns_its_T_layout(tpg, monkeypatch):
+    """A run without a budget lays its kept views' L layouts end to end and takes the Gram matrix of the whole buffer through a
+    borrowed view; with the digit kernel chosen, tpg_view_need_T hangs a T layout (bytes_each = 2 x 512 x 4 KiB = 4 MiB here)
+    on that view, and the view must give it back.  Four blocks of 16 384 loci; the device's used memory, read through the HIP
+    runtime the library runs on (tests/test_gpu_parity.py says why not torch), may grow by less than one such block over four
+    runs after a warm-up -- one block lost per run is 16 MiB.  (No other process allocates on this GPU meanwhile.)"""
+    import ctypes as C
+
+    monkeypatch.setenv("TPG_STREAM_BLOCKS", "4")
+    monkeypatch.setenv("TPG_GRAM_DIGITS", "1")
+    hip = C.CDLL("libamdhip64.so.7")
+
+    def used():
+        fr, tot = C.c_size_t(), C.c_size_t()
+        assert hip.hipMemGetInfo(C.byref(fr), C.byref(tot)) == 0
+        return tot.value - fr.value
+
+    ctx = tpg.Context(0)
+    st = tpg.Stream.synth(9, 256, 65536, npop=4, imputed_bytes=True, budget_bytes=0, ctx=ctx)
+    rep = st.run(k=4)["report"]  # warms the pools
+    assert rep["blocks"] == 4 and rep["block_loci"] == 16384 and rep["views_kept"]
+    ctx.sync()
+    before = used()
+    for _ in range(4):
+        st.run(k=4)
+    ctx.sync()
+    grown = used() - before
+    print("device memory grown over four runs:", grown, "bytes")
+    st.close()
+    ctx.close()
+    assert grown < 4 << 20, grown

@@ -354,10 +354,11 @@ bool tpg_comm_alltoall_usable(tpg_comm* comm) {
     off[(size_t)d] = (size_t)d * W;
     for (int w = 0; w < W; w++) hs[(size_t)d * W + w] = 0x5450470000000000ull + (uint64_t)me * 65536 + (uint64_t)d * 256 + (uint64_t)w;
   }
-  uint64_t *ds = nullptr, *dr = nullptr;
+  DevBuf sbuf, rbuf;
   int rc = TPG_OK;
   hipStream_t s = comm->ctx->stream;
-  if (tpg_pmalloc((void**)&ds, 8 * hs.size()) != hipSuccess || tpg_pmalloc((void**)&dr, 8 * hr.size()) != hipSuccess) rc = TPG_EHIP;
+  if (sbuf.alloc(8 * hs.size()) != TPG_OK || rbuf.alloc(8 * hr.size()) != TPG_OK) rc = TPG_EHIP;
+  uint64_t *const ds = sbuf.as<uint64_t>(), *const dr = rbuf.as<uint64_t>();
   rc = tpg_comm_agree(comm, rc);
   if (rc == TPG_OK) {
     if (hipMemcpyAsync(ds, hs.data(), 8 * hs.size(), hipMemcpyHostToDevice, s) != hipSuccess) rc = TPG_EHIP;
@@ -375,8 +376,6 @@ bool tpg_comm_alltoall_usable(tpg_comm* comm) {
           if (hr[(size_t)r * W + w] != 0x5450470000000000ull + (uint64_t)r * 65536 + (uint64_t)me * 256 + (uint64_t)w) rc = TPG_EHIP;
     rc = tpg_comm_agree(comm, rc);
   }
-  tpg_pfree(ds);
-  tpg_pfree(dr);
   comm->a2a_state = rc == TPG_OK ? 1 : -1;
   if (rc != TPG_OK && tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] all-to-all self-test failed on this communicator: no class exchange\n");
   return rc == TPG_OK;
@@ -410,17 +409,13 @@ extern "C" int tpg_comm_allreduce_f64(tpg_ctx* ctx, tpg_comm* comm, double* buf,
     TPG_REQUIRE(rc == 0, TPG_EHIP, "the host all-reduce callback failed (%d)", rc);
     return TPG_OK;
   }
-  double* d = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d, sizeof(double) * (size_t)count));
-  hipError_t e = hipMemcpyAsync(d, buf, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream);
-  int rc = e == hipSuccess ? tpg_comm_allreduce(comm, d, count, 1) : TPG_EHIP;
-  if (rc == TPG_OK) {
-    e = hipMemcpyAsync(buf, d, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  }
-  tpg_pfree(d);
-  if (e != hipSuccess) { tpg_set_error("all-reduce staging: %s", hipGetErrorString(e)); return TPG_EHIP; }
-  return rc;
+  DevBuf d;
+  TPG_TRY(d.alloc_n<double>((size_t)count));
+  TPG_HIP(hipMemcpyAsync(d.p, buf, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+  TPG_TRY(tpg_comm_allreduce(comm, d.p, count, 1));
+  TPG_HIP(hipMemcpyAsync(buf, d.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
+  return TPG_OK;
 }
 
 // Contiguous locus range [begin, end) of `rank`: boundaries on multiples of 128 loci (the K-group width of the packed
@@ -606,13 +601,6 @@ static int multi_rows_to_caller(tpg_ctx* ctx, double* dst, int64_t m, int64_t j0
   return TPG_OK;
 }
 
-struct PoolBuf {  // device scratch of one device thread, back to its pool on scope exit
-  void* p = nullptr;
-  int alloc(size_t bytes) { TPG_HIP(tpg_pmalloc(&p, bytes ? bytes : 16)); return TPG_OK; }
-  ~PoolBuf() { tpg_pfree(p); }
-  template <typename T> T* as() { return (T*)p; }
-};
-
 // A device holds its share of the panel whole (one upload, one pack) unless the share's bytes exceed the streaming budget:
 // then the call is the streamed form (stream.hip: every device sweeps its share in blocks, two block buffers, the same
 // exchanges afterwards) -- a 5 000 x 80 000 000 panel (400 GB) goes through the same entry points as a 5-GB one.
@@ -726,7 +714,7 @@ extern "C" int tpg_multi_grouped_alt_freq(tpg_multi* mg, const uint8_t* fbm_byte
     TPG_TRY(multi_shard_view(mg, r, fbm_bytes, nrow, rowInd1, n, colInd1, m, code256, &me));
     if (!me.v) return TPG_OK;
     const int64_t ml = me.j1 - me.j0;
-    PoolBuf d_out;
+    DevBuf d_out;
     TPG_TRY(d_out.alloc(sizeof(double) * (size_t)ml * (size_t)ncols));
     if (groupIds0) TPG_TRY(tpg_grouped_alt_freq_dip_pseudo(ctx, me.v, groupIds0, ngroups, ploidy, as_counts, d_out.as<double>()));
     else TPG_TRY(tpg_alt_freq_dip_pseudo(ctx, me.v, ploidy, as_counts, d_out.as<double>()));
@@ -784,7 +772,7 @@ extern "C" int tpg_multi_pop_fst(tpg_multi* mg, const uint8_t* fbm_bytes, int64_
     double* sn = sums[(size_t)r].data();
     if (!return_num_dem) TPG_TRY(tpg_pairwise_pop_fst_sums(ctx, me.v, groupIds0, ngroups, ploidy, method, pairs1, P, sn, sn + P));
     if (!by_locus) return TPG_OK;
-    PoolBuf da, db;
+    DevBuf da, db;
     TPG_TRY(da.alloc(sizeof(double) * (size_t)ml * (size_t)P));
     if (return_num_dem) TPG_TRY(db.alloc(sizeof(double) * (size_t)ml * (size_t)P));
     std::vector<double> tot((size_t)P);  // this shard's own ratios: not what the caller asked for
@@ -876,7 +864,7 @@ extern "C" int tpg_multi_pca_partial_svd(tpg_multi* mg, const uint8_t* fbm_bytes
       TpgEnter _enter(ctx);
       MultiShard& me = st[(size_t)r];
       const int64_t ml = me.j1 - me.j0;
-      PoolBuf dv, dc, ds, du, dd;
+      DevBuf dv, dc, ds, du, dd;
       // rank-local steps that can fail sit inside tpg_pca_partial_svd_sharded BEFORE its first exchange, where the ranks
       // agree on a status (tpg_comm_agree): nobody is left waiting in a collective
       int lrc = dv.alloc(sizeof(double) * (size_t)ml * (size_t)k);

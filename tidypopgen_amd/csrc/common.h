@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <vector>
@@ -147,13 +148,17 @@ struct GroupedCounts {
   ~GroupedCounts();
 };
 
+static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// A view owns its layouts: the destructor returns T, L, T4, lc_part and the cached counts to the pool.
 struct tpg_view {
   tpg_ctx* ctx;
   int64_t n, m;    // kept individuals / loci
   int64_t Q, KG;   // ceil(n/128), ceil(m/128)
-  mutable uint4* T;  // (4Q) row tiles x KG blocks; NULL in the views of tpg_view_create_pair until somebody needs it
-                     // (tpg_view_need_T builds it from L)
+  mutable uint4* T = nullptr;  // (4Q) row tiles x KG blocks; NULL in the views of tpg_view_create_pair until somebody needs it
+                               // (tpg_view_need_T builds it from L)
   uint4* L;        // (4KG) locus tiles x Q blocks
+  bool L_borrowed = false;  // L points into somebody else's block (stream.hip: the kept views' layouts end to end): not freed here
   size_t bytes_each;
   // T re-coded as FP4 (E2M1) operand nibbles for the pairwise kernel (pairwise.hip); written by the pack kernel for
   // the first view of tpg_view_create_pair, otherwise made from T on the first tpg_pairwise_accumulate; 2 x bytes_each
@@ -168,7 +173,17 @@ struct tpg_view {
   uint32_t* lc_part = nullptr;
   int lc_chunks = 0;
   int64_t lc_row = 0;
+
+  // n x m with no layout yet, or with somebody else's L (borrowed: a piece of a longer locus-tiled buffer)
+  tpg_view(tpg_ctx* c, int64_t n_, int64_t m_, uint4* borrowed_L = nullptr)
+      : ctx(c), n(n_), m(m_), Q(ceil_div(n_, 128)), KG(ceil_div(m_, 128)), L(borrowed_L), L_borrowed(borrowed_L != nullptr),
+        bytes_each((size_t)Q * (size_t)KG * 4096) {}
+  tpg_view(const tpg_view&) = delete;
+  tpg_view& operator=(const tpg_view&) = delete;
+  ~tpg_view();          // runtime.hip
+  void drop_derived();  // release everything that can be rebuilt from L: T, T4, lc_part and the cached counts
 };
+typedef std::unique_ptr<tpg_view> ViewPtr;
 
 // tile-packed int32 accumulators of the pairwise kernel: per unit (super-tile I of TPG_PW_TA row tiles, 32-column
 // tile jt >= TA I) 5 products x TA sub-tiles x 16 accumulator registers x 64 lanes (MFMA C/D order)
@@ -213,8 +228,6 @@ static inline int tpg_pw_products_for(bool ibs, bool king, bool as_or_grm) {
   if (ibs && !king && !as_or_grm) return TPG_PW_FOR_IBS_ALONE;
   return (ibs ? TPG_PW_FOR_IBS : 0) | (king ? TPG_PW_FOR_KING : 0) | (as_or_grm ? TPG_PW_FOR_AS : 0);
 }
-
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // The TPG_* environment switches (INTEGRATION.md "Environment" has the list; tests/test_env_switches.py keeps it true).  Both
 // read the environment on every call: a site that wants one read per process keeps the result in a static.
@@ -272,6 +285,39 @@ static inline int tpg_dmalloc(T** p, size_t count) {
   TPG_HIP(hipMalloc((void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
   return TPG_OK;
 }
+
+// The owner of ONE pool block: back to its pool at scope exit (the pool is the context's the calling thread entered).
+// free() is the explicit early release: the pool is size-bucketed and reuse is stream-ordered, so a block of O(n m) or O(n^2)
+// bytes that today goes back before a later allocation of the same call keeps an explicit free() at that spot.
+struct DevBuf {
+  void* p = nullptr;
+  int alloc(size_t bytes) {
+    free();
+    TPG_HIP(tpg_pmalloc(&p, bytes ? bytes : 16));
+    return TPG_OK;
+  }
+  template <typename T> int alloc_n(size_t count) { return alloc(sizeof(T) * count); }
+  void free() { if (p) tpg_pfree(p); p = nullptr; }
+  void* release() { void* q = p; p = nullptr; return q; }  // to a longer-lived owner
+  template <typename T> T* as() const { return (T*)p; }
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { free(); p = o.release(); } return *this; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { free(); }
+};
+// All scratch of one call, freed together
+struct DevArena {
+  std::vector<DevBuf> blocks;
+  template <typename T> int get(T** p, size_t count) {
+    DevBuf b;
+    TPG_TRY(b.alloc_n<T>(count));
+    *p = b.as<T>();
+    blocks.push_back(std::move(b));
+    return TPG_OK;
+  }
+};
 
 // Output buffer that may be host or device memory: kernels write to dev(); commit() copies back
 // if the user's pointer is not device memory.

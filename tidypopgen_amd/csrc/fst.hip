@@ -749,8 +749,9 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
     OutBuf ot, osn, osd;
     if (fst_tot) TPG_TRY(ot.init(fst_tot, sizeof(double) * (size_t)P));
     if (sum_num) { TPG_TRY(osn.init(sum_num, sizeof(double) * (size_t)P)); TPG_TRY(osd.init(sum_den, sizeof(double) * (size_t)P)); }
-    double* d_gp = nullptr;
-    TPG_HIP(tpg_pmalloc((void**)&d_gp, sizeof(double) * (size_t)cells * (size_t)(nbx + FSTG_SL)));
+    DevBuf gp;
+    TPG_TRY(gp.alloc_n<double>((size_t)cells * (size_t)(nbx + FSTG_SL)));
+    double* const d_gp = gp.as<double>();
     double* d_full = d_gp + (size_t)cells * (size_t)nbx;
     // reciprocals by table when the source is the class counts of diploids and the table fits (kmax valid alleles at most)
     const int kq = (src.cnt && !src.has_hap && kmax > 0 && kmax <= 4096) ? kmax : 0;
@@ -762,9 +763,8 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
                (const double*)d_gp, nbx, cells, d_full);
     TPG_LAUNCH(ctx, "fst_reduce", tpg_fst_hudson_gemm_final_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, (const double*)d_full,
                cells, ntile, pb.dev<int32_t>(), P, ot.dev<double>(), osn.dev<double>(), osd.dev<double>());
-    hipError_t e = hipGetLastError();
-    tpg_pfree(d_gp);  // stream-ordered
-    if (e != hipSuccess) { tpg_set_error("fst kernels: %s", hipGetErrorString(e)); return TPG_EHIP; }
+    TPG_CHECK_LAUNCH();
+    gp.free();  // stream-ordered
     if (fst_tot) TPG_TRY(ot.commit(ctx));
     if (sum_num) { TPG_TRY(osn.commit(ctx)); TPG_TRY(osd.commit(ctx)); }
     return TPG_OK;
@@ -774,21 +774,21 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
   const int ypass = (int)ceil_div(P, 256 * ppt);
   int nblocks = (int)(nchunks < 4 * ctx->num_cu ? nchunks : 4 * ctx->num_cu);
   if (nblocks < 1) nblocks = 1;
-  double* d_part = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_part, sizeof(double) * 2 * (size_t)nblocks * (size_t)P));
+  DevBuf part;
+  TPG_TRY(part.alloc_n<double>(2 * (size_t)nblocks * (size_t)P));
+  double* const d_part = part.as<double>();
   OutBuf ot, oa, ob, osn, osd;
-  int rc = TPG_OK;
-  if (sum_num) { rc = osn.init(sum_num, sizeof(double) * (size_t)P); if (rc == TPG_OK) rc = osd.init(sum_den, sizeof(double) * (size_t)P); }
+  if (sum_num) { TPG_TRY(osn.init(sum_num, sizeof(double) * (size_t)P)); TPG_TRY(osd.init(sum_den, sizeof(double) * (size_t)P)); }
   const size_t mp = sizeof(double) * (size_t)m * (size_t)P;
-  if (rc == TPG_OK && fst_tot) rc = ot.init(fst_tot, sizeof(double) * (size_t)P);
-  if (rc == TPG_OK && by_locus) rc = oa.init(out_a, mp);
-  if (rc == TPG_OK && return_num_dem) rc = ob.init(out_b, mp);
+  if (fst_tot) TPG_TRY(ot.init(fst_tot, sizeof(double) * (size_t)P));
+  if (by_locus) TPG_TRY(oa.init(out_a, mp));
+  if (return_num_dem) TPG_TRY(ob.init(out_b, mp));
   // the table kernel stages 32 bytes per (locus, population), at a stride of 64 populations when G <= 64
   const int gs_tab = G <= 64 ? 64 : G, lb_tab = G <= 64 ? 16 : LB;
   const size_t sh_tab = (size_t)lb_tab * gs_tab * 32 + (size_t)(kmax + 1) * FSTW_TAB * 8;
   const bool wc84_tab = fast && method == TPG_FST_WC84 && src.cnt && !src.has_hap && kmax > 0 && sh_tab <= 150 * 1024 &&
                         (int64_t)lb_tab * G <= 8 * 256;  // a thread prefetches at most 8 (locus, population) slots
-  if (rc == TPG_OK && wc84_tab) {  // reciprocals by table: see tpg_fst_wc84_tab_kernel
+  if (wc84_tab) {  // reciprocals by table: see tpg_fst_wc84_tab_kernel
     const int64_t nch = ceil_div(m, lb_tab);
     const int nbt = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (int64_t)nblocks));
     dim3 grid((unsigned)nbt, (unsigned)ypass);
@@ -801,14 +801,14 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
       std::vector<int32_t> tasks;
       fst_wc84_tiles(p0, P, tasks);
       ntask = (int)(tasks.size() / FSTW_TASK_INTS);
-      rc = tb.init(ctx, tasks.data(), sizeof(int32_t) * tasks.size());
+      TPG_TRY(tb.init(ctx, tasks.data(), sizeof(int32_t) * tasks.size()));
     }
-    if (rc == TPG_OK && ntask > 0) {
+    if (ntask > 0) {
       const int nbt2 = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (int64_t)nblocks));
       dim3 tgrid((unsigned)nbt2, (unsigned)ceil_div(ntask, 256));
       TPG_LAUNCH(ctx, "fst_wc84", tpg_fst_wc84_tile_kernel, tgrid, dim3(256), 0, src, m, G, kmax, tb.dev<int32_t>(), ntask, P,
                  d_part);
-    } else if (rc == TPG_OK) {
+    } else {
 #define FSTW_LAUNCH(PP, GSV)                                                                                                    \
   do {                                                                                                                          \
     (void)hipFuncSetAttribute((const void*)tpg_fst_wc84_tab_kernel<PP, GSV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_tab); \
@@ -821,12 +821,9 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
     else FSTW_LAUNCH(1, 0);
 #undef FSTW_LAUNCH
     }
-    if (rc == TPG_OK)
-      TPG_LAUNCH(ctx, "fst_reduce", tpg_fst_reduce_kernel, dim3((unsigned)ceil_div(P, 16)), dim3(256), 0, d_part, nbt, P,
-                 ot.dev<double>(), osn.dev<double>(), osd.dev<double>());
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { tpg_set_error("fst kernels: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  } else if (rc == TPG_OK) {
+    TPG_LAUNCH(ctx, "fst_reduce", tpg_fst_reduce_kernel, dim3((unsigned)ceil_div(P, 16)), dim3(256), 0, d_part, nbt, P,
+               ot.dev<double>(), osn.dev<double>(), osd.dev<double>());
+  } else {
     dim3 grid((unsigned)nblocks, (unsigned)ypass);
 #define FST_LAUNCH1(M, F, PP, NAME)                                                                              \
   do {                                                                                                           \
@@ -846,11 +843,9 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
     if (fst_tot || sum_num)
       TPG_LAUNCH(ctx, "fst_reduce", tpg_fst_reduce_kernel, dim3((unsigned)ceil_div(P, 16)), dim3(256), 0, d_part,
                  nblocks, P, ot.dev<double>(), osn.dev<double>(), osd.dev<double>());
-    hipError_t e = hipGetLastError();  // no wait: d_part returns to the pool in stream order, commit() waits for host outputs
-    if (e != hipSuccess) { tpg_set_error("fst kernels: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
   }
-  tpg_pfree(d_part);
-  TPG_TRY(rc);
+  TPG_CHECK_LAUNCH();  // no wait: d_part returns to the pool in stream order, commit() waits for host outputs
+  part.free();
   if (fst_tot) TPG_TRY(ot.commit(ctx));
   if (sum_num) { TPG_TRY(osn.commit(ctx)); TPG_TRY(osd.commit(ctx)); }
   if (by_locus) TPG_TRY(oa.commit(ctx));
@@ -878,17 +873,13 @@ extern "C" int tpg_pairwise_fst_loop(tpg_ctx* ctx, int method, const int32_t* pa
   if (freq_ref && method != TPG_FST_WC84) {
     InBuf bq;
     TPG_TRY(bq.init(ctx, freq_ref, bytes));
-    int* d_bad = nullptr;
-    TPG_HIP(tpg_pmalloc((void**)&d_bad, sizeof(int)));
+    DevBuf d_bad;
+    TPG_TRY(d_bad.alloc_n<int>(1));
     int bad = 0;
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(tpg_freq_ref_check_kernel, dim3(1024), dim3(256), 0, ctx->stream, bp.dev<double>(),
-                         bq.dev<double>(), (int64_t)m * G, d_bad);
-      e = tpg_fetch_small(ctx, &bad, d_bad, sizeof(int));
-    }
-    tpg_pfree(d_bad);
-    TPG_HIP(e);
+    TPG_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(tpg_freq_ref_check_kernel, dim3(1024), dim3(256), 0, ctx->stream, bp.dev<double>(),
+                       bq.dev<double>(), (int64_t)m * G, d_bad.as<int>());
+    TPG_HIP(tpg_fetch_small(ctx, &bad, d_bad.p, sizeof(int)));
     TPG_REQUIRE(!bad, TPG_EINVAL, "freq_ref is not 1 - freq_alt: the device path recomputes it and would not match the reference");
   }
   FstSrc src{nullptr, 0, 0, 0, bn.dev<double>(), bp.dev<double>(), nullptr, het_obs ? bh.dev<double>() : nullptr};

@@ -738,17 +738,6 @@ __global__ __launch_bounds__(256) void tpg_gcls_assemble_kernel(const double* __
 
 // ---------------------------------------------------------------------------
 // host
-struct GclsBufs {
-  std::vector<void*> ptrs;
-  ~GclsBufs() { for (void* p : ptrs) tpg_pfree(p); }
-  template <class T> hipError_t get(T** out, size_t count) {
-    void* p = nullptr;
-    hipError_t e = tpg_pmalloc(&p, sizeof(T) * std::max<size_t>(count, 1));
-    if (e == hipSuccess) { ptrs.push_back(p); *out = (T*)p; }
-    return e;
-  }
-};
-
 // cost models (microseconds per wave), fitted on the two kernels at n = 5 000 (12.2 ms at 1 000 000 loci, 6.0 ms on a
 // shard of 125 000 loci that holds as many classes): per tile 0.136 us per class (fold) + 0.079 us per block (expansion,
 // MFMA, operand streaming); digit kernel 1.0 us per 128 loci.  S is even: the two halves of the grid take S / 2 splits each.
@@ -780,23 +769,23 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
                              double* d_K, bool force, bool* done, bool centred_ok) {
   *done = false;
   if (m >= (1ll << 31) - 64 || (tpg_env_set("TPG_GRAM_DIGITS") && !force)) return TPG_OK;
-  GclsBufs B;
+  DevArena B;
   unsigned long long *d_key = nullptr, *d_key2 = nullptr, *d_ukeys = nullptr;
   uint32_t *d_idx = nullptr, *d_idx2 = nullptr, *d_counts = nullptr, *d_cnt = nullptr, *d_nblk = nullptr, *d_estart = nullptr,
            *d_bstart = nullptr;
   int* d_nruns = nullptr;
   long long* d_totals = nullptr;
   void* d_tmp = nullptr;
-  TPG_HIP(B.get(&d_key, (size_t)m)); TPG_HIP(B.get(&d_key2, (size_t)m)); TPG_HIP(B.get(&d_ukeys, (size_t)m));
-  TPG_HIP(B.get(&d_idx, (size_t)m)); TPG_HIP(B.get(&d_idx2, (size_t)m)); TPG_HIP(B.get(&d_counts, (size_t)m));
-  TPG_HIP(B.get(&d_cnt, (size_t)m)); TPG_HIP(B.get(&d_nblk, (size_t)m)); TPG_HIP(B.get(&d_estart, (size_t)m));
-  TPG_HIP(B.get(&d_bstart, (size_t)m)); TPG_HIP(B.get(&d_nruns, 1)); TPG_HIP(B.get(&d_totals, 2));
+  TPG_TRY(B.get(&d_key, (size_t)m)); TPG_TRY(B.get(&d_key2, (size_t)m)); TPG_TRY(B.get(&d_ukeys, (size_t)m));
+  TPG_TRY(B.get(&d_idx, (size_t)m)); TPG_TRY(B.get(&d_idx2, (size_t)m)); TPG_TRY(B.get(&d_counts, (size_t)m));
+  TPG_TRY(B.get(&d_cnt, (size_t)m)); TPG_TRY(B.get(&d_nblk, (size_t)m)); TPG_TRY(B.get(&d_estart, (size_t)m));
+  TPG_TRY(B.get(&d_bstart, (size_t)m)); TPG_TRY(B.get(&d_nruns, 1)); TPG_TRY(B.get(&d_totals, 2));
   size_t t_sort = 0, t_rle = 0, t_scan = 0;
   TPG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, d_key, d_key2, d_idx, d_idx2, (int)m, 0, 64, ctx->stream));
   TPG_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t_rle, d_key2, d_ukeys, d_counts, d_nruns, (int)m, ctx->stream));
   TPG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, d_cnt, d_estart, (int)m, ctx->stream));
   const size_t t_bytes = std::max(t_sort, std::max(t_rle, t_scan));
-  TPG_HIP(B.get((uint8_t**)&d_tmp, t_bytes));
+  TPG_TRY(B.get((uint8_t**)&d_tmp, t_bytes));
   long long totals[2] = {0, 0};
   {
     ProfScope ps(ctx, "gcls_classes");
@@ -860,13 +849,13 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
   ulonglong2* d_wblk2 = nullptr;
   uint4* d_T2g = nullptr;
   int2* d_order = nullptr;
-  TPG_HIP(B.get(&d_src, (size_t)nblocks * 64));
-  if (f64) TPG_HIP(B.get(&d_wblk, (size_t)nblocks));
-  else TPG_HIP(B.get(&d_wblk2, (size_t)nblocks + 4));
+  TPG_TRY(B.get(&d_src, (size_t)nblocks * 64));
+  if (f64) TPG_TRY(B.get(&d_wblk, (size_t)nblocks));
+  else TPG_TRY(B.get(&d_wblk2, (size_t)nblocks + 4));
   const int64_t rs2 = (nblocks + 1) / 2;  // row-tile stride of T2g: a uint4 per lane and PAIR of blocks
-  TPG_HIP(B.get(&d_T2g, (size_t)(4 * Q) * (size_t)rs2 * 64));
-  TPG_HIP(B.get(&d_order, (size_t)nun));
-  TPG_HIP(B.get(&d_slabs, (size_t)S * (size_t)nun * GCLS_SLAB));
+  TPG_TRY(B.get(&d_T2g, (size_t)(4 * Q) * (size_t)rs2 * 64));
+  TPG_TRY(B.get(&d_order, (size_t)nun));
+  TPG_TRY(B.get(&d_slabs, (size_t)S * (size_t)nun * GCLS_SLAB));
   TPG_HIP(tpg_h2d_async(ctx, d_order, order.data(), sizeof(int2) * (size_t)nun));
   TPG_HIP(hipMemsetAsync(d_src, 0xFF, sizeof(int32_t) * (size_t)nblocks * 64, ctx->stream));
   {
@@ -909,7 +898,7 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
              (const double*)d_slabs, (const int2*)d_order, nun, S, (int)n, d_K);
   TPG_CHECK_LAUNCH();
   *done = true;
-  return TPG_OK;  // the scratch blocks go back to the pool in stream order (GclsBufs)
+  return TPG_OK;  // the scratch blocks go back to the pool in stream order (DevArena)
 }
 
 // The gather wants a locus' 2 Q pieces next to each other: in the L layout they are 1 KiB apart, every 16-byte piece the
@@ -938,13 +927,13 @@ int tpg_gram_classes(tpg_ctx* ctx, const tpg_view* v, const double* d_w, double*
   *done = false;
   if (tpg_env_set("TPG_GRAM_DIGITS")) return TPG_OK;
   const int64_t n_lt = 4 * v->KG;
-  uint4* d_LM = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_LM, sizeof(uint4) * (size_t)n_lt * 32 * (size_t)v->Q * 2));
+  DevBuf d_LM;
+  TPG_TRY(d_LM.alloc_n<uint4>((size_t)n_lt * 32 * (size_t)v->Q * 2));
   TPG_LAUNCH(ctx, "gcls_l2lm", tpg_gcls_l2lm_kernel, dim3((unsigned)std::min<int64_t>(n_lt * ((v->Q + 3) / 4), (int64_t)ctx->num_cu * 32)),
-             dim3(256), 0, (const uint4*)v->L, v->Q, n_lt, d_LM);
-  const GclsSrc src{d_LM, 0, 2 * v->Q, 0, 0, 2, 1};
+             dim3(256), 0, (const uint4*)v->L, v->Q, n_lt, d_LM.as<uint4>());
+  const GclsSrc src{d_LM.as<uint4>(), 0, 2 * v->Q, 0, 0, 2, 1};
   const int rc = gram_classes_core(ctx, v->n, v->Q, v->m, src, d_w, d_what, d_K, false, done, centred_ok);
-  tpg_pfree(d_LM);  // stream-ordered
+  d_LM.free();  // stream-ordered
   return rc;
 }
 
@@ -1017,7 +1006,7 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
   const int R = comm->nranks, me = comm->rank;
   const int64_t n = v->n, m = v->m, Q = v->Q;
   if (R < 2 || R > 255 || n >= (1 << 30) || tpg_env_set("TPG_GRAM_NO_EXCHANGE")) return TPG_OK;
-  GclsBufs B;
+  DevArena B;
   int32_t *d_key = nullptr, *d_hist = nullptr, *d_perdest = nullptr;
   uint8_t* d_owner = nullptr;
   uint32_t *d_dest = nullptr, *d_dest2 = nullptr, *d_idx = nullptr, *d_idx2 = nullptr;
@@ -1026,16 +1015,16 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
   std::vector<int32_t> hist((size_t)n + 1, 0);
   // rank-local steps first, then the ranks agree on a status before the first exchange (nobody is left waiting in it)
   auto local = [&]() -> int {
-    TPG_HIP(B.get(&d_key, (size_t)std::max<int64_t>(m, 1)));
-    TPG_HIP(B.get(&d_hist, (size_t)n + 1));
-    TPG_HIP(B.get(&d_perdest, (size_t)R));
-    TPG_HIP(B.get(&d_owner, (size_t)n + 1));
-    TPG_HIP(B.get(&d_dest, (size_t)std::max<int64_t>(m, 1)));
-    TPG_HIP(B.get(&d_dest2, (size_t)std::max<int64_t>(m, 1)));
-    TPG_HIP(B.get(&d_idx, (size_t)std::max<int64_t>(m, 1)));
-    TPG_HIP(B.get(&d_idx2, (size_t)std::max<int64_t>(m, 1)));
+    TPG_TRY(B.get(&d_key, (size_t)std::max<int64_t>(m, 1)));
+    TPG_TRY(B.get(&d_hist, (size_t)n + 1));
+    TPG_TRY(B.get(&d_perdest, (size_t)R));
+    TPG_TRY(B.get(&d_owner, (size_t)n + 1));
+    TPG_TRY(B.get(&d_dest, (size_t)std::max<int64_t>(m, 1)));
+    TPG_TRY(B.get(&d_dest2, (size_t)std::max<int64_t>(m, 1)));
+    TPG_TRY(B.get(&d_idx, (size_t)std::max<int64_t>(m, 1)));
+    TPG_TRY(B.get(&d_idx2, (size_t)std::max<int64_t>(m, 1)));
     TPG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, d_dest, d_dest2, d_idx, d_idx2, (int)m, 0, 8, ctx->stream));
-    TPG_HIP(B.get((uint8_t**)&d_tmp, t_sort));
+    TPG_TRY(B.get((uint8_t**)&d_tmp, t_sort));
     TPG_HIP(hipMemsetAsync(d_hist, 0, sizeof(int32_t) * ((size_t)n + 1), ctx->stream));
     TPG_HIP(hipMemsetAsync(d_perdest, 0, sizeof(int32_t) * (size_t)R, ctx->stream));
     if (m > 0)
@@ -1100,7 +1089,7 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
     }
     TPG_HIP(hipMemcpyAsync(per_dest.data(), d_perdest, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
     TPG_HIP(hipStreamSynchronize(ctx->stream));
-    TPG_HIP(B.get(&d_send, (size_t)std::max<int64_t>(m, 1) * (size_t)recq));
+    TPG_TRY(B.get(&d_send, (size_t)std::max<int64_t>(m, 1) * (size_t)recq));
     if (m > 0)
       TPG_LAUNCH(ctx, "gclx_pack", tpg_gclx_pack_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(m, 4), (int64_t)ctx->num_cu * 16)),
                  dim3(256), 0, (const uint4*)v->L, Q, (const uint32_t*)d_idx2, d_scale, m, d_send);
@@ -1112,7 +1101,7 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
   {
     int32_t* d_cm = nullptr;
     auto cm_up = [&]() -> int {  // rank-local (an allocation, a copy): agreed on before the all-reduce like the steps above
-      TPG_HIP(B.get(&d_cm, (size_t)R * R));
+      TPG_TRY(B.get(&d_cm, (size_t)R * R));
       for (int d = 0; d < R; d++) cm[(size_t)me * R + d] = per_dest[(size_t)d];
       TPG_HIP(tpg_h2d_async(ctx, d_cm, cm.data(), sizeof(int32_t) * (size_t)R * R));
       return TPG_OK;
@@ -1135,8 +1124,8 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
     }
   }
   auto recv_alloc = [&]() -> int {
-    TPG_HIP(B.get(&d_recv, (size_t)std::max<int64_t>(m_in, 1) * (size_t)recq));
-    TPG_HIP(B.get(&d_w, (size_t)std::max<int64_t>(m_in, 1)));
+    TPG_TRY(B.get(&d_recv, (size_t)std::max<int64_t>(m_in, 1) * (size_t)recq));
+    TPG_TRY(B.get(&d_w, (size_t)std::max<int64_t>(m_in, 1)));
     return TPG_OK;
   };
   TPG_TRY(tpg_comm_agree(comm, recv_alloc()));

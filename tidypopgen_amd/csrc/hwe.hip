@@ -82,19 +82,15 @@ extern "C" int tpg_hwe_exact_counts(tpg_ctx* ctx, const int32_t* counts3, int64_
   TPG_TRY(in.init(ctx, counts3, sizeof(int32_t) * 3 * (size_t)count));
   OutBuf o;
   TPG_TRY(o.init(p, sizeof(double) * (size_t)count));
-  int32_t* d_bad = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_bad, sizeof(int32_t)));
+  DevBuf d_bad;
+  TPG_TRY(d_bad.alloc_n<int32_t>(1));
   int32_t bad = 0;
-  hipError_t e = tpg_push_small(ctx, d_bad, &bad, sizeof(bad));
-  if (e == hipSuccess) {
-    const unsigned grid = (unsigned)(ceil_div(count, 256) < 8192 ? ceil_div(count, 256) : 8192);
-    TPG_LAUNCH(ctx, "hwe_table", tpg_hwe_table_kernel, dim3(grid), dim3(256), 0, in.dev<int32_t>(), count, midp,
-               o.dev<double>(), d_bad);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = tpg_fetch_small(ctx, &bad, d_bad, sizeof(bad));  // waits for the kernel
-  tpg_pfree(d_bad);
-  if (e != hipSuccess) { tpg_set_error("hwe_exact_counts: %s", hipGetErrorString(e)); return TPG_EHIP; }
+  TPG_HIP(tpg_push_small(ctx, d_bad.p, &bad, sizeof(bad)));
+  const unsigned grid = (unsigned)(ceil_div(count, 256) < 8192 ? ceil_div(count, 256) : 8192);
+  TPG_LAUNCH(ctx, "hwe_table", tpg_hwe_table_kernel, dim3(grid), dim3(256), 0, in.dev<int32_t>(), count, midp,
+             o.dev<double>(), d_bad.as<int32_t>());
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(tpg_fetch_small(ctx, &bad, d_bad.p, sizeof(bad)));  // waits for the kernel
   TPG_REQUIRE(!(bad & HWE_BAD_NEGATIVE), TPG_EINVAL, "negative genotype count");
   TPG_REQUIRE(!(bad & HWE_BAD_TOO_LARGE), TPG_EUNSUPPORTED, "a table of 2^26 individuals or more");
   return o.commit(ctx);
@@ -105,21 +101,17 @@ extern "C" int tpg_loci_hwe(tpg_ctx* ctx, const tpg_view* v, int midp, double* p
   TPG_REQUIRE(ctx && v && p, TPG_EINVAL, "null argument");
   TPG_REQUIRE(midp == 0 || midp == 1, TPG_EINVAL, "midp must be 0 or 1");
   TPG_REQUIRE(v->n < TPG_HWE_MAX_N, TPG_EUNSUPPORTED, "exact test of 2^26 individuals or more");
-  int32_t* d_counts = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)v->m));
-  int rc = tpg_launch_loci_counts(ctx, v, d_counts);
+  DevBuf d_counts;
+  TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)v->m));
+  TPG_TRY(tpg_launch_loci_counts(ctx, v, d_counts.as<int32_t>()));
   OutBuf o;
-  if (rc == TPG_OK) rc = o.init(p, sizeof(double) * (size_t)v->m);
-  if (rc == TPG_OK) {
-    const unsigned grid = (unsigned)(ceil_div(v->m, 256) < 8192 ? ceil_div(v->m, 256) : 8192);
-    TPG_LAUNCH(ctx, "hwe_loci", tpg_hwe_loci_kernel, dim3(grid), dim3(256), 0, (const int4*)d_counts, v->m, midp,
-               o.dev<double>());
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { tpg_set_error("loci_hwe: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  }
-  tpg_pfree(d_counts);
-  TPG_TRY(rc);
+  TPG_TRY(o.init(p, sizeof(double) * (size_t)v->m));
+  const unsigned grid = (unsigned)(ceil_div(v->m, 256) < 8192 ? ceil_div(v->m, 256) : 8192);
+  TPG_LAUNCH(ctx, "hwe_loci", tpg_hwe_loci_kernel, dim3(grid), dim3(256), 0, (const int4*)d_counts.p, v->m, midp,
+             o.dev<double>());
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
+  TPG_CHECK_LAUNCH();
+  d_counts.free();
   return o.commit(ctx);
 }
 

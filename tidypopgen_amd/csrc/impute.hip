@@ -260,32 +260,28 @@ extern "C" int tpg_fbm_impute_simple_at(tpg_ctx* ctx, tpg_fbm* fbm, int64_t col0
   const int w = tpg_env_int("TPG_IMPUTE_WPL", 0);
   if (w == 1 || w == 4 || w == 16) wpl = w;
   const bool res = pieces <= (int64_t)IMP_PMAX * 64 * wpl;
-  int32_t* d_stat = nullptr;  // per locus: entries filled, or IMP_ALL_MISSING / IMP_REFUSED; then the report's three sums
+  DevBuf stat;  // per locus: entries filled, or IMP_ALL_MISSING / IMP_REFUSED; then the report's three sums
   const size_t stat_bytes = (4 * (size_t)fbm->ncol + 31) & ~(size_t)31;
-  TPG_HIP(tpg_pmalloc((void**)&d_stat, stat_bytes + 32));
-  unsigned long long* d_rep = (unsigned long long*)((uint8_t*)d_stat + stat_bytes);
-  hipError_t e = hipMemsetAsync(d_rep, 0, 32, ctx->stream);
+  TPG_TRY(stat.alloc(stat_bytes + 32));
+  int32_t* const d_stat = stat.as<int32_t>();
+  unsigned long long* d_rep = (unsigned long long*)(stat.as<uint8_t>() + stat_bytes);
+  TPG_HIP(hipMemsetAsync(d_rep, 0, 32, ctx->stream));
   unsigned long long h[3] = {0, 0, 0};
-  if (e == hipSuccess) {
-    if (wpl == 1) launch_store<1>(ctx, res, fbm, method, seed, col0, d_stat);
-    else if (wpl == 4) launch_store<4>(ctx, res, fbm, method, seed, col0, d_stat);
-    else launch_store<16>(ctx, res, fbm, method, seed, col0, d_stat);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
-    const unsigned blocks = (unsigned)std::min<int64_t>(1024, ceil_div(fbm->ncol, 256));
-    TPG_LAUNCH(ctx, "impute_report", tpg_impute_report_kernel, dim3(blocks), dim3(256), 0, (const int32_t*)d_stat, fbm->ncol, d_rep);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = tpg_fetch_small(ctx, h, d_rep, sizeof(h));
-  if (e == hipSuccess && h[2]) {
+  if (wpl == 1) launch_store<1>(ctx, res, fbm, method, seed, col0, d_stat);
+  else if (wpl == 4) launch_store<4>(ctx, res, fbm, method, seed, col0, d_stat);
+  else launch_store<16>(ctx, res, fbm, method, seed, col0, d_stat);
+  TPG_CHECK_LAUNCH();
+  const unsigned blocks = (unsigned)std::min<int64_t>(1024, ceil_div(fbm->ncol, 256));
+  TPG_LAUNCH(ctx, "impute_report", tpg_impute_report_kernel, dim3(blocks), dim3(256), 0, (const int32_t*)d_stat, fbm->ncol, d_rep);
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(tpg_fetch_small(ctx, h, d_rep, sizeof(h)));
+  if (h[2]) {
     TPG_LAUNCH(ctx, "impute_undo", tpg_impute_undo_kernel, dim3(4096), dim3(256), 0, fbm->d_bytes, fbm->nrow, fbm->ncol,
                (const int32_t*)d_stat);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    TPG_CHECK_LAUNCH();
+    TPG_HIP(hipStreamSynchronize(ctx->stream));
   }
-  tpg_pfree(d_stat);
-  TPG_HIP(e);
+  stat.free();
   TPG_REQUIRE(h[2] == 0, TPG_EUNSUPPORTED, "object x is already imputed (%llu loci hold a store byte above 3; the store is unchanged)",
               h[2]);
   if (rep) {
@@ -371,29 +367,22 @@ int tpg_view_impute_at(tpg_ctx* ctx, const tpg_view* raw, int method, uint64_t s
   TPG_REQUIRE(ctx && raw && out, TPG_EINVAL, "null argument");
   TPG_TRY(check_method(method));
   TPG_REQUIRE(raw->L, TPG_EINVAL, "the view has no locus-tiled layout");
-  tpg_view* v = new tpg_view{ctx, raw->n, raw->m, raw->Q, raw->KG, nullptr, nullptr, raw->bytes_each};
-  unsigned long long* d_rep = nullptr;
-  hipError_t e = tpg_pmalloc((void**)&v->L, v->bytes_each);
-  if (e == hipSuccess) e = tpg_pmalloc((void**)&d_rep, 16);
-  if (e == hipSuccess) e = hipMemsetAsync(d_rep, 0, 16, ctx->stream);
-  if (e == hipSuccess) {
-    const int64_t n_lt = 4 * raw->KG;
-    TPG_LAUNCH(ctx, "impute_view", tpg_impute_view_kernel, dim3((unsigned)ceil_div(n_lt, 4)), dim3(256), 0, (const uint4*)raw->L, v->L, n_lt,
-               raw->Q, raw->n, raw->m, method, seed, col0, d_rep);
-    e = hipGetLastError();
-  }
+  ViewPtr v(new tpg_view(ctx, raw->n, raw->m));
+  DevBuf d_rep;
+  TPG_HIP(tpg_pmalloc((void**)&v->L, v->bytes_each));
+  TPG_TRY(d_rep.alloc(16));
+  TPG_HIP(hipMemsetAsync(d_rep.p, 0, 16, ctx->stream));
+  const int64_t n_lt = 4 * raw->KG;
+  TPG_LAUNCH(ctx, "impute_view", tpg_impute_view_kernel, dim3((unsigned)ceil_div(n_lt, 4)), dim3(256), 0, (const uint4*)raw->L, v->L, n_lt,
+             raw->Q, raw->n, raw->m, method, seed, col0, d_rep.as<unsigned long long>());
+  TPG_CHECK_LAUNCH();
   unsigned long long h[2] = {0, 0};
-  if (e == hipSuccess && rep) e = tpg_fetch_small(ctx, h, d_rep, sizeof(h));
-  if (d_rep) tpg_pfree(d_rep);  // stream-ordered
-  if (e != hipSuccess) {
-    tpg_view_free(v);
-    TPG_HIP(e);
-  }
+  if (rep) TPG_HIP(tpg_fetch_small(ctx, h, d_rep.p, sizeof(h)));
   if (rep) {
     rep->imputed = (int64_t)h[0];
     rep->loci_all_missing = (int64_t)h[1];
   }
-  *out = v;
+  *out = v.release();
   return TPG_OK;
 }
 

@@ -350,21 +350,6 @@ __global__ __launch_bounds__(256) void tpg_ld_keep_kernel(const uint8_t* __restr
 // ---- host side --------------------------------------------------------------------------------------------------
 namespace {
 
-struct LdScratch {  // pooled device blocks of one call
-  std::vector<void*> blocks;
-  template <typename T>
-  int get(T** p, size_t count) {
-    void* q = nullptr;
-    TPG_HIP(tpg_pmalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-    blocks.push_back(q);
-    *p = (T*)q;
-    return TPG_OK;
-  }
-  ~LdScratch() {
-    for (void* q : blocks) tpg_pfree(q);
-  }
-};
-
 struct LdBand {
   int64_t words = 0;  // ceil(max(hi[j] - j) / 32)
   int32_t* d_sx = nullptr;
@@ -403,7 +388,7 @@ int ld_check_args(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, double thr
 }
 
 // counts -> Sx, d and the missing-value check; the window goes up.  Nothing of the caller's is written.
-int ld_prepare(tpg_ctx* ctx, const tpg_view* v, const std::vector<int64_t>& h, LdScratch& sc, LdBand* B) {
+int ld_prepare(tpg_ctx* ctx, const tpg_view* v, const std::vector<int64_t>& h, DevArena& sc, LdBand* B) {
   const int64_t m = v->m;
   int32_t* d_counts = nullptr;
   TPG_TRY(sc.get(&d_counts, 4 * (size_t)m));
@@ -446,7 +431,7 @@ extern "C" int tpg_ld_band_links(tpg_ctx* ctx, const tpg_view* v, const int64_t*
   TPG_TRY(ld_window(ctx, hi, v->m, h, &B.words));
   TPG_REQUIRE(stride_words >= B.words, TPG_EINVAL, "stride_words = %lld, the window needs %lld", (long long)stride_words,
               (long long)B.words);
-  LdScratch sc;
+  DevArena sc;
   TPG_TRY(ld_prepare(ctx, v, h, sc, &B));
   int32_t flags = 0;
   TPG_HIP(tpg_fetch_small(ctx, &flags, B.d_flags, sizeof(flags)));
@@ -473,7 +458,7 @@ extern "C" int tpg_ld_clump(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, 
   LdBand B;
   TPG_TRY(ld_window(ctx, hi, m, h, &B.words));
   const int64_t stride = B.words > 0 ? B.words : 1, bstride = B.words + 1;
-  LdScratch sc;
+  DevArena sc;
   TPG_TRY(ld_prepare(ctx, v, h, sc, &B));
   InBuf inS, inX;
   if (S) TPG_TRY(inS.init(ctx, S, sizeof(double) * (size_t)m));

@@ -848,10 +848,10 @@ extern "C" void tpg_pairwise_free(tpg_pairwise* pw) {
 extern "C" int tpg_pairwise_zero(tpg_ctx* ctx, tpg_pairwise* pw) {
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && pw, TPG_EINVAL, "null argument");
+  TPG_REQUIRE(!pw->reducing, TPG_EINVAL, "a reduction is in flight: tpg_pairwise_reduce_end first");
   ProfScope ps(ctx, "pairwise_zero");
   TPG_HIP(hipMemsetAsync(pw->acc, 0, pw_buffer_bytes(pw->n, pw->nranks), ctx->stream));
   pw->loci = 0;
-  TPG_REQUIRE(!pw->reducing, TPG_EINVAL, "a reduction is in flight: tpg_pairwise_reduce_end first");
   pw->reduced = false;
   pw->have = TPG_PW_HAVE_ALL;
   return TPG_OK;

@@ -87,17 +87,13 @@ __global__ __launch_bounds__(256) void tpg_pca_frobenius_kernel(const int4* __re
 static int pca_counts_center_scale(tpg_ctx* ctx, const tpg_view* v, int32_t* d_counts, double* d_center,
                                    double* d_scale) {
   TPG_TRY(tpg_launch_loci_counts(ctx, v, d_counts));
-  int* d_flags = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_flags, 2 * sizeof(int)));
-  hipError_t e = hipMemsetAsync(d_flags, 0, 2 * sizeof(int), ctx->stream);
+  DevBuf d_flags;
+  TPG_TRY(d_flags.alloc_n<int>(2));
+  TPG_HIP(hipMemsetAsync(d_flags.p, 0, 2 * sizeof(int), ctx->stream));
   int flags[2] = {0, 0};
-  if (e == hipSuccess) {
-    TPG_LAUNCH(ctx, "pca_center_scale", tpg_pca_center_scale_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts,
-               v->m, v->n, d_center, d_scale, d_flags);
-    e = tpg_fetch_small(ctx, flags, d_flags, sizeof(flags));
-  }
-  tpg_pfree(d_flags);
-  if (e != hipSuccess) { tpg_set_error("pca center/scale: %s", hipGetErrorString(e)); return TPG_EHIP; }
+  TPG_LAUNCH(ctx, "pca_center_scale", tpg_pca_center_scale_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts,
+             v->m, v->n, d_center, d_scale, d_flags.as<int>());
+  TPG_HIP(tpg_fetch_small(ctx, flags, d_flags.p, sizeof(flags)));
   // bigstatsr::big_SVD stops on missing values and on a zero scale
   TPG_REQUIRE(!flags[0], TPG_ENUMERIC, "You can't have missing values in 'X'.");
   TPG_REQUIRE(!flags[1], TPG_ENUMERIC, "Some variables have a zero scaling; remove them before attempting to scale variables.");
@@ -110,11 +106,10 @@ extern "C" int tpg_pca_center_scale(tpg_ctx* ctx, const tpg_view* v, double* cen
   OutBuf oc, os;
   TPG_TRY(oc.init(center, sizeof(double) * (size_t)v->m));
   TPG_TRY(os.init(scale, sizeof(double) * (size_t)v->m));
-  int32_t* d_counts = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)v->m));
-  int rc = pca_counts_center_scale(ctx, v, d_counts, oc.dev<double>(), os.dev<double>());
-  tpg_pfree(d_counts);
-  TPG_TRY(rc);
+  DevBuf d_counts;
+  TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)v->m));
+  TPG_TRY(pca_counts_center_scale(ctx, v, d_counts.as<int32_t>(), oc.dev<double>(), os.dev<double>()));
+  d_counts.free();
   TPG_TRY(oc.commit(ctx));
   return os.commit(ctx);
 }
@@ -122,14 +117,12 @@ extern "C" int tpg_pca_center_scale(tpg_ctx* ctx, const tpg_view* v, double* cen
 static int frobenius_from_counts(tpg_ctx* ctx, const tpg_view* v, const int32_t* d_counts, const double* d_center,
                                  const double* d_scale, double* out_host) {
   const int NB = 512;
-  double* d_part = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_part, sizeof(double) * NB));
+  DevBuf d_part;
+  TPG_TRY(d_part.alloc_n<double>(NB));
   TPG_LAUNCH(ctx, "pca_frobenius", tpg_pca_frobenius_kernel, dim3(NB), dim3(256), 0, (const int4*)d_counts, v->m, v->n,
-             d_center, d_scale, d_part);
+             d_center, d_scale, d_part.as<double>());
   std::vector<double> hp(NB);
-  hipError_t e = tpg_fetch_small(ctx, hp.data(), d_part, sizeof(double) * NB);
-  tpg_pfree(d_part);
-  if (e != hipSuccess) { tpg_set_error("frobenius: %s", hipGetErrorString(e)); return TPG_EHIP; }
+  TPG_HIP(tpg_fetch_small(ctx, hp.data(), d_part.p, sizeof(double) * NB));
   long double s = 0;
   for (int b = 0; b < NB; b++) s += hp[b];
   *out_host = (double)s;
@@ -143,12 +136,10 @@ extern "C" int tpg_square_frobenius(tpg_ctx* ctx, const tpg_view* v, const doubl
   InBuf ic, is;
   TPG_TRY(ic.init(ctx, center, sizeof(double) * (size_t)v->m));
   TPG_TRY(is.init(ctx, scale, sizeof(double) * (size_t)v->m));
-  int32_t* d_counts = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)v->m));
-  int rc = tpg_launch_loci_counts(ctx, v, d_counts);
-  if (rc == TPG_OK) rc = frobenius_from_counts(ctx, v, d_counts, ic.dev<double>(), is.dev<double>(), out);
-  tpg_pfree(d_counts);
-  return rc;
+  DevBuf d_counts;
+  TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)v->m));
+  TPG_TRY(tpg_launch_loci_counts(ctx, v, d_counts.as<int32_t>()));
+  return frobenius_from_counts(ctx, v, d_counts.as<int32_t>(), ic.dev<double>(), is.dev<double>(), out);
 }
 
 // ---------------------------------------------------------------------------
@@ -264,10 +255,10 @@ static int run_sweep(tpg_ctx* ctx, int mode, const uint4* P, int64_t nrowtiles, 
   int64_t S = 1;
   const int64_t row_blocks = ceil_div(nrowtiles, 4);
   while (row_blocks * S < 4 * ctx->num_cu && S * 2 <= nblocks && S < 64) S *= 2;
-  double *d_part = nullptr, *d_rsp = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_part, sizeof(double) * (size_t)S * KC * (size_t)rows_pad));
-  hipError_t e = tpg_pmalloc((void**)&d_rsp, sizeof(double) * (size_t)S * (size_t)rows_pad);
-  if (e != hipSuccess) { tpg_pfree(d_part); tpg_set_error("hipMalloc sweep: %s", hipGetErrorString(e)); return TPG_EHIP; }
+  DevBuf part, rspb;
+  TPG_TRY(part.alloc_n<double>((size_t)S * KC * (size_t)rows_pad));
+  TPG_TRY(rspb.alloc_n<double>((size_t)S * (size_t)rows_pad));
+  double *const d_part = part.as<double>(), *const d_rsp = rspb.as<double>();
   dim3 grid((unsigned)row_blocks, (unsigned)S);
   for (int k0 = 0; k0 < K; k0 += KC) {
     const int kc = K - k0 < KC ? K - k0 : KC;
@@ -291,11 +282,8 @@ static int run_sweep(tpg_ctx* ctx, int mode, const uint4* P, int64_t nrowtiles, 
     TPG_LAUNCH(ctx, "sweep_reduce", tpg_sweep_reduce_kernel, dim3(512), dim3(256), 0, d_part, rsp, (int)S, KC, kc,
                rows_pad, nrows, d_out, nrows, k0, d_col_div, rsp ? d_rss : nullptr);
   }
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  tpg_pfree(d_part);
-  tpg_pfree(d_rsp);
-  if (e != hipSuccess) { tpg_set_error("sweep: %s", hipGetErrorString(e)); return TPG_EHIP; }
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
   return TPG_OK;
 }
 
@@ -315,14 +303,13 @@ extern "C" int tpg_fbm256_prod_and_rowSumsSq(tpg_ctx* ctx, const tpg_view* v, co
   OutBuf oxv, orss;
   TPG_TRY(oxv.init(XV, sizeof(double) * (size_t)v->n * (size_t)K));
   TPG_TRY(orss.init(rss, sizeof(double) * (size_t)v->n));
-  double* d_inv = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_inv, sizeof(double) * (size_t)v->m));
-  TPG_LAUNCH(ctx, "inv_scale", tpg_inv_kernel, dim3(1024), dim3(256), 0, is.dev<double>(), v->m, d_inv);
+  DevBuf d_inv;
+  TPG_TRY(d_inv.alloc_n<double>((size_t)v->m));
+  TPG_LAUNCH(ctx, "inv_scale", tpg_inv_kernel, dim3(1024), dim3(256), 0, is.dev<double>(), v->m, d_inv.as<double>());
   TPG_TRY(tpg_view_need_T(ctx, v));
-  int rc = run_sweep(ctx, SW_COLSCALE, v->T, v->Q * 4, v->KG, v->n, v->m, ic.dev<double>(), d_inv, iv.dev<double>(),
-                     v->m, K, oxv.dev<double>(), nullptr, orss.dev<double>());
-  tpg_pfree(d_inv);
-  TPG_TRY(rc);
+  TPG_TRY(run_sweep(ctx, SW_COLSCALE, v->T, v->Q * 4, v->KG, v->n, v->m, ic.dev<double>(), d_inv.as<double>(), iv.dev<double>(),
+                    v->m, K, oxv.dev<double>(), nullptr, orss.dev<double>()));
+  d_inv.free();
   TPG_TRY(oxv.commit(ctx));
   return orss.commit(ctx);
 }
@@ -732,17 +719,14 @@ static int pca_gram_device(tpg_ctx* ctx, const tpg_view* v, const double* d_cent
                            double* d_K, bool own_center) {
   const int64_t n = v->n, m = v->m;
   // weight range decides the number of digits: smallest scale by a device reduction (16 bytes come back)
-  unsigned long long* d_rng = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_rng, 2 * sizeof(unsigned long long)));
+  DevBuf d_rng;
+  TPG_TRY(d_rng.alloc_n<unsigned long long>(2));
   const unsigned long long rng_init[2] = {0x7FF0000000000000ull, 0ull};  // +inf, no bad entry
   unsigned long long rng[2];
-  hipError_t er = tpg_push_small(ctx, d_rng, rng_init, sizeof(rng_init));
-  if (er == hipSuccess) {
-    hipLaunchKernelGGL(tpg_scale_range_kernel, dim3(512), dim3(256), 0, ctx->stream, d_scale, m, d_rng);
-    er = tpg_fetch_small(ctx, rng, d_rng, sizeof(rng));
-  }
-  tpg_pfree(d_rng);
-  TPG_HIP(er);
+  TPG_HIP(tpg_push_small(ctx, d_rng.p, rng_init, sizeof(rng_init)));
+  hipLaunchKernelGGL(tpg_scale_range_kernel, dim3(512), dim3(256), 0, ctx->stream, d_scale, m, d_rng.as<unsigned long long>());
+  TPG_HIP(tpg_fetch_small(ctx, rng, d_rng.p, sizeof(rng)));
+  d_rng.free();
   TPG_REQUIRE(rng[1] == 0, TPG_ENUMERIC, "zero or negative scale at locus %lld", (long long)(rng[1] - 1));
   double smin;
   memcpy(&smin, &rng[0], sizeof(double));
@@ -769,46 +753,40 @@ static int pca_gram_device(tpg_ctx* ctx, const tpg_view* v, const double* d_cent
   const int64_t nun = (int64_t)order.size();
   std::vector<int32_t> lut((size_t)nrt * (size_t)(nsbf + 1), -1);
   for (int64_t u = 0; u < nun; u++) lut[(size_t)order[(size_t)u].x * (size_t)(nsbf + 1) + (size_t)order[(size_t)u].y] = (int32_t)u;
-  uint32_t* d_DG = nullptr;
-  double *d_what = nullptr, *d_wc = nullptr, *d_r = nullptr, *d_part = nullptr;
-  long long* d_slabs = nullptr;
-  int2* d_order = nullptr;
-  int32_t* d_lut = nullptr;
-  int rc = TPG_OK;
-  hipError_t e = hipSuccess;
-#define GHIP(call) do { if (e == hipSuccess) { e = (call); if (e != hipSuccess) tpg_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e)); } } while (0)
-  GHIP(tpg_pmalloc((void**)&d_what, sizeof(double) * (size_t)m));
-  GHIP(tpg_pmalloc((void**)&d_wc, sizeof(double) * (size_t)m));
-  GHIP(tpg_pmalloc((void**)&d_r, sizeof(double) * (size_t)n));
-  GHIP(tpg_pmalloc((void**)&d_part, sizeof(double) * 512));
+  DevBuf b_DG, b_what, b_wc, b_r, b_part, b_slabs, b_order, b_lut;
+  TPG_TRY(b_what.alloc_n<double>((size_t)m));
+  TPG_TRY(b_wc.alloc_n<double>((size_t)m));
+  TPG_TRY(b_r.alloc_n<double>((size_t)n));
+  TPG_TRY(b_part.alloc_n<double>(512));
+  double *const d_what = b_what.as<double>(), *const d_wc = b_wc.as<double>(), *const d_r = b_r.as<double>(),
+               *const d_part = b_part.as<double>();
   // S' = G W G' by weight classes on the FP4 matrix cores when the weights take few distinct values (gramcls.hip:
   // always so under the binomial scaling); the digit-split int8 kernel below otherwise
   bool by_classes = false;
-  if (e == hipSuccess) {
-    double* d_w = nullptr;
-    GHIP(tpg_pmalloc((void**)&d_w, sizeof(double) * (size_t)m));
-    if (e == hipSuccess) {
-      TPG_LAUNCH(ctx, "pca_weights", tpg_pca_weights_kernel, dim3(1024), dim3(256), 0, d_scale, m, d_w);
-      rc = tpg_gram_classes(ctx, v, d_w, d_what, d_K, &by_classes, own_center);
-      if (rc == TPG_OK && by_classes)
-        TPG_LAUNCH(ctx, "pca_weights", tpg_pca_wc_kernel, dim3(1024), dim3(256), 0, (const double*)d_what, d_center, m, d_wc);
-    }
-    if (d_w) tpg_pfree(d_w);
-    if (rc != TPG_OK) { tpg_pfree(d_what); tpg_pfree(d_wc); tpg_pfree(d_r); tpg_pfree(d_part); return rc; }
-  }
+  {
+    DevBuf d_w;
+    TPG_TRY(d_w.alloc_n<double>((size_t)m));
+    TPG_LAUNCH(ctx, "pca_weights", tpg_pca_weights_kernel, dim3(1024), dim3(256), 0, d_scale, m, d_w.as<double>());
+    TPG_TRY(tpg_gram_classes(ctx, v, d_w.as<double>(), d_what, d_K, &by_classes, own_center));
+    if (by_classes)
+      TPG_LAUNCH(ctx, "pca_weights", tpg_pca_wc_kernel, dim3(1024), dim3(256), 0, (const double*)d_what, d_center, m, d_wc);
+  }  // (d_w goes back before the digit buffers are asked for: stream-ordered)
   if (!by_classes) {
-  if (e == hipSuccess && tpg_view_need_T(ctx, v) != TPG_OK) { tpg_pfree(d_what); tpg_pfree(d_wc); tpg_pfree(d_r); tpg_pfree(d_part); return TPG_EHIP; }
-  GHIP(tpg_pmalloc((void**)&d_DG, (size_t)v->KG * 4 * 2 * T * 8 * sizeof(uint32_t)));
-  GHIP(tpg_pmalloc((void**)&d_slabs, sizeof(long long) * (size_t)nun * PCA_SLAB_INTS));
-  GHIP(hipMemsetAsync(d_slabs, 0, sizeof(long long) * (size_t)nun * PCA_SLAB_INTS, ctx->stream));
+    TPG_TRY(tpg_view_need_T(ctx, v));
+    TPG_TRY(b_DG.alloc_n<uint32_t>((size_t)v->KG * 4 * 2 * T * 8));
+    TPG_TRY(b_slabs.alloc_n<long long>((size_t)nun * PCA_SLAB_INTS));
+    TPG_HIP(hipMemsetAsync(b_slabs.p, 0, sizeof(long long) * (size_t)nun * PCA_SLAB_INTS, ctx->stream));
   }
-  if (e == hipSuccess && !by_classes) {
+  uint32_t* const d_DG = b_DG.as<uint32_t>();
+  long long* const d_slabs = b_slabs.as<long long>();
+  if (!by_classes) {
     TPG_LAUNCH(ctx, "pca_digits", tpg_pca_digits_kernel, dim3(1024), dim3(256), 0, d_scale, d_center, m, v->KG, F, T,
                d_DG, d_what, d_wc);
-    GHIP(tpg_pmalloc((void**)&d_order, sizeof(int2) * (size_t)nun));
-    GHIP(hipMemcpyAsync(d_order, order.data(), sizeof(int2) * (size_t)nun, hipMemcpyHostToDevice, ctx->stream));
-    GHIP(tpg_pmalloc((void**)&d_lut, sizeof(int32_t) * lut.size()));
-    GHIP(hipMemcpyAsync(d_lut, lut.data(), sizeof(int32_t) * lut.size(), hipMemcpyHostToDevice, ctx->stream));
+    TPG_TRY(b_order.alloc_n<int2>((size_t)nun));
+    TPG_HIP(hipMemcpyAsync(b_order.p, order.data(), sizeof(int2) * (size_t)nun, hipMemcpyHostToDevice, ctx->stream));
+    TPG_TRY(b_lut.alloc_n<int32_t>(lut.size()));
+    TPG_HIP(hipMemcpyAsync(b_lut.p, lut.data(), sizeof(int32_t) * lut.size(), hipMemcpyHostToDevice, ctx->stream));
+    const int2* const d_order = b_order.as<int2>();
     // K-split S: units x S wave-units over the resident waves (one workgroup per CU, one wave per SIMD; grid a
     // multiple of the 8 XCDs).  Cost model: a launch is rounds(S) = ceil(units S / waves) rounds, a round costs its K
     // range (about 1.17 us per 128-locus group: 64 MFMAs at ~37 cycles) plus the flush of the accumulators (256
@@ -839,9 +817,10 @@ static int pca_gram_device(tpg_ctx* ctx, const tpg_view* v, const double* d_cent
 #undef GRAM_LAUNCH
       pass_base += v->KG * 4 * 2 * td * 8;
     }
-    GHIP(hipGetLastError());
+    TPG_CHECK_LAUNCH();
   }
-  if (e == hipSuccess && own_center) {
+  const int32_t* const d_lut = b_lut.as<int32_t>();
+  if (own_center) {
     if (!by_classes)
       TPG_LAUNCH(ctx, "pca_assemble", tpg_pca_assemble_kernel, dim3(2048), dim3(256), 0, d_slabs, (const int32_t*)d_lut, nsbf,
                  (int)n, F, (const double*)nullptr, 0.0, d_K);
@@ -849,58 +828,42 @@ static int pca_gram_device(tpg_ctx* ctx, const tpg_view* v, const double* d_cent
     TPG_LAUNCH(ctx, "pca_colmean", tpg_mean_kernel, dim3(1), dim3(256), 0, (const double*)d_r, (int)n, d_part);
     TPG_LAUNCH(ctx, "pca_double_center", tpg_double_center_kernel, dim3(2048), dim3(256), 0, d_K, (int)n,
                (const double*)d_r, (const double*)d_part);
-    GHIP(hipGetLastError());  // (no wait: the scratch blocks go back to the pool in stream order)
-  }
-  if (e == hipSuccess && !own_center) {
+    TPG_CHECK_LAUNCH();  // (no wait: the scratch blocks go back to the pool in stream order)
+  } else {
     // r_i = sum_j what_j c_j g_ij  (RAW sweep with a one-column table), C = sum_j what_j c_j^2
-    rc = tpg_view_need_T(ctx, v);
-    if (rc == TPG_OK) rc = run_sweep(ctx, SW_RAW, v->T, v->Q * 4, v->KG, n, m, nullptr, nullptr, d_wc, m, 1, d_r, nullptr, nullptr);
-  }
-  double Cc = 0;
-  if (e == hipSuccess && rc == TPG_OK && !own_center) {
+    TPG_TRY(tpg_view_need_T(ctx, v));
+    TPG_TRY(run_sweep(ctx, SW_RAW, v->T, v->Q * 4, v->KG, n, m, nullptr, nullptr, d_wc, m, 1, d_r, nullptr, nullptr));
     TPG_LAUNCH(ctx, "pca_dot", tpg_dot_kernel, dim3(512), dim3(256), 0, d_wc, d_center, m, d_part);
     std::vector<double> hp(512);
-    GHIP(tpg_fetch_small(ctx, hp.data(), d_part, sizeof(double) * 512));
+    TPG_HIP(tpg_fetch_small(ctx, hp.data(), d_part, sizeof(double) * 512));
     long double s = 0;
     for (int b = 0; b < 512; b++) s += hp[(size_t)b];
-    Cc = (double)s;
-  }
-  if (e == hipSuccess && rc == TPG_OK && !own_center) {
+    const double Cc = (double)s;
     if (!by_classes) {
       TPG_LAUNCH(ctx, "pca_assemble", tpg_pca_assemble_kernel, dim3(2048), dim3(256), 0, d_slabs, (const int32_t*)d_lut, nsbf,
                  (int)n, F, (const double*)d_r, Cc, d_K);
     } else {  // K = S' - r 1' - 1 r' + C on the matrix the class path left in d_K
-      GHIP(tpg_push_small(ctx, d_part, &Cc, sizeof(double)));
+      TPG_HIP(tpg_push_small(ctx, d_part, &Cc, sizeof(double)));
       TPG_LAUNCH(ctx, "pca_double_center", tpg_double_center_kernel, dim3(2048), dim3(256), 0, d_K, (int)n,
                  (const double*)d_r, (const double*)d_part);
     }
-    GHIP(hipGetLastError());
+    TPG_CHECK_LAUNCH();
   }
-#undef GHIP
-  tpg_pfree(d_DG); tpg_pfree(d_what); tpg_pfree(d_wc); tpg_pfree(d_r); tpg_pfree(d_part);
-  tpg_pfree(d_slabs);
-  tpg_pfree(d_order);
-  tpg_pfree(d_lut);
-  if (e != hipSuccess) return TPG_EHIP;
-  return rc;
+  return TPG_OK;
 }
 
 // K = H S' H for S' in d_K (the double centering pca_gram_device applies when `center` is the column mean): linear in
 // S', so every rank applies it to the S' of the classes it owns before the partial matrices are summed
 static int pca_double_center_inplace(tpg_ctx* ctx, double* d_K, int64_t n) {
-  double *d_r = nullptr, *d_part = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_r, sizeof(double) * (size_t)n));
-  hipError_t e = tpg_pmalloc((void**)&d_part, sizeof(double) * 512);
-  if (e == hipSuccess) {
-    TPG_LAUNCH(ctx, "pca_colmean", tpg_colmean_kernel, dim3((unsigned)n), dim3(256), 0, (const double*)d_K, (int)n, d_r);
-    TPG_LAUNCH(ctx, "pca_colmean", tpg_mean_kernel, dim3(1), dim3(256), 0, (const double*)d_r, (int)n, d_part);
-    TPG_LAUNCH(ctx, "pca_double_center", tpg_double_center_kernel, dim3(2048), dim3(256), 0, d_K, (int)n, (const double*)d_r,
-               (const double*)d_part);
-    e = hipGetLastError();
-  }
-  tpg_pfree(d_r);
-  tpg_pfree(d_part);
-  TPG_HIP(e);
+  DevBuf b_r, b_part;
+  TPG_TRY(b_r.alloc_n<double>((size_t)n));
+  TPG_TRY(b_part.alloc_n<double>(512));
+  double *const d_r = b_r.as<double>(), *const d_part = b_part.as<double>();
+  TPG_LAUNCH(ctx, "pca_colmean", tpg_colmean_kernel, dim3((unsigned)n), dim3(256), 0, (const double*)d_K, (int)n, d_r);
+  TPG_LAUNCH(ctx, "pca_colmean", tpg_mean_kernel, dim3(1), dim3(256), 0, (const double*)d_r, (int)n, d_part);
+  TPG_LAUNCH(ctx, "pca_double_center", tpg_double_center_kernel, dim3(2048), dim3(256), 0, d_K, (int)n, (const double*)d_r,
+             (const double*)d_part);
+  TPG_CHECK_LAUNCH();
   return TPG_OK;
 }
 
@@ -913,22 +876,17 @@ extern "C" int tpg_pca_gram(tpg_ctx* ctx, const tpg_view* v, const double* cente
   OutBuf ok;
   TPG_TRY(ok.init(K, sizeof(double) * (size_t)v->n * (size_t)v->n));
   // is `center` the column mean of these individuals (what tpg_pca_center_scale returns)?
-  int32_t* d_counts = nullptr;
-  int* d_flag = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)v->m));
-  hipError_t e = tpg_pmalloc((void**)&d_flag, 2 * sizeof(int));
+  DevBuf d_counts, d_flag;
+  TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)v->m));
+  TPG_TRY(d_flag.alloc_n<int>(2));
   int flag[2] = {1, 0};
-  int rc = e == hipSuccess ? tpg_launch_loci_counts(ctx, v, d_counts) : TPG_EHIP;
-  if (rc == TPG_OK) {
-    e = hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream);
-    TPG_LAUNCH(ctx, "pca_center_check", tpg_center_is_mean_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts,
-               ic.dev<double>(), v->m, v->n, d_flag);
-    if (e == hipSuccess) e = tpg_fetch_small(ctx, flag, d_flag, 2 * sizeof(int));
-    if (e != hipSuccess) { tpg_set_error("pca_gram: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  }
-  tpg_pfree(d_counts);
-  tpg_pfree(d_flag);
-  TPG_TRY(rc);
+  TPG_TRY(tpg_launch_loci_counts(ctx, v, d_counts.as<int32_t>()));
+  TPG_HIP(hipMemsetAsync(d_flag.p, 0, 2 * sizeof(int), ctx->stream));
+  TPG_LAUNCH(ctx, "pca_center_check", tpg_center_is_mean_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts.p,
+             ic.dev<double>(), v->m, v->n, d_flag.as<int>());
+  TPG_HIP(tpg_fetch_small(ctx, flag, d_flag.p, 2 * sizeof(int)));
+  d_counts.free();
+  d_flag.free();
   TPG_REQUIRE(!flag[1], TPG_ENUMERIC, "You can't have missing values in 'X'.");
   TPG_TRY(pca_gram_device(ctx, v, ic.dev<double>(), is.dev<double>(), ok.dev<double>(), flag[0] == 0));
   return ok.commit(ctx);
@@ -945,17 +903,13 @@ extern "C" int tpg_pca_gram_add(tpg_ctx* ctx, const tpg_view* v, const double* c
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && center && scale && K, TPG_EINVAL, "null argument");
   TPG_REQUIRE(tpg_is_device_ptr(K), TPG_EINVAL, "K must be device memory");
-  double* d_tmp = nullptr;
+  DevBuf d_tmp;
   const int64_t nn = v->n * v->n;
-  TPG_HIP(tpg_pmalloc((void**)&d_tmp, sizeof(double) * (size_t)nn));
-  int rc = tpg_pca_gram(ctx, v, center, scale, d_tmp);
-  if (rc == TPG_OK) {
-    TPG_LAUNCH(ctx, "pca_gram_add", tpg_add_inplace_kernel, dim3(2048), dim3(256), 0, K, (const double*)d_tmp, nn);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { tpg_set_error("gram add: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  }
-  tpg_pfree(d_tmp);
-  return rc;
+  TPG_TRY(d_tmp.alloc_n<double>((size_t)nn));
+  TPG_TRY(tpg_pca_gram(ctx, v, center, scale, d_tmp.as<double>()));
+  TPG_LAUNCH(ctx, "pca_gram_add", tpg_add_inplace_kernel, dim3(2048), dim3(256), 0, K, (const double*)d_tmp.p, nn);
+  TPG_CHECK_LAUNCH();
+  return TPG_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1218,6 +1172,7 @@ struct EigWork {
   // small host matrices go to the device, and the small products come back, through the context's mailbox (runtime.hip:
   // tpg_push_small / tpg_fetch_small): no copy engine and no stream synchronisation anywhere in the iteration
   double* xdev = nullptr;
+  DevArena mem;  // owns part, gpart, lam_dev, cdev, dtmp and xdev
   int init() {
     // K splits: ONE round of workgroups (two fit a CU: 66 KiB of LDS each) -- at n = 5 000, 79 row blocks x 6 splits = 474
     // of 512 places, 89.5 us per product; 16 splits (2.5 rounds, the last half empty) 94.6, 13 splits (two rounds and three
@@ -1230,21 +1185,13 @@ struct EigWork {
     // of many workgroups instead of a long loop in a few
     rows_per_chunk = n <= 4096 ? 32 : 64;
     nchunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-    TPG_HIP(tpg_pmalloc((void**)&part, sizeof(double) * (size_t)S * (size_t)b * (size_t)n));
-    TPG_HIP(tpg_pmalloc((void**)&gpart, sizeof(double) * (size_t)nchunks * 64 * 64));  // nchunks = n/32
-    TPG_HIP(tpg_pmalloc((void**)&lam_dev, sizeof(double) * 64));
-    TPG_HIP(tpg_pmalloc((void**)&cdev, sizeof(double) * 64 * 64));
-    TPG_HIP(tpg_pmalloc((void**)&dtmp, sizeof(double) * (size_t)b * (size_t)n));
-    TPG_HIP(tpg_pmalloc((void**)&xdev, sizeof(double) * (64 * 64 + 64)));
+    TPG_TRY(mem.get(&part, (size_t)S * (size_t)b * (size_t)n));
+    TPG_TRY(mem.get(&gpart, (size_t)nchunks * 64 * 64));  // nchunks = n/32
+    TPG_TRY(mem.get(&lam_dev, 64));
+    TPG_TRY(mem.get(&cdev, 64 * 64));
+    TPG_TRY(mem.get(&dtmp, (size_t)b * (size_t)n));
+    TPG_TRY(mem.get(&xdev, 64 * 64 + 64));
     return TPG_OK;
-  }
-  ~EigWork() {
-    if (part) tpg_pfree(part);
-    if (gpart) tpg_pfree(gpart);
-    if (lam_dev) tpg_pfree(lam_dev);
-    if (cdev) tpg_pfree(cdev);
-    if (dtmp) tpg_pfree(dtmp);
-    if (xdev) tpg_pfree(xdev);
   }
   int set_locked(const double* Lptr, int count, const double* lam_host) {
     L = Lptr;
@@ -1341,12 +1288,7 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
   EigWork w{ctx, d_K, n, b, 1};
   TPG_TRY(w.init());
   double *Q = nullptr, *Y = nullptr, *Y0 = nullptr, *Y1 = nullptr;
-  const size_t nbytes = sizeof(double) * (size_t)n * (size_t)b;
-  TPG_HIP(tpg_pmalloc((void**)&Q, nbytes));
-  TPG_HIP(tpg_pmalloc((void**)&Y, nbytes));
-  TPG_HIP(tpg_pmalloc((void**)&Y0, nbytes));
-  TPG_HIP(tpg_pmalloc((void**)&Y1, nbytes));
-  struct Free { double *a, *b, *c, *d; ~Free() { tpg_pfree(a); tpg_pfree(b); tpg_pfree(c); tpg_pfree(d); } } fr{Q, Y, Y0, Y1};
+  for (double** blk : {&Q, &Y, &Y0, &Y1}) TPG_TRY(w.mem.get(blk, (size_t)n * (size_t)b));
   auto colbytes = [&](int cols) { return sizeof(double) * (size_t)n * (size_t)cols; };
   auto axpby = [&](const double* x, double alpha, const double* y, double beta, double* out, int cols) -> int {
     TPG_LAUNCH(ctx, "eig_combine", tpg_combine_kernel, dim3(1024), dim3(256), 0, x, 1, (int64_t)n * cols, alpha, y,
@@ -1522,11 +1464,10 @@ __global__ __launch_bounds__(256) void tpg_deflate_kernel(double* __restrict__ K
 
 static int eig_topk_any(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambda_host, double* d_U, double tol) {
   if (k <= 52) return eig_topk(ctx, d_K, n, k, lambda_host, d_U, tol);
-  double *Kw = nullptr, *d_lam = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&Kw, sizeof(double) * (size_t)n * (size_t)n));
-  struct Free { void *a, *b; ~Free() { tpg_pfree(a); tpg_pfree(b); } } fr{Kw, nullptr};
-  TPG_HIP(tpg_pmalloc((void**)&d_lam, sizeof(double) * 32));
-  fr.b = d_lam;
+  DevBuf b_Kw, b_lam;
+  TPG_TRY(b_Kw.alloc_n<double>((size_t)n * (size_t)n));
+  TPG_TRY(b_lam.alloc_n<double>(32));
+  double *const Kw = b_Kw.as<double>(), *const d_lam = b_lam.as<double>();
   TPG_HIP(hipMemcpyAsync(Kw, d_K, sizeof(double) * (size_t)n * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
   const int KB = 26;
   for (int done = 0; done < k;) {
@@ -1599,21 +1540,18 @@ __global__ void tpg_tri_unpack_kernel(const double* __restrict__ tri, int n, dou
 int tpg_pca_gram_allreduce(tpg_ctx* ctx, tpg_comm* comm, double* d_K, int64_t n) {
   if (!comm || !(comm->nranks > 1 || comm->nccl)) return TPG_OK;
   const int64_t ntri = n * (n + 1) / 2;
-  double* d_tri = nullptr;
-  hipError_t e = tpg_pmalloc((void**)&d_tri, sizeof(double) * (size_t)ntri);
-  int lrc = TPG_OK;
-  if (e != hipSuccess) { tpg_set_error("gram all-reduce: %s", hipGetErrorString(e)); (void)hipGetLastError(); lrc = TPG_EHIP; }
-  lrc = tpg_comm_agree(comm, lrc);
-  if (lrc != TPG_OK) { tpg_pfree(d_tri); return lrc; }
+  DevBuf b_tri;
+  int lrc = b_tri.alloc_n<double>((size_t)ntri);
+  if (lrc != TPG_OK) (void)hipGetLastError();
+  TPG_TRY(tpg_comm_agree(comm, lrc));
+  double* const d_tri = b_tri.as<double>();
   TPG_LAUNCH(ctx, "pca_gram_tri", tpg_tri_pack_kernel, dim3(2048), dim3(256), 0, (const double*)d_K, (int)n, d_tri);
-  int rc;
   {
     ProfScope ps(ctx, "pca_gram_allreduce");
-    rc = tpg_comm_allreduce(comm, d_tri, ntri, 1);
+    TPG_TRY(tpg_comm_allreduce(comm, d_tri, ntri, 1));
   }
-  if (rc == TPG_OK) TPG_LAUNCH(ctx, "pca_gram_tri", tpg_tri_unpack_kernel, dim3(2048), dim3(256), 0, (const double*)d_tri, (int)n, d_K);
-  tpg_pfree(d_tri);
-  return rc;
+  TPG_LAUNCH(ctx, "pca_gram_tri", tpg_tri_unpack_kernel, dim3(2048), dim3(256), 0, (const double*)d_tri, (int)n, d_K);
+  return TPG_OK;
 }
 
 static int pca_svd_impl(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, int k, double tol, double* d, double* u,
@@ -1624,7 +1562,7 @@ static int pca_svd_impl(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, int k, 
   OutBuf oc, os, ou, ov;
   int32_t* d_counts = nullptr;
   double *d_K = nullptr, *d_dk = nullptr, *d_tri = nullptr;
-  struct Free { void *a, *b, *c, *d; ~Free() { tpg_pfree(a); tpg_pfree(b); tpg_pfree(c); tpg_pfree(d); } } fr{nullptr, nullptr, nullptr, nullptr};
+  DevBuf b_counts, b_K, b_dk, b_tri;
   StageTimer st(ctx, "svd");
   const bool exchange = comm && (comm->nranks > 1 || comm->nccl);
   const int64_t ntri = n * (n + 1) / 2;
@@ -1637,16 +1575,14 @@ static int pca_svd_impl(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, int k, 
     TPG_TRY(os.init(scale, sizeof(double) * (size_t)m));
     TPG_TRY(ou.init(u, sizeof(double) * (size_t)n * (size_t)k));
     TPG_TRY(ov.init(vload, sizeof(double) * (size_t)m * (size_t)k));
-    TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)m));
-    fr.a = d_counts;
-    TPG_HIP(tpg_pmalloc((void**)&d_K, sizeof(double) * (size_t)n * (size_t)n));
-    fr.b = d_K;
-    TPG_HIP(tpg_pmalloc((void**)&d_dk, sizeof(double) * (size_t)k));
-    fr.d = d_dk;
-    if (exchange) {
-      TPG_HIP(tpg_pmalloc((void**)&d_tri, sizeof(double) * (size_t)ntri));
-      fr.c = d_tri;
-    }
+    TPG_TRY(b_counts.alloc_n<int32_t>(4 * (size_t)m));
+    TPG_TRY(b_K.alloc_n<double>((size_t)n * (size_t)n));
+    TPG_TRY(b_dk.alloc_n<double>((size_t)k));
+    if (exchange) TPG_TRY(b_tri.alloc_n<double>((size_t)ntri));
+    d_counts = b_counts.as<int32_t>();
+    d_K = b_K.as<double>();
+    d_dk = b_dk.as<double>();
+    d_tri = b_tri.as<double>();
     TPG_TRY(pca_counts_center_scale(ctx, v, d_counts, oc.dev<double>(), os.dev<double>()));
     st.mark("counts, center, scale");
     if (square_frobenius) TPG_TRY(frobenius_from_counts(ctx, v, d_counts, oc.dev<double>(), os.dev<double>(), square_frobenius));
@@ -1927,12 +1863,10 @@ static int pca_loadings_device(tpg_ctx* ctx, const tpg_view* v, const double* d_
   // the scale of the digits: max |u|, found on the device (8 bytes come back, not the n x k matrix)
   double amax = 0;
   {
-    double* d_amax = nullptr;
-    TPG_HIP(tpg_pmalloc((void**)&d_amax, sizeof(double)));
-    TPG_LAUNCH(ctx, "loadings_u_digits", tpg_absmax_kernel, dim3(1), dim3(1024), 0, d_U, n * (int64_t)k, d_amax);
-    hipError_t ea = tpg_fetch_small(ctx, &amax, d_amax, sizeof(double));
-    tpg_pfree(d_amax);
-    TPG_HIP(ea);
+    DevBuf d_amax;
+    TPG_TRY(d_amax.alloc_n<double>(1));
+    TPG_LAUNCH(ctx, "loadings_u_digits", tpg_absmax_kernel, dim3(1), dim3(1024), 0, d_U, n * (int64_t)k, d_amax.as<double>());
+    TPG_HIP(tpg_fetch_small(ctx, &amax, d_amax.p, sizeof(double)));
   }
   TPG_REQUIRE(amax > 0 && amax == amax && amax < 1e300, TPG_ENUMERIC, "degenerate eigenvectors");
   int ex = 0;
@@ -1941,34 +1875,31 @@ static int pca_loadings_device(tpg_ctx* ctx, const tpg_view* v, const double* d_
   const int CT = (int)ceil_div((int64_t)k * LD_TU, 32);
   const int Cpad = CT * 32;
   const int64_t n_lt = v->KG * 4;
-  uint4* d_UD = nullptr;
-  int32_t* d_acc = nullptr;
-  double* d_usum = nullptr;
-  hipError_t e = tpg_pmalloc((void**)&d_UD, (size_t)v->Q * 4 * CT * 1024);
-  if (e == hipSuccess) e = tpg_pmalloc((void**)&d_acc, sizeof(int32_t) * (size_t)n_lt * 32 * (size_t)Cpad);
-  if (e == hipSuccess) e = tpg_pmalloc((void**)&d_usum, sizeof(double) * (size_t)k);
-  if (e == hipSuccess) {
-    TPG_LAUNCH(ctx, "loadings_u_digits", tpg_u_digits_kernel, dim3(1024), dim3(256), 0, d_U, n, k, FU, v->Q, CT, d_UD);
-    TPG_LAUNCH(ctx, "loadings_u_digits", tpg_uq_colsum_kernel, dim3((unsigned)k), dim3(256), 0, d_U, n, FU, d_usum);
-    const unsigned grid = (unsigned)ceil_div(n_lt, 4 * LD_NLT);
-    for (int ct0 = 0; ct0 < CT;) {
-      const int left = CT - ct0;
+  DevBuf b_UD, b_acc, b_usum;
+  TPG_TRY(b_UD.alloc((size_t)v->Q * 4 * CT * 1024));
+  TPG_TRY(b_acc.alloc_n<int32_t>((size_t)n_lt * 32 * (size_t)Cpad));
+  TPG_TRY(b_usum.alloc_n<double>((size_t)k));
+  uint4* const d_UD = b_UD.as<uint4>();
+  int32_t* const d_acc = b_acc.as<int32_t>();
+  double* const d_usum = b_usum.as<double>();
+  TPG_LAUNCH(ctx, "loadings_u_digits", tpg_u_digits_kernel, dim3(1024), dim3(256), 0, d_U, n, k, FU, v->Q, CT, d_UD);
+  TPG_LAUNCH(ctx, "loadings_u_digits", tpg_uq_colsum_kernel, dim3((unsigned)k), dim3(256), 0, d_U, n, FU, d_usum);
+  const unsigned grid = (unsigned)ceil_div(n_lt, 4 * LD_NLT);
+  for (int ct0 = 0; ct0 < CT;) {
+    const int left = CT - ct0;
 #define LD_LAUNCH(C)                                                                                             \
   TPG_LAUNCH(ctx, "loadings_mfma", tpg_loadings_mfma_kernel<C>, dim3(grid), dim3(256), 0, (const uint4*)v->L,     \
              (const uint4*)d_UD, n_lt, v->Q, ct0, CT, d_acc, Cpad)
-      if (left >= 4) { LD_LAUNCH(4); ct0 += 4; }
-      else if (left == 3) { LD_LAUNCH(3); ct0 += 3; }
-      else if (left == 2) { LD_LAUNCH(2); ct0 += 2; }
-      else { LD_LAUNCH(1); ct0 += 1; }
+    if (left >= 4) { LD_LAUNCH(4); ct0 += 4; }
+    else if (left == 3) { LD_LAUNCH(3); ct0 += 3; }
+    else if (left == 2) { LD_LAUNCH(2); ct0 += 2; }
+    else { LD_LAUNCH(1); ct0 += 1; }
 #undef LD_LAUNCH
-    }
-    TPG_LAUNCH(ctx, "loadings_finalize", tpg_loadings_finalize_kernel, dim3(2048), dim3(256), 0, (const int32_t*)d_acc,
-               Cpad, m, k, FU, d_center, d_scale, (const double*)d_usum, d_dk, d_V);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   }
-  tpg_pfree(d_UD); tpg_pfree(d_acc); tpg_pfree(d_usum);
-  if (e != hipSuccess) { tpg_set_error("loadings: %s", hipGetErrorString(e)); return TPG_EHIP; }
+  TPG_LAUNCH(ctx, "loadings_finalize", tpg_loadings_finalize_kernel, dim3(2048), dim3(256), 0, (const int32_t*)d_acc,
+             Cpad, m, k, FU, d_center, d_scale, (const double*)d_usum, d_dk, d_V);
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
   return TPG_OK;
 }
 
@@ -2008,33 +1939,26 @@ extern "C" int tpg_pca_loadings(tpg_ctx* ctx, const tpg_view* v, const double* c
   OutBuf ov;
   TPG_TRY(ov.init(vload, sizeof(double) * (size_t)m * (size_t)k));
   // missing values? (then z = 0 there and the FP64 sweep handles it; big_SVD itself never gets here)
-  int32_t* d_counts = nullptr;
-  int* d_flag = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)m));
-  hipError_t e = tpg_pmalloc((void**)&d_flag, 2 * sizeof(int));
+  DevBuf d_counts, d_flag;
+  TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)m));
+  TPG_TRY(d_flag.alloc_n<int>(2));
   int flag[2] = {0, 1};
-  int rc = e == hipSuccess ? tpg_launch_loci_counts(ctx, v, d_counts) : TPG_EHIP;
-  if (rc == TPG_OK) {
-    e = hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream);
-    TPG_LAUNCH(ctx, "pca_center_check", tpg_center_is_mean_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts,
-               ic.dev<double>(), m, n, d_flag);
-    if (e == hipSuccess) e = tpg_fetch_small(ctx, flag, d_flag, 2 * sizeof(int));
-    if (e != hipSuccess) { tpg_set_error("pca_loadings: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  }
-  tpg_pfree(d_counts);
-  tpg_pfree(d_flag);
-  TPG_TRY(rc);
+  TPG_TRY(tpg_launch_loci_counts(ctx, v, d_counts.as<int32_t>()));
+  TPG_HIP(hipMemsetAsync(d_flag.p, 0, 2 * sizeof(int), ctx->stream));
+  TPG_LAUNCH(ctx, "pca_center_check", tpg_center_is_mean_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts.p,
+             ic.dev<double>(), m, n, d_flag.as<int>());
+  TPG_HIP(tpg_fetch_small(ctx, flag, d_flag.p, 2 * sizeof(int)));
+  d_counts.free();
+  d_flag.free();
   if (!flag[1]) {
-    rc = pca_loadings_device(ctx, v, ic.dev<double>(), is.dev<double>(), iu.dev<double>(), id.dev<double>(), k,
-                             ov.dev<double>());
+    TPG_TRY(pca_loadings_device(ctx, v, ic.dev<double>(), is.dev<double>(), iu.dev<double>(), id.dev<double>(), k,
+                                ov.dev<double>()));
   } else {
-    double* d_inv = nullptr;
-    TPG_HIP(tpg_pmalloc((void**)&d_inv, sizeof(double) * (size_t)m));
-    TPG_LAUNCH(ctx, "inv_scale", tpg_inv_kernel, dim3(1024), dim3(256), 0, is.dev<double>(), m, d_inv);
-    rc = run_sweep(ctx, SW_ROWSCALE, v->L, v->KG * 4, v->Q, m, n, ic.dev<double>(), d_inv, iu.dev<double>(), n, k,
-                   ov.dev<double>(), id.dev<double>(), nullptr);
-    tpg_pfree(d_inv);
+    DevBuf d_inv;
+    TPG_TRY(d_inv.alloc_n<double>((size_t)m));
+    TPG_LAUNCH(ctx, "inv_scale", tpg_inv_kernel, dim3(1024), dim3(256), 0, is.dev<double>(), m, d_inv.as<double>());
+    TPG_TRY(run_sweep(ctx, SW_ROWSCALE, v->L, v->KG * 4, v->Q, m, n, ic.dev<double>(), d_inv.as<double>(), iu.dev<double>(), n, k,
+                      ov.dev<double>(), id.dev<double>(), nullptr));
   }
-  TPG_TRY(rc);
   return ov.commit(ctx);
 }

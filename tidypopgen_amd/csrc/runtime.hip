@@ -605,6 +605,10 @@ static void xfer_parallel(size_t bytes, F f) {
 
 static uint8_t* nib_stage_acquire(bool may_pin = true);
 static void nib_stage_release(uint8_t* p);
+struct StageBack {  // a pinned staging buffer goes back when its transfer returns
+  uint8_t* p;
+  ~StageBack() { nib_stage_release(p); }
+};
 static constexpr size_t XFER_PIECE = 64u << 20;  // a quarter of the process's pinned staging buffer (NIB_CHUNK)
 
 // device memory -> host memory the caller owns (pageable), large: through the process's pinned staging buffer in four pieces
@@ -624,7 +628,7 @@ static hipError_t tpg_download_pinned(tpg_ctx* ctx, uint8_t* dst, const uint8_t*
   // (a copy below 64 MiB takes the staging buffer only if the process already has one: pinning 256 MiB costs 35 - 40 ms)
   uint8_t* const pinned = off ? nullptr : nib_stage_acquire(bytes >= XFER_BIG);
   if (!pinned) return hipSuccess;
-  struct Back { uint8_t* p; ~Back() { nib_stage_release(p); } } back{pinned};
+  StageBack back{pinned};
   const size_t H = XFER_PIECE, np = (bytes + H - 1) / H;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipError_t e = hipSuccess;
@@ -795,11 +799,12 @@ static void nib_stage_release(uint8_t* p) {
 static hipError_t tpg_upload_packed(tpg_ctx* ctx, uint8_t* dst, const uint8_t* src, size_t bytes) {
   uint8_t* const pinned = nib_stage_acquire();
   if (!pinned) return tpg_upload(ctx, dst, src, bytes);  // no pinned memory to be had: the plain copy
-  struct Back { uint8_t* p; ~Back() { nib_stage_release(p); } } back{pinned};
-  uint8_t* d_stage = nullptr;
+  StageBack back{pinned};
+  DevBuf stage;
   // two halves, like the pinned buffer; a payload of one chunk needs its own packed size only
-  hipError_t e = tpg_pmalloc((void**)&d_stage, bytes <= NIB_CHUNK ? std::max<size_t>(bytes / 2, 16) : NIB_CHUNK);
-  if (e != hipSuccess) { (void)hipGetLastError(); return tpg_upload(ctx, dst, src, bytes); }  // HBM is that full: the plain copy
+  if (stage.alloc(bytes <= NIB_CHUNK ? bytes / 2 : NIB_CHUNK) != TPG_OK) { (void)hipGetLastError(); return tpg_upload(ctx, dst, src, bytes); }  // HBM is that full: the plain copy
+  uint8_t* const d_stage = stage.as<uint8_t>();
+  hipError_t e = hipSuccess;
   hipEvent_t ev[2] = {nullptr, nullptr};
   for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
   bool used[2] = {false, false};
@@ -846,7 +851,6 @@ static hipError_t tpg_upload_packed(tpg_ctx* ctx, uint8_t* dst, const uint8_t* s
   else (void)hipStreamSynchronize(ctx->stream);
   for (int q = 0; q < 2; q++)
     if (ev[q]) (void)hipEventDestroy(ev[q]);
-  tpg_pfree(d_stage);
   return e;
 }
 
@@ -873,7 +877,7 @@ hipError_t tpg_upload_bedpacked(tpg_ctx* ctx, uint8_t* dst, const uint8_t* src, 
   }
   uint8_t* const pinned = nib_stage_acquire();
   if (!pinned) return hipSuccess;
-  struct Back { uint8_t* p; ~Back() { nib_stage_release(p); } } back{pinned};
+  StageBack back{pinned};
   if (bpl > half) return hipSuccess;
   // columns per chunk.  (A block that fits ONE chunk -- the 134-MB blocks of an R driver loop -- is NOT cut further so that its
   // copy could run beside its packing: four chunks measured 2.3 ms against 1.9, a team start and join per chunk.)
@@ -933,7 +937,7 @@ static hipError_t tpg_upload_pinned(tpg_ctx* ctx, uint8_t* dst, const uint8_t* s
   static const bool off = tpg_env_int("TPG_UPLOAD_PINNED", 1) == 0;
   uint8_t* const pinned = off ? nullptr : nib_stage_acquire();
   if (!pinned) return tpg_upload(ctx, dst, src, bytes);
-  struct Back { uint8_t* p; ~Back() { nib_stage_release(p); } } back{pinned};
+  StageBack back{pinned};
   const size_t H = NIB_CHUNK / 4;  // 64 MiB pieces, four in the buffer: two copies may be in flight while two are being filled
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipError_t e = hipSuccess;
@@ -1231,67 +1235,42 @@ static int view_create_impl(tpg_ctx* ctx, const tpg_fbm* fbm, const int32_t* row
   memset(lut, 0, sizeof(lut));  // table, then its 16-byte flag area (zero)
   make_lut(code256_a, lut);
   if (two) make_lut(code256_b, lut + 256 + 16);
-  tpg_view* v[2] = {nullptr, nullptr};
-  int32_t *d_rows = nullptr, *d_cols = nullptr;
-  uint8_t* d_lut = nullptr;
-  auto fail = [&](int code) {
-    if (d_rows) tpg_pfree(d_rows);
-    if (d_cols) tpg_pfree(d_cols);
-    if (d_lut) tpg_pfree(d_lut);
-    tpg_view_free(v[0]);
-    tpg_view_free(v[1]);
-    return code;
-  };
-#define VHIP(call)                                                                       \
-  do {                                                                                   \
-    hipError_t _e = (call);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      tpg_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(_e)); \
-      return fail(TPG_EHIP);                                                             \
-    }                                                                                    \
-  } while (0)
+  ViewPtr v[2];
+  DevBuf d_rows, d_cols, d_lut;
   for (int k = 0; k < nv; k++) {
-    v[k] = new tpg_view{ctx, n, m, ceil_div(n, 128), ceil_div(m, 128), nullptr, nullptr, 0};
-    v[k]->bytes_each = (size_t)v[k]->Q * (size_t)v[k]->KG * 4096;
+    v[k].reset(new tpg_view(ctx, n, m));
     // A pair is "the raw view of the pairwise statistics + the imputed view of the PCA": neither reads the 2-bit T
     // layout (the pairwise kernel reads T4, the class Gram its own sorted layout), so the pair is packed as L + T4 and
     // L; whoever does want T gets it from L (tpg_view_need_T).
     // A single RAW-byte view (code256 == NULL) is what the pairwise statistics alone ask for (increment_{ibs,king,as}_counts
     // compare raw bytes, src/snp_ibs.cpp:47-54): it is packed as L + T4 too, which saves a stand-alone snp_ibs / snp_king /
     // pairwise_grm call, and every block of an R driver loop, the T -> T4 pass (0.7 ms at 5 000 x 1 000 000).
-    if (!two && code256_a) VHIP(tpg_pmalloc((void**)&v[k]->T, v[k]->bytes_each));
-    else if (k == 0) VHIP(tpg_pmalloc((void**)&v[k]->T4, 2 * v[k]->bytes_each));
-    VHIP(tpg_pmalloc((void**)&v[k]->L, v[k]->bytes_each));
+    if (!two && code256_a) TPG_HIP(tpg_pmalloc((void**)&v[k]->T, v[k]->bytes_each));
+    else if (k == 0) TPG_HIP(tpg_pmalloc((void**)&v[k]->T4, 2 * v[k]->bytes_each));
+    TPG_HIP(tpg_pmalloc((void**)&v[k]->L, v[k]->bytes_each));
   }
-  VHIP(tpg_pmalloc((void**)&d_lut, sizeof(lut)));
-  VHIP(tpg_h2d_async(ctx, d_lut, lut, (size_t)nv * (256 + 16)));
+  TPG_TRY(d_lut.alloc(sizeof(lut)));
+  TPG_HIP(tpg_h2d_async(ctx, d_lut.p, lut, (size_t)nv * (256 + 16)));
   if (rowInd1) {
-    VHIP(tpg_pmalloc((void**)&d_rows, sizeof(int32_t) * (size_t)n));
-    VHIP(tpg_h2d_async(ctx, d_rows, rowInd1, sizeof(int32_t) * (size_t)n));
+    TPG_TRY(d_rows.alloc_n<int32_t>((size_t)n));
+    TPG_HIP(tpg_h2d_async(ctx, d_rows.p, rowInd1, sizeof(int32_t) * (size_t)n));
   }
   if (colInd1) {
-    VHIP(tpg_pmalloc((void**)&d_cols, sizeof(int32_t) * (size_t)m));
-    VHIP(tpg_h2d_async(ctx, d_cols, colInd1, sizeof(int32_t) * (size_t)m));
+    TPG_TRY(d_cols.alloc_n<int32_t>((size_t)m));
+    TPG_HIP(tpg_h2d_async(ctx, d_cols.p, colInd1, sizeof(int32_t) * (size_t)m));
   }
-  int rc = tpg_launch_pack(ctx, fbm, d_rows, d_cols, d_lut, v[0], v[1]);
-  if (rc != TPG_OK) return fail(rc);
+  TPG_TRY(tpg_launch_pack(ctx, fbm, d_rows.as<int32_t>(), d_cols.as<int32_t>(), d_lut.as<uint8_t>(), v[0].get(), v[1].get()));
   // the "a byte that occurs maps to no 2-bit code" flags: the one host round trip of a view creation
   uint8_t back[2 * (256 + 16)];
-  VHIP(tpg_fetch_small(ctx, back, d_lut, (size_t)nv * (256 + 16)));
-#undef VHIP
+  TPG_HIP(tpg_fetch_small(ctx, back, d_lut.p, (size_t)nv * (256 + 16)));
   for (int k = 0; k < nv; k++) {
     int32_t bad;
     memcpy(&bad, back + k * (256 + 16) + 256, sizeof(bad));
-    if (bad) {
-      tpg_set_error("code256 maps an occurring FBM byte to a value outside {0,1,2,NA}; the 2-bit device path cannot represent it");
-      return fail(TPG_EUNSUPPORTED);
-    }
+    TPG_REQUIRE(!bad, TPG_EUNSUPPORTED,
+                "code256 maps an occurring FBM byte to a value outside {0,1,2,NA}; the 2-bit device path cannot represent it");
   }
-  if (d_rows) tpg_pfree(d_rows);
-  if (d_cols) tpg_pfree(d_cols);
-  tpg_pfree(d_lut);
-  *out_a = v[0];
-  if (two) *out_b = v[1];
+  *out_a = v[0].release();
+  if (two) *out_b = v[1].release();
   return TPG_OK;
 }
 
@@ -1311,14 +1290,23 @@ extern "C" int tpg_view_create_pair(tpg_ctx* ctx, const tpg_fbm* fbm, const int3
   return view_create_impl(ctx, fbm, rowInd1, n, colInd1, m, code256_a, code256_b, true, out_a, out_b);
 }
 
-extern "C" void tpg_view_free(tpg_view* v) {
-  if (!v) return;
-  if (v->T) tpg_pfree(v->T);
-  if (v->L) tpg_pfree(v->L);
-  if (v->T4) tpg_pfree(v->T4);
-  if (v->lc_part) tpg_pfree(v->lc_part);
-  delete v;
+tpg_view::~tpg_view() {
+  drop_derived();
+  if (L && !L_borrowed) tpg_pfree(L);
 }
+void tpg_view::drop_derived() {
+  if (T) tpg_pfree(T);
+  if (T4) tpg_pfree(T4);
+  if (lc_part) tpg_pfree(lc_part);
+  T = T4 = nullptr;
+  lc_part = nullptr;
+  lc_chunks = 0;
+  if (gc_cache.cnt && !gc_cache.borrowed) tpg_pfree(gc_cache.cnt);
+  gc_cache.cnt = nullptr;
+  gc_cache.nclass = 0;
+  gc_cls.clear();
+}
+extern "C" void tpg_view_free(tpg_view* v) { delete v; }
 extern "C" int64_t tpg_view_n(const tpg_view* v) { return v ? v->n : 0; }
 extern "C" int64_t tpg_view_m(const tpg_view* v) { return v ? v->m : 0; }
 
@@ -1329,18 +1317,13 @@ extern "C" int tpg_view_unpack(tpg_ctx* ctx, const tpg_view* v, uint8_t* codes) 
   OutBuf o;
   TPG_TRY(o.init(codes, (size_t)v->n * (size_t)v->m));
   TPG_TRY(tpg_launch_unpack(ctx, v, o.dev<uint8_t>(), 0));
-  uint8_t* d2 = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d2, (size_t)v->n * (size_t)v->m));
-  int rc = tpg_launch_unpack(ctx, v, d2, 1);
+  DevBuf d2;
+  TPG_TRY(d2.alloc((size_t)v->n * (size_t)v->m));
+  TPG_TRY(tpg_launch_unpack(ctx, v, d2.as<uint8_t>(), 1));
   std::vector<uint8_t> a((size_t)v->n * (size_t)v->m), b((size_t)v->n * (size_t)v->m);
-  if (rc == TPG_OK) {
-    hipError_t e = hipMemcpyAsync(a.data(), o.dev<uint8_t>(), a.size(), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b.data(), d2, b.size(), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { tpg_set_error("unpack copy failed: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  }
-  tpg_pfree(d2);
-  TPG_TRY(rc);
+  TPG_HIP(hipMemcpyAsync(a.data(), o.dev<uint8_t>(), a.size(), hipMemcpyDeviceToHost, ctx->stream));
+  TPG_HIP(hipMemcpyAsync(b.data(), d2.p, b.size(), hipMemcpyDeviceToHost, ctx->stream));
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
   TPG_REQUIRE(a == b, TPG_EHIP, "internal error: T and L layouts of the view disagree");
   return o.commit(ctx);
 }

@@ -101,21 +101,6 @@ __global__ void tpg_stream_add_kernel(double* __restrict__ y, const double* __re
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) y[i] += x[i];
 }
 
-struct DevBuf {  // pool block, back to its pool at scope exit (the pool is the context's the calling thread entered)
-  void* p = nullptr;
-  int alloc(size_t bytes) {
-    free();
-    TPG_HIP(tpg_pmalloc(&p, bytes ? bytes : 16));
-    return TPG_OK;
-  }
-  void free() { if (p) tpg_pfree(p); p = nullptr; }
-  ~DevBuf() { free(); }
-  template <typename T> T* as() const { return (T*)p; }
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
 static size_t device_used() {
   size_t fr = 0, tot = 0;
   if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -152,7 +137,7 @@ struct StreamRun {
   std::vector<uint8_t> contiguous;  // per block: colInd runs up by one over the block
 
   // block buffers of the store
-  uint8_t* d_blk[2] = {nullptr, nullptr};
+  DevBuf d_blk[2];
   // A byte store whose blocks are wanted through ONE code table goes up as 2 bits per genotype, packed on the host into the
   // layout of a .bed payload (host_bedpack.h: a quarter of the bytes over PCIe, half of the nibble pack's), and the device
   // packs its views with the .bed front end.  bedpack_lut: byte < 16 -> .bed code (valid = false: not this table); a block in
@@ -182,7 +167,7 @@ struct StreamRun {
   DevBuf d_icnt;  // the QC pass: n x 4 int32, the per-individual sums of the blocks so far (tpg_launch_indiv_accumulate)
   bool have_K = false;
   double fro = 0.0;
-  struct Kept { tpg_view* v = nullptr; DevBuf dc, ds; int64_t q0 = 0, mb = 0; bool L_borrowed = false; };
+  struct Kept { ViewPtr v; DevBuf dc, ds; int64_t q0 = 0, mb = 0; };
   std::deque<Kept> kept;
   // The PCA Gram of a run that keeps its imputed views (no budget) is NOT taken block by block: the class path pays for every
   // weight class a block holds (whole 64-locus MFMA blocks + a fold), and a block of an eighth of the panel still holds nearly
@@ -197,11 +182,6 @@ struct StreamRun {
                            // the loadings are then ONE call and ONE download (eight pieces of 19 MB took 7 ms, one of 160 MB 3)
   DevBuf bigL, big_c, big_s, d_vbig;
   int64_t gram_from = 0;  // loci (positions from P0) whose Gram is in K
-  void free_kept(Kept& kp) {
-    if (kp.v && kp.L_borrowed) kp.v->L = nullptr;  // it points into bigL
-    tpg_view_free(kp.v);
-    kp.v = nullptr;
-  }
   DevBuf d_u, d_nn[4];
   hipEvent_t ev_fin[4] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<double> dh;
@@ -367,7 +347,7 @@ struct StreamRun {
     return blk_bed[slot] ? (job_table ? code012 : nullptr) : job_table;
   }
   tpg_fbm block_fbm(int slot, int64_t mb) const {
-    tpg_fbm f{ctx, d_blk[slot], src->nrow, mb};
+    tpg_fbm f{ctx, d_blk[slot].as<uint8_t>(), src->nrow, mb};
     f.bed_bpl = src->kind == SRC_BED ? src->bpl : blk_bed[slot] ? (src->nrow + 3) / 4 : 0;
     return f;
   }
@@ -384,7 +364,7 @@ struct StreamRun {
     block_range(b, &q0, &q1);
     const int64_t nb = q1 - q0;
     const size_t unit = src->unit();
-    tpg_fbm f{ctx, d_blk[slot], src->nrow, nb};
+    tpg_fbm f{ctx, d_blk[slot].as<uint8_t>(), src->nrow, nb};
     f.bed_bpl = src->kind == SRC_BED ? src->bpl : 0;
     if (src->kind == SRC_SYNTH) {
       TPG_TRY(tpg_launch_synth(up_ctx, f.d_bytes, src->seed, src->nrow, nb, first_col(q0), src->npop, src->miss, src->imputed));
@@ -395,7 +375,7 @@ struct StreamRun {
     const uint8_t* host = nullptr;
     if (bedpack && contiguous[(size_t)b]) {
       bool ok = false;
-      TPG_HIP(tpg_upload_bedpacked(up_ctx, d_blk[slot], src->bytes + (size_t)first_col(q0) * unit, src->nrow, nb, bedpack_lut, &ok));
+      TPG_HIP(tpg_upload_bedpacked(up_ctx, d_blk[slot].as<uint8_t>(), src->bytes + (size_t)first_col(q0) * unit, src->nrow, nb, bedpack_lut, &ok));
       if (ok) {
         blk_bed[slot] = true;
         bytes_up += (size_t)nb * (size_t)((src->nrow + 3) / 4);
@@ -560,25 +540,24 @@ struct StreamRun {
   }
 
   // ------------------------------------------------------------------ the views of a block
-  int make_views(const tpg_fbm* f, int slot, tpg_view** v /* [3] */) {
+  int make_views(const tpg_fbm* f, int slot, ViewPtr* v /* [3] */) {
     const tpg_stream_job* j = job;
-    v[0] = v[1] = v[2] = nullptr;
-    if (ntab == 1) return tpg_view_create(ctx, f, j->rowInd1, n, nullptr, 0, block_table(slot, tab[0]), &v[0]);
+    tpg_view* p[3] = {nullptr, nullptr, nullptr};
+    int rc;
     // (two tables: one read of the block's bytes; three: the odd one out on its own)
     const int a = 0, b = ntab == 2 ? 1 : (view_of_pca >= 0 ? view_of_pca : 2);
-    TPG_TRY(tpg_view_create_pair(ctx, f, j->rowInd1, n, nullptr, 0, tab[a], tab[b], &v[a], &v[b]));
-    if (ntab == 3) {
-      const int c = 3 - a - b;
-      TPG_TRY(tpg_view_create(ctx, f, j->rowInd1, n, nullptr, 0, tab[c], &v[c]));
-    }
-    return TPG_OK;
+    if (ntab == 1) rc = tpg_view_create(ctx, f, j->rowInd1, n, nullptr, 0, block_table(slot, tab[0]), &p[0]);
+    else rc = tpg_view_create_pair(ctx, f, j->rowInd1, n, nullptr, 0, tab[a], tab[b], &p[a], &p[b]);
+    if (rc == TPG_OK && ntab == 3) rc = tpg_view_create(ctx, f, j->rowInd1, n, nullptr, 0, tab[3 - a - b], &p[3 - a - b]);
+    for (int t = 0; t < 3; t++) v[t].reset(p[t]);
+    return rc;
   }
 
   // ------------------------------------------------------------------ first sweep
   int alloc_common() {
     const size_t unit = src->unit();
     const int64_t bmax = std::min<int64_t>(B, P1 - P0);
-    for (int k = 0; k < 2 && k < nblocks; k++) TPG_HIP(tpg_pmalloc((void**)&d_blk[k], (size_t)bmax * unit));
+    for (int k = 0; k < 2 && k < nblocks; k++) TPG_TRY(d_blk[k].alloc((size_t)bmax * unit));
     for (int k = 0; k < 2; k++) {
       if (!out[k].ev) TPG_HIP(hipEventCreateWithFlags(&out[k].ev, hipEventDisableTiming));
       if (!out[k].ev2) TPG_HIP(hipEventCreateWithFlags(&out[k].ev2, hipEventDisableTiming));
@@ -657,11 +636,7 @@ struct StreamRun {
       TPG_TRY(wait_block(b));
       stamp("got block", b);
       const tpg_fbm f = block_fbm(slot, mb);
-      tpg_view* v[3];
-      struct Views {
-        tpg_view** v;
-        ~Views() { for (int t = 0; t < 3; t++) tpg_view_free(v[t]); }
-      } views{v};
+      ViewPtr v[3];
       TPG_TRY(make_views(&f, slot, v));
       // (a view creation ends with a host round trip behind its pack kernel: the block buffer has been read)
       release_block(b);
@@ -670,7 +645,7 @@ struct StreamRun {
       TPG_TRY(wait_slot(slot));
       stamp("output slot free", b);
       if (want_loc || want_fst) {
-        const tpg_view* vl = v[view_of_loc];
+        const tpg_view* vl = v[view_of_loc].get();
         if (j->alt_freq) TPG_TRY(tpg_alt_freq_dip_pseudo(ctx, vl, j->ploidy, j->as_counts, o.af.as<double>()));
         if (j->grouped_alt_freq)
           TPG_TRY(tpg_grouped_alt_freq_dip_pseudo(ctx, vl, j->groupIds0, G, j->ploidy, j->as_counts, o.gaf.as<double>()));
@@ -700,16 +675,13 @@ struct StreamRun {
         }
       }
       stamp("per-locus enqueued", b);
-      if (want_pw) TPG_TRY(tpg_pairwise_accumulate_products(ctx, pw, v[view_of_pw], 0, -1, products));
+      if (want_pw) TPG_TRY(tpg_pairwise_accumulate_products(ctx, pw, v[view_of_pw].get(), 0, -1, products));
       if (want_pca) {
-        tpg_view* vp = v[view_of_pca];
-        struct Imputed {
-          tpg_view* v = nullptr;
-          ~Imputed() { tpg_view_free(v); }
-        } imp;
+        tpg_view* vp = v[view_of_pca].get();
+        ViewPtr imp;
         if (impute) {  // keyed by position in the selection: q0 + the locus of the block
-          TPG_TRY(tpg_view_impute_at(ctx, vp, impute, j->impute_seed, q0, &imp.v, nullptr));
-          vp = imp.v;
+          TPG_TRY(tpg_view_impute_at(ctx, vp, impute, j->impute_seed, q0, &vp, nullptr));
+          imp.reset(vp);
         }
         double *dc = o.dc.as<double>(), *ds = o.ds.as<double>();
         Kept* kp = nullptr;
@@ -740,15 +712,8 @@ struct StreamRun {
         TPG_TRY(rows_out(j->center, 8, m, q0, dc, mb, 1, ev, keep_views ? -1 : slot));
         TPG_TRY(rows_out(j->scale, 8, m, q0, ds, mb, 1, ev, keep_views ? -1 : slot));
         if (kp) {
-          kp->v = vp;  // the imputed view stays for the loadings
-          if (imp.v) imp.v = nullptr;
-          else v[view_of_pca] = nullptr;
-          // what the loadings read is L; the other layouts go back to the pool now
-          if (kp->v->T) { tpg_pfree(kp->v->T); kp->v->T = nullptr; }
-          if (kp->v->T4) { tpg_pfree(kp->v->T4); kp->v->T4 = nullptr; }
-          if (kp->v->lc_part) { tpg_pfree(kp->v->lc_part); kp->v->lc_part = nullptr; kp->v->lc_chunks = 0; }
-          if (kp->v->gc_cache.cnt) { tpg_pfree(kp->v->gc_cache.cnt); kp->v->gc_cache.cnt = nullptr; kp->v->gc_cache.nclass = 0; }
-          kp->v->gc_cls.clear();
+          kp->v = std::move(imp ? imp : v[view_of_pca]);  // the imputed view stays for the loadings
+          kp->v->drop_derived();  // what the loadings read is L; the other layouts go back to the pool now
         }
         if (big_views) {
           // the block's L joins the others (a block starts on a multiple of 128 loci: whole locus tiles), its own copy goes back
@@ -759,16 +724,10 @@ struct StreamRun {
           TPG_HIP(tpg_copy_dev(ctx, big_s.as<double>() + (q0 - P0), ds, 8 * (size_t)mb));
           tpg_pfree(kp->v->L);  // stream-ordered
           kp->v->L = (uint4*)at;
-          kp->L_borrowed = true;
+          kp->v->L_borrowed = true;
           if (batch_gram && b == nblocks - 1) {
-            tpg_view bv{};
-            bv.ctx = ctx;
-            bv.n = n;
-            bv.m = (q1 - P0) - gram_from;
-            bv.Q = ceil_div(n, 128);
-            bv.KG = ceil_div(bv.m, 128);
-            bv.L = (uint4*)(bigL.as<uint8_t>() + (size_t)(gram_from / 128) * per128);
-            bv.bytes_each = (size_t)bv.KG * per128;
+            // (borrowed: the view returns whatever a callee hangs on it -- tpg_view_need_T's T -- and leaves L alone)
+            const tpg_view bv(ctx, n, (q1 - P0) - gram_from, (uint4*)(bigL.as<uint8_t>() + (size_t)(gram_from / 128) * per128));
             const double *bc = big_c.as<double>() + gram_from, *bs = big_s.as<double>() + gram_from;
             if (!have_K) TPG_TRY(tpg_pca_gram(ctx, &bv, bc, bs, d_K.as<double>()));
             else TPG_TRY(tpg_pca_gram_add(ctx, &bv, bc, bs, d_K.as<double>()));
@@ -840,17 +799,13 @@ struct StreamRun {
       stamp("wait for block", b);
       TPG_TRY(wait_block(b));
       const tpg_fbm f = block_fbm(slot, mb);
-      tpg_view* v[3];
-      struct Views {
-        tpg_view** v;
-        ~Views() { for (int t = 0; t < 3; t++) tpg_view_free(v[t]); }
-      } views{v};
+      ViewPtr v[3];
       TPG_TRY(make_views(&f, slot, v));
       release_block(b);
       stamp("packed", b);
       OutSlot& o = out[slot];
       TPG_TRY(wait_slot(slot));
-      const tpg_view* vl = v[0];
+      const tpg_view* vl = v[0].get();
       if (c->loci_counts) TPG_TRY(tpg_loci_counts(ctx, vl, o.lc.as<int32_t>()));
       if (c->hwe_p) TPG_TRY(tpg_loci_hwe(ctx, vl, c->midp, o.hw.as<double>()));
       if (c->grouped_counts) TPG_TRY(tpg_grouped_genotype_counts(ctx, vl, c->groupIds0, G, o.gcn.as<int32_t>()));
@@ -959,20 +914,12 @@ struct StreamRun {
     if (nblocks == 0) return TPG_OK;
     for (int s = 0; s < 2 && s < nblocks; s++) TPG_TRY(out[s].dv.alloc(8 * (size_t)k * (size_t)bmax));
     if (keep_views && big_views) {
-      const size_t per128 = (size_t)ceil_div(n, 128) * 4096;
-      tpg_view bv{};
-      bv.ctx = ctx;
-      bv.n = n;
-      bv.m = P1 - P0;
-      bv.Q = ceil_div(n, 128);
-      bv.KG = ceil_div(bv.m, 128);
-      bv.L = bigL.as<uint4>();
-      bv.bytes_each = (size_t)bv.KG * per128;
+      const tpg_view bv(ctx, n, P1 - P0, bigL.as<uint4>());
       TPG_TRY(d_vbig.alloc(8 * (size_t)k * (size_t)bv.m));
       TPG_TRY(tpg_pca_loadings(ctx, &bv, big_c.as<double>(), big_s.as<double>(), d_u.as<double>(), dh.data(), k, d_vbig.as<double>()));
       TPG_HIP(hipEventRecord(ev_fin[2], ctx->stream));
       TPG_TRY(rows_out(j->v, 8, m, P0, d_vbig.p, bv.m, k, ev_fin[2], -1));
-      for (Kept& kp : kept) free_kept(kp);
+      for (Kept& kp : kept) kp.v.reset();
       sample();
       return TPG_OK;
     }
@@ -982,10 +929,10 @@ struct StreamRun {
         const int slot = (int)(b & 1);
         OutSlot& o = out[slot];
         TPG_TRY(wait_slot(slot));
-        TPG_TRY(tpg_pca_loadings(ctx, kp.v, kp.dc.as<double>(), kp.ds.as<double>(), d_u.as<double>(), dh.data(), k, o.dv.as<double>()));
+        TPG_TRY(tpg_pca_loadings(ctx, kp.v.get(), kp.dc.as<double>(), kp.ds.as<double>(), d_u.as<double>(), dh.data(), k, o.dv.as<double>()));
         TPG_HIP(hipEventRecord(o.ev, ctx->stream));
         TPG_TRY(rows_out(j->v, 8, m, kp.q0, o.dv.p, kp.mb, k, o.ev, slot));
-        free_kept(kp);
+        kp.v.reset();
         b++;
         sample();
       }
@@ -1001,23 +948,20 @@ struct StreamRun {
       const int slot = (int)(b & 1);
       TPG_TRY(wait_block(b));
       const tpg_fbm f = block_fbm(slot, mb);
-      tpg_view* vp = nullptr;
-      TPG_TRY(tpg_view_create(ctx, &f, j->rowInd1, n, nullptr, 0, block_table(slot, code_pca), &vp));
+      tpg_view* made = nullptr;
+      TPG_TRY(tpg_view_create(ctx, &f, j->rowInd1, n, nullptr, 0, block_table(slot, code_pca), &made));
+      ViewPtr vp(made);
       if (impute) {
-        tpg_view* vi = nullptr;
-        const int rci = tpg_view_impute_at(ctx, vp, impute, j->impute_seed, q0, &vi, nullptr);
-        tpg_view_free(vp);
-        TPG_TRY(rci);
-        vp = vi;
+        TPG_TRY(tpg_view_impute_at(ctx, vp.get(), impute, j->impute_seed, q0, &made, nullptr));
+        vp.reset(made);
       }
       release_block(b);
       OutSlot& o = out[slot];
-      int rc = wait_slot(slot);
+      TPG_TRY(wait_slot(slot));
       // the same per-locus center and scale as in the first sweep (the same counts through the same arithmetic)
-      if (rc == TPG_OK) rc = tpg_pca_center_scale(ctx, vp, o.dc.as<double>(), o.ds.as<double>());
-      if (rc == TPG_OK) rc = tpg_pca_loadings(ctx, vp, o.dc.as<double>(), o.ds.as<double>(), d_u.as<double>(), dh.data(), k, o.dv.as<double>());
-      tpg_view_free(vp);
-      TPG_TRY(rc);
+      TPG_TRY(tpg_pca_center_scale(ctx, vp.get(), o.dc.as<double>(), o.ds.as<double>()));
+      TPG_TRY(tpg_pca_loadings(ctx, vp.get(), o.dc.as<double>(), o.ds.as<double>(), d_u.as<double>(), dh.data(), k, o.dv.as<double>()));
+      vp.reset();
       TPG_HIP(hipEventRecord(o.ev, ctx->stream));
       TPG_TRY(rows_out(j->v, 8, m, q0, o.dv.p, mb, k, o.ev, slot));
       sample();
@@ -1051,7 +995,6 @@ struct StreamRun {
       (void)hipStreamSynchronize(ctx->stream);
       if (down_ctx) (void)hipStreamSynchronize(down_ctx->stream);
       if (up_ctx) (void)hipStreamSynchronize(up_ctx->stream);
-      for (Kept& kp : kept) { free_kept(kp); kp.dc.free(); kp.ds.free(); }
       kept.clear();
       bigL.free();
       big_c.free();
@@ -1059,7 +1002,7 @@ struct StreamRun {
       d_vbig.free();
       if (pw) { tpg_pairwise_free(pw); pw = nullptr; }
       for (int k = 0; k < 2; k++) {
-        if (d_blk[k]) { tpg_pfree(d_blk[k]); d_blk[k] = nullptr; }
+        d_blk[k].free();
         OutSlot& o = out[k];
         o.af.free(); o.gaf.free(); o.gm.free(); o.lc.free(); o.dc.free(); o.ds.free(); o.dv.free();
       o.hw.free(); o.gcn.free(); o.ghw.free();
