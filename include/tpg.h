@@ -243,6 +243,61 @@ typedef struct tpg_ld_report {
 int tpg_ld_clump(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, double thr_r2, const double* S,
                  const uint8_t* exclude, uint8_t* keep, tpg_ld_report* report);
 
+/* ---- Runs of homozygosity (windows_indiv_roh, R/windows_indiv_roh.R:65-150 around detectRUNS::slidingRuns) ---------------
+ * detectRUNS is not part of the reference checkout, so the definition below is this project's own.  It is
+ * stated in integers; the two places where a double appears are spelled out.
+ * Input: a view of n individuals x m loci (codes 0, 1, 2, and 3 = missing), chrom (int32[m]) and pos (int64[m]) of its loci,
+ *   host or device memory, and the parameters below.  window_size W outside [1, 512], threshold outside [0, 1], a negative
+ *   max_*_window: TPG_EINVAL.
+ * Per individual:
+ *   1. opp[j] = (code == 1); with heterozygosity != 0 (runs of heterozygosity) opp[j] = (code is 0 or 2).  miss[j] = (code == 3).
+ *   2. brk[j], 0 <= j < m - 1, = chrom[j] != chrom[j + 1] || pos[j + 1] - pos[j] > max_gap.  Only neighbours are compared.  A
+ *      position that decreases inside a chromosome: TPG_EINVAL ("not ordered"); equal positions are allowed.
+ *   3. Window w covers the loci [w, w + W), 0 <= w <= m - W.  It is OK iff sum opp <= max_opp_window, sum miss <=
+ *      max_miss_window and no brk[j] for j in [w, w + W - 2]: a window never spans a chromosome boundary or a gap.  m < W:
+ *      no window, no run (TPG_OK).
+ *   4. The windows that contain locus j start in [max(0, j - W + 1), min(j, m - W)]: `cover` of them (1 .. W), `hits` of them
+ *      OK.  need[c] = max(1, ceil(threshold * (double)c)), c = 1 .. W: one IEEE double multiplication and one ceil, on the
+ *      host.  Locus j is IN A RUN iff hits >= need[cover] (the device compares integers).
+ *   5. A SEGMENT is a maximal stretch [a, b] of in-run loci with no brk between neighbours inside it; nSNP = b - a + 1,
+ *      length = pos[b] - pos[a], nOpp / nMiss = sum of opp / miss over [a, b].  It is a RUN iff nSNP >= min_snp, length >=
+ *      min_length_bps, (double)nSNP * 1000.0 >= min_density * (double)length (one multiplication on either side, no
+ *      division, no FMA), and nOpp <= max_opp_run, nMiss <= max_miss_run where those are >= 0.
+ * Output: all runs, ordered by (individual, first locus); deterministic, independent of chunking and launch geometry. */
+typedef struct tpg_roh_params {
+  int32_t window_size;     /* W */
+  double threshold;        /* share of the windows over a locus that must be OK */
+  int32_t min_snp;
+  int32_t heterozygosity;  /* 0: runs of homozygosity, otherwise runs of heterozygosity */
+  int32_t max_opp_window;
+  int32_t max_miss_window;
+  int64_t max_gap;         /* bp */
+  int64_t min_length_bps;
+  double min_density;      /* SNPs per kbp */
+  int32_t max_opp_run;     /* < 0: no limit */
+  int32_t max_miss_run;    /* < 0: no limit */
+} tpg_roh_params;
+typedef struct tpg_roh tpg_roh; /* the runs of one call, owned by the library (device memory) */
+/* loci per chunk of the status stage (a chunk is cut with a halo of W - 1 loci on either side; results do not depend on it) */
+#define TPG_ROH_CHUNK_LOCI 2048
+int64_t tpg_roh_chunk_loci(void);
+/* step 4 alone: row i = stride_words uint32, bit j & 31 of word j >> 5 <-> locus j of individual i is in a run;
+ * stride_words >= ceil(m / 32); unused words and padding bits are 0.  bits may be host or device memory. */
+int tpg_roh_snp_status(tpg_ctx* ctx, const tpg_view* v, const int32_t* chrom, const int64_t* pos, const tpg_roh_params* params,
+                       uint32_t* bits, int64_t stride_words);
+/* steps 1 - 5 on the device: two counts (segments, runs) cross to the host, nothing proportional to n m does */
+int tpg_roh_detect(tpg_ctx* ctx, const tpg_view* v, const int32_t* chrom, const int64_t* pos, const tpg_roh_params* params,
+                   tpg_roh** out);
+int64_t tpg_roh_count(const tpg_roh* r);
+/* tpg_roh_count entries each, 0-based, any may be NULL; host or device memory */
+int tpg_roh_fetch(tpg_ctx* ctx, const tpg_roh* r, int32_t* indiv0, int64_t* first0, int64_t* last0, int32_t* n_opp,
+                  int32_t* n_miss);
+/* per individual (n entries each): number of runs, sum of their lengths in bp */
+int tpg_roh_indiv_summary(tpg_ctx* ctx, const tpg_roh* r, int64_t* n_runs, int64_t* sum_length_bps);
+/* per locus (m entries): individuals with that locus inside a run (a difference array and a scan on the device) */
+int tpg_roh_locus_counts(tpg_ctx* ctx, const tpg_roh* r, int32_t* counts);
+void tpg_roh_free(tpg_roh* r);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

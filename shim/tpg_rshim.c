@@ -999,6 +999,97 @@ SEXP _tidypopgen_tpg_ld_clump(SEXP BM, SEXP rowInd, SEXP colInd, SEXP hi, SEXP t
   return out;
 }
 
+/* ---- runs of homozygosity -------------------------------------------------------------------------------------- */
+
+#pragma weak tpg_roh_detect
+#pragma weak tpg_roh_count
+#pragma weak tpg_roh_fetch
+#pragma weak tpg_roh_free
+
+/* tpg_indiv_roh(BM, rowInd, colInd, chrom, pos, params): the per-individual loop of R/windows_indiv_roh.R:129-143 (one row
+ * of the FBM and one detectRUNS::slidingRuns call per individual) in one call; include/tpg.h "Runs of homozygosity" is the
+ * definition.  chrom = one integer code per locus of colInd (as.integer(factor(chromosome))), pos = its position; params =
+ * 11 numbers in the order of tpg_roh_params: window_size, threshold, min_snp, heterozygosity, max_opp_window,
+ * max_miss_window, max_gap, min_length_bps, min_density, max_opp_run, max_miss_run (NA in the last two: no limit).
+ * -> list(indiv, nSNP, from, to, lengthBps, first, last), one entry per run ordered by (individual, first locus): indiv =
+ * position in rowInd, first / last = positions in colInd, all 1-based; from / to / lengthBps in bp. */
+static tpg_roh* g_roh_pending = NULL; /* the runs of a call whose R allocations are still to come: an R error there (a longjmp)
+                                         leaves them here, and the next call or the unload frees them */
+
+static void roh_drop_pending(void) {
+  if (g_roh_pending && tpg_roh_free) tpg_roh_free(g_roh_pending);
+  g_roh_pending = NULL;
+}
+
+static int32_t roh_int_param(const double* q, int k, double lo, double hi, const char* name) {
+  if (ISNAN(q[k]) || q[k] < lo || q[k] > hi || q[k] != floor(q[k]))
+    Rf_error("tidypopgen (GPU): params[%d] (%s) must be a whole number in [%.0f, %.0f]", k + 1, name, lo, hi);
+  return (int32_t)q[k];
+}
+
+SEXP _tidypopgen_tpg_indiv_roh(SEXP BM, SEXP rowInd, SEXP colInd, SEXP chrom, SEXP pos, SEXP params) {
+  TPG_NEEDS(tpg_roh_detect);
+  roh_drop_pending();
+  if ((TYPEOF(chrom) != INTSXP && TYPEOF(chrom) != REALSXP) || (TYPEOF(pos) != INTSXP && TYPEOF(pos) != REALSXP) ||
+      (TYPEOF(params) != INTSXP && TYPEOF(params) != REALSXP))
+    Rf_error("tidypopgen (GPU): chrom, pos and params must be integer or double vectors");
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP ch = PROTECT(as_int(chrom)), ps = PROTECT(as_real(pos)), pr = PROTECT(as_real(params));
+  const R_xlen_t m = XLENGTH(ci);
+  if (XLENGTH(ch) != m || XLENGTH(ps) != m) Rf_error("tidypopgen (GPU): chrom / pos and colInd differ in length");
+  if (XLENGTH(pr) != 11) Rf_error("tidypopgen (GPU): params must be the 11 numbers of tpg_roh_params");
+  const double* q = REAL(pr);
+  for (int k = 0; k < 9; k++)
+    if (ISNAN(q[k])) Rf_error("tidypopgen (GPU): NA in params[%d]", k + 1);
+  const double big = 2147483647.0, big64 = 9007199254740992.0; /* 2^53: the whole numbers a double holds exactly */
+  tpg_roh_params P;
+  P.window_size = roh_int_param(q, 0, -big, big, "window_size"); /* (the library says which windows it takes) */
+  P.threshold = q[1];
+  P.min_snp = roh_int_param(q, 2, -big, big, "min_snp");
+  P.heterozygosity = q[3] != 0;
+  P.max_opp_window = roh_int_param(q, 4, -big, big, "max_opp_window");
+  P.max_miss_window = roh_int_param(q, 5, -big, big, "max_miss_window");
+  if (fabs(q[6]) > big64 || fabs(q[7]) > big64) Rf_error("tidypopgen (GPU): max_gap / min_length_bps out of range");
+  P.max_gap = (int64_t)q[6];
+  P.min_length_bps = (int64_t)q[7];
+  P.min_density = q[8];
+  P.max_opp_run = ISNAN(q[9]) ? -1 : roh_int_param(q, 9, -big, big, "max_opp_run");
+  P.max_miss_run = ISNAN(q[10]) ? -1 : roh_int_param(q, 10, -big, big, "max_miss_run");
+  int64_t* p64 = (int64_t*)R_alloc((size_t)(m > 0 ? m : 1), sizeof(int64_t));
+  for (R_xlen_t j = 0; j < m; j++) {
+    if (INTEGER(ch)[j] == NA_INTEGER || !isfinite(REAL(ps)[j]) || fabs(REAL(ps)[j]) > big64)
+      Rf_error("tidypopgen (GPU): NA in chrom or pos");
+    p64[j] = (int64_t)REAL(ps)[j];
+  }
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  tpg_roh* r = NULL;
+  TPG_R_VIEW(v, tpg_roh_detect(ctx(), v, INTEGER(ch), p64, &P, &r));
+  g_roh_pending = r; /* from here to roh_drop_pending() every R allocation may raise an error */
+  const int64_t c = tpg_roh_count(r);
+  if (c > INT32_MAX) Rf_error("tidypopgen (GPU): too many runs for an R vector of integers");
+  SEXP vals[7];
+  static const char* names[7] = {"indiv", "nSNP", "from", "to", "lengthBps", "first", "last"};
+  static const int is_real[7] = {0, 0, 1, 1, 1, 0, 0};
+  for (int k = 0; k < 7; k++) vals[k] = PROTECT(Rf_allocVector(is_real[k] ? REALSXP : INTSXP, (R_xlen_t)c));
+  int64_t* ab = (int64_t*)R_alloc((size_t)(c > 0 ? 2 * c : 1), sizeof(int64_t));
+  const int rc = tpg_roh_fetch(ctx(), r, (int32_t*)INTEGER(vals[0]), ab, ab + c, NULL, NULL);
+  roh_drop_pending();
+  if (rc != TPG_OK) Rf_error("tidypopgen (GPU): %s", tpg_last_error());
+  for (int64_t k = 0; k < c; k++) {
+    const int64_t a = ab[k], b = ab[c + k];
+    INTEGER(vals[0])[k] += 1;
+    INTEGER(vals[1])[k] = (int)(b - a + 1);
+    REAL(vals[2])[k] = (double)p64[a];
+    REAL(vals[3])[k] = (double)p64[b];
+    REAL(vals[4])[k] = (double)(p64[b] - p64[a]);
+    INTEGER(vals[5])[k] = (int)a + 1;
+    INTEGER(vals[6])[k] = (int)b + 1;
+  }
+  SEXP out = named_list(7, names, vals);
+  UNPROTECT(12);
+  return out;
+}
+
 /* ---- registration ------------------------------------------------------------------------------------------------
  * Same names and arities as the reference's table (src/RcppExports.cpp:348-371).  These rows replace the rows of the
  * same name there, and so do the three HWE rows of tpg_rshim_entries_hwe[] below; the other rows of that table
@@ -1050,20 +1141,27 @@ const R_CallMethodDef tpg_rshim_entries_ld[] = {
     {"_tidypopgen_tpg_ld_clump", (DL_FUNC)&_tidypopgen_tpg_ld_clump, 7},
     {NULL, NULL, 0}};
 
+/* Runs of homozygosity, in a table of its own too: the reference's routine is R around detectRUNS, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_roh[] = {
+    {"_tidypopgen_tpg_indiv_roh", (DL_FUNC)&_tidypopgen_tpg_indiv_roh, 6},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the four tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the five tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
-                             sizeof(tpg_rshim_entries_ld) / sizeof(tpg_rshim_entries_ld[0])];
+                             sizeof(tpg_rshim_entries_ld) / sizeof(tpg_rshim_entries_ld[0]) +
+                             sizeof(tpg_rshim_entries_roh) / sizeof(tpg_rshim_entries_roh[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_hwe; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_ld; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_roh; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;
@@ -1075,6 +1173,7 @@ void R_init_tpgshim(DllInfo* dll) {
 void R_unload_tpgshim(DllInfo* dll) {
   (void)dll;
   _tidypopgen_tpg_release();
+  roh_drop_pending();
   if (g_multi) {
     tpg_multi_destroy(g_multi);
     g_multi = NULL;

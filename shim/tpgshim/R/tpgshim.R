@@ -106,6 +106,21 @@ tpg_ld_clump <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigsta
         if (is.null(S)) NULL else as.numeric(S), ex)
 }
 
+# runs of homozygosity of every individual in one call (the loop of R/windows_indiv_roh.R:129-143 around
+# detectRUNS::slidingRuns; include/tpg.h "Runs of homozygosity" is the definition).  chromosome / position describe the loci of
+# ind.col, which must be ordered.  Returns a data.frame with one row per run: indiv (position in ind.row), nSNP, from, to,
+# lengthBps, first, last (positions in ind.col).
+tpg_indiv_roh <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), chromosome, position,
+                          window_size = 15, threshold = 0.05, min_snp = 3, heterozygosity = FALSE, max_opp_window = 1,
+                          max_miss_window = 1, max_gap = 10^6, min_length_bps = 1000, min_density = 1 / 1000,
+                          max_opp_run = NULL, max_miss_run = NULL) {
+  params <- c(window_size, threshold, min_snp, as.numeric(heterozygosity), max_opp_window, max_miss_window, max_gap,
+              min_length_bps, min_density, if (is.null(max_opp_run)) NA_real_ else max_opp_run,
+              if (is.null(max_miss_run)) NA_real_ else max_miss_run)
+  as.data.frame(.Call(`_tidypopgen_tpg_indiv_roh`, X, as.integer(ind.row), as.integer(ind.col),
+                      as.integer(factor(chromosome, levels = unique(chromosome))), as.numeric(position), as.numeric(params)))
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

@@ -101,6 +101,8 @@ SYMBOLS = [
     "tpg_stream_close", "tpg_stream_run", "tpg_multi_stream_run", "tpg_fbm_impute_simple", "tpg_fbm_impute_simple_at", "tpg_view_impute",
     "tpg_hwe_exact_counts", "tpg_loci_hwe", "tpg_gt_grouped_hwe", "tpg_stream_qc",
     "tpg_ld_band_links", "tpg_ld_clump",
+    "tpg_roh_chunk_loci", "tpg_roh_snp_status", "tpg_roh_detect", "tpg_roh_count", "tpg_roh_fetch", "tpg_roh_indiv_summary",
+    "tpg_roh_locus_counts", "tpg_roh_free",
 ]
 
 
@@ -143,6 +145,14 @@ class LdReport(C.Structure):
                 ("band_bytes", C.c_int64)]
 
 
+class RohParams(C.Structure):
+    """tpg_roh_params of include/tpg.h, field for field"""
+    _fields_ = [("window_size", C.c_int32), ("threshold", C.c_double), ("min_snp", C.c_int32), ("heterozygosity", C.c_int32),
+                ("max_opp_window", C.c_int32), ("max_miss_window", C.c_int32), ("max_gap", C.c_int64),
+                ("min_length_bps", C.c_int64), ("min_density", C.c_double), ("max_opp_run", C.c_int32),
+                ("max_miss_run", C.c_int32)]
+
+
 class StreamReport(C.Structure):
     """tpg_stream_report of include/tpg.h"""
     _fields_ = [
@@ -166,6 +176,18 @@ if hasattr(lib, "tpg_stream_qc"):
 if hasattr(lib, "tpg_ld_clump"):
     lib.tpg_ld_band_links.argtypes = [vp, vp, vp, C.c_double, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.tpg_ld_clump.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp, C.POINTER(LdReport)]
+if hasattr(lib, "tpg_roh_detect"):
+    lib.tpg_roh_chunk_loci.restype = C.c_int64
+    lib.tpg_roh_chunk_loci.argtypes = []
+    lib.tpg_roh_snp_status.argtypes = [vp, vp, vp, vp, C.POINTER(RohParams), vp, C.c_int64]
+    lib.tpg_roh_detect.argtypes = [vp, vp, vp, vp, C.POINTER(RohParams), C.POINTER(vp)]
+    lib.tpg_roh_count.restype = C.c_int64
+    lib.tpg_roh_count.argtypes = [vp]
+    lib.tpg_roh_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.tpg_roh_indiv_summary.argtypes = [vp, vp, vp, vp]
+    lib.tpg_roh_locus_counts.argtypes = [vp, vp, vp]
+    lib.tpg_roh_free.restype = None
+    lib.tpg_roh_free.argtypes = [vp]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

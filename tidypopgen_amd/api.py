@@ -1641,6 +1641,133 @@ def loci_ld_clump(X: FBM, ind_row=None, ind_col=None, S=None, thr_r2: float = 0.
     return np.flatnonzero(keep) + 1 if return_id else keep
 
 
+# include/tpg.h "Runs of homozygosity": loci per chunk of the status stage (results do not depend on it; the seam tests do)
+ROH_CHUNK_LOCI = int(lib.tpg_roh_chunk_loci()) if hasattr(lib, "tpg_roh_chunk_loci") else 0
+
+
+def _roh_params(window_size=15, threshold=0.05, min_snp=3, heterozygosity=False, max_opp_window=1, max_miss_window=1,
+                max_gap=10**6, min_length_bps=1000, min_density=1 / 1000, max_opp_run=None, max_miss_run=None) -> "_lib.RohParams":
+    if not 1 <= int(window_size) <= 512:
+        raise ValueError("window_size must lie in 1..512")
+    if not 0.0 <= float(threshold) <= 1.0:
+        raise ValueError("threshold must lie in [0, 1]")
+    return _lib.RohParams(int(window_size), float(threshold), int(min_snp), int(bool(heterozygosity)), int(max_opp_window),
+                          int(max_miss_window), int(max_gap), int(min_length_bps), float(min_density),
+                          -1 if max_opp_run is None else int(max_opp_run), -1 if max_miss_run is None else int(max_miss_run))
+
+
+def _roh_loci(m: int, chromosome, position):
+    """chromosome -> int32 codes (neighbours with equal labels get equal codes), position -> int64; loci must be ordered: positions
+    non-decreasing inside a chromosome (neighbours are compared, as include/tpg.h states)"""
+    if position is None:
+        raise ValueError("runs of homozygosity need the positions of the loci")
+    pos = np.ascontiguousarray(position, dtype=np.int64)
+    if chromosome is None:
+        chrom = np.zeros(len(pos), dtype=np.int32)
+    else:
+        c = np.asarray(chromosome).ravel()  # only neighbours are compared: the index of the stretch of equal labels will do
+        chrom = np.zeros(len(c), dtype=np.int32)
+        if len(c) > 1:
+            np.cumsum(c[1:] != c[:-1], out=chrom[1:])
+    if chrom.shape != (m,) or pos.shape != (m,):
+        raise ValueError("chromosome / position must describe every locus of the view")
+    if np.any((chrom[1:] == chrom[:-1]) & (pos[1:] < pos[:-1])):
+        raise ValueError("loci are not ordered: positions decrease inside a chromosome")
+    return chrom, pos
+
+
+def roh_snp_status(v: View, chromosome, position, stride_words: Optional[int] = None, return_bits: bool = False, **params):
+    """tpg_roh_snp_status: is locus j of individual i in a run (step 4 of include/tpg.h "Runs of homozygosity")?  (n, m) bool;
+    with return_bits the packed rows as the library wrote them, (n, stride_words) uint32"""
+    P = _roh_params(**params)
+    chrom, pos = _roh_loci(v.m, chromosome, position)
+    stride = -(-v.m // 32) if stride_words is None else int(stride_words)
+    bits = np.full((v.n, stride), 0xFFFFFFFF, dtype=np.uint32)  # (every word is written: the library zeroes what it does not use)
+    check(lib.tpg_roh_snp_status(v.ctx.h, v.h, _ptr(chrom), _ptr(pos), C.byref(P), _ptr(bits), C.c_int64(stride)))
+    if return_bits:
+        return bits
+    return np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little")[:, :v.m].astype(bool)
+
+
+class Roh:
+    """the runs of one tpg_roh_detect call, in device memory until fetched (tpg_roh)"""
+
+    def __init__(self, v: View, chromosome, position, _loci=None, **params):
+        P = _roh_params(**params)
+        chrom, pos = _loci if _loci is not None else _roh_loci(v.m, chromosome, position)  # (_loci: what _roh_loci returned)
+        self.ctx, self.n, self.m = v.ctx, v.n, v.m
+        h = C.c_void_p()
+        check(lib.tpg_roh_detect(v.ctx.h, v.h, _ptr(chrom), _ptr(pos), C.byref(P), C.byref(h)))
+        self.h = h
+        self.count = int(lib.tpg_roh_count(h))
+
+    def fetch(self) -> dict:
+        c = self.count
+        out = dict(indiv=np.zeros(c, dtype=np.int32), first=np.zeros(c, dtype=np.int64), last=np.zeros(c, dtype=np.int64),
+                   n_opp=np.zeros(c, dtype=np.int32), n_miss=np.zeros(c, dtype=np.int32))
+        check(lib.tpg_roh_fetch(self.ctx.h, self.h, _ptr(out["indiv"]), _ptr(out["first"]), _ptr(out["last"]), _ptr(out["n_opp"]),
+                                _ptr(out["n_miss"])))
+        return out
+
+    def indiv_summary(self):
+        n_runs, total = np.zeros(self.n, dtype=np.int64), np.zeros(self.n, dtype=np.int64)
+        check(lib.tpg_roh_indiv_summary(self.ctx.h, self.h, _ptr(n_runs), _ptr(total)))
+        return n_runs, total
+
+    def locus_counts(self) -> np.ndarray:
+        counts = np.zeros(self.m, dtype=np.int32)
+        check(lib.tpg_roh_locus_counts(self.ctx.h, self.h, _ptr(counts)))
+        return counts
+
+    def free(self):
+        if self.h:
+            lib.tpg_roh_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def windows_indiv_roh(X: FBM, ind_row=None, ind_col=None, chromosome=None, position=None, window_size=15, threshold=0.05,
+                      min_snp=3, heterozygosity=False, max_opp_window=1, max_miss_window=1, max_gap=10**6, min_length_bps=1000,
+                      min_density=1 / 1000, max_opp_run=None, max_miss_run=None, ids=None, groups=None,
+                      return_report: bool = False):
+    """R/windows_indiv_roh.R:65-150 (around detectRUNS::slidingRuns; the definition is include/tpg.h "Runs of homozygosity"):
+    the per-individual loop of the reference in one call.  chromosome / position describe the loci of ind_col, in order.
+    Returns the reference's seven columns (group, id, chrom, nSNP, from, to, lengthBps) as a dict of arrays, one entry per
+    run, ordered by (individual, first locus), and first_locus / last_locus (0-based positions in ind_col), n_opp, n_miss.
+    id defaults to the row index (0-based position in ind_row), group to id, as in the reference's ungrouped case.  With
+    return_report also {n_runs, sum_length_bps (per individual), locus_counts (individuals with the locus inside a run)}."""
+    P = dict(window_size=window_size, threshold=threshold, min_snp=min_snp, heterozygosity=heterozygosity,
+             max_opp_window=max_opp_window, max_miss_window=max_miss_window, max_gap=max_gap, min_length_bps=min_length_bps,
+             min_density=min_density, max_opp_run=max_opp_run, max_miss_run=max_miss_run)
+    _roh_params(**P)  # (refuses a bad window before anything is packed)
+    if position is None:
+        raise ValueError("runs of homozygosity need the positions of the loci")
+    m = X.ncol if ind_col is None else len(ind_col)
+    loci = _roh_loci(m, chromosome, position)
+    v = View(X, ind_row, ind_col)
+    r = Roh(v, chromosome, position, _loci=loci, **P)
+    runs = r.fetch()
+    ids = np.arange(v.n) if ids is None else np.asarray(ids)
+    groups = ids if groups is None else np.asarray(groups)
+    if len(ids) != v.n or len(groups) != v.n:
+        raise ValueError("ids / groups must have one entry per individual of ind_row")
+    pos = np.asarray(position, dtype=np.int64)
+    chrom = np.zeros(v.m, dtype=np.int64) if chromosome is None else np.asarray(chromosome)
+    i, a, b = runs["indiv"], runs["first"], runs["last"]
+    out = {"group": groups[i], "id": ids[i], "chrom": chrom[a], "nSNP": (b - a + 1).astype(np.int64), "from": pos[a],
+           "to": pos[b], "lengthBps": pos[b] - pos[a], "first_locus": a, "last_locus": b, "n_opp": runs["n_opp"],
+           "n_miss": runs["n_miss"]}
+    if return_report:
+        n_runs, total = r.indiv_summary()
+        return out, {"n_runs": n_runs, "sum_length_bps": total, "locus_counts": r.locus_counts()}
+    return out
+
+
 def gt_impute_simple(X: FBM, method: str = "mode", seed: int = 0) -> FBM:
     """R/gt_impute_simple.R:54-93: the missing genotypes of X are filled in place (FBM.impute_simple) and X then reads
     through CODE_IMPUTE_PRED, as the reference leaves the gen_tibble's FBM; the report is left in `X.impute_report`.
