@@ -298,6 +298,44 @@ int tpg_roh_indiv_summary(tpg_ctx* ctx, const tpg_roh* r, int64_t* n_runs, int64
 int tpg_roh_locus_counts(tpg_ctx* ctx, const tpg_roh* r, int32_t* counts);
 void tpg_roh_free(tpg_roh* r);
 
+/* ---- Tajima's D (pop_tajimas_d, R/pop_tajimas_d.R:151-166; windows_pop_tajimas_d, R/windows_pop_tajimas_d.R:69-102 over
+ * R/windows_stats_generic.R:113-176; pi as src/gt_pi_diploid.cpp:22-35 and src/gt_grouped_pi_diploid.cpp:24-38) -----------
+ * Group g has N_g individuals in the view and n = 2 N_g sampled alleles: the group's size, not its typed count.  J is a set
+ * of loci (the whole view, or a window).
+ * pi:    pi(j, g) = x (v - x) / (v (v - 1) / 2), x = alternate alleles over the typed individuals of g at locus j, v = twice
+ *        their number; evaluated in exactly this order in IEEE double (no FMA contraction); v = 0 gives NaN.
+ * seg:   S = #{j in J : 0 < pi < 1}.  A NaN is not counted; pi = 1 (v = 2, x = 1) is not segregating.
+ * k_hat: the sum of pi over J, without a NaN guard: one locus at which the group has no typed individual makes k_hat, and D,
+ *        NaN.
+ * D:     (k_hat - S / a1) / sqrt(e1 S + e2 S (S - 1)) with a1 = sum_{i<n} 1/i, a2 = sum_{i<n} 1/i^2 (both summed in ascending
+ *        order of i), e1 = ((n + 1) / (3 (n - 1)) - 1 / a1) / a1, e2 = (2 (n^2 + n + 3) / (9 n (n - 1)) - (n + 2) / (n a1) +
+ *        a2 / a1^2) / (a1^2 + a2), all in double on the host.  Plain IEEE arithmetic, no special case: S = 0 gives NaN (0 / 0)
+ *        or +Inf (k_hat / 0), N_g = 1 gives e1 = e2 = 0 exactly.  A group nobody belongs to (the reference cannot have one):
+ *        D and k_hat NaN, seg 0.
+ * Windows: window w covers the loci lo[w] .. hi[w]-1 with a pad_na flag, the contract of tpg_window_stats.  n_loci = the
+ *        number of non-NaN pi in the window, -1 for a pad_na window.  D is NaN where pad_na is set or n_loci < min_loci; seg
+ *        and k_hat are reported all the same (0 and NaN for a pad_na window).
+ * Determinism: a result depends on (lo, hi, group) alone -- not on nw, on the window's place in the list or on launch
+ *        geometry -- and two calls give the same bits.  k_hat is within L 2^-52 k_hat of the exact sum of the L doubles.
+ * Diploid only (stopifnot_diploid): ploidy may be NULL; anything other than 2 in it is TPG_EINVAL.
+ * groupIds0 == NULL: one group of everybody.  Nothing proportional to m crosses PCIe. */
+/* host only, no context, no GPU: D from the additive pieces, so that a caller can add seg and k_hat over shards or blocks.
+ * n_alleles < 2 or seg < 0: TPG_EINVAL */
+int tpg_tajimas_d_from_sums(int64_t n_alleles, int64_t seg, double k_hat, double* d);
+/* loci per partial sum of the whole-view reduction (results do not depend on it) */
+#define TPG_TAJIMA_CHUNK_LOCI 1024
+int64_t tpg_tajima_chunk_loci(void);
+/* whole view: d, seg, k_hat have ngroups entries each, host memory (seg, k_hat may be NULL) */
+int tpg_pop_tajimas_d(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, const double* ploidy, double* d,
+                      int64_t* seg, double* k_hat);
+/* nw x ngroups column-major each; seg, k_hat, n_loci may be NULL; lo, hi, pad_na (may be NULL) and the outputs host or device
+ * memory.  A window outside [0, m], lo > hi, min_loci < 1, nw > TPG_TAJIMA_MAX_WINDOWS (one workgroup per window: split the
+ * list): TPG_EINVAL; nw == 0: TPG_OK, nothing written */
+#define TPG_TAJIMA_MAX_WINDOWS 16777215
+int tpg_windows_pop_tajimas_d(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, const double* ploidy,
+                              const int64_t* lo, const int64_t* hi, const uint8_t* pad_na, int64_t nw, int min_loci, double* d,
+                              int64_t* seg, double* k_hat, int32_t* n_loci);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

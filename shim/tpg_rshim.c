@@ -1090,6 +1090,91 @@ SEXP _tidypopgen_tpg_indiv_roh(SEXP BM, SEXP rowInd, SEXP colInd, SEXP chrom, SE
   return out;
 }
 
+/* ---- Tajima's D ------------------------------------------------------------------------------------------------- */
+
+#pragma weak tpg_pop_tajimas_d
+#pragma weak tpg_windows_pop_tajimas_d
+
+/* groupIds as the grouped entry points take it, or NULL (one group of everybody: ngroups must then be 1).  The result is
+ * returned UNPROTECTED: the caller must PROTECT it before anything else allocates (both callers do so in the same statement). */
+static SEXP tajima_groups(SEXP groupIds, SEXP ri, int G) {
+  if (groupIds == R_NilValue) {
+    if (G != 1) Rf_error("tidypopgen (GPU): groupIds = NULL means one group, ngroups must be 1");
+    return R_NilValue;
+  }
+  SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
+  if (XLENGTH(gid) != XLENGTH(ri)) Rf_error("tidypopgen (GPU): groupIds and rowInd differ in length");
+  UNPROTECT(1);
+  return gid;
+}
+
+/* tpg_pop_tajimas_d(BM, rowInd, colInd, groupIds, ngroups): the big_apply of gt_grouped_pi_diploid and the loop over groups
+ * of R/pop_tajimas_d.R:113-147 in one call (include/tpg.h "Tajima's D") -> one D per group; groupIds = NULL: one group */
+SEXP _tidypopgen_tpg_pop_tajimas_d(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups) {
+  TPG_NEEDS(tpg_pop_tajimas_d);
+  const int G = ngroups_of(ngroups);
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP gid = PROTECT(tajima_groups(groupIds, ri, G));
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, G));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_pop_tajimas_d(ctx(), v, gid == R_NilValue ? NULL : INTEGER(gid), G, NULL, REAL(out), NULL, NULL));
+  UNPROTECT(4);
+  return out;
+}
+
+/* tpg_windows_pop_tajimas_d(BM, rowInd, colInd, groupIds, ngroups, lo, hi, pad_na, min_loci): loci_pi and the
+ * windows_stats_generic(operator = "custom") call per group of R/windows_pop_tajimas_d.R:80-103 in one call.  lo / hi =
+ * 0-based half-open locus ranges (positions in colInd), integer or double; pad_na = logical, or NULL.
+ * -> list(stat, n_loci), nw x ngroups each: stat is NA_real_ where the reference assigns NA (a pad window, n_loci <
+ * min_loci) and the arithmetic value elsewhere, a NaN included; n_loci is NA_integer_ on a pad window. */
+SEXP _tidypopgen_tpg_windows_pop_tajimas_d(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP lo, SEXP hi,
+                                           SEXP pad_na, SEXP min_loci) {
+  TPG_NEEDS(tpg_windows_pop_tajimas_d);
+  const int G = ngroups_of(ngroups);
+  if ((TYPEOF(lo) != INTSXP && TYPEOF(lo) != REALSXP) || (TYPEOF(hi) != INTSXP && TYPEOF(hi) != REALSXP))
+    Rf_error("tidypopgen (GPU): lo and hi must be integer or double vectors");
+  const int ml = Rf_asInteger(min_loci);
+  if (ml == NA_INTEGER || ml < 1) Rf_error("min_loci must be positive."); /* R/windows_stats_generic.R:101-103 */
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP gid = PROTECT(tajima_groups(groupIds, ri, G));
+  SEXP lr = PROTECT(as_real(lo)), hr = PROTECT(as_real(hi));
+  SEXP pr = PROTECT(pad_na == R_NilValue ? R_NilValue : Rf_coerceVector(pad_na, LGLSXP));
+  const R_xlen_t nw = XLENGTH(lr);
+  if (XLENGTH(hr) != nw || (pr != R_NilValue && XLENGTH(pr) != nw)) Rf_error("tidypopgen (GPU): lo, hi and pad_na differ in length");
+  if (nw > INT_MAX) Rf_error("tidypopgen (GPU): too many windows for an R matrix");
+  SEXP mats[2];
+  mats[0] = PROTECT(Rf_allocMatrix(REALSXP, (int)nw, G));
+  mats[1] = PROTECT(Rf_allocMatrix(INTSXP, (int)nw, G));
+  static const char* names[2] = {"stat", "n_loci"};
+  SEXP out = PROTECT(named_list(2, names, mats));
+  int64_t* w64 = (int64_t*)R_alloc((size_t)(nw > 0 ? 2 * nw : 1), sizeof(int64_t));
+  uint8_t* p8 = (uint8_t*)R_alloc((size_t)(nw > 0 ? nw : 1), 1);
+  const double m = (double)XLENGTH(ci);
+  for (R_xlen_t w = 0; w < nw; w++) {
+    const double a = REAL(lr)[w], b = REAL(hr)[w];
+    if (!(a >= 0 && a <= b && b <= m) || a != floor(a) || b != floor(b))
+      Rf_error("tidypopgen (GPU): window %lld is NA, not whole numbers or outside [0, %.0f]", (long long)w + 1, m);
+    w64[w] = (int64_t)a;
+    w64[nw + w] = (int64_t)b;
+    p8[w] = 0;
+    if (pr != R_NilValue) {
+      if (LOGICAL(pr)[w] == NA_LOGICAL) Rf_error("tidypopgen (GPU): NA in pad_na");
+      p8[w] = LOGICAL(pr)[w] != 0;
+    }
+  }
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_windows_pop_tajimas_d(ctx(), v, gid == R_NilValue ? NULL : INTEGER(gid), G, NULL, w64, w64 + nw, p8,
+                                          (int64_t)nw, ml, REAL(mats[0]), NULL, NULL, (int32_t*)INTEGER(mats[1])));
+  double* stat = REAL(mats[0]);
+  int* nl = INTEGER(mats[1]);
+  for (R_xlen_t k = 0; k < nw * (R_xlen_t)G; k++) {
+    if (nl[k] < 0 || nl[k] < ml) stat[k] = NA_REAL; /* results$stat[results$n_loci < min_loci] <- NA, and runner's na_pad */
+    if (nl[k] < 0) nl[k] = NA_INTEGER;
+  }
+  UNPROTECT(9);
+  return out;
+}
+
 /* ---- registration ------------------------------------------------------------------------------------------------
  * Same names and arities as the reference's table (src/RcppExports.cpp:348-371).  These rows replace the rows of the
  * same name there, and so do the three HWE rows of tpg_rshim_entries_hwe[] below; the other rows of that table
@@ -1146,22 +1231,30 @@ const R_CallMethodDef tpg_rshim_entries_roh[] = {
     {"_tidypopgen_tpg_indiv_roh", (DL_FUNC)&_tidypopgen_tpg_indiv_roh, 6},
     {NULL, NULL, 0}};
 
+/* Tajima's D, in a table of its own: the reference computes it in R on top of gt_grouped_pi_diploid, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_tajima[] = {
+    {"_tidypopgen_tpg_pop_tajimas_d", (DL_FUNC)&_tidypopgen_tpg_pop_tajimas_d, 5},
+    {"_tidypopgen_tpg_windows_pop_tajimas_d", (DL_FUNC)&_tidypopgen_tpg_windows_pop_tajimas_d, 9},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the five tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the six tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
                              sizeof(tpg_rshim_entries_ld) / sizeof(tpg_rshim_entries_ld[0]) +
-                             sizeof(tpg_rshim_entries_roh) / sizeof(tpg_rshim_entries_roh[0])];
+                             sizeof(tpg_rshim_entries_roh) / sizeof(tpg_rshim_entries_roh[0]) +
+                             sizeof(tpg_rshim_entries_tajima) / sizeof(tpg_rshim_entries_tajima[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_hwe; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_ld; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_roh; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_tajima; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

@@ -121,6 +121,22 @@ tpg_indiv_roh <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigst
                       as.integer(factor(chromosome, levels = unique(chromosome))), as.numeric(position), as.numeric(params)))
 }
 
+# Tajima's D per group in one call (the big_apply and the loop over groups of R/pop_tajimas_d.R:113-147; include/tpg.h
+# "Tajima's D" is the definition).  group_ids0 = dplyr::group_indices(.x) - 1, or NULL for one group of everybody.
+tpg_pop_tajimas_d <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), group_ids0 = NULL,
+                              n_groups = 1L) {
+  .Call(`_tidypopgen_tpg_pop_tajimas_d`, X, as.integer(ind.row), as.integer(ind.col), group_ids0, as.integer(n_groups))
+}
+
+# Tajima's D per window and group in one call (loci_pi and the runner call per group of R/windows_pop_tajimas_d.R:80-103).
+# lo / hi: 0-based half-open ranges of positions in ind.col, one per window; pad_na: the windows runner pads under complete =
+# TRUE (NULL: none).  Returns list(stat, n_loci), windows x groups each.
+tpg_windows_pop_tajimas_d <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),
+                                      group_ids0 = NULL, n_groups = 1L, lo, hi, pad_na = NULL, min_loci = 1L) {
+  .Call(`_tidypopgen_tpg_windows_pop_tajimas_d`, X, as.integer(ind.row), as.integer(ind.col), group_ids0,
+        as.integer(n_groups), lo, hi, pad_na, as.integer(min_loci))
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

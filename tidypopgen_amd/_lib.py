@@ -103,6 +103,7 @@ SYMBOLS = [
     "tpg_ld_band_links", "tpg_ld_clump",
     "tpg_roh_chunk_loci", "tpg_roh_snp_status", "tpg_roh_detect", "tpg_roh_count", "tpg_roh_fetch", "tpg_roh_indiv_summary",
     "tpg_roh_locus_counts", "tpg_roh_free",
+    "tpg_tajimas_d_from_sums", "tpg_tajima_chunk_loci", "tpg_pop_tajimas_d", "tpg_windows_pop_tajimas_d",
 ]
 
 
@@ -188,6 +189,12 @@ if hasattr(lib, "tpg_roh_detect"):
     lib.tpg_roh_locus_counts.argtypes = [vp, vp, vp]
     lib.tpg_roh_free.restype = None
     lib.tpg_roh_free.argtypes = [vp]
+if hasattr(lib, "tpg_pop_tajimas_d"):
+    lib.tpg_tajimas_d_from_sums.argtypes = [C.c_int64, C.c_int64, C.c_double, c_f64p]
+    lib.tpg_tajima_chunk_loci.restype = C.c_int64
+    lib.tpg_tajima_chunk_loci.argtypes = []
+    lib.tpg_pop_tajimas_d.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.tpg_windows_pop_tajimas_d.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

@@ -1355,7 +1355,8 @@ def windows_stats_generic(x, chromosome, position=None, operator="mean", window_
                           size_unit="snp", min_loci=1, complete=False, ctx: Optional[Context] = None):
     """R/windows_stats_generic.R:47-184 for operator "mean" / "sum" -> dict(chromosome, start, end, stat, n_loci)"""
     if operator not in ("mean", "sum"):
-        raise ValueError("'arg' should be one of 'mean', 'sum' (custom functions run on the host in the reference)")
+        raise ValueError("'arg' should be one of 'mean', 'sum' (a custom function runs on the host in the reference; its one use, "
+                         "Tajima's D, is windows_pop_tajimas_d)")
     x = np.ascontiguousarray(x, dtype=np.float64)
     if len(chromosome) != len(x):
         raise ValueError("loci_table must have the same number of rows as x.")
@@ -1401,6 +1402,85 @@ def windows_pairwise_pop_fst(X: FBM, ind_row, ind_col, groupIds, ngroups: int, c
     with np.errstate(invalid="ignore", divide="ignore"):
         fst = num / den
     return dict(chromosome=wr["chromosome"], start=wr["start"], end=wr["end"], fst=fst)
+
+
+# include/tpg.h "Tajima's D": loci per partial sum of pop_tajimas_d (results do not depend on it)
+TAJIMA_CHUNK_LOCI = int(lib.tpg_tajima_chunk_loci()) if hasattr(lib, "tpg_tajima_chunk_loci") else 0
+
+
+def tajimas_d_from_sums(n_alleles: int, seg: int, k_hat: float) -> float:
+    """R/pop_tajimas_d.R:151-166 from its additive pieces (tpg_tajimas_d_from_sums; host arithmetic, no device): seg and
+    k_hat of shards or blocks of loci add up, D of the sums is D of the whole."""
+    d = C.c_double()
+    check(lib.tpg_tajimas_d_from_sums(C.c_int64(int(n_alleles)), C.c_int64(int(seg)), C.c_double(float(k_hat)), C.byref(d)))
+    return d.value
+
+
+def _tajima_groups(v: View, groupIds, ngroups):
+    if groupIds is None:
+        return None, 1
+    gid = _i32(groupIds)
+    if len(gid) != v.n:
+        raise ValueError("groupIds must have one entry per individual of ind_row")
+    return gid, int(ngroups)
+
+
+def pop_tajimas_d(X: FBM, ind_row=None, ind_col=None, groupIds=None, ngroups: int = 0, ploidy=None, return_sums: bool = False):
+    """R/pop_tajimas_d.R:51-148 (include/tpg.h "Tajima's D"): ungrouped (groupIds=None) a float, NaN where the reference gives
+    NA (a single individual: no device call); grouped an array of ngroups values.  return_sums: dict(tajimas_d, seg, k_hat)."""
+    n = X.nrow if ind_row is None else len(ind_row)
+    if groupIds is None and n <= 1:  # R/pop_tajimas_d.R:91-95
+        if ploidy is not None and np.any(_f64(ploidy) != 2.0):
+            raise _lib.TpgError(1, "Tajima's D only works on diploid data")  # TPG_EINVAL, as the library answers
+        return dict(tajimas_d=np.nan, seg=0, k_hat=np.nan) if return_sums else np.nan
+    v = View(X, ind_row, ind_col)
+    gid, G = _tajima_groups(v, groupIds, ngroups)
+    pl = _f64(ploidy)
+    d, seg, k = np.zeros(G), np.zeros(G, dtype=np.int64), np.zeros(G)
+    check(lib.tpg_pop_tajimas_d(v.ctx.h, v.h, _ptr(gid), C.c_int(G), _ptr(pl), _ptr(d), _ptr(seg), _ptr(k)))
+    if groupIds is None:
+        return dict(tajimas_d=float(d[0]), seg=int(seg[0]), k_hat=float(k[0])) if return_sums else float(d[0])
+    return dict(tajimas_d=d, seg=seg, k_hat=k) if return_sums else d
+
+
+def tajima_windows(v: View, groupIds, ngroups, lo, hi, pad_na=None, min_loci: int = 1, ploidy=None) -> dict:
+    """tpg_windows_pop_tajimas_d on explicit 0-based half-open locus ranges -> dict(tajimas_d, seg, k_hat, n_loci), each
+    (nw, G); n_loci is int32 with -1 on a pad_na window"""
+    gid, G = _tajima_groups(v, groupIds, ngroups)
+    lo, hi = np.ascontiguousarray(lo, dtype=np.int64), np.ascontiguousarray(hi, dtype=np.int64)
+    pad = None if pad_na is None else np.ascontiguousarray(pad_na, dtype=np.uint8)
+    nw = len(lo)
+    if len(hi) != nw or (pad is not None and len(pad) != nw):
+        raise ValueError("lo, hi and pad_na must have one entry per window")
+    pl = _f64(ploidy)
+    d, k = np.zeros((nw, G), order="F"), np.zeros((nw, G), order="F")
+    seg, nl = np.zeros((nw, G), dtype=np.int64, order="F"), np.zeros((nw, G), dtype=np.int32, order="F")
+    check(lib.tpg_windows_pop_tajimas_d(v.ctx.h, v.h, _ptr(gid), C.c_int(G), _ptr(pl), _ptr(lo), _ptr(hi), _ptr(pad),
+                                        C.c_int64(nw), C.c_int(int(min_loci)), _ptr(d), _ptr(seg), _ptr(k), _ptr(nl)))
+    return dict(tajimas_d=d, seg=seg, k_hat=k, n_loci=nl)
+
+
+def windows_pop_tajimas_d(X: FBM, ind_row, ind_col, groupIds, ngroups: int, chromosome, position=None, ploidy=None,
+                          window_size=None, step_size=None, size_unit="snp", min_loci=1, complete=False,
+                          return_sums: bool = False):
+    """R/windows_pop_tajimas_d.R:58-122 (type = "matrix"): the reference's runner call with a custom function per window and
+    group, as one segmented reduction behind the count sweep; pi (m x G) stays in HBM.  groupIds=None: one group.
+    -> dict(chromosome, start, end, n_loci (nw, G; NaN on a pad window), tajimas_d (nw, G)); return_sums adds seg, k_hat."""
+    v = View(X, ind_row, ind_col)
+    if len(chromosome) != v.m:
+        raise ValueError("loci_table must have the same number of rows as x.")
+    wr = window_index_ranges(chromosome, position, window_size, step_size, size_unit, complete)
+    if min_loci <= 0:
+        raise ValueError("min_loci must be positive.")
+    if min_loci > window_size:
+        raise ValueError("min_loci must be less than window_size.")
+    r = tajima_windows(v, groupIds, ngroups, wr["lo"], wr["hi"], wr["pad_na"], min_loci, ploidy)
+    n_loci = r["n_loci"].astype(float)
+    n_loci[r["n_loci"] < 0] = np.nan
+    out = dict(chromosome=wr["chromosome"], start=wr["start"], end=wr["end"], n_loci=n_loci, tajimas_d=r["tajimas_d"])
+    if return_sums:
+        out.update(seg=r["seg"], k_hat=r["k_hat"])
+    return out
 
 
 def _pbs_triplets(ngroups):
