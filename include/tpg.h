@@ -336,6 +336,73 @@ int tpg_windows_pop_tajimas_d(tpg_ctx* ctx, const tpg_view* v, const int32_t* gr
                               const int64_t* lo, const int64_t* hi, const uint8_t* pad_na, int64_t nw, int min_loci, double* d,
                               int64_t* seg, double* k_hat, int32_t* n_loci);
 
+/* ---- f2 blocks (gt_extract_f2, R/gt_extract_f2.R: gt_to_aftable + admixtools::afs_to_f2_blocks; admixtools is not part of
+ * the reference's sources, so the arithmetic is defined HERE; "(recalled)" marks what follows admixtools from memory) -------
+ * A view of N individuals in G groups; ploidy NULL = all 2, 1 = pseudohaploid as tpg_grouped_alt_freq_dip_pseudo treats it.
+ * Per locus j and group g, formed exactly as tpg_grouped_alt_freq_dip_pseudo forms them:
+ *   c(j,g) = valid alleles, p(j,g) = alt alleles / c.
+ *   t(j,g) = [c > 0] ("typed").
+ *   e(j,g) = p (1 - p) / max(1, c - 1) if apply_corr, else 0; evaluated as (p * (1 - p)) / max(1, c - 1) in IEEE double, no FMA
+ *            contraction (recalled: pmax(1, counts - 1); NOT the n - 1 of the Hudson numerator of tpg_pairwise_pop_fst).
+ * Locus filters, evaluated on the device from the G values of the locus (discard_from_aftable, recalled):
+ *   maxmiss: drop the locus if (double)#{g : !t} / (double)G > maxmiss.
+ *   minmaf / maxmaf: f = (sum of p over the typed groups, added in ascending g) / #typed; maf = min(f, 1 - f); drop the locus
+ *            if maf < minmaf or maf > maxmaf.  A locus with no typed group is dropped.
+ *   minac2 in {0, 1}: with 1, drop the locus if any group has c < 2.  (admixtools' experimental minac2 = 2: TPG_EINVAL.)
+ *   keep:    uint8[m], host or device memory, may be NULL: the caller's own mask (0 drops the locus).  Transitions,
+ *            transversions and outpop are filters on the locus table and stay with the caller.
+ *   poly(j) = the p of the typed groups are not all equal (cpp_is_polymorphic, recalled).
+ *   poly_only: bit 0 (TPG_F2_POLY_F2, default on) applies poly to f2 and cnt, bit 1 (TPG_F2_POLY_AP) to ap and ap_cnt.
+ * Blocks: block b covers the loci lo[b] .. hi[b]-1, the contract of tpg_window_stats: a block may be empty, blocks need not be
+ *   disjoint; lo > hi or a block outside [0, m]: TPG_EINVAL; nb == 0: TPG_OK, nothing written.
+ * Outputs: G x G x nb each, column-major with g1 fastest; any may be NULL; host or device memory.
+ *   cnt    (int32)  #{j in b : kept for f2, t(j,g1), t(j,g2)}
+ *   f2     (double) (1 / cnt) sum over those loci of [(p1 - p2)^2 - e1 - e2]; NaN where cnt = 0; for g1 == g2 exactly +0.0
+ *                   where cnt > 0 (so that an f4 with a repeated population reduces to f3)
+ *   ap_cnt, ap      the same for p1 p2 over the loci kept for ap; the diagonal of ap is the mean of p^2
+ *   n_kept (int64[nb]) loci of the block that passed the filters, before poly
+ *   A group nobody belongs to has cnt 0 and NaN in its row and column.
+ * The sums are formed as masked matrix products over the block's loci, so a value is within
+ *   (4 L + 16) 2^-52 (absolute, L = hi - lo) of the exact rational value of the definition; cnt, ap_cnt and n_kept are exact.
+ * Determinism: a cell depends on (lo, hi, g1, g2) and the filter arguments alone -- not on nb, on the block's place in the
+ *   list or on launch geometry -- and two calls give the same bits; f2 and ap are symmetric bit for bit.  No atomics.
+ * Limits: ngroups > TPG_F2_MAX_GROUPS or nb > TPG_F2_MAX_BLOCKS: TPG_EINVAL (split the list). */
+#define TPG_F2_POLY_F2 1
+#define TPG_F2_POLY_AP 2
+#define TPG_F2_MAX_GROUPS 4096
+#define TPG_F2_MAX_BLOCKS 16777215
+typedef struct tpg_f2_params {
+  double maxmiss;       /* 0 */
+  double minmaf;        /* 0 */
+  double maxmaf;        /* 0.5 */
+  int32_t minac2;       /* 0 */
+  int32_t poly_only;    /* TPG_F2_POLY_F2 */
+  int32_t apply_corr;   /* 1 */
+  const uint8_t* keep;  /* NULL */
+} tpg_f2_params;
+/* the reference's defaults (the comments above) */
+int tpg_f2_params_default(tpg_f2_params* p);
+/* loci a workgroup stages at a time, in ascending order from lo[b] (results do not depend on it; the tests put block lengths
+ * around it) */
+#define TPG_F2_CHUNK_LOCI 16
+int64_t tpg_f2_chunk_loci(void);
+/* groupIds0 == NULL: one group of everybody; params == NULL: the defaults.  Nothing proportional to m leaves the device. */
+int tpg_f2_blocks(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, const double* ploidy,
+                  const tpg_f2_params* params, const int64_t* lo, const int64_t* hi, int64_t nb, double* f2, int32_t* cnt,
+                  double* ap, int32_t* ap_cnt, int64_t* n_kept);
+/* host only, no context, no GPU: f4 (and f3) with the weighted delete-one block jackknife of Busing et al. 1999 (recalled:
+ * what admixtools uses) from f2 (G x G x nb as above, host memory) and block_len[nb] (n_kept).  quads0 = 4 nq 0-based group
+ * indices (A, B, C, D) per quadruple; f3(C; A, B) is the quadruple (C, A, C, B).  For one quadruple:
+ *   theta_b = 0.5 * (f2[A,D,b] + f2[B,C,b] - f2[A,C,b] - f2[B,D,b])      (added in this order)
+ *   blocks with theta_b NaN or block_len[b] <= 0 are left out; n_used = g = the blocks used; n_b = (double)block_len[b]
+ *   n = sum n_b;  theta = (sum n_b theta_b) / n;  theta_(-b) = (n theta - n_b theta_b) / (n - n_b);  h_b = n / n_b
+ *   est = g theta - sum (1 - n_b / n) theta_(-b)
+ *   tau_b = h_b theta - (h_b - 1) theta_(-b);  se = sqrt((1 / g) sum ((tau_b - est)^2 / (h_b - 1)))
+ * every sum in ascending b, in plain double, in the order written, no FMA contraction.  g < 2: est = theta (NaN if g = 0),
+ * se = NaN.  est, se (double[nq]) and n_used (int32[nq]) may each be NULL.  An index outside [0, G): TPG_EINVAL. */
+int tpg_f4_jackknife(const double* f2, int G, int64_t nb, const int64_t* block_len, const int32_t* quads0, int64_t nq,
+                     double* est, double* se, int32_t* n_used);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

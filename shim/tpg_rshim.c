@@ -1175,6 +1175,86 @@ SEXP _tidypopgen_tpg_windows_pop_tajimas_d(SEXP BM, SEXP rowInd, SEXP colInd, SE
   return out;
 }
 
+/* ---- f2 blocks ---------------------------------------------------------------------------------------------------- */
+
+#pragma weak tpg_f2_blocks
+#pragma weak tpg_f2_params_default
+
+static SEXP f2_array(SEXPTYPE type, int G, R_xlen_t nb) { /* G x G x nb, returned UNPROTECTED (the caller protects it at once) */
+  SEXP a = PROTECT(Rf_allocVector(type, (R_xlen_t)G * G * nb));
+  SEXP d = PROTECT(Rf_allocVector(INTSXP, 3));
+  INTEGER(d)[0] = G;
+  INTEGER(d)[1] = G;
+  INTEGER(d)[2] = (int)nb;
+  Rf_setAttrib(a, R_DimSymbol, d);
+  UNPROTECT(2);
+  return a;
+}
+
+/* tpg_f2_blocks(BM, rowInd, colInd, groupIds, ngroups, ploidy, lo, hi, params): gt_to_aftable, discard_from_aftable and
+ * afs_to_f2_blocks of R/gt_extract_f2.R:141-189 in one call (include/tpg.h "f2 blocks").  ploidy = NULL: all diploid.  lo / hi =
+ * 0-based half-open locus ranges (positions in colInd), integer or double.  params = c(maxmiss, minmaf, maxmaf, minac2,
+ * poly_only, apply_corr), optionally followed by the keep mask of the loci (one 0 / 1 per entry of colInd).
+ * -> list(f2, counts, ap, ap_counts: G x G x nb arrays; block_lengths: double[nb]).  NaN where a pair has no locus. */
+SEXP _tidypopgen_tpg_f2_blocks(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP ploidy, SEXP lo, SEXP hi,
+                               SEXP params) {
+  TPG_NEEDS(tpg_f2_blocks);
+  const int G = ngroups_of(ngroups);
+  if ((TYPEOF(lo) != INTSXP && TYPEOF(lo) != REALSXP) || (TYPEOF(hi) != INTSXP && TYPEOF(hi) != REALSXP) ||
+      (TYPEOF(params) != INTSXP && TYPEOF(params) != REALSXP && TYPEOF(params) != LGLSXP))
+    Rf_error("tidypopgen (GPU): lo, hi and params must be integer or double vectors");
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP gid = PROTECT(tajima_groups(groupIds, ri, G));
+  SEXP pl = PROTECT(ploidy == R_NilValue ? R_NilValue : Rf_coerceVector(ploidy, REALSXP));
+  SEXP lr = PROTECT(as_real(lo)), hr = PROTECT(as_real(hi)), pr = PROTECT(as_real(params));
+  const R_xlen_t nb = XLENGTH(lr), m = XLENGTH(ci);
+  if (XLENGTH(hr) != nb) Rf_error("tidypopgen (GPU): lo and hi differ in length");
+  if (pl != R_NilValue && XLENGTH(pl) != XLENGTH(ri)) Rf_error("tidypopgen (GPU): ploidy and rowInd differ in length");
+  if (XLENGTH(pr) != 6 && XLENGTH(pr) != 6 + m)
+    Rf_error("tidypopgen (GPU): params must be the 6 numbers of tpg_f2_params, alone or followed by one keep flag per locus");
+  if ((double)G * G * (double)nb > 2147483647.0) Rf_error("tidypopgen (GPU): too many blocks for an R integer array");
+  const double* q = REAL(pr);
+  for (R_xlen_t k = 0; k < XLENGTH(pr); k++)
+    if (ISNAN(q[k])) Rf_error("tidypopgen (GPU): NA in params[%lld]", (long long)k + 1);
+  tpg_f2_params P;
+  tpg_f2_params_default(&P);
+  P.maxmiss = q[0];
+  P.minmaf = q[1];
+  P.maxmaf = q[2];
+  P.minac2 = roh_int_param(q, 3, 0, 1, "minac2");
+  P.poly_only = roh_int_param(q, 4, 0, 3, "poly_only");
+  P.apply_corr = q[5] != 0;
+  uint8_t* keep = NULL;
+  if (XLENGTH(pr) > 6) {
+    keep = (uint8_t*)R_alloc((size_t)(m > 0 ? m : 1), 1);
+    for (R_xlen_t j = 0; j < m; j++) keep[j] = q[6 + j] != 0;
+  }
+  P.keep = keep;
+  int64_t* b64 = (int64_t*)R_alloc((size_t)(nb > 0 ? 3 * nb : 1), sizeof(int64_t));
+  for (R_xlen_t b = 0; b < nb; b++) {
+    const double x = REAL(lr)[b], y = REAL(hr)[b];
+    if (!(x >= 0 && x <= y && y <= (double)m) || x != floor(x) || y != floor(y))
+      Rf_error("tidypopgen (GPU): block %lld is NA, not whole numbers or outside [0, %.0f]", (long long)b + 1, (double)m);
+    b64[b] = (int64_t)x;
+    b64[nb + b] = (int64_t)y;
+  }
+  SEXP vals[5];
+  vals[0] = PROTECT(f2_array(REALSXP, G, nb));
+  vals[1] = PROTECT(f2_array(INTSXP, G, nb));
+  vals[2] = PROTECT(f2_array(REALSXP, G, nb));
+  vals[3] = PROTECT(f2_array(INTSXP, G, nb));
+  vals[4] = PROTECT(Rf_allocVector(REALSXP, nb));
+  static const char* names[5] = {"f2", "counts", "ap", "ap_counts", "block_lengths"};
+  SEXP out = PROTECT(named_list(5, names, vals));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_f2_blocks(ctx(), v, gid == R_NilValue ? NULL : INTEGER(gid), G, pl == R_NilValue ? NULL : REAL(pl), &P, b64,
+                              b64 + nb, (int64_t)nb, REAL(vals[0]), (int32_t*)INTEGER(vals[1]), REAL(vals[2]),
+                              (int32_t*)INTEGER(vals[3]), b64 + 2 * nb));
+  for (R_xlen_t b = 0; b < nb; b++) REAL(vals[4])[b] = (double)b64[2 * nb + b];
+  UNPROTECT(13);
+  return out;
+}
+
 /* ---- registration ------------------------------------------------------------------------------------------------
  * Same names and arities as the reference's table (src/RcppExports.cpp:348-371).  These rows replace the rows of the
  * same name there, and so do the three HWE rows of tpg_rshim_entries_hwe[] below; the other rows of that table
@@ -1237,17 +1317,23 @@ const R_CallMethodDef tpg_rshim_entries_tajima[] = {
     {"_tidypopgen_tpg_windows_pop_tajimas_d", (DL_FUNC)&_tidypopgen_tpg_windows_pop_tajimas_d, 9},
     {NULL, NULL, 0}};
 
+/* Blocked f2, in a table of its own: the reference hands the allele-frequency table to admixtools, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_f2[] = {
+    {"_tidypopgen_tpg_f2_blocks", (DL_FUNC)&_tidypopgen_tpg_f2_blocks, 9},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the six tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the seven tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
                              sizeof(tpg_rshim_entries_ld) / sizeof(tpg_rshim_entries_ld[0]) +
                              sizeof(tpg_rshim_entries_roh) / sizeof(tpg_rshim_entries_roh[0]) +
-                             sizeof(tpg_rshim_entries_tajima) / sizeof(tpg_rshim_entries_tajima[0])];
+                             sizeof(tpg_rshim_entries_tajima) / sizeof(tpg_rshim_entries_tajima[0]) +
+                             sizeof(tpg_rshim_entries_f2) / sizeof(tpg_rshim_entries_f2[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1255,6 +1341,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_ld; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_roh; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_tajima; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_f2; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

@@ -137,6 +137,24 @@ tpg_windows_pop_tajimas_d <- function(X, ind.row = bigstatsr::rows_along(X), ind
         as.integer(n_groups), lo, hi, pad_na, as.integer(min_loci))
 }
 
+# Blocked f2 and allele-frequency products in one call (gt_to_aftable, admixtools' discard_from_aftable and afs_to_f2_blocks of
+# R/gt_extract_f2.R:141-189; include/tpg.h "f2 blocks" is the definition).  lo / hi: 0-based half-open ranges of positions in
+# ind.col, one per jackknife block; ploidy = NULL: all diploid; keep: NULL or one logical per locus (transitions, transversions
+# and outpop are filters on the locus table: fold them into keep).  Returns list(f2, counts, ap, ap_counts: groups x groups x
+# blocks; block_lengths).
+tpg_f2_blocks <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), group_ids0 = NULL,
+                          n_groups = 1L, ploidy = NULL, lo, hi, maxmiss = 0, minmaf = 0, maxmaf = 0.5, minac2 = FALSE,
+                          poly_only = c("f2"), apply_corr = TRUE, keep = NULL) {
+  if (isTRUE(poly_only)) poly_only <- c("f2", "ap")
+  if (isFALSE(poly_only)) poly_only <- character(0)
+  if (!all(poly_only %in% c("f2", "ap"))) stop("poly_only: only 'f2' and 'ap' are supported")
+  if (!(isTRUE(minac2) || isFALSE(minac2))) stop("minac2 must be TRUE or FALSE (admixtools' minac2 = 2 is not supported)")
+  params <- c(maxmiss, minmaf, maxmaf, as.numeric(minac2), sum(c(f2 = 1, ap = 2)[unique(poly_only)]), as.numeric(apply_corr),
+              if (is.null(keep)) numeric(0) else as.numeric(as.logical(keep)))
+  .Call(`_tidypopgen_tpg_f2_blocks`, X, as.integer(ind.row), as.integer(ind.col), group_ids0, as.integer(n_groups), ploidy,
+        lo, hi, params)
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

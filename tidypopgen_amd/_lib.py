@@ -104,6 +104,7 @@ SYMBOLS = [
     "tpg_roh_chunk_loci", "tpg_roh_snp_status", "tpg_roh_detect", "tpg_roh_count", "tpg_roh_fetch", "tpg_roh_indiv_summary",
     "tpg_roh_locus_counts", "tpg_roh_free",
     "tpg_tajimas_d_from_sums", "tpg_tajima_chunk_loci", "tpg_pop_tajimas_d", "tpg_windows_pop_tajimas_d",
+    "tpg_f2_params_default", "tpg_f2_chunk_loci", "tpg_f2_blocks", "tpg_f4_jackknife",
 ]
 
 
@@ -154,6 +155,12 @@ class RohParams(C.Structure):
                 ("max_miss_run", C.c_int32)]
 
 
+class F2Params(C.Structure):
+    """tpg_f2_params of include/tpg.h, field for field"""
+    _fields_ = [("maxmiss", C.c_double), ("minmaf", C.c_double), ("maxmaf", C.c_double), ("minac2", C.c_int32),
+                ("poly_only", C.c_int32), ("apply_corr", C.c_int32), ("keep", vp)]
+
+
 class StreamReport(C.Structure):
     """tpg_stream_report of include/tpg.h"""
     _fields_ = [
@@ -195,6 +202,12 @@ if hasattr(lib, "tpg_pop_tajimas_d"):
     lib.tpg_tajima_chunk_loci.argtypes = []
     lib.tpg_pop_tajimas_d.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.tpg_windows_pop_tajimas_d.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
+if hasattr(lib, "tpg_f2_blocks"):
+    lib.tpg_f2_params_default.argtypes = [C.POINTER(F2Params)]
+    lib.tpg_f2_chunk_loci.restype = C.c_int64
+    lib.tpg_f2_chunk_loci.argtypes = []
+    lib.tpg_f2_blocks.argtypes = [vp, vp, vp, C.c_int, vp, C.POINTER(F2Params), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.tpg_f4_jackknife.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

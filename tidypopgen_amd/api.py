@@ -1483,6 +1483,167 @@ def windows_pop_tajimas_d(X: FBM, ind_row, ind_col, groupIds, ngroups: int, chro
     return out
 
 
+# include/tpg.h "f2 blocks": loci a workgroup stages at a time (results do not depend on it)
+F2_CHUNK_LOCI = int(lib.tpg_f2_chunk_loci()) if hasattr(lib, "tpg_f2_chunk_loci") else 0
+F2_POLY = {"f2": 1, "ap": 2}  # TPG_F2_POLY_F2, TPG_F2_POLY_AP
+
+
+def f2_block_ranges(chromosome, dist, blgsize=0.05):
+    """Jackknife blocks of admixtools (get_block_lengths, recalled) as 0-based half-open locus ranges (lo, hi): locus j starts a
+    new block when its chromosome differs from the previous locus's or when dist[j] - dist[first locus of the block] >= blgsize.
+    dist is the genetic distance in Morgans, or positions in bp when blgsize >= 100.  dist must not decrease within a
+    chromosome and a chromosome must not reappear: ValueError."""
+    chrom = np.asarray(chromosome)
+    d = np.asarray(dist, dtype=np.float64)
+    if chrom.ndim != 1 or d.shape != chrom.shape:
+        raise ValueError("chromosome and dist must be vectors of one length")
+    if not blgsize > 0:
+        raise ValueError("blgsize must be positive")
+    if np.isnan(d).any():
+        raise ValueError("dist has missing values")
+    m = len(chrom)
+    if m == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    new_chrom = np.r_[True, chrom[1:] != chrom[:-1]]
+    starts_c = np.flatnonzero(new_chrom)
+    labels = chrom[starts_c].tolist()
+    if len(set(labels)) != len(labels):
+        raise ValueError("a chromosome reappears: the loci must be sorted by chromosome")
+    if np.any((np.diff(d) < 0) & ~new_chrom[1:]):
+        raise ValueError("dist must be sorted within each chromosome")
+    lo = []
+    for a, b in zip(starts_c, np.r_[starts_c[1:], m]):
+        j = int(a)
+        while j < b:  # one binary search per block
+            lo.append(j)
+            j += int(np.searchsorted(d[j:b] - d[j] >= blgsize, True))
+    lo = np.asarray(lo, dtype=np.int64)
+    return lo, np.r_[lo[1:], m].astype(np.int64)
+
+
+def _f2_params(maxmiss, minmaf, maxmaf, minac2, poly_only, apply_corr, keep, m):
+    if minac2 not in (0, 1, False, True):
+        raise ValueError("minac2 must be FALSE / TRUE (0 / 1): admixtools' experimental minac2 = 2 is not supported")
+    if isinstance(poly_only, (bool, np.bool_)):
+        bits = 3 if poly_only else 0
+    elif isinstance(poly_only, (int, np.integer)):
+        bits = int(poly_only)
+    else:
+        names = [poly_only] if isinstance(poly_only, str) else list(poly_only)
+        bad = [s for s in names if s not in F2_POLY]
+        if bad:
+            raise ValueError(f"poly_only: {bad} not supported (only 'f2' and 'ap'; fst is out of scope)")
+        bits = sum({F2_POLY[s] for s in names})
+    if not 0 <= bits <= 3:
+        raise ValueError("poly_only out of range")
+    pr = _lib.F2Params()
+    check(lib.tpg_f2_params_default(C.byref(pr)))
+    pr.maxmiss, pr.minmaf, pr.maxmaf = float(maxmiss), float(minmaf), float(maxmaf)
+    pr.minac2, pr.poly_only, pr.apply_corr = int(minac2), bits, int(bool(apply_corr))
+    keep_arr = None
+    if keep is not None and not isinstance(keep, (int, np.integer)):
+        keep_arr = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if keep_arr.shape != (m,):
+            raise ValueError("keep must have one entry per locus of the view")
+        pr.keep = keep_arr.ctypes.data
+    elif keep is not None:
+        pr.keep = int(keep)  # a device pointer
+    return pr, keep_arr
+
+
+def f2_blocks(v: View, groupIds, ngroups, lo, hi, ploidy=None, maxmiss=0.0, minmaf=0.0, maxmaf=0.5, minac2=False,
+              poly_only=("f2",), apply_corr=True, keep=None, afprod=True, on_device=False) -> dict:
+    """tpg_f2_blocks (include/tpg.h "f2 blocks") on explicit 0-based half-open locus ranges -> dict(f2, counts, ap, ap_counts:
+    (G, G, nb) each, ap / ap_counts only with afprod; block_lengths: int64[nb], the kept loci).  groupIds=None: one group.
+    on_device=True: the four arrays stay in HBM and come back as raw device pointers (release with v.ctx.dev_free);
+    block_lengths is a host array all the same."""
+    if groupIds is None:
+        gid, G = None, 1
+    else:
+        gid, G = _i32(groupIds), int(ngroups)
+        if len(gid) != v.n:
+            raise ValueError("groupIds must have one entry per individual of ind_row")
+    lo, hi = np.ascontiguousarray(lo, dtype=np.int64), np.ascontiguousarray(hi, dtype=np.int64)
+    nb = len(lo)
+    if lo.ndim != 1 or hi.shape != lo.shape:
+        raise ValueError("lo and hi must have one entry per block")
+    pr, keep_arr = _f2_params(maxmiss, minmaf, maxmaf, minac2, poly_only, apply_corr, keep, v.m)
+    pl = _f64(ploidy)
+    if pl is not None and len(pl) != v.n:
+        raise ValueError("ploidy must have one entry per individual of ind_row")
+    nk = np.zeros(nb, dtype=np.int64)
+    names = ("f2", "counts") + (("ap", "ap_counts") if afprod else ())
+    dtypes = dict(f2=np.float64, counts=np.int32, ap=np.float64, ap_counts=np.int32)
+    cells = max(G, 1) * max(G, 1) * nb
+    out, ptrs = {}, {}
+    try:
+        for k in names:
+            if on_device:
+                out[k] = v.ctx.dev_alloc(max(cells, 1) * np.dtype(dtypes[k]).itemsize)
+                ptrs[k] = out[k]
+            else:
+                out[k] = np.zeros((G, G, nb), dtype=dtypes[k], order="F")
+                ptrs[k] = _ptr(out[k])
+        check(lib.tpg_f2_blocks(v.ctx.h, v.h, _ptr(gid), C.c_int(G), _ptr(pl), C.byref(pr), _ptr(lo), _ptr(hi), C.c_int64(nb),
+                                ptrs["f2"], ptrs["counts"], ptrs.get("ap", C.c_void_p(None)), ptrs.get("ap_counts", C.c_void_p(None)),
+                                _ptr(nk)))
+    except Exception:
+        if on_device:
+            for p in out.values():
+                v.ctx.dev_free(p)
+        raise
+    del keep_arr  # alive until here: pr.keep points into it
+    out["block_lengths"] = nk
+    return out
+
+
+def gt_extract_f2(X: FBM, ind_row, ind_col, groupIds, ngroups: int, chromosome, genetic_dist=None, position=None, blgsize=0.05,
+                  maxmiss=0, minmaf=0, maxmaf=0.5, minac2=False, poly_only=("f2",), apply_corr=True, afprod=True, keep=None,
+                  ploidy=None, **unsupported):
+    """R/gt_extract_f2.R:86-193 without the directory of .rds files: gt_to_aftable, admixtools' discard_from_aftable and
+    afs_to_f2_blocks as one device call; the m x 2G table never leaves HBM.  Blocks come from f2_block_ranges(chromosome,
+    genetic_dist, blgsize), or from position when blgsize >= 100 (bp).  -> dict(f2, counts, ap, ap_counts (G, G, nb),
+    block_lengths, lo, hi).  fst=, outpop / outpop_scale, transitions / transversions (locus-table filters: pass `keep`), outdir
+    and minac2 = 2 are out of scope: an unsupported argument raises."""
+    if unsupported:
+        raise TypeError(f"gt_extract_f2: unsupported argument(s) {sorted(unsupported)}")
+    v = View(X, ind_row, ind_col)
+    if len(chromosome) != v.m:
+        raise ValueError("chromosome must have one entry per locus of ind_col")
+    dist = position if blgsize >= 100 else genetic_dist
+    if dist is None:
+        raise ValueError("blgsize >= 100 is in bp and needs position; smaller values are in Morgans and need genetic_dist")
+    lo, hi = f2_block_ranges(chromosome, dist, blgsize)
+    out = f2_blocks(v, groupIds, ngroups, lo, hi, ploidy, maxmiss, minmaf, maxmaf, minac2, poly_only, apply_corr, keep, afprod)
+    out.update(lo=lo, hi=hi)
+    return out
+
+
+def f4_from_f2_blocks(f2, block_lengths, quads) -> dict:
+    """f4(A, B; C, D) per row of quads (0-based group indices) with the weighted block jackknife (tpg_f4_jackknife: host
+    arithmetic, no device) -> dict(est, se, z = est / se, n_blocks)"""
+    f2 = np.asfortranarray(f2, dtype=np.float64)
+    if f2.ndim != 3 or f2.shape[0] != f2.shape[1]:
+        raise ValueError("f2 must be G x G x n_blocks")
+    G, nb = f2.shape[0], f2.shape[2]
+    bl = np.ascontiguousarray(block_lengths, dtype=np.int64)
+    if bl.shape != (nb,):
+        raise ValueError("block_lengths must have one entry per block")
+    q = np.ascontiguousarray(np.asarray(quads, dtype=np.int32).reshape(-1, 4))
+    nq = len(q)
+    est, se, used = np.zeros(nq), np.zeros(nq), np.zeros(nq, dtype=np.int32)
+    check(lib.tpg_f4_jackknife(_ptr(f2), C.c_int(G), C.c_int64(nb), _ptr(bl), _ptr(q), C.c_int64(nq), _ptr(est), _ptr(se), _ptr(used)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = est / se
+    return dict(est=est, se=se, z=z, n_blocks=used)
+
+
+def f3_from_f2_blocks(f2, block_lengths, triples) -> dict:
+    """f3(C; A, B) per row (C, A, B) of triples: the quadruple (C, A; C, B) of f4_from_f2_blocks (the diagonal of f2 is +0.0)"""
+    t = np.asarray(triples, dtype=np.int32).reshape(-1, 3)
+    return f4_from_f2_blocks(f2, block_lengths, np.stack([t[:, 0], t[:, 1], t[:, 0], t[:, 2]], axis=1))
+
+
 def _pbs_triplets(ngroups):
     """utils::combn(levels, 3) order, with the Fst columns of (p1.p2, p1.p3, p2.p3) in combn(levels, 2) order"""
     pairs = combn2(ngroups)  # (2, P), 1-based
