@@ -539,16 +539,27 @@ static int multi_run(tpg_multi* mg, F fn) {
 
 // This device's share of the view (rowInd, colInd, code256) of a HOST FBM: the contiguous range [j0, j1) of colInd
 // (tpg_shard_loci), only the FBM columns that range touches uploaded, packed.  An empty share (more devices than
-// 128-locus groups) leaves f and v NULL: the device still takes part in the exchanges.
+// 128-locus groups) leaves f and v NULL: the device still takes part in the exchanges.  The shard owns both: they go back
+// inside their own context.
 struct MultiShard {
+  tpg_ctx* ctx = nullptr;
   tpg_fbm* f = nullptr;
   tpg_view* v = nullptr;
   int64_t j0 = 0, j1 = 0;
+  MultiShard() = default;
+  MultiShard(const MultiShard&) = delete;
+  MultiShard& operator=(const MultiShard&) = delete;
+  ~MultiShard() {
+    if (!f && !v) return;
+    TpgEnter _enter(ctx);
+    tpg_view_free(v);
+    tpg_fbm_free(f);
+  }
 };
 
 static int multi_shard_view(tpg_multi* mg, int r, const uint8_t* fbm_bytes, int64_t nrow, const int32_t* rowInd1, int64_t n,
                             const int32_t* colInd1, int64_t m, const double* code256, MultiShard* me) {
-  tpg_ctx* ctx = mg->ctx[(size_t)r];
+  tpg_ctx* ctx = me->ctx = mg->ctx[(size_t)r];
   TPG_TRY(tpg_shard_loci(m, mg->ndev, r, &me->j0, &me->j1));
   const int64_t j0 = me->j0, j1 = me->j1;
   if (j1 <= j0) return TPG_OK;
@@ -568,14 +579,6 @@ static int multi_shard_view(tpg_multi* mg, int r, const uint8_t* fbm_bytes, int6
   const double* table = code256;
   TPG_TRY(tpg_fbm_from_host_for_table(ctx, fbm_bytes + (size_t)c0 * (size_t)nrow, nrow, c1 - c0, code256, &me->f, &table));
   return tpg_view_create(ctx, me->f, rowInd1, n, colInd1 ? cols.data() : nullptr, j1 - j0, table, &me->v);
-}
-
-static void multi_shard_free(tpg_multi* mg, std::vector<MultiShard>& st) {
-  for (int r = 0; r < mg->ndev; r++) {
-    TpgEnter _enter(mg->ctx[(size_t)r]);
-    tpg_view_free(st[(size_t)r].v);
-    tpg_fbm_free(st[(size_t)r].f);
-  }
 }
 
 static int multi_check_args(tpg_multi* mg, const uint8_t* fbm_bytes, int64_t nrow, int64_t ncol, const int32_t* rowInd1,
@@ -677,7 +680,6 @@ extern "C" int tpg_multi_pairwise(tpg_multi* mg, const uint8_t* fbm_bytes, int64
     TpgEnter _enter(mg->ctx[(size_t)r]);
     tpg_pairwise_free(pw[(size_t)r]);
   }
-  multi_shard_free(mg, st);
   if (rc != TPG_OK) tpg_set_error("%s", err.c_str());
   return rc;
 }
@@ -720,9 +722,6 @@ extern "C" int tpg_multi_grouped_alt_freq(tpg_multi* mg, const uint8_t* fbm_byte
     else TPG_TRY(tpg_alt_freq_dip_pseudo(ctx, me.v, ploidy, as_counts, d_out.as<double>()));
     return multi_rows_to_caller(ctx, out, m, me.j0, d_out.as<double>(), ml, ncols);
   });
-  std::string err = rc == TPG_OK ? "" : tpg_last_error();
-  multi_shard_free(mg, st);
-  if (rc != TPG_OK) tpg_set_error("%s", err.c_str());
   return rc;
 }
 
@@ -798,9 +797,6 @@ extern "C" int tpg_multi_pop_fst(tpg_multi* mg, const uint8_t* fbm_bytes, int64_
       memcpy(fst_tot, ratio.data(), sizeof(double) * (size_t)P);
     }
   }
-  std::string err = rc == TPG_OK ? "" : tpg_last_error();
-  multi_shard_free(mg, st);
-  if (rc != TPG_OK) tpg_set_error("%s", err.c_str());
   return rc;
 }
 
@@ -839,17 +835,12 @@ extern "C" int tpg_multi_pca_partial_svd(tpg_multi* mg, const uint8_t* fbm_bytes
   if (!spread) {  // one device, no exchange
     tpg_ctx* ctx = mg->ctx[0];
     TpgEnter _enter(ctx);
-    tpg_fbm* f = nullptr;
-    tpg_view* v = nullptr;
+    MultiShard one;
+    one.ctx = ctx;
     const double* table = code256;
-    int rc = tpg_fbm_from_host_for_table(ctx, fbm_bytes, nrow, ncol, code256, &f, &table);
-    if (rc == TPG_OK) rc = tpg_view_create(ctx, f, rowInd1, n, colInd1, m, table, &v);
-    if (rc == TPG_OK) rc = tpg_pca_partial_svd(ctx, v, k, d, u, vload, center, scale, square_frobenius);
-    std::string err = rc == TPG_OK ? "" : tpg_last_error();
-    tpg_view_free(v);
-    tpg_fbm_free(f);
-    if (rc != TPG_OK) tpg_set_error("%s", err.c_str());
-    return rc;
+    TPG_TRY(tpg_fbm_from_host_for_table(ctx, fbm_bytes, nrow, ncol, code256, &one.f, &table));
+    TPG_TRY(tpg_view_create(ctx, one.f, rowInd1, n, colInd1, m, table, &one.v));
+    return tpg_pca_partial_svd(ctx, one.v, k, d, u, vload, center, scale, square_frobenius);
   }
   std::vector<MultiShard> st((size_t)mg->ndev);
   // phase 1 (no exchange): upload + pack; a failure here is known to all before anyone enters the Gram all-reduce
@@ -887,8 +878,5 @@ extern "C" int tpg_multi_pca_partial_svd(tpg_multi* mg, const uint8_t* fbm_bytes
       return TPG_OK;
     });
   if (rc == TPG_OK && square_frobenius) *square_frobenius = fro[0];
-  std::string err = rc == TPG_OK ? "" : tpg_last_error();
-  multi_shard_free(mg, st);
-  if (rc != TPG_OK) tpg_set_error("%s", err.c_str());
   return rc;
 }

@@ -138,17 +138,66 @@ struct tpg_fbm {
   bool pooled = false;  // d_bytes came from the context's pool (the per-block uploads of the increment_* mirrors)
 };
 
-// class-wise counts via MFMA: cls[n] in [0, nclass); cnt[3][Mpad][Cpad] (het, hom-alt, valid)
+// class-wise counts via MFMA: cls[n] in [0, nclass); cnt[3][Mpad][Cpad] (het, hom-alt, valid).  A description of the
+// buffer the VIEW owns (tpg_view::gc_buf): good until the next tpg_grouped_counts on that view, or its end
 struct GroupedCounts {
   int32_t* cnt = nullptr;
   int64_t Mpad = 0;  // 32 * n_lt
   int Cpad = 0;      // 32 * ceil(nclass/32)
   int nclass = 0;
-  bool borrowed = false;  // a view's cached counts handed out to a caller: not freed by the borrower
-  ~GroupedCounts();
 };
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Size-bucketed cache of device allocations (hipMalloc / hipFree cost milliseconds and synchronise
+// the device; a step of the hot path needs ~40 scratch buffers).  One pool PER CONTEXT: a context issues
+// all its work on one stream, so a block that goes back to its pool and out again is reused in stream
+// order; a block never crosses to another context (another device, or another stream of the same device).
+// tpg_pmalloc() serves the context the calling thread entered last (TpgEnter, first statement of every C-ABI
+// entry point, which also makes that context's device current); tpg_pfree() returns a block to the pool it
+// came from, or to hipFree() when that context is gone or the pointer is not the pool's.
+hipError_t tpg_pmalloc(void** p, size_t bytes);
+void tpg_pfree(void* p);
+void tpg_pool_trim(int pool_id);  // release the cached (free) blocks of one pool
+struct TpgEnter {
+  tpg_ctx* prev;
+  explicit TpgEnter(tpg_ctx* ctx);
+  ~TpgEnter();
+};
+tpg_ctx* tpg_current_ctx();
+
+// The owner of ONE pool block: back to its pool at scope exit (the pool is the context's the calling thread entered).
+// free() is the explicit early release: the pool is size-bucketed and reuse is stream-ordered, so a block of O(n m) or O(n^2)
+// bytes that today goes back before a later allocation of the same call keeps an explicit free() at that spot.
+struct DevBuf {
+  void* p = nullptr;
+  int alloc(size_t bytes) {
+    free();
+    TPG_HIP(tpg_pmalloc(&p, bytes ? bytes : 16));
+    return TPG_OK;
+  }
+  template <typename T> int alloc_n(size_t count) { return alloc(sizeof(T) * count); }
+  void free() { if (p) tpg_pfree(p); p = nullptr; }
+  void* release() { void* q = p; p = nullptr; return q; }  // to a longer-lived owner
+  template <typename T> T* as() const { return (T*)p; }
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { free(); p = o.release(); } return *this; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { free(); }
+};
+// All scratch of one call, freed together
+struct DevArena {
+  std::vector<DevBuf> blocks;
+  template <typename T> int get(T** p, size_t count) {
+    DevBuf b;
+    TPG_TRY(b.alloc_n<T>(count));
+    *p = b.as<T>();
+    blocks.push_back(std::move(b));
+    return TPG_OK;
+  }
+};
 
 // A view owns its layouts: the destructor returns T, L, T4, lc_part and the cached counts to the pool.
 struct tpg_view {
@@ -165,6 +214,7 @@ struct tpg_view {
   mutable uint4* T4 = nullptr;
   // the last per-class counts computed on this view (grouped_alt_freq, grouped_summaries and the Fst
   // methods of one analysis all use the same grouping): reused while the class vector is unchanged
+  mutable DevBuf gc_buf;  // gc_cache.cnt
   mutable GroupedCounts gc_cache;
   mutable std::vector<int32_t> gc_cls;
   // per-locus genotype counts as the fast pack kernel left them (it has every code in registers anyway): for each chunk of
@@ -237,23 +287,6 @@ static inline int tpg_env_int(const char* name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
-// Size-bucketed cache of device allocations (hipMalloc / hipFree cost milliseconds and synchronise
-// the device; a step of the hot path needs ~40 scratch buffers).  One pool PER CONTEXT: a context issues
-// all its work on one stream, so a block that goes back to its pool and out again is reused in stream
-// order; a block never crosses to another context (another device, or another stream of the same device).
-// tpg_pmalloc() serves the context the calling thread entered last (TpgEnter, first statement of every C-ABI
-// entry point, which also makes that context's device current); tpg_pfree() returns a block to the pool it
-// came from, or to hipFree() when that context is gone or the pointer is not the pool's.
-hipError_t tpg_pmalloc(void** p, size_t bytes);
-void tpg_pfree(void* p);
-void tpg_pool_trim(int pool_id);  // release the cached (free) blocks of one pool
-struct TpgEnter {
-  tpg_ctx* prev;
-  explicit TpgEnter(tpg_ctx* ctx);
-  ~TpgEnter();
-};
-tpg_ctx* tpg_current_ctx();
-
 // host -> device on the context's stream.  Up to a slot's size the source is copied into pinned memory first, so the
 // caller's buffer is free at return and nothing waits for the stream; larger copies are waited for.
 hipError_t tpg_h2d_async(tpg_ctx* ctx, void* dst, const void* src, size_t bytes);
@@ -286,39 +319,6 @@ static inline int tpg_dmalloc(T** p, size_t count) {
   return TPG_OK;
 }
 
-// The owner of ONE pool block: back to its pool at scope exit (the pool is the context's the calling thread entered).
-// free() is the explicit early release: the pool is size-bucketed and reuse is stream-ordered, so a block of O(n m) or O(n^2)
-// bytes that today goes back before a later allocation of the same call keeps an explicit free() at that spot.
-struct DevBuf {
-  void* p = nullptr;
-  int alloc(size_t bytes) {
-    free();
-    TPG_HIP(tpg_pmalloc(&p, bytes ? bytes : 16));
-    return TPG_OK;
-  }
-  template <typename T> int alloc_n(size_t count) { return alloc(sizeof(T) * count); }
-  void free() { if (p) tpg_pfree(p); p = nullptr; }
-  void* release() { void* q = p; p = nullptr; return q; }  // to a longer-lived owner
-  template <typename T> T* as() const { return (T*)p; }
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { free(); p = o.release(); } return *this; }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { free(); }
-};
-// All scratch of one call, freed together
-struct DevArena {
-  std::vector<DevBuf> blocks;
-  template <typename T> int get(T** p, size_t count) {
-    DevBuf b;
-    TPG_TRY(b.alloc_n<T>(count));
-    *p = b.as<T>();
-    blocks.push_back(std::move(b));
-    return TPG_OK;
-  }
-};
-
 // Output buffer that may be host or device memory: kernels write to dev(); commit() copies back
 // if the user's pointer is not device memory.
 bool tpg_is_device_ptr(const void* p);
@@ -340,6 +340,23 @@ struct InBuf {
   ~InBuf();
   template <typename T> const T* dev() { return (const T*)d; }
 };
+// Input array the HOST reads (argument checks, plans): the user's pointer if it is host memory, else `count` elements come down
+template <typename T>
+struct HostIn {
+  const T* p = nullptr;
+  std::vector<T> keep;
+  int init(tpg_ctx* ctx, const T* user, int64_t count) {
+    p = user;
+    if (!tpg_is_device_ptr(user)) return TPG_OK;
+    keep.resize((size_t)count);
+    TPG_HIP(tpg_download(ctx, keep.data(), user, sizeof(T) * (size_t)count));
+    p = keep.data();
+    return TPG_OK;
+  }
+  const T& operator[](int64_t i) const { return p[i]; }
+};
+// every [lo[i], hi[i]) inside [0, m], lo / hi in host or device memory; what = "window" | "block" (runtime.hip)
+int tpg_check_ranges(tpg_ctx* ctx, const int64_t* lo, const int64_t* hi, int64_t count, int64_t m, const char* what);
 
 void tpg_resident_release(tpg_ctx* ctx);
 
@@ -386,6 +403,19 @@ int tpg_launch_synth(tpg_ctx* ctx, uint8_t* d_bytes, uint64_t seed, int64_t nrow
 // per-locus
 int tpg_launch_loci_counts(tpg_ctx* ctx, const tpg_view* v, int32_t* d_counts /* m x 4 */);
 int tpg_grouped_counts(tpg_ctx* ctx, const tpg_view* v, const int32_t* h_cls, int nclass, GroupedCounts* out);
+// Class scheme shared by the grouped entry points (loci.hip): with pseudohaploids present class = 2*g + (ploidy==1),
+// otherwise class = g.  (ploidy is 1 or 2: the reference's dip_pseudo kernels assume it too.)  groupIds0 == NULL: all in group 0
+struct ClassPlan {
+  std::vector<int32_t> cls;
+  std::vector<int32_t> group_size;
+  int nclass = 0;
+  int has_hap = 0;
+};
+int make_class_plan(int64_t n, const int32_t* groupIds0, int ngroups, const double* ploidy, ClassPlan* cp);
+// its argument checks alone: ngroups > 0 and every id in [0, ngroups) (TPG_EINVAL); every ploidy 2 (TPG_EINVAL, "<what> only
+// works on diploid data": the reference's stopifnot_diploid)
+int tpg_check_group_ids(int64_t n, const int32_t* groupIds0, int ngroups);
+int tpg_require_diploid(int64_t n, const double* ploidy, const char* what);
 // per-individual counts that add up over views (loci.hip): d_acc (n x 4 int32, zero before the first view) += the view's loci,
 // read from L; tpg_launch_indiv_finish turns the sums over m loci into {n0, n1, n2, nNA} (d_out may be d_acc)
 int tpg_launch_indiv_accumulate(tpg_ctx* ctx, const tpg_view* v, int32_t* d_acc);

@@ -223,15 +223,6 @@ __global__ __launch_bounds__(256) void f2_gemm_kernel(F2Src src, int G, int ntil
     }
 }
 
-template <typename T>
-int f2_host_copy(tpg_ctx* ctx, const T* user, int64_t count, std::vector<T>* keep, const T** host) {
-  if (!tpg_is_device_ptr(user)) { *host = user; return TPG_OK; }
-  keep->resize((size_t)count);
-  TPG_HIP(tpg_download(ctx, keep->data(), user, sizeof(T) * (size_t)count));
-  *host = keep->data();
-  return TPG_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t tpg_f2_chunk_loci(void) { return F2_LB; }
@@ -282,33 +273,13 @@ extern "C" int tpg_f2_blocks(tpg_ctx* ctx, const tpg_view* v, const int32_t* gro
   TPG_REQUIRE(pr.maxmiss == pr.maxmiss && pr.minmaf == pr.minmaf && pr.maxmaf == pr.maxmaf, TPG_EINVAL, "a filter bound is NaN");
   const int G = ngroups;
   const int64_t m = v->m;
-  // classes as tpg_grouped_alt_freq_dip_pseudo forms them: 2 g + (ploidy == 1) once a pseudohaploid is present
-  int has_hap = 0;
-  if (ploidy)
-    for (int64_t i = 0; i < v->n; i++) {
-      TPG_REQUIRE(ploidy[i] == 1.0 || ploidy[i] == 2.0, TPG_EUNSUPPORTED,
-                  "ploidy[%lld] = %g: only diploid (2) and pseudohaploid (1) individuals are supported", (long long)i, ploidy[i]);
-      if (ploidy[i] == 1.0) has_hap = 1;
-    }
-  std::vector<int32_t> cls((size_t)v->n);
-  for (int64_t i = 0; i < v->n; i++) {
-    const int g = groupIds0 ? groupIds0[i] : 0;
-    TPG_REQUIRE(g >= 0 && g < G, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)", (long long)i, g, G);
-    cls[(size_t)i] = has_hap ? 2 * g + (ploidy[i] == 1.0 ? 1 : 0) : g;
-  }
+  ClassPlan cp;
+  TPG_TRY(make_class_plan(v->n, groupIds0, G, ploidy, &cp));
   if (nb == 0) return TPG_OK;
-  {
-    std::vector<int64_t> klo, khi;
-    const int64_t *hlo = nullptr, *hhi = nullptr;
-    TPG_TRY(f2_host_copy(ctx, lo, nb, &klo, &hlo));
-    TPG_TRY(f2_host_copy(ctx, hi, nb, &khi, &hhi));
-    for (int64_t b = 0; b < nb; b++)
-      TPG_REQUIRE(hlo[b] >= 0 && hlo[b] <= hhi[b] && hhi[b] <= m, TPG_EINVAL, "block %lld = [%lld, %lld) outside [0, %lld]",
-                  (long long)b, (long long)hlo[b], (long long)hhi[b], (long long)m);
-  }
+  TPG_TRY(tpg_check_ranges(ctx, lo, hi, nb, m, "block"));
   GroupedCounts gc;
-  TPG_TRY(tpg_grouped_counts(ctx, v, cls.data(), G * (has_hap ? 2 : 1), &gc));
-  const F2Src src{gc.cnt, gc.Mpad, gc.Cpad, has_hap};
+  TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
+  const F2Src src{gc.cnt, gc.Mpad, gc.Cpad, cp.has_hap};
   InBuf il, ih, ik;
   TPG_TRY(il.init(ctx, lo, sizeof(int64_t) * (size_t)nb));
   TPG_TRY(ih.init(ctx, hi, sizeof(int64_t) * (size_t)nb));

@@ -877,8 +877,8 @@ extern "C" int tpg_pairwise_fst_loop(tpg_ctx* ctx, int method, const int32_t* pa
     TPG_TRY(d_bad.alloc_n<int>(1));
     int bad = 0;
     TPG_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(tpg_freq_ref_check_kernel, dim3(1024), dim3(256), 0, ctx->stream, bp.dev<double>(),
-                       bq.dev<double>(), (int64_t)m * G, d_bad.as<int>());
+    TPG_LAUNCH(ctx, "freq_ref_check", tpg_freq_ref_check_kernel, dim3(1024), dim3(256), 0, bp.dev<double>(), bq.dev<double>(),
+               (int64_t)m * G, d_bad.as<int>());
     TPG_HIP(tpg_fetch_small(ctx, &bad, d_bad.p, sizeof(int)));
     TPG_REQUIRE(!bad, TPG_EINVAL, "freq_ref is not 1 - freq_alt: the device path recomputes it and would not match the reference");
   }
@@ -890,30 +890,16 @@ static int fused_fst(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, 
                      int method, const int32_t* pairs1, int P, int by_locus, int return_num_dem, double* fst_tot,
                      double* out_a, double* out_b, double* sum_num, double* sum_den) {
   TPG_REQUIRE(ctx && v && groupIds0, TPG_EINVAL, "null argument");
-  TPG_REQUIRE(ngroups > 0, TPG_EINVAL, "ngroups must be positive");
-  int has_hap = 0;
-  if (ploidy)
-    for (int64_t i = 0; i < v->n; i++) {
-      TPG_REQUIRE(ploidy[i] == 1.0 || ploidy[i] == 2.0, TPG_EUNSUPPORTED, "ploidy[%lld] = %g unsupported",
-                  (long long)i, ploidy[i]);
-      if (ploidy[i] == 1.0) has_hap = 1;
-    }
+  ClassPlan cp;
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, ploidy, &cp));
   // R/pairwise_pop_fst.R:110-115: pseudohaploids only with Hudson
-  TPG_REQUIRE(!has_hap || method == TPG_FST_HUDSON, TPG_EINVAL,
+  TPG_REQUIRE(!cp.has_hap || method == TPG_FST_HUDSON, TPG_EINVAL,
               "only method = Hudson is valid when the data include pseudohaploids");
-  std::vector<int32_t> cls((size_t)v->n);
-  for (int64_t i = 0; i < v->n; i++) {
-    TPG_REQUIRE(groupIds0[i] >= 0 && groupIds0[i] < ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)",
-                (long long)i, groupIds0[i], ngroups);
-    cls[(size_t)i] = has_hap ? 2 * groupIds0[i] + (ploidy[i] == 1.0 ? 1 : 0) : groupIds0[i];
-  }
   GroupedCounts gc;
-  TPG_TRY(tpg_grouped_counts(ctx, v, cls.data(), ngroups * (has_hap ? 2 : 1), &gc));
-  FstSrc src{gc.cnt, gc.Mpad, gc.Cpad, has_hap, nullptr, nullptr, nullptr, nullptr};
+  TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
+  FstSrc src{gc.cnt, gc.Mpad, gc.Cpad, cp.has_hap, nullptr, nullptr, nullptr, nullptr};
   // the valid alleles of a pair of populations never exceed four times the largest group
-  std::vector<int64_t> gsize((size_t)ngroups, 0);
-  for (int64_t i = 0; i < v->n; i++) gsize[(size_t)groupIds0[i]]++;
-  const int64_t kmax = 4 * *std::max_element(gsize.begin(), gsize.end());
+  const int64_t kmax = 4 * (int64_t)*std::max_element(cp.group_size.begin(), cp.group_size.end());
   return run_fst(ctx, method, src, v->m, ngroups, pairs1, P, by_locus, return_num_dem, fst_tot, out_a, out_b, sum_num,
                  sum_den, kmax < (1 << 20) ? (int)kmax : 0);
 }

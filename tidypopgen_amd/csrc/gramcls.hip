@@ -1028,8 +1028,8 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
     TPG_HIP(hipMemsetAsync(d_hist, 0, sizeof(int32_t) * ((size_t)n + 1), ctx->stream));
     TPG_HIP(hipMemsetAsync(d_perdest, 0, sizeof(int32_t) * (size_t)R, ctx->stream));
     if (m > 0)
-      hipLaunchKernelGGL(tpg_gclx_keys_kernel, dim3(512), dim3(256), 0, ctx->stream, d_counts, m, (int)n, d_key, d_hist);
-    TPG_HIP(hipGetLastError());
+      TPG_LAUNCH(ctx, "gclx_keys", tpg_gclx_keys_kernel, dim3(512), dim3(256), 0, d_counts, m, (int)n, d_key, d_hist);
+    TPG_CHECK_LAUNCH();
     return TPG_OK;
   };
   TPG_TRY(tpg_comm_agree(comm, local()));
@@ -1139,7 +1139,7 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
     *done = true;
     return TPG_OK;
   }
-  hipLaunchKernelGGL(tpg_gclx_weights_kernel, dim3(512), dim3(256), 0, ctx->stream, (const uint4*)d_recv, Q, m_in, d_w);
+  TPG_LAUNCH(ctx, "gclx_weights", tpg_gclx_weights_kernel, dim3(512), dim3(256), 0, (const uint4*)d_recv, Q, m_in, d_w);
   const GclsSrc src{d_recv, 0, recq, 0, 0, 2, 1};
   bool ok = false;
   TPG_TRY(gram_classes_core(ctx, n, Q, m_in, src, d_w, nullptr, d_K, true, &ok, true));  // (the caller double-centres: pca.hip)

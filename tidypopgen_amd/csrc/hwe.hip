@@ -120,15 +120,10 @@ extern "C" int tpg_gt_grouped_hwe(tpg_ctx* ctx, const tpg_view* v, const int32_t
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && groupIds0 && p, TPG_EINVAL, "null argument");
   TPG_REQUIRE(midp == 0 || midp == 1, TPG_EINVAL, "midp must be 0 or 1");
-  TPG_REQUIRE(ngroups >= 1, TPG_EINVAL, "ngroups must be positive");
-  std::vector<int32_t> cls((size_t)v->n);
-  for (int64_t i = 0; i < v->n; i++) {
-    TPG_REQUIRE(groupIds0[i] >= 0 && groupIds0[i] < ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)", (long long)i,
-                groupIds0[i], ngroups);
-    cls[(size_t)i] = groupIds0[i];
-  }
+  ClassPlan cp;
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, nullptr, &cp));
   GroupedCounts gc;
-  TPG_TRY(tpg_grouped_counts(ctx, v, cls.data(), ngroups, &gc));  // (n < 2^24 there)
+  TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));  // (n < 2^24 there)
   OutBuf o;
   TPG_TRY(o.init(p, sizeof(double) * (size_t)v->m * (size_t)ngroups));
   TPG_LAUNCH(ctx, "hwe_grouped", tpg_hwe_grouped_kernel, dim3((unsigned)ceil_div(v->m, 64)), dim3(256), 0,

@@ -360,13 +360,8 @@ struct LdBand {
 };
 
 // the window: hi[j] in [j, m), non-decreasing.  `hi` may be device memory.
-int ld_window(tpg_ctx* ctx, const int64_t* hi, int64_t m, std::vector<int64_t>& h, int64_t* words) {
-  h.resize((size_t)m);
-  if (tpg_is_device_ptr(hi)) {
-    TPG_HIP(tpg_download(ctx, h.data(), hi, sizeof(int64_t) * (size_t)m));
-  } else {
-    memcpy(h.data(), hi, sizeof(int64_t) * (size_t)m);
-  }
+int ld_window(tpg_ctx* ctx, const int64_t* hi, int64_t m, HostIn<int64_t>& h, int64_t* words) {
+  TPG_TRY(h.init(ctx, hi, m));
   int64_t W = 0;
   for (int64_t j = 0; j < m; j++) {
     TPG_REQUIRE(h[(size_t)j] >= j && h[(size_t)j] < m, TPG_EINVAL, "hi[%lld] = %lld outside [%lld, %lld)", (long long)j,
@@ -388,7 +383,7 @@ int ld_check_args(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, double thr
 }
 
 // counts -> Sx, d and the missing-value check; the window goes up.  Nothing of the caller's is written.
-int ld_prepare(tpg_ctx* ctx, const tpg_view* v, const std::vector<int64_t>& h, DevArena& sc, LdBand* B) {
+int ld_prepare(tpg_ctx* ctx, const tpg_view* v, const HostIn<int64_t>& h, DevArena& sc, LdBand* B) {
   const int64_t m = v->m;
   int32_t* d_counts = nullptr;
   TPG_TRY(sc.get(&d_counts, 4 * (size_t)m));
@@ -403,7 +398,7 @@ int ld_prepare(tpg_ctx* ctx, const tpg_view* v, const std::vector<int64_t>& h, D
   TPG_LAUNCH(ctx, "ld_prep", tpg_ld_prep_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, (const int4*)d_counts, v->n, m,
              B->d_sx, B->d_dd, B->d_flags);
   TPG_CHECK_LAUNCH();
-  TPG_HIP(tpg_upload(ctx, B->d_hi, h.data(), sizeof(int64_t) * (size_t)m));
+  TPG_HIP(tpg_upload(ctx, B->d_hi, h.p, sizeof(int64_t) * (size_t)m));
   return TPG_OK;
 }
 
@@ -426,7 +421,7 @@ extern "C" int tpg_ld_band_links(tpg_ctx* ctx, const tpg_view* v, const int64_t*
   TpgEnter _enter(ctx);
   TPG_TRY(ld_check_args(ctx, v, hi, thr_r2));
   TPG_REQUIRE(stride_words >= 0 && (bits || stride_words == 0), TPG_EINVAL, "null argument");
-  std::vector<int64_t> h;
+  HostIn<int64_t> h;
   LdBand B;
   TPG_TRY(ld_window(ctx, hi, v->m, h, &B.words));
   TPG_REQUIRE(stride_words >= B.words, TPG_EINVAL, "stride_words = %lld, the window needs %lld", (long long)stride_words,
@@ -454,7 +449,7 @@ extern "C" int tpg_ld_clump(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, 
   TPG_TRY(ld_check_args(ctx, v, hi, thr_r2));
   TPG_REQUIRE(keep, TPG_EINVAL, "null argument");
   const int64_t m = v->m;
-  std::vector<int64_t> h;
+  HostIn<int64_t> h;
   LdBand B;
   TPG_TRY(ld_window(ctx, hi, m, h, &B.words));
   const int64_t stride = B.words > 0 ? B.words : 1, bstride = B.words + 1;

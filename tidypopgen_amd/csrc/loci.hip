@@ -248,19 +248,14 @@ __global__ void tpg_ind_hetero_kernel(const int4* __restrict__ counts, int64_t n
 extern "C" int tpg_gt_ind_hetero(tpg_ctx* ctx, const tpg_view* v, int32_t* out) {
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && out, TPG_EINVAL, "null argument");
-  int32_t* d_counts = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)v->n));
-  int rc = tpg_indiv_counts(ctx, v, d_counts);
+  DevBuf d_counts;
+  TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)v->n));
+  TPG_TRY(tpg_indiv_counts(ctx, v, d_counts.as<int32_t>()));
   OutBuf o;
-  if (rc == TPG_OK) rc = o.init(out, sizeof(int32_t) * 2 * (size_t)v->n);
-  if (rc == TPG_OK) {
-    TPG_LAUNCH(ctx, "ind_hetero", tpg_ind_hetero_kernel, dim3(256), dim3(256), 0, (const int4*)d_counts, v->n,
-               o.dev<int32_t>());
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { tpg_set_error("ind_hetero: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  }
-  tpg_pfree(d_counts);
-  TPG_TRY(rc);
+  TPG_TRY(o.init(out, sizeof(int32_t) * 2 * (size_t)v->n));
+  TPG_LAUNCH(ctx, "ind_hetero", tpg_ind_hetero_kernel, dim3(256), dim3(256), 0, (const int4*)d_counts.p, v->n, o.dev<int32_t>());
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
   return o.commit(ctx);
 }
 
@@ -276,18 +271,14 @@ __global__ void tpg_pi_kernel(const int4* __restrict__ counts, int64_t m, double
 extern "C" int tpg_gt_pi_diploid(tpg_ctx* ctx, const tpg_view* v, double* pi) {
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && pi, TPG_EINVAL, "null argument");
-  int32_t* d_counts = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)v->m));
-  int rc = tpg_launch_loci_counts(ctx, v, d_counts);
+  DevBuf d_counts;
+  TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)v->m));
+  TPG_TRY(tpg_launch_loci_counts(ctx, v, d_counts.as<int32_t>()));
   OutBuf o;
-  if (rc == TPG_OK) rc = o.init(pi, sizeof(double) * (size_t)v->m);
-  if (rc == TPG_OK) {
-    TPG_LAUNCH(ctx, "pi_diploid", tpg_pi_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts, v->m, o.dev<double>());
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { tpg_set_error("pi: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  }
-  tpg_pfree(d_counts);
-  TPG_TRY(rc);
+  TPG_TRY(o.init(pi, sizeof(double) * (size_t)v->m));
+  TPG_LAUNCH(ctx, "pi_diploid", tpg_pi_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts.p, v->m, o.dev<double>());
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
   return o.commit(ctx);
 }
 
@@ -478,97 +469,93 @@ __global__ __launch_bounds__(256, 3) void tpg_grouped_counts_kernel(const uint4*
   }
 }
 
-GroupedCounts::~GroupedCounts() {
-  if (cnt && !borrowed) tpg_pfree(cnt);
-}
-
+// The view owns the counts (gc_buf) and remembers the class vector they belong to; *out describes them, on a hit and on a
+// miss alike
 int tpg_grouped_counts(tpg_ctx* ctx, const tpg_view* v, const int32_t* h_cls, int nclass, GroupedCounts* out) {
   TPG_REQUIRE(nclass > 0, TPG_EINVAL, "no classes");
   for (int64_t i = 0; i < v->n; i++)
     TPG_REQUIRE(h_cls[i] >= 0 && h_cls[i] < nclass, TPG_EINVAL, "class id %d of individual %lld out of [0,%d)",
                 h_cls[i], (long long)i, nclass);
-  const int GT = (int)ceil_div(nclass, 32);
-  const int64_t n_lt = v->KG * 4;
-  if (v->gc_cache.cnt && v->gc_cache.nclass == nclass && v->gc_cls.size() == (size_t)v->n &&
+  TPG_REQUIRE(v->n < (1 << 24), TPG_EUNSUPPORTED, "grouped counts of more than 2^24 individuals");  // FP32 sums of ones
+  GroupedCounts& gc = v->gc_cache;
+  if (gc.cnt && gc.nclass == nclass && v->gc_cls.size() == (size_t)v->n &&
       memcmp(v->gc_cls.data(), h_cls, sizeof(int32_t) * (size_t)v->n) == 0) {
-    *out = v->gc_cache;  // shallow copy of the cached buffer
-    out->borrowed = true;
+    *out = gc;
     return TPG_OK;
   }
-  if (v->gc_cache.cnt) { tpg_pfree(v->gc_cache.cnt); v->gc_cache.cnt = nullptr; }
-  out->Mpad = n_lt * 32;
-  out->Cpad = GT * 32;
-  out->nclass = nclass;
-  TPG_HIP(tpg_pmalloc((void**)&out->cnt, sizeof(int32_t) * 3 * (size_t)out->Mpad * (size_t)out->Cpad));
-  TPG_REQUIRE(v->n < (1 << 24), TPG_EUNSUPPORTED, "grouped counts of more than 2^24 individuals");  // FP32 sums of ones
+  const int GT = (int)ceil_div(nclass, 32);
+  const int64_t n_lt = v->KG * 4, Mpad = n_lt * 32;
+  const int Cpad = GT * 32;
+  gc = GroupedCounts();  // nothing cached until the new counts are enqueued
+  TPG_TRY(v->gc_buf.alloc_n<int32_t>(3 * (size_t)Mpad * (size_t)Cpad));  // (the old block goes back first)
+  int32_t* cnt = v->gc_buf.as<int32_t>();
   // class sizes (the valid count of a class is its size minus its missing genotypes), behind the class ids
   std::vector<int32_t> h_up((size_t)v->n + (size_t)GT * 32, 0);
   memcpy(h_up.data(), h_cls, sizeof(int32_t) * (size_t)v->n);
   for (int64_t i = 0; i < v->n; i++) h_up[(size_t)v->n + (size_t)h_cls[i]]++;
+  DevArena sc;
   int32_t* d_cls = nullptr;
   uint4* d_oh = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_cls, sizeof(int32_t) * h_up.size()));
-  hipError_t e = tpg_pmalloc((void**)&d_oh, (size_t)v->Q * 2 * GT * 1024);
-  if (e != hipSuccess) { tpg_pfree(d_cls); tpg_set_error("hipMalloc one-hot: %s", hipGetErrorString(e)); return TPG_EHIP; }
-  int rc = TPG_OK;
-  e = tpg_h2d_async(ctx, d_cls, h_up.data(), sizeof(int32_t) * h_up.size());
-  if (e != hipSuccess) { tpg_set_error("class upload: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-  if (rc == TPG_OK) {
-    TPG_LAUNCH(ctx, "onehot", tpg_onehot_kernel, dim3(1024), dim3(256), 0, d_cls, v->n, v->Q, GT, d_oh);
-    const unsigned grid = (unsigned)ceil_div(n_lt, 4 * GC_NLT);
-    int g0 = 0;
-    while (g0 < GT) {
-      if (GT - g0 >= 2) {
-        TPG_LAUNCH(ctx, "grouped_counts", tpg_grouped_counts_kernel<2>, dim3(grid), dim3(256), 0, (const uint4*)v->L,
-                   (const uint4*)d_oh, n_lt, v->Q, g0, GT, (const int32_t*)(d_cls + v->n), out->cnt, out->Mpad, out->Cpad);
-        g0 += 2;
-      } else {
-        TPG_LAUNCH(ctx, "grouped_counts", tpg_grouped_counts_kernel<1>, dim3(grid), dim3(256), 0, (const uint4*)v->L,
-                   (const uint4*)d_oh, n_lt, v->Q, g0, GT, (const int32_t*)(d_cls + v->n), out->cnt, out->Mpad, out->Cpad);
-        g0 += 1;
-      }
+  TPG_TRY(sc.get(&d_cls, h_up.size()));
+  TPG_TRY(sc.get(&d_oh, (size_t)v->Q * 2 * GT * 64));
+  TPG_HIP(tpg_h2d_async(ctx, d_cls, h_up.data(), sizeof(int32_t) * h_up.size()));
+  TPG_LAUNCH(ctx, "onehot", tpg_onehot_kernel, dim3(1024), dim3(256), 0, d_cls, v->n, v->Q, GT, d_oh);
+  const unsigned grid = (unsigned)ceil_div(n_lt, 4 * GC_NLT);
+  int g0 = 0;
+  while (g0 < GT) {
+    if (GT - g0 >= 2) {
+      TPG_LAUNCH(ctx, "grouped_counts", tpg_grouped_counts_kernel<2>, dim3(grid), dim3(256), 0, (const uint4*)v->L,
+                 (const uint4*)d_oh, n_lt, v->Q, g0, GT, (const int32_t*)(d_cls + v->n), cnt, Mpad, Cpad);
+      g0 += 2;
+    } else {
+      TPG_LAUNCH(ctx, "grouped_counts", tpg_grouped_counts_kernel<1>, dim3(grid), dim3(256), 0, (const uint4*)v->L,
+                 (const uint4*)d_oh, n_lt, v->Q, g0, GT, (const int32_t*)(d_cls + v->n), cnt, Mpad, Cpad);
+      g0 += 1;
     }
-    e = hipGetLastError();  // d_cls / d_oh go back to this context's pool below: reuse is stream-ordered, no wait needed
-    if (e != hipSuccess) { tpg_set_error("grouped counts: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
   }
-  tpg_pfree(d_cls);
-  tpg_pfree(d_oh);
-  if (rc == TPG_OK) {  // the view keeps the buffer; the caller borrows it
-    v->gc_cache = *out;
-    v->gc_cache.borrowed = false;
-    v->gc_cls.assign(h_cls, h_cls + v->n);
-    out->borrowed = true;
-  }
-  return rc;
+  TPG_CHECK_LAUNCH();  // d_cls / d_oh go back to this context's pool at scope exit: reuse is stream-ordered, no wait needed
+  gc.cnt = cnt;
+  gc.Mpad = Mpad;
+  gc.Cpad = Cpad;
+  gc.nclass = nclass;
+  v->gc_cls.assign(h_cls, h_cls + v->n);
+  *out = gc;
+  return TPG_OK;
 }
 
 // ---------------------------------------------------------------------------
-// Class scheme shared by the grouped entry points: with pseudohaploids present class = 2*g + (ploidy==1),
-// otherwise class = g.  (ploidy is 1 or 2: the reference's dip_pseudo kernels assume it too.)
-struct ClassPlan {
-  std::vector<int32_t> cls;
-  std::vector<int32_t> group_size;
-  int nclass = 0;
-  int has_hap = 0;
-};
+// The class plan and its argument checks (common.h)
+int tpg_check_group_ids(int64_t n, const int32_t* groupIds0, int ngroups) {
+  TPG_REQUIRE(ngroups > 0, TPG_EINVAL, "ngroups must be positive");
+  if (groupIds0)
+    for (int64_t i = 0; i < n; i++)
+      TPG_REQUIRE(groupIds0[i] >= 0 && groupIds0[i] < ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)", (long long)i,
+                  groupIds0[i], ngroups);
+  return TPG_OK;
+}
 
-static int make_class_plan(const tpg_view* v, const int32_t* groupIds0, int ngroups, const double* ploidy,
-                           ClassPlan* cp) {
+int tpg_require_diploid(int64_t n, const double* ploidy, const char* what) {
+  if (ploidy)
+    for (int64_t i = 0; i < n; i++) TPG_REQUIRE(ploidy[i] == 2.0, TPG_EINVAL, "%s only works on diploid data", what);
+  return TPG_OK;
+}
+
+int make_class_plan(int64_t n, const int32_t* groupIds0, int ngroups, const double* ploidy, ClassPlan* cp) {
   TPG_REQUIRE(ngroups > 0, TPG_EINVAL, "ngroups must be positive");
   cp->has_hap = 0;
   if (ploidy)
-    for (int64_t i = 0; i < v->n; i++) {
+    for (int64_t i = 0; i < n; i++) {
       TPG_REQUIRE(ploidy[i] == 1.0 || ploidy[i] == 2.0, TPG_EUNSUPPORTED,
                   "ploidy[%lld] = %g: only diploid (2) and pseudohaploid (1) individuals are supported",
                   (long long)i, ploidy[i]);
       if (ploidy[i] == 1.0) cp->has_hap = 1;
     }
+  TPG_TRY(tpg_check_group_ids(n, groupIds0, ngroups));
   cp->nclass = ngroups * (cp->has_hap ? 2 : 1);
-  cp->cls.resize((size_t)v->n);
+  cp->cls.resize((size_t)n);
   cp->group_size.assign((size_t)ngroups, 0);
-  for (int64_t i = 0; i < v->n; i++) {
+  for (int64_t i = 0; i < n; i++) {
     const int g = groupIds0 ? groupIds0[i] : 0;
-    TPG_REQUIRE(g >= 0 && g < ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)", (long long)i, g, ngroups);
     cp->group_size[(size_t)g]++;
     cp->cls[(size_t)i] = cp->has_hap ? 2 * g + (ploidy[i] == 1.0 ? 1 : 0) : g;
   }
@@ -680,7 +667,7 @@ extern "C" int tpg_gt_grouped_pi_diploid(tpg_ctx* ctx, const tpg_view* v, const 
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && groupIds0 && pi, TPG_EINVAL, "null argument");
   ClassPlan cp;
-  TPG_TRY(make_class_plan(v, groupIds0, ngroups, nullptr, &cp));
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, nullptr, &cp));
   GroupedCounts gc;
   TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
   const size_t bytes = sizeof(double) * (size_t)v->m * (size_t)ngroups;
@@ -718,7 +705,7 @@ extern "C" int tpg_grouped_genotype_counts(tpg_ctx* ctx, const tpg_view* v, cons
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && groupIds0 && out, TPG_EINVAL, "null argument");
   ClassPlan cp;
-  TPG_TRY(make_class_plan(v, groupIds0, ngroups, nullptr, &cp));
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, nullptr, &cp));
   GroupedCounts gc;
   TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
   OutBuf o;
@@ -791,52 +778,52 @@ __global__ __launch_bounds__(256) void tpg_finite_colsum_kernel(const double* __
   }
 }
 
+// The finite (drop_inf = 0: the non-NaN) column means of by-locus values d_loc (m x ncol, column-major) on the host: 64 block
+// partials per column, added up here in a fixed order.  Waits for the stream.
+static int finite_colmeans(tpg_ctx* ctx, const double* d_loc, int64_t m, int ncol, int drop_inf, double* means) {
+  const int NB = 64;
+  DevBuf d_part;
+  TPG_TRY(d_part.alloc_n<double>((size_t)2 * ncol * NB));
+  TPG_LAUNCH(ctx, "finite_colsum", tpg_finite_colsum_kernel, dim3(NB, (unsigned)ncol), dim3(256), 0, d_loc, m, drop_inf,
+             d_part.as<double>());
+  TPG_CHECK_LAUNCH();
+  std::vector<double> part((size_t)2 * ncol * NB);
+  TPG_HIP(tpg_download(ctx, part.data(), d_part.p, sizeof(double) * part.size()));  // (small: the mailbox) waits for the stream
+  for (int c = 0; c < ncol; c++) {
+    double s = 0, k = 0;
+    for (int b = 0; b < NB; b++) { s += part[((size_t)c * NB + b) * 2]; k += part[((size_t)c * NB + b) * 2 + 1]; }
+    means[c] = s / k;
+  }
+  return TPG_OK;
+}
+
 extern "C" int tpg_pop_global_stats(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups,
                                     const double* ploidy, double* by_locus, double* overall) {
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && groupIds0 && (by_locus || overall), TPG_EINVAL, "null argument");
-  if (ploidy)
-    for (int64_t i = 0; i < v->n; i++)  // stopifnot_diploid(.x), R/pop_global_stats.R:117
-      TPG_REQUIRE(ploidy[i] == 2.0, TPG_EINVAL, "pop_global_stats only works on diploid data");
+  TPG_TRY(tpg_require_diploid(v->n, ploidy, "pop_global_stats"));  // stopifnot_diploid(.x), R/pop_global_stats.R:117
   ClassPlan cp;
-  TPG_TRY(make_class_plan(v, groupIds0, ngroups, nullptr, &cp));
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, nullptr, &cp));
   GroupedCounts gc;
   TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
   const int64_t m = v->m;
   OutBuf ob;
-  double* d_tmp = nullptr;
+  DevBuf d_tmp;
   if (by_locus) TPG_TRY(ob.init(by_locus, sizeof(double) * 10 * (size_t)m));
-  else TPG_HIP(tpg_pmalloc((void**)&d_tmp, sizeof(double) * 10 * (size_t)m));
-  double* d_loc = by_locus ? ob.dev<double>() : d_tmp;
-  const int NB = 64;
-  double* d_part = nullptr;
-  hipError_t e = tpg_pmalloc((void**)&d_part, sizeof(double) * 2 * 10 * NB);
-  std::vector<double> part((size_t)2 * 10 * NB);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(tpg_global_stats_kernel, dim3(1024), dim3(256), 0, ctx->stream, (const int32_t*)gc.cnt, gc.Mpad,
-                       gc.Cpad, m, ngroups, d_loc);
-    if (overall) {
-      hipLaunchKernelGGL(tpg_finite_colsum_kernel, dim3(NB, 10), dim3(256), 0, ctx->stream, (const double*)d_loc, m, 1, d_part);
-      e = tpg_download(ctx, part.data(), d_part, sizeof(double) * part.size());  // (small: the mailbox) waits for the stream
-    } else {
-      e = hipStreamSynchronize(ctx->stream);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-  }
-  tpg_pfree(d_part);
-  tpg_pfree(d_tmp);
-  if (e != hipSuccess) { tpg_set_error("pop_global_stats: %s", hipGetErrorString(e)); return TPG_EHIP; }
+  else TPG_TRY(d_tmp.alloc_n<double>(10 * (size_t)m));
+  double* d_loc = by_locus ? ob.dev<double>() : d_tmp.as<double>();
+  TPG_LAUNCH(ctx, "global_stats", tpg_global_stats_kernel, dim3(1024), dim3(256), 0, (const int32_t*)gc.cnt, gc.Mpad, gc.Cpad, m,
+             ngroups, d_loc);
+  TPG_CHECK_LAUNCH();
   if (overall) {
     // is.na(res) <- is.infinite(res); colMeans(res, na.rm = TRUE); then the ratios of means (:203-210)
-    for (int c = 0; c < 10; c++) {
-      double s = 0, k = 0;
-      for (int b = 0; b < NB; b++) { s += part[((size_t)c * NB + b) * 2]; k += part[((size_t)c * NB + b) * 2 + 1]; }
-      overall[c] = s / k;
-    }
+    TPG_TRY(finite_colmeans(ctx, d_loc, m, 10, 1, overall));
     overall[6] = overall[3] / overall[2];
     overall[7] = overall[5] / overall[4];
     overall[8] = 1 - overall[0] / overall[1];
     overall[9] = overall[5] / (1 - overall[1]);
+  } else {
+    TPG_HIP(hipStreamSynchronize(ctx->stream));
   }
   if (by_locus) TPG_TRY(ob.commit(ctx));
   return TPG_OK;
@@ -880,9 +867,7 @@ extern "C" int tpg_window_stats(tpg_ctx* ctx, const double* x, int64_t m, int nc
   TPG_REQUIRE(op == 0 || op == 1, TPG_EINVAL, "operator must be 0 (mean) or 1 (sum)");
   TPG_REQUIRE(m >= 0 && ncol >= 1 && ncol <= 65535 && nw >= 0 && nw < 2147483647ll, TPG_EINVAL, "bad sizes");
   if (nw == 0) return TPG_OK;
-  for (int64_t w = 0; w < nw; w++)
-    TPG_REQUIRE(lo[w] >= 0 && lo[w] <= hi[w] && hi[w] <= m, TPG_EINVAL, "window %lld = [%lld, %lld) outside [0, %lld]",
-                (long long)w, (long long)lo[w], (long long)hi[w], (long long)m);
+  TPG_TRY(tpg_check_ranges(ctx, lo, hi, nw, m, "window"));
   InBuf ix, il, ih, ip;
   TPG_TRY(ix.init(ctx, x, sizeof(double) * (size_t)m * (size_t)ncol));
   TPG_TRY(il.init(ctx, lo, sizeof(int64_t) * (size_t)nw));
@@ -929,45 +914,23 @@ extern "C" int tpg_pop_basic_stats(tpg_ctx* ctx, const tpg_view* v, const int32_
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && v && groupIds0 && (by_locus || colmeans), TPG_EINVAL, "null argument");
   TPG_REQUIRE(which >= 0 && which <= 2, TPG_EINVAL, "which must be 0 (Ho), 1 (Hs) or 2 (Fis)");
-  if (ploidy)
-    for (int64_t i = 0; i < v->n; i++)  // stopifnot_diploid(.x)
-      TPG_REQUIRE(ploidy[i] == 2.0, TPG_EINVAL, "this statistic only works on diploid data");
+  TPG_TRY(tpg_require_diploid(v->n, ploidy, "this statistic"));  // stopifnot_diploid(.x)
   ClassPlan cp;
-  TPG_TRY(make_class_plan(v, groupIds0, ngroups, nullptr, &cp));
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, nullptr, &cp));
   GroupedCounts gc;
   TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
   const int64_t m = v->m;
   const size_t bytes = sizeof(double) * (size_t)m * (size_t)ngroups;
   OutBuf ob;
-  double* d_tmp = nullptr;
+  DevBuf d_tmp;
   if (by_locus) TPG_TRY(ob.init(by_locus, bytes));
-  else TPG_HIP(tpg_pmalloc((void**)&d_tmp, bytes));
-  double* d_loc = by_locus ? ob.dev<double>() : d_tmp;
-  const int NB = 64;
-  double* d_part = nullptr;
-  hipError_t e = tpg_pmalloc((void**)&d_part, sizeof(double) * 2 * (size_t)ngroups * NB);
-  std::vector<double> part((size_t)2 * ngroups * NB);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(tpg_pop_basic_kernel, dim3(2048), dim3(256), 0, ctx->stream, (const int32_t*)gc.cnt, gc.Mpad, gc.Cpad,
-                       m, ngroups, which, d_loc);
-    if (colmeans) {
-      hipLaunchKernelGGL(tpg_finite_colsum_kernel, dim3(NB, (unsigned)ngroups), dim3(256), 0, ctx->stream,
-                         (const double*)d_loc, m, 0, d_part);
-      e = tpg_download(ctx, part.data(), d_part, sizeof(double) * part.size());  // (small: the mailbox) waits for the stream
-    } else {
-      e = hipStreamSynchronize(ctx->stream);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-  }
-  tpg_pfree(d_part);
-  tpg_pfree(d_tmp);
-  if (e != hipSuccess) { tpg_set_error("pop_basic_stats: %s", hipGetErrorString(e)); return TPG_EHIP; }
-  if (colmeans)
-    for (int g = 0; g < ngroups; g++) {  // colMeans(x, na.rm = TRUE)
-      double sm = 0, k = 0;
-      for (int b = 0; b < NB; b++) { sm += part[((size_t)g * NB + b) * 2]; k += part[((size_t)g * NB + b) * 2 + 1]; }
-      colmeans[g] = sm / k;
-    }
+  else TPG_TRY(d_tmp.alloc(bytes));
+  double* d_loc = by_locus ? ob.dev<double>() : d_tmp.as<double>();
+  TPG_LAUNCH(ctx, "pop_basic", tpg_pop_basic_kernel, dim3(2048), dim3(256), 0, (const int32_t*)gc.cnt, gc.Mpad, gc.Cpad, m, ngroups,
+             which, d_loc);
+  TPG_CHECK_LAUNCH();
+  if (colmeans) TPG_TRY(finite_colmeans(ctx, d_loc, m, ngroups, 0, colmeans));  // colMeans(x, na.rm = TRUE)
+  else TPG_HIP(hipStreamSynchronize(ctx->stream));
   if (by_locus) TPG_TRY(ob.commit(ctx));
   return TPG_OK;
 }
@@ -999,22 +962,17 @@ extern "C" int tpg_alt_freq_dip_pseudo(tpg_ctx* ctx, const tpg_view* v, const do
   OutBuf o;
   TPG_TRY(o.init(out, sizeof(double) * 2 * (size_t)v->m));
   if (all_dip) {
-    int32_t* d_counts = nullptr;
-    TPG_HIP(tpg_pmalloc((void**)&d_counts, sizeof(int32_t) * 4 * (size_t)v->m));
-    int rc = tpg_launch_loci_counts(ctx, v, d_counts);
-    if (rc == TPG_OK) {
-      TPG_LAUNCH(ctx, "alt_freq_finalize", tpg_alt_freq_finalize_kernel, dim3(1024), dim3(256), 0,
-                 (const int4*)d_counts, v->m, as_counts, o.dev<double>());
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) { tpg_set_error("alt_freq: %s", hipGetErrorString(e)); rc = TPG_EHIP; }
-    }
-    tpg_pfree(d_counts);
-    TPG_TRY(rc);
-    return o.commit(ctx);
+    DevBuf d_counts;
+    TPG_TRY(d_counts.alloc_n<int32_t>(4 * (size_t)v->m));
+    TPG_TRY(tpg_launch_loci_counts(ctx, v, d_counts.as<int32_t>()));
+    TPG_LAUNCH(ctx, "alt_freq_finalize", tpg_alt_freq_finalize_kernel, dim3(1024), dim3(256), 0, (const int4*)d_counts.p, v->m,
+               as_counts, o.dev<double>());
+    TPG_CHECK_LAUNCH();
+    return o.commit(ctx);  // d_counts goes back to the pool behind the kernel: reuse is stream-ordered
   }
   // mixed ploidy: one group, two ploidy classes
   ClassPlan cp;
-  TPG_TRY(make_class_plan(v, nullptr, 1, ploidy, &cp));
+  TPG_TRY(make_class_plan(v->n, nullptr, 1, ploidy, &cp));
   GroupedCounts gc;
   TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
   // reuse the grouped finalize (mode 0 with G = 1 has the m x 2 layout wanted), then NA guard on the host side
@@ -1032,7 +990,7 @@ static int grouped_common(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupI
                           const double* ploidy, int mode, int as_counts, double* o0, size_t o0_count, double* o1,
                           double* o2, double* o3) {
   ClassPlan cp;
-  TPG_TRY(make_class_plan(v, groupIds0, ngroups, ploidy, &cp));
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, ploidy, &cp));
   GroupedCounts gc;
   TPG_TRY(tpg_grouped_counts(ctx, v, cp.cls.data(), cp.nclass, &gc));
   const size_t mg = (size_t)v->m * (size_t)ngroups;

@@ -907,12 +907,11 @@ static int pw_order_for(tpg_ctx* ctx, tpg_pairwise* pw, int RA, int RB, const in
         for (int J = pc * PG; J < j1; J++)
           if (RB * J + RB - 1 >= RA * I) order.push_back(make_int2(I, J));
     }
-    void* d = nullptr;
-    TPG_HIP(tpg_pmalloc(&d, sizeof(int2) * order.size()));
-    hipError_t e = hipMemcpyAsync(d, order.data(), sizeof(int2) * order.size(), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the host vector goes out of scope
-    if (e != hipSuccess) { tpg_pfree(d); tpg_set_error("pairwise unit table: %s", hipGetErrorString(e)); return TPG_EHIP; }
-    it = pw->orders.emplace(key, std::make_pair(d, (int64_t)order.size())).first;
+    DevBuf d;
+    TPG_TRY(d.alloc_n<int2>(order.size()));
+    TPG_HIP(hipMemcpyAsync(d.p, order.data(), sizeof(int2) * order.size(), hipMemcpyHostToDevice, ctx->stream));
+    TPG_HIP(hipStreamSynchronize(ctx->stream));  // the host vector goes out of scope
+    it = pw->orders.emplace(key, std::make_pair(d.release(), (int64_t)order.size())).first;
   }
   *d_order = (const int2*)it->second.first;
   *nun = it->second.second;
@@ -1456,30 +1455,25 @@ __global__ void tpg_grm_rect_kernel(double* __restrict__ M, int n, int ra, int r
 
 static int grm_from_as_band(tpg_ctx* ctx, tpg_comm* comm, int n, const PwBand& band, double* d_M) {
   const int NB = 2048;
-  double* d_part = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_part, sizeof(double) * (2 * NB + 2)));
-  double* d_sc = d_part + 2 * NB;
-  int rc = TPG_OK;
-  hipError_t e = hipMemsetAsync(d_part, 0, sizeof(double) * (2 * NB + 2), ctx->stream);
-  if (e == hipSuccess) {
-    if (band.r1 > band.r0)
-      TPG_LAUNCH(ctx, "grm_offdiag_sum", tpg_offdiag_sum_band_kernel, dim3(NB), dim3(256), 0, (const double*)d_M, n,
-                 (int)band.r0, (int)band.r1, d_part, d_part + NB);
-    TPG_LAUNCH(ctx, "grm_offdiag_sum", tpg_sum2_kernel, dim3(1), dim3(256), 0, (const double*)d_part,
-               (const double*)(d_part + NB), NB, d_sc);
-    if (comm) rc = tpg_comm_allreduce(comm, d_sc, 2, 1);  // sum and count over all ranks
-    if (rc == TPG_OK && band.r1 > band.r0) {
-      TPG_LAUNCH(ctx, "grm_scale", tpg_grm_rect_kernel, dim3(1024), dim3(256), 0, d_M, n, (int)band.r0, (int)band.r1,
-                 (int)band.r0, n, (const double*)d_sc);  // as stored
-      if (n > band.r1)
-        TPG_LAUNCH(ctx, "grm_scale", tpg_grm_rect_kernel, dim3(1024), dim3(256), 0, d_M, n, (int)band.r1, n, (int)band.r0,
-                   (int)band.r1, (const double*)d_sc);  // mirror image below the band's diagonal block
-    }
-    e = hipGetLastError();
+  DevBuf part;  // back to the pool at scope exit, stream-ordered: the pool hands it out again behind the kernels below
+  TPG_TRY(part.alloc_n<double>(2 * NB + 2));
+  double *d_part = part.as<double>(), *d_sc = d_part + 2 * NB;
+  TPG_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * (2 * NB + 2), ctx->stream));
+  if (band.r1 > band.r0)
+    TPG_LAUNCH(ctx, "grm_offdiag_sum", tpg_offdiag_sum_band_kernel, dim3(NB), dim3(256), 0, (const double*)d_M, n,
+               (int)band.r0, (int)band.r1, d_part, d_part + NB);
+  TPG_LAUNCH(ctx, "grm_offdiag_sum", tpg_sum2_kernel, dim3(1), dim3(256), 0, (const double*)d_part,
+             (const double*)(d_part + NB), NB, d_sc);
+  if (comm) TPG_TRY(tpg_comm_allreduce(comm, d_sc, 2, 1));  // sum and count over all ranks
+  if (band.r1 > band.r0) {
+    TPG_LAUNCH(ctx, "grm_scale", tpg_grm_rect_kernel, dim3(1024), dim3(256), 0, d_M, n, (int)band.r0, (int)band.r1,
+               (int)band.r0, n, (const double*)d_sc);  // as stored
+    if (n > band.r1)
+      TPG_LAUNCH(ctx, "grm_scale", tpg_grm_rect_kernel, dim3(1024), dim3(256), 0, d_M, n, (int)band.r1, n, (int)band.r0,
+                 (int)band.r1, (const double*)d_sc);  // mirror image below the band's diagonal block
   }
-  tpg_pfree(d_part);  // stream-ordered: the pool hands it out again behind the kernels above
-  if (e != hipSuccess) { tpg_set_error("grm (band): %s", hipGetErrorString(e)); return TPG_EHIP; }
-  return rc;
+  TPG_CHECK_LAUNCH();
+  return TPG_OK;
 }
 
 extern "C" int tpg_pairwise_grm(tpg_ctx* ctx, const tpg_pairwise* pw, double* out) {
@@ -1532,12 +1526,9 @@ extern "C" int tpg_block_means(tpg_ctx* ctx, const double* A, int64_t n, const i
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && A && groupIds0 && mean, TPG_EINVAL, "null argument");
   TPG_REQUIRE(n > 0 && ngroups > 0, TPG_EINVAL, "bad n = %lld or ngroups = %d", (long long)n, ngroups);
+  TPG_TRY(tpg_check_group_ids(n, groupIds0, ngroups));
   std::vector<int32_t> goff((size_t)ngroups + 1, 0), perm((size_t)n);
-  for (int64_t i = 0; i < n; i++) {
-    TPG_REQUIRE(groupIds0[i] >= 0 && groupIds0[i] < ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)",
-                (long long)i, groupIds0[i], ngroups);
-    goff[(size_t)groupIds0[i] + 1]++;
-  }
+  for (int64_t i = 0; i < n; i++) goff[(size_t)groupIds0[i] + 1]++;
   for (int g = 0; g < ngroups; g++) goff[(size_t)g + 1] += goff[(size_t)g];
   {
     std::vector<int32_t> fill(goff.begin(), goff.end() - 1);
@@ -1551,26 +1542,17 @@ extern "C" int tpg_block_means(tpg_ctx* ctx, const double* A, int64_t n, const i
   OutBuf om, oc;
   TPG_TRY(om.init(mean, sizeof(double) * gg));
   if (count) TPG_TRY(oc.init(count, sizeof(double) * gg));
+  DevArena sc;
   double *d_cs = nullptr, *d_cc = nullptr;
-  hipError_t e = tpg_pmalloc((void**)&d_cs, sizeof(double) * (size_t)n * (size_t)ngroups);
-  if (e == hipSuccess) e = tpg_pmalloc((void**)&d_cc, sizeof(double) * (size_t)n * (size_t)ngroups);
-  int rc = TPG_OK;
-  if (e == hipSuccess) {
-    [&]() -> int {
-      TPG_LAUNCH(ctx, "block_colsum", tpg_block_colsum_kernel, dim3((unsigned)n), dim3(64), 0, ia.dev<double>(), n,
-                 ngroups, ip.dev<int32_t>(), ig.dev<int32_t>(), skip_diag, d_cs, d_cc);
-      TPG_LAUNCH(ctx, "block_combine", tpg_block_combine_kernel, dim3((unsigned)ceil_div((int64_t)gg, 256)), dim3(256), 0,
-                 (const double*)d_cs, (const double*)d_cc, ngroups, ip.dev<int32_t>(), ig.dev<int32_t>(),
-                 om.dev<double>(), oc.dev<double>());
-      return TPG_OK;
-    }();
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  }
-  tpg_pfree(d_cs);
-  tpg_pfree(d_cc);
-  if (e != hipSuccess) { tpg_set_error("block means: %s", hipGetErrorString(e)); return TPG_EHIP; }
-  TPG_TRY(rc);
+  TPG_TRY(sc.get(&d_cs, (size_t)n * (size_t)ngroups));
+  TPG_TRY(sc.get(&d_cc, (size_t)n * (size_t)ngroups));
+  TPG_LAUNCH(ctx, "block_colsum", tpg_block_colsum_kernel, dim3((unsigned)n), dim3(64), 0, ia.dev<double>(), n, ngroups,
+             ip.dev<int32_t>(), ig.dev<int32_t>(), skip_diag, d_cs, d_cc);
+  TPG_LAUNCH(ctx, "block_combine", tpg_block_combine_kernel, dim3((unsigned)ceil_div((int64_t)gg, 256)), dim3(256), 0,
+             (const double*)d_cs, (const double*)d_cc, ngroups, ip.dev<int32_t>(), ig.dev<int32_t>(), om.dev<double>(),
+             oc.dev<double>());
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
   TPG_TRY(om.commit(ctx));
   if (count) TPG_TRY(oc.commit(ctx));
   return TPG_OK;
@@ -1746,24 +1728,21 @@ static int add_counts_to_caller(tpg_ctx* ctx, int which, const tpg_pairwise* pw,
     TPG_HIP(hipHostMalloc((void**)&r->stage, bytesA + bytesB, hipHostMallocDefault));
     r->stage_ints = (bytesA + bytesB) / sizeof(int32_t);
   }
-  uint8_t* d_out = nullptr;
-  TPG_HIP(tpg_pmalloc((void**)&d_out, bytesA + bytesB));
+  DevBuf out_buf;
+  TPG_TRY(out_buf.alloc(bytesA + bytesB));
+  uint8_t* d_out = out_buf.as<uint8_t>();
   const unsigned nt = (unsigned)ceil_div(pw->n, 32);
-  hipError_t e = hipSuccess;
-  {
-    ProfScope ps(ctx, "pairwise_counts_i32");
-    const dim3 grid(nt, nt);
-#define CNT2(TA_, TB_)                                                                                                        \
-  hipLaunchKernelGGL((tpg_pairwise_counts2_i32_kernel<TA_, TB_>), grid, dim3(256), 0, ctx->stream, (const int32_t*)pw->acc,   \
-                     (const int64_t*)pw->rowpad, (int)pw->nst, (int)pw->n, which, (int)pw->as_pad_quirk, (TA_*)d_out, biasA,  \
-                     (TB_*)(d_out + bytesA))
-    if (a16 && b16) CNT2(uint16_t, uint16_t);
-    else if (b16) CNT2(int32_t, uint16_t);
-    else if (a16) CNT2(uint16_t, int32_t);
-    else CNT2(int32_t, int32_t);
+  const dim3 grid(nt, nt);
+#define CNT2(TA_, TB_)                                                                                                       \
+  TPG_LAUNCH(ctx, "pairwise_counts_i32", (tpg_pairwise_counts2_i32_kernel<TA_, TB_>), grid, dim3(256), 0,                    \
+             (const int32_t*)pw->acc, (const int64_t*)pw->rowpad, (int)pw->nst, (int)pw->n, which, (int)pw->as_pad_quirk,    \
+             (TA_*)d_out, biasA, (TB_*)(d_out + bytesA))
+  if (a16 && b16) CNT2(uint16_t, uint16_t);
+  else if (b16) CNT2(int32_t, uint16_t);
+  else if (a16) CNT2(uint16_t, int32_t);
+  else CNT2(int32_t, int32_t);
 #undef CNT2
-    e = hipGetLastError();
-  }
+  hipError_t e = hipGetLastError();
   uint8_t* stage = (uint8_t*)r->stage;
   // Each matrix leaves the device in PIECES (an event behind each), and the team adds a piece as soon as it is in the staging
   // buffer: the additions run beside the transfer instead of a whole matrix behind it.  Piece p < NP: of the first matrix,
@@ -1780,7 +1759,7 @@ static int add_counts_to_caller(tpg_ctx* ctx, int which, const tpg_pairwise* pw,
     e = hipMemcpyAsync(stage + off, d_out + off, (hi - lo) * es, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipEventRecord(ev[q], ctx->stream);
   }
-  tpg_pfree(d_out);  // stream-ordered
+  out_buf.free();  // stream-ordered
   auto add = [&](int t, int q) {  // thread t's stripe of piece q
     const bool second = q >= npieces;
     const size_t lo = piece_lo(q % npieces), hi = piece_lo(q % npieces + 1);

@@ -360,17 +360,8 @@ struct RohPlan {
   std::vector<uint32_t> brk;   // KG * 4 + 1 words
   std::vector<uint32_t> wok;   // window w exists and crosses no break
   std::vector<int32_t> need;   // W + 1
-  std::vector<int64_t> pos;
+  HostIn<int64_t> pos;
 };
-
-int roh_fetch_input(tpg_ctx* ctx, const void* p, size_t bytes, void* host) {
-  if (tpg_is_device_ptr(p)) {
-    TPG_HIP(tpg_download(ctx, host, p, bytes));
-  } else {
-    memcpy(host, p, bytes);
-  }
-  return TPG_OK;
-}
 
 int roh_plan(tpg_ctx* ctx, const tpg_view* v, const int32_t* chrom, const int64_t* pos, const tpg_roh_params* P, RohPlan* pl) {
   TPG_REQUIRE(ctx && v && chrom && pos && P, TPG_EINVAL, "null argument");
@@ -386,10 +377,9 @@ int roh_plan(tpg_ctx* ctx, const tpg_view* v, const int32_t* chrom, const int64_
   pl->W = W;
   pl->HB = (W - 1 + 127) / 128;
   pl->nwords = ceil_div(m, 32);
-  std::vector<int32_t> ch((size_t)m);
-  pl->pos.resize((size_t)m);
-  TPG_TRY(roh_fetch_input(ctx, chrom, sizeof(int32_t) * (size_t)m, ch.data()));
-  TPG_TRY(roh_fetch_input(ctx, pos, sizeof(int64_t) * (size_t)m, pl->pos.data()));
+  HostIn<int32_t> ch;
+  TPG_TRY(ch.init(ctx, chrom, m));
+  TPG_TRY(pl->pos.init(ctx, pos, m));
   const size_t words = (size_t)v->KG * 4 + 1;
   pl->brk.assign(words, 0u);
   pl->wok.assign(words, 0u);
@@ -491,7 +481,7 @@ extern "C" int tpg_roh_detect(tpg_ctx* ctx, const tpg_view* v, const int32_t* ch
   R->n = n;
   R->m = m;
   TPG_TRY(R->pos.alloc_n<int64_t>((size_t)m));
-  TPG_HIP(tpg_upload(ctx, R->pos.p, pl.pos.data(), sizeof(int64_t) * (size_t)m));
+  TPG_HIP(tpg_upload(ctx, R->pos.p, pl.pos.p, sizeof(int64_t) * (size_t)m));
   if (m < pl.W) {
     *out = R.release();
     return TPG_OK;

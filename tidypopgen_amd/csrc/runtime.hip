@@ -578,6 +578,16 @@ InBuf::~InBuf() {
   if (owned_ptr) tpg_pfree(owned_ptr);
 }
 
+int tpg_check_ranges(tpg_ctx* ctx, const int64_t* lo, const int64_t* hi, int64_t count, int64_t m, const char* what) {
+  HostIn<int64_t> hlo, hhi;
+  TPG_TRY(hlo.init(ctx, lo, count));
+  TPG_TRY(hhi.init(ctx, hi, count));
+  for (int64_t i = 0; i < count; i++)
+    TPG_REQUIRE(hlo[i] >= 0 && hlo[i] <= hhi[i] && hhi[i] <= m, TPG_EINVAL, "%s %lld = [%lld, %lld) outside [0, %lld]", what,
+                (long long)i, (long long)hlo[i], (long long)hhi[i], (long long)m);
+  return TPG_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Host <-> HBM bulk transfers, the cold-start cost of every analysis (5 GB for a 5 000 x 1 000 000 FBM).  On the
 // MI355X boxes one hipMemcpy between device memory and pageable host memory whose pages are present runs at the
@@ -1301,9 +1311,8 @@ void tpg_view::drop_derived() {
   T = T4 = nullptr;
   lc_part = nullptr;
   lc_chunks = 0;
-  if (gc_cache.cnt && !gc_cache.borrowed) tpg_pfree(gc_cache.cnt);
-  gc_cache.cnt = nullptr;
-  gc_cache.nclass = 0;
+  gc_buf.free();
+  gc_cache = GroupedCounts();
   gc_cls.clear();
 }
 extern "C" void tpg_view_free(tpg_view* v) { delete v; }

@@ -756,9 +756,7 @@ struct StreamRun {
     TPG_REQUIRE(c->midp == 0 || c->midp == 1, TPG_EINVAL, "midp must be 0 or 1");
     if (c->grouped_counts || c->grouped_hwe_p) {
       TPG_REQUIRE(c->groupIds0 && c->ngroups >= 1, TPG_EINVAL, "grouped outputs need groupIds and ngroups");
-      for (int64_t i = 0; i < n; i++)
-        TPG_REQUIRE(c->groupIds0[i] >= 0 && c->groupIds0[i] < c->ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)", (long long)i,
-                    c->groupIds0[i], c->ngroups);
+      TPG_TRY(tpg_check_group_ids(n, c->groupIds0, c->ngroups));
     }
     TPG_REQUIRE(!c->indiv_counts || m < (1ll << 31), TPG_EUNSUPPORTED, "per-individual counts of 2^31 loci or more do not fit int32");
     want_loc = true;

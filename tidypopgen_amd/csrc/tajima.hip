@@ -166,38 +166,19 @@ __global__ __launch_bounds__(256) void tajima_windows_kernel(const double* __res
   if (n_loci) n_loci[o] = pad ? -1 : (int32_t)a.cnt;
 }
 
-// group of every individual, group sizes, (a1, e1, e2) per group; stopifnot_diploid (R/pop_tajimas_d.R:62, :108)
-struct TajPlan {
-  std::vector<int32_t> cls;
-  std::vector<int64_t> size;
+// the class plan (group of every individual, group sizes) and (a1, e1, e2) per group; stopifnot_diploid (R/pop_tajimas_d.R:62, :108)
+struct TajPlan : ClassPlan {
   std::vector<double> consts;  // 3 G
 };
 
 int tajima_plan(const tpg_view* v, const int32_t* groupIds0, int ngroups, const double* ploidy, TajPlan* p) {
   TPG_REQUIRE(ngroups >= 1 && ngroups <= 65535, TPG_EINVAL, "ngroups = %d out of [1, 65535]", ngroups);
-  if (ploidy)
-    for (int64_t i = 0; i < v->n; i++) TPG_REQUIRE(ploidy[i] == 2.0, TPG_EINVAL, "Tajima's D only works on diploid data");
-  p->cls.assign((size_t)v->n, 0);
-  p->size.assign((size_t)ngroups, 0);
-  for (int64_t i = 0; i < v->n; i++) {
-    const int g = groupIds0 ? groupIds0[i] : 0;
-    TPG_REQUIRE(g >= 0 && g < ngroups, TPG_EINVAL, "groupIds[%lld] = %d out of [0,%d)", (long long)i, g, ngroups);
-    p->cls[(size_t)i] = g;
-    p->size[(size_t)g]++;
-  }
+  TPG_TRY(tpg_require_diploid(v->n, ploidy, "Tajima's D"));
+  TPG_TRY(make_class_plan(v->n, groupIds0, ngroups, nullptr, p));
   p->consts.assign((size_t)3 * ngroups, NAN);  // a group nobody belongs to: NaN throughout
   for (int g = 0; g < ngroups; g++)
-    if (p->size[(size_t)g] > 0) tajima_consts(2 * p->size[(size_t)g], &p->consts[3 * g], &p->consts[3 * g + 1], &p->consts[3 * g + 2]);
-  return TPG_OK;
-}
-
-// lo / hi / pad_na as the host sees them, for the argument checks (they may live in device memory: nw words come down)
-template <typename T>
-int tajima_host_copy(tpg_ctx* ctx, const T* user, int64_t count, std::vector<T>* keep, const T** host) {
-  if (!tpg_is_device_ptr(user)) { *host = user; return TPG_OK; }
-  keep->resize((size_t)count);
-  TPG_HIP(tpg_download(ctx, keep->data(), user, sizeof(T) * (size_t)count));
-  *host = keep->data();
+    if (p->group_size[(size_t)g] > 0)
+      tajima_consts(2 * (int64_t)p->group_size[(size_t)g], &p->consts[3 * g], &p->consts[3 * g + 1], &p->consts[3 * g + 2]);
   return TPG_OK;
 }
 
@@ -244,7 +225,7 @@ extern "C" int tpg_pop_tajimas_d(tpg_ctx* ctx, const tpg_view* v, const int32_t*
   for (int g = 0; g < G; g++) {
     int64_t s;
     memcpy(&s, &out[(size_t)G + g], sizeof s);
-    const double k = pl.size[(size_t)g] > 0 ? out[(size_t)g] : NAN;
+    const double k = pl.group_size[(size_t)g] > 0 ? out[(size_t)g] : NAN;
     d[g] = tajima_d(k, s, pl.consts[3 * g], pl.consts[3 * g + 1], pl.consts[3 * g + 2]);
     if (seg) seg[g] = s;
     if (k_hat) k_hat[g] = k;
@@ -266,15 +247,7 @@ extern "C" int tpg_windows_pop_tajimas_d(tpg_ctx* ctx, const tpg_view* v, const 
   if (nw == 0) return TPG_OK;
   const int G = ngroups;
   const int64_t m = v->m;
-  {
-    std::vector<int64_t> klo, khi;
-    const int64_t *hlo = nullptr, *hhi = nullptr;
-    TPG_TRY(tajima_host_copy(ctx, lo, nw, &klo, &hlo));
-    TPG_TRY(tajima_host_copy(ctx, hi, nw, &khi, &hhi));
-    for (int64_t w = 0; w < nw; w++)
-      TPG_REQUIRE(hlo[w] >= 0 && hlo[w] <= hhi[w] && hhi[w] <= m, TPG_EINVAL, "window %lld = [%lld, %lld) outside [0, %lld]",
-                  (long long)w, (long long)hlo[w], (long long)hhi[w], (long long)m);
-  }
+  TPG_TRY(tpg_check_ranges(ctx, lo, hi, nw, m, "window"));
   GroupedCounts gc;
   TPG_TRY(tpg_grouped_counts(ctx, v, pl.cls.data(), G, &gc));
   InBuf il, ih, ip, ic;
