@@ -403,6 +403,82 @@ int tpg_f2_blocks(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int
 int tpg_f4_jackknife(const double* f2, int G, int64_t nb, const int64_t* block_len, const int32_t* quads0, int64_t nq,
                      double* est, double* se, int32_t* n_used);
 
+/* ---- admixture (gt_admixture, R/gt_admixture.R:62-100: the reference exports the panel to PLINK, runs an outside `admixture`
+ * binary and reads its .Q / .P files back; ADMIXTURE is not part of the reference's sources and nothing pins it, so the model
+ * and the algorithm are defined HERE: the plain EM of Tang et al. 2005 (FRAPPE), the fixed-point map that Alexander, Novembre
+ * and Lange 2009 accelerate) ------------------------------------------------------------------------------------------------
+ * Data and parameters.  A view of N individuals x M loci, diploid; g(i,j) in {0, 1, 2} is the dosage of the counted allele,
+ *   code 3 is missing and is skipped everywhere ("typed" = not missing).  K ancestral populations.  Q is N x K with rows that
+ *   sum to 1; F is K x M, the frequency of the COUNTED (alt) allele, the one tpg_alt_freq_dip_pseudo counts.  (ADMIXTURE's own
+ *   .P file may describe the other allele: compare 1 - P before concluding that two runs disagree.)
+ * Per typed entry.  p(i,j) = sum_k q(i,k) f(k,j) and pbar(i,j) = sum_k q(i,k) (1 - f(k,j)), both in ascending k, each term
+ *   joined by one fused multiply-add starting from +0.  pbar is a sum of positive terms of its own, never 1 - p: the bounds
+ *   below rest on that.
+ * Log-likelihood.  l(Q,F) = sum over typed (i,j) of [ g ln p + (2 - g) ln pbar ].  The device forms the term as ONE logarithm,
+ *   ln(p^g pbar^(2-g)) with the product p p, p pbar or pbar pbar rounded once; f in [eps, 1 - eps] keeps it >= eps^2.
+ * One EM step, both updates from the OLD (Q, F).  With w1 = g / p and w0 = (2 - g) / pbar:
+ *   a(k,j) = f(k,j) * sum_i q(i,k) w1(i,j);   b(k,j) = (1 - f(k,j)) * sum_i q(i,k) w0(i,j)      (sums over the typed i)
+ *   f'(k,j) = a / (a + b), then clamped into [eps, 1 - eps], eps = TPG_ADMIX_EPS
+ *   q'(i,k) = (q(i,k) / (2 T_i)) * sum_j [ f(k,j) w1(i,j) + (1 - f(k,j)) w0(i,j) ]              (sum over the typed j;
+ *             T_i = typed loci of i; the two products of a locus enter the sum as two terms)
+ *   A locus nobody is typed at keeps its f; so does (k, j) when a + b = 0, which takes q(i,k) = 0 at every typed i and cannot
+ *   happen from a start of this header.  An individual typed nowhere keeps its row.  Q has no clamp and is not renormalised:
+ *   with f in [eps, 1 - eps] and a row sum of 1, p and pbar are >= eps, and the update keeps the row sum at 1 up to rounding.
+ *   The clamp is a box constraint on a separable concave M-step, so the step stays a constrained EM step and l does not
+ *   decrease in exact arithmetic.
+ * Start.  q0 (N x K, column-major) and / or f0 (M x K, column-major: the shape of a .P file), host or device memory.  Each
+ *   q0 row is divided by its sum (added in ascending k); f0 is clamped.  An entry of q0 that is not finite or not positive, or
+ *   an entry of f0 that is not finite: TPG_EINVAL, found on the device.  Where q0 / f0 is NULL the start is drawn from `seed`,
+ *   a pure function of position (M = tpg_mix64, see "simple imputation" above), so it does not depend on launch shape:
+ *     u(h) = ((double)(h >> 11) + 0.5) * 2^-53 in IEEE double (the addition rounds to even once h >> 11 >= 2^52; 0 < u <= 1)
+ *     Q: h = M(M(seed ^ M(i)) ^ M(k));  q0(i,k) = u / (sum of the row's u, ascending k)
+ *     F: h = M(M((seed ^ 0xF0F0F0F0F0F0F0F0) ^ M(j)) ^ M(k));  f0(k,j) = 0.1 + 0.8 u (a product, then a sum: no fusing)
+ * Iteration.  State 0 is the start; iteration t makes state t from state t - 1, and the same pass yields l(t - 1).  Stop after
+ *   iteration t when t >= 2 and l(t-1) - l(t-2) < tol (converged = 1), or when t = max_iter (converged = 0 unless the rule
+ *   holds there too).  A final likelihood-only pass gives l of the returned state: n_iter = t, loglik = l(t), and
+ *   loglik_trace[0 .. t] = l(0) .. l(t); entries beyond t are not written.  max_iter = 0 returns the start and its l.  tol is
+ *   absolute (ADMIXTURE's default criterion, 1e-4).  The host reads one double per iteration; nothing proportional to N or M
+ *   crosses PCIe before the end.
+ * Flags.  update_f = 0: projection onto given frequencies (ADMIXTURE -P); P comes back as it went in after clamping, bit for
+ *   bit.  update_q = 0: the same for Q (after normalisation).
+ * Determinism.  A result depends on the view, K, the start and the parameters alone, not on launch geometry or device; two
+ *   calls give the same bits; no floating-point atomics.  Every sum has a fixed shape (csrc/admix.hip); the Q update adds
+ *   partial sums over chunks of TPG_ADMIX_CHUNK_LOCI loci in ascending chunk order.
+ * Accuracy, u = 2^-52, FP64 throughout, against the exact rational value of one step from the same (Q, F).  Every sum is a sum
+ *   of non-negative terms, so each rounding is a relative error of at most u / 2 <= u of the running value and they add up
+ *   (first order; the counts below are roundings along the longest path, whatever the order of a sum):
+ *     p: K (one per fused term);  pbar: K + 1 (1 - f);  w1: K + 1;  w0: K + 2
+ *     sum_i q w1: fused terms and N additions along any path, N + K + 1;  a: + 1;  b: N + K + 2, + 2 (1 - f, the product)
+ *     f' = a / (a + b): (N + K + 2) + (N + K + 5) + 1 = 2 N + 2 K + 8              <= (2 N + 4 K + 40) u f'   (unclamped)
+ *     sum_j [..]: terms K + 2 and K + 4, at most 2 T_i additions along any path; q / (2 T_i) and the product: 2
+ *     q': 2 T_i + K + 6                                                             <= (2 T_i + 2 K + 16) u q'
+ *     l, T typed entries: the argument p^g pbar^(2-g) carries g K + (2 - g)(K + 1) + 1 <= 2 K + 3 roundings, which moves ln by
+ *     that many u (absolute); ln itself is good to 1 ulp of the term; T additions:  |dl| <= u [ (2 T + 2) |l| + 2 (K + 4) T ]
+ *   An exact value within its bound of eps or 1 - eps may come back clamped or not.
+ * Errors.  K < 1, K > TPG_ADMIX_MAX_K, max_iter < 0, tol negative or NaN, an entry of ploidy other than 2 (NULL: all diploid),
+ *   a view with N = 0 or M = 0: TPG_EINVAL.  Q and P are written at the very end only: after an error they are untouched. */
+#define TPG_ADMIX_EPS 1e-5
+#define TPG_ADMIX_MAX_K 32
+/* loci per partial sum of the Q update (results do not depend on launch geometry; the tests put m around it) */
+#define TPG_ADMIX_CHUNK_LOCI 4096
+typedef struct tpg_admix_params {
+  int32_t max_iter;  /* 1000 */
+  double tol;        /* 1e-4 */
+  int32_t update_q;  /* 1 */
+  int32_t update_f;  /* 1 */
+  uint64_t seed;     /* 0 */
+} tpg_admix_params;
+int tpg_admix_params_default(tpg_admix_params* p);
+int64_t tpg_admix_chunk_loci(void);
+/* Q: N x K, P: M x K (P[j + k M] = f(k,j)), column-major doubles, host or device memory; q0 / f0 may be NULL (seeded start);
+ * params NULL = the defaults; loglik_trace has room for max_iter + 1 doubles or is NULL; loglik, loglik_trace, n_iter and
+ * converged are host memory and may each be NULL */
+int tpg_admix_em(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, const tpg_admix_params* params, const double* q0,
+                 const double* f0, double* Q, double* P, double* loglik, double* loglik_trace, int32_t* n_iter,
+                 int32_t* converged);
+/* l(Q, F) alone for a caller's own (Q, P), taken as given (no normalisation, no clamp): one likelihood-only pass */
+int tpg_admix_loglik(tpg_ctx* ctx, const tpg_view* v, int K, const double* Q, const double* P, double* loglik);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

@@ -1255,6 +1255,60 @@ SEXP _tidypopgen_tpg_f2_blocks(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds,
   return out;
 }
 
+/* ---- admixture ---------------------------------------------------------------------------------------------------- */
+
+#pragma weak tpg_admix_em
+#pragma weak tpg_admix_params_default
+
+/* tpg_admixture(BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0): the PLINK export, the outside `admixture` run and the
+ * reading back of its .Q / .P files (R/gt_admixture.R:86-236) as one call of the EM of include/tpg.h "admixture", for one k
+ * and one run.  seed = a double vector of length 1 holding a whole number in [0, 2^53]; q0 (N x k) / p0 (M x k) = a start, or
+ * NULL for the seeded one.  -> list(Q: N x k, P: M x k (frequency of the counted allele), loglik, n_iter, converged) */
+SEXP _tidypopgen_tpg_admixture(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0, SEXP p0) {
+  TPG_NEEDS(tpg_admix_em);
+  const int K = Rf_asInteger(k);
+  if (K == NA_INTEGER || K < 1) Rf_error("tidypopgen (GPU): k must be a positive integer");
+  if (TYPEOF(seed) != REALSXP || XLENGTH(seed) != 1) Rf_error("tidypopgen (GPU): seed must be a double vector of length 1");
+  const double sd = REAL(seed)[0];
+  if (!(sd >= 0 && sd <= 9007199254740992.0) || sd != floor(sd))
+    Rf_error("tidypopgen (GPU): seed must be a whole number in [0, 2^53]");
+  const int mi = Rf_asInteger(max_iter);
+  if (mi == NA_INTEGER || mi < 0) Rf_error("tidypopgen (GPU): max_iter must be a non-negative integer");
+  if ((TYPEOF(tol) != REALSXP && TYPEOF(tol) != INTSXP) || XLENGTH(tol) != 1) Rf_error("tidypopgen (GPU): tol must be one number");
+  SEXP ts = PROTECT(as_real(tol));
+  const double tl = REAL(ts)[0];
+  UNPROTECT(1);
+  if (!(tl >= 0)) Rf_error("tidypopgen (GPU): tol must be a non-negative number");
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  const R_xlen_t n = XLENGTH(ri), m = XLENGTH(ci);
+  if (n > INT_MAX || m > INT_MAX) Rf_error("tidypopgen (GPU): too many rows or columns for an R matrix");
+  SEXP qs = PROTECT(q0 == R_NilValue ? R_NilValue : Rf_coerceVector(q0, REALSXP));
+  SEXP ps = PROTECT(p0 == R_NilValue ? R_NilValue : Rf_coerceVector(p0, REALSXP));
+  if (qs != R_NilValue && XLENGTH(qs) != n * (R_xlen_t)K) Rf_error("tidypopgen (GPU): q0 must be length(rowInd) x k");
+  if (ps != R_NilValue && XLENGTH(ps) != m * (R_xlen_t)K) Rf_error("tidypopgen (GPU): p0 must be length(colInd) x k");
+  SEXP vals[5];
+  vals[0] = PROTECT(Rf_allocMatrix(REALSXP, (int)n, K));
+  vals[1] = PROTECT(Rf_allocMatrix(REALSXP, (int)m, K));
+  vals[2] = PROTECT(Rf_allocVector(REALSXP, 1));
+  vals[3] = PROTECT(Rf_allocVector(INTSXP, 1));
+  vals[4] = PROTECT(Rf_allocVector(LGLSXP, 1));
+  static const char* names[5] = {"Q", "P", "loglik", "n_iter", "converged"};
+  SEXP out = PROTECT(named_list(5, names, vals));
+  tpg_admix_params P;
+  tpg_admix_params_default(&P);
+  P.max_iter = mi;
+  P.tol = tl;
+  P.seed = (uint64_t)sd;
+  int32_t nit = 0, conv = 0;
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_admix_em(ctx(), v, NULL, K, &P, qs == R_NilValue ? NULL : REAL(qs), ps == R_NilValue ? NULL : REAL(ps),
+                             REAL(vals[0]), REAL(vals[1]), REAL(vals[2]), NULL, &nit, &conv));
+  INTEGER(vals[3])[0] = nit;
+  LOGICAL(vals[4])[0] = conv != 0;
+  UNPROTECT(10);
+  return out;
+}
+
 /* ---- registration ------------------------------------------------------------------------------------------------
  * Same names and arities as the reference's table (src/RcppExports.cpp:348-371).  These rows replace the rows of the
  * same name there, and so do the three HWE rows of tpg_rshim_entries_hwe[] below; the other rows of that table
@@ -1322,18 +1376,24 @@ const R_CallMethodDef tpg_rshim_entries_f2[] = {
     {"_tidypopgen_tpg_f2_blocks", (DL_FUNC)&_tidypopgen_tpg_f2_blocks, 9},
     {NULL, NULL, 0}};
 
+/* Admixture, in a table of its own: the reference runs an outside program, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_admix[] = {
+    {"_tidypopgen_tpg_admixture", (DL_FUNC)&_tidypopgen_tpg_admixture, 9},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the seven tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the eight tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
                              sizeof(tpg_rshim_entries_ld) / sizeof(tpg_rshim_entries_ld[0]) +
                              sizeof(tpg_rshim_entries_roh) / sizeof(tpg_rshim_entries_roh[0]) +
                              sizeof(tpg_rshim_entries_tajima) / sizeof(tpg_rshim_entries_tajima[0]) +
-                             sizeof(tpg_rshim_entries_f2) / sizeof(tpg_rshim_entries_f2[0])];
+                             sizeof(tpg_rshim_entries_f2) / sizeof(tpg_rshim_entries_f2[0]) +
+                             sizeof(tpg_rshim_entries_admix) / sizeof(tpg_rshim_entries_admix[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1342,6 +1402,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_roh; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_tajima; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_f2; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_admix; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

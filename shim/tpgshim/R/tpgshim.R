@@ -155,6 +155,21 @@ tpg_f2_blocks <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigst
         lo, hi, params)
 }
 
+# Ancestry proportions by EM on the GPU for one k and one run (the PLINK export, the outside `admixture` program and the reading
+# back of its .Q / .P files of R/gt_admixture.R:86-236; include/tpg.h "admixture" is the definition).  seed: one whole number;
+# q0 / p0: a start (individuals x k, loci x k) or NULL for the seeded one.  Returns the gt_admix list of the reference for that
+# run (k, Q, P, loglik), with n_iter and converged beside it.  P is the frequency of the counted (alt) allele.  crossval,
+# conda_env and outdir have no counterpart.
+gt_admixture_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), k, seed = 0,
+                             max_iter = 1000L, tol = 1e-4, q0 = NULL, p0 = NULL) {
+  res <- .Call(`_tidypopgen_tpg_admixture`, X, as.integer(ind.row), as.integer(ind.col), as.integer(k), as.numeric(seed),
+               as.integer(max_iter), as.numeric(tol), q0, p0)
+  adm_list <- list(k = as.integer(k), Q = list(res$Q), P = list(res$P), loglik = res$loglik, n_iter = res$n_iter,
+                   converged = res$converged)
+  class(adm_list) <- c("gt_admix", "list")
+  adm_list
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

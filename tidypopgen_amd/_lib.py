@@ -105,6 +105,7 @@ SYMBOLS = [
     "tpg_roh_locus_counts", "tpg_roh_free",
     "tpg_tajimas_d_from_sums", "tpg_tajima_chunk_loci", "tpg_pop_tajimas_d", "tpg_windows_pop_tajimas_d",
     "tpg_f2_params_default", "tpg_f2_chunk_loci", "tpg_f2_blocks", "tpg_f4_jackknife",
+    "tpg_admix_params_default", "tpg_admix_chunk_loci", "tpg_admix_em", "tpg_admix_loglik",
 ]
 
 
@@ -161,6 +162,12 @@ class F2Params(C.Structure):
                 ("poly_only", C.c_int32), ("apply_corr", C.c_int32), ("keep", vp)]
 
 
+class AdmixParams(C.Structure):
+    """tpg_admix_params of include/tpg.h, field for field"""
+    _fields_ = [("max_iter", C.c_int32), ("tol", C.c_double), ("update_q", C.c_int32), ("update_f", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class StreamReport(C.Structure):
     """tpg_stream_report of include/tpg.h"""
     _fields_ = [
@@ -208,6 +215,12 @@ if hasattr(lib, "tpg_f2_blocks"):
     lib.tpg_f2_chunk_loci.argtypes = []
     lib.tpg_f2_blocks.argtypes = [vp, vp, vp, C.c_int, vp, C.POINTER(F2Params), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     lib.tpg_f4_jackknife.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
+if hasattr(lib, "tpg_admix_em"):
+    lib.tpg_admix_params_default.argtypes = [C.POINTER(AdmixParams)]
+    lib.tpg_admix_chunk_loci.restype = C.c_int64
+    lib.tpg_admix_chunk_loci.argtypes = []
+    lib.tpg_admix_em.argtypes = [vp, vp, vp, C.c_int, C.POINTER(AdmixParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tpg_admix_loglik.argtypes = [vp, vp, C.c_int, vp, vp, vp]
 lib.tpg_stream_close.restype = None
 lib.tpg_stream_close.argtypes = [vp]
 lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]

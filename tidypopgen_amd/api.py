@@ -1644,6 +1644,83 @@ def f3_from_f2_blocks(f2, block_lengths, triples) -> dict:
     return f4_from_f2_blocks(f2, block_lengths, np.stack([t[:, 0], t[:, 1], t[:, 0], t[:, 2]], axis=1))
 
 
+# include/tpg.h "admixture": loci per partial sum of the Q update (results do not depend on launch geometry)
+ADMIX_CHUNK_LOCI = int(lib.tpg_admix_chunk_loci()) if hasattr(lib, "tpg_admix_chunk_loci") else 0
+
+
+def _admix_mat(x, rows: int, K: int, name: str):
+    """a start / state matrix for the C ABI: a numpy (rows, K) array -> column-major doubles; an int -> a device pointer"""
+    if x is None or isinstance(x, (int, np.integer)):
+        return x
+    a = np.asfortranarray(x, dtype=np.float64)
+    if a.shape != (rows, K):
+        raise ValueError(f"{name} must be {rows} x {K}, not {a.shape}")
+    return a
+
+
+def admix_em(v: View, K: int, Q0=None, F0=None, seed: int = 0, max_iter: int = 1000, tol: float = 1e-4, update_q: bool = True,
+             update_f: bool = True, return_trace: bool = False, ploidy=None) -> dict:
+    """tpg_admix_em (include/tpg.h "admixture"): maximum-likelihood ancestry proportions of a resident view by EM.  Q0 (n x K)
+    and F0 (m x K, the shape of a .P file) are numpy arrays or device pointers (int); None draws that half of the start from
+    `seed`.  -> dict(Q (n x K), P (m x K, frequency of the counted allele), loglik, n_iter, converged[, trace = l(0 .. n_iter)])"""
+    K = int(K)
+    q0, f0 = _admix_mat(Q0, v.n, K, "Q0"), _admix_mat(F0, v.m, K, "F0")
+    pr = _lib.AdmixParams(int(max_iter), float(tol), int(bool(update_q)), int(bool(update_f)), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    Q, P = np.zeros((v.n, max(K, 1)), order="F"), np.zeros((v.m, max(K, 1)), order="F")  # K < 1 is the library's to refuse
+    trace = np.full(max(int(max_iter), 0) + 1, np.nan)
+    ll, nit, conv = C.c_double(), C.c_int32(), C.c_int32()
+    pl = _f64(ploidy)
+    check(lib.tpg_admix_em(v.ctx.h, v.h, _ptr(pl), C.c_int(K), C.byref(pr), _ptr(q0), _ptr(f0), _ptr(Q), _ptr(P), C.byref(ll),
+                           _ptr(trace), C.byref(nit), C.byref(conv)))
+    out = dict(Q=Q, P=P, loglik=ll.value, n_iter=int(nit.value), converged=bool(conv.value))
+    if return_trace:
+        out["trace"] = trace[: nit.value + 1].copy()
+    return out
+
+
+def admix_loglik(v: View, Q, P) -> float:
+    """tpg_admix_loglik: l(Q, P) of the caller's own state, taken as given (no normalisation, no clamp)"""
+    if isinstance(Q, (int, np.integer)) or isinstance(P, (int, np.integer)):
+        raise ValueError("admix_loglik takes numpy arrays (K is read from their shape)")
+    q = np.asfortranarray(Q, dtype=np.float64)
+    K = q.shape[1] if q.ndim == 2 else 0
+    q, p = _admix_mat(q, v.n, K, "Q"), _admix_mat(P, v.m, K, "P")
+    ll = C.c_double()
+    check(lib.tpg_admix_loglik(v.ctx.h, v.h, C.c_int(K), _ptr(q), _ptr(p), C.byref(ll)))
+    return ll.value
+
+
+def gt_admixture(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, seed=None, max_iter: int = 1000,
+                 tol: float = 1e-4) -> dict:
+    """R/gt_admixture.R:62-236 with the EM of include/tpg.h "admixture" in place of the outside binary: every k of `k` (a
+    scalar or a list) is run n_runs times on one resident view.  seed has n_runs entries (repeated for every k) or
+    n_runs * len(k), one per run in the order of the result (k by k); None: 0, 1, ... in that order.
+    -> a gt_admix-shaped dict: k (one entry per run), Q, P, loglik as lists, plus n_iter and converged.
+    crossval, conda_env and outdir of the reference have no counterpart here: there is no cross-validation, no
+    outside program and no file; `log` is absent for the same reason.  P is the frequency of the counted allele."""
+    if k is None:
+        raise ValueError("k is required")
+    ks = [int(x) for x in np.atleast_1d(k)]
+    n_runs = int(n_runs)
+    if seed is not None:
+        seed = [int(s) for s in np.atleast_1d(seed)]
+        if len(seed) != n_runs and len(seed) != n_runs * len(ks):
+            raise ValueError("'seed' should be a vector of length 'n_runs' OR 'n_runs' * length(k)")
+        if len(seed) == n_runs:
+            seed = seed * len(ks)
+    else:
+        seed = list(range(n_runs * len(ks)))
+    v = View(X, ind_row, ind_col)
+    out = dict(k=[], Q=[], P=[], loglik=[], n_iter=[], converged=[])
+    for a, kk in enumerate(ks):
+        for b in range(n_runs):
+            r = admix_em(v, kk, seed=seed[a * n_runs + b], max_iter=max_iter, tol=tol)
+            out["k"].append(kk)
+            for name in ("Q", "P", "loglik", "n_iter", "converged"):
+                out[name].append(r[name])
+    return out
+
+
 def _pbs_triplets(ngroups):
     """utils::combn(levels, 3) order, with the Fst columns of (p1.p2, p1.p3, p2.p3) in combn(levels, 2) order"""
     pairs = combn2(ngroups)  # (2, P), 1-based

@@ -1,0 +1,487 @@
+// admix.hip -- maximum-likelihood ancestry proportions by EM (include/tpg.h "admixture").
+//
+// ADMIXTURE is not among the reference's sources (R/gt_admixture.R:86-100 exports the panel, runs an outside binary and reads
+// its .Q / .P files back), so the model, the EM step and the stop rule are the ones include/tpg.h defines.
+//
+// The state lives on the device as Qd[i * KT + k] and Fd[j * KT + k]: a row per individual / locus, padded from K to the
+// dispatch width KT in {1, 2, 3, 4, 8, 16, 32} with q = 0 and f = 0.5.  A padded term adds q f = +0 to p and to p-bar, so the
+// sums over KT equal the sums over K bit for bit and the hot loops carry no bound check on k.
+//
+// One iteration is two sweeps of the packed panel, both of the same shape: a workgroup of four waves owns 32 "row" entities
+// (lane r and r + 32 share one) and walks the other axis in blocks of 128, whose state rows are staged through LDS (128 KT
+// doubles; every lane of a half-wave reads the same row: a broadcast).  Wave w takes dword w of each 16-byte lane fragment
+// (common.h: 16 codes), so a thread sees the entities 128 b + 32 w + 16 h + e, e = 0 .. 15, of every block b in ascending
+// order.  p and p-bar are recomputed from Q and F for every typed entry: K fused multiply-adds each.
+//   F sweep  rows = the 32 loci of tile lt of L, walked axis = all individuals; registers f, 1 - f, A, B (4 KT doubles);
+//            the same pass adds ln(p^g pbar^(2 - g)) per entry: the likelihood of the OLD state (UPD = false: that alone).
+//   Q sweep  rows = the 32 individuals of row tile rt of T, walked axis = one chunk of TPG_ADMIX_CHUNK_LOCI loci; registers q, S
+//            (2 KT doubles); partials to part[chunk][i][k], added in ascending chunk order by admix_q_combine.
+// Every sum has a fixed shape: a thread's entries in ascending order, lane r + lane r + 32, then the four waves in order (and
+// for the likelihood a butterfly over the wave, the waves in order, the tiles by a one-workgroup kernel).  No atomics on
+// floating point; the only atomic is the integer OR of the Q0 / F0 validation flag.
+#include "common.h"
+#include "synth_common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int ADM_CHUNK = TPG_ADMIX_CHUNK_LOCI;
+static_assert(ADM_CHUNK % 128 == 0, "a chunk is whole blocks of T");
+constexpr uint64_t ADM_F_SALT = 0xF0F0F0F0F0F0F0F0ull;
+
+// u(h) of include/tpg.h: the addition rounds to nearest even once h >> 11 reaches 2^52, the same in every IEEE double
+__host__ __device__ inline double admix_u(uint64_t h) { return ((double)(h >> 11) + 0.5) * 0x1p-53; }
+
+__device__ __forceinline__ double admix_clamp(double f) {
+  return f < TPG_ADMIX_EPS ? TPG_ADMIX_EPS : f > 1.0 - TPG_ADMIX_EPS ? 1.0 - TPG_ADMIX_EPS : f;
+}
+__device__ __forceinline__ bool admix_finite(double x) { return fabs(x) <= 1.79769313486231570815e308; }
+
+// element e of a packed dword (common.h: e = 4 k + b at bits 8 b + 2 k)
+__device__ __forceinline__ int admix_code(uint32_t w, int e) { return (int)((w >> (8 * (e & 3) + 2 * (e >> 2))) & 3u); }
+
+// ---- start, validation, output ---------------------------------------------------------------------------------------
+__global__ void admix_seed_q_kernel(double* __restrict__ Qd, int64_t n, int K, int KT, uint64_t seed) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = tpg_mix64(seed ^ tpg_mix64((uint64_t)i));
+  double s = 0;
+  for (int k = 0; k < K; k++) s += admix_u(tpg_mix64(key ^ tpg_mix64((uint64_t)k)));
+  for (int k = 0; k < KT; k++) Qd[i * KT + k] = k < K ? admix_u(tpg_mix64(key ^ tpg_mix64((uint64_t)k))) / s : 0.0;
+}
+
+__global__ void admix_seed_f_kernel(double* __restrict__ Fd, int64_t m, int K, int KT, uint64_t seed) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const uint64_t key = tpg_mix64((seed ^ ADM_F_SALT) ^ tpg_mix64((uint64_t)j));
+  for (int k = 0; k < KT; k++) Fd[j * KT + k] = k < K ? 0.1 + 0.8 * admix_u(tpg_mix64(key ^ tpg_mix64((uint64_t)k))) : 0.5;
+}
+
+// q0 (n x K column-major) -> Qd, each row divided by its sum (ascending k); normalise = false: as given (tpg_admix_loglik).
+// bit 0 of *flag: an entry that is not finite or not positive
+__global__ void admix_load_q_kernel(const double* __restrict__ q0, double* __restrict__ Qd, int64_t n, int K, int KT, bool normalise,
+                                    int32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s = 0;
+  bool bad = false;
+  for (int k = 0; k < K; k++) {
+    const double x = q0[i + (int64_t)k * n];
+    bad |= !(admix_finite(x) && x > 0.0);
+    s += x;
+  }
+  if (normalise && bad) atomicOr(flag, 1);
+  for (int k = 0; k < KT; k++) {
+    const double x = k < K ? q0[i + (int64_t)k * n] : 0.0;
+    Qd[i * KT + k] = normalise && k < K ? x / s : x;
+  }
+}
+
+// f0 (m x K column-major) -> Fd, clamped; clamp = false: as given.  bit 1 of *flag: an entry that is not finite
+__global__ void admix_load_f_kernel(const double* __restrict__ f0, double* __restrict__ Fd, int64_t m, int K, int KT, bool clamp,
+                                    int32_t* __restrict__ flag) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  bool bad = false;
+  for (int k = 0; k < KT; k++) {
+    double x = 0.5;
+    if (k < K) {
+      x = f0[j + (int64_t)k * m];
+      bad |= !admix_finite(x);
+      if (clamp) x = admix_clamp(x);
+    }
+    Fd[j * KT + k] = x;
+  }
+  if (clamp && bad) atomicOr(flag, 2);
+}
+
+// rows x K column-major out of the padded state
+__global__ void admix_store_kernel(const double* __restrict__ Xd, int64_t rows, int K, int KT, double* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * K) return;
+  const int64_t i = idx % rows, k = idx / rows;
+  out[idx] = Xd[i * KT + k];
+}
+
+// ---- the two sweeps ----------------------------------------------------------------------------------------------------
+// rows 128 b .. 128 b + 127 of a padded state (rows beyond `rows`: `fill`) into LDS, contiguous 8-byte loads
+template <int KT>
+__device__ __forceinline__ void admix_stage(double* __restrict__ stage, const double* __restrict__ Xd, int64_t b, int64_t rows,
+                                            double fill) {
+  const int64_t i0 = b * 128;
+  for (int idx = threadIdx.x; idx < 128 * KT; idx += 256) stage[idx] = i0 + idx / KT < rows ? Xd[i0 * KT + idx] : fill;
+}
+
+// the waves of a workgroup in order: x[] of lanes 0 .. 31 of wave 0 becomes ((w0 + w1) + w2) + w3, cnt likewise.  LDS: red holds
+// NV x 32 doubles, value-major (lane r at red[v * 32 + r]: conflict-free)
+template <int NV>
+__device__ __forceinline__ void admix_wave_order_sum(double (&x)[NV], int& cnt, double* __restrict__ red, int* __restrict__ cnts, int w,
+                                                     int r, int h) {
+  __syncthreads();  // the staging area is free
+  for (int t = 1; t < 4; t++) {
+    if (w == t && h == 0) {
+#pragma unroll
+      for (int v = 0; v < NV; v++) red[v * 32 + r] = x[v];
+      cnts[r] = cnt;
+    }
+    __syncthreads();
+    if (w == 0 && h == 0) {
+#pragma unroll
+      for (int v = 0; v < NV; v++) x[v] += red[v * 32 + r];
+      cnt += cnts[r];
+    }
+    __syncthreads();
+  }
+}
+
+// F sweep: one workgroup per tile of 32 loci.  UPD: Fn receives f' (Fn != Fd); ll_part[lt] = the tile's share of l(Qd, Fd)
+template <int KT, bool UPD>
+__global__ __launch_bounds__(256) void admix_f_sweep_kernel(const uint32_t* __restrict__ L, int64_t Qb, int64_t n, int64_t m, int K,
+                                                            const double* __restrict__ Qd, const double* __restrict__ Fd,
+                                                            double* __restrict__ Fn, double* __restrict__ ll_part) {
+  constexpr int NA = UPD ? KT : 1;
+  __shared__ double stage[128 * KT];
+  __shared__ double wll[4];
+  __shared__ int cnts[32];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t lt = blockIdx.x, j = lt * 32 + r;
+  double f[KT], fb[KT], AB[2 * NA];
+#pragma unroll
+  for (int k = 0; k < KT; k++) {
+    f[k] = j < m ? Fd[j * KT + k] : 0.5;
+    fb[k] = 1.0 - f[k];
+  }
+#pragma unroll
+  for (int v = 0; v < 2 * NA; v++) AB[v] = 0.0;
+  double ll = 0.0;
+  int cnt = 0;
+  for (int64_t q = 0; q < Qb; q++) {
+    __syncthreads();
+    admix_stage<KT>(stage, Qd, q, n, 0.0);
+    __syncthreads();
+    const uint32_t wd = L[((lt * Qb + q) * 64 + lane) * 4 + w];
+#pragma unroll 2
+    for (int e = 0; e < 16; e++) {
+      const int g = admix_code(wd, e);
+      if (g == 3) continue;
+      const double* __restrict__ qs = stage + (32 * w + 16 * h + e) * KT;
+      double p = 0.0, pb = 0.0;
+#pragma unroll
+      for (int k = 0; k < KT; k++) {
+        p = fma(qs[k], f[k], p);
+        pb = fma(qs[k], fb[k], pb);
+      }
+      cnt++;
+      ll += log(g == 0 ? pb * pb : g == 1 ? p * pb : p * p);
+      if constexpr (UPD) {
+        const double w1 = (double)g / p, w0 = (double)(2 - g) / pb;
+#pragma unroll
+        for (int k = 0; k < KT; k++) {
+          AB[k] = fma(qs[k], w1, AB[k]);
+          AB[NA + k] = fma(qs[k], w0, AB[NA + k]);
+        }
+      }
+    }
+  }
+  // the likelihood: butterfly over the wave, the waves in order
+  for (int o = 32; o > 0; o >>= 1) ll += __shfl_xor(ll, o);
+  if (lane == 0) wll[w] = ll;
+  if constexpr (UPD) {
+#pragma unroll
+    for (int v = 0; v < 2 * NA; v++) AB[v] += __shfl_xor(AB[v], 32);
+    cnt += __shfl_xor(cnt, 32);
+    admix_wave_order_sum<2 * NA>(AB, cnt, stage, cnts, w, r, h);
+  } else {
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) ll_part[lt] = ((wll[0] + wll[1]) + wll[2]) + wll[3];
+  if constexpr (UPD) {
+    if (w != 0 || h != 0 || j >= m) return;
+#pragma unroll
+    for (int k = 0; k < KT; k++) {
+      double fn = k < K ? f[k] : 0.5;
+      if (k < K && cnt > 0) {
+        const double a = f[k] * AB[k], b = fb[k] * AB[NA + k], s = a + b;
+        if (s > 0.0) fn = admix_clamp(a / s);  // s = 0: every typed individual has q(i, k) = 0; the locus keeps f(k, j)
+      }
+      Fn[j * KT + k] = fn;
+    }
+  }
+}
+
+// Q sweep: workgroup (rt, c) = 32 individuals x one chunk of loci -> part[(c n + i) KT + k], cpart[c n + i] (typed loci)
+template <int KT>
+__global__ __launch_bounds__(256) void admix_q_sweep_kernel(const uint32_t* __restrict__ T, int64_t KG, int64_t n, int64_t m,
+                                                            const double* __restrict__ Qd, const double* __restrict__ Fd,
+                                                            double* __restrict__ part, int32_t* __restrict__ cpart) {
+  __shared__ double stage[128 * KT];
+  __shared__ int cnts[32];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t rt = blockIdx.x, c = blockIdx.y, i = rt * 32 + r;
+  double qv[KT], S[KT];
+#pragma unroll
+  for (int k = 0; k < KT; k++) {
+    qv[k] = i < n ? Qd[i * KT + k] : 0.0;
+    S[k] = 0.0;
+  }
+  int cnt = 0;
+  const int64_t kg0 = c * (ADM_CHUNK / 128), kg1 = kg0 + ADM_CHUNK / 128 < KG ? kg0 + ADM_CHUNK / 128 : KG;
+  for (int64_t kg = kg0; kg < kg1; kg++) {
+    __syncthreads();
+    admix_stage<KT>(stage, Fd, kg, m, 0.5);
+    __syncthreads();
+    const uint32_t wd = T[((rt * KG + kg) * 64 + lane) * 4 + w];
+#pragma unroll 2
+    for (int e = 0; e < 16; e++) {
+      const int g = admix_code(wd, e);
+      if (g == 3) continue;
+      const double* __restrict__ fs = stage + (32 * w + 16 * h + e) * KT;
+      double p = 0.0, pb = 0.0;
+#pragma unroll
+      for (int k = 0; k < KT; k++) {
+        p = fma(qv[k], fs[k], p);
+        pb = fma(qv[k], 1.0 - fs[k], pb);
+      }
+      cnt++;
+      const double w1 = (double)g / p, w0 = (double)(2 - g) / pb;
+#pragma unroll
+      for (int k = 0; k < KT; k++) S[k] = fma(1.0 - fs[k], w0, fma(fs[k], w1, S[k]));
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < KT; k++) S[k] += __shfl_xor(S[k], 32);
+  cnt += __shfl_xor(cnt, 32);
+  admix_wave_order_sum<KT>(S, cnt, stage, cnts, w, r, h);
+  if (w != 0 || h != 0 || i >= n) return;
+  const int64_t o = c * n + i;
+#pragma unroll
+  for (int k = 0; k < KT; k++) part[o * KT + k] = S[k];
+  cpart[o] = cnt;
+}
+
+// q'(i, k) = (q / (2 T_i)) * (the chunks' partials added in ascending order); T_i = 0 keeps the row
+__global__ void admix_q_combine_kernel(const double* __restrict__ part, const int32_t* __restrict__ cpart, int64_t nchunks, int64_t n,
+                                       int K, int KT, const double* __restrict__ Qd, double* __restrict__ Qn) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * KT) return;
+  const int64_t i = idx / KT;
+  const int k = (int)(idx % KT);
+  double q = 0.0;
+  if (k < K) {
+    double s = 0.0;
+    int64_t t = 0;
+    for (int64_t c = 0; c < nchunks; c++) {
+      s += part[(c * n + i) * KT + k];
+      t += cpart[c * n + i];
+    }
+    q = Qd[idx];
+    if (t > 0) q = (q / (2.0 * (double)t)) * s;
+  }
+  Qn[idx] = q;
+}
+
+// the tiles' shares of the likelihood: thread t adds the tiles t, t + 256, ...; butterfly; the four waves in order
+__global__ __launch_bounds__(256) void admix_ll_sum_kernel(const double* __restrict__ ll_part, int64_t ntiles, double* __restrict__ out) {
+  __shared__ double wll[4];
+  double s = 0.0;
+  for (int64_t t = threadIdx.x; t < ntiles; t += 256) s += ll_part[t];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) wll[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = ((wll[0] + wll[1]) + wll[2]) + wll[3];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+int admix_kt(int K) { return K <= 4 ? K : K <= 8 ? 8 : K <= 16 ? 16 : 32; }
+
+#define ADM_DISPATCH(kt, CALL) \
+  switch (kt) {                \
+    case 1: CALL(1); break;    \
+    case 2: CALL(2); break;    \
+    case 3: CALL(3); break;    \
+    case 4: CALL(4); break;    \
+    case 8: CALL(8); break;    \
+    case 16: CALL(16); break;  \
+    default: CALL(32); break;  \
+  }
+
+struct AdmixRun {
+  tpg_ctx* ctx;
+  const tpg_view* v;
+  int K, KT;
+  int64_t n, m, n_lt, n_rt, nchunks;
+  DevArena sc;
+  double *Q[2] = {}, *F[2] = {}, *part = nullptr, *ll_part = nullptr, *trace = nullptr;
+  int32_t *cpart = nullptr, *flag = nullptr;
+
+  int init(tpg_ctx* c, const tpg_view* view, int k, bool need_q_sweep, bool need_f_next, int64_t trace_len) {
+    ctx = c; v = view; K = k; KT = admix_kt(k);
+    n = v->n; m = v->m;
+    n_lt = ceil_div(m, 32); n_rt = ceil_div(n, 32); nchunks = ceil_div(m, ADM_CHUNK);
+    TPG_REQUIRE(n_lt <= 0x7FFFFFFF && n_rt <= 0x7FFFFFFF && nchunks <= 65535, TPG_EUNSUPPORTED, "admixture on a view of %lld x %lld",
+                (long long)n, (long long)m);
+    TPG_TRY(sc.get(&Q[0], (size_t)n * KT));
+    TPG_TRY(sc.get(&F[0], (size_t)m * KT));
+    TPG_TRY(sc.get(&ll_part, (size_t)n_lt));
+    TPG_TRY(sc.get(&trace, (size_t)trace_len));
+    TPG_TRY(sc.get(&flag, (size_t)1));
+    if (need_f_next) TPG_TRY(sc.get(&F[1], (size_t)m * KT));
+    if (need_q_sweep) {
+      TPG_TRY(tpg_view_need_T(ctx, v));
+      TPG_TRY(sc.get(&Q[1], (size_t)n * KT));
+      TPG_TRY(sc.get(&part, (size_t)nchunks * n * KT));
+      TPG_TRY(sc.get(&cpart, (size_t)nchunks * n));
+    }
+    return TPG_OK;
+  }
+
+  // l(Q[cur], F[cur]) -> trace[slot]; update: F[1 - cur] receives f' as well
+  int f_sweep(int cur_q, int cur_f, bool update, int64_t slot) {
+#define ADM_F(KT_)                                                                                                                  \
+  do {                                                                                                                              \
+    auto k_upd = admix_f_sweep_kernel<KT_, true>;                                                                                   \
+    auto k_ll = admix_f_sweep_kernel<KT_, false>;                                                                                   \
+    if (update)                                                                                                                     \
+      TPG_LAUNCH(ctx, "admix_f_sweep", k_upd, dim3((unsigned)n_lt), dim3(256), 0, (const uint32_t*)v->L, \
+                 v->Q, n, m, K, (const double*)Q[cur_q], (const double*)F[cur_f], F[1 - cur_f], ll_part);                           \
+    else                                                                                                                            \
+      TPG_LAUNCH(ctx, "admix_loglik", k_ll, dim3((unsigned)n_lt), dim3(256), 0, (const uint32_t*)v->L, \
+                 v->Q, n, m, K, (const double*)Q[cur_q], (const double*)F[cur_f], (double*)nullptr, ll_part);                       \
+  } while (0)
+    ADM_DISPATCH(KT, ADM_F);
+#undef ADM_F
+    TPG_LAUNCH(ctx, "admix_ll_sum", admix_ll_sum_kernel, dim3(1), dim3(256), 0, (const double*)ll_part, n_lt, trace + slot);
+    TPG_CHECK_LAUNCH();
+    return TPG_OK;
+  }
+
+  int q_sweep(int cur_q, int cur_f) {
+#define ADM_Q(KT_)                                                                                                               \
+  TPG_LAUNCH(ctx, "admix_q_sweep", admix_q_sweep_kernel<KT_>, dim3((unsigned)n_rt, (unsigned)nchunks), dim3(256), 0,              \
+             (const uint32_t*)v->T, v->KG, n, m, (const double*)Q[cur_q], (const double*)F[cur_f], part, cpart)
+    ADM_DISPATCH(KT, ADM_Q);
+#undef ADM_Q
+    TPG_LAUNCH(ctx, "admix_q_combine", admix_q_combine_kernel, dim3((unsigned)ceil_div(n * KT, 256)), dim3(256), 0, (const double*)part,
+               (const int32_t*)cpart, nchunks, n, K, KT, (const double*)Q[cur_q], Q[1 - cur_q]);
+    TPG_CHECK_LAUNCH();
+    return TPG_OK;
+  }
+};
+
+int admix_check_view(const tpg_view* v, int K) {
+  TPG_REQUIRE(K >= 1 && K <= TPG_ADMIX_MAX_K, TPG_EINVAL, "K = %d out of [1, %d]", K, TPG_ADMIX_MAX_K);
+  TPG_REQUIRE(v->n > 0 && v->m > 0, TPG_EINVAL, "admixture needs at least one individual and one locus (view of %lld x %lld)",
+              (long long)v->n, (long long)v->m);
+  return TPG_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t tpg_admix_chunk_loci(void) { return ADM_CHUNK; }
+
+extern "C" int tpg_admix_params_default(tpg_admix_params* p) {
+  TPG_REQUIRE(p, TPG_EINVAL, "null argument");
+  p->max_iter = 1000;
+  p->tol = 1e-4;
+  p->update_q = 1;
+  p->update_f = 1;
+  p->seed = 0;
+  return TPG_OK;
+}
+
+extern "C" int tpg_admix_em(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, const tpg_admix_params* params,
+                            const double* q0, const double* f0, double* Q, double* P, double* loglik, double* loglik_trace,
+                            int32_t* n_iter, int32_t* converged) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && v && Q && P, TPG_EINVAL, "null argument");
+  tpg_admix_params pr;
+  tpg_admix_params_default(&pr);
+  if (params) pr = *params;
+  TPG_TRY(admix_check_view(v, K));
+  TPG_REQUIRE(pr.max_iter >= 0, TPG_EINVAL, "max_iter = %d is negative", (int)pr.max_iter);
+  TPG_REQUIRE(pr.tol >= 0.0, TPG_EINVAL, "tol must be a non-negative number");  // false for a NaN too
+  TPG_TRY(tpg_require_diploid(v->n, ploidy, "admixture"));
+  const bool upd_q = pr.update_q != 0, upd_f = pr.update_f != 0;
+  const int64_t n = v->n, m = v->m;
+  AdmixRun run;
+  TPG_TRY(run.init(ctx, v, K, upd_q && pr.max_iter > 0, upd_f && pr.max_iter > 0, (int64_t)pr.max_iter + 1));
+  const int KT = run.KT;
+  const unsigned gn = (unsigned)ceil_div(n, 256), gm = (unsigned)ceil_div(m, 256);
+  // the start: the caller's, checked and normalised on the device, or the hash of (seed, position)
+  InBuf iq, ifr;
+  TPG_HIP(hipMemsetAsync(run.flag, 0, sizeof(int32_t), ctx->stream));
+  if (q0) {
+    TPG_TRY(iq.init(ctx, q0, sizeof(double) * (size_t)n * K));
+    TPG_LAUNCH(ctx, "admix_start", admix_load_q_kernel, dim3(gn), dim3(256), 0, iq.dev<double>(), run.Q[0], n, K, KT, true, run.flag);
+  } else {
+    TPG_LAUNCH(ctx, "admix_start", admix_seed_q_kernel, dim3(gn), dim3(256), 0, run.Q[0], n, K, KT, (uint64_t)pr.seed);
+  }
+  if (f0) {
+    TPG_TRY(ifr.init(ctx, f0, sizeof(double) * (size_t)m * K));
+    TPG_LAUNCH(ctx, "admix_start", admix_load_f_kernel, dim3(gm), dim3(256), 0, ifr.dev<double>(), run.F[0], m, K, KT, true, run.flag);
+  } else {
+    TPG_LAUNCH(ctx, "admix_start", admix_seed_f_kernel, dim3(gm), dim3(256), 0, run.F[0], m, K, KT, (uint64_t)pr.seed);
+  }
+  TPG_CHECK_LAUNCH();
+  if (q0 || f0) {
+    int32_t bad = 0;
+    TPG_HIP(tpg_fetch_small(ctx, &bad, run.flag, sizeof bad));
+    TPG_REQUIRE(!(bad & 1), TPG_EINVAL, "q0 has an entry that is not finite or not positive");
+    TPG_REQUIRE(!(bad & 2), TPG_EINVAL, "f0 has an entry that is not finite");
+  }
+  // state t - 1 -> state t; the F sweep of that pass leaves l(t - 1) in trace[t - 1]
+  std::vector<double> ll((size_t)pr.max_iter + 1);
+  int cq = 0, cf = 0, t = 0, conv = 0;
+  while (t < pr.max_iter) {
+    TPG_TRY(run.f_sweep(cq, cf, upd_f, t));
+    if (upd_q) TPG_TRY(run.q_sweep(cq, cf));
+    TPG_HIP(tpg_fetch_small(ctx, &ll[(size_t)t], run.trace + t, sizeof(double)));
+    if (upd_q) cq = 1 - cq;
+    if (upd_f) cf = 1 - cf;
+    t++;
+    if (t >= 2 && ll[(size_t)t - 1] - ll[(size_t)t - 2] < pr.tol) {
+      conv = 1;
+      break;
+    }
+  }
+  TPG_TRY(run.f_sweep(cq, cf, false, t));
+  TPG_HIP(tpg_fetch_small(ctx, &ll[(size_t)t], run.trace + t, sizeof(double)));
+  // nothing of the caller's has been written so far
+  OutBuf oq, op;
+  TPG_TRY(oq.init(Q, sizeof(double) * (size_t)n * K));
+  TPG_TRY(op.init(P, sizeof(double) * (size_t)m * K));
+  TPG_LAUNCH(ctx, "admix_store", admix_store_kernel, dim3((unsigned)ceil_div(n * K, 256)), dim3(256), 0, (const double*)run.Q[cq], n, K,
+             KT, oq.dev<double>());
+  TPG_LAUNCH(ctx, "admix_store", admix_store_kernel, dim3((unsigned)ceil_div(m * K, 256)), dim3(256), 0, (const double*)run.F[cf], m, K,
+             KT, op.dev<double>());
+  TPG_CHECK_LAUNCH();
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
+  TPG_TRY(oq.commit(ctx));
+  TPG_TRY(op.commit(ctx));
+  if (loglik) *loglik = ll[(size_t)t];
+  if (loglik_trace)
+    for (int s = 0; s <= t; s++) loglik_trace[s] = ll[(size_t)s];
+  if (n_iter) *n_iter = t;
+  if (converged) *converged = conv;
+  return TPG_OK;
+}
+
+extern "C" int tpg_admix_loglik(tpg_ctx* ctx, const tpg_view* v, int K, const double* Q, const double* P, double* loglik) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && v && Q && P && loglik, TPG_EINVAL, "null argument");
+  TPG_TRY(admix_check_view(v, K));
+  const int64_t n = v->n, m = v->m;
+  AdmixRun run;
+  TPG_TRY(run.init(ctx, v, K, false, false, 1));
+  InBuf iq, ip;
+  TPG_TRY(iq.init(ctx, Q, sizeof(double) * (size_t)n * K));
+  TPG_TRY(ip.init(ctx, P, sizeof(double) * (size_t)m * K));
+  TPG_LAUNCH(ctx, "admix_start", admix_load_q_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, iq.dev<double>(), run.Q[0], n, K,
+             run.KT, false, run.flag);
+  TPG_LAUNCH(ctx, "admix_start", admix_load_f_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ip.dev<double>(), run.F[0], m, K,
+             run.KT, false, run.flag);
+  TPG_TRY(run.f_sweep(0, 0, false, 0));
+  TPG_HIP(tpg_fetch_small(ctx, loglik, run.trace, sizeof(double)));
+  return TPG_OK;
+}
