@@ -40,73 +40,12 @@ if not os.path.exists(LIB_PATH):
 
 lib = C.CDLL(LIB_PATH)
 
-c_i32p = C.POINTER(C.c_int32)
-c_u8p = C.POINTER(C.c_uint8)
-c_f64p = C.POINTER(C.c_double)
-vp = C.c_void_p
-
-lib.tpg_last_error.restype = C.c_char_p
-lib.tpg_version.restype = C.c_char_p
-lib.tpg_comm_transport.restype = C.c_char_p
-lib.tpg_comm_transport.argtypes = [C.c_void_p]
-lib.tpg_pairwise_buffer_bytes.restype = C.c_size_t
-lib.tpg_pairwise_buffer_bytes.argtypes = [C.c_int64]
-lib.tpg_view_n.restype = C.c_int64
-lib.tpg_view_m.restype = C.c_int64
-lib.tpg_view_n.argtypes = [vp]
-lib.tpg_view_m.argtypes = [vp]
-lib.tpg_as_pad_quirk_blocks.restype = C.c_int64
-lib.tpg_as_pad_quirk_blocks.argtypes = [C.c_int64, C.c_int64]
-lib.tpg_pairwise_set_as_pad_quirk.argtypes = [vp, C.c_int64]
-lib.tpg_pairwise_products.argtypes = [vp]
-lib.tpg_filter_high_relatedness.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp]
-lib.tpg_multi_ctx.restype = vp
-lib.tpg_multi_comm.restype = vp
-lib.tpg_multi_ctx.argtypes = [vp, C.c_int]
-lib.tpg_multi_comm.argtypes = [vp, C.c_int]
-lib.tpg_multi_ndev.argtypes = [vp]
-lib.tpg_comm_rank.argtypes = [vp]
-lib.tpg_comm_size.argtypes = [vp]
-lib.tpg_pairwise_buffer_bytes_sharded.restype = C.c_size_t
-lib.tpg_pairwise_buffer_bytes_sharded.argtypes = [C.c_int64, C.c_int]
-HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64, C.c_int)
-for _name in ("tpg_ctx_destroy", "tpg_fbm_free", "tpg_view_free", "tpg_pairwise_free", "tpg_dev_free",
-              "tpg_comm_destroy", "tpg_multi_destroy"):
-    getattr(lib, _name).restype = None
-    getattr(lib, _name).argtypes = [vp]
-
-# every symbol include/tpg.h declares (checked by tests/test_abi.py against the header)
-SYMBOLS = [
-    "tpg_last_error", "tpg_version", "tpg_device_count", "tpg_host_bind_near_device", "tpg_ctx_create", "tpg_ctx_destroy", "tpg_ctx_set_stream", "tpg_ctx_sync",
-    "tpg_prof_enable", "tpg_prof_reset", "tpg_prof_only", "tpg_prof_get", "tpg_prof_dump", "tpg_dev_alloc", "tpg_dev_free",
-    "tpg_dev_to_host", "tpg_dev_from_host", "tpg_sym_eig_topk", "tpg_pca_loadings", "tpg_pairwise_pop_fst_sums", "tpg_fbm_from_host", "tpg_fbm_open_bk",
-    "tpg_fbm_synth", "tpg_fbm_alloc", "tpg_fbm_upload_cols", "tpg_pca_gram_add", "tpg_fbm_open_bed", "tpg_fbm_from_bed_host", "tpg_fbm_alloc_bed", "tpg_fbm_upload_bed_snps", "tpg_fbm_to_host", "tpg_fbm_free", "tpg_view_create", "tpg_view_create_pair", "tpg_view_create_from_host", "tpg_view_free", "tpg_view_n",
-    "tpg_view_m", "tpg_view_unpack", "tpg_loci_counts", "tpg_indiv_counts", "tpg_gt_ind_hetero", "tpg_gt_pi_diploid",
-    "tpg_gt_grouped_pi_diploid", "tpg_grouped_genotype_counts", "tpg_pop_global_stats", "tpg_pop_basic_stats", "tpg_window_stats", "tpg_pbs_from_fst", "tpg_alt_freq_dip_pseudo",
-    "tpg_grouped_alt_freq_dip_pseudo", "tpg_grouped_missingness", "tpg_grouped_summaries_dip_pseudo",
-    "tpg_pairwise_pop_fst", "tpg_pairwise_fst_loop", "tpg_pairwise_buffer_bytes", "tpg_pairwise_create",
-    "tpg_pairwise_free", "tpg_pairwise_zero", "tpg_pairwise_accumulate", "tpg_pairwise_counts", "tpg_pairwise_ibs",
-    "tpg_pairwise_king", "tpg_pairwise_allele_sharing", "tpg_pairwise_grm", "tpg_pairwise_epilogues", "tpg_block_means", "tpg_increment_ibs_counts",
-    "tpg_increment_king_numerator", "tpg_increment_as_counts", "tpg_pca_center_scale", "tpg_pca_gram",
-    "tpg_pca_partial_svd", "tpg_fbm256_prod_and_rowSumsSq", "tpg_square_frobenius",
-    "tpg_pairwise_set_as_pad_quirk", "tpg_as_pad_quirk_blocks", "tpg_increment_defer", "tpg_increment_flush", "tpg_resident_drop",
-    "tpg_increment_as_note_narrow_block", "tpg_filter_high_relatedness", "tpg_pca_random_svd",
-    "tpg_fbm256_valid_prod", "tpg_comm_unique_id", "tpg_comm_init_rank", "tpg_comm_init_host", "tpg_comm_destroy",
-    "tpg_comm_rank", "tpg_comm_size", "tpg_comm_transport", "tpg_shard_loci", "tpg_comm_allreduce_f64", "tpg_pairwise_buffer_bytes_sharded",
-    "tpg_pairwise_create_sharded", "tpg_pairwise_reduce", "tpg_pairwise_band", "tpg_pairwise_band_of", "tpg_pairwise_epilogues_sharded",
-    "tpg_pca_partial_svd_sharded", "tpg_multi_create", "tpg_multi_destroy", "tpg_multi_ndev", "tpg_multi_ctx", "tpg_multi_comm", "tpg_multi_pairwise",
-    "tpg_multi_grouped_alt_freq", "tpg_multi_pop_fst", "tpg_multi_pca_partial_svd",
-    "tpg_pairwise_accumulate_products", "tpg_pairwise_products", "tpg_pairwise_reduce_begin", "tpg_pairwise_reduce_end",
-    "tpg_stream_open_host", "tpg_stream_open_bk", "tpg_stream_open_bed", "tpg_stream_open_bed_host", "tpg_stream_open_synth",
-    "tpg_stream_close", "tpg_stream_run", "tpg_multi_stream_run", "tpg_fbm_impute_simple", "tpg_fbm_impute_simple_at", "tpg_view_impute",
-    "tpg_hwe_exact_counts", "tpg_loci_hwe", "tpg_gt_grouped_hwe", "tpg_stream_qc",
-    "tpg_ld_band_links", "tpg_ld_clump",
-    "tpg_roh_chunk_loci", "tpg_roh_snp_status", "tpg_roh_detect", "tpg_roh_count", "tpg_roh_fetch", "tpg_roh_indiv_summary",
-    "tpg_roh_locus_counts", "tpg_roh_free",
-    "tpg_tajimas_d_from_sums", "tpg_tajima_chunk_loci", "tpg_pop_tajimas_d", "tpg_windows_pop_tajimas_d",
-    "tpg_f2_params_default", "tpg_f2_chunk_loci", "tpg_f2_blocks", "tpg_f4_jackknife",
-    "tpg_admix_params_default", "tpg_admix_chunk_loci", "tpg_admix_em", "tpg_admix_loglik",
-]
+# the ctypes spelling of the C types include/tpg.h uses.  Every pointer to a scalar, opaque handle and handle out-parameter is
+# a c_void_p: it takes None, an int (a raw device address), a c_void_p, a byref() result and a ctypes array alike.
+vp, cstr = C.c_void_p, C.c_char_p
+ci, i64, u32, u64, sz, f64 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t, C.c_double
+P = C.POINTER  # of a struct mirrored below: takes byref(struct) and None
+HOST_ALLREDUCE = C.CFUNCTYPE(ci, vp, vp, i64, ci)  # the allreduce callback of tpg_comm_init_host
 
 
 class StreamJob(C.Structure):
@@ -178,53 +117,182 @@ class StreamReport(C.Structure):
     ]
 
 
-if hasattr(lib, "tpg_fbm_impute_simple"):  # (a library built before the entry points existed: build() reports it)
-    lib.tpg_fbm_impute_simple.argtypes = [vp, vp, C.c_int, C.c_uint64, C.POINTER(ImputeReport)]
-    lib.tpg_fbm_impute_simple_at.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_uint64, C.POINTER(ImputeReport)]
-    lib.tpg_view_impute.argtypes = [vp, vp, C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(ImputeReport)]
-if hasattr(lib, "tpg_loci_hwe"):
-    lib.tpg_hwe_exact_counts.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
-    lib.tpg_loci_hwe.argtypes = [vp, vp, C.c_int, vp]
-    lib.tpg_gt_grouped_hwe.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
-if hasattr(lib, "tpg_stream_qc"):
-    lib.tpg_stream_qc.argtypes = [vp, vp, C.POINTER(StreamQcJob), C.POINTER(StreamReport)]
-if hasattr(lib, "tpg_ld_clump"):
-    lib.tpg_ld_band_links.argtypes = [vp, vp, vp, C.c_double, vp, C.c_int64, C.POINTER(C.c_int64)]
-    lib.tpg_ld_clump.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp, C.POINTER(LdReport)]
-if hasattr(lib, "tpg_roh_detect"):
-    lib.tpg_roh_chunk_loci.restype = C.c_int64
-    lib.tpg_roh_chunk_loci.argtypes = []
-    lib.tpg_roh_snp_status.argtypes = [vp, vp, vp, vp, C.POINTER(RohParams), vp, C.c_int64]
-    lib.tpg_roh_detect.argtypes = [vp, vp, vp, vp, C.POINTER(RohParams), C.POINTER(vp)]
-    lib.tpg_roh_count.restype = C.c_int64
-    lib.tpg_roh_count.argtypes = [vp]
-    lib.tpg_roh_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.tpg_roh_indiv_summary.argtypes = [vp, vp, vp, vp]
-    lib.tpg_roh_locus_counts.argtypes = [vp, vp, vp]
-    lib.tpg_roh_free.restype = None
-    lib.tpg_roh_free.argtypes = [vp]
-if hasattr(lib, "tpg_pop_tajimas_d"):
-    lib.tpg_tajimas_d_from_sums.argtypes = [C.c_int64, C.c_int64, C.c_double, c_f64p]
-    lib.tpg_tajima_chunk_loci.restype = C.c_int64
-    lib.tpg_tajima_chunk_loci.argtypes = []
-    lib.tpg_pop_tajimas_d.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    lib.tpg_windows_pop_tajimas_d.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
-if hasattr(lib, "tpg_f2_blocks"):
-    lib.tpg_f2_params_default.argtypes = [C.POINTER(F2Params)]
-    lib.tpg_f2_chunk_loci.restype = C.c_int64
-    lib.tpg_f2_chunk_loci.argtypes = []
-    lib.tpg_f2_blocks.argtypes = [vp, vp, vp, C.c_int, vp, C.POINTER(F2Params), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
-    lib.tpg_f4_jackknife.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
-if hasattr(lib, "tpg_admix_em"):
-    lib.tpg_admix_params_default.argtypes = [C.POINTER(AdmixParams)]
-    lib.tpg_admix_chunk_loci.restype = C.c_int64
-    lib.tpg_admix_chunk_loci.argtypes = []
-    lib.tpg_admix_em.argtypes = [vp, vp, vp, C.c_int, C.POINTER(AdmixParams), vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.tpg_admix_loglik.argtypes = [vp, vp, C.c_int, vp, vp, vp]
-lib.tpg_stream_close.restype = None
-lib.tpg_stream_close.argtypes = [vp]
-lib.tpg_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]
-lib.tpg_multi_stream_run.argtypes = [vp, vp, C.POINTER(StreamJob), C.POINTER(StreamReport)]
+# name ->(restype, argtypes) of every function include/tpg.h declares, in header order (tests/test_abi.py parses the header
+# and checks each entry against it).  A new entry point gets its line here; nothing else declares a prototype.
+PROTOTYPES = {
+    "tpg_last_error": (cstr, []),
+    "tpg_version": (cstr, []),
+    # ---- context
+    "tpg_device_count": (ci, [vp]),
+    "tpg_ctx_create": (ci, [ci, vp]),
+    "tpg_ctx_destroy": (None, [vp]),
+    "tpg_host_bind_near_device": (ci, [ci, vp]),
+    "tpg_ctx_set_stream": (ci, [vp, vp]),
+    "tpg_ctx_sync": (ci, [vp]),
+    "tpg_prof_enable": (ci, [vp, ci]),
+    "tpg_prof_reset": (ci, [vp]),
+    "tpg_prof_only": (ci, [vp, cstr]),
+    "tpg_prof_get": (ci, [vp, cstr, vp, vp]),
+    "tpg_prof_dump": (ci, [vp, vp, sz]),
+    "tpg_dev_alloc": (ci, [vp, sz, vp]),
+    "tpg_dev_free": (None, [vp]),
+    "tpg_dev_to_host": (ci, [vp, vp, vp, sz]),
+    "tpg_dev_from_host": (ci, [vp, vp, vp, sz]),
+    # ---- genotype store
+    "tpg_fbm_from_host": (ci, [vp, vp, i64, i64, vp]),
+    "tpg_fbm_open_bk": (ci, [vp, cstr, i64, i64, vp]),
+    "tpg_fbm_alloc": (ci, [vp, i64, i64, vp]),
+    "tpg_fbm_upload_cols": (ci, [vp, vp, vp, i64, i64]),
+    "tpg_fbm_synth": (ci, [vp, u64, i64, i64, i64, ci, u32, ci, vp]),
+    "tpg_fbm_open_bed": (ci, [vp, cstr, i64, i64, vp]),
+    "tpg_fbm_from_bed_host": (ci, [vp, vp, i64, i64, vp]),
+    "tpg_fbm_alloc_bed": (ci, [vp, i64, i64, vp]),
+    "tpg_fbm_upload_bed_snps": (ci, [vp, vp, vp, i64, i64]),
+    "tpg_fbm_to_host": (ci, [vp, vp, vp]),
+    "tpg_fbm_free": (None, [vp]),
+    # ---- simple imputation
+    "tpg_fbm_impute_simple": (ci, [vp, vp, ci, u64, P(ImputeReport)]),
+    "tpg_fbm_impute_simple_at": (ci, [vp, vp, i64, ci, u64, P(ImputeReport)]),
+    "tpg_view_impute": (ci, [vp, vp, ci, u64, vp, P(ImputeReport)]),
+    "tpg_view_create": (ci, [vp, vp, vp, i64, vp, i64, vp, vp]),
+    "tpg_view_create_pair": (ci, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "tpg_view_create_from_host": (ci, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
+    "tpg_view_free": (None, [vp]),
+    "tpg_view_n": (i64, [vp]),
+    "tpg_view_m": (i64, [vp]),
+    "tpg_view_unpack": (ci, [vp, vp, vp]),
+    # ---- per-locus sweeps
+    "tpg_loci_counts": (ci, [vp, vp, vp]),
+    "tpg_indiv_counts": (ci, [vp, vp, vp]),
+    "tpg_gt_ind_hetero": (ci, [vp, vp, vp]),
+    "tpg_gt_pi_diploid": (ci, [vp, vp, vp]),
+    "tpg_gt_grouped_pi_diploid": (ci, [vp, vp, vp, ci, vp, vp]),
+    "tpg_grouped_genotype_counts": (ci, [vp, vp, vp, ci, vp]),
+    # ---- Hardy-Weinberg exact tests
+    "tpg_hwe_exact_counts": (ci, [vp, vp, i64, ci, vp]),
+    "tpg_loci_hwe": (ci, [vp, vp, ci, vp]),
+    "tpg_gt_grouped_hwe": (ci, [vp, vp, vp, ci, ci, vp]),
+    # ---- LD clumping
+    "tpg_ld_band_links": (ci, [vp, vp, vp, f64, vp, i64, vp]),
+    "tpg_ld_clump": (ci, [vp, vp, vp, f64, vp, vp, vp, P(LdReport)]),
+    # ---- runs of homozygosity
+    "tpg_roh_chunk_loci": (i64, []),
+    "tpg_roh_snp_status": (ci, [vp, vp, vp, vp, P(RohParams), vp, i64]),
+    "tpg_roh_detect": (ci, [vp, vp, vp, vp, P(RohParams), vp]),
+    "tpg_roh_count": (i64, [vp]),
+    "tpg_roh_fetch": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_roh_indiv_summary": (ci, [vp, vp, vp, vp]),
+    "tpg_roh_locus_counts": (ci, [vp, vp, vp]),
+    "tpg_roh_free": (None, [vp]),
+    # ---- Tajima's D
+    "tpg_tajimas_d_from_sums": (ci, [i64, i64, f64, vp]),
+    "tpg_tajima_chunk_loci": (i64, []),
+    "tpg_pop_tajimas_d": (ci, [vp, vp, vp, ci, vp, vp, vp, vp]),
+    "tpg_windows_pop_tajimas_d": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, i64, ci, vp, vp, vp, vp]),
+    # ---- f2 blocks
+    "tpg_f2_params_default": (ci, [P(F2Params)]),
+    "tpg_f2_chunk_loci": (i64, []),
+    "tpg_f2_blocks": (ci, [vp, vp, vp, ci, vp, P(F2Params), vp, vp, i64, vp, vp, vp, vp, vp]),
+    "tpg_f4_jackknife": (ci, [vp, ci, i64, vp, vp, i64, vp, vp, vp]),
+    # ---- admixture
+    "tpg_admix_params_default": (ci, [P(AdmixParams)]),
+    "tpg_admix_chunk_loci": (i64, []),
+    "tpg_admix_em": (ci, [vp, vp, vp, ci, P(AdmixParams), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_admix_loglik": (ci, [vp, vp, ci, vp, vp, vp]),
+    "tpg_pop_global_stats": (ci, [vp, vp, vp, ci, vp, vp, vp]),
+    "tpg_pop_basic_stats": (ci, [vp, vp, vp, ci, vp, ci, vp, vp]),
+    "tpg_window_stats": (ci, [vp, vp, i64, ci, vp, vp, vp, i64, ci, ci, vp, vp]),
+    "tpg_pbs_from_fst": (ci, [vp, vp, i64, ci, vp, ci, vp]),
+    "tpg_alt_freq_dip_pseudo": (ci, [vp, vp, vp, ci, vp]),
+    "tpg_grouped_alt_freq_dip_pseudo": (ci, [vp, vp, vp, ci, vp, ci, vp]),
+    "tpg_grouped_missingness": (ci, [vp, vp, vp, ci, vp]),
+    "tpg_grouped_summaries_dip_pseudo": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp]),
+    # ---- pairwise population Fst
+    "tpg_pairwise_pop_fst": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp]),
+    "tpg_pairwise_pop_fst_sums": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp]),
+    "tpg_pairwise_fst_loop": (ci, [vp, ci, vp, ci, i64, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp]),
+    # ---- pairwise individual matrices
+    "tpg_pairwise_buffer_bytes": (sz, [i64]),
+    "tpg_pairwise_create": (ci, [vp, i64, vp, vp]),
+    "tpg_pairwise_free": (None, [vp]),
+    "tpg_pairwise_zero": (ci, [vp, vp]),
+    "tpg_pairwise_accumulate": (ci, [vp, vp, vp, i64, i64]),
+    "tpg_pairwise_accumulate_products": (ci, [vp, vp, vp, i64, i64, ci]),
+    "tpg_pairwise_products": (ci, [vp]),
+    "tpg_pairwise_set_as_pad_quirk": (ci, [vp, i64]),
+    "tpg_as_pad_quirk_blocks": (i64, [i64, i64]),
+    "tpg_pairwise_counts": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_pairwise_ibs": (ci, [vp, vp, ci, i64, vp]),
+    "tpg_pairwise_king": (ci, [vp, vp, vp]),
+    "tpg_pairwise_allele_sharing": (ci, [vp, vp, vp]),
+    "tpg_pairwise_grm": (ci, [vp, vp, vp]),
+    "tpg_pairwise_epilogues": (ci, [vp, vp, ci, i64, vp, vp, vp, vp]),
+    "tpg_block_means": (ci, [vp, vp, i64, vp, ci, ci, vp, vp]),
+    "tpg_filter_high_relatedness": (ci, [vp, vp, i64, f64, vp, vp]),
+    "tpg_increment_defer": (ci, [vp, ci]),
+    "tpg_increment_ibs_counts": (ci, [vp, vp, vp, vp, i64, i64, vp, i64, vp, i64]),
+    "tpg_increment_king_numerator": (ci, [vp, vp, vp, vp, i64, i64, vp, i64, vp, i64]),
+    "tpg_increment_as_counts": (ci, [vp, vp, vp, vp, i64, i64, vp, i64, vp, i64]),
+    "tpg_increment_flush": (ci, [vp]),
+    "tpg_resident_drop": (ci, [vp]),
+    "tpg_increment_as_note_narrow_block": (ci, [vp, vp, i64]),
+    # ---- SNP-block shards over the GPUs of one node
+    "tpg_comm_unique_id": (ci, [vp]),
+    "tpg_comm_init_rank": (ci, [vp, ci, ci, vp, vp]),
+    "tpg_comm_init_host": (ci, [vp, ci, ci, HOST_ALLREDUCE, vp, vp]),
+    "tpg_comm_destroy": (None, [vp]),
+    "tpg_comm_transport": (cstr, [vp]),
+    "tpg_comm_rank": (ci, [vp]),
+    "tpg_comm_size": (ci, [vp]),
+    "tpg_shard_loci": (ci, [i64, ci, ci, vp, vp]),
+    "tpg_comm_allreduce_f64": (ci, [vp, vp, vp, i64]),
+    "tpg_pairwise_buffer_bytes_sharded": (sz, [i64, ci]),
+    "tpg_pairwise_create_sharded": (ci, [vp, vp, i64, vp]),
+    "tpg_pairwise_reduce": (ci, [vp, vp, vp]),
+    "tpg_pairwise_reduce_begin": (ci, [vp, vp, vp]),
+    "tpg_pairwise_reduce_end": (ci, [vp, vp, vp]),
+    "tpg_pairwise_band": (ci, [vp, vp, vp]),
+    "tpg_pairwise_band_of": (ci, [i64, ci, ci, vp, vp]),
+    "tpg_pairwise_epilogues_sharded": (ci, [vp, vp, vp, ci, i64, vp, vp, vp, vp]),
+    "tpg_pca_partial_svd_sharded": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "tpg_multi_create": (ci, [ci, vp, vp]),
+    "tpg_multi_destroy": (None, [vp]),
+    "tpg_multi_ndev": (ci, [vp]),
+    "tpg_multi_ctx": (vp, [vp, ci]),
+    "tpg_multi_comm": (vp, [vp, ci]),
+    "tpg_multi_pairwise": (ci, [vp, vp, i64, i64, vp, i64, vp, i64, ci, vp, vp, vp, vp]),
+    "tpg_multi_grouped_alt_freq": (ci, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, ci, vp, ci, vp]),
+    "tpg_multi_pop_fst": (ci, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp]),
+    "tpg_multi_pca_partial_svd": (ci, [vp, vp, i64, i64, vp, i64, vp, i64, vp, ci, vp, vp, vp, vp, vp, vp]),
+    # ---- streamed whole analyses
+    "tpg_stream_open_host": (ci, [vp, vp, i64, i64, sz, vp]),
+    "tpg_stream_open_bk": (ci, [vp, cstr, i64, i64, sz, vp]),
+    "tpg_stream_open_bed": (ci, [vp, cstr, i64, i64, sz, vp]),
+    "tpg_stream_open_bed_host": (ci, [vp, vp, i64, i64, sz, vp]),
+    "tpg_stream_open_synth": (ci, [vp, u64, i64, i64, ci, u32, ci, sz, vp]),
+    "tpg_stream_close": (None, [vp]),
+    "tpg_stream_run": (ci, [vp, vp, P(StreamJob), P(StreamReport)]),
+    "tpg_multi_stream_run": (ci, [vp, vp, P(StreamJob), P(StreamReport)]),
+    "tpg_stream_qc": (ci, [vp, vp, P(StreamQcJob), P(StreamReport)]),
+    # ---- PCA
+    "tpg_pca_center_scale": (ci, [vp, vp, vp, vp]),
+    "tpg_pca_gram": (ci, [vp, vp, vp, vp, vp]),
+    "tpg_pca_gram_add": (ci, [vp, vp, vp, vp, vp]),
+    "tpg_pca_partial_svd": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "tpg_pca_random_svd": (ci, [vp, vp, ci, f64, vp, vp, vp, vp, vp, vp]),
+    "tpg_sym_eig_topk": (ci, [vp, vp, i64, ci, vp, vp]),
+    "tpg_pca_loadings": (ci, [vp, vp, vp, vp, vp, vp, ci, vp]),
+    "tpg_fbm256_prod_and_rowSumsSq": (ci, [vp, vp, vp, vp, vp, ci, vp, vp]),
+    "tpg_square_frobenius": (ci, [vp, vp, vp, vp, vp]),
+    "tpg_fbm256_valid_prod": (ci, [vp, vp, vp, ci, vp]),
+}
+
+for _name, (_restype, _argtypes) in PROTOTYPES.items():
+    if hasattr(lib, _name):  # (a library built before the entry point existed still imports: build() reports what it lacks)
+        getattr(lib, _name).restype = _restype
+        getattr(lib, _name).argtypes = _argtypes
+
+SYMBOLS = list(PROTOTYPES)
 
 
 def check(rc: int) -> None:

@@ -72,17 +72,17 @@ class Context:
 
     def __init__(self, device: int = 0):
         h = C.c_void_p()
-        check(lib.tpg_ctx_create(C.c_int(device), C.byref(h)))
+        check(lib.tpg_ctx_create(device, C.byref(h)))
         self.h = h
         self.device = device
 
     def set_stream(self, hip_stream: Optional[int]):
-        check(lib.tpg_ctx_set_stream(self.h, C.c_void_p(hip_stream)))
+        check(lib.tpg_ctx_set_stream(self.h, hip_stream))
 
     def dev_alloc(self, nbytes: int) -> "C.c_void_p":
         """raw device memory for outputs that stay in HBM between two library calls; release with dev_free"""
         p = C.c_void_p()
-        check(lib.tpg_dev_alloc(self.h, C.c_size_t(int(nbytes)), C.byref(p)))
+        check(lib.tpg_dev_alloc(self.h, int(nbytes), C.byref(p)))
         return p
 
     def dev_free(self, p):
@@ -92,7 +92,7 @@ class Context:
         check(lib.tpg_ctx_sync(self.h))
 
     def prof_enable(self, on: bool = True):
-        check(lib.tpg_prof_enable(self.h, C.c_int(int(on))))
+        check(lib.tpg_prof_enable(self.h, int(on)))
 
     def prof_reset(self):
         check(lib.tpg_prof_reset(self.h))
@@ -109,7 +109,7 @@ class Context:
 
     def prof_dump(self) -> dict:
         buf = C.create_string_buffer(1 << 16)
-        check(lib.tpg_prof_dump(self.h, buf, C.c_size_t(len(buf))))
+        check(lib.tpg_prof_dump(self.h, buf, len(buf)))
         out = {}
         for line in buf.value.decode().splitlines():
             name, n, ms = line.split("\t")
@@ -143,7 +143,7 @@ def bind_host_near_device(device: int = 0) -> int:
     (tpg_host_bind_near_device: what `numactl --cpunodebind` does for a one-process-per-GPU launcher).  Returns the node,
     or -1 when nothing was done (one node, node unknown, too few of this process's CPUs on it)."""
     node = C.c_int(-1)
-    check(lib.tpg_host_bind_near_device(C.c_int(device), C.byref(node)))
+    check(lib.tpg_host_bind_near_device(device, C.byref(node)))
     return node.value
 
 
@@ -169,7 +169,7 @@ class FBM:
             raise TypeError("FBM bytes must be a 2-D uint8 array (individuals x loci)")
         a = np.asfortranarray(a)
         h = C.c_void_p()
-        check(lib.tpg_fbm_from_host(ctx.h, _ptr(a), C.c_int64(a.shape[0]), C.c_int64(a.shape[1]), C.byref(h)))
+        check(lib.tpg_fbm_from_host(ctx.h, _ptr(a), a.shape[0], a.shape[1], C.byref(h)))
         return cls(ctx, h, a.shape[0], a.shape[1], code256)
 
     @classmethod
@@ -177,7 +177,7 @@ class FBM:
         """HBM for an FBM whose columns arrive block by block (upload_cols)"""
         ctx = ctx or default_context()
         h = C.c_void_p()
-        check(lib.tpg_fbm_alloc(ctx.h, C.c_int64(nrow), C.c_int64(ncol), C.byref(h)))
+        check(lib.tpg_fbm_alloc(ctx.h, nrow, ncol, C.byref(h)))
         return cls(ctx, h, nrow, ncol, code256)
 
     def upload_cols(self, host_cols, col0: int, ctx: Optional[Context] = None):
@@ -185,13 +185,13 @@ class FBM:
         pass another Context (another stream) to run the upload beside kernels of this FBM's own context"""
         a = np.asarray(host_cols)
         assert a.dtype == np.uint8 and a.ndim == 2 and a.flags.f_contiguous and a.shape[0] == self.nrow
-        check(lib.tpg_fbm_upload_cols((ctx or self.ctx).h, self.h, _ptr(a), C.c_int64(col0), C.c_int64(a.shape[1])))
+        check(lib.tpg_fbm_upload_cols((ctx or self.ctx).h, self.h, _ptr(a), col0, a.shape[1]))
 
     @classmethod
     def open_bk(cls, path: str, nrow: int, ncol: int, ctx: Optional[Context] = None, code256=None) -> "FBM":
         ctx = ctx or default_context()
         h = C.c_void_p()
-        check(lib.tpg_fbm_open_bk(ctx.h, path.encode(), C.c_int64(nrow), C.c_int64(ncol), C.byref(h)))
+        check(lib.tpg_fbm_open_bk(ctx.h, path.encode(), nrow, ncol, C.byref(h)))
         return cls(ctx, h, nrow, ncol, code256)
 
     @classmethod
@@ -199,7 +199,7 @@ class FBM:
         """A PLINK .bed file as the genotype store (n, m = line counts of the .fam / .bim files)"""
         ctx = ctx or default_context()
         h = C.c_void_p()
-        check(lib.tpg_fbm_open_bed(ctx.h, path.encode(), C.c_int64(n), C.c_int64(m), C.byref(h)))
+        check(lib.tpg_fbm_open_bed(ctx.h, path.encode(), n, m, C.byref(h)))
         return cls(ctx, h, n, m, code256)
 
     @classmethod
@@ -207,7 +207,7 @@ class FBM:
         """HBM for a .bed store whose SNPs arrive block by block (upload_bed_snps)"""
         ctx = ctx or default_context()
         h = C.c_void_p()
-        check(lib.tpg_fbm_alloc_bed(ctx.h, C.c_int64(n), C.c_int64(m), C.byref(h)))
+        check(lib.tpg_fbm_alloc_bed(ctx.h, n, m, C.byref(h)))
         return cls(ctx, h, n, m, code256)
 
     def upload_bed_snps(self, host_bytes, snp0: int, nsnps: int, ctx: Optional[Context] = None):
@@ -215,7 +215,7 @@ class FBM:
         its 3-byte magic); another Context (another stream) runs the upload beside kernels of this store's own context"""
         a = np.asarray(host_bytes)
         assert a.dtype == np.uint8 and a.flags.c_contiguous and a.size == nsnps * ((self.nrow + 3) // 4)
-        check(lib.tpg_fbm_upload_bed_snps((ctx or self.ctx).h, self.h, _ptr(a), C.c_int64(snp0), C.c_int64(nsnps)))
+        check(lib.tpg_fbm_upload_bed_snps((ctx or self.ctx).h, self.h, _ptr(a), snp0, nsnps))
 
     @classmethod
     def synth(cls, seed: int, nrow: int, ncol: int, j0: int = 0, npop: int = 51, miss: float = 0.02,
@@ -223,8 +223,7 @@ class FBM:
         ctx = ctx or default_context()
         thr = min(int(round(miss * 2 ** 32)), 2 ** 32 - 1)
         h = C.c_void_p()
-        check(lib.tpg_fbm_synth(ctx.h, C.c_uint64(seed), C.c_int64(nrow), C.c_int64(ncol), C.c_int64(j0),
-                                C.c_int(npop), C.c_uint32(thr), C.c_int(int(imputed_bytes)), C.byref(h)))
+        check(lib.tpg_fbm_synth(ctx.h, seed, nrow, ncol, j0, npop, thr, int(imputed_bytes), C.byref(h)))
         return cls(ctx, h, nrow, ncol, code256)
 
     def impute_simple(self, method: str = "mode", seed: int = 0) -> dict:
@@ -232,7 +231,7 @@ class FBM:
         byte 4 + fill, which CODE_IMPUTE_PRED reads and the raw-byte analyses go on treating as missing.  Returns the
         report {"imputed", "loci_all_missing"}.  The FBM's code256 is left as it is (gt_impute_simple below switches it)."""
         rep = _lib.ImputeReport()
-        check(lib.tpg_fbm_impute_simple(self.ctx.h, self.h, C.c_int(_impute_method(method)), C.c_uint64(seed), C.byref(rep)))
+        check(lib.tpg_fbm_impute_simple(self.ctx.h, self.h, _impute_method(method), seed, C.byref(rep)))
         return {"imputed": int(rep.imputed), "loci_all_missing": int(rep.loci_all_missing)}
 
     def to_numpy(self) -> np.ndarray:
@@ -264,8 +263,8 @@ class View:
         else:
             code = _f64(code256)  # None = raw bytes
         h = C.c_void_p()
-        check(lib.tpg_view_create(self.ctx.h, X.h, _ptr(r), C.c_int64(0 if r is None else len(r)), _ptr(c),
-                                  C.c_int64(0 if c is None else len(c)), _ptr(code), C.byref(h)))
+        check(lib.tpg_view_create(self.ctx.h, X.h, _ptr(r), 0 if r is None else len(r), _ptr(c),
+                                  0 if c is None else len(c), _ptr(code), C.byref(h)))
         self.h = h
         self.n = int(lib.tpg_view_n(h))
         self.m = int(lib.tpg_view_m(h))
@@ -277,8 +276,8 @@ class View:
         r, c = _i32(ind_row), _i32(ind_col)
         ca, cb = _f64(code256_a), _f64(code256_b)
         ha, hb = C.c_void_p(), C.c_void_p()
-        check(lib.tpg_view_create_pair(X.ctx.h, X.h, _ptr(r), C.c_int64(0 if r is None else len(r)), _ptr(c),
-                                       C.c_int64(0 if c is None else len(c)), _ptr(ca), _ptr(cb), C.byref(ha), C.byref(hb)))
+        check(lib.tpg_view_create_pair(X.ctx.h, X.h, _ptr(r), 0 if r is None else len(r), _ptr(c),
+                                       0 if c is None else len(c), _ptr(ca), _ptr(cb), C.byref(ha), C.byref(hb)))
         out = []
         for h in (ha, hb):
             v = cls.__new__(cls)
@@ -292,7 +291,7 @@ class View:
         (tpg_view_impute): the only route for a .bed-form store.  The report is left in `.impute_report` of the result."""
         h = C.c_void_p()
         rep = _lib.ImputeReport()
-        check(lib.tpg_view_impute(self.ctx.h, self.h, C.c_int(_impute_method(method)), C.c_uint64(seed), C.byref(h), C.byref(rep)))
+        check(lib.tpg_view_impute(self.ctx.h, self.h, _impute_method(method), seed, C.byref(h), C.byref(rep)))
         v = View.__new__(View)
         v.X, v.ctx, v.h = self.X, self.ctx, h
         v.n, v.m = int(lib.tpg_view_n(h)), int(lib.tpg_view_m(h))
@@ -322,12 +321,12 @@ class Pairwise:
     def __init__(self, ctx: Context, n: int, ext_buffer: Optional[int] = None):
         self.ctx, self.n = ctx, n
         h = C.c_void_p()
-        check(lib.tpg_pairwise_create(ctx.h, C.c_int64(n), C.c_void_p(ext_buffer), C.byref(h)))
+        check(lib.tpg_pairwise_create(ctx.h, n, ext_buffer, C.byref(h)))
         self.h = h
 
     @staticmethod
     def buffer_bytes(n: int) -> int:
-        return int(lib.tpg_pairwise_buffer_bytes(C.c_int64(n)))
+        return int(lib.tpg_pairwise_buffer_bytes(n))
 
     def zero(self):
         check(lib.tpg_pairwise_zero(self.ctx.h, self.h))
@@ -336,10 +335,9 @@ class Pairwise:
         """products: None = all five cross-products; else an OR of PW_V / PW_D / PW_H / PW_A or one of the sets
         PW_FOR_AS / PW_FOR_IBS / PW_FOR_KING (the kernel specialised for that set runs: include/tpg.h)"""
         if products is None:
-            check(lib.tpg_pairwise_accumulate(self.ctx.h, self.h, view.h, C.c_int64(col_begin), C.c_int64(col_end)))
+            check(lib.tpg_pairwise_accumulate(self.ctx.h, self.h, view.h, col_begin, col_end))
         else:
-            check(lib.tpg_pairwise_accumulate_products(self.ctx.h, self.h, view.h, C.c_int64(col_begin), C.c_int64(col_end),
-                                                       C.c_int(int(products))))
+            check(lib.tpg_pairwise_accumulate_products(self.ctx.h, self.h, view.h, col_begin, col_end, int(products)))
 
     def products(self) -> int:
         """the products whose sums are complete since the last zero()"""
@@ -347,7 +345,7 @@ class Pairwise:
 
     def set_as_pad_quirk(self, narrow_blocks: int):
         """opt-in emulation of reference quirk Q1 (include/tpg.h): +narrow_blocks on every allele-sharing numerator"""
-        check(lib.tpg_pairwise_set_as_pad_quirk(self.h, C.c_int64(int(narrow_blocks))))
+        check(lib.tpg_pairwise_set_as_pad_quirk(self.h, int(narrow_blocks)))
 
     def _mat(self):
         return np.zeros((self.n, self.n), order="F")
@@ -360,7 +358,7 @@ class Pairwise:
 
     def ibs(self, type: str = "proportion", m: int = 0) -> np.ndarray:
         out = self._mat()
-        check(lib.tpg_pairwise_ibs(self.ctx.h, self.h, C.c_int(0 if type == "proportion" else 1), C.c_int64(m), _ptr(out)))
+        check(lib.tpg_pairwise_ibs(self.ctx.h, self.h, 0 if type == "proportion" else 1, m, _ptr(out)))
         return out
 
     def king(self) -> np.ndarray:
@@ -382,7 +380,7 @@ class Pairwise:
         """IBS, KING, allele sharing and GRM from one pass over the accumulators"""
         names = ("ibs", "king", "allele_sharing", "grm")
         outs = {k: self._mat() for k in which}
-        check(lib.tpg_pairwise_epilogues(self.ctx.h, self.h, C.c_int(0 if ibs_type == "proportion" else 1), C.c_int64(m),
+        check(lib.tpg_pairwise_epilogues(self.ctx.h, self.h, 0 if ibs_type == "proportion" else 1, m,
                                          *[_ptr(outs.get(k)) for k in names]))
         return outs
 
@@ -415,7 +413,7 @@ class Comm:
     def init_rank(cls, ctx: Context, nranks: int, rank: int, unique_id: Optional[bytes]) -> "Comm":
         h = C.c_void_p()
         idbuf = (C.c_uint8 * 128).from_buffer_copy(unique_id) if unique_id is not None else None
-        check(lib.tpg_comm_init_rank(ctx.h, C.c_int(nranks), C.c_int(rank), idbuf, C.byref(h)))
+        check(lib.tpg_comm_init_rank(ctx.h, nranks, rank, idbuf, C.byref(h)))
         return cls(ctx, h, nranks, rank)
 
     @classmethod
@@ -453,21 +451,21 @@ class Comm:
 
         cb = _lib.HOST_ALLREDUCE(_cb)
         h = C.c_void_p()
-        check(lib.tpg_comm_init_host(ctx.h, C.c_int(nranks), C.c_int(rank), cb, None, C.byref(h)))
+        check(lib.tpg_comm_init_host(ctx.h, nranks, rank, cb, None, C.byref(h)))
         return cls(ctx, h, nranks, rank, keep=cb)
 
     def shard_loci(self, m_total: int):
         b, e = C.c_int64(), C.c_int64()
-        check(lib.tpg_shard_loci(C.c_int64(m_total), C.c_int(self.nranks), C.c_int(self.rank), C.byref(b), C.byref(e)))
+        check(lib.tpg_shard_loci(m_total, self.nranks, self.rank, C.byref(b), C.byref(e)))
         return b.value, e.value
 
     def allreduce_f64(self, buf, count: Optional[int] = None):
         """in-place sum over the ranks of a float64 numpy array, or of `count` doubles at a device pointer"""
         if isinstance(buf, np.ndarray):
             assert buf.dtype == np.float64 and buf.flags.c_contiguous or buf.flags.f_contiguous
-            check(lib.tpg_comm_allreduce_f64(self.ctx.h, self.h, _ptr(buf), C.c_int64(buf.size)))
+            check(lib.tpg_comm_allreduce_f64(self.ctx.h, self.h, _ptr(buf), buf.size))
             return buf
-        check(lib.tpg_comm_allreduce_f64(self.ctx.h, self.h, _ptr(buf), C.c_int64(int(count))))
+        check(lib.tpg_comm_allreduce_f64(self.ctx.h, self.h, _ptr(buf), int(count)))
         return buf
 
     def transport(self) -> str:
@@ -493,7 +491,7 @@ class ShardedPairwise(Pairwise):
     def __init__(self, comm: Comm, n: int):
         self.ctx, self.n, self.comm = comm.ctx, n, comm
         h = C.c_void_p()
-        check(lib.tpg_pairwise_create_sharded(comm.ctx.h, comm.h, C.c_int64(n), C.byref(h)))
+        check(lib.tpg_pairwise_create_sharded(comm.ctx.h, comm.h, n, C.byref(h)))
         self.h = h
 
     def reduce(self):
@@ -515,8 +513,8 @@ class ShardedPairwise(Pairwise):
     def epilogues(self, which=("ibs", "king", "allele_sharing", "grm"), ibs_type: str = "proportion", m: int = 0) -> dict:
         names = ("ibs", "king", "allele_sharing", "grm")
         outs = {k: np.full((self.n, self.n), np.nan, order="F") for k in which}  # outside the band: left as NaN
-        check(lib.tpg_pairwise_epilogues_sharded(self.ctx.h, self.comm.h, self.h, C.c_int(0 if ibs_type == "proportion" else 1),
-                                                 C.c_int64(m), *[_ptr(outs.get(k)) for k in names]))
+        check(lib.tpg_pairwise_epilogues_sharded(self.ctx.h, self.comm.h, self.h, 0 if ibs_type == "proportion" else 1,
+                                                 m, *[_ptr(outs.get(k)) for k in names]))
         return outs
 
 
@@ -526,12 +524,12 @@ class Multi:
     def __init__(self, ndev: int, devices=None):
         h = C.c_void_p()
         dv = _i32(devices)
-        check(lib.tpg_multi_create(C.c_int(ndev), _ptr(dv), C.byref(h)))
+        check(lib.tpg_multi_create(ndev, _ptr(dv), C.byref(h)))
         self.h, self.ndev = h, ndev
 
     def transport(self) -> str:
         """transport of the device threads' communicators: 'none', 'host callback' or 'rccl: <library as loaded>'"""
-        return lib.tpg_comm_transport(C.c_void_p(lib.tpg_multi_comm(self.h, C.c_int(0)))).decode()
+        return lib.tpg_comm_transport(lib.tpg_multi_comm(self.h, 0)).decode()
 
     def pairwise(self, X_bytes, ind_row=None, ind_col=None, which=("ibs", "king", "allele_sharing", "grm"),
                  ibs_type: str = "proportion") -> dict:
@@ -543,8 +541,8 @@ class Multi:
         m = X_bytes.shape[1] if c is None else len(c)
         names = ("ibs", "king", "allele_sharing", "grm")
         outs = {k: np.full((n, n), np.nan, order="F") for k in which}
-        check(lib.tpg_multi_pairwise(self.h, _ptr(X_bytes), C.c_int64(X_bytes.shape[0]), C.c_int64(X_bytes.shape[1]),
-                                     _ptr(r), C.c_int64(n), _ptr(c), C.c_int64(m), C.c_int(0 if ibs_type == "proportion" else 1),
+        check(lib.tpg_multi_pairwise(self.h, _ptr(X_bytes), X_bytes.shape[0], X_bytes.shape[1],
+                                     _ptr(r), n, _ptr(c), m, 0 if ibs_type == "proportion" else 1,
                                      *[_ptr(outs.get(k)) for k in names]))
         return outs
 
@@ -555,8 +553,7 @@ class Multi:
         r, c = _i32(ind_row), _i32(ind_col)
         n = X_bytes.shape[0] if r is None else len(r)
         m = X_bytes.shape[1] if c is None else len(c)
-        args = (_ptr(X_bytes), C.c_int64(X_bytes.shape[0]), C.c_int64(X_bytes.shape[1]), _ptr(r), C.c_int64(n), _ptr(c),
-                C.c_int64(m))
+        args = (_ptr(X_bytes), X_bytes.shape[0], X_bytes.shape[1], _ptr(r), n, _ptr(c), m)
         return args, n, m, (X_bytes, r, c)
 
     def loci_alt_freq(self, X_bytes, ind_row=None, ind_col=None, groupIds=None, ngroups: int = 0, ploidy=None,
@@ -566,8 +563,8 @@ class Multi:
         gid, code = _i32(groupIds), _f64(code256)
         pl = np.full(n, 2.0) if ploidy is None else _f64(ploidy)
         out = np.zeros((m, 2 * ngroups if gid is not None else 2), order="F")
-        check(lib.tpg_multi_grouped_alt_freq(self.h, *args, _ptr(code), _ptr(gid), C.c_int(ngroups), _ptr(pl),
-                                             C.c_int(int(as_counts)), _ptr(out)))
+        check(lib.tpg_multi_grouped_alt_freq(self.h, *args, _ptr(code), _ptr(gid), ngroups, _ptr(pl),
+                                             int(as_counts), _ptr(out)))
         return out
 
     def pairwise_pop_fst(self, X_bytes, ind_row, ind_col, groupIds, ngroups: int, ploidy=None, method: str = "Hudson",
@@ -582,9 +579,9 @@ class Multi:
         gid, code = _i32(groupIds), _f64(code256)
         pl = np.full(n, 2.0) if ploidy is None else _f64(ploidy)
         tot, a, b = _fst_outputs(m, P, by_locus, return_num_dem)
-        check(lib.tpg_multi_pop_fst(self.h, *args, _ptr(code), _ptr(gid), C.c_int(ngroups), _ptr(pl),
-                                    C.c_int(FST_METHODS[method]), _ptr(pairs_c), C.c_int(P), C.c_int(int(by_locus)),
-                                    C.c_int(int(return_num_dem)), _ptr(tot), _ptr(a), _ptr(b)))
+        check(lib.tpg_multi_pop_fst(self.h, *args, _ptr(code), _ptr(gid), ngroups, _ptr(pl),
+                                    FST_METHODS[method], _ptr(pairs_c), P, int(by_locus),
+                                    int(return_num_dem), _ptr(tot), _ptr(a), _ptr(b)))
         return _fst_result(tot, a, b, by_locus, return_num_dem)
 
     def gt_pca_partialSVD(self, X_bytes, ind_row=None, ind_col=None, k: int = 10, total_var: bool = True,
@@ -597,7 +594,7 @@ class Multi:
         vl = np.zeros((m, k), order="F")
         center, scale = np.zeros(m), np.zeros(m)
         fro = C.c_double()
-        check(lib.tpg_multi_pca_partial_svd(self.h, *args, _ptr(code), C.c_int(k), _ptr(d), _ptr(u), _ptr(vl), _ptr(center),
+        check(lib.tpg_multi_pca_partial_svd(self.h, *args, _ptr(code), k, _ptr(d), _ptr(u), _ptr(vl), _ptr(center),
                                             _ptr(scale), C.byref(fro) if total_var else None))
         out = dict(d=d, u=u, v=vl, center=center, scale=scale, method="partialSVD")
         if total_var:
@@ -634,15 +631,14 @@ class Stream:
         if a.dtype != np.uint8 or a.ndim != 2 or not a.flags.f_contiguous:
             raise TypeError("FBM bytes must be a 2-D uint8 array in Fortran order (individuals x loci)")
         h = C.c_void_p()
-        check(lib.tpg_stream_open_host(ctx.h, _ptr(a), C.c_int64(a.shape[0]), C.c_int64(a.shape[1]),
-                                       C.c_size_t(int(budget_bytes)), C.byref(h)))
+        check(lib.tpg_stream_open_host(ctx.h, _ptr(a), a.shape[0], a.shape[1], int(budget_bytes), C.byref(h)))
         return cls(ctx, h, a.shape[0], a.shape[1], keep=a)
 
     @classmethod
     def open_bk(cls, path: str, nrow: int, ncol: int, budget_bytes: int = 0, ctx: Optional[Context] = None) -> "Stream":
         ctx = ctx or default_context()
         h = C.c_void_p()
-        check(lib.tpg_stream_open_bk(ctx.h, path.encode(), C.c_int64(nrow), C.c_int64(ncol), C.c_size_t(int(budget_bytes)),
+        check(lib.tpg_stream_open_bk(ctx.h, path.encode(), nrow, ncol, int(budget_bytes),
                                      C.byref(h)))
         return cls(ctx, h, nrow, ncol)
 
@@ -650,7 +646,7 @@ class Stream:
     def open_bed(cls, path: str, n: int, m: int, budget_bytes: int = 0, ctx: Optional[Context] = None) -> "Stream":
         ctx = ctx or default_context()
         h = C.c_void_p()
-        check(lib.tpg_stream_open_bed(ctx.h, path.encode(), C.c_int64(n), C.c_int64(m), C.c_size_t(int(budget_bytes)),
+        check(lib.tpg_stream_open_bed(ctx.h, path.encode(), n, m, int(budget_bytes),
                                       C.byref(h)))
         return cls(ctx, h, n, m)
 
@@ -661,7 +657,7 @@ class Stream:
         a = np.ascontiguousarray(payload, dtype=np.uint8)
         assert a.size == m * ((n + 3) // 4)
         h = C.c_void_p()
-        check(lib.tpg_stream_open_bed_host(ctx.h, _ptr(a), C.c_int64(n), C.c_int64(m), C.c_size_t(int(budget_bytes)),
+        check(lib.tpg_stream_open_bed_host(ctx.h, _ptr(a), n, m, int(budget_bytes),
                                            C.byref(h)))
         return cls(ctx, h, n, m, keep=a)
 
@@ -672,8 +668,8 @@ class Stream:
         ctx = ctx or default_context()
         thr = min(int(round(miss * 2 ** 32)), 2 ** 32 - 1)
         h = C.c_void_p()
-        check(lib.tpg_stream_open_synth(ctx.h, C.c_uint64(seed), C.c_int64(nrow), C.c_int64(ncol), C.c_int(npop),
-                                        C.c_uint32(thr), C.c_int(int(imputed_bytes)), C.c_size_t(int(budget_bytes)), C.byref(h)))
+        check(lib.tpg_stream_open_synth(ctx.h, seed, nrow, ncol, npop, thr, int(imputed_bytes), int(budget_bytes),
+                                        C.byref(h)))
         return cls(ctx, h, nrow, ncol)
 
     def run(self, ind_row=None, ind_col=None, pairwise=(), ibs_type: str = "proportion", code256=CODE_012, ploidy=None,
@@ -854,7 +850,7 @@ def snp_king(X: FBM, ind_row=None, ind_col=None, block_size=None):
 
 def as_pad_quirk_blocks(m: int, block_size: int) -> int:
     """blocks narrower than the widest when CutBySize(m, block_size) cuts m loci (R/local_reimplementations.R:13-15)"""
-    return int(lib.tpg_as_pad_quirk_blocks(C.c_int64(int(m)), C.c_int64(int(block_size))))
+    return int(lib.tpg_as_pad_quirk_blocks(int(m), int(block_size)))
 
 
 def _as_pass(X, ind_row, ind_col, block_size, emulate_as_pad_quirk):
@@ -883,8 +879,8 @@ def block_means(A, groupIds, ngroups: int, skip_diag: bool = True, ctx: Optional
     A = np.asfortranarray(A, dtype=np.float64)
     gid = _i32(groupIds)
     mean, cnt = np.zeros((ngroups, ngroups), order="F"), np.zeros((ngroups, ngroups), order="F")
-    check(lib.tpg_block_means(ctx.h, _ptr(A), C.c_int64(A.shape[0]), _ptr(gid), C.c_int(ngroups),
-                              C.c_int(int(skip_diag)), _ptr(mean), _ptr(cnt)))
+    check(lib.tpg_block_means(ctx.h, _ptr(A), A.shape[0], _ptr(gid), ngroups,
+                              int(skip_diag), _ptr(mean), _ptr(cnt)))
     return mean, cnt
 
 
@@ -950,7 +946,7 @@ def filter_high_relatedness(matrix, kings_threshold, ids=None, ctx: Optional[Con
         n, mp = A.shape[0], _ptr(A)
     ids = np.array([str(k) for k in range(1, n + 1)]) if ids is None else np.asarray(ids)
     keep, order = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
-    check(lib.tpg_filter_high_relatedness(ctx.h, mp, C.c_int64(n), C.c_double(float(kings_threshold)), _ptr(keep),
+    check(lib.tpg_filter_high_relatedness(ctx.h, mp, n, float(kings_threshold), _ptr(keep),
                                           _ptr(order)))
     keepb = keep.astype(bool)
     passed = ids[order][keepb[order]]
@@ -977,7 +973,7 @@ def increment_as_counts(k, k2, X_bytes, rowInd, colInd, ctx: Optional[Context] =
     ctx = ctx or default_context()
     _increment(lib.tpg_increment_as_counts, k, k2, X_bytes, rowInd, colInd, ctx, flush)
     if emulate_as_pad_quirk and scratch_cols is not None and scratch_cols == len(colInd) + 1:
-        check(lib.tpg_increment_as_note_narrow_block(ctx.h, _ptr(k), C.c_int64(k.shape[0])))
+        check(lib.tpg_increment_as_note_narrow_block(ctx.h, _ptr(k), k.shape[0]))
 
 
 def increment_flush(ctx: Optional[Context] = None):
@@ -998,9 +994,9 @@ def _increment(fn, a, b, X_bytes, rowInd, colInd, ctx, flush):
     assert X_bytes.dtype == np.uint8 and X_bytes.flags.f_contiguous
     assert a.flags.f_contiguous and b.flags.f_contiguous and a.dtype == np.float64 and b.dtype == np.float64
     r, c = _i32(rowInd), _i32(colInd)
-    check(lib.tpg_increment_defer(ctx.h, C.c_int(int(not flush))))  # switching it off flushes what is pending
-    check(fn(ctx.h, _ptr(a), _ptr(b), _ptr(X_bytes), C.c_int64(X_bytes.shape[0]), C.c_int64(X_bytes.shape[1]),
-             _ptr(r), C.c_int64(len(r)), _ptr(c), C.c_int64(len(c))))
+    check(lib.tpg_increment_defer(ctx.h, int(not flush)))  # switching it off flushes what is pending
+    check(fn(ctx.h, _ptr(a), _ptr(b), _ptr(X_bytes), X_bytes.shape[0], X_bytes.shape[1],
+             _ptr(r), len(r), _ptr(c), len(c)))
 
 
 def _ploidy(v: View, ploidy):
@@ -1037,7 +1033,7 @@ def gt_grouped_pi_diploid(v: View, groupIds, ngroups: int) -> dict:
     """src/gt_grouped_pi_diploid.cpp:7-42"""
     pi, n = np.zeros((v.m, ngroups), order="F"), np.zeros((v.m, ngroups), order="F")
     gid = _i32(groupIds)
-    check(lib.tpg_gt_grouped_pi_diploid(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pi), _ptr(n)))
+    check(lib.tpg_gt_grouped_pi_diploid(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(pi), _ptr(n)))
     return dict(pi=pi, n=n)
 
 
@@ -1045,7 +1041,7 @@ def grouped_genotype_counts(v: View, groupIds, ngroups: int) -> np.ndarray:
     """the genotype table of gt_grouped_hwe (src/hwe.cpp:238-250) -> (3, m, G) int32: [k] = individuals with k alternate alleles"""
     out = np.zeros((3, ngroups, v.m), dtype=np.int32)  # three column-major m x G matrices
     gid = _i32(groupIds)
-    check(lib.tpg_grouped_genotype_counts(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(out)))
+    check(lib.tpg_grouped_genotype_counts(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(out)))
     return np.ascontiguousarray(out.transpose(0, 2, 1))
 
 
@@ -1058,7 +1054,7 @@ def hwe_on_matrix(geno_counts, midp, ctx: Optional[Context] = None) -> np.ndarra
         raise ValueError("geno_counts must have the rows hom1, het, hom2")
     counts = np.ascontiguousarray(g[:3].T, dtype=np.int32)  # column-major 3 x m
     out = np.zeros(counts.shape[0])
-    check(lib.tpg_hwe_exact_counts(ctx.h, _ptr(counts), C.c_int64(counts.shape[0]), C.c_int(int(bool(midp))), _ptr(out)))
+    check(lib.tpg_hwe_exact_counts(ctx.h, _ptr(counts), counts.shape[0], bool(midp), _ptr(out)))
     return out
 
 
@@ -1071,7 +1067,7 @@ def gt_grouped_hwe(v: View, groupIds, ngroups: int, mid_p: bool = True) -> np.nd
     """src/hwe.cpp:220-253 -> (m, G) p-values; counts and tests both on the device (tpg_gt_grouped_hwe)"""
     out = np.zeros((v.m, ngroups), order="F")
     gid = _i32(groupIds)
-    check(lib.tpg_gt_grouped_hwe(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), C.c_int(int(bool(mid_p))), _ptr(out)))
+    check(lib.tpg_gt_grouped_hwe(v.ctx.h, v.h, _ptr(gid), ngroups, bool(mid_p), _ptr(out)))
     return out
 
 
@@ -1081,7 +1077,7 @@ def loci_hwe(X: FBM, ind_row=None, ind_col=None, mid_p: bool = True) -> np.ndarr
         raise ValueError("Not implemented for a single individual")
     v = View(X, ind_row, ind_col)
     out = np.zeros(v.m)
-    check(lib.tpg_loci_hwe(v.ctx.h, v.h, C.c_int(int(bool(mid_p))), _ptr(out)))
+    check(lib.tpg_loci_hwe(v.ctx.h, v.h, bool(mid_p), _ptr(out)))
     return out
 
 
@@ -1148,7 +1144,7 @@ def pop_global_stats(X: FBM, ind_row, ind_col, groupIds, ngroups: int, ploidy=No
     pl = _ploidy(v, ploidy)
     loc = np.zeros((v.m, 10), order="F") if by_locus else None
     ov = np.zeros(10)
-    check(lib.tpg_pop_global_stats(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl),
+    check(lib.tpg_pop_global_stats(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl),
                                    _ptr(loc) if by_locus else None, _ptr(ov)))
     return loc if by_locus else ov
 
@@ -1158,7 +1154,7 @@ def _pop_basic(X, ind_row, ind_col, groupIds, ngroups, ploidy, which, by_locus, 
     gid, pl = _i32(groupIds), _ploidy(v, ploidy)
     loc = np.zeros((v.m, ngroups), order="F") if by_locus else None
     cm = np.zeros(ngroups)
-    check(lib.tpg_pop_basic_stats(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl), C.c_int(which),
+    check(lib.tpg_pop_basic_stats(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl), which,
                                   _ptr(loc) if by_locus else None, _ptr(cm)))
     if not include_global:
         return loc if by_locus else cm
@@ -1204,7 +1200,7 @@ def alt_freq_dip_pseudo_cpp(v: View, ploidy=None, as_counts: bool = False) -> np
     """src/alt_freq_dip_pseudo_cpp.cpp:8-58 -> (m, 2)"""
     out = np.zeros((v.m, 2), order="F")
     pl = _ploidy(v, ploidy)
-    check(lib.tpg_alt_freq_dip_pseudo(v.ctx.h, v.h, _ptr(pl), C.c_int(int(as_counts)), _ptr(out)))
+    check(lib.tpg_alt_freq_dip_pseudo(v.ctx.h, v.h, _ptr(pl), int(as_counts), _ptr(out)))
     return out
 
 
@@ -1226,8 +1222,8 @@ def grouped_alt_freq_dip_pseudo_cpp(v: View, groupIds, ngroups: int, ploidy=None
     """src/grouped_alt_freq_dip_pseudo_cpp.cpp:8-58 -> (m, 2G)"""
     out = np.zeros((v.m, 2 * ngroups), order="F")
     gid, pl = _i32(groupIds), _ploidy(v, ploidy)
-    check(lib.tpg_grouped_alt_freq_dip_pseudo(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl),
-                                              C.c_int(int(as_counts)), _ptr(out)))
+    check(lib.tpg_grouped_alt_freq_dip_pseudo(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl),
+                                              int(as_counts), _ptr(out)))
     return out
 
 
@@ -1235,7 +1231,7 @@ def grouped_missingness_cpp(v: View, groupIds, ngroups: int):
     """src/grouped_missingness_cpp.cpp:8-33 -> (m, G)"""
     out = np.zeros((v.m, ngroups), order="F")
     gid = _i32(groupIds)
-    check(lib.tpg_grouped_missingness(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(out)))
+    check(lib.tpg_grouped_missingness(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(out)))
     return out
 
 
@@ -1243,7 +1239,7 @@ def grouped_summaries_dip_pseudo_cpp(v: View, groupIds, ngroups: int, ploidy=Non
     """src/grouped_summaries_dip_pseudo_cpp.cpp:11-63"""
     outs = [np.zeros((v.m, ngroups), order="F") for _ in range(4)]
     gid, pl = _i32(groupIds), _ploidy(v, ploidy)
-    check(lib.tpg_grouped_summaries_dip_pseudo(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl),
+    check(lib.tpg_grouped_summaries_dip_pseudo(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl),
                                                *[_ptr(o) for o in outs]))
     return dict(freq_alt=outs[0], freq_ref=outs[1], n=outs[2], het_obs=outs[3])
 
@@ -1287,14 +1283,14 @@ def pairwise_pop_fst(X: FBM, ind_row, ind_col, groupIds, ngroups: int, ploidy=No
         if by_locus:
             raise ValueError("sums = True returns totals only")
         sn, sd = np.zeros(P), np.zeros(P)
-        check(lib.tpg_pairwise_pop_fst_sums(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl),
-                                            C.c_int(FST_METHODS[method]), _ptr(pairs_c), C.c_int(P), _ptr(sn), _ptr(sd)))
+        check(lib.tpg_pairwise_pop_fst_sums(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl),
+                                            FST_METHODS[method], _ptr(pairs_c), P, _ptr(sn), _ptr(sd)))
         with np.errstate(invalid="ignore", divide="ignore"):
             return dict(fst_tot=sn / sd, sum_num=sn, sum_den=sd)
     tot, a, b = _fst_outputs(v.m, P, by_locus, return_num_dem)
-    check(lib.tpg_pairwise_pop_fst(v.ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl),
-                                   C.c_int(FST_METHODS[method]), _ptr(pairs_c), C.c_int(P), C.c_int(int(by_locus)),
-                                   C.c_int(int(return_num_dem)), _ptr(tot), _ptr(a), _ptr(b)))
+    check(lib.tpg_pairwise_pop_fst(v.ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl),
+                                   FST_METHODS[method], _ptr(pairs_c), P, int(by_locus),
+                                   int(return_num_dem), _ptr(tot), _ptr(a), _ptr(b)))
     return _fst_result(tot, a, b, by_locus, return_num_dem)
 
 
@@ -1346,8 +1342,8 @@ def _window_stats(ctx, x_ptr, m, ncol, wr, op, min_loci):
     stat = np.zeros((nw, ncol), order="F")
     nl = np.zeros((nw, ncol), dtype=np.int32, order="F")
     lo, hi, pad = wr["lo"], wr["hi"], wr["pad_na"]
-    check(lib.tpg_window_stats(ctx.h, x_ptr, C.c_int64(m), C.c_int(ncol), _ptr(lo), _ptr(hi), _ptr(pad), C.c_int64(nw),
-                               C.c_int(op), C.c_int(int(min_loci)), _ptr(stat), _ptr(nl)))
+    check(lib.tpg_window_stats(ctx.h, x_ptr, m, ncol, _ptr(lo), _ptr(hi), _ptr(pad), nw,
+                               op, int(min_loci), _ptr(stat), _ptr(nl)))
     return stat, nl
 
 
@@ -1392,8 +1388,8 @@ def windows_pairwise_pop_fst(X: FBM, ind_row, ind_col, groupIds, ngroups: int, c
     nbytes = 8 * v.m * P
     d_num, d_den = ctx.dev_alloc(nbytes), ctx.dev_alloc(nbytes)
     try:
-        check(lib.tpg_pairwise_pop_fst(ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl), C.c_int(FST_METHODS["Hudson"]),
-                                       _ptr(pairs_c), C.c_int(P), C.c_int(1), C.c_int(1), None, d_num, d_den))
+        check(lib.tpg_pairwise_pop_fst(ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl), FST_METHODS["Hudson"],
+                                       _ptr(pairs_c), P, 1, 1, None, d_num, d_den))
         num, _ = _window_stats(ctx, d_num, v.m, P, wr, 0, min_loci)
         den, _ = _window_stats(ctx, d_den, v.m, P, wr, 0, min_loci)
     finally:
@@ -1412,7 +1408,7 @@ def tajimas_d_from_sums(n_alleles: int, seg: int, k_hat: float) -> float:
     """R/pop_tajimas_d.R:151-166 from its additive pieces (tpg_tajimas_d_from_sums; host arithmetic, no device): seg and
     k_hat of shards or blocks of loci add up, D of the sums is D of the whole."""
     d = C.c_double()
-    check(lib.tpg_tajimas_d_from_sums(C.c_int64(int(n_alleles)), C.c_int64(int(seg)), C.c_double(float(k_hat)), C.byref(d)))
+    check(lib.tpg_tajimas_d_from_sums(int(n_alleles), int(seg), float(k_hat), C.byref(d)))
     return d.value
 
 
@@ -1437,7 +1433,7 @@ def pop_tajimas_d(X: FBM, ind_row=None, ind_col=None, groupIds=None, ngroups: in
     gid, G = _tajima_groups(v, groupIds, ngroups)
     pl = _f64(ploidy)
     d, seg, k = np.zeros(G), np.zeros(G, dtype=np.int64), np.zeros(G)
-    check(lib.tpg_pop_tajimas_d(v.ctx.h, v.h, _ptr(gid), C.c_int(G), _ptr(pl), _ptr(d), _ptr(seg), _ptr(k)))
+    check(lib.tpg_pop_tajimas_d(v.ctx.h, v.h, _ptr(gid), G, _ptr(pl), _ptr(d), _ptr(seg), _ptr(k)))
     if groupIds is None:
         return dict(tajimas_d=float(d[0]), seg=int(seg[0]), k_hat=float(k[0])) if return_sums else float(d[0])
     return dict(tajimas_d=d, seg=seg, k_hat=k) if return_sums else d
@@ -1455,8 +1451,8 @@ def tajima_windows(v: View, groupIds, ngroups, lo, hi, pad_na=None, min_loci: in
     pl = _f64(ploidy)
     d, k = np.zeros((nw, G), order="F"), np.zeros((nw, G), order="F")
     seg, nl = np.zeros((nw, G), dtype=np.int64, order="F"), np.zeros((nw, G), dtype=np.int32, order="F")
-    check(lib.tpg_windows_pop_tajimas_d(v.ctx.h, v.h, _ptr(gid), C.c_int(G), _ptr(pl), _ptr(lo), _ptr(hi), _ptr(pad),
-                                        C.c_int64(nw), C.c_int(int(min_loci)), _ptr(d), _ptr(seg), _ptr(k), _ptr(nl)))
+    check(lib.tpg_windows_pop_tajimas_d(v.ctx.h, v.h, _ptr(gid), G, _ptr(pl), _ptr(lo), _ptr(hi), _ptr(pad),
+                                        nw, int(min_loci), _ptr(d), _ptr(seg), _ptr(k), _ptr(nl)))
     return dict(tajimas_d=d, seg=seg, k_hat=k, n_loci=nl)
 
 
@@ -1584,8 +1580,8 @@ def f2_blocks(v: View, groupIds, ngroups, lo, hi, ploidy=None, maxmiss=0.0, minm
             else:
                 out[k] = np.zeros((G, G, nb), dtype=dtypes[k], order="F")
                 ptrs[k] = _ptr(out[k])
-        check(lib.tpg_f2_blocks(v.ctx.h, v.h, _ptr(gid), C.c_int(G), _ptr(pl), C.byref(pr), _ptr(lo), _ptr(hi), C.c_int64(nb),
-                                ptrs["f2"], ptrs["counts"], ptrs.get("ap", C.c_void_p(None)), ptrs.get("ap_counts", C.c_void_p(None)),
+        check(lib.tpg_f2_blocks(v.ctx.h, v.h, _ptr(gid), G, _ptr(pl), C.byref(pr), _ptr(lo), _ptr(hi), nb,
+                                ptrs["f2"], ptrs["counts"], ptrs.get("ap"), ptrs.get("ap_counts"),
                                 _ptr(nk)))
     except Exception:
         if on_device:
@@ -1632,7 +1628,7 @@ def f4_from_f2_blocks(f2, block_lengths, quads) -> dict:
     q = np.ascontiguousarray(np.asarray(quads, dtype=np.int32).reshape(-1, 4))
     nq = len(q)
     est, se, used = np.zeros(nq), np.zeros(nq), np.zeros(nq, dtype=np.int32)
-    check(lib.tpg_f4_jackknife(_ptr(f2), C.c_int(G), C.c_int64(nb), _ptr(bl), _ptr(q), C.c_int64(nq), _ptr(est), _ptr(se), _ptr(used)))
+    check(lib.tpg_f4_jackknife(_ptr(f2), G, nb, _ptr(bl), _ptr(q), nq, _ptr(est), _ptr(se), _ptr(used)))
     with np.errstate(invalid="ignore", divide="ignore"):
         z = est / se
     return dict(est=est, se=se, z=z, n_blocks=used)
@@ -1670,7 +1666,7 @@ def admix_em(v: View, K: int, Q0=None, F0=None, seed: int = 0, max_iter: int = 1
     trace = np.full(max(int(max_iter), 0) + 1, np.nan)
     ll, nit, conv = C.c_double(), C.c_int32(), C.c_int32()
     pl = _f64(ploidy)
-    check(lib.tpg_admix_em(v.ctx.h, v.h, _ptr(pl), C.c_int(K), C.byref(pr), _ptr(q0), _ptr(f0), _ptr(Q), _ptr(P), C.byref(ll),
+    check(lib.tpg_admix_em(v.ctx.h, v.h, _ptr(pl), K, C.byref(pr), _ptr(q0), _ptr(f0), _ptr(Q), _ptr(P), C.byref(ll),
                            _ptr(trace), C.byref(nit), C.byref(conv)))
     out = dict(Q=Q, P=P, loglik=ll.value, n_iter=int(nit.value), converged=bool(conv.value))
     if return_trace:
@@ -1686,7 +1682,7 @@ def admix_loglik(v: View, Q, P) -> float:
     K = q.shape[1] if q.ndim == 2 else 0
     q, p = _admix_mat(q, v.n, K, "Q"), _admix_mat(P, v.m, K, "P")
     ll = C.c_double()
-    check(lib.tpg_admix_loglik(v.ctx.h, v.h, C.c_int(K), _ptr(q), _ptr(p), C.byref(ll)))
+    check(lib.tpg_admix_loglik(v.ctx.h, v.h, K, _ptr(q), _ptr(p), C.byref(ll)))
     return ll.value
 
 
@@ -1753,14 +1749,14 @@ def nwise_pop_pbs(X: FBM, ind_row, ind_col, groupIds, ngroups: int, ploidy=None,
     tot = np.zeros(P)
     d_fst = ctx.dev_alloc(8 * v.m * P)
     try:
-        check(lib.tpg_pairwise_pop_fst(ctx.h, v.h, _ptr(gid), C.c_int(ngroups), _ptr(pl), C.c_int(FST_METHODS[fst_method]),
-                                       _ptr(pairs_c), C.c_int(P), C.c_int(1), C.c_int(0), _ptr(tot), d_fst, None))
+        check(lib.tpg_pairwise_pop_fst(ctx.h, v.h, _ptr(gid), ngroups, _ptr(pl), FST_METHODS[fst_method],
+                                       _ptr(pairs_c), P, 1, 0, _ptr(tot), d_fst, None))
         out = np.zeros((v.m, 6 * len(trips)), order="F")
-        check(lib.tpg_pbs_from_fst(ctx.h, d_fst, C.c_int64(v.m), C.c_int(P), _ptr(tcols), C.c_int(len(trips)), _ptr(out)))
+        check(lib.tpg_pbs_from_fst(ctx.h, d_fst, v.m, P, _ptr(tcols), len(trips), _ptr(out)))
         res = dict(pbs=out)
         if return_fst:
             f = np.zeros((v.m, P), order="F")
-            check(lib.tpg_dev_to_host(ctx.h, _ptr(f), d_fst, C.c_size_t(f.nbytes)))
+            check(lib.tpg_dev_to_host(ctx.h, _ptr(f), d_fst, f.nbytes))
             res["fst"] = f
     finally:
         ctx.dev_free(d_fst)
@@ -1780,9 +1776,9 @@ def _fst_loop(method, pairwise_combn, n, freq_alt, freq_ref, het_obs, by_locus, 
     m, G = n.shape
     mats = [None if x is None else np.asfortranarray(x, dtype=float) for x in (freq_alt, freq_ref, het_obs)]
     tot, a, b = _fst_outputs(m, P, by_locus or return_num_dem, return_num_dem)
-    check(lib.tpg_pairwise_fst_loop(ctx.h, C.c_int(FST_METHODS[method]), _ptr(pairs_c), C.c_int(P), C.c_int64(m),
-                                    C.c_int(G), _ptr(n), *[_ptr(x) for x in mats], C.c_int(int(by_locus)),
-                                    C.c_int(int(return_num_dem)), _ptr(tot), _ptr(a), _ptr(b)))
+    check(lib.tpg_pairwise_fst_loop(ctx.h, FST_METHODS[method], _ptr(pairs_c), P, m,
+                                    G, _ptr(n), *[_ptr(x) for x in mats], int(by_locus),
+                                    int(return_num_dem), _ptr(tot), _ptr(a), _ptr(b)))
     return _fst_result(tot, a, b, by_locus or return_num_dem, return_num_dem)
 
 
@@ -1824,7 +1820,7 @@ def sym_eig_topk(K, k: int, ctx: Optional[Context] = None):
     K = np.asfortranarray(K, dtype=float)
     n = K.shape[0]
     lam, U = np.zeros(k), np.zeros((n, k), order="F")
-    check(lib.tpg_sym_eig_topk(ctx.h, _ptr(K), C.c_int64(n), C.c_int(k), _ptr(lam), _ptr(U)))
+    check(lib.tpg_sym_eig_topk(ctx.h, _ptr(K), n, k, _ptr(lam), _ptr(U)))
     return lam, U
 
 
@@ -1834,7 +1830,7 @@ def pca_loadings(v: View, center, scale, U, d) -> np.ndarray:
     U = np.asfortranarray(U, dtype=float)
     k = U.shape[1]
     out = np.zeros((v.m, k), order="F")
-    check(lib.tpg_pca_loadings(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(U), _ptr(d), C.c_int(k), _ptr(out)))
+    check(lib.tpg_pca_loadings(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(U), _ptr(d), k, _ptr(out)))
     return out
 
 
@@ -1856,7 +1852,7 @@ def gt_pca_partialSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, total_var
     vl = np.zeros((v.m, k), order="F")
     center, scale = np.zeros(v.m), np.zeros(v.m)
     fro = C.c_double()
-    check(lib.tpg_pca_partial_svd(v.ctx.h, v.h, C.c_int(k), _ptr(d), _ptr(u), _ptr(vl), _ptr(center), _ptr(scale),
+    check(lib.tpg_pca_partial_svd(v.ctx.h, v.h, k, _ptr(d), _ptr(u), _ptr(vl), _ptr(center), _ptr(scale),
                                   C.byref(fro) if total_var else None))
     out = dict(d=d, u=u, v=vl, center=center, scale=scale, method="partialSVD")
     if total_var:
@@ -1911,7 +1907,7 @@ def ld_band_links(v: View, hi, thr_r2: float = 0.2, return_links: bool = False):
     width = int((hi - np.arange(v.m)).max(initial=0))
     bits = np.zeros((v.m, max(1, -(-width // 32))), dtype=np.uint32)
     links = C.c_int64()
-    check(lib.tpg_ld_band_links(v.ctx.h, v.h, _ptr(hi), C.c_double(thr_r2), _ptr(bits), C.c_int64(bits.shape[1]), C.byref(links)))
+    check(lib.tpg_ld_band_links(v.ctx.h, v.h, _ptr(hi), thr_r2, _ptr(bits), bits.shape[1], C.byref(links)))
     return (bits, int(links.value)) if return_links else bits
 
 
@@ -1924,7 +1920,7 @@ def ld_clump(v: View, hi, thr_r2: float = 0.2, S=None, exclude=None, return_repo
         raise ValueError("S and exclude must have one entry per locus of the view")
     keep = np.zeros(v.m, dtype=np.uint8)
     rep = _lib.LdReport()
-    check(lib.tpg_ld_clump(v.ctx.h, v.h, _ptr(hi), C.c_double(thr_r2), _ptr(s), _ptr(ex), _ptr(keep), C.byref(rep)))
+    check(lib.tpg_ld_clump(v.ctx.h, v.h, _ptr(hi), thr_r2, _ptr(s), _ptr(ex), _ptr(keep), C.byref(rep)))
     keep = keep.astype(bool)
     if return_report:
         return keep, {f: int(getattr(rep, f)) for f, _ in _lib.LdReport._fields_}
@@ -2001,7 +1997,7 @@ def roh_snp_status(v: View, chromosome, position, stride_words: Optional[int] = 
     chrom, pos = _roh_loci(v.m, chromosome, position)
     stride = -(-v.m // 32) if stride_words is None else int(stride_words)
     bits = np.full((v.n, stride), 0xFFFFFFFF, dtype=np.uint32)  # (every word is written: the library zeroes what it does not use)
-    check(lib.tpg_roh_snp_status(v.ctx.h, v.h, _ptr(chrom), _ptr(pos), C.byref(P), _ptr(bits), C.c_int64(stride)))
+    check(lib.tpg_roh_snp_status(v.ctx.h, v.h, _ptr(chrom), _ptr(pos), C.byref(P), _ptr(bits), stride))
     if return_bits:
         return bits
     return np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little")[:, :v.m].astype(bool)
@@ -2110,7 +2106,7 @@ def gt_pca_randomSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, tol: float
     vl = np.zeros((v.m, k), order="F")
     center, scale = np.zeros(v.m), np.zeros(v.m)
     fro = C.c_double()
-    check(lib.tpg_pca_random_svd(v.ctx.h, v.h, C.c_int(k), C.c_double(tol), _ptr(d), _ptr(u), _ptr(vl), _ptr(center),
+    check(lib.tpg_pca_random_svd(v.ctx.h, v.h, k, tol, _ptr(d), _ptr(u), _ptr(vl), _ptr(center),
                                  _ptr(scale), C.byref(fro) if total_var else None))
     out = dict(d=d, u=u, v=vl, center=center, scale=scale, method="randomSVD")
     if total_var:
@@ -2159,7 +2155,7 @@ def predict_gt_pca(pca: dict, X: Optional[FBM] = None, ind_row=None, ind_col=Non
     pairs = [(a, b) for a in range(L) for b in range(a, L)]
     tab = np.asfortranarray(np.stack([Vs[:, a] * Vs[:, b] for a, b in pairs], axis=1))
     masked = np.zeros((v.n, len(pairs)), order="F")
-    check(lib.tpg_fbm256_valid_prod(v.ctx.h, v.h, _ptr(tab), C.c_int(len(pairs)), _ptr(masked)))
+    check(lib.tpg_fbm256_valid_prod(v.ctx.h, v.h, _ptr(tab), len(pairs), _ptr(masked)))
     out = np.zeros((v.n, L), order="F")
     for i in range(v.n):
         A = np.zeros((L, L))
@@ -2181,7 +2177,7 @@ def _prod_and_rss(v: View, center, scale, V):
     XV = np.zeros((v.n, V.shape[1]), order="F")
     rss = np.zeros(v.n)
     center, scale = _f64(center), _f64(scale)
-    check(lib.tpg_fbm256_prod_and_rowSumsSq(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(V), C.c_int(V.shape[1]),
+    check(lib.tpg_fbm256_prod_and_rowSumsSq(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(V), V.shape[1],
                                             _ptr(XV), _ptr(rss)))
     return XV, rss
 
@@ -2196,7 +2192,7 @@ def fbm256_prod_and_rowSumsSq(X: FBM, ind_row, ind_col, center, scale, V, code25
     rss = np.zeros(v.n)
     center, scale = _f64(center), _f64(scale)
     check(lib.tpg_fbm256_prod_and_rowSumsSq(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(V),
-                                            C.c_int(V.shape[1]), _ptr(XV), _ptr(rss)))
+                                            V.shape[1], _ptr(XV), _ptr(rss)))
     return XV, rss
 
 

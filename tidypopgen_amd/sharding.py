@@ -28,7 +28,7 @@ def shard_loci(m_total: int, world: int, rank: int, align: int = 128):
     if world < 1 or not (0 <= rank < world) or align != 128:
         raise ValueError("bad world/rank")
     b, e = C.c_int64(), C.c_int64()
-    check(lib.tpg_shard_loci(C.c_int64(m_total), C.c_int(world), C.c_int(rank), C.byref(b), C.byref(e)))
+    check(lib.tpg_shard_loci(m_total, world, rank, C.byref(b), C.byref(e)))
     return b.value, e.value
 
 
@@ -37,7 +37,7 @@ def band_rows(n: int, world: int, rank: int):
     cover rows [row0, row1) x columns [row0, n) and the mirror image rows [row0, n) x columns [row0, row1)
     (tpg_pairwise_band_of).  The bands of all ranks tile the N x N matrices."""
     a, b = C.c_int64(), C.c_int64()
-    check(lib.tpg_pairwise_band_of(C.c_int64(n), C.c_int(world), C.c_int(rank), C.byref(a), C.byref(b)))
+    check(lib.tpg_pairwise_band_of(n, world, rank, C.byref(a), C.byref(b)))
     return a.value, b.value
 
 
