@@ -551,7 +551,11 @@ int tpg_pairwise_fst_loop(tpg_ctx* ctx, int method, const int32_t* pairs1, int P
  * (v valid, d = dosage-1, h heterozygous), from which every count matrix of
  * increment_ibs_counts / increment_king_numerator / increment_as_counts follows.
  * If ext_buffer != NULL it must be device memory of tpg_pairwise_buffer_bytes(n)
- * bytes (e.g. a torch tensor, so that the caller can all-reduce it over RCCL). */
+ * bytes (e.g. a torch tensor).  What the buffer holds is private: the matrix cores multiply the MISSING plane m = 1 - v, so
+ * the sums in it are MM = mm' and HM = hm', and the count / epilogue entry points rebuild V = L - m_i - m_j + MM_ij and
+ * A = Hc_i - HM_ij from them, the diagonals and the number L of loci the accumulators have seen.  L is not in the buffer: buffers
+ * of several ranks are summed by tpg_pairwise_create_sharded + tpg_pairwise_reduce (which sums L with them), not by an
+ * all-reduce of the caller's. */
 size_t tpg_pairwise_buffer_bytes(int64_t n);
 int tpg_pairwise_create(tpg_ctx* ctx, int64_t n, void* ext_buffer, tpg_pairwise** out);
 void tpg_pairwise_free(tpg_pairwise* pw);

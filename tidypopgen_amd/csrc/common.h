@@ -237,7 +237,10 @@ typedef std::unique_ptr<tpg_view> ViewPtr;
 
 // tile-packed int32 accumulators of the pairwise kernel: per unit (super-tile I of TPG_PW_TA row tiles, 32-column
 // tile jt >= TA I) 5 products x TA sub-tiles x 16 accumulator registers x 64 lanes (MFMA C/D order)
-#define TPG_PW_PRODUCTS 5  // V, D, H, HV (= A[i][j]), VH (= A[j][i])
+// The slabs hold what the matrix cores summed: MM = mm' (m = missing) where the outputs want V = vv', HM = hm' and MH = mh'
+// where they want A = hv' and its transpose; the readers rebuild V and A (pairwise.hip: tpg_pw_tile_counts).
+#define TPG_PW_PRODUCTS 5
+enum { TPG_PW_SLAB_MM = 0, TPG_PW_SLAB_D = 1 /* D, or D + H (TPG_PW_DH) */, TPG_PW_SLAB_H = 2, TPG_PW_SLAB_HM = 3, TPG_PW_SLAB_MH = 4 };
 #define TPG_PW_TA 3        // A row tiles per wave: 96 x 32 pairs, 15 accumulator tiles (240 AGPRs); see pairwise.hip
 #define TPG_PW_PLANE_INTS (TPG_PW_TA * 16 * 64)
 #define TPG_PW_TILE_INTS (TPG_PW_PRODUCTS * TPG_PW_PLANE_INTS)
@@ -255,9 +258,13 @@ struct tpg_pairwise {
   // Sharding over the ranks of a tpg_comm (comm.hip).  The slab of unit (I, jt) sits at tpg_pw_unit_index + rowpad[I]:
   // super-tile rows are dealt to the ranks in contiguous bands of (nearly) equal unit counts, every band padded to
   // `chunk_units` slabs, so that ONE reduce-scatter with equal counts leaves rank r with the sums of band r.  A
-  // single rank has one band, rowpad = 0 and chunk_units = ntp: the unsharded layout.
+  // single rank has one band, rowpad = 0 and chunk_units = ntp (+ tail_units): the unsharded layout.
+  // The last `tail_units` slabs of every chunk are not tiles: they take the diagonals MM_ii and D_ii of ALL individuals (two
+  // int32 vectors of 32 ceil(n / 32)), which V and A are rebuilt from.  A rank's band does not hold the diagonal tiles of the
+  // columns to its right, so before the reduce-scatter every rank copies its partial diagonals into the tail of every chunk:
+  // the one it gets back holds their sums.
   int nranks = 1, rank = 0;
-  int64_t chunk_units = 0;
+  int64_t chunk_units = 0, tail_units = 0;
   std::vector<int32_t> band;   // nranks + 1 super-tile boundaries: band r = rows [band[r], band[r + 1])
   int64_t* rowpad = nullptr;   // device int64[nst]
   bool reduced = false;        // after tpg_pairwise_reduce: only this rank's band holds (complete) sums

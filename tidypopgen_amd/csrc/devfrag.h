@@ -22,54 +22,56 @@ __device__ __forceinline__ int tpg_lut(uint32_t lut, uint32_t codes) {
 }
 
 // FP4 operand nibble of the pairwise kernel (pairwise.hip): one magnitude bit per operand plane -- 0x1 = FP4 0.5, 0x2 = 1.0,
-// 0x4 = 2.0 -- for heterozygous (h), typed (v) and homozygous (d), bit 3 = the sign of d (dosage 0).  Which plane takes which
+// 0x4 = 2.0 -- for heterozygous (h), MISSING (m) and homozygous (d), bit 3 = the sign of d (dosage 0).  Which plane takes which
 // magnitude does not change a single sum (the E8M0 block scales undo it: TPG_T4_SC_*), only the bit patterns the matrix cores
 // multiply -- and their clock under the MFMAs is a POWER limit that depends on those (tools/pw_power_probe.py), so the
-// assignment is a compile-time choice that was measured (TPG_T4_ENC, tools/enc_ab.py): 0 = h 0.5, v 1, d 2 (rounds 2 - 4).
+// assignment is a compile-time choice that was measured (TPG_T4_ENC, tools/enc_ab.py): 0 = h 0.5, m 1, d 2 (rounds 2 - 4).
+// For the same reason the plane that three of the five products multiply marks the missing genotypes (a few percent of
+// ones), not the typed ones: V = vv' and A = hv' are rebuilt from MM = mm' and HM = hm' by the epilogues (pairwise.hip).
 #ifndef TPG_T4_ENC
 #define TPG_T4_ENC 0
 #endif
 #if TPG_T4_ENC == 0
 #define TPG_T4_MH 1u
-#define TPG_T4_MV 2u
+#define TPG_T4_MM 2u
 #define TPG_T4_MD 4u
 #elif TPG_T4_ENC == 1
 #define TPG_T4_MH 1u
-#define TPG_T4_MV 4u
+#define TPG_T4_MM 4u
 #define TPG_T4_MD 2u
 #elif TPG_T4_ENC == 2
 #define TPG_T4_MH 2u
-#define TPG_T4_MV 1u
+#define TPG_T4_MM 1u
 #define TPG_T4_MD 4u
 #elif TPG_T4_ENC == 3
 #define TPG_T4_MH 2u
-#define TPG_T4_MV 4u
+#define TPG_T4_MM 4u
 #define TPG_T4_MD 1u
 #elif TPG_T4_ENC == 4
 #define TPG_T4_MH 4u
-#define TPG_T4_MV 1u
+#define TPG_T4_MM 1u
 #define TPG_T4_MD 2u
 #else
 #define TPG_T4_MH 4u
-#define TPG_T4_MV 2u
+#define TPG_T4_MM 2u
 #define TPG_T4_MD 1u
 #endif
-// 2-bit code -> nibble: dosage 0 -> v | d | sign, 1 -> v | h, 2 -> v | d, missing -> 0  (0x0006030E for TPG_T4_ENC = 0)
-#ifndef TPG_T4_VMISS
-#define TPG_NIB_LUT ((TPG_T4_MV | TPG_T4_MD | 8u) | ((TPG_T4_MV | TPG_T4_MH) << 8) | ((TPG_T4_MV | TPG_T4_MD) << 16))
-#else
-// TIMING EXPERIMENT (round 6, wrong sums): the "v" bit marks the MISSING genotypes instead of the typed ones, i.e. the plane
-// that three of the five products multiply is 2 % ones instead of 98 % -- what the complement form V = L - m_i - m_j + MM,
-// HV = H_ii - HM would feed the matrix cores -- to see what the power-limited clock does with it (DESIGN.md 3.1 "Round 6")
-#define TPG_NIB_LUT ((TPG_T4_MD | 8u) | ((TPG_T4_MH) << 8) | ((TPG_T4_MD) << 16) | ((TPG_T4_MV) << 24))
-#endif
+// 2-bit code -> nibble: dosage 0 -> d | sign, 1 -> h, 2 -> d, missing (3) -> m  (0x0204010C for TPG_T4_ENC = 0).  PADDING
+// (individuals >= n, loci >= m) is nibble 0: it contributes nothing to any plane.  The 2-bit layouts code padding as 3 like
+// a missing genotype, so whoever makes nibbles tells the two apart by position (tpg_t4_keep).
+#define TPG_NIB_LUT ((TPG_T4_MD | 8u) | ((TPG_T4_MH) << 8) | ((TPG_T4_MD) << 16) | ((TPG_T4_MM) << 24))
 // E8M0 block scale (all four bytes equal) that turns a plane of magnitude bit M into 0 / +-1: 0.5 x 2, 1 x 1, 2 x 0.5
 #define TPG_T4_SC(M) ((M) == 1u ? (int)0x80808080 : (M) == 2u ? 0x7f7f7f7f : 0x7e7e7e7e)
-// one T dword (16 codes) -> two T4 dwords (16 nibbles)
-__device__ __forceinline__ void tpg_t4_words(uint32_t w, uint32_t& lo, uint32_t& hi) {
+// byte mask of the elements 4 k + b (b = 0..3) of a T dword that lie inside the data when `left` elements of the dword do
+__device__ __forceinline__ uint32_t tpg_t4_keep(int64_t left, int k) {
+  const int64_t c = left - 4 * k;
+  return c >= 4 ? 0xFFFFFFFFu : c <= 0 ? 0u : (1u << (8 * (int)c)) - 1u;
+}
+// one T dword (16 codes) -> two T4 dwords (16 nibbles); `left` = how many of its 16 elements are data (the rest is padding)
+__device__ __forceinline__ void tpg_t4_words(uint32_t w, int64_t left, uint32_t& lo, uint32_t& hi) {
   uint32_t nb[4];
 #pragma unroll
-  for (int k = 0; k < 4; k++) nb[k] = (uint32_t)tpg_lut(TPG_NIB_LUT, tpg_codes(w, k));
+  for (int k = 0; k < 4; k++) nb[k] = (uint32_t)tpg_lut(TPG_NIB_LUT, tpg_codes(w, k)) & tpg_t4_keep(left, k);
   lo = nb[0] | (nb[1] << 4);
   hi = nb[2] | (nb[3] << 4);
 }

@@ -378,9 +378,9 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
         const int sT = g >> 1;
         uint32_t* dst4 = T4v + (((rt * KG + bj) * 2 + (sT >> 1)) * 64 + 4 * iqq + 32 * (g & 1)) * 4 + 2 * (sT & 1);
 #pragma unroll
-        for (int b = 0; b < 4; b++) {
+        for (int b = 0; b < 4; b++) {  // lane 4 iqq + b (+ 32 (g & 1)): individual 32 rt + 4 iqq + b, loci 128 bj + 16 g ...
           uint32_t lo, hi;
-          tpg_t4_words(W[b], lo, hi);
+          tpg_t4_words(W[b], rt * 32 + 4 * iqq + b < n ? m - (bj * TILE + 16 * g) : 0, lo, hi);
           *reinterpret_cast<uint2*>(dst4 + b * 4) = make_uint2(lo, hi);
         }
       }
@@ -397,6 +397,15 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
         N[k][1] = (uint32_t)tpg_lut(TPG_NIB_LUT, __builtin_amdgcn_perm(t2, t0, 0x07060302u));
         N[k][2] = (uint32_t)tpg_lut(TPG_NIB_LUT, __builtin_amdgcn_perm(t3, t1, 0x05040100u));
         N[k][3] = (uint32_t)tpg_lut(TPG_NIB_LUT, __builtin_amdgcn_perm(t3, t1, 0x07060302u));
+      }
+      // padding is nibble 0, not the nibble of a missing genotype (devfrag.h): workgroup-uniform test, nothing to do inside the data
+      if (!(bj * TILE + TILE <= m && bi * TILE + TILE <= n)) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+          const int64_t left = rt * 32 + 4 * iqq + b < n ? m - (bj * TILE + 16 * g) : 0;
+#pragma unroll
+          for (int k = 0; k < 4; k++) N[k][b] &= tpg_t4_keep(left, k);
+        }
       }
       const int sT = g >> 1;
       gchar2* B4 = (gchar2*)tpg_pack_uniform64((int64_t)(T4v + ((rt * KG + bj) * 2) * 256));  // the two T4 blocks of (rt, kg)

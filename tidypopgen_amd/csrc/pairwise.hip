@@ -14,11 +14,18 @@
 // so the fused pass needs 3 symmetric + 1 general product = 2.5 N^2 M MACs instead of the
 // reference's 12 N^2 M FP64 flops for IBS+KING+AS.
 //
+// The matrix cores do not multiply v, which is nearly all ones, but its complement m = 1 - v (missing): the clock they hold
+// is a power limit that follows the operand bits, and a plane of 2 % ones switches less than one of 98 %.
+// With MM = mm' and HM = hm' (same instructions, same slabs), L loci accumulated, m_i = MM_ii missing genotypes and
+// Hc_i = L - MM_ii - D_ii heterozygous calls of individual i (every typed genotype is het or hom: D_ii + H_ii = L - m_i)
+//   V_ij = L - m_i - m_j + MM_ij        A_ij = Hc_i - HM_ij
+// exactly, in integers: the epilogues rebuild V and A (tpg_pw_tile_counts) before the formulas above.
+//
 // The features are small enough for FP4 (E2M1: 0, 0.5, 1, 1.5, 2, 3, 4, 6 and their negatives), whose MFMA
 // (v_mfma_scale_f32_32x32x64_f8f6f4) contracts 64 loci in the 32 cycles the int8 form needs for 32.  The view's T
 // layout is re-coded once (tpg_t4_expand_kernel) with one NIBBLE per genotype whose bits ARE the three operand planes:
 //   bit 0 = heterozygous            plane h = nibble & 0x1 -> FP4 0.5
-//   bit 1 = typed                   plane v = nibble & 0x2 -> FP4 1.0
+//   bit 1 = missing                 plane m = nibble & 0x2 -> FP4 1.0   (padding: nibble 0)
 //   bit 2 = homozygous              plane d = nibble & 0xC -> FP4 +2.0 (dosage 2) / -2.0 (dosage 0: bit 3 = sign)
 // so a plane of 8 loci costs ONE v_and_b32 (the int8 form of this kernel spent 19 VALU per 16 loci on v_perm lookups
 // and was bound by VALU issue at 36.6 cycles per MFMA).  The E8M0 block scales of the instruction undo the 0.5 / 2.0
@@ -53,12 +60,12 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
-#define TPG_NIB_V (TPG_T4_MV * 0x11111111u)
+#define TPG_NIB_M (TPG_T4_MM * 0x11111111u)
 #define TPG_NIB_H (TPG_T4_MH * 0x11111111u)
 #define TPG_NIB_D ((TPG_T4_MD | 8u) * 0x11111111u)
 // E8M0 block scales (one byte per 32 contracted elements; all four bytes equal, so the byte select does not matter): the
-// kernels' sc1 / sc2 / sch are the scales of the v / h / d planes (1, 2, 1/2 with the encoding of rounds 2 - 4)
-#define TPG_SC_ONE TPG_T4_SC(TPG_T4_MV)
+// kernels' sc1 / sc2 / sch are the scales of the m / h / d planes (1, 2, 1/2 with the encoding of rounds 2 - 4)
+#define TPG_SC_ONE TPG_T4_SC(TPG_T4_MM)
 #define TPG_SC_TWO TPG_T4_SC(TPG_T4_MH)
 #define TPG_SC_HALF TPG_T4_SC(TPG_T4_MD)
 
@@ -71,30 +78,35 @@ __device__ __forceinline__ v8i tpg_w8(v4i a) { return v8i{a[0], a[1], a[2], a[3]
 // fragments of 32 nibbles: dwords 0, 1 -> block 2 kg, dwords 2, 3 -> block 2 kg + 1.  Which locus lands on which
 // nibble of which lane half is immaterial -- the MFMA sums over all 64 -- as long as every row tile uses the same
 // map, which it does.
+// T codes padding (individuals >= n, loci >= m) as 3 like a missing genotype; its nibble is 0, a missing genotype's is the m bit:
+// block (rt, kg), lane (r, h), dword s holds individual 32 rt + r, loci 128 kg + 32 s + 16 h ... + 15 (common.h).
 __global__ __launch_bounds__(256) void tpg_t4_expand_kernel(const uint4* __restrict__ T, uint4* __restrict__ T4,
-                                                            int64_t nblocks) {
+                                                            int64_t nblocks, int64_t KG, int64_t n, int64_t m) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nblocks * 64; i += (int64_t)gridDim.x * 256) {
     const int64_t blk = i >> 6;
     const int lane = (int)(i & 63);
     const uint4 w = T[i];
     const uint32_t in[4] = {w.x, w.y, w.z, w.w};
+    const int64_t rt = blk / KG, kg = blk - rt * KG;
+    const bool row_in = rt * 32 + (lane & 31) < n;
     uint32_t out[8];
 #pragma unroll
-    for (int s = 0; s < 4; s++) tpg_t4_words(in[s], out[2 * s], out[2 * s + 1]);
+    for (int s = 0; s < 4; s++)
+      tpg_t4_words(in[s], row_in ? m - (kg * 128 + 32 * s + 16 * (lane >> 5)) : 0, out[2 * s], out[2 * s + 1]);
     T4[(blk * 2) * 64 + lane] = make_uint4(out[0], out[1], out[2], out[3]);
     T4[(blk * 2 + 1) * 64 + lane] = make_uint4(out[4], out[5], out[6], out[7]);
   }
 }
 
 struct Frag3 {
-  v4i v, d, h;
+  v4i m, d, h;
 };
 
-__device__ __forceinline__ Frag3 tpg_planes(v4u w, uint32_t mv, uint32_t md, uint32_t mh) {
+__device__ __forceinline__ Frag3 tpg_planes(v4u w, uint32_t mm, uint32_t md, uint32_t mh) {
   Frag3 f;
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    f.v[k] = (int)(w[k] & mv);
+    f.m[k] = (int)(w[k] & mm);
     f.d[k] = (int)(w[k] & md);
     f.h[k] = (int)(w[k] & mh);
   }
@@ -163,11 +175,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_kernel(const uint4* __res
     }
     const char* pb0 = (const char*)(T4 + (((int64_t)jt * KG + k0) * 2) * 64);
 
-    v16f cV[TA], cD[TA], cH[TA], cHV[TA], cVH[TA];
+    v16f cMM[TA], cD[TA], cH[TA], cHM[TA], cMH[TA];
 #pragma unroll
     for (int t = 0; t < TA; t++)
 #pragma unroll
-      for (int r = 0; r < 16; r++) { cV[t][r] = 0.f; cD[t][r] = 0.f; cH[t][r] = 0.f; cHV[t][r] = 0.f; cVH[t][r] = 0.f; }
+      for (int r = 0; r < 16; r++) { cMM[t][r] = 0.f; cD[t][r] = 0.f; cH[t][r] = 0.f; cHM[t][r] = 0.f; cMH[t][r] = 0.f; }
 
     if (k0 < k1) {
       const int kl = k1 - 1;
@@ -202,8 +214,8 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_kernel(const uint4* __res
       Frag3 P[2][TA + 1];
 #pragma unroll
       for (int t = 0; t < TA; t++)
-        P[0][t] = tpg_planes(RA[0][t][0], there[t] ? TPG_NIB_V : 0u, there[t] ? TPG_NIB_D : 0u, there[t] ? TPG_NIB_H : 0u);
-      P[0][TA] = tpg_planes(RB[0][0], TPG_NIB_V, TPG_NIB_D, TPG_NIB_H);
+        P[0][t] = tpg_planes(RA[0][t][0], there[t] ? TPG_NIB_M : 0u, there[t] ? TPG_NIB_D : 0u, there[t] ? TPG_NIB_H : 0u);
+      P[0][TA] = tpg_planes(RB[0][0], TPG_NIB_M, TPG_NIB_D, TPG_NIB_H);
       // TAIL = false: a group of the main loop, whose groups kg and kg + 1 lie inside the K range: no plane mask depends on
       // the position (the masks of an absent A tile are loop-invariant SGPRs); TAIL = true: the last, partial body
       auto group = [&](auto Cc, auto Nn, auto Mm, auto Tl, int kg) {
@@ -223,20 +235,20 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_kernel(const uint4* __res
 #pragma unroll
           for (int t = 0; t < TA; t++) {
             const bool keep = there[t] && (s == 0 ? live : live1);
-            P[nx][t] = tpg_planes(s == 0 ? RA[C][t][1] : RA[N][t][0], keep ? TPG_NIB_V : 0u, keep ? TPG_NIB_D : 0u,
+            P[nx][t] = tpg_planes(s == 0 ? RA[C][t][1] : RA[N][t][0], keep ? TPG_NIB_M : 0u, keep ? TPG_NIB_D : 0u,
                                   keep ? TPG_NIB_H : 0u);
           }
-          P[nx][TA] = tpg_planes(s == 0 ? RB[C][1] : RB[N][0], TPG_NIB_V, TPG_NIB_D, TPG_NIB_H);
+          P[nx][TA] = tpg_planes(s == 0 ? RB[C][1] : RB[N][0], TPG_NIB_M, TPG_NIB_D, TPG_NIB_H);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cV[t] = MFMA_F4(P[cur][t].v, P[cur][TA].v, cV[t], sc1, sc1);
+          for (int t = 0; t < TA; t++) cMM[t] = MFMA_F4(P[cur][t].m, P[cur][TA].m, cMM[t], sc1, sc1);
 #pragma unroll
           for (int t = 0; t < TA; t++) cD[t] = MFMA_F4(P[cur][t].d, P[cur][TA].d, cD[t], sch, sch);
 #pragma unroll
           for (int t = 0; t < TA; t++) cH[t] = MFMA_F4(P[cur][t].h, P[cur][TA].h, cH[t], sc2, sc2);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cHV[t] = MFMA_F4(P[cur][t].h, P[cur][TA].v, cHV[t], sc2, sc1);
+          for (int t = 0; t < TA; t++) cHM[t] = MFMA_F4(P[cur][t].h, P[cur][TA].m, cHM[t], sc2, sc1);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cVH[t] = MFMA_F4(P[cur][t].v, P[cur][TA].h, cVH[t], sc1, sc2);
+          for (int t = 0; t < TA; t++) cMH[t] = MFMA_F4(P[cur][t].m, P[cur][TA].h, cMH[t], sc1, sc2);
           // 12 (TA + 1) plane masks and TA + 1 loads spread over the 5 TA MFMAs of the step
 #pragma unroll
           for (int q = 0; q < 5 * TA; q++) {
@@ -281,11 +293,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_kernel(const uint4* __res
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int o = (t * 16 + r) * 64;
-        atomicAdd(slab + 0 * TPG_PW_PLANE_INTS + o, (int)cV[t][r]);
-        atomicAdd(slab + 1 * TPG_PW_PLANE_INTS + o, (int)cD[t][r]);
-        atomicAdd(slab + 2 * TPG_PW_PLANE_INTS + o, (int)cH[t][r]);
-        atomicAdd(slab + 3 * TPG_PW_PLANE_INTS + o, (int)cHV[t][r]);
-        atomicAdd(slab + 4 * TPG_PW_PLANE_INTS + o, (int)cVH[t][r]);
+        atomicAdd(slab + TPG_PW_SLAB_MM * TPG_PW_PLANE_INTS + o, (int)cMM[t][r]);
+        atomicAdd(slab + TPG_PW_SLAB_D * TPG_PW_PLANE_INTS + o, (int)cD[t][r]);
+        atomicAdd(slab + TPG_PW_SLAB_H * TPG_PW_PLANE_INTS + o, (int)cH[t][r]);
+        atomicAdd(slab + TPG_PW_SLAB_HM * TPG_PW_PLANE_INTS + o, (int)cHM[t][r]);
+        atomicAdd(slab + TPG_PW_SLAB_MH * TPG_PW_PLANE_INTS + o, (int)cMH[t][r]);
       }
   }
 }
@@ -315,16 +327,16 @@ struct PwSet {
   static constexpr bool pV = (MASK & TPG_PW_V) != 0, pD = (MASK & TPG_PW_D) != 0, pH = (MASK & TPG_PW_H) != 0,
                         pA = (MASK & TPG_PW_A) != 0, pS = (MASK & TPG_PW_DH) != 0;
   static constexpr int NP = (pV ? 1 : 0) + (pD ? 1 : 0) + (pH ? 1 : 0) + (pA ? 2 : 0) + (pS ? 2 : 0);  // MFMAs per tile pair
-  static constexpr bool wv = pV || pA, wd = pD || pS, wh = pH || pA || pS;  // operand planes wanted
-  static constexpr int NPL = (wv ? 1 : 0) + (wd ? 1 : 0) + (wh ? 1 : 0);
+  static constexpr bool wm = pV || pA, wd = pD || pS, wh = pH || pA || pS;  // operand planes wanted
+  static constexpr int NPL = (wm ? 1 : 0) + (wd ? 1 : 0) + (wh ? 1 : 0);
 };
 
 template <int MASK>
-__device__ __forceinline__ Frag3 tpg_planes_of(v4u w, uint32_t mv, uint32_t md, uint32_t mh) {
+__device__ __forceinline__ Frag3 tpg_planes_of(v4u w, uint32_t mm, uint32_t md, uint32_t mh) {
   Frag3 f;
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    if constexpr (PwSet<MASK>::wv) f.v[k] = (int)(w[k] & mv);
+    if constexpr (PwSet<MASK>::wm) f.m[k] = (int)(w[k] & mm);
     if constexpr (PwSet<MASK>::wd) f.d[k] = (int)(w[k] & md);
     if constexpr (PwSet<MASK>::wh) f.h[k] = (int)(w[k] & mh);
   }
@@ -371,13 +383,13 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
       const int tile = t < RA ? RA * I + t : RB * J + (t - RA);
       pt[t] = (const char*)(T4 + ((int64_t)(tile < nct ? tile : 0) * KG * 2 + kb0) * 64);
     }
-    v16f cV[RA][RB], cD[RA][RB], cH[RA][RB], cHV[RA][RB], cVH[RA][RB];
+    v16f cMM[RA][RB], cD[RA][RB], cH[RA][RB], cHM[RA][RB], cMH[RA][RB];
 #pragma unroll
     for (int a = 0; a < RA; a++)
 #pragma unroll
       for (int b = 0; b < RB; b++)
 #pragma unroll
-        for (int r = 0; r < 16; r++) { cV[a][b][r] = 0.f; cD[a][b][r] = 0.f; cH[a][b][r] = 0.f; cHV[a][b][r] = 0.f; cVH[a][b][r] = 0.f; }
+        for (int r = 0; r < 16; r++) { cMM[a][b][r] = 0.f; cD[a][b][r] = 0.f; cH[a][b][r] = 0.f; cHM[a][b][r] = 0.f; cMH[a][b][r] = 0.f; }
 
     if (kb0 < kb1) {
       const int kl = kb1 - 1;
@@ -397,7 +409,7 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
       }
       Frag3 P[2][NT];
 #pragma unroll
-      for (int t = 0; t < NT; t++) P[0][t] = tpg_planes_of<MASK>(R[0][t], TPG_NIB_V, TPG_NIB_D, TPG_NIB_H);
+      for (int t = 0; t < NT; t++) P[0][t] = tpg_planes_of<MASK>(R[0][t], TPG_NIB_M, TPG_NIB_D, TPG_NIB_H);
       auto step = [&](auto Sc, int kb) {
         constexpr int s = decltype(Sc)::value, cur = s & 1, nx = cur ^ 1, sl = (s + 1) % NS, ld = (s + NS - 1) % NS;
         // the slot whose planes were taken in the previous step is free: block kb + NS - 1
@@ -407,17 +419,17 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
 #pragma unroll
         for (int t = 0; t < NT; t++) {
           const bool keep = t >= RA || live1;
-          P[nx][t] = tpg_planes_of<MASK>(R[sl][t], keep ? TPG_NIB_V : 0u, keep ? TPG_NIB_D : 0u, keep ? TPG_NIB_H : 0u);
+          P[nx][t] = tpg_planes_of<MASK>(R[sl][t], keep ? TPG_NIB_M : 0u, keep ? TPG_NIB_D : 0u, keep ? TPG_NIB_H : 0u);
         }
 #pragma unroll
         for (int a = 0; a < RA; a++)
 #pragma unroll
           for (int b = 0; b < RB; b++) {
-            if constexpr (PS::pV) cV[a][b] = MFMA_F4(P[cur][a].v, P[cur][RA + b].v, cV[a][b], sc1, sc1);
+            if constexpr (PS::pV) cMM[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].m, cMM[a][b], sc1, sc1);
             if constexpr (PS::pD || PS::pS) cD[a][b] = MFMA_F4(P[cur][a].d, P[cur][RA + b].d, cD[a][b], sch, sch);
             if constexpr (PS::pH) cH[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].h, cH[a][b], sc2, sc2);
-            if constexpr (PS::pA) cHV[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].v, cHV[a][b], sc2, sc1);
-            if constexpr (PS::pA) cVH[a][b] = MFMA_F4(P[cur][a].v, P[cur][RA + b].h, cVH[a][b], sc1, sc2);
+            if constexpr (PS::pA) cHM[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].m, cHM[a][b], sc2, sc1);
+            if constexpr (PS::pA) cMH[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].h, cMH[a][b], sc1, sc2);
           }
         // (the second MFMA into the D + H sums: a pass of its own, 2 RA RB MFMAs behind the first into the same registers)
         if constexpr (PS::pS) {
@@ -448,11 +460,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
           int32_t* slab = acc_out + (tpg_pw_unit_index(nst, I3, ct) + rowpad[I3]) * TPG_PW_TILE_INTS + a3 * 16 * 64 + lane;
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            if constexpr (PS::pV) atomicAdd(slab + 0 * TPG_PW_PLANE_INTS + r * 64, (int)cV[a][b][r]);
-            if constexpr (PS::pD || PS::pS) atomicAdd(slab + 1 * TPG_PW_PLANE_INTS + r * 64, (int)cD[a][b][r]);  // (pS: D + H)
-            if constexpr (PS::pH) atomicAdd(slab + 2 * TPG_PW_PLANE_INTS + r * 64, (int)cH[a][b][r]);
-            if constexpr (PS::pA) atomicAdd(slab + 3 * TPG_PW_PLANE_INTS + r * 64, (int)cHV[a][b][r]);
-            if constexpr (PS::pA) atomicAdd(slab + 4 * TPG_PW_PLANE_INTS + r * 64, (int)cVH[a][b][r]);
+            if constexpr (PS::pV) atomicAdd(slab + TPG_PW_SLAB_MM * TPG_PW_PLANE_INTS + r * 64, (int)cMM[a][b][r]);
+            if constexpr (PS::pD || PS::pS) atomicAdd(slab + TPG_PW_SLAB_D * TPG_PW_PLANE_INTS + r * 64, (int)cD[a][b][r]);  // (pS: D + H)
+            if constexpr (PS::pH) atomicAdd(slab + TPG_PW_SLAB_H * TPG_PW_PLANE_INTS + r * 64, (int)cH[a][b][r]);
+            if constexpr (PS::pA) atomicAdd(slab + TPG_PW_SLAB_HM * TPG_PW_PLANE_INTS + r * 64, (int)cHM[a][b][r]);
+            if constexpr (PS::pA) atomicAdd(slab + TPG_PW_SLAB_MH * TPG_PW_PLANE_INTS + r * 64, (int)cMH[a][b][r]);
           }
         }
       }
@@ -535,13 +547,13 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
       const int tile = f < 2 * RA ? 2 * RA * I + f : 2 * RB * J + (f - 2 * RA);
       src[q] = (glb_t)(T4 + ((int64_t)(tile < nct ? tile : 0) * KG * 2 + kb0) * 64);
     }
-    v16f cV[RA][RB], cD[RA][RB], cH[RA][RB], cHV[RA][RB], cVH[RA][RB];
+    v16f cMM[RA][RB], cD[RA][RB], cH[RA][RB], cHM[RA][RB], cMH[RA][RB];
 #pragma unroll
     for (int a = 0; a < RA; a++)
 #pragma unroll
       for (int b = 0; b < RB; b++)
 #pragma unroll
-        for (int r = 0; r < 16; r++) { cV[a][b][r] = 0.f; cD[a][b][r] = 0.f; cH[a][b][r] = 0.f; cHV[a][b][r] = 0.f; cVH[a][b][r] = 0.f; }
+        for (int r = 0; r < 16; r++) { cMM[a][b][r] = 0.f; cD[a][b][r] = 0.f; cH[a][b][r] = 0.f; cHM[a][b][r] = 0.f; cMH[a][b][r] = 0.f; }
 
     if (kb0 < kb1) {
       const int kl = kb1 - 1;
@@ -582,7 +594,7 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
       RD(std::integral_constant<int, 1>{}, W[1]);
       Frag3 P[2][NT];
 #pragma unroll
-      for (int t = 0; t < NT; t++) P[0][t] = tpg_planes_of<MASK>(W[0][t], TPG_NIB_V, TPG_NIB_D, TPG_NIB_H);
+      for (int t = 0; t < NT; t++) P[0][t] = tpg_planes_of<MASK>(W[0][t], TPG_NIB_M, TPG_NIB_D, TPG_NIB_H);
       auto step = [&](auto Sc, auto Cc, int kb) {  // block kb: stage s, planes in P[cur]; block kb + 1: words in W[cur ^ 1]
         constexpr int s = decltype(Sc)::value, cur = decltype(Cc)::value, nx = cur ^ 1, s2 = (s + 2) % NST;
         // my pieces of block kb + 2 have landed (younger DMAs: blocks kb + 3 .. kb + NST - 1); behind the barrier everybody's
@@ -594,7 +606,7 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
 #pragma unroll
         for (int t = 0; t < NT; t++) {
           const bool keep = t >= RA || live1;
-          P[nx][t] = tpg_planes_of<MASK>(W[nx][t], keep ? TPG_NIB_V : 0u, keep ? TPG_NIB_D : 0u, keep ? TPG_NIB_H : 0u);
+          P[nx][t] = tpg_planes_of<MASK>(W[nx][t], keep ? TPG_NIB_M : 0u, keep ? TPG_NIB_D : 0u, keep ? TPG_NIB_H : 0u);
         }
         // (W[cur] held block kb: masked a step ago)
         RD(std::integral_constant<int, s2>{}, W[cur]);
@@ -602,11 +614,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
         for (int a = 0; a < RA; a++)
 #pragma unroll
           for (int b = 0; b < RB; b++) {
-            if constexpr (PS::pV) cV[a][b] = MFMA_F4(P[cur][a].v, P[cur][RA + b].v, cV[a][b], sc1, sc1);
+            if constexpr (PS::pV) cMM[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].m, cMM[a][b], sc1, sc1);
             if constexpr (PS::pD) cD[a][b] = MFMA_F4(P[cur][a].d, P[cur][RA + b].d, cD[a][b], sch, sch);
             if constexpr (PS::pH) cH[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].h, cH[a][b], sc2, sc2);
-            if constexpr (PS::pA) cHV[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].v, cHV[a][b], sc2, sc1);
-            if constexpr (PS::pA) cVH[a][b] = MFMA_F4(P[cur][a].v, P[cur][RA + b].h, cVH[a][b], sc1, sc2);
+            if constexpr (PS::pA) cHM[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].m, cHM[a][b], sc2, sc1);
+            if constexpr (PS::pA) cMH[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].h, cMH[a][b], sc1, sc2);
           }
         // the DMAs and the ring reads spread over the first MFMAs, the plane masks between all of them
         __builtin_amdgcn_sched_group_barrier(SGB_VMEM_READ, NLD, 0);
@@ -639,11 +651,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
           int32_t* slab = acc_out + (tpg_pw_unit_index(nst, I3, ct) + rowpad[I3]) * TPG_PW_TILE_INTS + a3 * 16 * 64 + lane;
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            if constexpr (PS::pV) atomicAdd(slab + 0 * TPG_PW_PLANE_INTS + r * 64, (int)cV[a][b][r]);
-            if constexpr (PS::pD) atomicAdd(slab + 1 * TPG_PW_PLANE_INTS + r * 64, (int)cD[a][b][r]);
-            if constexpr (PS::pH) atomicAdd(slab + 2 * TPG_PW_PLANE_INTS + r * 64, (int)cH[a][b][r]);
-            if constexpr (PS::pA) atomicAdd(slab + 3 * TPG_PW_PLANE_INTS + r * 64, (int)cHV[a][b][r]);
-            if constexpr (PS::pA) atomicAdd(slab + 4 * TPG_PW_PLANE_INTS + r * 64, (int)cVH[a][b][r]);
+            if constexpr (PS::pV) atomicAdd(slab + TPG_PW_SLAB_MM * TPG_PW_PLANE_INTS + r * 64, (int)cMM[a][b][r]);
+            if constexpr (PS::pD) atomicAdd(slab + TPG_PW_SLAB_D * TPG_PW_PLANE_INTS + r * 64, (int)cD[a][b][r]);
+            if constexpr (PS::pH) atomicAdd(slab + TPG_PW_SLAB_H * TPG_PW_PLANE_INTS + r * 64, (int)cH[a][b][r]);
+            if constexpr (PS::pA) atomicAdd(slab + TPG_PW_SLAB_HM * TPG_PW_PLANE_INTS + r * 64, (int)cHM[a][b][r]);
+            if constexpr (PS::pA) atomicAdd(slab + TPG_PW_SLAB_MH * TPG_PW_PLANE_INTS + r * 64, (int)cMH[a][b][r]);
           }
         }
       }
@@ -654,12 +666,15 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
 // ---------------------------------------------------------------------------
 #include "host/host_bands.h"  // pw_bands
 
+// slabs at the end of every chunk that hold the two diagonal vectors (tpg_pairwise in common.h)
+static int64_t pw_tail_units(int64_t n) { return ceil_div(2 * 32 * ceil_div(n, 32), TPG_PW_TILE_INTS); }
+
 static size_t pw_buffer_bytes(int64_t n, int nranks) {
   const int64_t nst = ceil_div(n, 32 * TA);
   std::vector<int32_t> band;
   int64_t chunk;
   pw_bands(nst, nranks, band, chunk);
-  return (size_t)(chunk * nranks) * TPG_PW_TILE_INTS * sizeof(int32_t);
+  return (size_t)((chunk + pw_tail_units(n)) * nranks) * TPG_PW_TILE_INTS * sizeof(int32_t);
 }
 
 extern "C" size_t tpg_pairwise_buffer_bytes(int64_t n) { return pw_buffer_bytes(n, 1); }
@@ -674,9 +689,11 @@ static int pairwise_create(tpg_ctx* ctx, int64_t n, int nranks, int rank, void* 
   pw->nranks = nranks;
   pw->rank = rank;
   pw_bands(pw->nst, nranks, pw->band, pw->chunk_units);
+  pw->tail_units = pw_tail_units(n);
+  pw->chunk_units += pw->tail_units;
   {
     // units (I, jt), jt >= 2 I, in patch order: blocks of 16 column tiles, inside a block row after row.  Column
-    // tiles that hold only padding (32 jt >= n: all-missing codes, zero products) are left out -- their slabs stay
+    // tiles that hold only padding (32 jt >= n: zero nibbles, zero products) are left out -- their slabs stay
     // zero and no epilogue reads them.
     const int nst = (int)pw->nst, nct = (int)ceil_div(n, 32);
     std::vector<int2> order;
@@ -728,6 +745,37 @@ extern "C" int tpg_pairwise_create_sharded(tpg_ctx* ctx, const tpg_comm* comm, i
   return pairwise_create(ctx, n, comm->nranks, comm->rank, nullptr, out);
 }
 
+// Element (i, i) of plane `plane` out of the tile-packed slabs: row r of tile (t, t) sits in register (r & 3) + 4 (r >> 3)
+// of lane r + 32 ((r >> 2) & 1) (tpg_cd_row).  Every kernel computes the diagonal tiles (unit (t / TA, t) holds jt >= TA I).
+__device__ __forceinline__ int tpg_pw_diag_of_slabs(const int32_t* __restrict__ acc, const int64_t* __restrict__ rowpad, int nst,
+                                                    int plane, int i) {
+  const int t = i >> 5, r = i & 31, reg = (r & 3) + 4 * (r >> 3), lane = r + 32 * ((r >> 2) & 1);
+  return acc[(tpg_pw_unit_index(nst, t / TA, t) + rowpad[t / TA]) * TPG_PW_TILE_INTS + plane * TPG_PW_PLANE_INTS +
+             ((t % TA) * 16 + reg) * 64 + lane];
+}
+
+// This rank's (partial) diagonals MM_ii and D_ii into the tail of EVERY chunk: behind the reduce-scatter the tail of the
+// rank's own chunk holds the complete ones of all individuals.  npad = 32 ceil(n / 32); tail r starts at tail0 + r stride.
+__global__ __launch_bounds__(256) void tpg_pairwise_diag_kernel(int32_t* __restrict__ acc, const int64_t* __restrict__ rowpad,
+                                                                int nst, int npad, int nranks, int64_t tail0, int64_t stride) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= npad) return;
+  const int mm = tpg_pw_diag_of_slabs(acc, rowpad, nst, TPG_PW_SLAB_MM, i), dd = tpg_pw_diag_of_slabs(acc, rowpad, nst, TPG_PW_SLAB_D, i);
+  for (int r = 0; r < nranks; r++) {
+    acc[tail0 + r * stride + i] = mm;
+    acc[tail0 + r * stride + npad + i] = dd;
+  }
+}
+
+static int64_t pw_tail_offset(const tpg_pairwise* pw, int rank) {  // in int32 from pw->acc
+  return ((int64_t)(rank + 1) * pw->chunk_units - pw->tail_units) * TPG_PW_TILE_INTS;
+}
+static void pw_launch_diag(tpg_ctx* ctx, tpg_pairwise* pw) {
+  const int npad = 32 * (int)ceil_div(pw->n, 32);
+  TPG_LAUNCH(ctx, "pairwise_diag", tpg_pairwise_diag_kernel, dim3((unsigned)ceil_div(npad, 256)), dim3(256), 0, pw->acc,
+             (const int64_t*)pw->rowpad, (int)pw->nst, npad, pw->nranks, pw_tail_offset(pw, 0), pw->chunk_units * TPG_PW_TILE_INTS);
+}
+
 // Sum the partial cross-products of all ranks: one reduce-scatter of the int32 slabs (exact, order independent).
 // Afterwards this rank holds the complete sums of ITS band of super-tile rows only, and the count / epilogue entry
 // points write only the part of the N x N outputs that band covers: rows [row0, row1) x columns >= row0 and its
@@ -751,6 +799,8 @@ extern "C" int tpg_pairwise_reduce(tpg_ctx* ctx, tpg_comm* comm, tpg_pairwise* p
   if (comm->nranks > 1 || comm->nccl) TPG_TRY(tpg_comm_allreduce_f64(ctx, comm, word, 6));
   const double loci = word[0];
   TPG_REQUIRE(loci <= (double)TPG_PW_MAX_LOCI, TPG_EUNSUPPORTED, "%.0f loci over all ranks overflow the int32 pair counts", loci);
+  pw_launch_diag(ctx, pw);  // the diagonals travel with the slabs (tpg_pairwise in common.h)
+  TPG_CHECK_LAUNCH();
   {
     ProfScope ps(ctx, "pairwise_reduce_scatter");
     TPG_TRY(tpg_comm_reduce_scatter_i32(comm, pw->acc, pw->chunk_units * TPG_PW_TILE_INTS));
@@ -787,6 +837,8 @@ extern "C" int tpg_pairwise_reduce_begin(tpg_ctx* ctx, tpg_comm* side, tpg_pairw
   TPG_REQUIRE(word[0] <= (double)TPG_PW_MAX_LOCI, TPG_EUNSUPPORTED, "%.0f loci over all ranks overflow the int32 pair counts", word[0]);
   if (!pw->ev_acc) TPG_HIP(hipEventCreateWithFlags(&pw->ev_acc, hipEventDisableTiming));
   if (!pw->ev_red) TPG_HIP(hipEventCreateWithFlags(&pw->ev_red, hipEventDisableTiming));
+  pw_launch_diag(ctx, pw);  // the diagonals travel with the slabs (tpg_pairwise in common.h)
+  TPG_CHECK_LAUNCH();
   TPG_HIP(hipEventRecord(pw->ev_acc, ctx->stream));          // behind the accumulate kernels of pw's context
   TPG_HIP(hipStreamWaitEvent(sc->stream, pw->ev_acc, 0));
   {
@@ -1047,7 +1099,8 @@ extern "C" int tpg_pairwise_accumulate_products(tpg_ctx* ctx, tpg_pairwise* pw, 
     TPG_HIP(tpg_pmalloc((void**)&t4, 2 * v->bytes_each));
     const int64_t nblocks = 4 * v->Q * v->KG;
     int grid = (int)std::min<int64_t>(ceil_div(nblocks * 64, 256), (int64_t)ctx->num_cu * 32);
-    TPG_LAUNCH(ctx, "t4_expand", tpg_t4_expand_kernel, dim3((unsigned)grid), dim3(256), 0, (const uint4*)v->T, t4, nblocks);
+    TPG_LAUNCH(ctx, "t4_expand", tpg_t4_expand_kernel, dim3((unsigned)grid), dim3(256), 0, (const uint4*)v->T, t4, nblocks, v->KG,
+               v->n, v->m);
     v->T4 = t4;
   }
   const int64_t kg0 = col_begin / 128, kg1 = ceil_div(col_end, 128);
@@ -1163,6 +1216,40 @@ __device__ __forceinline__ void tpg_pw_emit(const PwCounts c, int mode, double s
   }
 }
 
+// The five planes of tile (ti, tj), ti <= tj, read once -- lane index on the slab's lane: contiguous 4-byte loads -- into
+// sp[plane][row][col] (row, col inside the tile), then V and A rebuilt in place from MM, HM and MH (file header):
+//   sp[0] = V = L - m_i - m_j + MM    sp[1] = D (or D + H)    sp[2] = H    sp[3] = A[i][j] = Hc_i - HM    sp[4] = A[j][i] = Hc_j - MH
+// with i = 32 ti + row, j = 32 tj + col, m_i = MM_ii and Hc_i = L - MM_ii - D_ii (meaningful where A was accumulated: plane D
+// is then D alone).  L = loci accumulated.  diag = the diagonals MM_ii, D_ii of all npad individuals as tpg_pairwise_reduce left
+// them (the band of a rank lacks the diagonal tiles of the columns to its right), or NULL: the slabs hold every diagonal tile.
+// Every sum is an integer in [0, L]: exact in int32.  256 threads; ends with a barrier.
+__device__ __forceinline__ void tpg_pw_tile_counts(const int32_t* __restrict__ acc, const int64_t* __restrict__ rowpad, int nst,
+                                                   int npad, int ti, int tj, int L, const int32_t* __restrict__ diag,
+                                                   int (*sp)[32][33]) {
+  __shared__ int dg[2][64];  // [MM_ii, D_ii][rows of ti, then columns of tj]
+  const int32_t* p = acc + (tpg_pw_unit_index(nst, ti / TA, tj) + rowpad[ti / TA]) * TPG_PW_TILE_INTS + ((ti % TA) * 16) * 64;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int idx = threadIdx.x + 256 * e, reg = idx >> 6, lane = idx & 63;
+#pragma unroll
+    for (int q = 0; q < 5; q++) sp[q][tpg_cd_row(reg, lane)][lane & 31] = p[q * TPG_PW_PLANE_INTS + reg * 64 + lane];
+  }
+  if (threadIdx.x < 128) {
+    const int q = threadIdx.x >> 6, k = threadIdx.x & 63, i = k < 32 ? 32 * ti + k : 32 * tj + (k - 32);
+    dg[q][k] = diag ? diag[q * npad + i] : tpg_pw_diag_of_slabs(acc, rowpad, nst, q ? TPG_PW_SLAB_D : TPG_PW_SLAB_MM, i);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int idx = threadIdx.x + 256 * e, row = idx & 31, col = idx >> 5;
+    const int mi = dg[0][row], mj = dg[0][32 + col];
+    sp[TPG_PW_SLAB_MM][row][col] = L - mi - mj + sp[TPG_PW_SLAB_MM][row][col];
+    sp[TPG_PW_SLAB_HM][row][col] = (L - mi - dg[1][row]) - sp[TPG_PW_SLAB_HM][row][col];
+    sp[TPG_PW_SLAB_MH][row][col] = (L - mj - dg[1][32 + col]) - sp[TPG_PW_SLAB_MH][row][col];
+  }
+  __syncthreads();
+}
+
 // One workgroup per 32 x 32 tile (ti <= tj) of the stored band.  The five count planes of the tile are read once,
 // lane index on the slab's lane (contiguous 4-byte loads), into LDS; the tile is then written twice -- as it stands,
 // threads running down a column of the column-major outputs, and mirrored for the lower triangle, threads running
@@ -1170,7 +1257,8 @@ __device__ __forceinline__ void tpg_pw_emit(const PwCounts c, int mode, double s
 // is fetched more than once.
 __global__ __launch_bounds__(256) void tpg_pairwise_epilogue_kernel(const int32_t* __restrict__ acc,
                                                                     const int64_t* __restrict__ rowpad, int ti0,
-                                                                    int nst, int n,
+                                                                    int nst, int n, int L,
+                                                                    const int32_t* __restrict__ diag,
                                                                     int mode, double scale, long long quirk,
                                                                     double* __restrict__ o0,
                                                                     double* __restrict__ o1, double* __restrict__ o2,
@@ -1179,15 +1267,7 @@ __global__ __launch_bounds__(256) void tpg_pairwise_epilogue_kernel(const int32_
   const int ti = blockIdx.y + ti0, tj = blockIdx.x + ti0;  // tile rows of this rank's band, columns from its first one
   if (ti > tj) return;
   __shared__ int sp[5][32][33];
-  const int32_t* p = acc + (tpg_pw_unit_index(nst, ti / TA, tj) + rowpad[ti / TA]) * TPG_PW_TILE_INTS + ((ti % TA) * 16) * 64;
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    const int idx = threadIdx.x + 256 * e, reg = idx >> 6, lane = idx & 63;
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), col = lane & 31;
-#pragma unroll
-    for (int q = 0; q < 5; q++) sp[q][row][col] = p[q * TPG_PW_PLANE_INTS + reg * 64 + lane];
-  }
-  __syncthreads();
+  tpg_pw_tile_counts(acc, rowpad, nst, 32 * ((n + 31) / 32), ti, tj, L, diag, sp);
 #pragma unroll
   for (int e = 0; e < 4; e++) {
     const int idx = threadIdx.x + 256 * e;
@@ -1230,6 +1310,11 @@ static PwBand pw_band(const tpg_pairwise* pw) {
   return b;
 }
 
+// where the epilogue finds the diagonals MM_ii, D_ii: in the tail of the rank's chunk once the band is all it holds
+static const int32_t* pw_diag(const tpg_pairwise* pw, const PwBand& b) {
+  return b.whole ? nullptr : pw->acc + pw_tail_offset(pw, pw->rank);
+}
+
 // device -> caller for an output the caller holds in host memory: everything, or just the band's two rectangles
 static int pw_commit(tpg_ctx* ctx, OutBuf& o, int64_t n, const PwBand& b) {
   if (!o.owned || !o.user) return TPG_OK;  // the caller's pointer is device memory: written in place
@@ -1262,8 +1347,8 @@ static int run_epilogue(tpg_ctx* ctx, const tpg_pairwise* pw, int mode, double s
   const unsigned nt = (unsigned)ceil_div(pw->n, 32);
   if (band.nti > 0) {
     TPG_LAUNCH(ctx, "pairwise_epilogue", tpg_pairwise_epilogue_kernel, dim3(nt - (unsigned)band.ti0, (unsigned)band.nti),
-               dim3(256), 0, (const int32_t*)pw->acc, (const int64_t*)pw->rowpad, band.ti0, (int)pw->nst, (int)pw->n, mode,
-               scale, (long long)pw->as_pad_quirk, b[0].dev<double>(), b[1].dev<double>(), b[2].dev<double>(),
+               dim3(256), 0, (const int32_t*)pw->acc, (const int64_t*)pw->rowpad, band.ti0, (int)pw->nst, (int)pw->n,
+               (int)pw->loci, pw_diag(pw, band), mode, scale, (long long)pw->as_pad_quirk, b[0].dev<double>(), b[1].dev<double>(), b[2].dev<double>(),
                b[3].dev<double>(), b[4].dev<double>(), b[5].dev<double>());
     TPG_CHECK_LAUNCH();
   }
@@ -1349,7 +1434,8 @@ static int epilogues_impl(tpg_ctx* ctx, tpg_comm* comm, const tpg_pairwise* pw, 
   const unsigned nt = (unsigned)ceil_div(pw->n, 32);
   if (band.nti > 0) {
     TPG_LAUNCH(ctx, "pairwise_epilogue", tpg_pairwise_epilogue_kernel, dim3(nt - (unsigned)band.ti0, (unsigned)band.nti),
-               dim3(256), 0, (const int32_t*)pw->acc, (const int64_t*)pw->rowpad, band.ti0, (int)pw->nst, n, 4,
+               dim3(256), 0, (const int32_t*)pw->acc, (const int64_t*)pw->rowpad, band.ti0, (int)pw->nst, n,
+               (int)pw->loci, pw_diag(pw, band), 4,
                ibs_type == TPG_IBS_PROPORTION ? 1.0 : (double)m, (long long)pw->as_pad_quirk, bi.dev<double>(),
                bk.dev<double>(), as_dst, (double*)nullptr, (double*)nullptr, (double*)nullptr);
     TPG_CHECK_LAUNCH();
@@ -1642,20 +1728,12 @@ void tpg_resident_release(tpg_ctx* ctx) {  // called by tpg_ctx_destroy and tpg_
 template <typename OA, typename OB>
 __global__ __launch_bounds__(256) void tpg_pairwise_counts2_i32_kernel(const int32_t* __restrict__ acc,
                                                                        const int64_t* __restrict__ rowpad, int nst, int n,
-                                                                       int which, int quirk, OA* __restrict__ oA, int biasA,
+                                                                       int L, int which, int quirk, OA* __restrict__ oA, int biasA,
                                                                        OB* __restrict__ oB) {
   const int ti = blockIdx.y, tj = blockIdx.x;
   if (ti > tj) return;
   __shared__ int sp[5][32][33];
-  const int32_t* p = acc + (tpg_pw_unit_index(nst, ti / TA, tj) + rowpad[ti / TA]) * TPG_PW_TILE_INTS + ((ti % TA) * 16) * 64;
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    const int idx = threadIdx.x + 256 * e, reg = idx >> 6, lane = idx & 63;
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), col = lane & 31;
-#pragma unroll
-    for (int q = 0; q < 5; q++) sp[q][row][col] = p[q * TPG_PW_PLANE_INTS + reg * 64 + lane];
-  }
-  __syncthreads();
+  tpg_pw_tile_counts(acc, rowpad, nst, 32 * ((n + 31) / 32), ti, tj, L, nullptr, sp);
   auto emit = [&](int row, int col, int64_t idx, bool mirrored) {
     const int V = sp[0][row][col], D = sp[1][row][col], H = sp[2][row][col];
     const int Aij = mirrored ? sp[4][row][col] : sp[3][row][col], Aji = mirrored ? sp[3][row][col] : sp[4][row][col];
@@ -1735,7 +1813,8 @@ static int add_counts_to_caller(tpg_ctx* ctx, int which, const tpg_pairwise* pw,
   const dim3 grid(nt, nt);
 #define CNT2(TA_, TB_)                                                                                                       \
   TPG_LAUNCH(ctx, "pairwise_counts_i32", (tpg_pairwise_counts2_i32_kernel<TA_, TB_>), grid, dim3(256), 0,                    \
-             (const int32_t*)pw->acc, (const int64_t*)pw->rowpad, (int)pw->nst, (int)pw->n, which, (int)pw->as_pad_quirk,    \
+             (const int32_t*)pw->acc, (const int64_t*)pw->rowpad, (int)pw->nst, (int)pw->n, (int)pw->loci, which,            \
+             (int)pw->as_pad_quirk,                                                                                          \
              (TA_*)d_out, biasA, (TB_*)(d_out + bytesA))
   if (a16 && b16) CNT2(uint16_t, uint16_t);
   else if (b16) CNT2(int32_t, uint16_t);
