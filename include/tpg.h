@@ -909,6 +909,75 @@ int tpg_square_frobenius(tpg_ctx* ctx, const tpg_view* v, const double* center, 
  * behind predict(project_method = "least_squares") (R/predict_gt_pca.R:221-228) */
 int tpg_fbm256_valid_prod(tpg_ctx* ctx, const tpg_view* v, const double* Tab, int K, double* out);
 
+/* ---- pcadapt (gt_pcadapt, R/gt_pcadapt.R:44-86 around bigsnpr::snp_pcadapt; bigsnpr is not among the reference's sources, so
+ * the arithmetic is defined HERE.  Recalled from bigsnpr / pcadapt: the statistic is a robust Mahalanobis distance of the
+ * per-locus z-scores of the regression of each locus on the K PCA scores, the robust location / scatter is an OGK estimate,
+ * the distance is divided by the genomic-control factor median(dist) / qchisq(0.5, K) and referred to chi-square(K), and U
+ * must be orthonormal (bigsnpr checks it with all.equal).  THIS PROJECT'S choices: the degrees of freedom n - K - 1 of the
+ * residual variance (a constant factor on z changes nothing downstream), median / MAD as the scale of OGK with two iterations
+ * and no reweighting step, the treatment of ties, -0 and non-finite values in a median, every operation order below, and the
+ * evaluation of the chi-square tail) ---------------------------------------------------------------------------------------
+ * Inputs.  A view of n individuals x m loci, codes 0 / 1 / 2; a missing genotype: TPG_ENUMERIC, as tpg_pca_center_scale
+ *   (impute first).  U: n x K column-major, host or device memory.  TPG_EINVAL unless 1 <= K <= TPG_PCADAPT_MAX_K, n - K - 1 >= 1
+ *   and max |U'U - I| <= 1e-8 (host, plain double sums in ascending i).
+ * 1. z-scores (m x K, column-major).  With the genotype counts n0, n1, n2 of locus j: S1 = n1 + 2 n2, S2 = n1 + 4 n2,
+ *   mean_j = S1 / n, tot_j = (n S2 - S1^2) / n (exact integers, one division), beta_jk = sum_i (g_ij - mean_j) U_ik (the FP64
+ *   row-scaled sweep of csrc/pca.hip), rss_j = tot_j - sum_k beta_jk^2 (k ascending, each square subtracted in turn),
+ *   z_jk = beta_jk / sqrt(rss_j / (n - K - 1)).  tot_j == 0 or rss_j <= 0: the whole row of z is NaN, the locus is INVALID.
+ *   Error of the sweep: a sum of n products |d beta_jk| <= n eps ||g_j - mean_j||_2 ||U_k||_2 = n eps sqrt(tot_j) (eps = 2^-53,
+ *   first order, whatever the order of the sum or the fusing of its multiply-adds; the rounding of mean_j adds at most
+ *   eps mean_j sum_i |U_ik| <= eps 2 sqrt(n)).  Through rss: |d rss_j| <= 2 sum_k |beta_jk| |d beta_jk| + (K + 1) eps tot_j, and
+ *   with z = beta sqrt(dof / rss):  |d z_jk| <= |z_jk| (|d beta_jk| / |beta_jk| + |d rss_j| / (2 rss_j)) + 3 eps |z_jk|: the
+ *   factor tot_j / rss_j amplifies the relative error of tot_j into that of rss_j.  tests/test_gpu_pcadapt.py evaluates this
+ *   bound per cell from the extended-precision route of tests/pcadapt_ref.py.
+ * 2. Column statistics, over the FINITE entries of a column only (NaN and +-inf never enter a count or a rank); a value is
+ *   read as x + 0.0, i.e. -0 counts as +0.  s = the ascending sort, c = its length:  med = s[(c-1)/2] for odd c,
+ *   (s[c/2 - 1] + s[c/2]) / 2 for even c;  mad(x) = med(|x - med(x)|) over the entries whose deviation is finite;
+ *   sigma(x) = 1.4826 mad(x).  Exact selections: bit for bit numpy.median of the same values.  c = 0: NaN.
+ * 3. Robust distance, OGK (Maronna and Zamar 2002) with median / MAD.  A row of Z with an entry that is not finite is invalid
+ *   (its distance is NaN); X(0) = the M' valid rows.  M' < K + 2, or a sigma below that is 0 or not finite: TPG_ENUMERIC.
+ *   For t = 1, 2:  s_k = sigma(X_k);  Y_k = X_k / s_k (one division per element);  R_aa = 1,
+ *   R_ab = R_ba = (sp sp - sm sm) / 4 with sp = sigma(Y_a + Y_b), sm = sigma(Y_a - Y_b), a < b (each sum or difference rounded
+ *   once);  R = E Lambda E' on the host (csrc/host/host_eig.h: host_sym_eig, eigenvalues descending; K = 1: E = 1);
+ *   X(t) = W = Y E, W_jk = sum_a Y_ja E_ak, a ascending from +0, no FMA contraction.
+ *   Then nu_k = med(W_k), Gamma_k = sigma(W_k)^2 and dist_j = sum_k ((W_jk - nu_k)^2 / Gamma_k), k ascending from +0.
+ *   A sign flip of an eigenvector leaves dist unchanged exactly (med(-x) = -med(x)).  K = 1: dist = ((z - med) / sigma)^2 up to
+ *   the roundings of the two scalings.  center / cov are nu and diag(Gamma) taken back to the coordinates of Z: a row is
+ *   x = B w with B = (D1 E1)(D2 E2), D_t = diag(s of iteration t), so center = B nu, cov = B diag(Gamma) B', in the loop order of
+ *   csrc/host/host_pcadapt.h: host_ogk_backmap.
+ * 4. Genomic control and p-values.  q50(K) = the root of log Q(K/2, x/2) = log(1/2) by bisection on the host until the ends are
+ *   neighbouring doubles (Q by the finite sums for half-integer a, csrc/host/host_pcadapt.h); lambda = med(dist) / q50(K);
+ *   stat_j = dist_j / lambda;  log10p_j = log Q(K/2, stat_j / 2) / ln 10 with Q the regularised upper incomplete gamma function:
+ *   the series of P and log1p(-P) for x < a + 1, otherwise the modified-Lentz continued fraction and
+ *   -x + a ln x - lgamma(a) + ln(cf), so that a stat in the thousands gets a finite log10p.  One function for host and device
+ *   (tpg_logq), lgamma(a) from the host.  A NaN in gives a NaN out.
+ * Determinism.  Selections are exact; the only atomics are integer counts.  A result depends on the inputs alone. */
+#define TPG_PCADAPT_MAX_K 64
+/* keys per candidate list of the selection kernel = threads of its workgroup: a bucket of at most this many keys is collected
+ * into scratch and finished there (csrc/pcadapt.hip; the tests put their row counts around it) */
+#define TPG_SELECT_TILE 1024
+int64_t tpg_select_tile(void);
+/* The selection primitive on its own.  X: rows x ncols doubles, column-major with leading dimension ld >= rows, host or device
+ * memory; med, mad (double[ncols]) and n_finite (int64[ncols], may be NULL; the count of finite entries) host or device.
+ * mad = 0 (all finite entries equal) is a result here, not an error.  rows < 2^31. */
+int tpg_col_median_mad(tpg_ctx* ctx, const double* X, int64_t rows, int ncols, int64_t ld, double* med, double* mad,
+                       int64_t* n_finite);
+/* step 1: z (m x K, host or device), n_valid (host, may be NULL) = the number of valid loci; z is written at the end only */
+int tpg_pcadapt_zscores(tpg_ctx* ctx, const tpg_view* v, const double* U, int K, double* z, int64_t* n_valid);
+/* step 3 on any m x K matrix Z (column-major, host or device): dist[m] (host or device); center[K], cov[K x K] and
+ * basis[2 K K] (E of the first, then of the second iteration, column-major) in host memory, each may be NULL; n_valid (host,
+ * may be NULL) = M' */
+int tpg_robust_dist_ogk(tpg_ctx* ctx, const double* Z, int64_t m, int K, double* dist, double* center, double* cov,
+                        double* basis, int64_t* n_valid);
+/* out[i] = log10 of the upper tail of chi-square(df) at x[i] (host or device memory, count entries); df >= 1 */
+int tpg_pchisq_log10_upper(tpg_ctx* ctx, const double* x, int64_t count, int df, double* out);
+/* host only: the median of chi-square(df) */
+int tpg_qchisq_median(int df, double* out);
+/* The whole scan: steps 1 - 4.  z (m x K, may be NULL), dist, stat, log10p (m each) host or device; gc_lambda and n_valid host,
+ * may be NULL.  Bit for bit the three staged calls.  Nothing of the caller's is written before the end. */
+int tpg_pcadapt(tpg_ctx* ctx, const tpg_view* v, const double* U, int K, double* z, double* dist, double* stat, double* log10p,
+                double* gc_lambda, int64_t* n_valid);
+
 #ifdef __cplusplus
 }
 #endif

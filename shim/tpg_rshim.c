@@ -1309,6 +1309,35 @@ SEXP _tidypopgen_tpg_admixture(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP s
   return out;
 }
 
+/* ---- pcadapt ------------------------------------------------------------------------------------------------------ */
+
+#pragma weak tpg_pcadapt
+
+/* tpg_pcadapt(BM, rowInd, colInd, U): the genome scan of R/gt_pcadapt.R:44-86 (bigsnpr::snp_pcadapt) as one call of the scan of
+ * include/tpg.h "pcadapt".  U = the first K columns of the PCA's u (length(rowInd) x K, numeric; K is read from its length).
+ * -> list(score: M (= dist / gc_lambda), dist: M, log10p: M, gc_lambda) */
+SEXP _tidypopgen_tpg_pcadapt(SEXP BM, SEXP rowInd, SEXP colInd, SEXP U) {
+  TPG_NEEDS(tpg_pcadapt);
+  if (TYPEOF(U) != REALSXP && TYPEOF(U) != INTSXP) Rf_error("tidypopgen (GPU): U must be a numeric matrix");
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  const R_xlen_t n = XLENGTH(ri), m = XLENGTH(ci);
+  SEXP us = PROTECT(as_real(U));
+  if (n < 1 || XLENGTH(us) < n || XLENGTH(us) % n != 0) Rf_error("tidypopgen (GPU): U must have length(rowInd) rows");
+  const R_xlen_t K = XLENGTH(us) / n;
+  if (K > INT_MAX) Rf_error("tidypopgen (GPU): too many columns in U");
+  SEXP vals[4];
+  vals[0] = PROTECT(Rf_allocVector(REALSXP, m));
+  vals[1] = PROTECT(Rf_allocVector(REALSXP, m));
+  vals[2] = PROTECT(Rf_allocVector(REALSXP, m));
+  vals[3] = PROTECT(Rf_allocVector(REALSXP, 1));
+  static const char* names[4] = {"score", "dist", "log10p", "gc_lambda"};
+  SEXP out = PROTECT(named_list(4, names, vals));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_pcadapt(ctx(), v, REAL(us), (int)K, NULL, REAL(vals[1]), REAL(vals[0]), REAL(vals[2]), REAL(vals[3]), NULL));
+  UNPROTECT(8);
+  return out;
+}
+
 /* ---- registration ------------------------------------------------------------------------------------------------
  * Same names and arities as the reference's table (src/RcppExports.cpp:348-371).  These rows replace the rows of the
  * same name there, and so do the three HWE rows of tpg_rshim_entries_hwe[] below; the other rows of that table
@@ -1381,11 +1410,16 @@ const R_CallMethodDef tpg_rshim_entries_admix[] = {
     {"_tidypopgen_tpg_admixture", (DL_FUNC)&_tidypopgen_tpg_admixture, 9},
     {NULL, NULL, 0}};
 
+/* The pcadapt scan, in a table of its own: the reference's routine is bigsnpr's, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_pcadapt[] = {
+    {"_tidypopgen_tpg_pcadapt", (DL_FUNC)&_tidypopgen_tpg_pcadapt, 4},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the eight tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the nine tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1393,7 +1427,8 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_roh) / sizeof(tpg_rshim_entries_roh[0]) +
                              sizeof(tpg_rshim_entries_tajima) / sizeof(tpg_rshim_entries_tajima[0]) +
                              sizeof(tpg_rshim_entries_f2) / sizeof(tpg_rshim_entries_f2[0]) +
-                             sizeof(tpg_rshim_entries_admix) / sizeof(tpg_rshim_entries_admix[0])];
+                             sizeof(tpg_rshim_entries_admix) / sizeof(tpg_rshim_entries_admix[0]) +
+                             sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1403,6 +1438,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_tajima; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_f2; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_admix; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_pcadapt; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

@@ -170,6 +170,21 @@ gt_admixture_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bi
   adm_list
 }
 
+# PCA-based genome scan on the GPU (R/gt_pcadapt.R:44-86 around bigsnpr::snp_pcadapt; include/tpg.h "pcadapt" is the definition).
+# U.row: the first k columns of the PCA's u for the rows ind.row.  Returns the reference's object: a data.frame(score) of class
+# "mhtest" whose `predict` attribute gives log10 p-values from the chi-square with k degrees of freedom; dist, the device's own
+# log10p and the genomic-control factor ride along as attributes.
+gt_pcadapt_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), U.row) {
+  U.row <- as.matrix(U.row)
+  if (nrow(U.row) != length(ind.row)) stop("U.row must have one row per element of ind.row")
+  K <- ncol(U.row)
+  storage.mode(U.row) <- "double"
+  res <- .Call(`_tidypopgen_tpg_pcadapt`, X, as.integer(ind.row), as.integer(ind.col), U.row)
+  fun.pred <- function(xtr) stats::pchisq(xtr, df = K, lower.tail = FALSE, log.p = TRUE) / log(10)
+  structure(data.frame(score = res$score), class = c("mhtest", "data.frame"), transfo = identity, predict = fun.pred,
+            dist = res$dist, log10p = res$log10p, gc_lambda = res$gc_lambda)
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

@@ -285,6 +285,14 @@ PROTOTYPES = {
     "tpg_fbm256_prod_and_rowSumsSq": (ci, [vp, vp, vp, vp, vp, ci, vp, vp]),
     "tpg_square_frobenius": (ci, [vp, vp, vp, vp, vp]),
     "tpg_fbm256_valid_prod": (ci, [vp, vp, vp, ci, vp]),
+    # ---- pcadapt
+    "tpg_select_tile": (i64, []),
+    "tpg_col_median_mad": (ci, [vp, vp, i64, ci, i64, vp, vp, vp]),
+    "tpg_pcadapt_zscores": (ci, [vp, vp, vp, ci, vp, vp]),
+    "tpg_robust_dist_ogk": (ci, [vp, vp, i64, ci, vp, vp, vp, vp, vp]),
+    "tpg_pchisq_log10_upper": (ci, [vp, vp, i64, ci, vp]),
+    "tpg_qchisq_median": (ci, [ci, vp]),
+    "tpg_pcadapt": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
 }
 
 for _name, (_restype, _argtypes) in PROTOTYPES.items():

@@ -1860,6 +1860,116 @@ def gt_pca_partialSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, total_var
     return out
 
 
+# ---------------------------------------------------------------------------
+# pcadapt (include/tpg.h "pcadapt")
+
+# keys per candidate list of the selection kernel (the tests put their row counts around it)
+SELECT_TILE = int(lib.tpg_select_tile())
+
+
+def col_median_mad(X, ctx: Optional[Context] = None, return_counts: bool = False):
+    """tpg_col_median_mad: exact median and MAD (unscaled) of the finite entries of every column of X (rows x ncols; a
+    Fortran-ordered array is read in place, and a view X = A[:rows, :] of a taller Fortran array goes down with its leading
+    dimension).  -> (med, mad[, n_finite])"""
+    ctx = ctx or default_context()
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be a matrix with at least one row and one column")
+    if not (X.flags.f_contiguous or (X.strides[0] == 8 and X.strides[1] % 8 == 0 and X.strides[1] >= 8 * X.shape[0])):
+        X = np.asfortranarray(X)
+    rows, ncols = X.shape
+    ld = X.strides[1] // 8 if ncols > 1 else rows
+    med, mad, cnt = np.zeros(ncols), np.zeros(ncols), np.zeros(ncols, dtype=np.int64)
+    check(lib.tpg_col_median_mad(ctx.h, _ptr(X), rows, ncols, ld, _ptr(med), _ptr(mad), _ptr(cnt)))
+    return (med, mad, cnt) if return_counts else (med, mad)
+
+
+def pcadapt_zscores(v: View, U, return_n_valid: bool = False):
+    """tpg_pcadapt_zscores: the m x K z-scores of the regression of every locus on the columns of U (n x K, orthonormal); an
+    invalid locus (monomorphic, or no residual variance) is a row of NaN"""
+    U = np.asfortranarray(U, dtype=np.float64)
+    if U.ndim != 2 or U.shape[0] != v.n:
+        raise ValueError(f"U must have {v.n} rows, not shape {U.shape}")
+    K = U.shape[1]
+    z = np.zeros((v.m, max(K, 1)), order="F")
+    nv = C.c_int64()
+    check(lib.tpg_pcadapt_zscores(v.ctx.h, v.h, _ptr(U), K, _ptr(z), C.byref(nv)))
+    return (z, int(nv.value)) if return_n_valid else z
+
+
+def robust_dist_ogk(Z, return_basis: bool = False, ctx: Optional[Context] = None) -> dict:
+    """tpg_robust_dist_ogk: the robust squared Mahalanobis distance of the rows of Z (m x K) from an OGK location / scatter
+    with median and MAD.  -> dict(dist, center, cov, n_valid[, basis = (2, K, K): the eigenvectors of the two iterations])"""
+    ctx = ctx or default_context()
+    Z = np.asfortranarray(Z, dtype=np.float64)
+    if Z.ndim != 2:
+        raise ValueError("Z must be a matrix")
+    m, K = Z.shape
+    dist, center, cov = np.zeros(m), np.zeros(max(K, 1)), np.zeros((max(K, 1), max(K, 1)), order="F")
+    basis = np.zeros(2 * max(K, 1) ** 2)
+    nv = C.c_int64()
+    check(lib.tpg_robust_dist_ogk(ctx.h, _ptr(Z), m, K, _ptr(dist), _ptr(center), _ptr(cov), _ptr(basis), C.byref(nv)))
+    out = dict(dist=dist, center=center, cov=cov, n_valid=int(nv.value))
+    if return_basis:
+        out["basis"] = np.stack([basis[:K * K].reshape((K, K), order="F"), basis[K * K:].reshape((K, K), order="F")])
+    return out
+
+
+def pchisq_log10_upper(x, df: int, ctx: Optional[Context] = None) -> np.ndarray:
+    """log10 of the upper tail of chi-square(df) at x: finite where the tail itself underflows"""
+    ctx = ctx or default_context()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros(x.shape)
+    check(lib.tpg_pchisq_log10_upper(ctx.h, _ptr(x), x.size, int(df), _ptr(out)))
+    return out
+
+
+def qchisq_median(df: int) -> float:
+    """the median of chi-square(df) (host only)"""
+    out = C.c_double()
+    check(lib.tpg_qchisq_median(int(df), C.byref(out)))
+    return out.value
+
+
+def pcadapt(v: View, U, return_zscores: bool = False) -> dict:
+    """tpg_pcadapt: z-scores, robust distance, genomic control and log10 p-values in one call"""
+    U = np.asfortranarray(U, dtype=np.float64)
+    if U.ndim != 2 or U.shape[0] != v.n:
+        raise ValueError(f"U must have {v.n} rows, not shape {U.shape}")
+    K = U.shape[1]
+    z = np.zeros((v.m, max(K, 1)), order="F") if return_zscores else None
+    dist, stat, lp = np.zeros(v.m), np.zeros(v.m), np.zeros(v.m)
+    lam, nv = C.c_double(), C.c_int64()
+    check(lib.tpg_pcadapt(v.ctx.h, v.h, _ptr(U), K, _ptr(z), _ptr(dist), _ptr(stat), _ptr(lp), C.byref(lam), C.byref(nv)))
+    out = dict(dist=dist, stat=stat, log10_p=lp, gc_lambda=lam.value, n_valid=int(nv.value))
+    if return_zscores:
+        out["zscores"] = z
+    return out
+
+
+def gt_pcadapt(X: FBM, pca: dict, k, ind_row=None, ind_col=None, impute: Optional[str] = None, impute_seed: int = 0,
+               return_zscores: bool = False) -> dict:
+    """R/gt_pcadapt.R:44-86: a genome scan for selection on the first k components of `pca` (a gt_pca_* result: its "u").
+    As the reference, k must be a scalar no larger than the number of components in pca, and the genotypes must have no
+    missing value (impute = "mode" | "mean0" | "random" fills them from the kept rows first, as in the PCA).
+    -> dict(score (= dist / gc_lambda), dist, log10_p, p, gc_lambda, n_valid[, zscores])"""
+    if np.ndim(k) != 0 or isinstance(k, (bool, np.bool_)) or int(k) != k:
+        raise ValueError("'k' should be a single integer value")
+    k = int(k)
+    u = np.asarray(pca["u"], dtype=np.float64)
+    if k > u.shape[1]:
+        raise ValueError("K is too large: 'k' should not be larger than the number of components in 'x'")
+    if k < 1:
+        raise ValueError("'k' should be a single integer value")
+    v = _pca_view(X, ind_row, ind_col, CODE_IMPUTE_PRED, impute, impute_seed)
+    r = pcadapt(v, u[:, :k], return_zscores=return_zscores)
+    out = dict(score=r["stat"], dist=r["dist"], log10_p=r["log10_p"], p=np.power(10.0, r["log10_p"]), gc_lambda=r["gc_lambda"],
+               n_valid=r["n_valid"])
+    if return_zscores:
+        out["zscores"] = r["zscores"]
+    return out
+
+
 def ld_window_hi(chromosome, position=None, size=500.0, use_positions: bool = True, m: Optional[int] = None) -> np.ndarray:
     """the window of include/tpg.h "LD clumping": hi[j] = last locus (0-based) that is a neighbour of j.  With positions,
     neighbours are loci of the same chromosome with |position difference| <= size * 1000; without, loci of the same

@@ -287,6 +287,12 @@ static int run_sweep(tpg_ctx* ctx, int mode, const uint4* P, int64_t nrowtiles, 
   return TPG_OK;
 }
 
+// common.h: the FP64 row-scaled sweep over the L layout for other translation units (pcadapt.hip)
+int tpg_sweep_loci_rowscale(tpg_ctx* ctx, const tpg_view* v, const double* d_center, const double* d_inv_scale, const double* d_U,
+                            int K, double* d_out) {
+  return run_sweep(ctx, SW_ROWSCALE, v->L, v->KG * 4, v->Q, v->m, v->n, d_center, d_inv_scale, d_U, v->n, K, d_out, nullptr, nullptr);
+}
+
 __global__ void tpg_inv_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ y) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = 1.0 / x[i];
 }
