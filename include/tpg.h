@@ -978,6 +978,83 @@ int tpg_qchisq_median(int df, double* out);
 int tpg_pcadapt(tpg_ctx* ctx, const tpg_view* v, const double* U, int K, double* z, double* dist, double* stat, double* log10p,
                 double* gc_lambda, int64_t* n_valid);
 
+/* ---- autoSVD (gt_pca_autoSVD, R/gt_pca_autoSVD.R around bigsnpr::snp_autoSVD; bigsnpr, bigutilsr and robustbase are not among
+ * the reference's sources, so the arithmetic is defined HERE.  Recalled from those packages: clump, compute the SVD, take the
+ * square root of a robust Mahalanobis distance of the loadings, smooth it with a Gaussian rolling mean per chromosome, call
+ * outliers by a Tukey fence that is corrected for skewness by the medcouple and for multiplicity by Bonferroni, remove them,
+ * repeat.  THIS PROJECT'S choices: the OGK distance of "pcadapt" as the robust distance, the medcouple as an exact selection
+ * over the ratios b / a (below) instead of the kernel values (a - b) / (a + b), every order, tie rule and evaluation below ----
+ * Inputs.  A view of n x m, codes 0 / 1 / 2; a missing genotype: TPG_ENUMERIC, as for the PCA.  chrom[m], int32, every
+ *   chromosome one contiguous run (else TPG_EINVAL).  hi[m]: the window of "LD clumping"; NULL skips clumping.  k in
+ *   [1, TPG_PCADAPT_MAX_K], thr_r2, roll_size in [0, 1024], alpha_tukey in (0, 1), min_mac >= 0, max_iter >= 0.
+ * 0. MAC filter.  mac_j = min(Sx_j, 2 n - Sx_j); loci with mac_j < min_mac are excluded (min_mac = 0: none; a monomorphic
+ *   locus then fails in the PCA as it does there).
+ * 1. Clumping.  tpg_ld_clump(v, hi, thr_r2, S = NULL, exclude = step 0); without hi the kept set is the complement of step 0.
+ * 2. Loop, iter = 0.  iter += 1; the SVD of the kept loci, exactly tpg_pca_partial_svd on a view of those loci.  iter > max_iter:
+ *   stop, converged = 0.  Otherwise steps 3 - 5 on V (m_keep x k); no outlier: stop, converged = 1; else remove the outliers and
+ *   repeat.  The SVD returned is that of the final kept set; at most max_iter + 1 SVDs are computed.
+ * 3. Statistic.  S_j = sqrt(dist_j), dist = tpg_robust_dist_ogk(V).  A dist that is not finite: TPG_ENUMERIC.
+ * 4. Rolling mean per chromosome segment of the kept loci.  Radius R = roll_size, len = 2 R + 1; R = 0: S2 = S.  A segment
+ *   shorter than len: TPG_EINVAL ("roll_size exceeds the number of variants on at least one chromosome").  Weights (host):
+ *   a = 3/8 if len <= 10 else 1/2;  p1 = (1 - a) / (len + 1 - 2 a);  L = qnorm_upper(p1);  t_i = -L + i (2 L / (len - 1)),
+ *   i = 0 .. len - 1;  w_i = exp(-(t_i t_i) / 2) / sqrt(2 pi).  S2_j = (sum w_i x_{j-R+i}) / (sum w_i), both sums over the i whose
+ *   locus lies inside the segment, i ascending from +0, no FMA contraction, one division.
+ *   qnorm_upper(p) = the root x of 0.5 erfc(x / sqrt 2) = p by bisection on [-40, 40] on the host until the ends are
+ *   neighbouring doubles; the upper end (csrc/host/host_autosvd.h).
+ * 5. Fence (tukey_mc_up) over the c finite values of S2, read as x + 0.0; s = the ascending sort; c < 2^31.
+ *   Quartiles (R's type 7): Q(p) = s[lo] + (h - lo)(s[lo + 1] - s[lo]), h = (c - 1) p, lo = floor(h) (lo + 1 capped at c - 1);
+ *   Q1 = Q(0.25), Q3 = Q(0.75).  Median: the rule of "pcadapt" step 2.
+ *   Medcouple: z_i = x_i - med (one rounding; every z must be finite), A = {z > 0}, B = {|z| : z <= 0} ascending, the k values
+ *   with z = 0 first; n+ = |A| + k, n- = |B|, N = n+ n- (int64).  The multiset of N ratios in [0, +inf]: r = b / a (one
+ *   correctly rounded division) for every a in A and b in B; +inf for each of the k zero rows against every b > 0; for the k x k
+ *   ties at the median k (k - 1) / 2 ratios 0, k ratios 1 and k (k - 1) / 2 ratios +inf (robustbase's sign(k - 1 - i - j)
+ *   kernel).  With r_lo, r_hi the ratios of ascending ranks (N - 1) / 2 and N / 2:  mc = (g(r_lo) + g(r_hi)) / 2,
+ *   g(r) = (1 - r) / (1 + r), g(+inf) = -1.  c = 0: NaN.  b / a is non-decreasing in b and non-increasing in a after rounding, so
+ *   the ratios <= t of a row are a prefix of B: the count of ratios <= t is exact in O(c log c), and the two ranks are found by
+ *   bisection over the 63-bit pattern of t on the device.  The n+ x n- values are never formed.
+ *   Coefficient: coef = (qnorm_upper(alpha / c) - z75) / (2 z75), z75 = qnorm_upper(0.25) (Tukey's 1.5 for alpha / c = 0.0035).
+ *   Fence: thr = Q3 + coef (Q3 - Q1) exp(3 mc) if mc >= 0, else with exp(4 mc); on the host, in that order.
+ *   Outliers: S2_j > thr, strictly.
+ * Determinism.  Selections and counts are exact integers; the only atomics are integer counts. */
+/* the view of loci idx0[count] (int64, 0-based, host or device memory; any order, duplicates allowed) of another view -- also
+ * of one that no store can re-pack (tpg_view_impute).  Indistinguishable from a view packed from the store with those columns.
+ * An index outside [0, m) or count < 1: TPG_EINVAL. */
+int tpg_view_select_loci(tpg_ctx* ctx, const tpg_view* v, const int64_t* idx0, int64_t count, tpg_view** out);
+/* host only: qnorm_upper(p), 0 < p < 1 */
+int tpg_qnorm_upper(double p, double* x);
+/* host only: the 2 radius + 1 weights of step 4 (radius 0: the single weight 1); radius in [0, 1024] */
+int tpg_rollmean_weights(int radius, double* w);
+/* step 4 on its own.  x / out: m doubles, host or device memory (may be the same array); seg_start: nseg + 1 increasing int64,
+ * seg_start[0] = 0, seg_start[nseg] = m: segment s covers [seg_start[s], seg_start[s + 1]) */
+int tpg_rollmean_segments(tpg_ctx* ctx, const double* x, int64_t m, const int64_t* seg_start, int64_t nseg, int radius,
+                          double* out);
+/* the medcouple of the finite values of x[count] (host or device memory); mc on the host */
+int tpg_medcouple(tpg_ctx* ctx, const double* x, int64_t count, double* mc);
+/* step 5 on its own: report[TPG_TUKEY_REPORT_DOUBLES] (host) = {n_finite, q1, q3, med, mc, coef, thr} */
+#define TPG_TUKEY_REPORT_DOUBLES 7
+int tpg_tukey_mc_up(tpg_ctx* ctx, const double* x, int64_t count, double alpha, double* report);
+/* Steps 0 - 5.  *out: the result, owned by the library until tpg_autosvd_free.  chrom and hi host or device memory.  S, S2, the
+ * sort, the fence, the compaction of the kept list and the sub-view stay on the device; V passes through host memory once per
+ * iteration (m_keep x k doubles down with the SVD, up again for the distance). */
+int tpg_pca_auto_svd(tpg_ctx* ctx, const tpg_view* v, const int32_t* chrom, const int64_t* hi, int k, double thr_r2, int roll_size,
+                     double alpha_tukey, int64_t min_mac, int max_iter, void** out);
+int64_t tpg_autosvd_count(const void* r); /* kept loci */
+int tpg_autosvd_iters(const void* r);     /* SVDs computed */
+int tpg_autosvd_converged(const void* r);
+/* host memory, any may be NULL: d[k], u n x k, vload count x k, center[count], scale[count], idx0[count] (ascending loci of the
+ * view) */
+int tpg_autosvd_fetch(const void* r, double* d, double* u, double* vload, double* center, double* scale, int64_t* idx0,
+                      double* square_frobenius);
+/* detection pass iter (0-based; there are tpg_autosvd_iters of them, one fewer when the loop stopped at max_iter): the size of
+ * its kept list, its number of outliers and its fence report */
+int tpg_autosvd_history(const void* r, int iter, int64_t* n_kept, int64_t* n_outliers, double* report);
+/* its outliers, n_outliers each, any may be NULL: position in that pass's kept list, locus of the view */
+int tpg_autosvd_outliers(const void* r, int iter, int64_t* pos0, int64_t* idx0);
+/* its runs of at least min_size outliers that are consecutive in that pass's kept list and lie on one chromosome, as loci of
+ * the view (first, last); at most n_outliers / min_size of them; first0 / last0 may be NULL (count alone) */
+int tpg_autosvd_intervals(const void* r, int iter, int64_t min_size, int64_t* first0, int64_t* last0, int64_t* count);
+void tpg_autosvd_free(void* r);
+
 #ifdef __cplusplus
 }
 #endif

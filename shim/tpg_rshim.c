@@ -1338,6 +1338,117 @@ SEXP _tidypopgen_tpg_pcadapt(SEXP BM, SEXP rowInd, SEXP colInd, SEXP U) {
   return out;
 }
 
+/* ---- autoSVD ------------------------------------------------------------------------------------------------------ */
+
+#pragma weak tpg_pca_auto_svd
+#pragma weak tpg_autosvd_count
+#pragma weak tpg_autosvd_iters
+#pragma weak tpg_autosvd_converged
+#pragma weak tpg_autosvd_fetch
+#pragma weak tpg_autosvd_history
+#pragma weak tpg_autosvd_intervals
+#pragma weak tpg_autosvd_free
+
+/* tpg_pca_auto_svd(BM, rowInd, colInd, chrom, pos, hi, params): R/gt_pca_autoSVD.R (bigsnpr::snp_autoSVD) as one call of
+ * include/tpg.h "autoSVD".  chrom = one integer code per locus of colInd; pos = its position, or NULL (no lrldr then); hi = the
+ * clumping window (0-based last neighbour of every locus), or NULL to skip clumping; params = 7 numbers: k, thr_r2, roll_size,
+ * int_min_size, alpha_tukey, min_mac, max_iter.
+ * -> the big_SVD list(d, u, v, center, scale, n_iter, converged) with attr "subset" (positions in colInd of the kept loci,
+ * 1-based) and attr "lrldr" = list(Chr, Start, Stop), one entry per run of at least int_min_size consecutive outliers */
+static void* g_asv_pending = NULL; /* the result of a call whose R allocations are still to come (as g_roh_pending) */
+
+static void asv_drop_pending(void) {
+  if (g_asv_pending && tpg_autosvd_free) tpg_autosvd_free(g_asv_pending);
+  g_asv_pending = NULL;
+}
+
+SEXP _tidypopgen_tpg_pca_auto_svd(SEXP BM, SEXP rowInd, SEXP colInd, SEXP chrom, SEXP pos, SEXP hi, SEXP params) {
+  TPG_NEEDS(tpg_pca_auto_svd);
+  asv_drop_pending();
+  if ((TYPEOF(chrom) != INTSXP && TYPEOF(chrom) != REALSXP) || (TYPEOF(params) != INTSXP && TYPEOF(params) != REALSXP) ||
+      (pos != R_NilValue && TYPEOF(pos) != INTSXP && TYPEOF(pos) != REALSXP) ||
+      (hi != R_NilValue && TYPEOF(hi) != INTSXP && TYPEOF(hi) != REALSXP))
+    Rf_error("tidypopgen (GPU): chrom, pos, hi and params must be integer or double vectors");
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP ch = PROTECT(as_int(chrom)), pr = PROTECT(as_real(params));
+  SEXP ps = PROTECT(pos == R_NilValue ? pos : as_real(pos)), hs = PROTECT(hi == R_NilValue ? hi : as_real(hi));
+  const R_xlen_t n = XLENGTH(ri), m = XLENGTH(ci);
+  if (XLENGTH(ch) != m || (ps != R_NilValue && XLENGTH(ps) != m) || (hs != R_NilValue && XLENGTH(hs) != m))
+    Rf_error("tidypopgen (GPU): chrom / pos / hi and colInd differ in length");
+  if (XLENGTH(pr) != 7) Rf_error("tidypopgen (GPU): params must be 7 numbers: k, thr_r2, roll_size, int_min_size, alpha_tukey, min_mac, max_iter");
+  const double* q = REAL(pr);
+  for (int k = 0; k < 7; k++)
+    if (ISNAN(q[k])) Rf_error("tidypopgen (GPU): NA in params[%d]", k + 1);
+  const double big = 2147483647.0;
+  const int K = roh_int_param(q, 0, 1, big, "k"), roll = roh_int_param(q, 2, 0, big, "roll_size");
+  const int min_size = roh_int_param(q, 3, 1, big, "int_min_size"), min_mac = roh_int_param(q, 5, 0, big, "min_mac");
+  const int max_iter = roh_int_param(q, 6, 0, big, "max_iter");
+  for (R_xlen_t j = 0; j < m; j++)
+    if (INTEGER(ch)[j] == NA_INTEGER) Rf_error("tidypopgen (GPU): NA in chrom");
+  int64_t* h64 = NULL;
+  if (hs != R_NilValue) {
+    h64 = (int64_t*)R_alloc((size_t)(m > 0 ? m : 1), sizeof(int64_t));
+    for (R_xlen_t j = 0; j < m; j++) {
+      if (!isfinite(REAL(hs)[j]) || fabs(REAL(hs)[j]) > big) Rf_error("tidypopgen (GPU): NA in hi");
+      h64[j] = (int64_t)REAL(hs)[j];
+    }
+  }
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  void* r = NULL;
+  TPG_R_VIEW(v, tpg_pca_auto_svd(ctx(), v, INTEGER(ch), h64, K, q[1], roll, q[4], (int64_t)min_mac, max_iter, &r));
+  g_asv_pending = r; /* from here to asv_drop_pending() every R allocation may raise an error */
+  const int64_t c = tpg_autosvd_count(r);
+  const int iters = tpg_autosvd_iters(r), conv = tpg_autosvd_converged(r), passes = conv ? iters : iters - 1;
+  SEXP vals[7];
+  static const char* names[7] = {"d", "u", "v", "center", "scale", "n_iter", "converged"};
+  vals[0] = PROTECT(Rf_allocVector(REALSXP, K));
+  vals[1] = PROTECT(Rf_allocMatrix(REALSXP, (int)n, K));
+  vals[2] = PROTECT(Rf_allocMatrix(REALSXP, (int)c, K));
+  vals[3] = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)c));
+  vals[4] = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)c));
+  vals[5] = PROTECT(Rf_allocVector(INTSXP, 1));
+  vals[6] = PROTECT(Rf_allocVector(LGLSXP, 1));
+  SEXP subset = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)c));
+  int64_t* idx = (int64_t*)R_alloc((size_t)(c > 0 ? c : 1), sizeof(int64_t));
+  /* the runs of every pass: counted first, so that every R vector exists before the result is let go */
+  int64_t nrun = 0;
+  for (int it = 0; it < passes; it++) {
+    int64_t cnt = 0;
+    if (tpg_autosvd_intervals(r, it, min_size, NULL, NULL, &cnt) != TPG_OK) Rf_error("tidypopgen (GPU): %s", tpg_last_error());
+    nrun += cnt;
+  }
+  if (ps == R_NilValue) nrun = 0;
+  SEXP lr[3];
+  static const char* lr_names[3] = {"Chr", "Start", "Stop"};
+  lr[0] = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)nrun));
+  lr[1] = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)nrun));
+  lr[2] = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)nrun));
+  int64_t* ab = (int64_t*)R_alloc((size_t)(nrun > 0 ? 2 * nrun : 1), sizeof(int64_t));
+  int rc = tpg_autosvd_fetch(r, REAL(vals[0]), REAL(vals[1]), REAL(vals[2]), REAL(vals[3]), REAL(vals[4]), idx, NULL);
+  int64_t at = 0;
+  for (int it = 0; rc == TPG_OK && nrun > 0 && it < passes; it++) {
+    int64_t cnt = 0;
+    rc = tpg_autosvd_intervals(r, it, min_size, ab + at, ab + nrun + at, &cnt);
+    at += cnt;
+  }
+  asv_drop_pending();
+  if (rc != TPG_OK) Rf_error("tidypopgen (GPU): %s", tpg_last_error());
+  for (int64_t j = 0; j < c; j++) INTEGER(subset)[j] = (int)idx[j] + 1;
+  for (int64_t k = 0; k < nrun; k++) {
+    INTEGER(lr[0])[k] = INTEGER(ch)[ab[k]];
+    REAL(lr[1])[k] = REAL(ps)[ab[k]];
+    REAL(lr[2])[k] = REAL(ps)[ab[nrun + k]];
+  }
+  INTEGER(vals[5])[0] = iters;
+  LOGICAL(vals[6])[0] = conv != 0;
+  SEXP out = PROTECT(named_list(7, names, vals));
+  SEXP lrl = PROTECT(named_list(3, lr_names, lr));
+  Rf_setAttrib(out, Rf_install("subset"), subset);
+  Rf_setAttrib(out, Rf_install("lrldr"), lrl);
+  UNPROTECT(19);
+  return out;
+}
+
 /* ---- registration ------------------------------------------------------------------------------------------------
  * Same names and arities as the reference's table (src/RcppExports.cpp:348-371).  These rows replace the rows of the
  * same name there, and so do the three HWE rows of tpg_rshim_entries_hwe[] below; the other rows of that table
@@ -1415,11 +1526,16 @@ const R_CallMethodDef tpg_rshim_entries_pcadapt[] = {
     {"_tidypopgen_tpg_pcadapt", (DL_FUNC)&_tidypopgen_tpg_pcadapt, 4},
     {NULL, NULL, 0}};
 
+/* autoSVD, in a table of its own: the reference's routine is bigsnpr's, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_autosvd[] = {
+    {"_tidypopgen_tpg_pca_auto_svd", (DL_FUNC)&_tidypopgen_tpg_pca_auto_svd, 7},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the nine tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the ten tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1428,7 +1544,8 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_tajima) / sizeof(tpg_rshim_entries_tajima[0]) +
                              sizeof(tpg_rshim_entries_f2) / sizeof(tpg_rshim_entries_f2[0]) +
                              sizeof(tpg_rshim_entries_admix) / sizeof(tpg_rshim_entries_admix[0]) +
-                             sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0])];
+                             sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0]) +
+                             sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1439,6 +1556,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_f2; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_admix; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_pcadapt; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_autosvd; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;
@@ -1451,6 +1569,7 @@ void R_unload_tpgshim(DllInfo* dll) {
   (void)dll;
   _tidypopgen_tpg_release();
   roh_drop_pending();
+  asv_drop_pending();
   if (g_multi) {
     tpg_multi_destroy(g_multi);
     g_multi = NULL;

@@ -185,6 +185,33 @@ gt_pcadapt_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigs
             dist = res$dist, log10p = res$log10p, gc_lambda = res$gc_lambda)
 }
 
+# PCA with removal of long-range LD regions on the GPU (R/gt_pca_autoSVD.R around bigsnpr::snp_autoSVD; include/tpg.h "autoSVD" is
+# the definition).  infos.chr / infos.pos describe the loci of ind.col, in order; thr.r2 = NA skips clumping; size is the clumping
+# window in kb (in loci without positions).  Returns the big_SVD list with attr(, "subset") (the kept loci, as positions in the
+# FBM) and attr(, "lrldr") (a data.frame Chr / Start / Stop, only with positions), as bigsnpr does.
+gt_pca_autoSVD_gpu <- function(X, infos.chr, infos.pos = NULL, ind.row = bigstatsr::rows_along(X),
+                               ind.col = bigstatsr::cols_along(X), k = 10L, thr.r2 = 0.2, size = 100 / thr.r2, roll.size = 50L,
+                               int.min.size = 20L, alpha.tukey = 0.05, min.mac = 10L, max.iter = 5L) {
+  chr <- as.integer(factor(infos.chr, levels = unique(infos.chr)))
+  if (length(chr) != length(ind.col)) stop("infos.chr must have one entry per element of ind.col")
+  hi <- NULL
+  if (!is.na(thr.r2)) {
+    hi <- numeric(length(chr))
+    for (idx in split(seq_along(chr), chr)) {
+      hi[idx] <- if (is.null(infos.pos)) pmin(idx + floor(size), max(idx)) - 1
+                 else min(idx) + findInterval(infos.pos[idx] + size * 1000, infos.pos[idx]) - 2
+    }
+  }
+  params <- c(k, if (is.na(thr.r2)) 0 else thr.r2, roll.size, int.min.size, alpha.tukey, min.mac, max.iter)
+  res <- .Call(`_tidypopgen_tpg_pca_auto_svd`, X, as.integer(ind.row), as.integer(ind.col), chr,
+               if (is.null(infos.pos)) NULL else as.numeric(infos.pos), hi, as.numeric(params))
+  lr <- attr(res, "lrldr")
+  out <- structure(res[c("d", "u", "v", "center", "scale")], class = "big_SVD", subset = ind.col[attr(res, "subset")],
+                   lrldr = data.frame(Chr = unique(infos.chr)[lr$Chr], Start = lr$Start, Stop = lr$Stop),
+                   n_iter = res$n_iter, converged = res$converged)
+  out
+}
+
 # whole analyses on every GPU of the node (TPG_DEVICES); X is the FBM.code256 of a gen_tibble (attr(x$genotypes, "fbm"))
 # which: the matrices wanted; only the cross-products they need are computed (GRM alone: 2 of 5, KING + GRM: 4 of 5)
 tpg_snp_pairwise <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X),

@@ -293,6 +293,22 @@ PROTOTYPES = {
     "tpg_pchisq_log10_upper": (ci, [vp, vp, i64, ci, vp]),
     "tpg_qchisq_median": (ci, [ci, vp]),
     "tpg_pcadapt": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
+    # ---- autoSVD
+    "tpg_view_select_loci": (ci, [vp, vp, vp, i64, vp]),
+    "tpg_qnorm_upper": (ci, [f64, vp]),
+    "tpg_rollmean_weights": (ci, [ci, vp]),
+    "tpg_rollmean_segments": (ci, [vp, vp, i64, vp, i64, ci, vp]),
+    "tpg_medcouple": (ci, [vp, vp, i64, vp]),
+    "tpg_tukey_mc_up": (ci, [vp, vp, i64, f64, vp]),
+    "tpg_pca_auto_svd": (ci, [vp, vp, vp, vp, ci, f64, ci, f64, i64, ci, vp]),
+    "tpg_autosvd_count": (i64, [vp]),
+    "tpg_autosvd_iters": (ci, [vp]),
+    "tpg_autosvd_converged": (ci, [vp]),
+    "tpg_autosvd_fetch": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_autosvd_history": (ci, [vp, ci, vp, vp, vp]),
+    "tpg_autosvd_outliers": (ci, [vp, ci, vp, vp]),
+    "tpg_autosvd_intervals": (ci, [vp, ci, i64, vp, vp, vp]),
+    "tpg_autosvd_free": (None, [vp]),
 }
 
 for _name, (_restype, _argtypes) in PROTOTYPES.items():

@@ -298,6 +298,17 @@ class View:
         v.impute_report = {"imputed": int(rep.imputed), "loci_all_missing": int(rep.loci_all_missing)}
         return v
 
+    def select_loci(self, idx) -> "View":
+        """a new view of the loci idx (0-based positions in this view; any order, duplicates allowed) gathered on the device
+        (tpg_view_select_loci): also works where the store cannot be packed again, as behind impute()"""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+        h = C.c_void_p()
+        check(lib.tpg_view_select_loci(self.ctx.h, self.h, _ptr(idx), len(idx), C.byref(h)))
+        v = View.__new__(View)
+        v.X, v.ctx, v.h = self.X, self.ctx, h
+        v.n, v.m = int(lib.tpg_view_n(h)), int(lib.tpg_view_m(h))
+        return v
+
     def unpack(self) -> np.ndarray:
         out = np.zeros((self.n, self.m), dtype=np.uint8, order="F")
         check(lib.tpg_view_unpack(self.ctx.h, self.h, _ptr(out)))
@@ -1970,11 +1981,13 @@ def gt_pcadapt(X: FBM, pca: dict, k, ind_row=None, ind_col=None, impute: Optiona
     return out
 
 
-def ld_window_hi(chromosome, position=None, size=500.0, use_positions: bool = True, m: Optional[int] = None) -> np.ndarray:
+def ld_window_hi(chromosome, position=None, size=500.0, use_positions: bool = True, m: Optional[int] = None,
+                 check_runs: bool = True) -> np.ndarray:
     """the window of include/tpg.h "LD clumping": hi[j] = last locus (0-based) that is a neighbour of j.  With positions,
     neighbours are loci of the same chromosome with |position difference| <= size * 1000; without, loci of the same
     chromosome with |index difference| <= size.  Loci must be ordered: every chromosome one contiguous run, positions
-    non-decreasing inside it (is_loci_table_ordered stops the reference otherwise).  chromosome = None: one chromosome."""
+    non-decreasing inside it (is_loci_table_ordered stops the reference otherwise).  chromosome = None: one chromosome.
+    check_runs = False leaves the check of the runs to the callee (gt_pca_autoSVD: the library refuses them)."""
     if chromosome is None:
         if m is None:
             m = len(position)
@@ -1983,7 +1996,7 @@ def ld_window_hi(chromosome, position=None, size=500.0, use_positions: bool = Tr
         chrom = np.unique(np.asarray(chromosome), return_inverse=True)[1].astype(np.int64).ravel()
     m = len(chrom)
     starts = np.r_[0, np.flatnonzero(chrom[1:] != chrom[:-1]) + 1, m] if m else np.array([0, 0])
-    if len(np.unique(chrom[starts[:-1]])) != len(starts) - 1:
+    if check_runs and len(np.unique(chrom[starts[:-1]])) != len(starts) - 1:
         raise ValueError("loci are not ordered: a chromosome appears in more than one run")
     hi = np.empty(m, dtype=np.int64)
     if use_positions:
@@ -2063,6 +2076,145 @@ def loci_ld_clump(X: FBM, ind_row=None, ind_col=None, S=None, thr_r2: float = 0.
         ex[e - 1] = 1
     keep = ld_clump(v, hi, thr_r2, S, ex)
     return np.flatnonzero(keep) + 1 if return_id else keep
+
+
+# ---------------------------------------------------------------------------
+# autoSVD (include/tpg.h "autoSVD")
+
+TUKEY_REPORT_FIELDS = ("n_finite", "q1", "q3", "med", "mc", "coef", "thr")
+
+
+def qnorm_upper(p: float) -> float:
+    """the upper quantile of the standard normal, the root of 0.5 erfc(x / sqrt 2) = p (host only)"""
+    out = C.c_double()
+    check(lib.tpg_qnorm_upper(float(p), C.byref(out)))
+    return out.value
+
+
+def rollmean_weights(roll_size: int) -> np.ndarray:
+    """the 2 roll_size + 1 Gaussian weights of the rolling mean (host only)"""
+    w = np.zeros(2 * max(int(roll_size), 0) + 1)
+    check(lib.tpg_rollmean_weights(int(roll_size), _ptr(w)))
+    return w
+
+
+def _chrom_codes(chromosome, m: int) -> np.ndarray:
+    if chromosome is None:
+        return np.zeros(m, dtype=np.int32)
+    chrom = np.unique(np.asarray(chromosome), return_inverse=True)[1].astype(np.int32).ravel()
+    if len(chrom) != m:
+        raise ValueError("chromosome must describe every locus")
+    return chrom
+
+
+def rollmean(x, chromosome=None, roll_size: int = 50, ctx: Optional[Context] = None) -> np.ndarray:
+    """tpg_rollmean_segments: the Gaussian rolling mean of x with radius roll_size inside every run of equal chromosome"""
+    ctx = ctx or default_context()
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    chrom = _chrom_codes(chromosome, len(x))
+    seg = np.r_[0, np.flatnonzero(chrom[1:] != chrom[:-1]) + 1, len(x)].astype(np.int64)
+    out = np.zeros(len(x))
+    check(lib.tpg_rollmean_segments(ctx.h, _ptr(x), len(x), _ptr(seg), len(seg) - 1, int(roll_size), _ptr(out)))
+    return out
+
+
+def medcouple(x, ctx: Optional[Context] = None) -> float:
+    """tpg_medcouple: the medcouple of the finite values of x, an exact selection on the device"""
+    ctx = ctx or default_context()
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    out = C.c_double()
+    check(lib.tpg_medcouple(ctx.h, _ptr(x) if len(x) else None, len(x), C.byref(out)))
+    return out.value
+
+
+def tukey_mc_up(x, alpha: float = 0.05, ctx: Optional[Context] = None) -> dict:
+    """tpg_tukey_mc_up: the upper Tukey fence of x, corrected for skewness (medcouple) and multiplicity (alpha / count).
+    -> dict(n_finite, q1, q3, med, mc, coef, thr)"""
+    ctx = ctx or default_context()
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    rep = np.zeros(len(TUKEY_REPORT_FIELDS))
+    check(lib.tpg_tukey_mc_up(ctx.h, _ptr(x) if len(x) else None, len(x), float(alpha), _ptr(rep)))
+    out = dict(zip(TUKEY_REPORT_FIELDS, rep.tolist()))
+    out["n_finite"] = int(out["n_finite"])
+    return out
+
+
+def pca_auto_svd(v: View, chrom, hi=None, k: int = 10, thr_r2: float = 0.2, roll_size: int = 50, alpha_tukey: float = 0.05,
+                 min_mac: int = 10, max_iter: int = 5, int_min_size: int = 20) -> dict:
+    """tpg_pca_auto_svd on a view: chrom (m,) int32 codes, hi the clumping window of ld_window_hi or None for no clumping.
+    -> dict(d, u, v, center, scale, square_frobenius, idx0 (kept loci of the view, 0-based), n_iter, converged,
+    history = [dict(n_kept, n_outliers, report, pos0, idx0, intervals = [(first locus, last locus), ...])])"""
+    chrom = np.ascontiguousarray(chrom, dtype=np.int32)
+    if chrom.shape != (v.m,):
+        raise ValueError("chrom must have one entry per locus of the view")
+    hi = None if hi is None else _ld_hi(v, hi)
+    h = C.c_void_p()
+    check(lib.tpg_pca_auto_svd(v.ctx.h, v.h, _ptr(chrom), _ptr(hi), int(k), 0.0 if hi is None else float(thr_r2), int(roll_size),
+                               float(alpha_tukey), int(min_mac), int(max_iter), C.byref(h)))
+    try:
+        mk, iters = int(lib.tpg_autosvd_count(h)), int(lib.tpg_autosvd_iters(h))
+        conv = bool(lib.tpg_autosvd_converged(h))
+        d, u, vl = np.zeros(k), np.zeros((v.n, k), order="F"), np.zeros((mk, k), order="F")
+        center, scale, idx0 = np.zeros(mk), np.zeros(mk), np.zeros(mk, dtype=np.int64)
+        fro = C.c_double()
+        check(lib.tpg_autosvd_fetch(h, _ptr(d), _ptr(u), _ptr(vl), _ptr(center), _ptr(scale), _ptr(idx0), C.byref(fro)))
+        history = []
+        for it in range(iters if conv else iters - 1):
+            nk, no = C.c_int64(), C.c_int64()
+            rep = np.zeros(len(TUKEY_REPORT_FIELDS))
+            check(lib.tpg_autosvd_history(h, it, C.byref(nk), C.byref(no), _ptr(rep)))
+            pos, oi = np.zeros(no.value, dtype=np.int64), np.zeros(no.value, dtype=np.int64)
+            cap = max(1, no.value // max(1, int(int_min_size)))
+            first, last, cnt = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64), C.c_int64()
+            if no.value:
+                check(lib.tpg_autosvd_outliers(h, it, _ptr(pos), _ptr(oi)))
+            check(lib.tpg_autosvd_intervals(h, it, int(int_min_size), _ptr(first), _ptr(last), C.byref(cnt)))
+            report = dict(zip(TUKEY_REPORT_FIELDS, rep.tolist()))
+            report["n_finite"] = int(report["n_finite"])
+            history.append(dict(n_kept=int(nk.value), n_outliers=int(no.value), report=report, pos0=pos, idx0=oi,
+                                intervals=[(int(a), int(b)) for a, b in zip(first[:cnt.value], last[:cnt.value])]))
+    finally:
+        lib.tpg_autosvd_free(h)
+    return dict(d=d, u=u, v=vl, center=center, scale=scale, square_frobenius=fro.value, idx0=idx0, n_iter=iters, converged=conv,
+                history=history)
+
+
+def gt_pca_autoSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, thr_r2: Optional[float] = 0.2, use_positions: bool = True,
+                   size=None, roll_size: int = 50, int_min_size: int = 20, alpha_tukey: float = 0.05, min_mac: int = 10,
+                   max_iter: int = 5, chromosome=None, position=None, total_var: bool = True, impute: Optional[str] = None,
+                   impute_seed: int = 0) -> dict:
+    """R/gt_pca_autoSVD.R (around bigsnpr::snp_autoSVD; the definition is include/tpg.h "autoSVD"): clump, compute the SVD,
+    find the loci whose loadings are outliers in consecutive stretches (long-range LD regions), remove them, repeat until none
+    is left or max_iter SVDs have been cleaned.  chromosome / position describe the loci of ind_col, in order.  thr_r2 = None
+    skips clumping; size is the clumping window (default 100 / thr_r2: kb with use_positions, loci without).  A missing
+    genotype is an error unless impute = "mode" | "mean0" | "random" fills the view first.
+    -> dict(d, u, v, center, scale, method = "autoSVD", loci (1-based indices into ind_col of the kept loci), lrldr (only with
+    positions: [(chromosome, position of the first, position of the last)] of every run of at least int_min_size outliers,
+    accumulated over the iterations), n_iter, converged, history[, square_frobenius])"""
+    v = _pca_view(X, ind_row, ind_col, CODE_IMPUTE_PRED, impute, impute_seed)
+    chrom = _chrom_codes(chromosome, v.m)
+    hi = None
+    if thr_r2 is not None:
+        if size is None:
+            size = 100.0 / thr_r2
+        if use_positions and position is None:
+            raise ValueError("use_positions = TRUE needs positions; pass use_positions=False to count in loci")
+        hi = ld_window_hi(chromosome, position, size, use_positions, m=v.m, check_runs=False)
+        if len(hi) != v.m:
+            raise ValueError("chromosome / position must describe every locus of ind_col")
+    r = pca_auto_svd(v, chrom, hi, k=k, thr_r2=0.0 if thr_r2 is None else thr_r2, roll_size=roll_size, alpha_tukey=alpha_tukey,
+                     min_mac=min_mac, max_iter=max_iter, int_min_size=int_min_size)
+    out = dict(d=r["d"], u=r["u"], v=r["v"], center=r["center"], scale=r["scale"], method="autoSVD", loci=r["idx0"] + 1,
+               n_iter=r["n_iter"], converged=r["converged"], history=r["history"])
+    if position is not None:
+        pos = np.asarray(position)
+        if len(pos) != v.m:
+            raise ValueError("position must describe every locus of ind_col")
+        names = np.zeros(v.m, dtype=np.int64) if chromosome is None else np.asarray(chromosome)
+        out["lrldr"] = [(names[a].item(), pos[a].item(), pos[b].item()) for h in r["history"] for a, b in h["intervals"]]
+    if total_var:
+        out["square_frobenius"] = r["square_frobenius"]
+    return out
 
 
 # include/tpg.h "Runs of homozygosity": loci per chunk of the status stage (results do not depend on it; the seam tests do)
