@@ -479,6 +479,54 @@ int tpg_admix_em(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, c
 /* l(Q, F) alone for a caller's own (Q, P), taken as given (no normalisation, no clamp): one likelihood-only pass */
 int tpg_admix_loglik(tpg_ctx* ctx, const tpg_view* v, int K, const double* Q, const double* P, double* loglik);
 
+/* ---- admixture cross-validation (gt_admixture(crossval = TRUE), R/gt_admixture.R:20, 37, 184-196, 287-290: the reference passes
+ * --cv to the outside binary and reads "CV error" back from its log; nothing pins that number, so what is computed is defined
+ * HERE.  The procedure -- hold-out folds of the typed genotypes, a refit per fold, the binomial deviance of the held-out genotypes
+ * under the refit -- is that of Alexander and Lange 2011, RECALLED, NOT PINNED) -------------------------------------------------
+ * Folds.  The fold of an entry is a pure function of (cv_seed, i, j), the 0-based position in the VIEW (kept row, kept column),
+ *   not in the store, so it does not depend on launch shape, block plan or device.  With M = tpg_mix64 and 64-bit unsigned
+ *   arithmetic:
+ *     key = M((cv_seed ^ 0xC3C3C3C3C3C3C3C3) ^ M(j));  h = M(key ^ M(i));  fold(i,j) = ((h >> 32) * folds) >> 32.
+ *   2 <= folds <= TPG_ADMIX_MAX_FOLDS.  Only typed entries are ever held out; the padding stays code 3.
+ * Hold-out view.  train_f is the view with every typed entry of fold f set to code 3 and everything else unchanged: a NEW view of
+ *   the same geometry (tpg_view_holdout), which any entry point takes.  A locus or an individual typed nowhere in train_f is
+ *   handled by the EM as "admixture" says: it keeps its start, and the held-out entries are still predicted from that state.
+ * Hold-out sums of a state (Q, F) for a pair (full, train) of the same geometry, over the entries typed in `full` and missing in
+ *   `train`:
+ *     ll_h  = sum ln(p^g pbar^(2-g)), p and pbar formed exactly as in "admixture" (ascending k, fused terms, pbar a sum of its
+ *             own, the product rounded once, one logarithm);
+ *     n_h   = the number of such entries;  het_h = the number of them with g = 1 (both int64, exact).
+ *   Q and P are taken as given (no normalisation, no clamp), as tpg_admix_loglik takes them.
+ * Deviance and CV error.  Per held-out entry dev = 2 [ g ln(g / 2p) + (2 - g) ln((2 - g) / 2 pbar) ] with 0 ln 0 = 0, which is
+ *   -2 ln(p^g pbar^(2-g)) - [g = 1] 4 ln 2.  So for fold f, in IEEE double,
+ *     dev_f = -2.0 * ll_f - 2.772588722239781 * (double)het_f          (two products, then one subtraction, no fusing)
+ *     cv_error = (dev_0 + dev_1 + ... in ascending f) / (double)(n_0 + n_1 + ...).
+ *   A constant factor or offset per entry does not move the K that minimises cv_error; ADMIXTURE's own number may differ by one.
+ * Cross-validation (tpg_admix_cv).  For f = 0 .. folds - 1 in order: train_f; tpg_admix_em on it with the caller's parameters and
+ *   the SAME start for every fold (q0 / f0, or the seeded one); the hold-out sums of (v, train_f) from the Q and P of that run,
+ *   which never leave the device; train_f is freed, so the peak extra memory is one view (its L and T layouts).  Then
+ *   tpg_admix_cv_error.  Nothing proportional to N or M crosses PCIe (a host q0 / f0 goes up once).
+ * Rounding.  ll_h obeys the bound of "admixture" with T = n_h: |dl| <= u [ (2 T + 2) |l| + 2 (K + 4) T ].  The counts are exact.
+ *   Every sum has a fixed shape (a thread's entries ascending, a butterfly over the wave, the four waves in order, the tiles by a
+ *   one-workgroup kernel); no floating-point atomics; two calls give the same bits. */
+#define TPG_ADMIX_MAX_FOLDS 64
+/* train_f of `full` as a new view (free it with tpg_view_free); n_held (host memory, may be NULL) = the entries held out.
+ * folds outside [2, TPG_ADMIX_MAX_FOLDS], fold outside [0, folds), a view without its locus-tiled layout: TPG_EINVAL */
+int tpg_view_holdout(tpg_ctx* ctx, const tpg_view* full, int folds, int fold, uint64_t cv_seed, tpg_view** out, int64_t* n_held);
+/* Q: N x K, P: M x K, column-major doubles, host or device memory; ll, n_held and n_het are host memory and may each be NULL.
+ * Views of different n or m, K outside [1, TPG_ADMIX_MAX_K]: TPG_EINVAL, nothing written */
+int tpg_admix_holdout_sums(tpg_ctx* ctx, const tpg_view* full, const tpg_view* train, int K, const double* Q, const double* P,
+                           double* ll, int64_t* n_held, int64_t* n_het);
+/* host only, no context, no GPU: the deviances (fold_dev[folds], may be NULL) and the CV error from the folds' sums.  folds out of
+ * range, a negative count, more heterozygotes than entries, a total count of 0: TPG_EINVAL, nothing written */
+int tpg_admix_cv_error(int folds, const double* fold_ll, const int64_t* fold_count, const int64_t* fold_het, double* fold_dev,
+                       double* cv_error);
+/* the per-fold arrays (host memory) have `folds` entries and may each be NULL; q0 / f0 as in tpg_admix_em.  Errors: those of
+ * tpg_admix_em, and folds out of range.  Every output is written at the very end: after an error they are untouched. */
+int tpg_admix_cv(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, const tpg_admix_params* params, int folds,
+                 uint64_t cv_seed, const double* q0, const double* f0, double* cv_error, double* fold_ll, int64_t* fold_count,
+                 int64_t* fold_het, int32_t* fold_iter, int32_t* fold_converged);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

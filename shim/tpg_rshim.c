@@ -1309,6 +1309,75 @@ SEXP _tidypopgen_tpg_admixture(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP s
   return out;
 }
 
+/* ---- admixture cross-validation ----------------------------------------------------------------------------------- */
+
+#pragma weak tpg_admix_cv
+#pragma weak tpg_admix_cv_error
+
+/* tpg_admixture_cv(BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0, folds, cv_seed): what crossval = TRUE adds to a run of
+ * R/gt_admixture.R:184-196 (the outside binary's --cv and the "CV error" line of its log), as one call of tpg_admix_cv of
+ * include/tpg.h "admixture cross-validation" for one k and one run.  The first nine arguments are those of tpg_admixture; folds =
+ * an integer in [2, 64]; cv_seed follows the rule of seed.
+ * -> list(cv_error, fold_deviance: folds, fold_count: folds (double), fold_n_iter: folds (integer), fold_converged: folds) */
+SEXP _tidypopgen_tpg_admixture_cv(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0, SEXP p0,
+                                  SEXP folds, SEXP cv_seed) {
+  TPG_NEEDS(tpg_admix_cv);
+  TPG_NEEDS(tpg_admix_cv_error);
+  const int K = Rf_asInteger(k);
+  if (K == NA_INTEGER || K < 1) Rf_error("tidypopgen (GPU): k must be a positive integer");
+  if (TYPEOF(seed) != REALSXP || XLENGTH(seed) != 1) Rf_error("tidypopgen (GPU): seed must be a double vector of length 1");
+  const double sd = REAL(seed)[0];
+  if (!(sd >= 0 && sd <= 9007199254740992.0) || sd != floor(sd))
+    Rf_error("tidypopgen (GPU): seed must be a whole number in [0, 2^53]");
+  const int mi = Rf_asInteger(max_iter);
+  if (mi == NA_INTEGER || mi < 0) Rf_error("tidypopgen (GPU): max_iter must be a non-negative integer");
+  if ((TYPEOF(tol) != REALSXP && TYPEOF(tol) != INTSXP) || XLENGTH(tol) != 1) Rf_error("tidypopgen (GPU): tol must be one number");
+  SEXP ts = PROTECT(as_real(tol));
+  const double tl = REAL(ts)[0];
+  UNPROTECT(1);
+  if (!(tl >= 0)) Rf_error("tidypopgen (GPU): tol must be a non-negative number");
+  const int nf = Rf_asInteger(folds);
+  if (nf == NA_INTEGER || nf < 2 || nf > TPG_ADMIX_MAX_FOLDS) Rf_error("tidypopgen (GPU): folds must be an integer in [2, 64]");
+  if (TYPEOF(cv_seed) != REALSXP || XLENGTH(cv_seed) != 1) Rf_error("tidypopgen (GPU): cv_seed must be a double vector of length 1");
+  const double cs = REAL(cv_seed)[0];
+  if (!(cs >= 0 && cs <= 9007199254740992.0) || cs != floor(cs))
+    Rf_error("tidypopgen (GPU): cv_seed must be a whole number in [0, 2^53]");
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  const R_xlen_t n = XLENGTH(ri), m = XLENGTH(ci);
+  SEXP qs = PROTECT(q0 == R_NilValue ? R_NilValue : Rf_coerceVector(q0, REALSXP));
+  SEXP ps = PROTECT(p0 == R_NilValue ? R_NilValue : Rf_coerceVector(p0, REALSXP));
+  if (qs != R_NilValue && XLENGTH(qs) != n * (R_xlen_t)K) Rf_error("tidypopgen (GPU): q0 must be length(rowInd) x k");
+  if (ps != R_NilValue && XLENGTH(ps) != m * (R_xlen_t)K) Rf_error("tidypopgen (GPU): p0 must be length(colInd) x k");
+  SEXP vals[5];
+  vals[0] = PROTECT(Rf_allocVector(REALSXP, 1));
+  vals[1] = PROTECT(Rf_allocVector(REALSXP, nf));
+  vals[2] = PROTECT(Rf_allocVector(REALSXP, nf));
+  vals[3] = PROTECT(Rf_allocVector(INTSXP, nf));
+  vals[4] = PROTECT(Rf_allocVector(LGLSXP, nf));
+  static const char* names[5] = {"cv_error", "fold_deviance", "fold_count", "fold_n_iter", "fold_converged"};
+  SEXP out = PROTECT(named_list(5, names, vals));
+  tpg_admix_params P;
+  tpg_admix_params_default(&P);
+  P.max_iter = mi;
+  P.tol = tl;
+  P.seed = (uint64_t)sd;
+  double ll[TPG_ADMIX_MAX_FOLDS], cv = 0;
+  int64_t cnt[TPG_ADMIX_MAX_FOLDS], het[TPG_ADMIX_MAX_FOLDS];
+  int32_t nit[TPG_ADMIX_MAX_FOLDS], conv[TPG_ADMIX_MAX_FOLDS];
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_admix_cv(ctx(), v, NULL, K, &P, nf, (uint64_t)cs, qs == R_NilValue ? NULL : REAL(qs),
+                             ps == R_NilValue ? NULL : REAL(ps), &cv, ll, cnt, het, nit, conv));
+  TPG_R(tpg_admix_cv_error(nf, ll, cnt, het, REAL(vals[1]), &cv));
+  REAL(vals[0])[0] = cv;
+  for (int f = 0; f < nf; f++) {
+    REAL(vals[2])[f] = (double)cnt[f];
+    INTEGER(vals[3])[f] = nit[f];
+    LOGICAL(vals[4])[f] = conv[f] != 0;
+  }
+  UNPROTECT(10);
+  return out;
+}
+
 /* ---- pcadapt ------------------------------------------------------------------------------------------------------ */
 
 #pragma weak tpg_pcadapt
@@ -1521,6 +1590,11 @@ const R_CallMethodDef tpg_rshim_entries_admix[] = {
     {"_tidypopgen_tpg_admixture", (DL_FUNC)&_tidypopgen_tpg_admixture, 9},
     {NULL, NULL, 0}};
 
+/* Admixture cross-validation, in a table of its own (tpg_rshim_entries_admix[] keeps its one row). */
+const R_CallMethodDef tpg_rshim_entries_admix_cv[] = {
+    {"_tidypopgen_tpg_admixture_cv", (DL_FUNC)&_tidypopgen_tpg_admixture_cv, 11},
+    {NULL, NULL, 0}};
+
 /* The pcadapt scan, in a table of its own: the reference's routine is bigsnpr's, without a native row. */
 const R_CallMethodDef tpg_rshim_entries_pcadapt[] = {
     {"_tidypopgen_tpg_pcadapt", (DL_FUNC)&_tidypopgen_tpg_pcadapt, 4},
@@ -1535,7 +1609,7 @@ const R_CallMethodDef tpg_rshim_entries_autosvd[] = {
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the ten tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the eleven tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1544,6 +1618,7 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_tajima) / sizeof(tpg_rshim_entries_tajima[0]) +
                              sizeof(tpg_rshim_entries_f2) / sizeof(tpg_rshim_entries_f2[0]) +
                              sizeof(tpg_rshim_entries_admix) / sizeof(tpg_rshim_entries_admix[0]) +
+                             sizeof(tpg_rshim_entries_admix_cv) / sizeof(tpg_rshim_entries_admix_cv[0]) +
                              sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0]) +
                              sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0])];
   size_t k = 0;
@@ -1555,6 +1630,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_tajima; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_f2; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_admix; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_admix_cv; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_pcadapt; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_autosvd; e->name; e++) all[k++] = *e;
   all[k].name = NULL;

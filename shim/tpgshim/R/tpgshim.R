@@ -158,14 +158,21 @@ tpg_f2_blocks <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigst
 # Ancestry proportions by EM on the GPU for one k and one run (the PLINK export, the outside `admixture` program and the reading
 # back of its .Q / .P files of R/gt_admixture.R:86-236; include/tpg.h "admixture" is the definition).  seed: one whole number;
 # q0 / p0: a start (individuals x k, loci x k) or NULL for the seeded one.  Returns the gt_admix list of the reference for that
-# run (k, Q, P, loglik), with n_iter and converged beside it.  P is the frequency of the counted (alt) allele.  crossval,
+# run (k, Q, P, loglik), with n_iter and converged beside it.  P is the frequency of the counted (alt) allele.
+# crossval = TRUE adds cv, the name the reference uses: the cv_folds-fold cross-validation error of this k from the same start
+# (include/tpg.h "admixture cross-validation"; cv_seed, one whole number, keys the folds).
 # conda_env and outdir have no counterpart.
 gt_admixture_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), k, seed = 0,
-                             max_iter = 1000L, tol = 1e-4, q0 = NULL, p0 = NULL) {
+                             max_iter = 1000L, tol = 1e-4, q0 = NULL, p0 = NULL, crossval = FALSE, cv_folds = 5L, cv_seed = 0) {
   res <- .Call(`_tidypopgen_tpg_admixture`, X, as.integer(ind.row), as.integer(ind.col), as.integer(k), as.numeric(seed),
                as.integer(max_iter), as.numeric(tol), q0, p0)
   adm_list <- list(k = as.integer(k), Q = list(res$Q), P = list(res$P), loglik = res$loglik, n_iter = res$n_iter,
                    converged = res$converged)
+  if (isTRUE(crossval)) {
+    cvres <- .Call(`_tidypopgen_tpg_admixture_cv`, X, as.integer(ind.row), as.integer(ind.col), as.integer(k), as.numeric(seed),
+                   as.integer(max_iter), as.numeric(tol), q0, p0, as.integer(cv_folds), as.numeric(cv_seed))
+    adm_list$cv <- cvres$cv_error
+  }
   class(adm_list) <- c("gt_admix", "list")
   adm_list
 }

@@ -199,6 +199,11 @@ PROTOTYPES = {
     "tpg_admix_chunk_loci": (i64, []),
     "tpg_admix_em": (ci, [vp, vp, vp, ci, P(AdmixParams), vp, vp, vp, vp, vp, vp, vp, vp]),
     "tpg_admix_loglik": (ci, [vp, vp, ci, vp, vp, vp]),
+    # ---- admixture cross-validation
+    "tpg_view_holdout": (ci, [vp, vp, ci, ci, u64, vp, vp]),
+    "tpg_admix_holdout_sums": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp]),
+    "tpg_admix_cv_error": (ci, [ci, vp, vp, vp, vp, vp]),
+    "tpg_admix_cv": (ci, [vp, vp, vp, ci, P(AdmixParams), ci, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tpg_pop_global_stats": (ci, [vp, vp, vp, ci, vp, vp, vp]),
     "tpg_pop_basic_stats": (ci, [vp, vp, vp, ci, vp, ci, vp, vp]),
     "tpg_window_stats": (ci, [vp, vp, i64, ci, vp, vp, vp, i64, ci, ci, vp, vp]),

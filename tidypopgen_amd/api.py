@@ -298,6 +298,19 @@ class View:
         v.impute_report = {"imputed": int(rep.imputed), "loci_all_missing": int(rep.loci_all_missing)}
         return v
 
+    def holdout(self, folds: int, fold: int, cv_seed: int = 0) -> "View":
+        """a new view of the same rows / columns with the typed genotypes of one cross-validation fold set to missing
+        (tpg_view_holdout, include/tpg.h "admixture cross-validation"); their number is left in `.n_held` of the result"""
+        h = C.c_void_p()
+        held = C.c_int64()
+        check(lib.tpg_view_holdout(self.ctx.h, self.h, int(folds), int(fold), int(cv_seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h),
+                                   C.byref(held)))
+        v = View.__new__(View)
+        v.X, v.ctx, v.h = self.X, self.ctx, h
+        v.n, v.m = int(lib.tpg_view_n(h)), int(lib.tpg_view_m(h))
+        v.n_held = int(held.value)
+        return v
+
     def select_loci(self, idx) -> "View":
         """a new view of the loci idx (0-based positions in this view; any order, duplicates allowed) gathered on the device
         (tpg_view_select_loci): also works where the store cannot be packed again, as behind impute()"""
@@ -1697,14 +1710,67 @@ def admix_loglik(v: View, Q, P) -> float:
     return ll.value
 
 
+ADMIX_MAX_FOLDS = 64  # TPG_ADMIX_MAX_FOLDS of include/tpg.h
+
+
+def admix_holdout_sums(full: View, train: View, Q, P) -> dict:
+    """tpg_admix_holdout_sums: over the entries typed in `full` and missing in `train` (two views of the same geometry, as
+    View.holdout makes them), from the caller's own (Q, P) taken as given -> dict(ll = sum ln(p^g pbar^(2-g)), n_held, n_het)"""
+    if isinstance(Q, (int, np.integer)) or isinstance(P, (int, np.integer)):
+        raise ValueError("admix_holdout_sums takes numpy arrays (K is read from their shape)")
+    q = np.asfortranarray(Q, dtype=np.float64)
+    K = q.shape[1] if q.ndim == 2 else 0
+    q, p = _admix_mat(q, full.n, K, "Q"), _admix_mat(P, full.m, K, "P")
+    ll, cnt, het = C.c_double(), C.c_int64(), C.c_int64()
+    check(lib.tpg_admix_holdout_sums(full.ctx.h, full.h, train.h, K, _ptr(q), _ptr(p), C.byref(ll), C.byref(cnt), C.byref(het)))
+    return dict(ll=ll.value, n_held=int(cnt.value), n_het=int(het.value))
+
+
+def admix_cv_error(fold_ll, fold_count, fold_het) -> dict:
+    """tpg_admix_cv_error (host only): the folds' hold-out sums -> dict(cv_error, fold_deviance); deviance of fold f =
+    -2 ll_f - 4 ln 2 het_f, cv_error = their sum / the total count"""
+    ll = np.ascontiguousarray(fold_ll, dtype=np.float64).ravel()
+    cnt = np.ascontiguousarray(fold_count, dtype=np.int64).ravel()
+    het = np.ascontiguousarray(fold_het, dtype=np.int64).ravel()
+    if not (len(ll) == len(cnt) == len(het)):
+        raise ValueError("fold_ll, fold_count and fold_het must have one entry per fold")
+    dev = np.zeros(max(len(ll), 1))
+    cv = C.c_double()
+    check(lib.tpg_admix_cv_error(len(ll), _ptr(ll), _ptr(cnt), _ptr(het), _ptr(dev), C.byref(cv)))
+    return dict(cv_error=cv.value, fold_deviance=dev[: len(ll)])
+
+
+def admix_cv(v: View, K: int, folds: int = 5, cv_seed: int = 0, Q0=None, F0=None, seed: int = 0, max_iter: int = 1000,
+             tol: float = 1e-4, update_q: bool = True, update_f: bool = True, ploidy=None) -> dict:
+    """tpg_admix_cv (include/tpg.h "admixture cross-validation"): for every fold, the EM on the view without the fold's genotypes
+    (the same start each time: Q0 / F0 or the seeded one) and the deviance of the held-out genotypes under that fit, all on the
+    device.  -> dict(cv_error, fold_deviance, fold_ll, fold_count, fold_het, fold_n_iter, fold_converged)"""
+    K, folds = int(K), int(folds)
+    q0, f0 = _admix_mat(Q0, v.n, K, "Q0"), _admix_mat(F0, v.m, K, "F0")
+    pr = _lib.AdmixParams(int(max_iter), float(tol), int(bool(update_q)), int(bool(update_f)), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    nf = min(max(folds, 1), ADMIX_MAX_FOLDS)  # folds out of range is the library's to refuse
+    ll, cnt, het = np.zeros(nf), np.zeros(nf, dtype=np.int64), np.zeros(nf, dtype=np.int64)
+    nit, conv = np.zeros(nf, dtype=np.int32), np.zeros(nf, dtype=np.int32)
+    cv = C.c_double()
+    pl = _f64(ploidy)
+    check(lib.tpg_admix_cv(v.ctx.h, v.h, _ptr(pl), K, C.byref(pr), folds, int(cv_seed) & 0xFFFFFFFFFFFFFFFF, _ptr(q0), _ptr(f0),
+                           C.byref(cv), _ptr(ll), _ptr(cnt), _ptr(het), _ptr(nit), _ptr(conv)))
+    dev = admix_cv_error(ll, cnt, het)["fold_deviance"]
+    return dict(cv_error=cv.value, fold_deviance=dev, fold_ll=ll, fold_count=cnt, fold_het=het, fold_n_iter=nit,
+                fold_converged=conv.astype(bool))
+
+
 def gt_admixture(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, seed=None, max_iter: int = 1000,
-                 tol: float = 1e-4) -> dict:
+                 tol: float = 1e-4, crossval: bool = False, cv_folds: int = 5, cv_seed: int = 0) -> dict:
     """R/gt_admixture.R:62-236 with the EM of include/tpg.h "admixture" in place of the outside binary: every k of `k` (a
     scalar or a list) is run n_runs times on one resident view.  seed has n_runs entries (repeated for every k) or
     n_runs * len(k), one per run in the order of the result (k by k); None: 0, 1, ... in that order.
     -> a gt_admix-shaped dict: k (one entry per run), Q, P, loglik as lists, plus n_iter and converged.
-    crossval, conda_env and outdir of the reference have no counterpart here: there is no cross-validation, no
-    outside program and no file; `log` is absent for the same reason.  P is the frequency of the counted allele."""
+    crossval=True adds `cv`, parallel to `k` (the name the reference uses): the cv_folds-fold cross-validation error of that
+    run's k and seed on the same resident view (admix_cv; include/tpg.h "admixture cross-validation" is the definition, so the
+    number orders the k as ADMIXTURE's does without being ADMIXTURE's).  The smallest cv marks the k to use.
+    conda_env and outdir of the reference have no counterpart here: there is no outside program and no file; `log` is absent
+    for the same reason.  P is the frequency of the counted allele."""
     if k is None:
         raise ValueError("k is required")
     ks = [int(x) for x in np.atleast_1d(k)]
@@ -1717,14 +1783,21 @@ def gt_admixture(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, se
             seed = seed * len(ks)
     else:
         seed = list(range(n_runs * len(ks)))
+    if crossval and not (isinstance(cv_folds, (int, np.integer)) and 2 <= cv_folds <= ADMIX_MAX_FOLDS):
+        raise ValueError(f"'cv_folds' should be an integer in [2, {ADMIX_MAX_FOLDS}]")
     v = View(X, ind_row, ind_col)
     out = dict(k=[], Q=[], P=[], loglik=[], n_iter=[], converged=[])
+    if crossval:
+        out["cv"] = []
     for a, kk in enumerate(ks):
         for b in range(n_runs):
             r = admix_em(v, kk, seed=seed[a * n_runs + b], max_iter=max_iter, tol=tol)
             out["k"].append(kk)
             for name in ("Q", "P", "loglik", "n_iter", "converged"):
                 out[name].append(r[name])
+            if crossval:
+                out["cv"].append(admix_cv(v, kk, folds=cv_folds, cv_seed=cv_seed, seed=seed[a * n_runs + b], max_iter=max_iter,
+                                          tol=tol)["cv_error"])
     return out
 
 

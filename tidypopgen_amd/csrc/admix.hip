@@ -485,3 +485,257 @@ extern "C" int tpg_admix_loglik(tpg_ctx* ctx, const tpg_view* v, int K, const do
   TPG_HIP(tpg_fetch_small(ctx, loglik, run.trace, sizeof(double)));
   return TPG_OK;
 }
+
+// ---- cross-validation (include/tpg.h "admixture cross-validation") -----------------------------------------------------------
+// Two kernels.  admix_holdout_view: L -> the L of a new view with the typed entries of one fold set to code 3; the geometry of
+// tpg_impute_view_kernel (a wave per tile of 32 loci, four tiles per workgroup, lane (r, h) owns locus r), one read and one write of
+// the layout.  The fold of an entry is a hash of (cv_seed, i, j); M(i) of the 128 individuals of a block is the same for the four
+// tiles of a workgroup, so it is staged once per block through LDS (a broadcast read) and an entry costs one tpg_mix64.
+// admix_holdout_sweep: the likelihood-only pass over the entries typed in `full` and missing in `train`: wave w decodes dword w of
+// BOTH planes at the same offset; the sum shape is that of admix_f_sweep_kernel<KT, false>; the two counts are integers (wave sum,
+// one integer atomic per wave).
+namespace {
+
+constexpr uint64_t ADM_CV_SALT = 0xC3C3C3C3C3C3C3C3ull;
+
+__host__ __device__ inline int admix_fold_of(uint64_t locus_key, uint64_t mi, int folds) {
+  const uint64_t h = tpg_mix64(locus_key ^ mi);
+  return (int)(((h >> 32) * (uint64_t)folds) >> 32);
+}
+
+__global__ __launch_bounds__(256) void admix_holdout_view_kernel(const uint4* __restrict__ L, uint4* __restrict__ out, int64_t n_lt,
+                                                                 int64_t Qb, int folds, int fold, uint64_t cv_seed,
+                                                                 unsigned long long* __restrict__ d_held) {
+  __shared__ uint64_t mi[2][128];  // M(i) of the block's individuals; two buffers: one barrier per block
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int64_t lt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool live = lt < n_lt;  // a wave beyond the last tile still stages and meets the barriers
+  const uint64_t key = tpg_mix64((cv_seed ^ ADM_CV_SALT) ^ tpg_mix64((uint64_t)(lt * 32 + r)));
+  int held = 0;
+  for (int64_t q = 0; q < Qb; q++) {
+    uint64_t* __restrict__ ms = mi[q & 1];
+    if (threadIdx.x < 128) ms[threadIdx.x] = tpg_mix64((uint64_t)(128 * q + threadIdx.x));
+    __syncthreads();
+    if (!live) continue;
+    const uint4 a = L[(lt * Qb + q) * 64 + lane];
+    uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+      // typed entries only: the padding (individuals >= n, loci >= m) is code 3 and stays so
+      uint32_t typed = ~(w[d] & (w[d] >> 1)) & 0x55555555u;
+      while (typed) {
+        const int pos = __ffs(typed) - 1;  // 8 b + 2 k: element 4 k + b
+        typed &= typed - 1;
+        const int e = 4 * ((pos & 7) >> 1) + (pos >> 3);
+        if (admix_fold_of(key, ms[32 * d + 16 * h + e], folds) == fold) {
+          w[d] |= 3u << pos;
+          held++;
+        }
+      }
+    }
+    out[(lt * Qb + q) * 64 + lane] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  for (int o = 32; o > 0; o >>= 1) held += __shfl_xor(held, o);
+  if (lane == 0 && held) atomicAdd(d_held, (unsigned long long)held);
+}
+
+// one workgroup per tile of 32 loci; Lf / Lt: the L planes of the full and the training view (the same geometry).
+// ll_part[lt] = the tile's share of sum ln(p^g pbar^(2 - g)) over the held-out entries; d_cnt[0] += their number, d_cnt[1] += g = 1
+template <int KT>
+__global__ __launch_bounds__(256) void admix_holdout_sweep_kernel(const uint32_t* __restrict__ Lf, const uint32_t* __restrict__ Lt,
+                                                                  int64_t Qb, int64_t n, int64_t m, const double* __restrict__ Qd,
+                                                                  const double* __restrict__ Fd, double* __restrict__ ll_part,
+                                                                  unsigned long long* __restrict__ d_cnt) {
+  __shared__ double stage[128 * KT];
+  __shared__ double wll[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t lt = blockIdx.x, j = lt * 32 + r;
+  double f[KT], fb[KT];
+#pragma unroll
+  for (int k = 0; k < KT; k++) {
+    f[k] = j < m ? Fd[j * KT + k] : 0.5;
+    fb[k] = 1.0 - f[k];
+  }
+  double ll = 0.0;
+  int cnt = 0, het = 0;
+  for (int64_t q = 0; q < Qb; q++) {
+    __syncthreads();
+    admix_stage<KT>(stage, Qd, q, n, 0.0);
+    __syncthreads();
+    const int64_t at = ((lt * Qb + q) * 64 + lane) * 4 + w;
+    const uint32_t wf = Lf[at], wt = Lt[at];
+    // held out: typed in full (not both bits set) and missing in train (both bits set)
+    uint32_t ho = ~(wf & (wf >> 1)) & (wt & (wt >> 1)) & 0x55555555u;
+    if (ho == 0) continue;
+    // the lane's own held-out entries, bit e = entry e: walked in ascending order, as the likelihood pass adds them; a wave makes
+    // as many trips as its fullest lane holds entries, not 16 with a share 1 / folds of its lanes active
+    uint32_t mine = 0;
+#pragma unroll
+    for (int e = 0; e < 16; e++) mine |= ((ho >> (8 * (e & 3) + 2 * (e >> 2))) & 1u) << e;
+    while (mine) {
+      const int e = __ffs(mine) - 1;
+      mine &= mine - 1;
+      const int g = admix_code(wf, e);
+      const double* __restrict__ qs = stage + (32 * w + 16 * h + e) * KT;
+      double p = 0.0, pb = 0.0;
+#pragma unroll
+      for (int k = 0; k < KT; k++) {
+        p = fma(qs[k], f[k], p);
+        pb = fma(qs[k], fb[k], pb);
+      }
+      cnt++;
+      het += g == 1;
+      ll += log(g == 0 ? pb * pb : g == 1 ? p * pb : p * p);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    ll += __shfl_xor(ll, o);
+    cnt += __shfl_xor(cnt, o);
+    het += __shfl_xor(het, o);
+  }
+  if (lane == 0) {
+    wll[w] = ll;
+    if (cnt) atomicAdd(d_cnt, (unsigned long long)cnt);
+    if (het) atomicAdd(d_cnt + 1, (unsigned long long)het);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) ll_part[lt] = ((wll[0] + wll[1]) + wll[2]) + wll[3];
+}
+
+int admix_check_folds(int folds) {
+  TPG_REQUIRE(folds >= 2 && folds <= TPG_ADMIX_MAX_FOLDS, TPG_EINVAL, "folds = %d out of [2, %d]", folds, TPG_ADMIX_MAX_FOLDS);
+  return TPG_OK;
+}
+
+// train_f of `full` (the caller holds the context)
+int admix_view_holdout(tpg_ctx* ctx, const tpg_view* full, int folds, int fold, uint64_t cv_seed, tpg_view** out, int64_t* n_held) {
+  TPG_TRY(admix_check_folds(folds));
+  TPG_REQUIRE(fold >= 0 && fold < folds, TPG_EINVAL, "fold = %d out of [0, %d)", fold, folds);
+  TPG_REQUIRE(full->L, TPG_EINVAL, "the view has no locus-tiled layout");
+  const int64_t n_lt = 4 * full->KG;
+  TPG_REQUIRE(ceil_div(n_lt, 4) <= 0x7FFFFFFF, TPG_EUNSUPPORTED, "a hold-out view of %lld loci", (long long)full->m);
+  ViewPtr v(new tpg_view(ctx, full->n, full->m));
+  DevBuf d_held;
+  TPG_HIP(tpg_pmalloc((void**)&v->L, v->bytes_each));
+  TPG_TRY(d_held.alloc(8));
+  TPG_HIP(hipMemsetAsync(d_held.p, 0, 8, ctx->stream));
+  TPG_LAUNCH(ctx, "admix_holdout_view", admix_holdout_view_kernel, dim3((unsigned)ceil_div(n_lt, 4)), dim3(256), 0,
+             (const uint4*)full->L, v->L, n_lt, full->Q, folds, fold, cv_seed, d_held.as<unsigned long long>());
+  TPG_CHECK_LAUNCH();
+  if (n_held) {
+    unsigned long long hh = 0;
+    TPG_HIP(tpg_fetch_small(ctx, &hh, d_held.p, sizeof hh));
+    *n_held = (int64_t)hh;
+  }
+  *out = v.release();
+  return TPG_OK;
+}
+
+}  // namespace
+
+extern "C" int tpg_view_holdout(tpg_ctx* ctx, const tpg_view* full, int folds, int fold, uint64_t cv_seed, tpg_view** out,
+                                int64_t* n_held) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && full && out, TPG_EINVAL, "null argument");
+  return admix_view_holdout(ctx, full, folds, fold, cv_seed, out, n_held);
+}
+
+extern "C" int tpg_admix_holdout_sums(tpg_ctx* ctx, const tpg_view* full, const tpg_view* train, int K, const double* Q,
+                                      const double* P, double* ll, int64_t* n_held, int64_t* n_het) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && full && train && Q && P, TPG_EINVAL, "null argument");
+  TPG_TRY(admix_check_view(full, K));
+  TPG_REQUIRE(full->n == train->n && full->m == train->m, TPG_EINVAL, "the full view is %lld x %lld, the training view %lld x %lld",
+              (long long)full->n, (long long)full->m, (long long)train->n, (long long)train->m);
+  TPG_REQUIRE(full->L && train->L, TPG_EINVAL, "a view has no locus-tiled layout");
+  const int64_t n = full->n, m = full->m;
+  AdmixRun run;
+  TPG_TRY(run.init(ctx, full, K, false, false, 1));
+  unsigned long long* d_cnt = nullptr;
+  TPG_TRY(run.sc.get(&d_cnt, (size_t)2));
+  TPG_HIP(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  InBuf iq, ip;
+  TPG_TRY(iq.init(ctx, Q, sizeof(double) * (size_t)n * K));
+  TPG_TRY(ip.init(ctx, P, sizeof(double) * (size_t)m * K));
+  TPG_LAUNCH(ctx, "admix_start", admix_load_q_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, iq.dev<double>(), run.Q[0], n, K,
+             run.KT, false, run.flag);
+  TPG_LAUNCH(ctx, "admix_start", admix_load_f_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ip.dev<double>(), run.F[0], m, K,
+             run.KT, false, run.flag);
+#define ADM_H(KT_)                                                                                                                 \
+  TPG_LAUNCH(ctx, "admix_holdout_sweep", admix_holdout_sweep_kernel<KT_>, dim3((unsigned)run.n_lt), dim3(256), 0,                  \
+             (const uint32_t*)full->L, (const uint32_t*)train->L, full->Q, n, m, (const double*)run.Q[0], (const double*)run.F[0], \
+             run.ll_part, d_cnt)
+  ADM_DISPATCH(run.KT, ADM_H);
+#undef ADM_H
+  TPG_LAUNCH(ctx, "admix_ll_sum", admix_ll_sum_kernel, dim3(1), dim3(256), 0, (const double*)run.ll_part, run.n_lt, run.trace);
+  TPG_CHECK_LAUNCH();
+  double l = 0.0;
+  unsigned long long c[2] = {0, 0};
+  TPG_HIP(tpg_fetch_small(ctx, &l, run.trace, sizeof l));
+  TPG_HIP(tpg_fetch_small(ctx, c, d_cnt, sizeof c));
+  if (ll) *ll = l;
+  if (n_held) *n_held = (int64_t)c[0];
+  if (n_het) *n_het = (int64_t)c[1];
+  return TPG_OK;
+}
+
+extern "C" int tpg_admix_cv_error(int folds, const double* fold_ll, const int64_t* fold_count, const int64_t* fold_het, double* fold_dev,
+                                  double* cv_error) {
+  TPG_REQUIRE(fold_ll && fold_count && fold_het && cv_error, TPG_EINVAL, "null argument");
+  TPG_TRY(admix_check_folds(folds));
+  double dev[TPG_ADMIX_MAX_FOLDS], sum = 0.0;
+  int64_t total = 0;
+  for (int f = 0; f < folds; f++) {
+    TPG_REQUIRE(fold_count[f] >= 0 && fold_het[f] >= 0 && fold_het[f] <= fold_count[f], TPG_EINVAL,
+                "fold %d: %lld held-out entries, %lld of them heterozygous", f, (long long)fold_count[f], (long long)fold_het[f]);
+    // -2 ln(p^g pbar^(2 - g)) - [g = 1] 4 ln 2: two products, then one subtraction (this file is compiled without contraction)
+    const double a = -2.0 * fold_ll[f], b = 2.772588722239781 * (double)fold_het[f];
+    dev[f] = a - b;
+    sum = f == 0 ? dev[0] : sum + dev[f];
+    total += fold_count[f];
+  }
+  TPG_REQUIRE(total > 0, TPG_EINVAL, "no held-out entry in any fold");
+  if (fold_dev)
+    for (int f = 0; f < folds; f++) fold_dev[f] = dev[f];
+  *cv_error = sum / (double)total;
+  return TPG_OK;
+}
+
+extern "C" int tpg_admix_cv(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, const tpg_admix_params* params, int folds,
+                            uint64_t cv_seed, const double* q0, const double* f0, double* cv_error, double* fold_ll,
+                            int64_t* fold_count, int64_t* fold_het, int32_t* fold_iter, int32_t* fold_converged) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && v && cv_error, TPG_EINVAL, "null argument");
+  TPG_TRY(admix_check_folds(folds));
+  TPG_TRY(admix_check_view(v, K));
+  const int64_t n = v->n, m = v->m;
+  // the start goes to the device once; every fold's EM reads it there, and its Q and P stay there for the hold-out sums
+  InBuf iq, ifr;
+  if (q0) TPG_TRY(iq.init(ctx, q0, sizeof(double) * (size_t)n * K));
+  if (f0) TPG_TRY(ifr.init(ctx, f0, sizeof(double) * (size_t)m * K));
+  DevBuf Qd, Pd;
+  TPG_TRY(Qd.alloc_n<double>((size_t)n * K));
+  TPG_TRY(Pd.alloc_n<double>((size_t)m * K));
+  double ll[TPG_ADMIX_MAX_FOLDS], cv = 0.0;
+  int64_t cnt[TPG_ADMIX_MAX_FOLDS], het[TPG_ADMIX_MAX_FOLDS];
+  int32_t it[TPG_ADMIX_MAX_FOLDS], conv[TPG_ADMIX_MAX_FOLDS];
+  for (int f = 0; f < folds; f++) {
+    tpg_view* t = nullptr;
+    TPG_TRY(admix_view_holdout(ctx, v, folds, f, cv_seed, &t, nullptr));
+    ViewPtr train(t);  // back to the pool before the next fold's is made: one extra view (L and T) at a time
+    TPG_TRY(tpg_admix_em(ctx, t, ploidy, K, params, q0 ? iq.dev<double>() : nullptr, f0 ? ifr.dev<double>() : nullptr, Qd.as<double>(),
+                         Pd.as<double>(), nullptr, nullptr, &it[f], &conv[f]));
+    TPG_TRY(tpg_admix_holdout_sums(ctx, v, t, K, Qd.as<double>(), Pd.as<double>(), &ll[f], &cnt[f], &het[f]));
+  }
+  TPG_TRY(tpg_admix_cv_error(folds, ll, cnt, het, nullptr, &cv));
+  // nothing of the caller's has been written so far
+  *cv_error = cv;
+  for (int f = 0; f < folds; f++) {
+    if (fold_ll) fold_ll[f] = ll[f];
+    if (fold_count) fold_count[f] = cnt[f];
+    if (fold_het) fold_het[f] = het[f];
+    if (fold_iter) fold_iter[f] = it[f];
+    if (fold_converged) fold_converged[f] = conv[f];
+  }
+  return TPG_OK;
+}
