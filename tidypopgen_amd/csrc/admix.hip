@@ -318,6 +318,7 @@ struct AdmixRun {
   int init(tpg_ctx* c, const tpg_view* view, int k, bool need_q_sweep, bool need_f_next, int64_t trace_len) {
     ctx = c; v = view; K = k; KT = admix_kt(k);
     n = v->n; m = v->m;
+    TPG_TRY(tpg_view_need_L(ctx, v));  // every sweep over the loci reads it
     n_lt = ceil_div(m, 32); n_rt = ceil_div(n, 32); nchunks = ceil_div(m, ADM_CHUNK);
     TPG_REQUIRE(n_lt <= 0x7FFFFFFF && n_rt <= 0x7FFFFFFF && nchunks <= 65535, TPG_EUNSUPPORTED, "admixture on a view of %lld x %lld",
                 (long long)n, (long long)m);
@@ -611,7 +612,7 @@ int admix_check_folds(int folds) {
 int admix_view_holdout(tpg_ctx* ctx, const tpg_view* full, int folds, int fold, uint64_t cv_seed, tpg_view** out, int64_t* n_held) {
   TPG_TRY(admix_check_folds(folds));
   TPG_REQUIRE(fold >= 0 && fold < folds, TPG_EINVAL, "fold = %d out of [0, %d)", fold, folds);
-  TPG_REQUIRE(full->L, TPG_EINVAL, "the view has no locus-tiled layout");
+  TPG_TRY(tpg_view_need_L(ctx, full));
   const int64_t n_lt = 4 * full->KG;
   TPG_REQUIRE(ceil_div(n_lt, 4) <= 0x7FFFFFFF, TPG_EUNSUPPORTED, "a hold-out view of %lld loci", (long long)full->m);
   ViewPtr v(new tpg_view(ctx, full->n, full->m));
@@ -647,7 +648,8 @@ extern "C" int tpg_admix_holdout_sums(tpg_ctx* ctx, const tpg_view* full, const 
   TPG_TRY(admix_check_view(full, K));
   TPG_REQUIRE(full->n == train->n && full->m == train->m, TPG_EINVAL, "the full view is %lld x %lld, the training view %lld x %lld",
               (long long)full->n, (long long)full->m, (long long)train->n, (long long)train->m);
-  TPG_REQUIRE(full->L && train->L, TPG_EINVAL, "a view has no locus-tiled layout");
+  TPG_TRY(tpg_view_need_L(ctx, full));
+  TPG_TRY(tpg_view_need_L(ctx, train));
   const int64_t n = full->n, m = full->m;
   AdmixRun run;
   TPG_TRY(run.init(ctx, full, K, false, false, 1));

@@ -55,7 +55,7 @@ __global__ void asv_gather_kernel(const uint4* __restrict__ L, uint4* __restrict
 
 // d_idx: device, every entry already known to lie in [0, v->m)
 int select_loci_device(tpg_ctx* ctx, const tpg_view* v, const int64_t* d_idx, int64_t count, tpg_view** out) {
-  TPG_REQUIRE(v->L, TPG_EINVAL, "the view has no locus-tiled layout");
+  TPG_TRY(tpg_view_need_L(ctx, v));
   ViewPtr w(new tpg_view(ctx, v->n, count));
   TPG_HIP(tpg_pmalloc((void**)&w->L, w->bytes_each));
   const int64_t total = (int64_t)(w->bytes_each / 16);

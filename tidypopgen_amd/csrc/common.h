@@ -199,14 +199,19 @@ struct DevArena {
   }
 };
 
-// A view owns its layouts: the destructor returns T, L, T4, lc_part and the cached counts to the pool.
+// A view owns its layouts: the destructor returns T, L, LM, T4, lc_part and the cached counts to the pool.
 struct tpg_view {
   tpg_ctx* ctx;
   int64_t n, m;    // kept individuals / loci
   int64_t Q, KG;   // ceil(n/128), ceil(m/128)
   mutable uint4* T = nullptr;  // (4Q) row tiles x KG blocks; NULL in the views of tpg_view_create_pair until somebody needs it
                                // (tpg_view_need_T builds it from L)
-  uint4* L;        // (4KG) locus tiles x Q blocks
+  mutable uint4* L;  // (4KG) locus tiles x Q blocks; NULL in a view that holds LM instead until somebody needs it
+                     // (tpg_view_need_L builds it from LM)
+  // L's 16-byte pieces LOCUS-MAJOR (devfrag.h: tpg_lm_piece), bytes_each like L: what the class Gram's gather and the loadings of
+  // the PCA read.  The fast pack kernel writes it INSTEAD of L for the second (imputed) view of tpg_view_create_pair; a
+  // view without it that goes to the class Gram is copied into a scratch LM per call (gramcls.hip: tpg_gcls_l2lm_kernel)
+  mutable uint4* LM = nullptr;
   bool L_borrowed = false;  // L points into somebody else's block (stream.hip: the kept views' layouts end to end): not freed here
   size_t bytes_each;
   // T re-coded as FP4 (E2M1) operand nibbles for the pairwise kernel (pairwise.hip); written by the pack kernel for
@@ -231,7 +236,8 @@ struct tpg_view {
   tpg_view(const tpg_view&) = delete;
   tpg_view& operator=(const tpg_view&) = delete;
   ~tpg_view();          // runtime.hip
-  void drop_derived();  // release everything that can be rebuilt from L: T, T4, lc_part and the cached counts
+  // release everything that can be rebuilt: T, T4, lc_part, the cached counts, and LM where the view holds L as well
+  void drop_derived();
 };
 typedef std::unique_ptr<tpg_view> ViewPtr;
 
@@ -405,6 +411,8 @@ int tpg_launch_pack(tpg_ctx* ctx, const tpg_fbm* fbm, const int32_t* d_rows, con
 int tpg_launch_unpack(tpg_ctx* ctx, const tpg_view* v, uint8_t* d_codes, int from_L);
 // the T layout of a view that was packed without it (from L; a no-op when it is there)
 int tpg_view_need_T(tpg_ctx* ctx, const tpg_view* v);
+// the L layout of a view that was packed locus-major (from LM; a no-op when it is there): every reader of v->L calls it first
+int tpg_view_need_L(tpg_ctx* ctx, const tpg_view* v);
 // impute.hip: tpg_view_impute with the view's first locus at position col0 of the object being imputed (a streamed block)
 int tpg_view_impute_at(tpg_ctx* ctx, const tpg_view* raw, int method, uint64_t seed, int64_t col0, tpg_view** out,
                        tpg_impute_report* rep);

@@ -79,6 +79,26 @@ __device__ __forceinline__ void tpg_t4_words(uint32_t w, int64_t left, uint32_t&
 // bit position of element e (0..15) inside a packed dword
 __host__ __device__ __forceinline__ int tpg_elem_shift(int e) { return 8 * (e & 3) + 2 * (e >> 2); }
 
+// The LM ("locus-major") form of the L layout (common.h): the same 16-byte pieces -- lane (r, h) of block (lt, q) -- with the
+// 2 Q pieces of a locus next to each other, q-major then h.  Piece index of locus j = 32 lt + r:
+__host__ __device__ __forceinline__ int64_t tpg_lm_piece(int64_t j, int64_t Q, int64_t q, int h) { return (j * Q + q) * 2 + h; }
+// One task of the streaming transposition between the two: a workgroup of 256 threads takes the blocks (lt, q0 .. q0 + 3) of
+// L, 4 KiB, through uint4 sh[32][8] = [locus in tile][2 (q - q0) + h].  On the L side thread t holds lane t & 63 of block
+// q0 + (t >> 6): 1 KiB contiguous per wave; on the LM side piece p = t & 7 of locus r = t >> 3: 128 contiguous bytes per locus.
+// Chunks q >= Q do not exist on either side (on = false).
+struct TpgLmSide {
+  int64_t piece;  // uint4 index in the layout
+  int row, col;   // in sh
+  bool on;
+};
+__device__ __forceinline__ int64_t tpg_lm_tasks(int64_t n_lt, int64_t Q) { return n_lt * ((Q + 3) / 4); }
+__device__ __forceinline__ void tpg_lm_task(int64_t task, int64_t Q, int tid, TpgLmSide& l, TpgLmSide& lm) {
+  const int64_t QG = (Q + 3) / 4, lt = task / QG, q0 = (task % QG) * 4;
+  const int lane = tid & 63, wv = tid >> 6, r = tid >> 3, p = tid & 7;
+  l = TpgLmSide{(lt * Q + q0 + wv) * 64 + lane, lane & 31, 2 * wv + (lane >> 5), q0 + wv < Q};
+  lm = TpgLmSide{tpg_lm_piece(lt * 32 + r, Q, q0, 0) + p, r, p, q0 + (p >> 1) < Q};
+}
+
 // MFMA 32x32 C/D register -> row inside the 32x32 tile (col = lane & 31)
 __device__ __forceinline__ int tpg_cd_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 

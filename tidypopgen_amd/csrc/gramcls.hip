@@ -905,33 +905,36 @@ static int gram_classes_core(tpg_ctx* ctx, int64_t n, int64_t Q, int64_t m, cons
 // quarter of a 64-byte sector whose other three quarters belong to other loci (5 GB fetched for 1.25 GB used at
 // 5 000 x 1 000 000).  So the view is first copied LOCUS-MAJOR (LM: locus j = 2 Q consecutive pieces, q-major, then h) by a
 // streaming transpose -- a workgroup takes the blocks (lt, q0 .. q0 + 3), 4 KiB, and writes 128 contiguous bytes per
-// locus -- and the gather reads 32 contiguous bytes per (locus, q) whose sector neighbours are the next q of the same
+// locus (devfrag.h: tpg_lm_task) -- and the gather reads 32 contiguous bytes per (locus, q) whose sector neighbours are the next q of the same
 // locus, wanted by the next task: 0.5 + 0.7 ms instead of 2.1.
 __global__ __launch_bounds__(256) void tpg_gcls_l2lm_kernel(const uint4* __restrict__ L, int64_t Q, int64_t n_lt,
                                                             uint4* __restrict__ LM) {
   __shared__ uint4 sh[32][8];  // [locus in tile][2 (q - q0) + h]
-  const int64_t QG = (Q + 3) / 4;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int64_t task = blockIdx.x; task < n_lt * QG; task += gridDim.x) {
-    const int64_t lt = task / QG, q0 = (task % QG) * 4;
-    if (q0 + wv < Q) sh[lane & 31][2 * wv + (lane >> 5)] = L[(lt * Q + q0 + wv) * 64 + lane];
+  for (int64_t task = blockIdx.x; task < tpg_lm_tasks(n_lt, Q); task += gridDim.x) {
+    TpgLmSide l, lm;
+    tpg_lm_task(task, Q, (int)threadIdx.x, l, lm);  // (devfrag.h; pack.hip has the inverse, tpg_lm2l_kernel)
+    if (l.on) sh[l.row][l.col] = L[l.piece];
     __syncthreads();
-    const int r = threadIdx.x >> 3, p = threadIdx.x & 7;
-    if (q0 + (p >> 1) < Q) LM[((lt * 32 + r) * Q + q0) * 2 + p] = sh[r][p];
+    if (lm.on) LM[lm.piece] = sh[lm.row][lm.col];
     __syncthreads();
   }
 }
 
+// A view that was packed locus-major (the imputed view of tpg_view_create_pair) is the gather's source as it is; any other
+// view is copied first.
 int tpg_gram_classes(tpg_ctx* ctx, const tpg_view* v, const double* d_w, double* d_what, double* d_K, bool* done,
                      bool centred_ok) {
   *done = false;
   if (tpg_env_set("TPG_GRAM_DIGITS")) return TPG_OK;
   const int64_t n_lt = 4 * v->KG;
   DevBuf d_LM;
-  TPG_TRY(d_LM.alloc_n<uint4>((size_t)n_lt * 32 * (size_t)v->Q * 2));
-  TPG_LAUNCH(ctx, "gcls_l2lm", tpg_gcls_l2lm_kernel, dim3((unsigned)std::min<int64_t>(n_lt * ((v->Q + 3) / 4), (int64_t)ctx->num_cu * 32)),
-             dim3(256), 0, (const uint4*)v->L, v->Q, n_lt, d_LM.as<uint4>());
-  const GclsSrc src{d_LM.as<uint4>(), 0, 2 * v->Q, 0, 0, 2, 1};
+  if (!v->LM) {
+    TPG_TRY(tpg_view_need_L(ctx, v));
+    TPG_TRY(d_LM.alloc_n<uint4>((size_t)n_lt * 32 * (size_t)v->Q * 2));
+    TPG_LAUNCH(ctx, "gcls_l2lm", tpg_gcls_l2lm_kernel, dim3((unsigned)std::min<int64_t>(n_lt * ((v->Q + 3) / 4), (int64_t)ctx->num_cu * 32)),
+               dim3(256), 0, (const uint4*)v->L, v->Q, n_lt, d_LM.as<uint4>());
+  }
+  const GclsSrc src{v->LM ? v->LM : d_LM.as<uint4>(), 0, 2 * v->Q, 0, 0, 2, 1};
   const int rc = gram_classes_core(ctx, v->n, v->Q, v->m, src, d_w, d_what, d_K, false, done, centred_ok);
   d_LM.free();  // stream-ordered
   return rc;
@@ -1090,6 +1093,7 @@ int tpg_gram_classes_exchanged(tpg_ctx* ctx, tpg_comm* comm, const tpg_view* v, 
     TPG_HIP(hipMemcpyAsync(per_dest.data(), d_perdest, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
     TPG_HIP(hipStreamSynchronize(ctx->stream));
     TPG_TRY(B.get(&d_send, (size_t)std::max<int64_t>(m, 1) * (size_t)recq));
+    TPG_TRY(tpg_view_need_L(ctx, v));
     if (m > 0)
       TPG_LAUNCH(ctx, "gclx_pack", tpg_gclx_pack_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(m, 4), (int64_t)ctx->num_cu * 16)),
                  dim3(256), 0, (const uint4*)v->L, Q, (const uint32_t*)d_idx2, d_scale, m, d_send);

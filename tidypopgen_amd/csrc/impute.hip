@@ -366,7 +366,7 @@ int tpg_view_impute_at(tpg_ctx* ctx, const tpg_view* raw, int method, uint64_t s
                        tpg_impute_report* rep) {
   TPG_REQUIRE(ctx && raw && out, TPG_EINVAL, "null argument");
   TPG_TRY(check_method(method));
-  TPG_REQUIRE(raw->L, TPG_EINVAL, "the view has no locus-tiled layout");
+  TPG_TRY(tpg_view_need_L(ctx, raw));
   ViewPtr v(new tpg_view(ctx, raw->n, raw->m));
   DevBuf d_rep;
   TPG_HIP(tpg_pmalloc((void**)&v->L, v->bytes_each));

@@ -405,6 +405,7 @@ int ld_prepare(tpg_ctx* ctx, const tpg_view* v, const HostIn<int64_t>& h, DevAre
 int ld_launch_band(tpg_ctx* ctx, const tpg_view* v, double thr_r2, const LdBand& B, uint32_t* d_bits, int64_t stride,
                    uint32_t* d_back, int64_t bstride) {
   const int64_t m = v->m;
+  TPG_TRY(tpg_view_need_L(ctx, v));
   if (stride > 0) TPG_HIP(hipMemsetAsync(d_bits, 0, sizeof(uint32_t) * (size_t)m * (size_t)stride, ctx->stream));
   if (d_back) TPG_HIP(hipMemsetAsync(d_back, 0, sizeof(uint32_t) * (size_t)m * (size_t)bstride, ctx->stream));
   TPG_LAUNCH(ctx, "ld_band", tpg_ld_band_kernel, dim3((unsigned)ceil_div(m, 32)), dim3(256), 0, (const uint4*)v->L, v->Q, v->n,

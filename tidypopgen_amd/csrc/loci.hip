@@ -82,6 +82,7 @@ int tpg_launch_loci_counts(tpg_ctx* ctx, const tpg_view* v, int32_t* d_counts) {
     return TPG_OK;
   }
   const int64_t n_lt = v->KG * 4;
+  TPG_TRY(tpg_view_need_L(ctx, v));
   TPG_LAUNCH(ctx, "loci_counts", tpg_loci_counts_kernel, dim3((unsigned)ceil_div(n_lt, 4)), dim3(256), 0,
              (const uint4*)v->L, n_lt, v->Q, v->n, v->m, (int4*)d_counts);
   TPG_CHECK_LAUNCH();
@@ -224,6 +225,7 @@ int tpg_launch_indiv_accumulate(tpg_ctx* ctx, const tpg_view* v, int32_t* d_acc)
   const int64_t gy = ceil_div(n_lt, tiles);
   TPG_REQUIRE(gy <= 65535 && gx <= 0x7FFFFFFF, TPG_EUNSUPPORTED, "per-individual counts of a view of %lld x %lld", (long long)v->n,
               (long long)v->m);
+  TPG_TRY(tpg_view_need_L(ctx, v));
   TPG_LAUNCH(ctx, "indiv_accumulate", tpg_indiv_accumulate_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0,
              (const uint4*)v->L, n_lt, v->Q, v->n, v->m, (int)tiles, d_acc);
   TPG_CHECK_LAUNCH();
@@ -499,6 +501,7 @@ int tpg_grouped_counts(tpg_ctx* ctx, const tpg_view* v, const int32_t* h_cls, in
   TPG_TRY(sc.get(&d_cls, h_up.size()));
   TPG_TRY(sc.get(&d_oh, (size_t)v->Q * 2 * GT * 64));
   TPG_HIP(tpg_h2d_async(ctx, d_cls, h_up.data(), sizeof(int32_t) * h_up.size()));
+  TPG_TRY(tpg_view_need_L(ctx, v));
   TPG_LAUNCH(ctx, "onehot", tpg_onehot_kernel, dim3(1024), dim3(256), 0, d_cls, v->n, v->Q, GT, d_oh);
   const unsigned grid = (unsigned)ceil_div(n_lt, 4 * GC_NLT);
   int g0 = 0;

@@ -7,6 +7,7 @@
 // takes tpg_pack_fast_kernel below.  HBM-bound: reads n*m bytes, writes n*m/2 bytes.  Replaces the per-block
 // byte decode loops of the reference (src/snp_ibs.cpp:45-55, src/snp_king.cpp:45-58, src/snp_as.cpp:44-53 and
 // the SubBMCode256Acc accessor in src/alt_freq_dip_pseudo_cpp.cpp:15-16).
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -118,6 +119,12 @@ __global__ __launch_bounds__(256) void tpg_pack_kernel(const uint8_t* __restrict
 // T0 / T1 may be NULL (the view gets no T layout: tpg_view_need_T makes it from L if it is ever wanted); T4 (may be
 // NULL) = the FP4 operand layout of view 0 for the pairwise kernel (pairwise.hip), written instead of being expanded
 // from T later: every T word goes out as the two T4 words of the same lane.
+// LM1 (NV = 2): L1 is view 1's LM buffer -- its L words go out locus-major (devfrag.h: tpg_lm_piece), the same 16-byte pieces
+// with the 2 Q of a locus next to each other, which is the order both readers of the PCA's imputed view want (the class
+// Gram's gather, the loadings).  The eight threads of a locus hold 32 contiguous bytes per chunk; written chunk by chunk as
+// dwords that is eight half-sector runs per wave store against the two 128-byte runs of an L store (2.24 against 2.03 ms for
+// the bench's pair).  So the words of the workgroup's first chunk wait for the second: threads s and s ^ 1 of a piece trade
+// one word, and every thread stores 8 bytes -- 64 contiguous bytes per locus and store, eight loci per wave.
 #ifndef PACK_NSUB
 #define PACK_NSUB 2  // individual chunks per workgroup, all their loads issued up front
 #endif
@@ -133,7 +140,7 @@ typedef pk_u4 pk_u4a8 __attribute__((aligned(8)));
 // bytes, and one v_perm_b32 with the four composed entries table[bigsnpr's byte of .bed code b] turns them into codes.  The
 // generic kernel did this route until now: two passes + a T -> T4 expansion + the counts kernel over L, 5.5 ms more per step
 // at 5 000 x 1 000 000 than the byte FBM.
-template <int NV, bool BED = false>
+template <int NV, bool BED = false, bool LM1 = false>
 __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __restrict__ fbm, int64_t nrow,
                                                             const int32_t* __restrict__ cols, uint8_t* lut_and_flag,
                                                             int64_t n, int64_t m, int64_t Q, int64_t KG,
@@ -141,6 +148,7 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
                                                             uint32_t* __restrict__ T1, uint32_t* __restrict__ L1,
                                                             uint32_t* __restrict__ T4, int xcd_map,
                                                             uint32_t* __restrict__ P0, uint32_t* __restrict__ P1) {
+  static_assert(!LM1 || NV == 2, "the second view of a pair");
   // dynamic: the tables + one TILE x TILE array of code bytes per view that gets a T or T4 layout (tpg_pack_lds_bytes).  A view
   // with L only -- the imputed view of the bench's pair -- needs no pass through LDS at all, and with 17 instead of 33 KiB a CU
   // holds six workgroups instead of four: the kernel is bound by the bytes it has in flight, not by HBM or the VALU
@@ -262,6 +270,8 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
 #pragma unroll
     for (int it = 0; it < 4; it++) cnt3[vw][it] = 0;
   const bool cnt_on = P0 != nullptr;
+  static_assert(!LM1 || NSUB == 2, "the locus-major store pairs the two chunks of a workgroup");
+  uint32_t lmw[4] = {0, 0, 0, 0};  // LM1: view 1's L words of chunk bi0, kept for the store with chunk bi0 + 1
 #pragma unroll
   for (int sub = 0; sub < NSUB; sub++) {
   const int64_t bi = bi0 + sub;
@@ -277,6 +287,10 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
     const uint32_t rot0 = (uint32_t)(16 * c16 + 32 * (l0 >> 4)) & 127u;
     const uint32_t cb[2] = {(uint32_t)l0 * TILE + rot0, (uint32_t)l0 * TILE + (rot0 ^ 64u)};  // `codes` offset of it even / odd
     const uint32_t loff = (uint32_t)(l0 + 32 * (c16 & 1)) * 16u + (uint32_t)(c16 >> 1) * 4u;  // inside a 1-KiB L block
+    // locus-major: behind piece (128 bj + 32 it, bi, 0) -- l0 loci of 2 Q pieces further, piece h = c16 & 1, dword s = c16 >> 1
+    const uint32_t loff_lm = (uint32_t)tpg_lm_piece(l0, Q, 0, c16 & 1) * 16u + (uint32_t)(c16 >> 1) * 4u;
+    // ... and of the 8 bytes this thread stores for a PAIR of chunks: dwords (s & 2, s | 1) of piece h, chunk bi0 + (s & 1)
+    const uint32_t loff_lm2 = (uint32_t)tpg_lm_piece(l0, Q, (c16 >> 1) & 1, c16 & 1) * 16u + (uint32_t)(c16 >> 2) * 8u;
     typedef __attribute__((address_space(1))) char gchar;
     typedef __attribute__((address_space(1))) uint32_t gu32;
 #pragma unroll
@@ -319,9 +333,23 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
           if (inside && i0 + 16 <= n) { c[2] = conv(vb[sub][it].x, vw); c[3] = conv(vb[sub][it].y, vw); }
         }
         if (need_[vw]) *reinterpret_cast<uint4*>(codes + cb[it & 1] + it * 32 * TILE) = make_uint4(c[0], c[1], c[2], c[3]);
-        gchar* Lb = (gchar*)tpg_pack_uniform64((int64_t)((vw ? L1 : L0) + ((bj * 4 + it) * Q + bi) * 256));  // L block (lt = 4 bj + it, bi)
+        const bool lm = LM1 && vw == 1;
+        gchar* Lb = (gchar*)tpg_pack_uniform64((int64_t)(
+            lm ? L1 + tpg_lm_piece(bj * TILE + 32 * it, Q, bi, 0) * 4 : (vw ? L1 : L0) + ((bj * 4 + it) * Q + bi) * 256));  // L block (lt = 4 bj + it, bi)
         const uint32_t lw = c[0] | (c[1] << 2) | (c[2] << 4) | (c[3] << 6);
-        *(gu32*)(Lb + loff) = lw;
+        if (lm && sub == 0 && bi + 1 < Q) {
+          lmw[it] = lw;
+        } else if (lm && sub == 1) {
+          // s even: {own word of chunk bi0, the partner's (s + 1)}; s odd: {the partner's (s - 1) of chunk bi0 + 1, own}
+          typedef uint32_t pk_u2 __attribute__((ext_vector_type(2)));
+          typedef __attribute__((address_space(1))) pk_u2 gu2;
+          const bool odd = (c16 >> 1) & 1;
+          const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(odd ? lmw[it] : lw), 0x4E /* quad_perm [2, 3, 0, 1] */, 0xF, 0xF, true);
+          gchar* Lp = (gchar*)tpg_pack_uniform64((int64_t)(L1 + tpg_lm_piece(bj * TILE + 32 * it, Q, bi0, 0) * 4));
+          *(gu2*)(Lp + loff_lm2) = odd ? pk_u2{got, lw} : pk_u2{lmw[it], got};
+        } else {
+          *(gu32*)(Lb + (lm ? loff_lm : loff)) = lw;  // (locus-major: the last chunk of an odd Q)
+        }
         if (cnt_on) {  // (the padding code 3 of individuals past n, loci past m, is not a genotype: masked out)
           uint32_t wc = lw;
           if constexpr (!FULL && BED) {  // individual i0 + 4 k + b sits at bits 8 b + 2 k of the L word
@@ -467,30 +495,39 @@ int tpg_launch_pack(tpg_ctx* ctx, const tpg_fbm* fbm, const int32_t* d_rows, con
     if (!lp0)
       for (tpg_view* w : {v, v2})
         if (w && w->lc_part) { tpg_pfree(w->lc_part); w->lc_part = nullptr; w->lc_chunks = 0; }
+    const bool lm1 = v2 && v2->LM && !v2->L;  // the second view of a pair holds LM instead of L (tpg_view_create_pair)
+    TPG_REQUIRE(v->L && (!v2 || v2->L || v2->LM), TPG_EINVAL, "a view has no buffer for its locus-tiled layout");
     auto lds_bytes = [&](int nv, bool t_a, bool t_b) { return (size_t)nv * (256 + 16) + (size_t)((t_a ? 1 : 0) + (t_b ? 1 : 0)) * TILE * TILE; };
-    if (v2 && fast_bed)
-      TPG_LAUNCH(ctx, "pack2", (tpg_pack_fast_kernel<2, true>), g1, dim3(256), lds_bytes(2, v->T || v->T4, v2->T != nullptr), fbm->d_bytes, fbm->bed_bpl, d_cols, (uint8_t*)d_lut,
-                 v->n, v->m, v->Q, v->KG, (uint32_t*)v->T, (uint32_t*)v->L, (uint32_t*)v2->T, (uint32_t*)v2->L,
-                 (uint32_t*)v->T4, xmap, lp0, lp1);
+#define PACK2_GO(BED_, LM_, NROW_)                                                                                                   \
+  TPG_LAUNCH(ctx, "pack2", (tpg_pack_fast_kernel<2, BED_, LM_>), g1, dim3(256), lds_bytes(2, v->T || v->T4, v2->T != nullptr),       \
+             fbm->d_bytes, NROW_, d_cols, (uint8_t*)d_lut, v->n, v->m, v->Q, v->KG, (uint32_t*)v->T, (uint32_t*)v->L,                \
+             (uint32_t*)v2->T, (uint32_t*)(LM_ ? v2->LM : v2->L), (uint32_t*)v->T4, xmap, lp0, lp1)
+    if (v2 && fast_bed) {
+      if (lm1) PACK2_GO(true, true, fbm->bed_bpl);
+      else PACK2_GO(true, false, fbm->bed_bpl);
+    }
     else if (fast_bed)
       TPG_LAUNCH(ctx, "pack", (tpg_pack_fast_kernel<1, true>), g1, dim3(256), lds_bytes(1, v->T || v->T4, false), fbm->d_bytes, fbm->bed_bpl, d_cols, (uint8_t*)d_lut,
                  v->n, v->m, v->Q, v->KG, (uint32_t*)v->T, (uint32_t*)v->L, (uint32_t*)nullptr, (uint32_t*)nullptr,
                  (uint32_t*)v->T4, xmap, lp0, lp1);
-    else if (v2)
-      TPG_LAUNCH(ctx, "pack2", tpg_pack_fast_kernel<2>, g1, dim3(256), lds_bytes(2, v->T || v->T4, v2->T != nullptr), fbm->d_bytes, fbm->nrow, d_cols, (uint8_t*)d_lut,
-                 v->n, v->m, v->Q, v->KG, (uint32_t*)v->T, (uint32_t*)v->L, (uint32_t*)v2->T, (uint32_t*)v2->L,
-                 (uint32_t*)v->T4, xmap, lp0, lp1);
+    else if (v2) {
+      if (lm1) PACK2_GO(false, true, fbm->nrow);
+      else PACK2_GO(false, false, fbm->nrow);
+    }
     else
       TPG_LAUNCH(ctx, "pack", tpg_pack_fast_kernel<1>, g1, dim3(256), lds_bytes(1, v->T || v->T4, false), fbm->d_bytes, fbm->nrow, d_cols, (uint8_t*)d_lut,
                  v->n, v->m, v->Q, v->KG, (uint32_t*)v->T, (uint32_t*)v->L, (uint32_t*)nullptr, (uint32_t*)nullptr,
                  (uint32_t*)v->T4, xmap, lp0, lp1);
+#undef PACK2_GO
     TPG_CHECK_LAUNCH();
     return TPG_OK;
   }
-  // the generic kernel writes T and L only: a view created without T gets it here, and a T4 it was given is dropped
-  // (tpg_pairwise_accumulate makes it from T when it is needed)
+  // the generic kernel writes T and L only: a view created without T gets it here, a view created with LM for L gets L, and
+  // a T4 it was given is dropped (tpg_pairwise_accumulate makes it from T when it is needed)
   for (tpg_view* w : {v, v2}) {
     if (!w) continue;
+    if (!w->L) TPG_HIP(tpg_pmalloc((void**)&w->L, w->bytes_each));
+    if (w->LM) { tpg_pfree(w->LM); w->LM = nullptr; }
     if (!w->T) TPG_HIP(tpg_pmalloc((void**)&w->T, w->bytes_each));
     if (w->T4) { tpg_pfree(w->T4); w->T4 = nullptr; }
   }
@@ -560,8 +597,36 @@ __global__ __launch_bounds__(256) void tpg_l2t_kernel(const uint32_t* __restrict
   }
 }
 
+// L from LM: tpg_gcls_l2lm_kernel (gramcls.hip) backwards, the same tasks through the same LDS tile (devfrag.h: tpg_lm_task).
+// Only runs for the imputed view of a pair that is handed to something other than the PCA's class Gram and loadings.
+__global__ __launch_bounds__(256) void tpg_lm2l_kernel(const uint4* __restrict__ LM, int64_t Q, int64_t n_lt, uint4* __restrict__ L) {
+  __shared__ uint4 sh[32][8];  // [locus in tile][2 (q - q0) + h]
+  for (int64_t task = blockIdx.x; task < tpg_lm_tasks(n_lt, Q); task += gridDim.x) {
+    TpgLmSide l, lm;
+    tpg_lm_task(task, Q, (int)threadIdx.x, l, lm);
+    if (lm.on) sh[lm.row][lm.col] = LM[lm.piece];
+    __syncthreads();
+    if (l.on) L[l.piece] = sh[l.row][l.col];
+    __syncthreads();
+  }
+}
+
+int tpg_view_need_L(tpg_ctx* ctx, const tpg_view* v) {
+  if (v->L) return TPG_OK;
+  TPG_REQUIRE(v->LM, TPG_EINVAL, "the view has no locus-tiled layout");
+  const int64_t n_lt = 4 * v->KG;
+  uint4* l = nullptr;
+  TPG_HIP(tpg_pmalloc((void**)&l, v->bytes_each));
+  TPG_LAUNCH(ctx, "lm2l", tpg_lm2l_kernel, dim3((unsigned)std::min<int64_t>(n_lt * ((v->Q + 3) / 4), (int64_t)ctx->num_cu * 32)), dim3(256),
+             0, (const uint4*)v->LM, v->Q, n_lt, l);
+  v->L = l;  // (kept: the view owns both from now on)
+  TPG_CHECK_LAUNCH();
+  return TPG_OK;
+}
+
 int tpg_view_need_T(tpg_ctx* ctx, const tpg_view* v) {
   if (v->T) return TPG_OK;
+  TPG_TRY(tpg_view_need_L(ctx, v));
   TPG_REQUIRE(v->KG < 2147483647ll && v->Q <= 65535, TPG_EINVAL, "view too large for the pack grid");
   uint4* t = nullptr;
   TPG_HIP(tpg_pmalloc((void**)&t, v->bytes_each));
@@ -574,6 +639,7 @@ int tpg_view_need_T(tpg_ctx* ctx, const tpg_view* v) {
 
 int tpg_launch_unpack(tpg_ctx* ctx, const tpg_view* v, uint8_t* d_codes, int from_L) {
   if (!from_L) TPG_TRY(tpg_view_need_T(ctx, v));
+  else TPG_TRY(tpg_view_need_L(ctx, v));
   TPG_LAUNCH(ctx, "unpack", tpg_unpack_kernel, dim3(2048), dim3(256), 0, (const uint32_t*)v->T,
              (const uint32_t*)v->L, from_L, v->n, v->m, v->Q, v->KG, d_codes);
   TPG_CHECK_LAUNCH();

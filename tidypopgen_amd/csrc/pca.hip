@@ -290,6 +290,7 @@ static int run_sweep(tpg_ctx* ctx, int mode, const uint4* P, int64_t nrowtiles, 
 // common.h: the FP64 row-scaled sweep over the L layout for other translation units (pcadapt.hip)
 int tpg_sweep_loci_rowscale(tpg_ctx* ctx, const tpg_view* v, const double* d_center, const double* d_inv_scale, const double* d_U,
                             int K, double* d_out) {
+  TPG_TRY(tpg_view_need_L(ctx, v));
   return run_sweep(ctx, SW_ROWSCALE, v->L, v->KG * 4, v->Q, v->m, v->n, d_center, d_inv_scale, d_U, v->n, K, d_out, nullptr, nullptr);
 }
 
@@ -1706,6 +1707,12 @@ __global__ __launch_bounds__(256) void tpg_uq_colsum_kernel(const double* __rest
 // tile per wave and a fragment per MFMA straight from L2 the kernel moved 20 GB per launch at C5 through the L1s
 // and was bound by that (1.6 ms).  The A side is the code bytes themselves (no missing values here, see the Gram
 // kernel).
+// LMV: the genotypes come from the view's LM layout (common.h), where the 16-byte piece of lane (r, h) and chunk q sits at
+// tpg_lm_piece(32 lt + r, Q, q, h).  Fetched as the operand wants it -- lane (r, h) its own piece -- every quarter of a
+// wave's load touches 16 cache lines for 16 bytes each (0.69 ms against 0.56 from L).  So a tile's chunks are fetched in
+// PAIRS by two loads in which four neighbouring lanes take the 64 contiguous bytes (chunk q0 | q0 + 1, h) of one locus --
+// load X the loci 16 X .. 16 X + 15 -- and the pieces change lanes in registers: a v_cndmask_b32 puts the pieces of ONE chunk
+// of both loads into one register (load 1's through a quad permutation), a ds_bpermute_b32 hands them to their lanes.
 #ifndef LD_NLT
 #define LD_NLT 2
 #endif
@@ -1725,7 +1732,7 @@ __device__ __forceinline__ void tpg_pca_static_for(F&& f) {
   }
 }
 
-template <int CTP>
+template <int CTP, bool LMV>
 __global__ __launch_bounds__(256, LD_WGS) void tpg_loadings_mfma_kernel(const uint4* __restrict__ L,
                                                                    const uint4* __restrict__ UD, int64_t n_lt,
                                                                    int64_t Q, int ct0, int CT,
@@ -1751,17 +1758,34 @@ __global__ __launch_bounds__(256, LD_WGS) void tpg_loadings_mfma_kernel(const ui
     asm("" : "+v"(off));
     return *(const uint4*)(p + off);
   };
+  // The genotypes of the tile that starts at p (the same base in both layouts: a tile is Q KiB in either).  L: chunk q of this
+  // lane's (r, h).  LMV: load X of the pair of chunks q, q + 1 with q even -- lane i takes piece (chunk q + ((i >> 1) & 1),
+  // h = i & 1) of locus 16 X + (i >> 2); a chunk past the end is the last one again, fetched and never used.
+  const int ldq = (lane >> 1) & 1;
+  const uint32_t aoff = LMV ? (uint32_t)tpg_lm_piece(lane >> 2, Qi, 0, lane & 1) * 16u : (uint32_t)lane * 16u;
+  auto LDA = [&](const char* p, int q, int X) {
+    uint32_t off;
+    if constexpr (LMV) off = aoff + (uint32_t)tpg_lm_piece(16 * X, Qi, q + ldq < Qi ? q + ldq : Qi - 1, 0) * 16u;
+    else off = aoff + (uint32_t)q * 1024u;
+    asm("" : "+v"(off));
+    return *(const uint4*)(p + off);
+  };
+  // LMV: the lane (times 4, for ds_bpermute_b32) in which lane (r, h) finds its piece of chunk q0 once the pieces of that
+  // chunk are in one register -- load 0's in the lanes that fetched them (i & 2 == 0), load 1's moved there from lane i ^ 2;
+  // for chunk q0 + 1 the two loads trade places: this lane ^ 2
+  const int lm_src = (((lane & 15) * 4 + ((lane >> 4) & 1) * 2 + (lane >> 5)) * 4);
   // The genotype stream goes through LD_D rotating register slots, fetched LD_D - 1 groups ahead, and the digit fragments of
   // group q' wait in slot q' & 1, fetched TWO groups ahead of the barrier behind which they are used; the loop is unrolled by
   // LD_D so that every slot is a compile-time index (copying a register that a load has just been issued into -- the
   // a = a1, a1 = a2 of the first form of this loop -- makes the wave wait for that load: SQ_WAIT_ANY 52 %).
+  // LMV: slots 2 p and 2 p + 1 hold the two loads of a pair; the even groups fetch the next pair, the odd ones nothing.
   constexpr int LD_D = 4;
   static_assert(LD_D % 2 == 0, "the slot of a group's digit fragments is its parity");
   uint4 AR[LD_D][LD_NLT];
 #pragma unroll
-  for (int d = 0; d < LD_D - 1; d++)
+  for (int d = 0; d < (LMV ? 2 : LD_D - 1); d++)
 #pragma unroll
-    for (int t = 0; t < LD_NLT; t++) AR[d][t] = LDG(pa[t], d < Qi ? d : Qi - 1);
+    for (int t = 0; t < LD_NLT; t++) AR[d][t] = LMV ? LDA(pa[t], 0, d) : LDA(pa[t], d < Qi ? d : Qi - 1, 0);
   // this wave's share of a group's fragments: items wv, wv + 4, ... of the 4 * CTP (K step, column tile) pairs
   const char* pu = (const char*)(UD + ct0 * 64);  // fragment (ks, c) = block ks * CT + c
   uint4 un[2][CTP];
@@ -1779,8 +1803,33 @@ __global__ __launch_bounds__(256, LD_WGS) void tpg_loadings_mfma_kernel(const ui
     constexpr int C = decltype(Cc)::value, M = decltype(Mm)::value;
     const int qa = q + LD_D - 1 < Qi ? q + LD_D - 1 : Qi - 1, qu = q + 2 < Qi ? q + 2 : Qi - 1;
     const int cur = q & 1;
+    if constexpr (!LMV) {
 #pragma unroll
-    for (int t = 0; t < LD_NLT; t++) AR[M][t] = LDG(pa[t], qa);
+      for (int t = 0; t < LD_NLT; t++) AR[M][t] = LDA(pa[t], qa, 0);
+    } else if constexpr (C % 2 == 0) {
+      static_assert(LD_D == 4, "a pair in use, a pair in flight");
+      const int qb = q + 2 < Qi ? q + 2 : Qi - 1;
+#pragma unroll
+      for (int t = 0; t < LD_NLT; t++) {
+        AR[(C + 2) % LD_D][t] = LDA(pa[t], qb, 0);
+        AR[M][t] = LDA(pa[t], qb, 1);
+      }
+    }
+    uint4 av[LD_NLT];  // chunk q of lane (r, h)
+#pragma unroll
+    for (int t = 0; t < LD_NLT; t++) {
+      if constexpr (LMV) {
+        constexpr int P = C & ~1, dq = C & 1;
+        auto turn = [&](uint32_t a, uint32_t b) {
+          const uint32_t bs = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0x4E /* quad_perm [2, 3, 0, 1] */, 0xF, 0xF, true);
+          return (uint32_t)__builtin_amdgcn_ds_bpermute(lm_src ^ (dq ? 8 : 0), (int)(ldq == dq ? a : bs));
+        };
+        av[t] = make_uint4(turn(AR[P][t].x, AR[P + 1][t].x), turn(AR[P][t].y, AR[P + 1][t].y), turn(AR[P][t].z, AR[P + 1][t].z),
+                           turn(AR[P][t].w, AR[P + 1][t].w));
+      } else {
+        av[t] = AR[C][t];
+      }
+    }
 #pragma unroll
     for (int j = 0; j < CTP; j++) un[C & 1][j] = ufrag(qu, j);
 #pragma unroll
@@ -1788,7 +1837,7 @@ __global__ __launch_bounds__(256, LD_WGS) void tpg_loadings_mfma_kernel(const ui
       v4i fg[LD_NLT];
 #pragma unroll
       for (int t = 0; t < LD_NLT; t++) {
-        const uint32_t w = s == 0 ? AR[C][t].x : s == 1 ? AR[C][t].y : s == 2 ? AR[C][t].z : AR[C][t].w;
+        const uint32_t w = s == 0 ? av[t].x : s == 1 ? av[t].y : s == 2 ? av[t].z : av[t].w;
 #pragma unroll
         for (int k = 0; k < 4; k++) fg[t][k] = (int)tpg_codes(w, k);
       }
@@ -1891,11 +1940,18 @@ static int pca_loadings_device(tpg_ctx* ctx, const tpg_view* v, const double* d_
   TPG_LAUNCH(ctx, "loadings_u_digits", tpg_u_digits_kernel, dim3(1024), dim3(256), 0, d_U, n, k, FU, v->Q, CT, d_UD);
   TPG_LAUNCH(ctx, "loadings_u_digits", tpg_uq_colsum_kernel, dim3((unsigned)k), dim3(256), 0, d_U, n, FU, d_usum);
   const unsigned grid = (unsigned)ceil_div(n_lt, 4 * LD_NLT);
+  if (!v->LM) TPG_TRY(tpg_view_need_L(ctx, v));  // (a view packed locus-major is read as it is)
   for (int ct0 = 0; ct0 < CT;) {
     const int left = CT - ct0;
 #define LD_LAUNCH(C)                                                                                             \
-  TPG_LAUNCH(ctx, "loadings_mfma", tpg_loadings_mfma_kernel<C>, dim3(grid), dim3(256), 0, (const uint4*)v->L,     \
-             (const uint4*)d_UD, n_lt, v->Q, ct0, CT, d_acc, Cpad)
+  do {                                                                                                           \
+    if (v->LM)                                                                                                   \
+      TPG_LAUNCH(ctx, "loadings_mfma", (tpg_loadings_mfma_kernel<C, true>), dim3(grid), dim3(256), 0,            \
+                 (const uint4*)v->LM, (const uint4*)d_UD, n_lt, v->Q, ct0, CT, d_acc, Cpad);                     \
+    else                                                                                                         \
+      TPG_LAUNCH(ctx, "loadings_mfma", (tpg_loadings_mfma_kernel<C, false>), dim3(grid), dim3(256), 0,           \
+                 (const uint4*)v->L, (const uint4*)d_UD, n_lt, v->Q, ct0, CT, d_acc, Cpad);                      \
+  } while (0)
     if (left >= 4) { LD_LAUNCH(4); ct0 += 4; }
     else if (left == 3) { LD_LAUNCH(3); ct0 += 3; }
     else if (left == 2) { LD_LAUNCH(2); ct0 += 2; }
@@ -1963,6 +2019,7 @@ extern "C" int tpg_pca_loadings(tpg_ctx* ctx, const tpg_view* v, const double* c
     DevBuf d_inv;
     TPG_TRY(d_inv.alloc_n<double>((size_t)m));
     TPG_LAUNCH(ctx, "inv_scale", tpg_inv_kernel, dim3(1024), dim3(256), 0, is.dev<double>(), m, d_inv.as<double>());
+    TPG_TRY(tpg_view_need_L(ctx, v));
     TPG_TRY(run_sweep(ctx, SW_ROWSCALE, v->L, v->KG * 4, v->Q, m, n, ic.dev<double>(), d_inv.as<double>(), iu.dev<double>(), n, k,
                       ov.dev<double>(), id.dev<double>(), nullptr));
   }

@@ -1251,13 +1251,14 @@ static int view_create_impl(tpg_ctx* ctx, const tpg_fbm* fbm, const int32_t* row
     v[k].reset(new tpg_view(ctx, n, m));
     // A pair is "the raw view of the pairwise statistics + the imputed view of the PCA": neither reads the 2-bit T
     // layout (the pairwise kernel reads T4, the class Gram its own sorted layout), so the pair is packed as L + T4 and
-    // L; whoever does want T gets it from L (tpg_view_need_T).
+    // L; whoever does want T gets it from L (tpg_view_need_T).  The imputed view's two readers in the PCA want a locus' pieces
+    // next to each other, so it is packed as LM and whoever does want L gets it from LM (tpg_view_need_L).
     // A single RAW-byte view (code256 == NULL) is what the pairwise statistics alone ask for (increment_{ibs,king,as}_counts
     // compare raw bytes, src/snp_ibs.cpp:47-54): it is packed as L + T4 too, which saves a stand-alone snp_ibs / snp_king /
     // pairwise_grm call, and every block of an R driver loop, the T -> T4 pass (0.7 ms at 5 000 x 1 000 000).
     if (!two && code256_a) TPG_HIP(tpg_pmalloc((void**)&v[k]->T, v[k]->bytes_each));
     else if (k == 0) TPG_HIP(tpg_pmalloc((void**)&v[k]->T4, 2 * v[k]->bytes_each));
-    TPG_HIP(tpg_pmalloc((void**)&v[k]->L, v[k]->bytes_each));
+    TPG_HIP(tpg_pmalloc((void**)(k == 1 ? &v[k]->LM : &v[k]->L), v[k]->bytes_each));
   }
   TPG_TRY(d_lut.alloc(sizeof(lut)));
   TPG_HIP(tpg_h2d_async(ctx, d_lut.p, lut, (size_t)nv * (256 + 16)));
@@ -1303,11 +1304,13 @@ extern "C" int tpg_view_create_pair(tpg_ctx* ctx, const tpg_fbm* fbm, const int3
 tpg_view::~tpg_view() {
   drop_derived();
   if (L && !L_borrowed) tpg_pfree(L);
+  if (LM) tpg_pfree(LM);
 }
 void tpg_view::drop_derived() {
   if (T) tpg_pfree(T);
   if (T4) tpg_pfree(T4);
   if (lc_part) tpg_pfree(lc_part);
+  if (L && LM) { tpg_pfree(LM); LM = nullptr; }
   T = T4 = nullptr;
   lc_part = nullptr;
   lc_chunks = 0;

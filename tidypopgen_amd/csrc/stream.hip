@@ -713,7 +713,10 @@ struct StreamRun {
         TPG_TRY(rows_out(j->scale, 8, m, q0, ds, mb, 1, ev, keep_views ? -1 : slot));
         if (kp) {
           kp->v = std::move(imp ? imp : v[view_of_pca]);  // the imputed view stays for the loadings
-          kp->v->drop_derived();  // what the loadings read is L; the other layouts go back to the pool now
+          // what the kept view's readers want is L (the counts and the sweep of tpg_pca_loadings, the copy into bigL below): a
+          // pair's imputed view, packed locus-major for the Gram above, is turned once; the other layouts go back to the pool now
+          TPG_TRY(tpg_view_need_L(ctx, kp->v.get()));
+          kp->v->drop_derived();
         }
         if (big_views) {
           // the block's L joins the others (a block starts on a multiple of 128 loci: whole locus tiles), its own copy goes back
