@@ -527,6 +527,85 @@ int tpg_admix_cv(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, c
                  uint64_t cv_seed, const double* q0, const double* f0, double* cv_error, double* fold_ll, int64_t* fold_count,
                  int64_t* fold_het, int32_t* fold_iter, int32_t* fold_converged);
 
+/* ---- sNMF (gt_snmf, R/gt_snmf.R: the reference writes a .geno file and calls LEA::snmf; LEA is not part of the reference's
+ * sources and nothing pins it, so what is computed is defined HERE: sparse non-negative matrix factorisation by alternating
+ * non-negative least squares (Frichot et al. 2014; Kim and Park 2007), RECALLED, NOT PINNED) --------------------------------------
+ * Data.  A view of N individuals x M loci, diploid.  x(i,j,c) = [g(i,j) = c] for c in {0, 1, 2}: three indicator columns per
+ *   locus.  A missing entry (code 3) has all three indicators 0 and STAYS IN THE LOSS (the recalled bit encoding of sNMF does
+ *   this; it keeps both normal matrices shared by every system).  A caller who wants otherwise imputes the view first.
+ * State.  K in [1, TPG_SNMF_MAX_K].  Q is N x K, non-negative, rows summing to 1.  G(j,c,k) >= 0 with sum_c G(j,c,k) = 1,
+ *   returned as a 3M x K column-major matrix with row 3 j + c (the order of LEA's .G file).  P(j,k) = G(j,1,k) / 2 + G(j,2,k)
+ *   (a quotient, then a sum), M x K: the frequency of the counted allele.
+ * Ridge.  ridge(C) of a K x K matrix C: rho = (TPG_SNMF_RIDGE * tr) / (double)K with tr = C(0,0) + C(1,1) + ... in ascending k;
+ *   C + rho I.  With it every matrix below is positive definite and every NNLS optimum is unique.
+ * NNLS(C, b) = argmin over x >= 0 of x'Cx / 2 - b'x.
+ * One iteration, from Q to (G, Q'):
+ *   1. A = ridge(Q'Q).
+ *   2. for every (j,c): b(k) = sum over the i with g(i,j) = c of Q(i,k);  gt(j,c,.) = NNLS(A, b).
+ *   3. s(j,k) = gt(j,0,k) + gt(j,1,k) + gt(j,2,k) in that order.  s > TPG_SNMF_TINY: G(j,c,k) = gt(j,c,k) / s; else G(j,c,k) = 1/3
+ *      (1.0 / 3.0) in the three classes.
+ *   4. B = ridge(GG' + alpha 11'): GG'(k,l) = sum over the 3M rows of G(.,k) G(.,l); alpha is added to every entry, then the ridge
+ *      from the trace of that sum.
+ *   5. for every i: b_i(k) = sum over the typed j of G(j,g(i,j),k);  qt = NNLS(B, b_i);  r = qt(0) + qt(1) + ... in ascending k.
+ *      r > TPG_SNMF_TINY: Q'(i,k) = qt(k) / r; else Q'(i,k) = 1 / K (1.0 / (double)K).
+ *   Criterion.  ls = T - 2 sum_i Q'(i,.).b_i + sum_kl (Q''Q')(k,l) (GG')(k,l), T = the typed entries of the view, GG' without alpha
+ *   and without ridge: ||X - Q'G'||^2 of the returned pair written out, from sums the iteration has anyway (no extra sweep).
+ *   The dot products are fused multiply-adds in ascending k (k major, then l) from +0.
+ * Start.  q0 (N x K column-major, host or device memory): each row divided by its sum (ascending k); an entry that is not
+ *   finite or not positive: TPG_EINVAL, found on the device (as tpg_admix_em does).  q0 = NULL: the seeded Q of "admixture",
+ *   bit for bit, from `seed`.
+ * Iteration.  State 0 is the start; iteration t makes (G, Q)(t) from Q(t - 1) and ls(t).  Stop after iteration t >= 2 when
+ *   |ls(t-1) - ls(t)| <= tol * ls(t-1) (converged = 1), or at t = max_iter.  ls_trace[0 .. t-1] = ls(1) .. ls(t); ls = ls(t).
+ *   max_iter = 0 returns the start, G = 1/3 everywhere, n_iter = 0 and ls = NaN.  The host reads one double per iteration.
+ * NNLS contract.  With w = b - C x and bmax = max |b(k)|, a returned x has x >= 0, |w(k)| <= tau bmax where x(k) > 0 and
+ *   w(k) <= tau bmax where x(k) = 0, tau = TPG_SNMF_KKT_TOL.  A system that misses this when the solver stops is counted in
+ *   n_unsolved (int64; its x is still >= 0); 0 is the expected value.  The solver (csrc/snmf.hip) is Lawson and Hanson's
+ *   active-set method on the normal equations, each inner solve a Cholesky factorisation of the masked matrix with one step
+ *   of iterative refinement.
+ * Hold-out by fraction.  With h(i,j) of "admixture cross-validation" (the same salt and order, `seed` in the place of cv_seed),
+ *   an entry is held out iff it is typed and (h >> 32) < floor(fraction * 2^32), 0 < fraction < 1: a NEW view, exactly as
+ *   tpg_view_holdout makes one.
+ * Cross-entropy sums of a state (Q, G) for a pair (full, train) of the same geometry.  Per entry with genotype g:
+ *   p = sum_k q(i,k) G(j,g,k), fused terms in ascending k from +0; term = -ln max(p, TPG_SNMF_P_FLOOR).  Summed over (a) the
+ *   entries typed in `full` and missing in `train` (masked) and (b) the entries typed in `train` (all); each a double sum and
+ *   an int64 count; the cross-entropy is sum / count.  Q and G are taken as given.
+ * Determinism.  As "admixture": every sum has a fixed shape (csrc/snmf.hip), no floating-point atomics, no dependence on launch
+ *   geometry; the Q step's right-hand sides are partial sums over chunks of TPG_ADMIX_CHUNK_LOCI loci added in ascending chunk
+ *   order; Gram matrices are sums over tiles of TPG_SNMF_GRAM_ROWS rows added in ascending tile order.  Two calls: same bits.
+ * Out of scope: K > TPG_SNMF_MAX_K, ploidy other than 2, LEA's I initialisation and project files, sNMF inside tpg_stream_* /
+ *   tpg_multi_*, a loss that masks missing entries instead of zeroing them.
+ * Errors.  K outside [1, TPG_SNMF_MAX_K], max_iter < 0, tol or alpha negative or NaN, ploidy other than 2, N = 0 or M = 0,
+ *   fraction outside (0, 1), views of different geometry: TPG_EINVAL.  Q, G and P are written at the very end only: after an
+ *   error every output is untouched. */
+#define TPG_SNMF_MAX_K 16
+#define TPG_SNMF_RIDGE 1e-10
+#define TPG_SNMF_TINY 1e-9
+#define TPG_SNMF_KKT_TOL 1e-12
+#define TPG_SNMF_P_FLOOR 1e-9
+#define TPG_SNMF_GRAM_ROWS 256
+/* the defaults of gt_snmf: tpg_snmf takes its parameters one by one */
+#define TPG_SNMF_MAX_ITER 200
+#define TPG_SNMF_TOL 1e-5
+#define TPG_SNMF_ALPHA 10.0
+/* Q: N x K, G: 3M x K, P: M x K, column-major doubles, host or device memory, G and P may be NULL; q0 may be NULL (seeded start);
+ * ls_trace has room for max_iter doubles or is NULL; ls, ls_trace, n_iter, converged and n_unsolved (the total over the run) are
+ * host memory and may each be NULL */
+int tpg_snmf(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, int max_iter, double tol, double alpha, uint64_t seed,
+             const double* q0, double* Q, double* G, double* P, double* ls, double* ls_trace, int* n_iter, int* converged,
+             int64_t* n_unsolved);
+/* one iteration from Q_in, taken as given (no normalisation): Q_out (N x K), G_out (3M x K, may be NULL), ls and n_unsolved (host
+ * memory, may be NULL) */
+int tpg_snmf_step(tpg_ctx* ctx, const tpg_view* v, int K, double alpha, const double* Q_in, double* Q_out, double* G_out, double* ls,
+                  int64_t* n_unsolved);
+/* the batched solver alone: X(r,.) = NNLS(A, B(r,.)), A K x K symmetric positive definite (no ridge is added), B and X
+ * nrhs x K column-major, host or device memory */
+int tpg_nnls_shared(tpg_ctx* ctx, int K, const double* A, const double* B, int64_t nrhs, double* X, int64_t* n_unsolved);
+/* the fraction hold-out of `full` as a new view (free it with tpg_view_free); n_held (host memory, may be NULL) */
+int tpg_view_holdout_fraction(tpg_ctx* ctx, const tpg_view* full, double fraction, uint64_t seed, tpg_view** out, int64_t* n_held);
+/* Q: N x K, G: 3M x K, column-major doubles, host or device memory; the four outputs are host memory and may each be NULL */
+int tpg_snmf_cross_entropy_sums(tpg_ctx* ctx, const tpg_view* full, const tpg_view* train, int K, const double* Q, const double* G,
+                                double* sum_masked, int64_t* n_masked, double* sum_all, int64_t* n_all);
+
 /* pop_global_stats (R/pop_global_stats.R:113-212, with compute_np_mn, src/compute_np_mn.cpp:8-34): by_locus =
  * m x 10 column-major {Ho, Hs, Ht, Dst, Htp, Dstp, Fst, Fstp, Fis, Dest} (may be NULL), overall = the 10
  * by_locus = FALSE values (may be NULL).  ploidy (may be NULL) must be all 2: the reference stops otherwise. */

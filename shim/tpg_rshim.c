@@ -29,6 +29,7 @@
  */
 #define _POSIX_C_SOURCE 200809L /* strdup, mmap */
 #include <fcntl.h>
+#include <float.h>
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
@@ -1407,6 +1408,86 @@ SEXP _tidypopgen_tpg_pcadapt(SEXP BM, SEXP rowInd, SEXP colInd, SEXP U) {
   return out;
 }
 
+/* ---- sNMF ---------------------------------------------------------------------------------------------------------- */
+
+#pragma weak tpg_snmf
+#pragma weak tpg_view_holdout_fraction
+#pragma weak tpg_snmf_cross_entropy_sums
+
+/* tpg_snmf(BM, rowInd, colInd, k, alpha, tolerance, iterations, seed, percentage, q0): the .geno export and the LEA::snmf run of
+ * R/gt_snmf.R as one call of the sNMF of include/tpg.h "sNMF", for one k and one run.  seed = a double vector of length 1 holding
+ * a whole number in [0, 2^53]; percentage = NULL (no cross-entropy) or one number in (0, 1): that share of the typed genotypes is
+ * held out (the mask is keyed by seed), the fit runs on the rest, as LEA's does, and cv / cv_all are the masked / all
+ * cross-entropies; q0 (N x k) = a start, or NULL for the seeded one.
+ * -> list(Q: N x k, P: M x k (frequency of the counted allele), G: 3M x k (row 3 j + c), ls, n_iter, converged, cv, cv_all);
+ * cv and cv_all are NA_real_ without percentage */
+SEXP _tidypopgen_tpg_snmf(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP alpha, SEXP tolerance, SEXP iterations, SEXP seed,
+                          SEXP percentage, SEXP q0) {
+  TPG_NEEDS(tpg_snmf);
+  TPG_NEEDS(tpg_view_holdout_fraction);
+  TPG_NEEDS(tpg_snmf_cross_entropy_sums);
+  const int K = Rf_asInteger(k);
+  if (K == NA_INTEGER || K < 1) Rf_error("tidypopgen (GPU): k must be a positive integer");
+  if ((TYPEOF(alpha) != REALSXP && TYPEOF(alpha) != INTSXP) || XLENGTH(alpha) != 1) Rf_error("tidypopgen (GPU): alpha must be one number");
+  if ((TYPEOF(tolerance) != REALSXP && TYPEOF(tolerance) != INTSXP) || XLENGTH(tolerance) != 1)
+    Rf_error("tidypopgen (GPU): tolerance must be one number");
+  SEXP as = PROTECT(as_real(alpha)), ts = PROTECT(as_real(tolerance));
+  const double al = REAL(as)[0], tl = REAL(ts)[0];
+  UNPROTECT(2);
+  if (!(al >= 0 && al <= DBL_MAX)) Rf_error("tidypopgen (GPU): alpha must be a finite non-negative number");
+  if (!(tl >= 0)) Rf_error("tidypopgen (GPU): tolerance must be a non-negative number");
+  const int mi = Rf_asInteger(iterations);
+  if (mi == NA_INTEGER || mi < 0) Rf_error("tidypopgen (GPU): iterations must be a non-negative integer");
+  if (TYPEOF(seed) != REALSXP || XLENGTH(seed) != 1) Rf_error("tidypopgen (GPU): seed must be a double vector of length 1");
+  const double sd = REAL(seed)[0];
+  if (!(sd >= 0 && sd <= 9007199254740992.0) || sd != floor(sd))
+    Rf_error("tidypopgen (GPU): seed must be a whole number in [0, 2^53]");
+  double pct = 0;
+  if (percentage != R_NilValue) {
+    if ((TYPEOF(percentage) != REALSXP && TYPEOF(percentage) != INTSXP) || XLENGTH(percentage) != 1)
+      Rf_error("tidypopgen (GPU): percentage must be NULL or one number");
+    SEXP ps = PROTECT(as_real(percentage));
+    pct = REAL(ps)[0];
+    UNPROTECT(1);
+    if (!(pct > 0 && pct < 1)) Rf_error("tidypopgen (GPU): percentage must lie strictly between 0 and 1");
+  }
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  const R_xlen_t n = XLENGTH(ri), m = XLENGTH(ci);
+  if (n > INT_MAX || m > INT_MAX / 3) Rf_error("tidypopgen (GPU): too many rows or columns for an R matrix");
+  SEXP qs = PROTECT(q0 == R_NilValue ? R_NilValue : Rf_coerceVector(q0, REALSXP));
+  if (qs != R_NilValue && XLENGTH(qs) != n * (R_xlen_t)K) Rf_error("tidypopgen (GPU): q0 must be length(rowInd) x k");
+  SEXP vals[8];
+  vals[0] = PROTECT(Rf_allocMatrix(REALSXP, (int)n, K));
+  vals[1] = PROTECT(Rf_allocMatrix(REALSXP, (int)m, K));
+  vals[2] = PROTECT(Rf_allocMatrix(REALSXP, (int)(3 * m), K));
+  vals[3] = PROTECT(Rf_allocVector(REALSXP, 1));
+  vals[4] = PROTECT(Rf_allocVector(INTSXP, 1));
+  vals[5] = PROTECT(Rf_allocVector(LGLSXP, 1));
+  vals[6] = PROTECT(Rf_allocVector(REALSXP, 1));
+  vals[7] = PROTECT(Rf_allocVector(REALSXP, 1));
+  static const char* names[8] = {"Q", "P", "G", "ls", "n_iter", "converged", "cv", "cv_all"};
+  SEXP out = PROTECT(named_list(8, names, vals));
+  int nit = 0, conv = 0;
+  double sm = 0, sa = 0;
+  int64_t nm = 0, na = 0;
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  tpg_view* train = NULL;
+  int rc = TPG_OK;
+  if (pct > 0) rc = tpg_view_holdout_fraction(ctx(), v, pct, (uint64_t)sd, &train, NULL);
+  if (rc == TPG_OK)
+    rc = tpg_snmf(ctx(), train ? train : v, NULL, K, mi, tl, al, (uint64_t)sd, qs == R_NilValue ? NULL : REAL(qs), REAL(vals[0]),
+                  REAL(vals[2]), REAL(vals[1]), REAL(vals[3]), NULL, &nit, &conv, NULL);
+  if (rc == TPG_OK && train) rc = tpg_snmf_cross_entropy_sums(ctx(), v, train, K, REAL(vals[0]), REAL(vals[2]), &sm, &nm, &sa, &na);
+  if (train) tpg_view_free(train);
+  TPG_R_VIEW(v, rc);
+  INTEGER(vals[4])[0] = nit;
+  LOGICAL(vals[5])[0] = conv != 0;
+  REAL(vals[6])[0] = train && nm > 0 ? sm / (double)nm : NA_REAL;
+  REAL(vals[7])[0] = train && na > 0 ? sa / (double)na : NA_REAL;
+  UNPROTECT(12);
+  return out;
+}
+
 /* ---- autoSVD ------------------------------------------------------------------------------------------------------ */
 
 #pragma weak tpg_pca_auto_svd
@@ -1605,11 +1686,16 @@ const R_CallMethodDef tpg_rshim_entries_autosvd[] = {
     {"_tidypopgen_tpg_pca_auto_svd", (DL_FUNC)&_tidypopgen_tpg_pca_auto_svd, 7},
     {NULL, NULL, 0}};
 
+/* sNMF, in a table of its own: the reference hands a .geno file to LEA, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_snmf[] = {
+    {"_tidypopgen_tpg_snmf", (DL_FUNC)&_tidypopgen_tpg_snmf, 10},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the eleven tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the twelve tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1620,7 +1706,8 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_admix) / sizeof(tpg_rshim_entries_admix[0]) +
                              sizeof(tpg_rshim_entries_admix_cv) / sizeof(tpg_rshim_entries_admix_cv[0]) +
                              sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0]) +
-                             sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0])];
+                             sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0]) +
+                             sizeof(tpg_rshim_entries_snmf) / sizeof(tpg_rshim_entries_snmf[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1633,6 +1720,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_admix_cv; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_pcadapt; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_autosvd; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_snmf; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

@@ -177,6 +177,26 @@ gt_admixture_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bi
   adm_list
 }
 
+# Ancestry proportions by sparse non-negative matrix factorisation on the GPU for one k and one run (the .geno export and the
+# LEA::snmf run of R/gt_snmf.R; include/tpg.h "sNMF" is the definition).  seed: one whole number; q0: a start (individuals x k) or
+# NULL for the seeded one.  entropy = TRUE holds a share `percentage` of the typed genotypes out, fits on the rest, as LEA does, and
+# adds cv (the masked cross-entropy, the name the reference uses) and cv_all.  Returns the gt_admix list of the reference for that
+# run (k, Q, P, G, algorithm), with ls, n_iter and converged beside it.  project, I and ploidy have no counterpart.
+gt_snmf_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), k, alpha = 10,
+                        tolerance = 1e-5, entropy = FALSE, percentage = 0.05, iterations = 200L, seed = 0, q0 = NULL) {
+  res <- .Call(`_tidypopgen_tpg_snmf`, X, as.integer(ind.row), as.integer(ind.col), as.integer(k), as.numeric(alpha),
+               as.numeric(tolerance), as.integer(iterations), as.numeric(seed), if (isTRUE(entropy)) as.numeric(percentage) else NULL,
+               q0)
+  adm_list <- list(k = as.integer(k), Q = list(res$Q), P = list(res$P), G = list(res$G), ls = res$ls, n_iter = res$n_iter,
+                   converged = res$converged, algorithm = "SNMF")
+  if (isTRUE(entropy)) {
+    adm_list$cv <- res$cv
+    adm_list$cv_all <- res$cv_all
+  }
+  class(adm_list) <- c("gt_admix", "list")
+  adm_list
+}
+
 # PCA-based genome scan on the GPU (R/gt_pcadapt.R:44-86 around bigsnpr::snp_pcadapt; include/tpg.h "pcadapt" is the definition).
 # U.row: the first k columns of the PCA's u for the rows ind.row.  Returns the reference's object: a data.frame(score) of class
 # "mhtest" whose `predict` attribute gives log10 p-values from the chi-square with k degrees of freedom; dist, the device's own

@@ -204,6 +204,12 @@ PROTOTYPES = {
     "tpg_admix_holdout_sums": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp]),
     "tpg_admix_cv_error": (ci, [ci, vp, vp, vp, vp, vp]),
     "tpg_admix_cv": (ci, [vp, vp, vp, ci, P(AdmixParams), ci, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    # ---- sNMF
+    "tpg_snmf": (ci, [vp, vp, vp, ci, ci, f64, f64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_snmf_step": (ci, [vp, vp, ci, f64, vp, vp, vp, vp, vp]),
+    "tpg_nnls_shared": (ci, [vp, ci, vp, vp, i64, vp, vp]),
+    "tpg_view_holdout_fraction": (ci, [vp, vp, f64, u64, vp, vp]),
+    "tpg_snmf_cross_entropy_sums": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
     "tpg_pop_global_stats": (ci, [vp, vp, vp, ci, vp, vp, vp]),
     "tpg_pop_basic_stats": (ci, [vp, vp, vp, ci, vp, ci, vp, vp]),
     "tpg_window_stats": (ci, [vp, vp, i64, ci, vp, vp, vp, i64, ci, ci, vp, vp]),

@@ -311,6 +311,19 @@ class View:
         v.n_held = int(held.value)
         return v
 
+    def holdout_fraction(self, fraction: float, seed: int = 0) -> "View":
+        """a new view of the same rows / columns with a share `fraction` of the typed genotypes set to missing, chosen by the hash of
+        (seed, position) (tpg_view_holdout_fraction, include/tpg.h "sNMF"); their number is left in `.n_held` of the result"""
+        h = C.c_void_p()
+        held = C.c_int64()
+        check(lib.tpg_view_holdout_fraction(self.ctx.h, self.h, float(fraction), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h),
+                                            C.byref(held)))
+        v = View.__new__(View)
+        v.X, v.ctx, v.h = self.X, self.ctx, h
+        v.n, v.m = int(lib.tpg_view_n(h)), int(lib.tpg_view_m(h))
+        v.n_held = int(held.value)
+        return v
+
     def select_loci(self, idx) -> "View":
         """a new view of the loci idx (0-based positions in this view; any order, duplicates allowed) gathered on the device
         (tpg_view_select_loci): also works where the store cannot be packed again, as behind impute()"""
@@ -1798,6 +1811,120 @@ def gt_admixture(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, se
             if crossval:
                 out["cv"].append(admix_cv(v, kk, folds=cv_folds, cv_seed=cv_seed, seed=seed[a * n_runs + b], max_iter=max_iter,
                                           tol=tol)["cv_error"])
+    return out
+
+
+SNMF_MAX_K = 16  # TPG_SNMF_MAX_K of include/tpg.h
+
+
+def snmf(v: View, K: int, Q0=None, seed: int = 0, alpha: float = 10.0, tol: float = 1e-5, max_iter: int = 200,
+         return_trace: bool = False, ploidy=None) -> dict:
+    """tpg_snmf (include/tpg.h "sNMF"): ancestry proportions of a resident view by sparse non-negative matrix factorisation.  Q0
+    (n x K) is a numpy array or a device pointer (int); None draws the start from `seed` (the seeded Q of admix_em).
+    -> dict(Q (n x K), G (3m x K, row 3 j + c), P (m x K, frequency of the counted allele), ls, n_iter, converged, n_unsolved
+    [, trace = ls(1 .. n_iter)])"""
+    K = int(K)
+    q0 = _admix_mat(Q0, v.n, K, "Q0")
+    kk = max(K, 1)  # K < 1 is the library's to refuse
+    Q, G, P = np.zeros((v.n, kk), order="F"), np.zeros((3 * v.m, kk), order="F"), np.zeros((v.m, kk), order="F")
+    trace = np.full(max(int(max_iter), 0) + 1, np.nan)
+    ls, nit, conv, uns = C.c_double(), C.c_int(), C.c_int(), C.c_int64()
+    pl = _f64(ploidy)
+    check(lib.tpg_snmf(v.ctx.h, v.h, _ptr(pl), K, int(max_iter), float(tol), float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(q0),
+                       _ptr(Q), _ptr(G), _ptr(P), C.byref(ls), _ptr(trace), C.byref(nit), C.byref(conv), C.byref(uns)))
+    out = dict(Q=Q, G=G, P=P, ls=ls.value, n_iter=int(nit.value), converged=bool(conv.value), n_unsolved=int(uns.value))
+    if return_trace:
+        out["trace"] = trace[: nit.value].copy()
+    return out
+
+
+def snmf_step(v: View, Q, alpha: float = 10.0) -> dict:
+    """tpg_snmf_step: one iteration from the caller's own Q (n x K, taken as given) -> dict(Q, G (3m x K), ls, n_unsolved)"""
+    if isinstance(Q, (int, np.integer)):
+        raise ValueError("snmf_step takes a numpy array (K is read from its shape)")
+    q = np.asfortranarray(Q, dtype=np.float64)
+    K = q.shape[1] if q.ndim == 2 else 0
+    q = _admix_mat(q, v.n, K, "Q")
+    Qn, G = np.zeros((v.n, max(K, 1)), order="F"), np.zeros((3 * v.m, max(K, 1)), order="F")
+    ls, uns = C.c_double(), C.c_int64()
+    check(lib.tpg_snmf_step(v.ctx.h, v.h, K, float(alpha), _ptr(q), _ptr(Qn), _ptr(G), C.byref(ls), C.byref(uns)))
+    return dict(Q=Qn, G=G, ls=ls.value, n_unsolved=int(uns.value))
+
+
+def nnls_shared(A, B, ctx: Optional[Context] = None, return_unsolved: bool = False):
+    """tpg_nnls_shared: X(r, .) = argmin over x >= 0 of x'Ax / 2 - B(r, .)'x for every row of B (nrhs x K), A K x K symmetric
+    positive definite -> X (nrhs x K) [, n_unsolved: the systems that miss the KKT contract of include/tpg.h "sNMF"]"""
+    ctx = ctx or default_context()
+    a, b = np.asfortranarray(A, dtype=np.float64), np.asfortranarray(B, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or b.ndim != 2 or b.shape[1] != a.shape[0]:
+        raise ValueError(f"A must be K x K and B nrhs x K, not {a.shape} and {b.shape}")
+    X = np.zeros(b.shape, order="F")
+    uns = C.c_int64()
+    check(lib.tpg_nnls_shared(ctx.h, a.shape[0], _ptr(a), _ptr(b), b.shape[0], _ptr(X), C.byref(uns)))
+    return (X, int(uns.value)) if return_unsolved else X
+
+
+def snmf_cross_entropy(full: View, train: View, Q, G) -> dict:
+    """tpg_snmf_cross_entropy_sums: -ln max(p, floor) of the genotypes under (Q, G), taken as given, summed over the entries typed in
+    `full` and missing in `train` (masked) and over those typed in `train` (all); two views of the same geometry, as
+    View.holdout_fraction makes them -> dict(masked, all (the cross-entropies), sum_masked, n_masked, sum_all, n_all)"""
+    if isinstance(Q, (int, np.integer)) or isinstance(G, (int, np.integer)):
+        raise ValueError("snmf_cross_entropy takes numpy arrays (K is read from their shape)")
+    q = np.asfortranarray(Q, dtype=np.float64)
+    K = q.shape[1] if q.ndim == 2 else 0
+    q, g = _admix_mat(q, full.n, K, "Q"), _admix_mat(G, 3 * full.m, K, "G")
+    sm, sa, nm, na = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+    check(lib.tpg_snmf_cross_entropy_sums(full.ctx.h, full.h, train.h, K, _ptr(q), _ptr(g), C.byref(sm), C.byref(nm), C.byref(sa),
+                                          C.byref(na)))
+    return dict(masked=sm.value / nm.value if nm.value else float("nan"), all=sa.value / na.value if na.value else float("nan"),
+                sum_masked=sm.value, n_masked=int(nm.value), sum_all=sa.value, n_all=int(na.value))
+
+
+def gt_snmf(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, alpha: float = 10, tolerance: float = 1e-5,
+            entropy: bool = False, percentage: float = 0.05, iterations: int = 200, seed=None, impute: Optional[str] = None) -> dict:
+    """R/gt_snmf.R with the sNMF of include/tpg.h "sNMF" in place of LEA::snmf: every k of `k` (a scalar or a list) is run n_runs
+    times on one resident view.  seed is handled as gt_admixture handles it: n_runs entries (repeated for every k) or
+    n_runs * len(k), one per run in the order of the result; None: 0, 1, ... in that order.
+    -> a gt_admix-shaped dict: k (one entry per run), Q, P (frequency of the counted allele), G (3m x K, LEA's .G order), ls,
+    n_iter and converged as lists, algorithm = "SNMF".  entropy=True holds a share `percentage` of the typed genotypes out (the mask
+    is drawn from the run's seed), fits on the hold-out view, as LEA does, and adds `cv` (the masked cross-entropy, the name the
+    reference uses: the smallest marks the k to use) and `cv_all` (that of the genotypes the fit saw).
+    impute = "mode" | "mean0" | "random" fills the missing genotypes first (View.impute); by default they stay in the loss as
+    zeros.  project, I and a ploidy other than 2 of the reference have no counterpart here: there is no project file, the start is
+    the seeded one, and the three-class encoding is the diploid one."""
+    if k is None:
+        raise ValueError("k is required")
+    ks = [int(x) for x in np.atleast_1d(k)]
+    n_runs = int(n_runs)
+    if seed is not None:
+        seed = [int(s) for s in np.atleast_1d(seed)]
+        if len(seed) != n_runs and len(seed) != n_runs * len(ks):
+            raise ValueError("'seed' should be a vector of length 'n_runs' OR 'n_runs' * length(k)")
+        if len(seed) == n_runs:
+            seed = seed * len(ks)
+    else:
+        seed = list(range(n_runs * len(ks)))
+    if entropy and not 0.0 < float(percentage) < 1.0:
+        raise ValueError("'percentage' should lie strictly between 0 and 1")
+    v = View(X, ind_row, ind_col)
+    if impute is not None:
+        v = v.impute(impute)
+    out = dict(k=[], Q=[], P=[], G=[], ls=[], n_iter=[], converged=[], algorithm="SNMF")
+    if entropy:
+        out["cv"], out["cv_all"] = [], []
+    for a, kk in enumerate(ks):
+        for b in range(n_runs):
+            sd = seed[a * n_runs + b]
+            train = v.holdout_fraction(percentage, sd) if entropy else v
+            r = snmf(train, kk, seed=sd, alpha=alpha, tol=tolerance, max_iter=iterations)
+            out["k"].append(kk)
+            for name in ("Q", "P", "G", "ls", "n_iter", "converged"):
+                out[name].append(r[name])
+            if entropy:
+                ce = snmf_cross_entropy(v, train, r["Q"], r["G"])
+                out["cv"].append(ce["masked"])
+                out["cv_all"].append(ce["all"])
+                train.free()
     return out
 
 

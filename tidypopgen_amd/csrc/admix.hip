@@ -19,63 +19,16 @@
 // Every sum has a fixed shape: a thread's entries in ascending order, lane r + lane r + 32, then the four waves in order (and
 // for the likelihood a butterfly over the wave, the waves in order, the tiles by a one-workgroup kernel).  No atomics on
 // floating point; the only atomic is the integer OR of the Q0 / F0 validation flag.
-#include "common.h"
-#include "synth_common.h"
-
-#include <math.h>
+#include "admix_common.h"
 
 namespace {
 
-constexpr int ADM_CHUNK = TPG_ADMIX_CHUNK_LOCI;
-static_assert(ADM_CHUNK % 128 == 0, "a chunk is whole blocks of T");
-constexpr uint64_t ADM_F_SALT = 0xF0F0F0F0F0F0F0F0ull;
-
-// u(h) of include/tpg.h: the addition rounds to nearest even once h >> 11 reaches 2^52, the same in every IEEE double
-__host__ __device__ inline double admix_u(uint64_t h) { return ((double)(h >> 11) + 0.5) * 0x1p-53; }
-
-__device__ __forceinline__ double admix_clamp(double f) {
-  return f < TPG_ADMIX_EPS ? TPG_ADMIX_EPS : f > 1.0 - TPG_ADMIX_EPS ? 1.0 - TPG_ADMIX_EPS : f;
-}
-__device__ __forceinline__ bool admix_finite(double x) { return fabs(x) <= 1.79769313486231570815e308; }
-
-// element e of a packed dword (common.h: e = 4 k + b at bits 8 b + 2 k)
-__device__ __forceinline__ int admix_code(uint32_t w, int e) { return (int)((w >> (8 * (e & 3) + 2 * (e >> 2))) & 3u); }
-
-// ---- start, validation, output ---------------------------------------------------------------------------------------
-__global__ void admix_seed_q_kernel(double* __restrict__ Qd, int64_t n, int K, int KT, uint64_t seed) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t key = tpg_mix64(seed ^ tpg_mix64((uint64_t)i));
-  double s = 0;
-  for (int k = 0; k < K; k++) s += admix_u(tpg_mix64(key ^ tpg_mix64((uint64_t)k)));
-  for (int k = 0; k < KT; k++) Qd[i * KT + k] = k < K ? admix_u(tpg_mix64(key ^ tpg_mix64((uint64_t)k))) / s : 0.0;
-}
-
+// ---- start, validation (the frequencies; admix_common.h has Q's) ------------------------------------------------------
 __global__ void admix_seed_f_kernel(double* __restrict__ Fd, int64_t m, int K, int KT, uint64_t seed) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
   const uint64_t key = tpg_mix64((seed ^ ADM_F_SALT) ^ tpg_mix64((uint64_t)j));
   for (int k = 0; k < KT; k++) Fd[j * KT + k] = k < K ? 0.1 + 0.8 * admix_u(tpg_mix64(key ^ tpg_mix64((uint64_t)k))) : 0.5;
-}
-
-// q0 (n x K column-major) -> Qd, each row divided by its sum (ascending k); normalise = false: as given (tpg_admix_loglik).
-// bit 0 of *flag: an entry that is not finite or not positive
-__global__ void admix_load_q_kernel(const double* __restrict__ q0, double* __restrict__ Qd, int64_t n, int K, int KT, bool normalise,
-                                    int32_t* __restrict__ flag) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = 0;
-  bool bad = false;
-  for (int k = 0; k < K; k++) {
-    const double x = q0[i + (int64_t)k * n];
-    bad |= !(admix_finite(x) && x > 0.0);
-    s += x;
-  }
-  if (normalise && bad) atomicOr(flag, 1);
-  for (int k = 0; k < KT; k++) {
-    const double x = k < K ? q0[i + (int64_t)k * n] : 0.0;
-    Qd[i * KT + k] = normalise && k < K ? x / s : x;
-  }
 }
 
 // f0 (m x K column-major) -> Fd, clamped; clamp = false: as given.  bit 1 of *flag: an entry that is not finite
@@ -94,45 +47,6 @@ __global__ void admix_load_f_kernel(const double* __restrict__ f0, double* __res
     Fd[j * KT + k] = x;
   }
   if (clamp && bad) atomicOr(flag, 2);
-}
-
-// rows x K column-major out of the padded state
-__global__ void admix_store_kernel(const double* __restrict__ Xd, int64_t rows, int K, int KT, double* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= rows * K) return;
-  const int64_t i = idx % rows, k = idx / rows;
-  out[idx] = Xd[i * KT + k];
-}
-
-// ---- the two sweeps ----------------------------------------------------------------------------------------------------
-// rows 128 b .. 128 b + 127 of a padded state (rows beyond `rows`: `fill`) into LDS, contiguous 8-byte loads
-template <int KT>
-__device__ __forceinline__ void admix_stage(double* __restrict__ stage, const double* __restrict__ Xd, int64_t b, int64_t rows,
-                                            double fill) {
-  const int64_t i0 = b * 128;
-  for (int idx = threadIdx.x; idx < 128 * KT; idx += 256) stage[idx] = i0 + idx / KT < rows ? Xd[i0 * KT + idx] : fill;
-}
-
-// the waves of a workgroup in order: x[] of lanes 0 .. 31 of wave 0 becomes ((w0 + w1) + w2) + w3, cnt likewise.  LDS: red holds
-// NV x 32 doubles, value-major (lane r at red[v * 32 + r]: conflict-free)
-template <int NV>
-__device__ __forceinline__ void admix_wave_order_sum(double (&x)[NV], int& cnt, double* __restrict__ red, int* __restrict__ cnts, int w,
-                                                     int r, int h) {
-  __syncthreads();  // the staging area is free
-  for (int t = 1; t < 4; t++) {
-    if (w == t && h == 0) {
-#pragma unroll
-      for (int v = 0; v < NV; v++) red[v * 32 + r] = x[v];
-      cnts[r] = cnt;
-    }
-    __syncthreads();
-    if (w == 0 && h == 0) {
-#pragma unroll
-      for (int v = 0; v < NV; v++) x[v] += red[v * 32 + r];
-      cnt += cnts[r];
-    }
-    __syncthreads();
-  }
 }
 
 // F sweep: one workgroup per tile of 32 loci.  UPD: Fn receives f' (Fn != Fd); ll_part[lt] = the tile's share of l(Qd, Fd)
@@ -279,17 +193,6 @@ __global__ void admix_q_combine_kernel(const double* __restrict__ part, const in
     if (t > 0) q = (q / (2.0 * (double)t)) * s;
   }
   Qn[idx] = q;
-}
-
-// the tiles' shares of the likelihood: thread t adds the tiles t, t + 256, ...; butterfly; the four waves in order
-__global__ __launch_bounds__(256) void admix_ll_sum_kernel(const double* __restrict__ ll_part, int64_t ntiles, double* __restrict__ out) {
-  __shared__ double wll[4];
-  double s = 0.0;
-  for (int64_t t = threadIdx.x; t < ntiles; t += 256) s += ll_part[t];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) wll[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = ((wll[0] + wll[1]) + wll[2]) + wll[3];
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -496,8 +399,6 @@ extern "C" int tpg_admix_loglik(tpg_ctx* ctx, const tpg_view* v, int K, const do
 // BOTH planes at the same offset; the sum shape is that of admix_f_sweep_kernel<KT, false>; the two counts are integers (wave sum,
 // one integer atomic per wave).
 namespace {
-
-constexpr uint64_t ADM_CV_SALT = 0xC3C3C3C3C3C3C3C3ull;
 
 __host__ __device__ inline int admix_fold_of(uint64_t locus_key, uint64_t mi, int folds) {
   const uint64_t h = tpg_mix64(locus_key ^ mi);
