@@ -1182,6 +1182,107 @@ int tpg_autosvd_outliers(const void* r, int iter, int64_t* pos0, int64_t* idx0);
 int tpg_autosvd_intervals(const void* r, int iter, int64_t min_size, int64_t* first0, int64_t* last0, int64_t* count);
 void tpg_autosvd_free(void* r);
 
+/* ---- k-means on PCA scores (gt_cluster_pca, R/gt_cluster_pca.R:78-170 around stats::kmeans; stats::kmeans is Hartigan-Wong
+ * driven by R's random generator, neither part of the reference's sources nor reproducible, so what is computed is defined
+ * HERE: Lloyd's algorithm from seeded start rows, NOT PINNED BY THE REFERENCE) ------------------------------------------------
+ * Data.  X is n x d doubles, column-major (x_ij at X[i + j n]), host or device memory, every entry finite (else TPG_ENUMERIC).
+ * A run is (k, seed), 1 <= k <= n.  Its centres are a k x d column-major block (centre c, coordinate j at c + j k).
+ * Start.  With M = tpg_mix64 (see "simple imputation") and 64-bit unsigned arithmetic, h_i = M(seed ^ M(i)), i = 0 .. n - 1.
+ *   The start rows are the k rows with the smallest (h_i, i) in that order: centre c is the row with the c-th smallest key.
+ *   A pure function of (seed, n, k): tpg_kmeans_start (csrc/host/host_kmeans.h).  With centers0 the given centres are the start.
+ * Assign.  D(i,c) = sum_j (x_ij - c_j)^2 in the direct form: from +0, j ascending, t = x_ij - c_j (one rounding), then
+ *   D = fma(t, t, D).  Point i goes to the centre with the smallest D(i,c); on equal D the smaller c wins (a scan in ascending c
+ *   that replaces the best on strictly smaller only).
+ * Update.  A centre becomes the mean of its points: per coordinate the sum over its points in ASCENDING i, one after the other
+ *   from +0 (plain additions), then one division by (double)count.  A centre that owns no point keeps its position.
+ * Iterate.  Iteration t = 1, 2, ... is an assign, then an update with the new labels.  Before iteration 1 every label is -1, so
+ *   the first assign changes every label.  A run has converged when an assign changes no label (its update is then skipped: it
+ *   would reproduce the same centres bit for bit); n_iter counts assigns; a run that has not converged after max_iter assigns
+ *   stops after the update of iteration max_iter (converged = 0).  Either way the returned centres are the means of the returned
+ *   labels, except for centres that own no point; n_empty is the number of those under the returned labels.
+ * WSS.  e_i = D(i, label(i)) under the returned centres, formed as in Assign.  The n values are padded with +0 to a multiple of
+ *   TPG_KMEANS_TILE; a tile of TPG_KMEANS_TILE consecutive points is summed by halving (for s = TILE/2, TILE/4, .. 1:
+ *   e[l] += e[l + s] for l < s); the tile sums are added in ascending tile order from +0.  What compute_wss of
+ *   R/gt_cluster_pca.R recomputes, in a stated order.  tpg_kmeans_step returns this sum for its own assign: the smallest D(i,.)
+ *   of every point under C_in.
+ * Batch.  R runs in one call.  A run's result is a function of (X, n, d, k, seed or centers0, max_iter) alone: it does not depend
+ *   on the other runs of the batch, and two calls give the same bits.  There are no floating-point atomics; the integer atomics
+ *   count labels that changed and points per centre.  Runs that have stopped leave the list of live runs on the device and cost
+ *   nothing further; the host reads one integer (the number of live runs) per iteration.
+ * Centres pass through LDS in chunks of floor(TPG_KMEANS_CHUNK_DOUBLES / d) centres (csrc/kmeans.hip); the chunking does not
+ *   enter the arithmetic.
+ * Rounding bounds (u = 2^-53; eps = 2 u covers the second-order terms for every n, d inside the limits; A = max |x_ij|):
+ *   a computed D differs from the exact one of the same operands by at most (d + 2) eps D: d fused terms, all non-negative,
+ *     and one subtraction each;
+ *   a centre coordinate, a mean of at most n values of magnitude at most A in any order of addition:
+ *     bound_centre = n eps A;
+ *   wss under exact centres, n non-negative terms in any order: (n + d + 2) eps wss; centres off by delta move each e_i by at most
+ *     2 d (2 A) delta + d delta^2, so with delta = bound_centre
+ *     bound_wss = (n + d + 2) eps wss + n d (4 A + bound_centre) bound_centre.
+ *   Two evaluations (the device's and a restatement's) of the same labels differ by at most twice these.
+ * Limits.  1 <= n <= TPG_KMEANS_MAX_N, 1 <= d <= TPG_KMEANS_MAX_D, 1 <= k <= min(n, TPG_KMEANS_MAX_K), 1 <= R <=
+ *   TPG_KMEANS_MAX_RUNS, max_iter >= 1; outside them TPG_EINVAL.  After an error every output is untouched.
+ * Out of scope: Ward clustering (method = "ward" of the reference), other starts (k-means++), k-means inside tpg_stream_* /
+ *   tpg_multi_*. */
+#define TPG_KMEANS_MAX_N 16777216
+#define TPG_KMEANS_MAX_D 64
+#define TPG_KMEANS_MAX_K 1024
+#define TPG_KMEANS_MAX_RUNS 65535
+#define TPG_KMEANS_TILE 256
+#define TPG_KMEANS_CHUNK_DOUBLES 4096
+int64_t tpg_kmeans_chunk_doubles(void); /* TPG_KMEANS_CHUNK_DOUBLES of the library as built */
+/* host only: idx[k] = the start rows (0-based) */
+int tpg_kmeans_start(uint64_t seed, int64_t n, int k, int32_t* idx);
+/* one assign and one update from C_in (k x d): labels[n] (0-based), C_out (k x d, may be NULL), counts[k] (may be NULL) and wss
+ * (one double, the value under C_in and the new labels, may be NULL); every pointer host or device memory */
+int tpg_kmeans_step(tpg_ctx* ctx, const double* X, int64_t n, int d, int k, const double* C_in, int32_t* labels, double* C_out,
+                    int32_t* counts, double* wss);
+/* R runs.  k[R] and seed[R] (the seeds' 64 bits, read as unsigned); centers0 NULL or the start centres of every run, run r's
+ * k_r x d block at offset d (k_0 + .. + k_{r-1}); labels n x R column-major int32 (0-based); centers (may be NULL) laid out as
+ * centers0; wss, n_iter, converged, n_empty: R values each, any may be NULL.  Every pointer host or device memory. */
+int tpg_kmeans_batch(tpg_ctx* ctx, const double* X, int64_t n, int d, int R, const int32_t* k, const int64_t* seed, int max_iter,
+                     const double* centers0, int32_t* labels, double* centers, double* wss, int32_t* n_iter, int32_t* converged,
+                     int32_t* n_empty);
+
+/* ---- DAPC (gt_dapc, R/gt_dapc.R:137-255 around MASS::lda(XU, pop, tol = 1e-30) and predict(); MASS is not among the
+ * reference's sources, so the discriminant analysis is defined HERE, RECALLED FROM MASS, NOT PINNED) ---------------------------
+ * X is n x d column-major (the first n_pca PCA scores), grp0[n] the 0-based group in [0, G).
+ *   n_g = the group count, pi_g = n_g / n, mu_g = the group mean, mu = sum_g pi_g mu_g (g ascending).
+ *   W = (1 / (n - G)) sum_i (x_i - mu_g(i)) (x_i - mu_g(i))',   B = (1 / (G - 1)) sum_g n_g (mu_g - mu) (mu_g - mu)'.
+ *   W = R'R (Cholesky, R upper); a pivot R_jj^2 <= 2^-40 T_jj, T_jj = sum_i (x_ij - mu_j)^2 / (n - 1) the total variance of the
+ *   variable -- a variable that is constant within the groups up to rounding, or a linear combination of the others there,
+ *   where MASS stops -- is TPG_ENUMERIC.  M = R^-T B R^-1 = E diag(lambda) E' (the symmetric
+ *   eigen-decomposition of csrc/host/host_eig.h, lambda descending).  scaling S = R^-1 E, so S'WS = I and S'BS = diag(lambda);
+ *   svd = sqrt(max(lambda, 0)).  L = #{svd^2 > 1e-10} among the first min(d, G - 1) (R/gt_dapc.R:189); S, svd and eig keep L
+ *   columns.
+ *   Sign (this project's choice; MASS fixes none): the entry of largest magnitude of each column of S is positive, on equal
+ *   magnitudes the smaller row decides.
+ *   n_da = min(asked, G - 1, d, L) (at least 1, else TPG_ENUMERIC: no discriminant function separates the groups).
+ *   ind.coord = (X - 1 mu') S[:, :n_da];  grp.coord = its group means;  m_g = (mu_g - mu)' S[:, :n_da].
+ *   posterior: q_ig = 0.5 ||z_i - m_g||^2 - ln pi_g over the n_da coordinates, p_ig = exp(-(q_ig - min_g q_ig)) / (the sum of
+ *   these over g, g ascending);  assign_i = the g of smallest q_ig, on a tie the smaller g.
+ *   eig = svd^2 (all L);  loadings = S[:, :n_da].
+ * var of gt_dapc is sum d[:n_pca] / sum d over the singular values d of the PCA object -- of d, not of d^2, R/gt_dapc.R:182
+ *   verbatim -- and is formed in Python.
+ * Errors: G < 2, an empty group, n <= G, d outside [1, 64], a label outside [0, G): TPG_EINVAL.  A non-finite x: TPG_ENUMERIC.
+ * Per-locus loadings (R/gt_dapc.R:246-255): var_load = V[:, :n_pca] loadings (m x n_da; each entry a sum of fused terms in
+ *   ascending PCA index from +0);  var_contr(j,a) = var_load(j,a)^2 / c_a with c_a = the column's sum of squares, formed as the
+ *   WSS above (tiles of TPG_KMEANS_TILE rows by halving, tiles in ascending order);  c_a < 1e-12: the column is all zeros.
+ *   Rounding (eps as above): var_load(j,a) lies within E = (n_pca + 1) eps sum_p |V_jp| |l_pa| of the exact product; its square
+ *   within q = 2 |var_load| E + E^2; c_a within Ec = sum_j q_j + (m + 2) eps c_a; var_contr within q / c_a + var_contr Ec / c_a +
+ *   2 eps var_contr.
+ * Out of scope: predict() on new individuals, cross-validation of n_pca (xvalDapc), priors other than the group proportions. */
+/* host only.  With Lmax = min(d, G - 1): prior[G], means G x d, scaling d x Lmax, svd[Lmax] (columns / entries beyond *n_lda are
+ * 0), ind_coord n x Lmax and grp_coord G x Lmax (the first *n_da_out columns are written), posterior n x G, assign[n] (0-based);
+ * all column-major host memory; mu_out[d] may be NULL */
+int tpg_lda(const double* X, int64_t n, int d, const int32_t* grp0, int G, int n_da, double* prior, double* means, double* mu_out,
+            double* scaling, double* svd, int32_t* n_lda, int32_t* n_da_out, double* ind_coord, double* grp_coord,
+            double* posterior, int32_t* assign);
+/* V: m rows, leading dimension ldv >= m, at least n_pca columns; loadings n_pca x n_da; var_load and var_contr m x n_da; all
+ * column-major, host or device memory.  1 <= n_pca <= 64, 1 <= n_da <= 64 */
+int tpg_dapc_var_contr(tpg_ctx* ctx, const double* V, int64_t m, int64_t ldv, int n_pca, const double* loadings, int n_da,
+                       double* var_load, double* var_contr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1488,6 +1488,88 @@ SEXP _tidypopgen_tpg_snmf(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP alpha,
   return out;
 }
 
+/* ---- clusters on PCA scores ------------------------------------------------------------------------------------------ */
+
+#pragma weak tpg_kmeans_batch
+
+static uint64_t mix64(uint64_t x) { /* tpg_mix64 of include/tpg.h "simple imputation" */
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+/* tpg_cluster_pca(scores, k, n_start, n_iter, seed): the loop over k of R/gt_cluster_pca.R:137-155 (stats::kmeans with nstart and
+ * compute_wss) as ONE call of the batched k-means of include/tpg.h "k-means on PCA scores".  scores = the n x n_pca numeric matrix
+ * of PCA scores; k = the numbers of clusters to try (whole numbers in [1, n]); n_start, n_iter positive integers; seed = a double
+ * vector of length 1 holding a whole number in [0, 2^53].  Every k > 1 gets n_start runs from the seeds M(seed ^ M((k << 32) + t)),
+ * k = 1 one run; per k the run of smallest WSS is returned, on a tie the smaller t.
+ * -> list(groups: n x length(k) integer, 1-based, WSS: length(k), n_iter, converged, n_empty: of the run returned) */
+SEXP _tidypopgen_tpg_cluster_pca(SEXP scores, SEXP k, SEXP n_start, SEXP n_iter, SEXP seed) {
+  TPG_NEEDS(tpg_kmeans_batch);
+  SEXP dim = Rf_getAttrib(scores, R_DimSymbol);
+  if ((TYPEOF(scores) != REALSXP && TYPEOF(scores) != INTSXP) || Rf_length(dim) != 2)
+    Rf_error("tidypopgen (GPU): scores must be a numeric matrix");
+  const int n = INTEGER(dim)[0], d = INTEGER(dim)[1];
+  if (n < 1 || d < 1) Rf_error("tidypopgen (GPU): scores must have at least one row and one column");
+  if ((TYPEOF(k) != REALSXP && TYPEOF(k) != INTSXP) || XLENGTH(k) < 1 || XLENGTH(k) > INT_MAX)
+    Rf_error("tidypopgen (GPU): k must be a vector of whole numbers");
+  const int ns = Rf_asInteger(n_start), mi = Rf_asInteger(n_iter);
+  if (ns == NA_INTEGER || ns < 1) Rf_error("tidypopgen (GPU): n_start must be a positive integer");
+  if (mi == NA_INTEGER || mi < 1) Rf_error("tidypopgen (GPU): n_iter must be a positive integer");
+  if (TYPEOF(seed) != REALSXP || XLENGTH(seed) != 1) Rf_error("tidypopgen (GPU): seed must be a double vector of length 1");
+  const double sd = REAL(seed)[0];
+  if (!(sd >= 0 && sd <= 9007199254740992.0) || sd != floor(sd))
+    Rf_error("tidypopgen (GPU): seed must be a whole number in [0, 2^53]");
+  SEXP xs = PROTECT(as_real(scores)), kr = PROTECT(as_real(k));
+  const int nk = (int)XLENGTH(kr);
+  int64_t R = 0;
+  for (int a = 0; a < nk; a++) {
+    const double kk = REAL(kr)[a];
+    if (!(kk >= 1 && kk <= n) || kk != floor(kk)) Rf_error("tidypopgen (GPU): every k must be a whole number in [1, nrow(scores)]");
+    R += kk == 1 ? 1 : ns;
+  }
+  if (R > TPG_KMEANS_MAX_RUNS) Rf_error("tidypopgen (GPU): %lld runs in one call, at most %d", (long long)R, TPG_KMEANS_MAX_RUNS);
+  SEXP vals[5];
+  vals[0] = PROTECT(Rf_allocMatrix(INTSXP, n, nk));
+  vals[1] = PROTECT(Rf_allocVector(REALSXP, nk));
+  vals[2] = PROTECT(Rf_allocVector(INTSXP, nk));
+  vals[3] = PROTECT(Rf_allocVector(LGLSXP, nk));
+  vals[4] = PROTECT(Rf_allocVector(INTSXP, nk));
+  static const char* names[5] = {"groups", "WSS", "n_iter", "converged", "n_empty"};
+  SEXP out = PROTECT(named_list(5, names, vals));
+  /* R's transient storage: freed when .Call returns or errors */
+  int32_t* rk = (int32_t*)R_alloc((size_t)R, sizeof(int32_t));
+  int64_t* rs = (int64_t*)R_alloc((size_t)R, sizeof(int64_t));
+  int32_t* lab = (int32_t*)R_alloc((size_t)R * (size_t)n, sizeof(int32_t));
+  double* wss = (double*)R_alloc((size_t)R, sizeof(double));
+  int32_t* st = (int32_t*)R_alloc((size_t)3 * (size_t)R, sizeof(int32_t));
+  int64_t r = 0;
+  for (int a = 0; a < nk; a++) {
+    const uint64_t kk = (uint64_t)REAL(kr)[a];
+    for (int t = 0; t < (kk == 1 ? 1 : ns); t++, r++) {
+      rk[r] = (int32_t)kk;
+      rs[r] = (int64_t)mix64((uint64_t)sd ^ mix64((kk << 32) + (uint64_t)t));
+    }
+  }
+  TPG_R(tpg_kmeans_batch(ctx(), REAL(xs), n, d, (int)R, rk, rs, mi, NULL, lab, NULL, wss, st, st + R, st + 2 * R));
+  r = 0;
+  for (int a = 0; a < nk; a++) {
+    const int cnt = rk[r] == 1 ? 1 : ns;
+    int64_t best = r;
+    for (int t = 1; t < cnt; t++)
+      if (wss[r + t] < wss[best]) best = r + t;
+    for (int i = 0; i < n; i++) INTEGER(vals[0])[(size_t)a * (size_t)n + (size_t)i] = lab[(size_t)best * (size_t)n + (size_t)i] + 1;
+    REAL(vals[1])[a] = wss[best];
+    INTEGER(vals[2])[a] = st[best];
+    LOGICAL(vals[3])[a] = st[R + best] != 0;
+    INTEGER(vals[4])[a] = st[2 * R + best];
+    r += cnt;
+  }
+  UNPROTECT(8);
+  return out;
+}
+
 /* ---- autoSVD ------------------------------------------------------------------------------------------------------ */
 
 #pragma weak tpg_pca_auto_svd
@@ -1691,11 +1773,16 @@ const R_CallMethodDef tpg_rshim_entries_snmf[] = {
     {"_tidypopgen_tpg_snmf", (DL_FUNC)&_tidypopgen_tpg_snmf, 10},
     {NULL, NULL, 0}};
 
+/* Clusters on PCA scores, in a table of its own: the reference loops over stats::kmeans in R, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_cluster[] = {
+    {"_tidypopgen_tpg_cluster_pca", (DL_FUNC)&_tidypopgen_tpg_cluster_pca, 5},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the twelve tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the thirteen tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1707,7 +1794,8 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_admix_cv) / sizeof(tpg_rshim_entries_admix_cv[0]) +
                              sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0]) +
                              sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0]) +
-                             sizeof(tpg_rshim_entries_snmf) / sizeof(tpg_rshim_entries_snmf[0])];
+                             sizeof(tpg_rshim_entries_snmf) / sizeof(tpg_rshim_entries_snmf[0]) +
+                             sizeof(tpg_rshim_entries_cluster) / sizeof(tpg_rshim_entries_cluster[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1721,6 +1809,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_pcadapt; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_autosvd; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_snmf; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_cluster; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

@@ -197,6 +197,34 @@ gt_snmf_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstat
   adm_list
 }
 
+# Clusters on PCA scores on the GPU (R/gt_cluster_pca.R:75-177; include/tpg.h "k-means on PCA scores" is the definition: Lloyd's
+# algorithm from seeded start rows in the place of stats::kmeans, every run of every k in one batch).  x: a gt_pca object;
+# seed: one whole number.  Returns the reference's gt_cluster_pca object (clusters$method, n_pca, k, WSS, AIC, BIC, groups), with
+# n_iter, converged and n_empty of the winning runs beside them, so gt_cluster_pca_best_k() and gt_dapc() run on it unchanged.
+# method = "ward" has no counterpart.
+gt_cluster_pca_gpu <- function(x, n_pca = NULL, k_clusters = c(1, round(nrow(x$u) / 10)), n_iter = 1e5, n_start = 10, seed = 0) {
+  if (is.null(x) || !inherits(x, "gt_pca")) stop("'x' should be a 'gt_pca' object")
+  n <- nrow(x$u)
+  if (is.null(n_pca)) n_pca <- length(x$d)
+  if (length(k_clusters) == 1) {
+    nb_clust <- k_clusters
+  } else if (length(k_clusters) == 2) {
+    nb_clust <- k_clusters[1]:k_clusters[2]
+  } else {
+    stop("'k_clusters' should be either a single value, or the minimum and maximum to be tested")
+  }
+  x_scores <- sweep(x$u, 2, x$d, "*")[, seq_len(n_pca), drop = FALSE]
+  res <- .Call(`_tidypopgen_tpg_cluster_pca`, x_scores, as.numeric(nb_clust), as.integer(n_start), as.integer(n_iter),
+               as.numeric(seed))
+  groups <- lapply(seq_along(nb_clust), function(i) stats::setNames(res$groups[, i], rownames(x$u)))
+  names(groups) <- nb_clust
+  x$clusters <- list(method = "kmeans", n_pca = n_pca, k = nb_clust, WSS = res$WSS,
+                     AIC = n * log(res$WSS / n) + 2 * nb_clust, BIC = n * log(res$WSS / n) + log(n) * nb_clust,
+                     groups = groups, n_iter = res$n_iter, converged = res$converged, n_empty = res$n_empty)
+  class(x) <- c("gt_cluster_pca", class(x))
+  x
+}
+
 # PCA-based genome scan on the GPU (R/gt_pcadapt.R:44-86 around bigsnpr::snp_pcadapt; include/tpg.h "pcadapt" is the definition).
 # U.row: the first k columns of the PCA's u for the rows ind.row.  Returns the reference's object: a data.frame(score) of class
 # "mhtest" whose `predict` attribute gives log10 p-values from the chi-square with k degrees of freedom; dist, the device's own

@@ -320,6 +320,14 @@ PROTOTYPES = {
     "tpg_autosvd_outliers": (ci, [vp, ci, vp, vp]),
     "tpg_autosvd_intervals": (ci, [vp, ci, i64, vp, vp, vp]),
     "tpg_autosvd_free": (None, [vp]),
+    # ---- k-means on PCA scores
+    "tpg_kmeans_chunk_doubles": (i64, []),
+    "tpg_kmeans_start": (ci, [u64, i64, ci, vp]),
+    "tpg_kmeans_step": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp, vp]),
+    "tpg_kmeans_batch": (ci, [vp, vp, i64, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+    # ---- DAPC
+    "tpg_lda": (ci, [vp, i64, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_dapc_var_contr": (ci, [vp, vp, i64, i64, ci, vp, ci, vp, vp]),
 }
 
 for _name, (_restype, _argtypes) in PROTOTYPES.items():

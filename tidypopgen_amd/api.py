@@ -1928,6 +1928,314 @@ def gt_snmf(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, alpha: 
     return out
 
 
+# ---------------------------------------------------------------------------
+# k-means on PCA scores and DAPC (include/tpg.h "k-means on PCA scores", "DAPC")
+
+# doubles of centre coordinates one LDS chunk of the assign kernel holds (the tests put k * d around it)
+KMEANS_CHUNK_DOUBLES = int(lib.tpg_kmeans_chunk_doubles())
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x: int) -> int:
+    """tpg_mix64 on a Python int (the splitmix64 finaliser)"""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def kmeans_run_seed(seed: int, k: int, t: int) -> int:
+    """the seed of start t of gt_cluster_pca's runs at k clusters: M(seed ^ M((k << 32) + t))"""
+    return _mix64((int(seed) & _M64) ^ _mix64(((int(k) << 32) + int(t)) & _M64))
+
+
+def _scores(X):
+    x = np.asfortranarray(X, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("X must be a matrix of n points x d coordinates")
+    return x
+
+
+def kmeans_start(seed: int, n: int, k: int) -> np.ndarray:
+    """tpg_kmeans_start: the k start rows (0-based) of a run, a pure function of (seed, n, k)"""
+    idx = np.zeros(max(int(k), 1), dtype=np.int32)
+    check(lib.tpg_kmeans_start(int(seed) & _M64, int(n), int(k), _ptr(idx)))
+    return idx[:k]
+
+
+def kmeans_step(X, centers, ctx: Optional[Context] = None) -> dict:
+    """tpg_kmeans_step: one assign and one update from the given centres (k x d) -> dict(labels (0-based), centers, counts, wss:
+    the sum of the smallest squared distances under the GIVEN centres)"""
+    ctx = ctx or default_context()
+    x, c = _scores(X), _scores(centers)
+    n, d = x.shape
+    k = c.shape[0]
+    if c.shape[1] != d:
+        raise ValueError(f"centers must be k x {d}, not {c.shape}")
+    labels, counts = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(k, 1), dtype=np.int32)
+    cn, wss = np.zeros((max(k, 1), max(d, 1)), order="F"), C.c_double()
+    check(lib.tpg_kmeans_step(ctx.h, _ptr(x), n, d, k, _ptr(c), _ptr(labels), _ptr(cn), _ptr(counts), C.byref(wss)))
+    return dict(labels=labels, centers=cn, counts=counts, wss=wss.value)
+
+
+def kmeans_batch(X, k, seed=None, max_iter: int = 100000, centers0=None, return_centers: bool = True,
+                 ctx: Optional[Context] = None) -> dict:
+    """tpg_kmeans_batch: len(k) independent Lloyd runs over the same points in one call.  k and seed: one entry per run;
+    centers0 (instead of seed): a list of k_r x d start centres.  -> dict(labels (n x R, 0-based), centers (list of k_r x d), wss,
+    n_iter, converged, n_empty)"""
+    ctx = ctx or default_context()
+    x = _scores(X)
+    n, d = x.shape
+    ks = np.ascontiguousarray(np.atleast_1d(k), dtype=np.int32)
+    R = len(ks)
+    if R < 1:
+        raise ValueError("at least one run is needed")
+    if (seed is None) == (centers0 is None):
+        raise ValueError("give either one seed per run or the start centres")
+    seeds = c0 = None
+    if seed is not None:
+        sd = [int(s) & _M64 for s in np.atleast_1d(np.asarray(seed, dtype=object))]
+        if len(sd) != R:
+            raise ValueError(f"{len(sd)} seeds for {R} runs")
+        seeds = np.array(sd, dtype=np.uint64).view(np.int64)
+    else:
+        if len(centers0) != R:
+            raise ValueError(f"{len(centers0)} start blocks for {R} runs")
+        blocks = [_scores(c) for c in centers0]
+        for kk, b in zip(ks, blocks):
+            if b.shape != (kk, d):
+                raise ValueError(f"a start block of shape {b.shape} for k = {kk}, d = {d}")
+        c0 = np.concatenate([b.ravel(order="F") for b in blocks])
+    ktot = int(np.maximum(ks, 0).sum())
+    labels = np.zeros((max(n, 1), R), dtype=np.int32, order="F")
+    cen = np.zeros(max(ktot * d, 1)) if return_centers else None
+    wss, n_iter = np.zeros(R), np.zeros(R, dtype=np.int32)
+    conv, n_empty = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32)
+    check(lib.tpg_kmeans_batch(ctx.h, _ptr(x), n, d, R, _ptr(ks), _ptr(seeds), int(max_iter), _ptr(c0), _ptr(labels), _ptr(cen),
+                               _ptr(wss), _ptr(n_iter), _ptr(conv), _ptr(n_empty)))
+    out = dict(labels=labels[:n], wss=wss, n_iter=n_iter, converged=conv.astype(bool), n_empty=n_empty)
+    if return_centers:
+        off = np.concatenate([[0], np.cumsum(ks.astype(np.int64))]) * d
+        out["centers"] = [cen[off[r]:off[r + 1]].reshape((int(ks[r]), d), order="F") for r in range(R)]
+    return out
+
+
+def gt_cluster_pca(pca: dict, n_pca: Optional[int] = None, k_clusters=None, n_iter: int = 100000, n_start: int = 10, seed: int = 0,
+                   method: str = "kmeans", ctx: Optional[Context] = None) -> dict:
+    """R/gt_cluster_pca.R:75-177 with the Lloyd k-means of include/tpg.h in place of stats::kmeans: scores = u d (the first n_pca
+    columns); every k of k_clusters (one value, or (min, max); default (1, round(n / 10))) gets n_start runs from the seeds
+    kmeans_run_seed(seed, k, t), ALL runs of ALL k in one tpg_kmeans_batch call; per k the run of smallest WSS wins (on a tie the
+    smaller t).  k = 1 is one run (every start gives the column means).  -> the pca dict plus clusters = dict(method, n_pca, k,
+    WSS, AIC, BIC, groups ({k: labels, 1-based as R's}), n_iter, converged, n_empty)."""
+    if method == "ward":
+        raise NotImplementedError("method = 'ward' is out of scope (DESIGN.md section 10): hierarchical clustering is not built")
+    if method != "kmeans":
+        raise ValueError("'method' should be one of 'kmeans', 'ward'")
+    u, dd = np.asarray(pca["u"], dtype=np.float64), np.asarray(pca["d"], dtype=np.float64)
+    n = u.shape[0]
+    n_pca = len(dd) if n_pca is None else int(n_pca)
+    if not 1 <= n_pca <= len(dd):
+        raise ValueError(f"n_pca = {n_pca} outside [1, {len(dd)}]")
+    kc = [int(round(n / 10))] if k_clusters is None else [int(x) for x in np.atleast_1d(k_clusters)]
+    if k_clusters is None:
+        kc = [1, max(kc[0], 1)]
+    if len(kc) == 1:
+        ks = kc
+    elif len(kc) == 2:
+        ks = list(range(kc[0], kc[1] + 1))
+    else:
+        raise ValueError("'k_clusters' should be either a single value, or the minimum and maximum to be tested")
+    if not ks or ks[0] < 1:
+        raise ValueError("'k_clusters' should name at least one k >= 1")
+    n_start = int(n_start)
+    if n_start < 1:
+        raise ValueError("n_start must be at least 1")
+    scores = np.asfortranarray((u * dd[None, :])[:, :n_pca])
+    run_k, run_seed = [], []
+    for kk in ks:
+        for t in range(1 if kk == 1 else n_start):
+            run_k.append(kk)
+            run_seed.append(kmeans_run_seed(seed, kk, t))
+    r = kmeans_batch(scores, run_k, run_seed, max_iter=int(n_iter), return_centers=False, ctx=ctx)
+    wss, groups, iters, conv, empty = [], {}, [], [], []
+    at = 0
+    for kk in ks:
+        cnt = 1 if kk == 1 else n_start
+        best = at + int(np.argmin(r["wss"][at:at + cnt]))  # (the first minimum: the smaller t)
+        wss.append(float(r["wss"][best]))
+        groups[kk] = r["labels"][:, best].astype(np.int32) + 1
+        iters.append(int(r["n_iter"][best]))
+        conv.append(bool(r["converged"][best]))
+        empty.append(int(r["n_empty"][best]))
+        at += cnt
+    wss, kv = np.array(wss), np.array(ks, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        base = n * np.log(wss / n)
+    out = dict(pca)
+    out["clusters"] = dict(method=method, n_pca=n_pca, k=list(ks), WSS=wss, AIC=base + 2 * kv, BIC=base + math.log(n) * kv,
+                           groups=groups, n_iter=iters, converged=conv, n_empty=empty)
+    return out
+
+
+def _ward_d_two_groups(x: np.ndarray) -> np.ndarray:
+    """cutree(hclust(dist(x), method = "ward.D"), k = 2) of scalars: agglomeration by the Lance-Williams update of Ward's
+    criterion on the plain distances until two clusters are left; the closest pair merges, on a tie the first pair in the order
+    (i, j), i < j, i ascending then j.  -> 1 / 2 per value, group 1 the one that holds the first value"""
+    L = len(x)
+    if L < 2:
+        raise ValueError("the series is too short to be cut in two groups")
+    D = np.abs(x[:, None] - x[None, :]).astype(np.float64)
+    size, alive, member = np.ones(L), list(range(L)), [[i] for i in range(L)]
+    while len(alive) > 2:
+        bi = bj = -1
+        best = np.inf
+        for a in range(len(alive)):
+            for b in range(a + 1, len(alive)):
+                if D[alive[a], alive[b]] < best:
+                    best, bi, bj = D[alive[a], alive[b]], alive[a], alive[b]
+        for kx in alive:
+            if kx != bi and kx != bj:
+                tot = size[bi] + size[bj] + size[kx]
+                D[bi, kx] = D[kx, bi] = ((size[bi] + size[kx]) * D[bi, kx] + (size[bj] + size[kx]) * D[bj, kx] - size[kx] * D[bi, bj]) / tot
+        size[bi] += size[bj]
+        member[bi] += member[bj]
+        alive.remove(bj)
+    out = np.zeros(L, dtype=np.int64)
+    first = alive[0] if 0 in member[alive[0]] else alive[1]
+    for a in alive:
+        out[member[a]] = 1 if a == first else 2
+    return out
+
+
+def gt_cluster_pca_best_k(x: dict, stat: str = "BIC", criterion: str = "diffNgroup") -> dict:
+    """R/gt_cluster_pca_best_k.R:102-166, the five criteria with their quirks: best_k is the 1-based POSITION in clusters["k"] as
+    in R (the k itself when the range starts at 1); "goodfit" subtracts 1 from it; "goesup" / "smoothNgoesup" on a series that
+    never goes up is an error.  -> x plus best_k"""
+    if "clusters" not in x:
+        raise ValueError("'x' should be a 'gt_cluster_pca' object generated with 'gt_cluster_pca()'")
+    if stat not in ("BIC", "AIC", "WSS"):
+        raise ValueError("'stat' should be one of 'BIC', 'AIC', 'WSS'")
+    s = np.asarray(x["clusters"][stat], dtype=np.float64)
+
+    def first_rise(v):
+        up = np.nonzero(np.diff(v) > 0)[0]
+        if len(up) == 0:
+            raise ValueError(f"{stat} never goes up over the k that were tested")
+        return int(up[0]) + 1
+
+    if criterion == "min":
+        n_clust = int(np.argmin(s)) + 1
+    elif criterion == "goesup":
+        n_clust = first_rise(s)
+    elif criterion == "goodfit":
+        below = np.nonzero(s < s.min() + 0.1 * (s.max() - s.min()))[0]
+        if len(below) == 0:
+            raise ValueError(f"{stat} is constant over the k that were tested")
+        n_clust = int(below[0]) + 1 - 1
+    elif criterion == "diffNgroup":
+        df = np.diff(s)
+        grp = _ward_d_two_groups(df)
+        means = [df[grp == 1].mean(), df[grp == 2].mean()]
+        good = 1 if means[0] <= means[1] else 2
+        n_clust = int(np.nonzero(grp == good)[0].max()) + 1 + 1
+    elif criterion == "smoothNgoesup":
+        if len(s) < 3:
+            raise ValueError("the series is too short to be smoothed")
+        t = s.copy()
+        t[1:-1] = (s[:-2] + s[1:-1] + s[2:]) / 3.0
+        n_clust = first_rise(t)
+    else:
+        raise ValueError("'criterion' should be one of 'diffNgroup', 'min', 'goesup', 'smoothNgoesup', 'goodfit'")
+    out = dict(x)
+    out["best_k"] = n_clust
+    return out
+
+
+def lda(X, grp, n_da: Optional[int] = None) -> dict:
+    """tpg_lda (host only): the discriminant analysis of include/tpg.h "DAPC" of n x d scores by the 0-based groups grp ->
+    dict(prior, means (G x d), mu, scaling (d x L), svd (L), n_da, ind_coord (n x n_da), grp_coord (G x n_da), posterior (n x G),
+    assign (0-based))"""
+    x = _scores(X)
+    n, d = x.shape
+    g = np.ascontiguousarray(grp, dtype=np.int32)
+    if g.shape != (n,):
+        raise ValueError(f"grp must hold {n} labels")
+    G = int(g.max()) + 1 if n else 0
+    lmax = max(min(d, G - 1), 1)
+    prior, means, mu = np.zeros(max(G, 1)), np.zeros((max(G, 1), max(d, 1)), order="F"), np.zeros(max(d, 1))
+    scaling, svd = np.zeros((max(d, 1), lmax), order="F"), np.zeros(lmax)
+    ind, gc = np.zeros((max(n, 1), lmax), order="F"), np.zeros((max(G, 1), lmax), order="F")
+    post, assign = np.zeros((max(n, 1), max(G, 1)), order="F"), np.zeros(max(n, 1), dtype=np.int32)
+    L, nda = C.c_int32(), C.c_int32()
+    check(lib.tpg_lda(_ptr(x), n, d, _ptr(g), G, lmax if n_da is None else int(n_da), _ptr(prior), _ptr(means), _ptr(mu), _ptr(scaling),
+                      _ptr(svd), C.byref(L), C.byref(nda), _ptr(ind), _ptr(gc), _ptr(post), _ptr(assign)))
+    L, nda = L.value, nda.value
+    return dict(prior=prior, means=means, mu=mu, scaling=scaling[:, :L], svd=svd[:L], n_da=nda, ind_coord=ind[:, :nda],
+                grp_coord=gc[:, :nda], posterior=post, assign=assign)
+
+
+def dapc_var_contr(V, loadings, ctx: Optional[Context] = None) -> dict:
+    """tpg_dapc_var_contr: var_load = V loadings (V m x n_pca, loadings n_pca x n_da) and var_contr, its squares over the
+    column's sum of squares (a column whose sum is below 1e-12: zeros)"""
+    ctx = ctx or default_context()
+    v, ld = _scores(V), _scores(loadings)
+    m, n_pca = v.shape
+    if ld.shape[0] != n_pca:
+        raise ValueError(f"loadings must have {n_pca} rows, not {ld.shape[0]}")
+    n_da = ld.shape[1]
+    vl, vc = np.zeros((max(m, 1), max(n_da, 1)), order="F"), np.zeros((max(m, 1), max(n_da, 1)), order="F")
+    check(lib.tpg_dapc_var_contr(ctx.h, _ptr(v), m, m, n_pca, _ptr(ld), n_da, _ptr(vl), _ptr(vc)))
+    return dict(var_load=vl, var_contr=vc)
+
+
+def gt_dapc(x: dict, pop=None, n_pca: Optional[int] = None, n_da: Optional[int] = None, loadings_by_locus: bool = True,
+            ctx: Optional[Context] = None) -> dict:
+    """R/gt_dapc.R:122-260 with the discriminant analysis of include/tpg.h "DAPC" in place of MASS::lda / predict.  pop: None (the
+    groups of x["best_k"], a position in clusters["k"] as in R), a vector of n labels, or a number (that position in
+    clusters["k"]).  -> dict with the reference's names: n.pca, n.da, tab, grp (the labels), var, eig, loadings, means, ind.coord,
+    grp.coord, prior, posterior, assign (a label per individual) and, with loadings_by_locus, var.contr and var.load."""
+    if x.get("center") is None:
+        raise ValueError("'x' was run without centering; centering is necessary for 'gt_dapc'")
+    u, dd = np.asarray(x["u"], dtype=np.float64), np.asarray(x["d"], dtype=np.float64)
+    clustered = "clusters" in x
+    if pop is None:
+        if not clustered or x.get("best_k") is None:
+            raise ValueError("if 'pop' is not set, 'x' should be a 'gt_cluster_pca'")
+        pop = x["best_k"]
+    if np.ndim(pop) == 0:
+        if not (clustered and isinstance(pop, (int, np.integer))):
+            raise ValueError("x does not include pre-defined populations, and `pop' is not provided")
+        ks = x["clusters"]["k"]
+        if not 1 <= int(pop) <= len(ks):
+            raise ValueError(f"pop = {pop} is not a position in the k that were tested")
+        grp = np.asarray(x["clusters"]["groups"][ks[int(pop) - 1]])
+    else:
+        grp = np.asarray(pop)
+    if grp.shape != (u.shape[0],):
+        raise ValueError(f"pop must hold {u.shape[0]} labels")
+    levels, g0 = np.unique(grp, return_inverse=True)
+    n_pop = len(levels)
+    if n_pca is None:
+        n_pca = x["clusters"]["n_pca"] if clustered else len(dd)
+        if n_pca > n_pop:
+            n_pca = n_pop - 1
+    else:
+        n_pca = min(int(n_pca), u.shape[1])
+    if n_pca < 1:
+        raise ValueError("n_pca must be at least 1")
+    tab = np.asfortranarray((u * dd[None, :])[:, :n_pca])
+    r = lda(tab, g0, None if n_da is None else int(round(n_da)))
+    nda = r["n_da"]
+    res = {"n.pca": n_pca, "n.da": nda, "tab": tab, "grp": grp, "var": float(dd[:n_pca].sum() / dd.sum()), "eig": r["svd"] ** 2,
+           "loadings": np.asfortranarray(r["scaling"][:, :nda]), "means": r["means"], "ind.coord": r["ind_coord"],
+           "grp.coord": r["grp_coord"], "prior": r["prior"], "posterior": r["posterior"], "assign": levels[r["assign"]],
+           "levels": levels}
+    if loadings_by_locus:
+        vc = dapc_var_contr(np.asarray(x["v"])[:, :n_pca], res["loadings"], ctx=ctx)
+        res["var.contr"], res["var.load"] = vc["var_contr"], vc["var_load"]
+    return res
+
+
 def _pbs_triplets(ngroups):
     """utils::combn(levels, 3) order, with the Fst columns of (p1.p2, p1.p3, p2.p3) in combn(levels, 2) order"""
     pairs = combn2(ngroups)  # (2, P), 1-based
