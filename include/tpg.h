@@ -1022,7 +1022,15 @@ int tpg_pca_random_svd(tpg_ctx* ctx, const tpg_view* v, int k, double tol, doubl
  * tpg_pca_loadings the rows of v = Z'u/d that belong to the rank's loci (d = sqrt(lambda)). */
 /* K: BOTH triangles filled and bitwise symmetric (K[i + j n] == K[j + i n]; what tpg_pca_gram / tpg_pca_gram_add write): the
  * products K Q read K by rows or by columns, whichever is faster, so a matrix that is symmetric only to rounding, or has one
- * triangle filled, gives the eigenpairs of neither. */
+ * triangle filled, gives the eigenpairs of neither.
+ * Contract, for any scale of K from 2^-600 to 2^600 times unit size (residuals are taken relative to lambda_1 before they are
+ * squared): |K u_j - lambda_j u_j| <= 1e-12 lambda_1 on acceptance, lambda descending to that tolerance, U orthonormal.
+ * k at or above the rank r of K: the k - r trailing values are 0 +- 1e-9 lambda_1 and their vectors an orthonormal basis of a
+ * part of the null space, orthogonal to the leading ones; a repeated eigenvalue gets an orthonormal basis of (a part of) its
+ * eigenspace.  Beyond 52 components the batches after the first are projected against the vectors already found and accept
+ * relative to the first batch's lambda_1 (the residual of a later pair is taken inside the complement of the earlier vectors: in
+ * full it can reach sqrt(k) times the tolerance), so the same holds there -- except k = n on a SINGULAR matrix through that route
+ * (n > 52), which is not supported: ask for k < n, or for at most the rank. */
 int tpg_sym_eig_topk(tpg_ctx* ctx, const double* K, int64_t n, int k, double* lambda, double* U);
 int tpg_pca_loadings(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale,
                      const double* U, const double* d, int k, double* vload);

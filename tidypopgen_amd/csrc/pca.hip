@@ -1114,9 +1114,13 @@ __global__ __launch_bounds__(256) void tpg_right_mult_kernel(const double* __res
 // Rayleigh-Ritz rotation and residuals in one pass over the block: Y0 = A X (Ritz vectors), Y1 = Yk X (K times them,
 // Yk = K A) and, per workgroup of 32 rows, the column sums of (Y1 - Y0 diag(theta))^2 -- only the residual NORMS are
 // wanted, not the Gram matrix of the residuals; tpg_gram_reduce_kernel adds the partial sums in block order.
+// The residual is taken relative to lambda_1 BEFORE it is squared: times 2^-e1, e1 the binary exponent of the current
+// estimate of lambda_1 (an exact scaling, so the sums are those of the unscaled residuals times 2^(-2 e1) to the bit as long as
+// neither under- nor overflows).  Unscaled, the square of a residual of a matrix 2^-600 K is 0 -- every pair looked
+// converged -- and that of 2^600 K is +inf -- none ever did.
 __global__ __launch_bounds__(256) void tpg_ritz_kernel(const double* __restrict__ A, const double* __restrict__ Yk, int n,
                                                        int p, const double* __restrict__ X,
-                                                       const double* __restrict__ theta, double* __restrict__ Y0,
+                                                       const double* __restrict__ theta, int e1, double* __restrict__ Y0,
                                                        double* __restrict__ Y1, double* __restrict__ rpart) {
   __shared__ double xs[64 * 64];
   for (int idx = threadIdx.x; idx < p * p; idx += 256) xs[idx] = X[idx];
@@ -1145,7 +1149,7 @@ __global__ __launch_bounds__(256) void tpg_ritz_kernel(const double* __restrict_
     if (live && j < p) {
       Y0[row + (int64_t)j * n] = a0[c];
       Y1[row + (int64_t)j * n] = a1[c];
-      r = a1[c] - theta[j] * a0[c];
+      r = ldexp(a1[c] - theta[j] * a0[c], -e1);
       r *= r;
     }
 #pragma unroll
@@ -1235,15 +1239,15 @@ struct EigWork {
     TPG_HIP(tpg_fetch_small(ctx, C.data(), cdev, sizeof(double) * (size_t)p * bb));
     return TPG_OK;
   }
-  // Ritz step: Y0 = A X, Y1 = Yk X, res2[j] = |Y1_j - theta_j Y0_j|^2 (host, after a synchronisation)
-  int ritz(const double* A, const double* Yk, int p, const std::vector<double>& X, const std::vector<double>& theta,
+  // Ritz step: Y0 = A X, Y1 = Yk X, res2[j] = |2^-e1 (Y1_j - theta_j Y0_j)|^2 (host, after a synchronisation)
+  int ritz(const double* A, const double* Yk, int p, const std::vector<double>& X, const std::vector<double>& theta, int e1,
            double* Y0, double* Y1, std::vector<double>& res2) {
     double* dx = xdev;
     TPG_HIP(tpg_push_small(ctx, dx, X.data(), sizeof(double) * (size_t)p * p));
     TPG_HIP(tpg_push_small(ctx, dx + 64 * 64, theta.data(), sizeof(double) * (size_t)p));
     const int nblk = (n + 31) / 32;
     TPG_LAUNCH(ctx, "eig_ritz", tpg_ritz_kernel, dim3((unsigned)nblk), dim3(256), 0, A, Yk, n, p, (const double*)dx,
-               (const double*)(dx + 64 * 64), Y0, Y1, gpart);
+               (const double*)(dx + 64 * 64), e1, Y0, Y1, gpart);
     TPG_LAUNCH(ctx, "eig_gram_reduce", tpg_gram_reduce_kernel, dim3((unsigned)((p + 63) / 64)), dim3(256), 0,
                (const double*)gpart, nblk, p, 1, (const double*)nullptr, cdev);
     res2.assign((size_t)p, 0.0);
@@ -1283,14 +1287,20 @@ struct StageTimer {
   }
 };
 
-static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambda_host, double* d_U, double tol = 1e-12) {
+// eig_topk: the solver described above.  A later batch of eig_topk_any passes the np_ eigenvectors of the earlier batches
+// (d_P, orthonormal; d_K is then the deflated matrix) and the first batch's lambda_1 (*lam1_io > 0): the block -- its
+// random start, and again after every filter -- and the product K' A of every Rayleigh-Ritz step are projected against
+// d_P, pairs are accepted relative to that lambda_1 and the block is at most the n - np_ dimensions that are left.
+// *lam1_io receives the lambda_1 the pairs were accepted against.  With np_ = 0 nothing of this is reached.
+static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambda_host, double* d_U, double tol = 1e-12,
+                    const double* d_P = nullptr, int np_ = 0, double* lam1_io = nullptr) {
   // block = 2k + 12 (RSpectra, which the reference calls, keeps ncv = 2k + 1 Lanczos vectors): K Q is bound by
   // reading K, so extra columns are nearly free, and a block that reaches past the k wanted values into the
   // bulk of the spectrum converges in far fewer filter / Rayleigh-Ritz rounds than k + 12 columns do
   int b = 2 * k + 12;
   b = tpg_env_int("TPG_EIG_BLOCK", b);
   if (b > 64) b = 64;
-  if (b > n) b = n;
+  if (b > n - np_) b = n - np_;
   TPG_REQUIRE(k <= b, TPG_EINVAL, "k = %d too large (at most %d components)", k, b);
   EigWork w{ctx, d_K, n, b, 1};
   TPG_TRY(w.init());
@@ -1304,10 +1314,24 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
     return TPG_OK;
   };
 
+  // A <- A - P (P'A) for the earlier batches' vectors, 64 (the small products' limit) at a time
+  auto project_earlier = [&](double* A, int cols, double* tmp) -> int {
+    for (int c0 = 0; c0 < np_; c0 += 64) {
+      const int pc = std::min(64, np_ - c0);
+      const double* P = d_P + (size_t)n * (size_t)c0;
+      std::vector<double> Cm;
+      TPG_TRY(w.gram(P, pc, A, cols, Cm));
+      TPG_TRY(w.rmult(P, pc, Cm, cols, tmp));
+      TPG_TRY(axpby(tmp, -1.0, A, 1.0, A, cols));
+    }
+    return TPG_OK;
+  };
+
   // CholQR (twice) of the `act` columns at A, after projecting out the `nl` locked columns at L
   auto orthonormalize = [&](double* A, int act, const double* L, int nl, double* tmp, int passes = 2) -> int {
     int extra_passes = 0;
     for (int pass = 0; pass < passes; pass++) {
+      TPG_TRY(project_earlier(A, act, tmp));
       if (nl > 0) {
         std::vector<double> Cm;
         TPG_TRY(w.gram(L, nl, A, act, Cm));      // nl x act
@@ -1351,13 +1375,15 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
   TPG_LAUNCH(ctx, "eig_random", tpg_fill_random_kernel, dim3(512), dim3(256), 0, Q, (int64_t)n * b, (uint64_t)0x5EED);
   // uniform random columns are well conditioned: one CholQR pass leaves them orthonormal to ~1e-13, which is all the
   // first Rayleigh-Ritz step (spectral bounds for the filter) asks for
-  TPG_TRY(orthonormalize(Q, b, nullptr, 0, Y, 1));
+  TPG_TRY(orthonormalize(Q, b, nullptr, 0, Y, np_ > 0 ? 2 : 1));  // (projected against d_P: a second pass cleans up)
   st.mark("init + orthonormalize");
   std::vector<double> lam((size_t)b, 0.0), theta, X, H;
   int nl = 0;
   const int MAXIT = 200;
   const double TOL = tol, AMP = 1e6;  // a pair is accepted when its residual |K u - lambda u| <= TOL * lambda_1
-  double lam1 = 0;
+  const bool own_scale = !(lam1_io && *lam1_io > 0);
+  double lam1 = own_scale ? 0 : *lam1_io;
+  int e1 = 0;  // binary exponent of the lambda_1 the residuals of this round are scaled by
   for (int it = 0; it < MAXIT && nl < k; it++) {
     const int act = b - nl;
     double* A = Q + (size_t)n * nl;
@@ -1365,6 +1391,10 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
     TPG_TRY(w.set_locked(Q, nl, lam.data()));
     // Rayleigh-Ritz on the active columns (deflated operator)
     TPG_TRY(w.apply(A, 1.0, nullptr, 0, nullptr, 0, Y));  // Y = K' A
+    // A later batch works with the operator restricted to the complement of the earlier vectors P: K' A keeps a component
+    // P (K' P)' A, the earlier pairs' own residuals (each up to TOL * lambda_1), which no rotation of the block can remove
+    // -- a residual measured with it never gets below it.  (H = A'Y is the same either way: A is orthogonal to P.)
+    TPG_TRY(project_earlier(Y, act, Y0));
     TPG_TRY(w.gram(A, act, Y, act, H));
     st.mark("apply + gram(H)");
     for (int i = 0; i < act; i++)
@@ -1376,20 +1406,22 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
     // The random start block has no converged pair and the filter works on any basis of the subspace: its first
     // Rayleigh-Ritz step only supplies the Ritz VALUES (the filter's interval), so the rotation to Ritz vectors and the
     // residuals (three products, a Gram matrix and a host round trip) are left out -- and so are the eigenvectors of H
-    const bool first = it == 0 && b < n;  // (a block that spans the whole space is exact at once)
+    const bool first = it == 0 && b < n - np_;  // (a block that spans the whole space is exact at once)
     host_sym_eig(H, act, theta, X, !first);
     st.mark("host_sym_eig");
     std::vector<double> RR;
     if (first) {
-      lam1 = fabs(theta[0]) > 0 ? fabs(theta[0]) : 1.0;
+      if (own_scale) lam1 = fabs(theta[0]) > 0 ? fabs(theta[0]) : 1.0;
     } else {
-      TPG_TRY(w.ritz(A, Y, act, X, theta, Y0, Y1, RR));  // Ritz vectors, K * Ritz vectors, |K a - theta a|^2
+      if (own_scale && nl == 0) lam1 = fabs(theta[0]) > 0 ? fabs(theta[0]) : 1.0;
+      frexp(lam1, &e1);
+      TPG_TRY(w.ritz(A, Y, act, X, theta, e1, Y0, Y1, RR));  // Ritz vectors, K * Ritz vectors, |2^-e1 (K a - theta a)|^2
       TPG_HIP(tpg_copy_dev(ctx, A, Y0, colbytes(act)));
-      if (nl == 0) lam1 = fabs(theta[0]) > 0 ? fabs(theta[0]) : 1.0;
       st.mark("ritz vectors + residuals");
     }
+    const double lam1s = ldexp(lam1, -e1);  // in [1/2, 1): the residual norms below are on this scale
     int newly = 0;
-    while (!first && newly < act && nl + newly < k && sqrt(std::max(0.0, RR[(size_t)newly])) < TOL * lam1) newly++;
+    while (!first && newly < act && nl + newly < k && sqrt(std::max(0.0, RR[(size_t)newly])) < TOL * lam1s) newly++;
     for (int j = 0; j < newly; j++) lam[(size_t)(nl + j)] = theta[(size_t)j];
     nl += newly;
     if (nl >= k) break;
@@ -1410,7 +1442,7 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
     if (tpg_env_set("TPG_DEBUG"))
       fprintf(stderr, "[eig] it %d act %d locked %d (+%d) deg %d theta_first %.4g theta_last %.4g lam1 %.4g res0 %.3g\n", it,
               act, nl, newly, deg, theta[(size_t)newly], theta[(size_t)act - 1], lam1,
-              first ? -1.0 : sqrt(std::max(0.0, RR[(size_t)newly])) / lam1);
+              first ? -1.0 : sqrt(std::max(0.0, RR[(size_t)newly])) / lam1s);
     w.b = act2;
     TPG_TRY(w.set_locked(Q, nl, lam.data()));
     // KA2 was formed with the previous deflation; the newly locked directions are (numerically)
@@ -1438,6 +1470,7 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
   }
   TPG_REQUIRE(nl >= k, TPG_ENUMERIC, "eigen solver did not converge (%d of %d pairs)", nl, k);
   for (int j = 0; j < k; j++) lambda_host[j] = lam[(size_t)j];
+  if (lam1_io) *lam1_io = lam1;
   TPG_HIP(tpg_copy_dev(ctx, d_U, Q, colbytes(k)));  // (stream order: the scratch blocks go back to the pool after it)
   return TPG_OK;
 }
@@ -1450,7 +1483,15 @@ static int pca_loadings_device(tpg_ctx* ctx, const tpg_view* v, const double* d_
 // is at most 64 columns wide (LDS tiles of its kernels), so the spectrum is taken in batches of 26 pairs (block 2 * 26 +
 // 12 = 64) with EXPLICIT deflation in between: K <- K - U_b diag(lambda_b) U_b' on a scratch copy of the matrix moves the
 // converged eigenvalues to 0 +- eps * lambda_1 and leaves the other pairs alone, so the next batch converges to the next
-// 26.  Later batches meet a stricter absolute tolerance (it is relative to THEIR largest eigenvalue).
+// 26.  The deflated matrix alone does not keep a later batch orthogonal to the earlier ones once its own eigenvalues are
+// no larger than that eps * lambda_1 -- k at or above the rank of K -- so every later batch is also PROJECTED against the
+// vectors already found (eig_topk: d_P), accepts its pairs relative to the FIRST batch's lambda_1 (relative to its own
+// largest eigenvalue a batch of zeros could never be accepted) and takes a block of at most the n - done dimensions left.
+// A later batch's residual is that of the matrix restricted to the complement of the earlier vectors; the full residual adds
+// the earlier pairs' own, at most sqrt(done) times the acceptance tolerance.
+// Contract for k at or above the rank r: the k - r trailing values are 0 +- 1e-9 lambda_1 and their vectors an orthonormal
+// basis of a part of the null space, orthogonal to the rest.  Not covered: k = n on a singular matrix (the last batch then
+// has to span the whole remaining null space from a block with no room to spare).
 __global__ __launch_bounds__(256) void tpg_deflate_kernel(double* __restrict__ K, int n, const double* __restrict__ U,
                                                           const double* __restrict__ lam, int kb) {
   __shared__ double ui[16][33], uj[16][33];  // [row in tile][component], kb <= 32
@@ -1477,10 +1518,11 @@ static int eig_topk_any(tpg_ctx* ctx, const double* d_K, int n, int k, double* l
   double *const Kw = b_Kw.as<double>(), *const d_lam = b_lam.as<double>();
   TPG_HIP(hipMemcpyAsync(Kw, d_K, sizeof(double) * (size_t)n * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
   const int KB = 26;
+  double lam1 = 0;  // the first batch's lambda_1: every batch accepts relative to it
   for (int done = 0; done < k;) {
     const int kb = std::min(KB, k - done);
     double* Ub = d_U + (size_t)done * (size_t)n;
-    TPG_TRY(eig_topk(ctx, Kw, n, kb, lambda_host + done, Ub, tol));
+    TPG_TRY(eig_topk(ctx, Kw, n, kb, lambda_host + done, Ub, tol, d_U, done, &lam1));
     done += kb;
     if (done < k) {
       TPG_HIP(tpg_h2d_async(ctx, d_lam, lambda_host + done - kb, sizeof(double) * (size_t)kb));
