@@ -1230,8 +1230,8 @@ void tpg_autosvd_free(void* r);
  *   Two evaluations (the device's and a restatement's) of the same labels differ by at most twice these.
  * Limits.  1 <= n <= TPG_KMEANS_MAX_N, 1 <= d <= TPG_KMEANS_MAX_D, 1 <= k <= min(n, TPG_KMEANS_MAX_K), 1 <= R <=
  *   TPG_KMEANS_MAX_RUNS, max_iter >= 1; outside them TPG_EINVAL.  After an error every output is untouched.
- * Out of scope: Ward clustering (method = "ward" of the reference), other starts (k-means++), k-means inside tpg_stream_* /
- *   tpg_multi_*. */
+ * Out of scope: other starts (k-means++), k-means inside tpg_stream_* / tpg_multi_*.  (method = "ward" of the reference: "Ward
+ *   clustering on PCA scores" below.) */
 #define TPG_KMEANS_MAX_N 16777216
 #define TPG_KMEANS_MAX_D 64
 #define TPG_KMEANS_MAX_K 1024
@@ -1251,6 +1251,55 @@ int tpg_kmeans_step(tpg_ctx* ctx, const double* X, int64_t n, int d, int k, cons
 int tpg_kmeans_batch(tpg_ctx* ctx, const double* X, int64_t n, int d, int R, const int32_t* k, const int64_t* seed, int max_iter,
                      const double* centers0, int32_t* labels, double* centers, double* wss, int32_t* n_iter, int32_t* converged,
                      int32_t* n_empty);
+
+/* the WSS of R given labellings in one call: labels n x R column-major int32 (0-based, labelling r in [0, k[r]), else
+ * TPG_EINVAL), k[R], wss[R]; counts (may be NULL) the points per label, labelling r's k_r entries at offset k_0 + .. + k_{r-1}.
+ * The centres are the means of the labels by the "Update" rule (a label that owns no point has no centre and enters nothing), e_i
+ * is formed as in "Assign" and summed as in "WSS": no arithmetic of its own, so the labels a run of tpg_kmeans_batch returned
+ * give that run's wss bit for bit, and bound_wss holds as for such a run.  Limits as tpg_kmeans_batch.  Every pointer host or
+ * device memory. */
+int tpg_cluster_wss(tpg_ctx* ctx, const double* X, int64_t n, int d, int R, const int32_t* k, const int32_t* labels, double* wss,
+                    int32_t* counts);
+
+/* ---- Ward clustering on PCA scores (method = "ward" of gt_cluster_pca, R/gt_cluster_pca.R:156-166: for every k,
+ * cutree(hclust(dist(x)^2, method = "ward.D2"), k); stats::hclust is not among the reference's sources, so the arithmetic is
+ * defined HERE, NOT PINNED BY AN R RUN.  The tree does not depend on k: one tree is built and cut at every k) -----------------
+ * ward.D2 squares its input before the Lance-Williams recurrence and takes the root of the heights afterwards, so the reference
+ *   runs Ward's recurrence on d^4: power = 2.  The proper criterion (each merge the one of least growth of the within-group sum
+ *   of squares) runs it on d^2: power = 1.
+ * Data.  X is n x d doubles, column-major, host or device memory, every entry finite (else TPG_ENUMERIC).  1 <= n <=
+ *   TPG_HCLUST_MAX_N (the full matrix is 8 n^2 bytes, 8 GiB there), 1 <= d <= TPG_KMEANS_MAX_D, power in {1, 2}; outside these
+ *   limits TPG_EINVAL, before anything is allocated.  After an error every output is untouched.
+ * Start.  D2(i,j) in the direct form of "Assign" above: from +0, coordinates ascending, t = x_i - x_j (one rounding),
+ *   D2 = fma(t, t, D2).  S(i,j) = D2 for power 1, S(i,j) = D2 * D2 (one rounding) for power 2.  S is symmetric by construction.
+ * Clusters.  Every point is a cluster of size 1 whose slot is its index; a cluster's slot is always the smallest index among its
+ *   members.
+ * Step s = 1 .. n - 1.  Among the live pairs a < b the one of smallest S(a,b) merges; on equal S the smallest a wins, then the
+ *   smallest b.  merge_a[s-1] = a, merge_b[s-1] = b, height[s-1] = S(a,b).  For every other live c, the sizes converted to double:
+ *     p = (n_a + n_c) S(a,c),  q = (n_b + n_c) S(b,c),  r = n_c S(a,b),  S(a,c) = S(c,a) = ((p + q) - r) / ((n_a + n_b) + n_c),
+ *   every operation rounded once, nothing fused.  Then n_a += n_b and b is dead.
+ * Cut at k.  The first n - k merges are applied; the clusters are labelled 0, 1, .. in the order in which they first appear in
+ *   ascending i (cutree's numbering: the rank of the cluster's slot).  The cut goes by step number, not by height: a height may
+ *   come out an ulp below its predecessor.
+ * WSS of a labelling: tpg_cluster_wss above.
+ * Relation to R.  hclust$height = sqrt(height).  hclust$merge (tpg_hclust_r_merge): -(i + 1) for point i on its own, the 1-based
+ *   step number for a cluster, a singleton before a cluster, of two singletons the smaller point and of two clusters the earlier
+ *   step first.  hclust$order is not produced.
+ * No random generator, no floating-point atomic: the result is a pure function of (X, power), two calls give the same bits.
+ * Out of scope: other linkages, a distance matrix as input, order and plots, Ward inside tpg_stream_* / tpg_multi_*. */
+#define TPG_HCLUST_MAX_N 32768
+/* merge_a, merge_b (int32) and height: n - 1 entries each (0-based slots), host or device memory; n = 1 writes nothing */
+int tpg_hclust_ward(tpg_ctx* ctx, const double* X, int64_t n, int d, int power, int32_t* merge_a, int32_t* merge_b, double* height);
+/* the same, and list_len[n - 1] (may be NULL): list_len[s] = the rows whose nearest neighbour was searched again between
+ * step s and step s + 1 of the device's nearest-neighbour list (list_len[0] = n, the first fill): a diagnostic of
+ * tools/hclust_probe.py, no part of the definition */
+int tpg_hclust_ward_trace(tpg_ctx* ctx, const double* X, int64_t n, int d, int power, int32_t* merge_a, int32_t* merge_b,
+                          double* height, int32_t* list_len);
+/* host only: labels n x R column-major (0-based), column r the cut at k[r] clusters.  TPG_EINVAL (nothing written) for a k
+ * outside [1, n] and for a merge list with a step that does not name two live slots a < b */
+int tpg_hclust_cut(int64_t n, const int32_t* merge_a, const int32_t* merge_b, int R, const int32_t* k, int32_t* labels);
+/* host only: merge (n - 1) x 2 int32 column-major, R's convention */
+int tpg_hclust_r_merge(int64_t n, const int32_t* merge_a, const int32_t* merge_b, int32_t* merge);
 
 /* ---- DAPC (gt_dapc, R/gt_dapc.R:137-255 around MASS::lda(XU, pop, tol = 1e-30) and predict(); MASS is not among the
  * reference's sources, so the discriminant analysis is defined HERE, RECALLED FROM MASS, NOT PINNED) ---------------------------

@@ -1570,6 +1570,65 @@ SEXP _tidypopgen_tpg_cluster_pca(SEXP scores, SEXP k, SEXP n_start, SEXP n_iter,
   return out;
 }
 
+/* ---- Ward clustering on PCA scores ----------------------------------------------------------------------------------- */
+
+#pragma weak tpg_hclust_ward
+#pragma weak tpg_hclust_cut
+#pragma weak tpg_hclust_r_merge
+#pragma weak tpg_cluster_wss
+
+/* tpg_cluster_pca_ward(scores, k, power): the loop over k of R/gt_cluster_pca.R:156-166 (hclust(dist(x)^2, "ward.D2") and cutree
+ * per k, then compute_wss) as ONE tree of include/tpg.h "Ward clustering on PCA scores", cut at every k, and one tpg_cluster_wss
+ * call.  scores = the n x n_pca numeric matrix of PCA scores; k = the numbers of clusters (whole numbers in [1, n]); power = 2
+ * (the reference: the recurrence on d^4) or 1 (Ward's criterion, on d^2).  Every k is at most TPG_KMEANS_MAX_K = 1024, the
+ * limit of tpg_cluster_wss, and is checked before the tree is built.
+ * -> list(groups: n x length(k) integer, 1-based, WSS: length(k), merge: (n - 1) x 2 integer as hclust$merge, height: n - 1,
+ * the root of S as hclust$height) */
+SEXP _tidypopgen_tpg_cluster_pca_ward(SEXP scores, SEXP k, SEXP power) {
+  TPG_NEEDS(tpg_hclust_ward);
+  TPG_NEEDS(tpg_hclust_cut);
+  TPG_NEEDS(tpg_hclust_r_merge);
+  TPG_NEEDS(tpg_cluster_wss);
+  SEXP dim = Rf_getAttrib(scores, R_DimSymbol);
+  if ((TYPEOF(scores) != REALSXP && TYPEOF(scores) != INTSXP) || Rf_length(dim) != 2)
+    Rf_error("tidypopgen (GPU): scores must be a numeric matrix");
+  const int n = INTEGER(dim)[0], d = INTEGER(dim)[1];
+  if (n < 1 || d < 1) Rf_error("tidypopgen (GPU): scores must have at least one row and one column");
+  if ((TYPEOF(k) != REALSXP && TYPEOF(k) != INTSXP) || XLENGTH(k) < 1) Rf_error("tidypopgen (GPU): k must be a vector of whole numbers");
+  if (XLENGTH(k) > TPG_KMEANS_MAX_RUNS) Rf_error("tidypopgen (GPU): k holds more than %d values", TPG_KMEANS_MAX_RUNS);
+  if ((TYPEOF(power) != REALSXP && TYPEOF(power) != INTSXP) || XLENGTH(power) != 1) Rf_error("tidypopgen (GPU): power must be 1 or 2");
+  const int pw = Rf_asInteger(power);
+  if (pw != 1 && pw != 2) Rf_error("tidypopgen (GPU): power must be 1 or 2");
+  SEXP xs = PROTECT(as_real(scores)), kr = PROTECT(as_real(k));
+  const int nk = (int)XLENGTH(kr);
+  for (int a = 0; a < nk; a++) {
+    const double kk = REAL(kr)[a];
+    if (!(kk >= 1 && kk <= n) || kk != floor(kk)) Rf_error("tidypopgen (GPU): every k must be a whole number in [1, nrow(scores)]");
+    /* tpg_cluster_wss would refuse it: say so before the tree is built */
+    if (kk > TPG_KMEANS_MAX_K) Rf_error("tidypopgen (GPU): k = %.0f is above %d, the largest k the WSS is summed for", kk, TPG_KMEANS_MAX_K);
+  }
+  SEXP vals[4];
+  vals[0] = PROTECT(Rf_allocMatrix(INTSXP, n, nk));
+  vals[1] = PROTECT(Rf_allocVector(REALSXP, nk));
+  vals[2] = PROTECT(Rf_allocMatrix(INTSXP, n - 1, 2));
+  vals[3] = PROTECT(Rf_allocVector(REALSXP, n - 1));
+  static const char* names[4] = {"groups", "WSS", "merge", "height"};
+  SEXP out = PROTECT(named_list(4, names, vals));
+  /* R's transient storage: freed when .Call returns or errors */
+  int32_t* ki = (int32_t*)R_alloc((size_t)nk, sizeof(int32_t));
+  int32_t* mab = (int32_t*)R_alloc((size_t)2 * (size_t)n, sizeof(int32_t));
+  int32_t* lab = (int32_t*)R_alloc((size_t)nk * (size_t)n, sizeof(int32_t));
+  for (int a = 0; a < nk; a++) ki[a] = (int32_t)REAL(kr)[a];
+  TPG_R(tpg_hclust_ward(ctx(), REAL(xs), n, d, pw, mab, mab + n, REAL(vals[3])));
+  TPG_R(tpg_hclust_cut(n, mab, mab + n, nk, ki, lab));
+  TPG_R(tpg_hclust_r_merge(n, mab, mab + n, INTEGER(vals[2])));
+  TPG_R(tpg_cluster_wss(ctx(), REAL(xs), n, d, nk, ki, lab, REAL(vals[1]), NULL));
+  for (size_t t = 0; t < (size_t)nk * (size_t)n; t++) INTEGER(vals[0])[t] = lab[t] + 1;
+  for (int s = 0; s < n - 1; s++) REAL(vals[3])[s] = sqrt(REAL(vals[3])[s]);
+  UNPROTECT(7);
+  return out;
+}
+
 /* ---- autoSVD ------------------------------------------------------------------------------------------------------ */
 
 #pragma weak tpg_pca_auto_svd
@@ -1778,11 +1837,16 @@ const R_CallMethodDef tpg_rshim_entries_cluster[] = {
     {"_tidypopgen_tpg_cluster_pca", (DL_FUNC)&_tidypopgen_tpg_cluster_pca, 5},
     {NULL, NULL, 0}};
 
+/* Ward clustering on PCA scores, in a table of its own (tpg_rshim_entries_cluster[] keeps its one row). */
+const R_CallMethodDef tpg_rshim_entries_hclust[] = {
+    {"_tidypopgen_tpg_cluster_pca_ward", (DL_FUNC)&_tidypopgen_tpg_cluster_pca_ward, 3},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the thirteen tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the fourteen tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1795,7 +1859,8 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0]) +
                              sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0]) +
                              sizeof(tpg_rshim_entries_snmf) / sizeof(tpg_rshim_entries_snmf[0]) +
-                             sizeof(tpg_rshim_entries_cluster) / sizeof(tpg_rshim_entries_cluster[0])];
+                             sizeof(tpg_rshim_entries_cluster) / sizeof(tpg_rshim_entries_cluster[0]) +
+                             sizeof(tpg_rshim_entries_hclust) / sizeof(tpg_rshim_entries_hclust[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1810,6 +1875,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_autosvd; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_snmf; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_cluster; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_hclust; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

@@ -201,7 +201,7 @@ gt_snmf_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstat
 # algorithm from seeded start rows in the place of stats::kmeans, every run of every k in one batch).  x: a gt_pca object;
 # seed: one whole number.  Returns the reference's gt_cluster_pca object (clusters$method, n_pca, k, WSS, AIC, BIC, groups), with
 # n_iter, converged and n_empty of the winning runs beside them, so gt_cluster_pca_best_k() and gt_dapc() run on it unchanged.
-# method = "ward" has no counterpart.
+# method = "ward" is gt_cluster_pca_ward_gpu below.
 gt_cluster_pca_gpu <- function(x, n_pca = NULL, k_clusters = c(1, round(nrow(x$u) / 10)), n_iter = 1e5, n_start = 10, seed = 0) {
   if (is.null(x) || !inherits(x, "gt_pca")) stop("'x' should be a 'gt_pca' object")
   n <- nrow(x$u)
@@ -221,6 +221,35 @@ gt_cluster_pca_gpu <- function(x, n_pca = NULL, k_clusters = c(1, round(nrow(x$u
   x$clusters <- list(method = "kmeans", n_pca = n_pca, k = nb_clust, WSS = res$WSS,
                      AIC = n * log(res$WSS / n) + 2 * nb_clust, BIC = n * log(res$WSS / n) + log(n) * nb_clust,
                      groups = groups, n_iter = res$n_iter, converged = res$converged, n_empty = res$n_empty)
+  class(x) <- c("gt_cluster_pca", class(x))
+  x
+}
+
+# method = "ward" of gt_cluster_pca on the GPU (R/gt_cluster_pca.R:156-169; include/tpg.h "Ward clustering on PCA scores" is the
+# definition): ONE tree, cut at every k, in the place of one stats::hclust per k.  criterion = "reference" is the reference's
+# hclust(dist(x)^2, "ward.D2"), Ward's recurrence on d^4; "ward" is the proper criterion, on d^2.  Returns the reference's
+# gt_cluster_pca object with the tree's merge and height (as hclust reports them) beside the groups, so gt_cluster_pca_best_k()
+# and gt_dapc() run on it unchanged.  hclust$order is not produced.  k goes up to 1024 (the limit of the WSS call): the default
+# range passes that from 10 246 individuals on and is then an error before the tree is built; give k_clusters.
+gt_cluster_pca_ward_gpu <- function(x, n_pca = NULL, k_clusters = c(1, round(nrow(x$u) / 10)), criterion = c("reference", "ward")) {
+  if (is.null(x) || !inherits(x, "gt_pca")) stop("'x' should be a 'gt_pca' object")
+  criterion <- match.arg(criterion)
+  n <- nrow(x$u)
+  if (is.null(n_pca)) n_pca <- length(x$d)
+  if (length(k_clusters) == 1) {
+    nb_clust <- k_clusters
+  } else if (length(k_clusters) == 2) {
+    nb_clust <- k_clusters[1]:k_clusters[2]
+  } else {
+    stop("'k_clusters' should be either a single value, or the minimum and maximum to be tested")
+  }
+  x_scores <- sweep(x$u, 2, x$d, "*")[, seq_len(n_pca), drop = FALSE]
+  res <- .Call(`_tidypopgen_tpg_cluster_pca_ward`, x_scores, as.numeric(nb_clust), if (criterion == "reference") 2L else 1L)
+  groups <- lapply(seq_along(nb_clust), function(i) stats::setNames(res$groups[, i], rownames(x$u)))
+  names(groups) <- nb_clust
+  x$clusters <- list(method = "ward", criterion = criterion, n_pca = n_pca, k = nb_clust, WSS = res$WSS,
+                     AIC = n * log(res$WSS / n) + 2 * nb_clust, BIC = n * log(res$WSS / n) + log(n) * nb_clust,
+                     groups = groups, merge = res$merge, height = res$height)
   class(x) <- c("gt_cluster_pca", class(x))
   x
 }

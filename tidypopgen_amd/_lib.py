@@ -325,6 +325,12 @@ PROTOTYPES = {
     "tpg_kmeans_start": (ci, [u64, i64, ci, vp]),
     "tpg_kmeans_step": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp, vp]),
     "tpg_kmeans_batch": (ci, [vp, vp, i64, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_cluster_wss": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp]),
+    # ---- Ward clustering on PCA scores
+    "tpg_hclust_ward": (ci, [vp, vp, i64, ci, ci, vp, vp, vp]),
+    "tpg_hclust_ward_trace": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp]),
+    "tpg_hclust_cut": (ci, [i64, vp, vp, ci, vp, vp]),
+    "tpg_hclust_r_merge": (ci, [i64, vp, vp, vp]),
     # ---- DAPC
     "tpg_lda": (ci, [vp, i64, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tpg_dapc_var_contr": (ci, [vp, vp, i64, i64, ci, vp, ci, vp, vp]),

@@ -2028,7 +2028,7 @@ def gt_cluster_pca(pca: dict, n_pca: Optional[int] = None, k_clusters=None, n_it
     smaller t).  k = 1 is one run (every start gives the column means).  -> the pca dict plus clusters = dict(method, n_pca, k,
     WSS, AIC, BIC, groups ({k: labels, 1-based as R's}), n_iter, converged, n_empty)."""
     if method == "ward":
-        raise NotImplementedError("method = 'ward' is out of scope (DESIGN.md section 10): hierarchical clustering is not built")
+        raise NotImplementedError("method = 'ward' is not forwarded from here yet: call gt_cluster_pca_ward (DESIGN.md section 3.14)")
     if method != "kmeans":
         raise ValueError("'method' should be one of 'kmeans', 'ward'")
     u, dd = np.asarray(pca["u"], dtype=np.float64), np.asarray(pca["d"], dtype=np.float64)
@@ -2074,6 +2074,105 @@ def gt_cluster_pca(pca: dict, n_pca: Optional[int] = None, k_clusters=None, n_it
     out = dict(pca)
     out["clusters"] = dict(method=method, n_pca=n_pca, k=list(ks), WSS=wss, AIC=base + 2 * kv, BIC=base + math.log(n) * kv,
                            groups=groups, n_iter=iters, converged=conv, n_empty=empty)
+    return out
+
+
+HCLUST_MAX_N = 32768  # TPG_HCLUST_MAX_N
+KMEANS_MAX_K = 1024    # TPG_KMEANS_MAX_K: the largest k tpg_kmeans_batch and tpg_cluster_wss take
+
+
+def hclust_ward(X, power: int = 2, ctx: Optional[Context] = None, *, return_list_len: bool = False) -> dict:
+    """tpg_hclust_ward: the Ward tree of n points x d coordinates (include/tpg.h "Ward clustering on PCA scores").  power = 2 is
+    the reference's hclust(dist(x)^2, "ward.D2"), the recurrence on d^4; power = 1 the proper criterion, on d^2.  -> dict(n,
+    merge_a, merge_b (0-based slots), height (the S of every merge, NOT its root), merge ((n - 1) x 2, R's hclust$merge)[,
+    list_len: the device's recompute list per step, a diagnostic])"""
+    ctx = ctx or default_context()
+    x = _scores(X)
+    n, d = x.shape
+    m = max(n - 1, 0)
+    ma, mb, h = np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1))
+    ll = np.zeros(max(m, 1), dtype=np.int32) if return_list_len else None
+    check(lib.tpg_hclust_ward_trace(ctx.h, _ptr(x), n, d, int(power), _ptr(ma), _ptr(mb), _ptr(h), _ptr(ll)))
+    merge = np.zeros((m, 2), dtype=np.int32, order="F")
+    check(lib.tpg_hclust_r_merge(n, _ptr(ma), _ptr(mb), _ptr(merge if m else None)))
+    out = dict(n=n, merge_a=ma[:m], merge_b=mb[:m], height=h[:m], merge=merge)
+    if return_list_len:
+        out["list_len"] = ll[:m]
+    return out
+
+
+def hclust_cut(tree: dict, k) -> np.ndarray:
+    """tpg_hclust_cut (host only): labels n x len(k), 0-based, column r the first n - k[r] merges of the tree, the clusters
+    numbered in the order in which they first appear (cutree's numbering)"""
+    n = int(tree["n"])
+    ks = np.ascontiguousarray(np.atleast_1d(k), dtype=np.int32)
+    ma, mb = _i32(tree["merge_a"]), _i32(tree["merge_b"])
+    if len(ma) != n - 1 or len(mb) != n - 1:
+        raise ValueError(f"a tree of {n} points has {n - 1} merges")
+    labels = np.zeros((max(n, 1), len(ks)), dtype=np.int32, order="F")
+    check(lib.tpg_hclust_cut(n, _ptr(ma if n > 1 else None), _ptr(mb if n > 1 else None), len(ks), _ptr(ks), _ptr(labels)))
+    return labels[:n]
+
+
+def cluster_wss(X, labels, k, return_counts: bool = False, ctx: Optional[Context] = None):
+    """tpg_cluster_wss: the within-group sum of squares of every column of labels (n x R, 0-based, column r in [0, k[r])) in one
+    call, by the kernels a run of kmeans_batch ends in -> wss (R)[, counts: a list of k_r points per label]"""
+    ctx = ctx or default_context()
+    x = _scores(X)
+    n, d = x.shape
+    lab = np.asfortranarray(labels, dtype=np.int32)
+    if lab.ndim == 1:
+        lab = np.asfortranarray(lab[:, None])
+    ks = np.ascontiguousarray(np.atleast_1d(k), dtype=np.int32)
+    R = len(ks)
+    if lab.shape != (n, R):
+        raise ValueError(f"labels must be {n} x {R}, not {lab.shape}")
+    wss = np.zeros(max(R, 1))
+    cnt = np.zeros(max(int(np.maximum(ks, 0).sum()), 1), dtype=np.int32) if return_counts else None
+    check(lib.tpg_cluster_wss(ctx.h, _ptr(x), n, d, R, _ptr(ks), _ptr(lab), _ptr(wss), _ptr(cnt)))
+    if not return_counts:
+        return wss[:R]
+    off = np.concatenate([[0], np.cumsum(np.maximum(ks, 0).astype(np.int64))])
+    return wss[:R], [cnt[off[r]:off[r + 1]] for r in range(R)]
+
+
+def gt_cluster_pca_ward(pca: dict, n_pca: Optional[int] = None, k_clusters=None, criterion: str = "reference",
+                        ctx: Optional[Context] = None) -> dict:
+    """method = "ward" of R/gt_cluster_pca.R:156-169 with ONE tree for every k in place of the reference's hclust per k: scores,
+    the range of k and its default as gt_cluster_pca; criterion = "reference" is the reference's hclust(dist(x)^2, "ward.D2")
+    (Ward's recurrence on d^4), "ward" the proper criterion (on d^2).  The tree is cut at every k on the host and all WSS come
+    from one cluster_wss call, which takes k up to KMEANS_MAX_K = 1024: the default range 1 .. round(n / 10) goes past that from
+    n = 10 246, and a range that does is refused here, before the tree is built (give k_clusters then).  -> the pca dict plus
+    clusters = dict(method="ward", criterion, n_pca, k, WSS, AIC, BIC, groups ({k: labels, 1-based as R's}), merge and height as
+    hclust reports them (height the root of S))."""
+    if criterion not in ("reference", "ward"):
+        raise ValueError("'criterion' should be one of 'reference', 'ward'")
+    u, dd = np.asarray(pca["u"], dtype=np.float64), np.asarray(pca["d"], dtype=np.float64)
+    n = u.shape[0]
+    n_pca = len(dd) if n_pca is None else int(n_pca)
+    if not 1 <= n_pca <= len(dd):
+        raise ValueError(f"n_pca = {n_pca} outside [1, {len(dd)}]")
+    kc = [1, max(int(round(n / 10)), 1)] if k_clusters is None else [int(x) for x in np.atleast_1d(k_clusters)]
+    if len(kc) == 1:
+        ks = kc
+    elif len(kc) == 2:
+        ks = list(range(kc[0], kc[1] + 1))
+    else:
+        raise ValueError("'k_clusters' should be either a single value, or the minimum and maximum to be tested")
+    if not ks or ks[0] < 1:
+        raise ValueError("'k_clusters' should name at least one k >= 1")
+    if ks[-1] > min(n, KMEANS_MAX_K):
+        raise ValueError(f"'k_clusters' reaches k = {ks[-1]}, above min(n = {n}, {KMEANS_MAX_K}), the largest k the WSS is summed for")
+    scores = np.asfortranarray((u * dd[None, :])[:, :n_pca])
+    tree = hclust_ward(scores, power=2 if criterion == "reference" else 1, ctx=ctx)
+    labels = hclust_cut(tree, ks)
+    wss, kv = cluster_wss(scores, labels, ks, ctx=ctx), np.array(ks, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        base = n * np.log(wss / n)
+    out = dict(pca)
+    out["clusters"] = dict(method="ward", criterion=criterion, n_pca=n_pca, k=list(ks), WSS=wss, AIC=base + 2 * kv,
+                           BIC=base + math.log(n) * kv, groups={kk: labels[:, r] + 1 for r, kk in enumerate(ks)},
+                           merge=tree["merge"], height=np.sqrt(tree["height"]))
     return out
 
 

@@ -368,6 +368,16 @@ struct HostIn {
   }
   const T& operator[](int64_t i) const { return p[i]; }
 };
+// device -> the caller's array (host or device memory); a NULL `user` is an output nobody asked for
+template <typename T>
+static inline int tpg_deliver(tpg_ctx* ctx, T* user, const T* d_src, size_t count) {
+  if (!user || !count) return TPG_OK;
+  if (tpg_is_device_ptr(user)) TPG_HIP(tpg_copy_dev(ctx, user, d_src, sizeof(T) * count));
+  else TPG_HIP(tpg_download(ctx, user, d_src, sizeof(T) * count));
+  return TPG_OK;
+}
+// kmeans.hip: every entry of a device array finite, else TPG_ENUMERIC naming `what`; `sc` is the call's scratch (it gives the flag)
+int tpg_check_finite(tpg_ctx* ctx, const double* dX, int64_t count, DevArena& sc, const char* what);
 // every [lo[i], hi[i]) inside [0, m], lo / hi in host or device memory; what = "window" | "block" (runtime.hip)
 int tpg_check_ranges(tpg_ctx* ctx, const int64_t* lo, const int64_t* hi, int64_t count, int64_t m, const char* what);
 

@@ -13,6 +13,8 @@
 //   km_means    a thread per (centre, coordinate) adds its points up in that order and divides: the order of addition is a
 //               function of the labels alone, so no launch shape, batch or atomic enters a centre.
 // The host reads one integer per iteration, the length of the live list.
+// tpg_cluster_wss (the WSS of given labellings, for the Ward route of hclust.hip) counts the labels and reuses km_order, km_means and
+// the tile sums.
 #include <math.h>
 
 #include <algorithm>
@@ -256,6 +258,27 @@ __global__ void km_counts_kernel(const int32_t* __restrict__ starts, int k, int3
   if (c < k) counts[c] = starts[c + 1] - starts[c];
 }
 
+// counts of every run in the layout of the centres, from the sorted lists' starts
+__global__ void km_counts_runs_kernel(const int32_t* __restrict__ starts, const int32_t* __restrict__ rk, const int64_t* __restrict__ roff,
+                                      int32_t* __restrict__ counts) {
+  const int run = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= rk[run]) return;
+  const int32_t* __restrict__ st = starts + roff[run] + run;
+  counts[roff[run] + c] = st[c + 1] - st[c];
+}
+
+// given labels (tpg_cluster_wss): points per centre by integer atomics, as the assign kernel leaves them; a label outside
+// [0, k_run) raises the flag and is not counted
+__global__ void km_label_count_kernel(int64_t n, const int32_t* __restrict__ rk, const int64_t* __restrict__ roff,
+                                      const int32_t* __restrict__ labels, int32_t* __restrict__ counts, int* __restrict__ flag) {
+  const int run = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int lab = labels[i + (int64_t)run * n];
+  if (lab < 0 || lab >= rk[run]) *flag = 1;
+  else atomicAdd(&counts[roff[run] + lab], 1);
+}
+
 __global__ void km_iota_kernel(int32_t* __restrict__ p, int count) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < count) p[t] = t;
@@ -366,7 +389,10 @@ int km_check_k(int k, int64_t n) {
   return TPG_OK;
 }
 
-int km_check_finite(tpg_ctx* ctx, const double* dX, int64_t count, DevArena& sc, const char* what) {
+}  // namespace
+
+// common.h: every entry of a device array finite, else TPG_ENUMERIC naming `what`; the flag comes out of the caller's arena
+int tpg_check_finite(tpg_ctx* ctx, const double* dX, int64_t count, DevArena& sc, const char* what) {
   int* d_flag;
   TPG_TRY(sc.get(&d_flag, 4));
   TPG_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
@@ -377,17 +403,6 @@ int km_check_finite(tpg_ctx* ctx, const double* dX, int64_t count, DevArena& sc,
   TPG_REQUIRE(!flag, TPG_ENUMERIC, "%s holds a value that is not finite", what);
   return TPG_OK;
 }
-
-// device -> the caller's array (host or device memory)
-template <typename T>
-int km_deliver(tpg_ctx* ctx, T* user, const T* d_src, size_t count) {
-  if (!user) return TPG_OK;
-  if (tpg_is_device_ptr(user)) TPG_HIP(tpg_copy_dev(ctx, user, d_src, sizeof(T) * count));
-  else TPG_HIP(tpg_download(ctx, user, d_src, sizeof(T) * count));
-  return TPG_OK;
-}
-
-}  // namespace
 
 extern "C" int64_t tpg_kmeans_chunk_doubles(void) { return KM_CHUNK; }
 
@@ -412,8 +427,8 @@ extern "C" int tpg_kmeans_step(tpg_ctx* ctx, const double* X, int64_t n, int d, 
   KmBatch b;
   const int32_t hk = k;
   TPG_TRY(b.init(ctx, ix.dev<double>(), n, d, 1, &hk));
-  TPG_TRY(km_check_finite(ctx, b.X, n * d, b.sc, "X"));
-  TPG_TRY(km_check_finite(ctx, ic.dev<double>(), (int64_t)k * d, b.sc, "C_in"));
+  TPG_TRY(tpg_check_finite(ctx, b.X, n * d, b.sc, "X"));
+  TPG_TRY(tpg_check_finite(ctx, ic.dev<double>(), (int64_t)k * d, b.sc, "C_in"));
   TPG_HIP(tpg_copy_dev(ctx, b.C, ic.dev<double>(), sizeof(double) * (size_t)k * d));
   TPG_TRY(b.assign<true>(b.live[0], 1));
   TPG_TRY(b.sum_tiles());
@@ -422,10 +437,10 @@ extern "C" int tpg_kmeans_step(tpg_ctx* ctx, const double* X, int64_t n, int d, 
   TPG_TRY(b.sc.get(&d_cnt, (size_t)k));
   TPG_LAUNCH(ctx, "km_counts", km_counts_kernel, dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, b.starts, k, d_cnt);
   TPG_CHECK_LAUNCH();
-  TPG_TRY(km_deliver(ctx, labels, b.labels, (size_t)n));
-  TPG_TRY(km_deliver(ctx, C_out, b.C, (size_t)k * d));
-  TPG_TRY(km_deliver(ctx, counts, d_cnt, (size_t)k));
-  TPG_TRY(km_deliver(ctx, wss, b.wss, 1));
+  TPG_TRY(tpg_deliver(ctx, labels, b.labels, (size_t)n));
+  TPG_TRY(tpg_deliver(ctx, C_out, b.C, (size_t)k * d));
+  TPG_TRY(tpg_deliver(ctx, counts, d_cnt, (size_t)k));
+  TPG_TRY(tpg_deliver(ctx, wss, b.wss, 1));
   TPG_HIP(hipStreamSynchronize(ctx->stream));
   return TPG_OK;
 }
@@ -445,11 +460,11 @@ extern "C" int tpg_kmeans_batch(tpg_ctx* ctx, const double* X, int64_t n, int d,
   TPG_TRY(ix.init(ctx, X, sizeof(double) * (size_t)n * d));
   KmBatch b;
   TPG_TRY(b.init(ctx, ix.dev<double>(), n, d, R, hk.p));
-  TPG_TRY(km_check_finite(ctx, b.X, n * d, b.sc, "X"));
+  TPG_TRY(tpg_check_finite(ctx, b.X, n * d, b.sc, "X"));
   if (centers0) {
     InBuf ic;
     TPG_TRY(ic.init(ctx, centers0, sizeof(double) * (size_t)b.ktot * d));
-    TPG_TRY(km_check_finite(ctx, ic.dev<double>(), b.ktot * d, b.sc, "centers0"));
+    TPG_TRY(tpg_check_finite(ctx, ic.dev<double>(), b.ktot * d, b.sc, "centers0"));
     TPG_HIP(tpg_copy_dev(ctx, b.C, ic.dev<double>(), sizeof(double) * (size_t)b.ktot * d));
     TPG_HIP(hipStreamSynchronize(ctx->stream));  // (ic may own the copy it is read from)
   } else {
@@ -481,12 +496,56 @@ extern "C" int tpg_kmeans_batch(tpg_ctx* ctx, const double* X, int64_t n, int d,
     if (L > 0) TPG_TRY(b.update(b.live[cur], L));
   }
   TPG_TRY(b.final_wss());
-  TPG_TRY(km_deliver(ctx, labels, b.labels, (size_t)n * R));
-  TPG_TRY(km_deliver(ctx, centers, b.C, (size_t)b.ktot * d));
-  TPG_TRY(km_deliver(ctx, wss, b.wss, (size_t)R));
-  TPG_TRY(km_deliver(ctx, n_iter, b.n_iter, (size_t)R));
-  TPG_TRY(km_deliver(ctx, converged, b.converged, (size_t)R));
-  TPG_TRY(km_deliver(ctx, n_empty, b.n_empty, (size_t)R));
+  TPG_TRY(tpg_deliver(ctx, labels, b.labels, (size_t)n * R));
+  TPG_TRY(tpg_deliver(ctx, centers, b.C, (size_t)b.ktot * d));
+  TPG_TRY(tpg_deliver(ctx, wss, b.wss, (size_t)R));
+  TPG_TRY(tpg_deliver(ctx, n_iter, b.n_iter, (size_t)R));
+  TPG_TRY(tpg_deliver(ctx, converged, b.converged, (size_t)R));
+  TPG_TRY(tpg_deliver(ctx, n_empty, b.n_empty, (size_t)R));
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
+  return TPG_OK;
+}
+
+// The WSS of R given labellings: the means of the labels by km_order / km_means and the tile sums of km_wss, the kernels a run
+// of tpg_kmeans_batch ends in, so a labelling that such a run returned gets that run's bits back.
+extern "C" int tpg_cluster_wss(tpg_ctx* ctx, const double* X, int64_t n, int d, int R, const int32_t* k, const int32_t* labels,
+                               double* wss, int32_t* counts) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && X && k && labels && wss, TPG_EINVAL, "null argument");
+  TPG_TRY(km_check_shape(n, d));
+  TPG_REQUIRE(R >= 1 && R <= TPG_KMEANS_MAX_RUNS, TPG_EINVAL, "R = %d outside [1, %d]", R, TPG_KMEANS_MAX_RUNS);
+  HostIn<int32_t> hk;
+  TPG_TRY(hk.init(ctx, k, R));
+  for (int r = 0; r < R; r++) TPG_TRY(km_check_k(hk[r], n));
+  InBuf ix, il;
+  TPG_TRY(ix.init(ctx, X, sizeof(double) * (size_t)n * d));
+  TPG_TRY(il.init(ctx, labels, sizeof(int32_t) * (size_t)n * R));
+  KmBatch b;
+  TPG_TRY(b.init(ctx, ix.dev<double>(), n, d, R, hk.p));
+  TPG_TRY(tpg_check_finite(ctx, b.X, n * d, b.sc, "X"));
+  TPG_HIP(tpg_copy_dev(ctx, b.labels, il.dev<int32_t>(), sizeof(int32_t) * (size_t)n * R));
+  TPG_HIP(hipMemsetAsync(b.C, 0, sizeof(double) * (size_t)b.ktot * d, ctx->stream));  // (a centre that owns nothing stays: at +0)
+  int* d_flag;
+  TPG_TRY(b.sc.get(&d_flag, 4));
+  TPG_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
+  TPG_LAUNCH(ctx, "km_label_count", km_label_count_kernel, dim3((unsigned)b.tiles, (unsigned)R), dim3(KM_TILE), 0, n, b.rk, b.roff,
+             b.labels, b.counts, d_flag);
+  TPG_CHECK_LAUNCH();
+  int flag = 0;
+  TPG_HIP(tpg_fetch_small(ctx, &flag, d_flag, sizeof(int)));  // (il may own the copy the labels were read from: it has been read)
+  TPG_REQUIRE(!flag, TPG_EINVAL, "a label outside [0, k) of its labelling");
+  TPG_TRY(b.update(b.live[0], R));
+  TPG_TRY(b.final_wss());
+  int32_t* d_cnt = nullptr;
+  if (counts) {
+    TPG_TRY(b.sc.get(&d_cnt, (size_t)b.ktot));
+    TPG_LAUNCH(ctx, "km_counts_runs", km_counts_runs_kernel, dim3((unsigned)ceil_div(b.kmax, 256), (unsigned)R), dim3(256), 0, b.starts,
+               b.rk, b.roff, d_cnt);
+    TPG_CHECK_LAUNCH();
+  }
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
+  TPG_TRY(tpg_deliver(ctx, wss, b.wss, (size_t)R));
+  TPG_TRY(tpg_deliver(ctx, counts, d_cnt, (size_t)b.ktot));
   TPG_HIP(hipStreamSynchronize(ctx->stream));
   return TPG_OK;
 }
