@@ -527,6 +527,69 @@ int tpg_admix_cv(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, c
                  uint64_t cv_seed, const double* q0, const double* f0, double* cv_error, double* fold_ll, int64_t* fold_count,
                  int64_t* fold_het, int32_t* fold_iter, int32_t* fold_converged);
 
+/* ---- admixture, accelerated (no counterpart in the reference: the outside binary accelerates its own block relaxation; here the
+ * EM map of "admixture" is wrapped in squared extrapolation, SQUAREM, scheme S3 of Varadhan and Roland 2008, RECALLED, NOT
+ * PINNED.  The same likelihood and the same EM step; fewer of them) --------------------------------------------------------------
+ * State.  theta = (Q, F) of "admixture"; E(theta) is one EM step of that section, clamp included; l(theta) its likelihood.  The
+ *   pass that applies E to theta also yields l(theta), as there.
+ * One cycle from theta0, with a step limit a_max (4 at the start of a run):
+ *   1. theta1 = E(theta0), which yields l(theta0); theta2 = E(theta1), which yields l(theta1).
+ *   2. Stop rule, the plain one ("a plain EM step gained less than tol"): if l(theta1) - l(theta0) < tol, return theta2 with
+ *      converged = 1, as the plain EM returns the state one step past the compared pair.
+ *   3. Per entry, in IEEE double, one rounding per operation, no fusing:  r = theta1 - theta0;  v = (theta2 - theta1) - r.
+ *   4. sr = sum r^2 and sv = sum v^2 over every entry of the halves being updated (Q only with update_f = 0, F only with
+ *      update_q = 0), each term joined to its sum by one fused multiply-add.  The shape of the sums is fixed: the K live columns of
+ *      the state stored row by row (row i: q(i, 0 .. K - 1), row j: f(0 .. K - 1, j)) padded to the dispatch width, padding
+ *      excluded, cut into tiles of 2048 stored doubles; in a tile, thread t of 256 adds the entries 256 e + t in ascending e, then a
+ *      butterfly over each wave of 64 and the four waves in order; Q's tiles come before F's, and a one-workgroup kernel has thread
+ *      t add the tiles t, t + 256, ... in ascending order, then the same butterfly and wave order.  No floating-point atomics.
+ *   5. The host reads sr and sv (two doubles per cycle) and forms alpha = -sqrt(sr / sv), a correctly rounded quotient, then a
+ *      correctly rounded root.  sv = 0, or an alpha that is not finite: alpha = -1.  Then alpha is clipped into [-a_max, -1].
+ *   6. theta' raw, per entry: fma(a2, v, fma(-2 alpha, r, theta0)) with a2 = alpha * alpha rounded once.
+ *   7. The projection of theta' raw onto the feasible set, row by row (a row = one individual of Q or one locus of F):
+ *        F: each entry clamped into [eps, 1 - eps], eps = TPG_ADMIX_EPS;
+ *        Q: each entry raised to at least eps, then the row divided by its sum, added in ascending k from 0 (the normalisation of
+ *           the start);
+ *        a row in which nothing moved (r = v = 0 in every entry) keeps theta0 bit for bit.  A locus or an individual typed
+ *        nowhere is such a row, since E keeps it.
+ *   8. theta'' = E(theta'), which yields l(theta').  ACCEPT if l(theta') is finite and l(theta') >= l(theta1): the next cycle
+ *      starts from theta''; if alpha was clipped at -a_max, a_max becomes 4 a_max.  REJECT otherwise: the next cycle starts from
+ *      theta2, and a_max becomes max(1, a_max / 4).  No extra likelihood pass is spent either way.  In exact arithmetic
+ *      l(theta'') >= l(theta') >= l(theta1) >= l(theta0) and l(theta2) >= l(theta1): the likelihoods at the starts of the cycles do
+ *      not decrease.
+ * Counting.  n_iter counts EM steps, so it compares with the plain EM's and with max_iter; a cycle costs three.  max_iter reached
+ *   inside a cycle abandons the cycle and returns the last state an EM step produced (theta1 or theta2); reached with the third
+ *   step of a cycle it returns the state the next cycle would have started from (theta'', or theta2 after a rejection), and the
+ *   cycle counts.  converged = 1 only by the stop rule.  A final likelihood-only pass gives loglik of the returned state.
+ *   loglik_trace = l of every state an EM step was applied to, in order, then loglik: n_iter + 1 entries (per whole cycle
+ *   l(theta0), l(theta1), l(theta')).  alpha[c] and accepted[c] (1 / 0) of cycle c = 0 .. n_cycles - 1, n_cycles and n_rejected
+ *   are additional outputs.  max_iter = 0, both update flags 0 (every cycle then has sr = sv = 0, alpha = -1 and theta' = theta0),
+ *   the errors and "outputs untouched after an error" are as in tpg_admix_em.
+ * Determinism.  As "admixture": a result is a function of the view, K, the start and the parameters alone; two calls give the
+ *   same bits.
+ * Rounding, u = 2^-52, first order, nn = the number of entries summed.  Against the exact sum of (theta1 - theta0)^2 of the given
+ *   doubles, sr carries the rounding of r (twice in the square), the fused term and at most nn - 1 additions that are not exact
+ *   (adding 0 is): |d sr| <= (nn + 3) u sr.  v is a difference of differences, so its error is absolute:
+ *     |dv| <= u (|theta2 - theta1| + |r| + |v|);   |d sv| <= 2 sum |v| |dv| + (nn + 3) u sv.
+ *   Given sr and sv, alpha is bit-exact; given alpha, r and v, theta' raw is bit-exact. */
+/* tpg_admix_em's arguments, then: alpha (double) and accepted (int32) with room for max_iter / 3 entries each (integer division),
+ * n_cycles, n_rejected; host memory, each may be NULL */
+int tpg_admix_em_squarem(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, const tpg_admix_params* params,
+                         const double* q0, const double* f0, double* Q, double* P, double* loglik, double* loglik_trace,
+                         int32_t* n_iter, int32_t* converged, double* alpha, int32_t* accepted, int32_t* n_cycles,
+                         int32_t* n_rejected);
+/* tpg_admix_cv with every fold refitted by tpg_admix_em_squarem: the same folds, hold-out sums and error */
+int tpg_admix_cv_squarem(tpg_ctx* ctx, const tpg_view* v, const double* ploidy, int K, const tpg_admix_params* params, int folds,
+                         uint64_t cv_seed, const double* q0, const double* f0, double* cv_error, double* fold_ll,
+                         int64_t* fold_count, int64_t* fold_het, int32_t* fold_iter, int32_t* fold_converged);
+/* steps 3 to 7 for a caller's own theta0, theta1, theta2 (q*: n x K, f*: m x K, column-major doubles, host or device memory, taken
+ * as given: no normalisation, no clamp) and a_max >= 1.  sr, sv, alpha: host memory; Qp / Pp = the projected theta', Qraw / Praw =
+ * theta' raw (the shapes of q0 / f0, host or device memory); a half that is not updated comes back as theta0 in both.  Every output
+ * may be NULL.  K out of [1, TPG_ADMIX_MAX_K], n or m < 1, a_max < 1 or NaN: TPG_EINVAL, nothing written */
+int tpg_admix_squarem_point(tpg_ctx* ctx, int64_t n, int64_t m, int K, int update_q, int update_f, const double* q0,
+                            const double* f0, const double* q1, const double* f1, const double* q2, const double* f2, double a_max,
+                            double* sr, double* sv, double* alpha, double* Qp, double* Pp, double* Qraw, double* Praw);
+
 /* ---- sNMF (gt_snmf, R/gt_snmf.R: the reference writes a .geno file and calls LEA::snmf; LEA is not part of the reference's
  * sources and nothing pins it, so what is computed is defined HERE: sparse non-negative matrix factorisation by alternating
  * non-negative least squares (Frichot et al. 2014; Kim and Park 2007), RECALLED, NOT PINNED) --------------------------------------

@@ -1265,8 +1265,8 @@ SEXP _tidypopgen_tpg_f2_blocks(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds,
  * reading back of its .Q / .P files (R/gt_admixture.R:86-236) as one call of the EM of include/tpg.h "admixture", for one k
  * and one run.  seed = a double vector of length 1 holding a whole number in [0, 2^53]; q0 (N x k) / p0 (M x k) = a start, or
  * NULL for the seeded one.  -> list(Q: N x k, P: M x k (frequency of the counted allele), loglik, n_iter, converged) */
-SEXP _tidypopgen_tpg_admixture(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0, SEXP p0) {
-  TPG_NEEDS(tpg_admix_em);
+static SEXP admixture_call(int squarem, SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0,
+                           SEXP p0) {
   const int K = Rf_asInteger(k);
   if (K == NA_INTEGER || K < 1) Rf_error("tidypopgen (GPU): k must be a positive integer");
   if (TYPEOF(seed) != REALSXP || XLENGTH(seed) != 1) Rf_error("tidypopgen (GPU): seed must be a double vector of length 1");
@@ -1287,27 +1287,40 @@ SEXP _tidypopgen_tpg_admixture(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP s
   SEXP ps = PROTECT(p0 == R_NilValue ? R_NilValue : Rf_coerceVector(p0, REALSXP));
   if (qs != R_NilValue && XLENGTH(qs) != n * (R_xlen_t)K) Rf_error("tidypopgen (GPU): q0 must be length(rowInd) x k");
   if (ps != R_NilValue && XLENGTH(ps) != m * (R_xlen_t)K) Rf_error("tidypopgen (GPU): p0 must be length(colInd) x k");
-  SEXP vals[5];
+  SEXP vals[7];
   vals[0] = PROTECT(Rf_allocMatrix(REALSXP, (int)n, K));
   vals[1] = PROTECT(Rf_allocMatrix(REALSXP, (int)m, K));
   vals[2] = PROTECT(Rf_allocVector(REALSXP, 1));
   vals[3] = PROTECT(Rf_allocVector(INTSXP, 1));
   vals[4] = PROTECT(Rf_allocVector(LGLSXP, 1));
-  static const char* names[5] = {"Q", "P", "loglik", "n_iter", "converged"};
-  SEXP out = PROTECT(named_list(5, names, vals));
+  vals[5] = PROTECT(Rf_allocVector(INTSXP, 1));
+  vals[6] = PROTECT(Rf_allocVector(INTSXP, 1));
+  static const char* names[7] = {"Q", "P", "loglik", "n_iter", "converged", "n_cycles", "n_rejected"};
+  SEXP out = PROTECT(named_list(squarem ? 7 : 5, names, vals));
   tpg_admix_params P;
   tpg_admix_params_default(&P);
   P.max_iter = mi;
   P.tol = tl;
   P.seed = (uint64_t)sd;
-  int32_t nit = 0, conv = 0;
+  int32_t nit = 0, conv = 0, ncyc = 0, nrej = 0;
   tpg_view* v = view_of(BM, ri, ci, 0);
-  TPG_R_VIEW(v, tpg_admix_em(ctx(), v, NULL, K, &P, qs == R_NilValue ? NULL : REAL(qs), ps == R_NilValue ? NULL : REAL(ps),
-                             REAL(vals[0]), REAL(vals[1]), REAL(vals[2]), NULL, &nit, &conv));
+  if (squarem)
+    TPG_R_VIEW(v, tpg_admix_em_squarem(ctx(), v, NULL, K, &P, qs == R_NilValue ? NULL : REAL(qs), ps == R_NilValue ? NULL : REAL(ps),
+                                       REAL(vals[0]), REAL(vals[1]), REAL(vals[2]), NULL, &nit, &conv, NULL, NULL, &ncyc, &nrej));
+  else
+    TPG_R_VIEW(v, tpg_admix_em(ctx(), v, NULL, K, &P, qs == R_NilValue ? NULL : REAL(qs), ps == R_NilValue ? NULL : REAL(ps),
+                               REAL(vals[0]), REAL(vals[1]), REAL(vals[2]), NULL, &nit, &conv));
   INTEGER(vals[3])[0] = nit;
   LOGICAL(vals[4])[0] = conv != 0;
-  UNPROTECT(10);
+  INTEGER(vals[5])[0] = ncyc;
+  INTEGER(vals[6])[0] = nrej;
+  UNPROTECT(12);
   return out;
+}
+
+SEXP _tidypopgen_tpg_admixture(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0, SEXP p0) {
+  TPG_NEEDS(tpg_admix_em);
+  return admixture_call(0, BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0);
 }
 
 /* ---- admixture cross-validation ----------------------------------------------------------------------------------- */
@@ -1320,10 +1333,8 @@ SEXP _tidypopgen_tpg_admixture(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP s
  * include/tpg.h "admixture cross-validation" for one k and one run.  The first nine arguments are those of tpg_admixture; folds =
  * an integer in [2, 64]; cv_seed follows the rule of seed.
  * -> list(cv_error, fold_deviance: folds, fold_count: folds (double), fold_n_iter: folds (integer), fold_converged: folds) */
-SEXP _tidypopgen_tpg_admixture_cv(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0, SEXP p0,
-                                  SEXP folds, SEXP cv_seed) {
-  TPG_NEEDS(tpg_admix_cv);
-  TPG_NEEDS(tpg_admix_cv_error);
+static SEXP admixture_cv_call(int squarem, SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0,
+                              SEXP p0, SEXP folds, SEXP cv_seed) {
   const int K = Rf_asInteger(k);
   if (K == NA_INTEGER || K < 1) Rf_error("tidypopgen (GPU): k must be a positive integer");
   if (TYPEOF(seed) != REALSXP || XLENGTH(seed) != 1) Rf_error("tidypopgen (GPU): seed must be a double vector of length 1");
@@ -1366,8 +1377,9 @@ SEXP _tidypopgen_tpg_admixture_cv(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEX
   int64_t cnt[TPG_ADMIX_MAX_FOLDS], het[TPG_ADMIX_MAX_FOLDS];
   int32_t nit[TPG_ADMIX_MAX_FOLDS], conv[TPG_ADMIX_MAX_FOLDS];
   tpg_view* v = view_of(BM, ri, ci, 0);
-  TPG_R_VIEW(v, tpg_admix_cv(ctx(), v, NULL, K, &P, nf, (uint64_t)cs, qs == R_NilValue ? NULL : REAL(qs),
-                             ps == R_NilValue ? NULL : REAL(ps), &cv, ll, cnt, het, nit, conv));
+  TPG_R_VIEW(v, (squarem ? tpg_admix_cv_squarem : tpg_admix_cv)(ctx(), v, NULL, K, &P, nf, (uint64_t)cs,
+                                                                qs == R_NilValue ? NULL : REAL(qs),
+                                                                ps == R_NilValue ? NULL : REAL(ps), &cv, ll, cnt, het, nit, conv));
   TPG_R(tpg_admix_cv_error(nf, ll, cnt, het, REAL(vals[1]), &cv));
   REAL(vals[0])[0] = cv;
   for (int f = 0; f < nf; f++) {
@@ -1377,6 +1389,36 @@ SEXP _tidypopgen_tpg_admixture_cv(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEX
   }
   UNPROTECT(10);
   return out;
+}
+
+SEXP _tidypopgen_tpg_admixture_cv(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0, SEXP p0,
+                                  SEXP folds, SEXP cv_seed) {
+  TPG_NEEDS(tpg_admix_cv);
+  TPG_NEEDS(tpg_admix_cv_error);
+  return admixture_cv_call(0, BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0, folds, cv_seed);
+}
+
+/* ---- admixture, accelerated ---------------------------------------------------------------------------------------- */
+
+#pragma weak tpg_admix_em_squarem
+#pragma weak tpg_admix_cv_squarem
+
+/* tpg_admixture_squarem(BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0): tpg_admixture with the EM under squared extrapolation
+ * (tpg_admix_em_squarem of include/tpg.h "admixture, accelerated").  The same arguments and checks.
+ * -> list(Q, P, loglik, n_iter (EM steps), converged, n_cycles, n_rejected) */
+SEXP _tidypopgen_tpg_admixture_squarem(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0,
+                                       SEXP p0) {
+  TPG_NEEDS(tpg_admix_em_squarem);
+  return admixture_call(1, BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0);
+}
+
+/* tpg_admixture_cv_squarem(BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0, folds, cv_seed): tpg_admixture_cv with every fold
+ * refitted by the accelerated driver (tpg_admix_cv_squarem).  The same arguments, checks and result list. */
+SEXP _tidypopgen_tpg_admixture_cv_squarem(SEXP BM, SEXP rowInd, SEXP colInd, SEXP k, SEXP seed, SEXP max_iter, SEXP tol, SEXP q0,
+                                          SEXP p0, SEXP folds, SEXP cv_seed) {
+  TPG_NEEDS(tpg_admix_cv_squarem);
+  TPG_NEEDS(tpg_admix_cv_error);
+  return admixture_cv_call(1, BM, rowInd, colInd, k, seed, max_iter, tol, q0, p0, folds, cv_seed);
 }
 
 /* ---- pcadapt ------------------------------------------------------------------------------------------------------ */
@@ -1817,6 +1859,15 @@ const R_CallMethodDef tpg_rshim_entries_admix_cv[] = {
     {"_tidypopgen_tpg_admixture_cv", (DL_FUNC)&_tidypopgen_tpg_admixture_cv, 11},
     {NULL, NULL, 0}};
 
+/* Accelerated admixture and its cross-validation, each in a table of its own (the two tables above keep their rows). */
+const R_CallMethodDef tpg_rshim_entries_admix_squarem[] = {
+    {"_tidypopgen_tpg_admixture_squarem", (DL_FUNC)&_tidypopgen_tpg_admixture_squarem, 9},
+    {NULL, NULL, 0}};
+
+const R_CallMethodDef tpg_rshim_entries_admix_cv_squarem[] = {
+    {"_tidypopgen_tpg_admixture_cv_squarem", (DL_FUNC)&_tidypopgen_tpg_admixture_cv_squarem, 11},
+    {NULL, NULL, 0}};
+
 /* The pcadapt scan, in a table of its own: the reference's routine is bigsnpr's, without a native row. */
 const R_CallMethodDef tpg_rshim_entries_pcadapt[] = {
     {"_tidypopgen_tpg_pcadapt", (DL_FUNC)&_tidypopgen_tpg_pcadapt, 4},
@@ -1846,7 +1897,7 @@ const R_CallMethodDef tpg_rshim_entries_hclust[] = {
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the fourteen tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the sixteen tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1856,6 +1907,8 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_f2) / sizeof(tpg_rshim_entries_f2[0]) +
                              sizeof(tpg_rshim_entries_admix) / sizeof(tpg_rshim_entries_admix[0]) +
                              sizeof(tpg_rshim_entries_admix_cv) / sizeof(tpg_rshim_entries_admix_cv[0]) +
+                             sizeof(tpg_rshim_entries_admix_squarem) / sizeof(tpg_rshim_entries_admix_squarem[0]) +
+                             sizeof(tpg_rshim_entries_admix_cv_squarem) / sizeof(tpg_rshim_entries_admix_cv_squarem[0]) +
                              sizeof(tpg_rshim_entries_pcadapt) / sizeof(tpg_rshim_entries_pcadapt[0]) +
                              sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0]) +
                              sizeof(tpg_rshim_entries_snmf) / sizeof(tpg_rshim_entries_snmf[0]) +
@@ -1871,6 +1924,8 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_f2; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_admix; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_admix_cv; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_admix_squarem; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_admix_cv_squarem; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_pcadapt; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_autosvd; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_snmf; e->name; e++) all[k++] = *e;

@@ -177,6 +177,25 @@ gt_admixture_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bi
   adm_list
 }
 
+# gt_admixture_gpu with the EM under squared extrapolation (include/tpg.h "admixture, accelerated"): the same likelihood, the same
+# arguments and the same list, reached in fewer EM steps; n_iter still counts EM steps, and n_cycles and n_rejected (the
+# extrapolation cycles, and those of them that were rejected) sit beside it.  crossval = TRUE refits every fold the same way.
+gt_admixture_squarem_gpu <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), k, seed = 0,
+                                     max_iter = 1000L, tol = 1e-4, q0 = NULL, p0 = NULL, crossval = FALSE, cv_folds = 5L,
+                                     cv_seed = 0) {
+  res <- .Call(`_tidypopgen_tpg_admixture_squarem`, X, as.integer(ind.row), as.integer(ind.col), as.integer(k), as.numeric(seed),
+               as.integer(max_iter), as.numeric(tol), q0, p0)
+  adm_list <- list(k = as.integer(k), Q = list(res$Q), P = list(res$P), loglik = res$loglik, n_iter = res$n_iter,
+                   converged = res$converged, n_cycles = res$n_cycles, n_rejected = res$n_rejected)
+  if (isTRUE(crossval)) {
+    cvres <- .Call(`_tidypopgen_tpg_admixture_cv_squarem`, X, as.integer(ind.row), as.integer(ind.col), as.integer(k),
+                   as.numeric(seed), as.integer(max_iter), as.numeric(tol), q0, p0, as.integer(cv_folds), as.numeric(cv_seed))
+    adm_list$cv <- cvres$cv_error
+  }
+  class(adm_list) <- c("gt_admix", "list")
+  adm_list
+}
+
 # Ancestry proportions by sparse non-negative matrix factorisation on the GPU for one k and one run (the .geno export and the
 # LEA::snmf run of R/gt_snmf.R; include/tpg.h "sNMF" is the definition).  seed: one whole number; q0: a start (individuals x k) or
 # NULL for the seeded one.  entropy = TRUE holds a share `percentage` of the typed genotypes out, fits on the rest, as LEA does, and

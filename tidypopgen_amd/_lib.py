@@ -204,6 +204,10 @@ PROTOTYPES = {
     "tpg_admix_holdout_sums": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp]),
     "tpg_admix_cv_error": (ci, [ci, vp, vp, vp, vp, vp]),
     "tpg_admix_cv": (ci, [vp, vp, vp, ci, P(AdmixParams), ci, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    # ---- admixture, accelerated
+    "tpg_admix_em_squarem": (ci, [vp, vp, vp, ci, P(AdmixParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_admix_cv_squarem": (ci, [vp, vp, vp, ci, P(AdmixParams), ci, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_admix_squarem_point": (ci, [vp, i64, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp]),
     # ---- sNMF
     "tpg_snmf": (ci, [vp, vp, vp, ci, ci, f64, f64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tpg_snmf_step": (ci, [vp, vp, ci, f64, vp, vp, vp, vp, vp]),

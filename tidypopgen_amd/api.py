@@ -1691,12 +1691,27 @@ def _admix_mat(x, rows: int, K: int, name: str):
     return a
 
 
+def _admix_accel(accel) -> bool:
+    """accel of admix_em / admix_cv / gt_admixture: None = the plain EM; "squarem" = the driver of include/tpg.h "admixture,
+    accelerated"; anything else is a ValueError"""
+    if accel is None:
+        return False
+    if accel == "squarem":
+        return True
+    raise ValueError(f"accel must be None or 'squarem', not {accel!r}")
+
+
 def admix_em(v: View, K: int, Q0=None, F0=None, seed: int = 0, max_iter: int = 1000, tol: float = 1e-4, update_q: bool = True,
-             update_f: bool = True, return_trace: bool = False, ploidy=None) -> dict:
+             update_f: bool = True, return_trace: bool = False, ploidy=None, accel=None) -> dict:
     """tpg_admix_em (include/tpg.h "admixture"): maximum-likelihood ancestry proportions of a resident view by EM.  Q0 (n x K)
     and F0 (m x K, the shape of a .P file) are numpy arrays or device pointers (int); None draws that half of the start from
-    `seed`.  -> dict(Q (n x K), P (m x K, frequency of the counted allele), loglik, n_iter, converged[, trace = l(0 .. n_iter)])"""
+    `seed`.  -> dict(Q (n x K), P (m x K, frequency of the counted allele), loglik, n_iter, converged[, trace = l(0 .. n_iter)])
+    accel="squarem": tpg_admix_em_squarem (include/tpg.h "admixture, accelerated"), the same EM step under squared
+    extrapolation; n_iter still counts EM steps, and the dict gains n_cycles, n_rejected[, alpha, accepted: one entry per cycle;
+    trace = l of every state a step was applied to, then loglik]."""
     K = int(K)
+    if _admix_accel(accel):
+        return _admix_em_squarem(v, K, Q0, F0, seed, max_iter, tol, update_q, update_f, return_trace, ploidy)
     q0, f0 = _admix_mat(Q0, v.n, K, "Q0"), _admix_mat(F0, v.m, K, "F0")
     pr = _lib.AdmixParams(int(max_iter), float(tol), int(bool(update_q)), int(bool(update_f)), int(seed) & 0xFFFFFFFFFFFFFFFF)
     Q, P = np.zeros((v.n, max(K, 1)), order="F"), np.zeros((v.m, max(K, 1)), order="F")  # K < 1 is the library's to refuse
@@ -1709,6 +1724,46 @@ def admix_em(v: View, K: int, Q0=None, F0=None, seed: int = 0, max_iter: int = 1
     if return_trace:
         out["trace"] = trace[: nit.value + 1].copy()
     return out
+
+
+def _admix_em_squarem(v, K, Q0, F0, seed, max_iter, tol, update_q, update_f, return_trace, ploidy) -> dict:
+    q0, f0 = _admix_mat(Q0, v.n, K, "Q0"), _admix_mat(F0, v.m, K, "F0")
+    pr = _lib.AdmixParams(int(max_iter), float(tol), int(bool(update_q)), int(bool(update_f)), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    Q, P = np.zeros((v.n, max(K, 1)), order="F"), np.zeros((v.m, max(K, 1)), order="F")  # K < 1 is the library's to refuse
+    trace = np.full(max(int(max_iter), 0) + 1, np.nan)
+    nc = max(int(max_iter), 0) // 3 + 1
+    alpha, acc = np.full(nc, np.nan), np.zeros(nc, dtype=np.int32)
+    ll, nit, conv, ncyc, nrej = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    pl = _f64(ploidy)
+    check(lib.tpg_admix_em_squarem(v.ctx.h, v.h, _ptr(pl), K, C.byref(pr), _ptr(q0), _ptr(f0), _ptr(Q), _ptr(P), C.byref(ll),
+                                   _ptr(trace), C.byref(nit), C.byref(conv), _ptr(alpha), _ptr(acc), C.byref(ncyc), C.byref(nrej)))
+    out = dict(Q=Q, P=P, loglik=ll.value, n_iter=int(nit.value), converged=bool(conv.value), n_cycles=int(ncyc.value),
+               n_rejected=int(nrej.value))
+    if return_trace:
+        out["trace"] = trace[: nit.value + 1].copy()
+        out["alpha"] = alpha[: ncyc.value].copy()
+        out["accepted"] = acc[: ncyc.value].astype(bool)
+    return out
+
+
+def admix_squarem_point(Q0, F0, Q1, F1, Q2, F2, a_max: float = 4.0, update_q: bool = True, update_f: bool = True, ctx=None) -> dict:
+    """tpg_admix_squarem_point (include/tpg.h "admixture, accelerated", steps 3 to 7) for the caller's own theta0, theta1, theta2
+    (Q*: n x K, F*: m x K numpy arrays, taken as given) -> dict(sr, sv, alpha, Q, P = the projected theta', Q_raw, P_raw = theta'
+    before the projection).  ctx: a Context (None: the default one)."""
+    q = [np.asfortranarray(x, dtype=np.float64) for x in (Q0, Q1, Q2)]
+    f = [np.asfortranarray(x, dtype=np.float64) for x in (F0, F1, F2)]
+    if q[0].ndim != 2 or f[0].ndim != 2 or q[0].shape[1] != f[0].shape[1]:
+        raise ValueError("Q0 must be n x K and F0 m x K")
+    (n, K), m = q[0].shape, f[0].shape[0]
+    for a, name in zip(q[1:] + f[1:], ("Q1", "Q2", "F1", "F2")):
+        _admix_mat(a, n if name[0] == "Q" else m, K, name)
+    ctx = ctx if ctx is not None else default_context()
+    out = [np.zeros((n, K), order="F"), np.zeros((m, K), order="F"), np.zeros((n, K), order="F"), np.zeros((m, K), order="F")]
+    sr, sv, al = C.c_double(), C.c_double(), C.c_double()
+    check(lib.tpg_admix_squarem_point(ctx.h, n, m, K, int(bool(update_q)), int(bool(update_f)), _ptr(q[0]), _ptr(f[0]), _ptr(q[1]),
+                                      _ptr(f[1]), _ptr(q[2]), _ptr(f[2]), float(a_max), C.byref(sr), C.byref(sv), C.byref(al),
+                                      _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3])))
+    return dict(sr=sr.value, sv=sv.value, alpha=al.value, Q=out[0], P=out[1], Q_raw=out[2], P_raw=out[3])
 
 
 def admix_loglik(v: View, Q, P) -> float:
@@ -1754,11 +1809,13 @@ def admix_cv_error(fold_ll, fold_count, fold_het) -> dict:
 
 
 def admix_cv(v: View, K: int, folds: int = 5, cv_seed: int = 0, Q0=None, F0=None, seed: int = 0, max_iter: int = 1000,
-             tol: float = 1e-4, update_q: bool = True, update_f: bool = True, ploidy=None) -> dict:
+             tol: float = 1e-4, update_q: bool = True, update_f: bool = True, ploidy=None, accel=None) -> dict:
     """tpg_admix_cv (include/tpg.h "admixture cross-validation"): for every fold, the EM on the view without the fold's genotypes
     (the same start each time: Q0 / F0 or the seeded one) and the deviance of the held-out genotypes under that fit, all on the
-    device.  -> dict(cv_error, fold_deviance, fold_ll, fold_count, fold_het, fold_n_iter, fold_converged)"""
+    device.  -> dict(cv_error, fold_deviance, fold_ll, fold_count, fold_het, fold_n_iter, fold_converged)
+    accel="squarem": tpg_admix_cv_squarem, every fold refitted by the accelerated driver."""
     K, folds = int(K), int(folds)
+    entry = lib.tpg_admix_cv_squarem if _admix_accel(accel) else lib.tpg_admix_cv
     q0, f0 = _admix_mat(Q0, v.n, K, "Q0"), _admix_mat(F0, v.m, K, "F0")
     pr = _lib.AdmixParams(int(max_iter), float(tol), int(bool(update_q)), int(bool(update_f)), int(seed) & 0xFFFFFFFFFFFFFFFF)
     nf = min(max(folds, 1), ADMIX_MAX_FOLDS)  # folds out of range is the library's to refuse
@@ -1766,15 +1823,15 @@ def admix_cv(v: View, K: int, folds: int = 5, cv_seed: int = 0, Q0=None, F0=None
     nit, conv = np.zeros(nf, dtype=np.int32), np.zeros(nf, dtype=np.int32)
     cv = C.c_double()
     pl = _f64(ploidy)
-    check(lib.tpg_admix_cv(v.ctx.h, v.h, _ptr(pl), K, C.byref(pr), folds, int(cv_seed) & 0xFFFFFFFFFFFFFFFF, _ptr(q0), _ptr(f0),
-                           C.byref(cv), _ptr(ll), _ptr(cnt), _ptr(het), _ptr(nit), _ptr(conv)))
+    check(entry(v.ctx.h, v.h, _ptr(pl), K, C.byref(pr), folds, int(cv_seed) & 0xFFFFFFFFFFFFFFFF, _ptr(q0), _ptr(f0),
+                C.byref(cv), _ptr(ll), _ptr(cnt), _ptr(het), _ptr(nit), _ptr(conv)))
     dev = admix_cv_error(ll, cnt, het)["fold_deviance"]
     return dict(cv_error=cv.value, fold_deviance=dev, fold_ll=ll, fold_count=cnt, fold_het=het, fold_n_iter=nit,
                 fold_converged=conv.astype(bool))
 
 
 def gt_admixture(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, seed=None, max_iter: int = 1000,
-                 tol: float = 1e-4, crossval: bool = False, cv_folds: int = 5, cv_seed: int = 0) -> dict:
+                 tol: float = 1e-4, crossval: bool = False, cv_folds: int = 5, cv_seed: int = 0, accel=None) -> dict:
     """R/gt_admixture.R:62-236 with the EM of include/tpg.h "admixture" in place of the outside binary: every k of `k` (a
     scalar or a list) is run n_runs times on one resident view.  seed has n_runs entries (repeated for every k) or
     n_runs * len(k), one per run in the order of the result (k by k); None: 0, 1, ... in that order.
@@ -1782,10 +1839,13 @@ def gt_admixture(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, se
     crossval=True adds `cv`, parallel to `k` (the name the reference uses): the cv_folds-fold cross-validation error of that
     run's k and seed on the same resident view (admix_cv; include/tpg.h "admixture cross-validation" is the definition, so the
     number orders the k as ADMIXTURE's does without being ADMIXTURE's).  The smallest cv marks the k to use.
+    accel="squarem" runs every fit and every cross-validation refit under squared extrapolation (include/tpg.h "admixture,
+    accelerated"): the same likelihood in fewer EM steps; n_iter still counts EM steps.
     conda_env and outdir of the reference have no counterpart here: there is no outside program and no file; `log` is absent
     for the same reason.  P is the frequency of the counted allele."""
     if k is None:
         raise ValueError("k is required")
+    _admix_accel(accel)
     ks = [int(x) for x in np.atleast_1d(k)]
     n_runs = int(n_runs)
     if seed is not None:
@@ -1804,13 +1864,13 @@ def gt_admixture(X: FBM, ind_row=None, ind_col=None, k=None, n_runs: int = 1, se
         out["cv"] = []
     for a, kk in enumerate(ks):
         for b in range(n_runs):
-            r = admix_em(v, kk, seed=seed[a * n_runs + b], max_iter=max_iter, tol=tol)
+            r = admix_em(v, kk, seed=seed[a * n_runs + b], max_iter=max_iter, tol=tol, accel=accel)
             out["k"].append(kk)
             for name in ("Q", "P", "loglik", "n_iter", "converged"):
                 out[name].append(r[name])
             if crossval:
                 out["cv"].append(admix_cv(v, kk, folds=cv_folds, cv_seed=cv_seed, seed=seed[a * n_runs + b], max_iter=max_iter,
-                                          tol=tol)["cv_error"])
+                                          tol=tol, accel=accel)["cv_error"])
     return out
 
 
