@@ -736,6 +736,44 @@ int tpg_pairwise_fst_loop(tpg_ctx* ctx, int method, const int32_t* pairs1, int P
                           const double* het_obs, int by_locus, int return_num_dem, double* fst_tot,
                           double* out_a, double* out_b);
 
+/* ---- windowed pairwise Fst (windows_pairwise_pop_fst, R/windows_pairwise_pop_fst.R:62-107 over
+ * R/windows_stats_generic.R:113-179; the Fst behind windows_nwise_pop_pbs, R/windows_nwise_pop_pbs.R:78-114 with
+ * pbs_one_triplet of R/nwise_pop_pbs.R:116-157 = tpg_pbs_from_fst) -----------------------------------------------------
+ * Per-locus terms: for pair (g1, g2) and locus j, num(j) and den(j) are exactly the doubles tpg_pairwise_pop_fst(...,
+ *        return_num_dem = 1) writes for that method: the same statement order, IEEE double, no FMA contraction.
+ * Windows: window w covers the loci lo[w] .. hi[w]-1 with a pad_na flag, the contract of tpg_window_stats.  n_num = the
+ *        number of non-NaN num in the window, n_den = the number of non-NaN den: counted separately, as the reference's two
+ *        windows_stats_generic calls do (they differ at a pseudohaploid group with one typed allele, where p q / (n - 1) is
+ *        0 / 0 while den is finite).  mean_num = (sum of the non-NaN num) / n_num, NaN where the window is padded, n_num = 0
+ *        or n_num < min_loci; mean_den likewise with n_den.  fst = mean_num / mean_den, one IEEE division of those two
+ *        doubles.  n_num and n_den are -1 on a pad_na window.
+ * Sums:  with C = TPG_WINFST_CHUNK_LOCI, b0 = C ceil(lo / C) and b1 = C floor(hi / C): if b0 >= b1 the window's terms are
+ *        added one by one in ascending locus order; otherwise the terms of lo .. b0-1 one by one, then the sums of the
+ *        whole chunks b0 / C .. b1 / C - 1 in ascending order (each the sum of its 64 terms in ascending locus order,
+ *        started from 0), then the terms of b1 .. hi-1 one by one.  A window sum is within L 2^-52 sum |x_j| of the exact
+ *        sum of its L non-NaN doubles.
+ * Determinism: a cell depends on (lo, hi, pair, method, the view and its grouping) alone -- not on nw, on the window's place
+ *        in the list, on the other windows or on launch geometry.  No floating-point atomics; two calls give the same bits.
+ * Methods: TPG_FST_HUDSON, TPG_FST_NEI87, TPG_FST_WC84; pseudohaploids only with Hudson (TPG_EINVAL otherwise, with the
+ *        message of tpg_pairwise_pop_fst).
+ * Outputs are nw x P column-major; fst is required, the other four may be NULL.  lo, hi, pad_na (may be NULL) and every output
+ * may be host or device memory; pairs1 (2 x P column-major, 1-based) is host memory.  Nothing proportional to m crosses PCIe,
+ * and no m x P matrix is formed.
+ * A window outside [0, m], lo > hi, min_loci < 1, a pair outside [1, ngroups], P < 1, nw > TPG_WINFST_MAX_WINDOWS (one
+ * workgroup row per window: split the list): TPG_EINVAL, nothing written; nw == 0: TPG_OK, nothing written. */
+#define TPG_WINFST_CHUNK_LOCI 64
+#define TPG_WINFST_MAX_WINDOWS 16777215
+/* loci per chunk partial (a power of two; results are defined in terms of it, see "Sums" above) */
+int64_t tpg_winfst_chunk_loci(void);
+/* host only, no context: the bytes tpg_windows_pairwise_pop_fst takes from the device pool as scratch, beyond the view's
+ * count table and the device copies of arguments and outputs the caller keeps in host memory: the chunk partials, 24 bytes
+ * per (whole chunk, pair), and the pair list.  At most m P / 2 + 8 P + 32; nw does not enter.  A bad size: -1 */
+int64_t tpg_windows_fst_scratch_bytes(int64_t m, int ngroups, int P, int64_t nw);
+int tpg_windows_pairwise_pop_fst(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, const double* ploidy,
+                                 int method, const int32_t* pairs1, int P, const int64_t* lo, const int64_t* hi,
+                                 const uint8_t* pad_na, int64_t nw, int min_loci, double* fst, double* mean_num,
+                                 double* mean_den, int32_t* n_num, int32_t* n_den);
+
 /* ---- pairwise individual matrices (IBS / KING / allele sharing / GRM) ---- */
 /* Accumulators for the four integer cross-products V=vv', D=dd', H=hh', A=hv'
  * (v valid, d = dosage-1, h heterozygous), from which every count matrix of

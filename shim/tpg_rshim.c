@@ -1176,6 +1176,192 @@ SEXP _tidypopgen_tpg_windows_pop_tajimas_d(SEXP BM, SEXP rowInd, SEXP colInd, SE
   return out;
 }
 
+/* ---- windowed pairwise Fst and PBS ------------------------------------------------------------------------------- */
+
+#pragma weak tpg_windows_pairwise_pop_fst
+/* the PBS row keeps the window Fst in device memory between two library calls: the three symbols it does that with and the PBS
+ * kernel's entry point are weak as well, so that the shim still links against the host-only stand-in, which has none of them */
+#pragma weak tpg_dev_alloc
+#pragma weak tpg_dev_free
+#pragma weak tpg_dev_to_host
+#pragma weak tpg_pbs_from_fst
+
+/* lo / hi (REALSXP, coerced by the caller) and pad_na (LGLSXP or NULL) as _tidypopgen_tpg_windows_pop_tajimas_d checks them:
+ * whole numbers with 0 <= lo <= hi <= m.  w64 = lo[nw] then hi[nw], p8 = the pad flags, both in R's transient storage. */
+static R_xlen_t winfst_windows(SEXP lr, SEXP hr, SEXP pr, double m, int64_t** w64_out, uint8_t** p8_out) {
+  const R_xlen_t nw = XLENGTH(lr);
+  if (XLENGTH(hr) != nw || (pr != R_NilValue && XLENGTH(pr) != nw)) Rf_error("tidypopgen (GPU): lo, hi and pad_na differ in length");
+  if (nw > INT_MAX) Rf_error("tidypopgen (GPU): too many windows for an R matrix");
+  int64_t* w64 = (int64_t*)R_alloc((size_t)(nw > 0 ? 2 * nw : 1), sizeof(int64_t));
+  uint8_t* p8 = (uint8_t*)R_alloc((size_t)(nw > 0 ? nw : 1), 1);
+  for (R_xlen_t w = 0; w < nw; w++) {
+    const double a = REAL(lr)[w], b = REAL(hr)[w];
+    if (!(a >= 0 && a <= b && b <= m) || a != floor(a) || b != floor(b))
+      Rf_error("tidypopgen (GPU): window %lld is NA, not whole numbers or outside [0, %.0f]", (long long)w + 1, m);
+    w64[w] = (int64_t)a;
+    w64[nw + w] = (int64_t)b;
+    p8[w] = 0;
+    if (pr != R_NilValue) {
+      if (LOGICAL(pr)[w] == NA_LOGICAL) Rf_error("tidypopgen (GPU): NA in pad_na");
+      p8[w] = LOGICAL(pr)[w] != 0;
+    }
+  }
+  *w64_out = w64;
+  *p8_out = p8;
+  return nw;
+}
+
+/* utils::combn(G, 2), 1-based, 2 x P column-major, in R's transient storage */
+static int32_t* winfst_pairs(int G) {
+  const int P = G * (G - 1) / 2;
+  int32_t* pairs = (int32_t*)R_alloc((size_t)(P > 0 ? 2 * P : 1), sizeof(int32_t));
+  int k = 0;
+  for (int a = 1; a <= G; a++)
+    for (int b = a + 1; b <= G; b++) {
+      pairs[2 * k] = a;
+      pairs[2 * k + 1] = b;
+      k++;
+    }
+  return pairs;
+}
+
+/* the arguments both rows share, checked in the order of _tidypopgen_tpg_windows_pop_tajimas_d; at least 2 (Fst) or 3 (PBS) groups */
+static int winfst_checks(SEXP ngroups, SEXP lo, SEXP hi, SEXP min_loci, int min_groups, int* ml_out) {
+  const int G = ngroups_of(ngroups);
+  if (G < min_groups) {
+    if (min_groups == 3) Rf_error("At least 3 populations are required to compute PBS."); /* R/nwise_pop_pbs.R */
+    Rf_error("tidypopgen (GPU): pairwise Fst needs at least 2 populations");
+  }
+  if (G > 2048) Rf_error("tidypopgen (GPU): too many populations for a matrix of pairs");
+  if ((TYPEOF(lo) != INTSXP && TYPEOF(lo) != REALSXP) || (TYPEOF(hi) != INTSXP && TYPEOF(hi) != REALSXP))
+    Rf_error("tidypopgen (GPU): lo and hi must be integer or double vectors");
+  const int ml = Rf_asInteger(min_loci);
+  if (ml == NA_INTEGER || ml < 1) Rf_error("min_loci must be positive."); /* R/windows_stats_generic.R:101-103 */
+  *ml_out = ml;
+  return G;
+}
+
+/* tpg_windows_pairwise_pop_fst(BM, rowInd, colInd, groupIds, ngroups, method, lo, hi, pad_na, min_loci): the by-locus
+ * numerators and denominators and the two windows_stats_generic(operator = "mean") calls of
+ * R/windows_pairwise_pop_fst.R:62-107 in one call that never forms them (include/tpg.h "windowed pairwise Fst").  method: 0
+ * Hudson (what the reference always takes here), 1 Nei87, 2 WC84; every pair of utils::combn(ngroups, 2); lo / hi / pad_na as
+ * _tidypopgen_tpg_windows_pop_tajimas_d takes them.  -> the nw x P matrix of window Fst: NA_real_ where the reference assigns
+ * NA (a pad window, fewer than min_loci numerators or denominators), the arithmetic value elsewhere, a NaN included. */
+SEXP _tidypopgen_tpg_windows_pairwise_pop_fst(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP method, SEXP lo,
+                                              SEXP hi, SEXP pad_na, SEXP min_loci) {
+  TPG_NEEDS(tpg_windows_pairwise_pop_fst);
+  int ml;
+  const int G = winfst_checks(ngroups, lo, hi, min_loci, 2, &ml);
+  const int meth = Rf_asInteger(method);
+  if (meth == NA_INTEGER || meth < 0 || meth > 2) Rf_error("tidypopgen (GPU): method must be 0 (Hudson), 1 (Nei87) or 2 (WC84)");
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
+  if (XLENGTH(gid) != XLENGTH(ri)) Rf_error("tidypopgen (GPU): groupIds and rowInd differ in length");
+  SEXP lr = PROTECT(as_real(lo)), hr = PROTECT(as_real(hi));
+  SEXP pr = PROTECT(pad_na == R_NilValue ? R_NilValue : Rf_coerceVector(pad_na, LGLSXP));
+  int64_t* w64;
+  uint8_t* p8;
+  const R_xlen_t nw = winfst_windows(lr, hr, pr, (double)XLENGTH(ci), &w64, &p8);
+  const int P = G * (G - 1) / 2;
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)nw, P));
+  const int32_t* pairs = winfst_pairs(G);
+  const size_t cells = (size_t)nw * (size_t)P;
+  int32_t* nn = (int32_t*)R_alloc(cells > 0 ? 2 * cells : 1, sizeof(int32_t));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  TPG_R_VIEW(v, tpg_windows_pairwise_pop_fst(ctx(), v, INTEGER(gid), G, NULL, meth, pairs, P, w64, w64 + nw, p8, (int64_t)nw, ml,
+                                             REAL(out), NULL, NULL, nn, nn + cells));
+  double* f = REAL(out);
+  for (size_t k = 0; k < cells; k++)
+    if (nn[k] < ml || nn[cells + k] < ml) f[k] = NA_REAL; /* stat[n_loci < min_loci] <- NA of either mean, and runner's na_pad */
+  UNPROTECT(7);
+  return out;
+}
+
+/* tpg_windows_nwise_pop_pbs(BM, rowInd, colInd, groupIds, ngroups, lo, hi, pad_na, min_loci, return_fst):
+ * R/windows_nwise_pop_pbs.R:78-114 -- the windowed Hudson Fst above (the reference's windows_pairwise_pop_fst takes Hudson
+ * whatever it is told) kept in device memory, and pbs_one_triplet of R/nwise_pop_pbs.R:116-157 on it for every triplet of
+ * utils::combn(ngroups, 3).  -> list(pbs, fst): pbs nw x 6 T (per triplet pbs_1, pbs_2, pbs_3, pbsn1_1, pbsn1_2, pbsn1_3),
+ * NA_real_ where one of the triplet's three Fst is NA; fst the nw x P matrix of the row above, or NULL unless return_fst. */
+SEXP _tidypopgen_tpg_windows_nwise_pop_pbs(SEXP BM, SEXP rowInd, SEXP colInd, SEXP groupIds, SEXP ngroups, SEXP lo, SEXP hi,
+                                           SEXP pad_na, SEXP min_loci, SEXP return_fst) {
+  TPG_NEEDS(tpg_windows_pairwise_pop_fst);
+  TPG_NEEDS(tpg_pbs_from_fst);
+  TPG_NEEDS(tpg_dev_alloc);
+  TPG_NEEDS(tpg_dev_free);
+  TPG_NEEDS(tpg_dev_to_host);
+  int ml;
+  const int G = winfst_checks(ngroups, lo, hi, min_loci, 3, &ml);
+  const int want_fst = Rf_asLogical(return_fst);
+  if (want_fst == NA_LOGICAL) Rf_error("return_fst must be a logical value (TRUE or FALSE)");
+  const int P = G * (G - 1) / 2;
+  const double T_d = (double)G * (G - 1) * (G - 2) / 6.0;
+  if (6.0 * T_d > (double)INT_MAX) Rf_error("tidypopgen (GPU): too many triplets for an R matrix");
+  const int T = (int)T_d;
+  SEXP ri = PROTECT(as_int(rowInd)), ci = PROTECT(as_int(colInd));
+  SEXP gid = PROTECT(Rf_coerceVector(groupIds, INTSXP));
+  if (XLENGTH(gid) != XLENGTH(ri)) Rf_error("tidypopgen (GPU): groupIds and rowInd differ in length");
+  SEXP lr = PROTECT(as_real(lo)), hr = PROTECT(as_real(hi));
+  SEXP pr = PROTECT(pad_na == R_NilValue ? R_NilValue : Rf_coerceVector(pad_na, LGLSXP));
+  int64_t* w64;
+  uint8_t* p8;
+  const R_xlen_t nw = winfst_windows(lr, hr, pr, (double)XLENGTH(ci), &w64, &p8);
+  if ((double)nw * 6.0 * T_d > 4503599627370496.0) Rf_error("tidypopgen (GPU): the PBS matrix is too large");
+  SEXP vals[2];
+  vals[0] = PROTECT(Rf_allocMatrix(REALSXP, (int)nw, 6 * T));
+  vals[1] = PROTECT(want_fst ? Rf_allocMatrix(REALSXP, (int)nw, P) : R_NilValue);
+  static const char* names[2] = {"pbs", "fst"};
+  SEXP out = PROTECT(named_list(2, names, vals));
+  const int32_t* pairs = winfst_pairs(G);
+  /* the Fst columns (p1.p2, p1.p3, p2.p3) of every triplet, 0-based, triplets and pairs in combn order */
+  int32_t* trip = (int32_t*)R_alloc((size_t)3 * (size_t)T, sizeof(int32_t));
+  {
+    int t = 0;
+#define WINFST_COL(a, b) (((a) - 1) * G - ((a) - 1) * (a) / 2 + ((b) - (a) - 1)) /* the column of pair (a, b), a < b, 1-based */
+    for (int a = 1; a <= G; a++)
+      for (int b = a + 1; b <= G; b++)
+        for (int c = b + 1; c <= G; c++) {
+          trip[3 * t] = WINFST_COL(a, b);
+          trip[3 * t + 1] = WINFST_COL(a, c);
+          trip[3 * t + 2] = WINFST_COL(b, c);
+          t++;
+        }
+#undef WINFST_COL
+  }
+  const size_t cells = (size_t)nw * (size_t)P;
+  int32_t* nn = (int32_t*)R_alloc(cells > 0 ? 2 * cells : 1, sizeof(int32_t));
+  tpg_view* v = view_of(BM, ri, ci, 0);
+  /* from here to the release of the view and the device buffer nothing may longjmp: the status is looked at afterwards */
+  void* d_fst = NULL;
+  const size_t fst_bytes = sizeof(double) * cells;
+  int rc = tpg_dev_alloc(ctx(), fst_bytes, &d_fst);
+  if (rc == TPG_OK)
+    rc = tpg_windows_pairwise_pop_fst(ctx(), v, INTEGER(gid), G, NULL, TPG_FST_HUDSON, pairs, P, w64, w64 + nw, p8, (int64_t)nw, ml,
+                                      (double*)d_fst, NULL, NULL, nn, nn + cells);
+  if (rc == TPG_OK && nw > 0) rc = tpg_pbs_from_fst(ctx(), (const double*)d_fst, (int64_t)nw, P, trip, T, REAL(vals[0]));
+  if (rc == TPG_OK && nw > 0 && want_fst) rc = tpg_dev_to_host(ctx(), REAL(vals[1]), d_fst, fst_bytes);
+  if (d_fst) tpg_dev_free(d_fst);
+  tpg_view_free(v);
+  if (rc != TPG_OK) Rf_error("tidypopgen (GPU): %s", tpg_last_error());
+  double* pbs = REAL(vals[0]);
+  for (int t = 0; t < T; t++)
+    for (R_xlen_t w = 0; w < nw; w++) {
+      int na = 0;
+      for (int q = 0; q < 3; q++) {
+        const size_t k = (size_t)w + (size_t)trip[3 * t + q] * (size_t)nw;
+        na |= nn[k] < ml || nn[cells + k] < ml;
+      }
+      if (na)
+        for (int q = 0; q < 6; q++) pbs[(size_t)w + ((size_t)6 * (size_t)t + (size_t)q) * (size_t)nw] = NA_REAL;
+    }
+  if (want_fst) {
+    double* f = REAL(vals[1]);
+    for (size_t k = 0; k < cells; k++)
+      if (nn[k] < ml || nn[cells + k] < ml) f[k] = NA_REAL;
+  }
+  UNPROTECT(9);
+  return out;
+}
+
 /* ---- f2 blocks ---------------------------------------------------------------------------------------------------- */
 
 #pragma weak tpg_f2_blocks
@@ -1893,11 +2079,18 @@ const R_CallMethodDef tpg_rshim_entries_hclust[] = {
     {"_tidypopgen_tpg_cluster_pca_ward", (DL_FUNC)&_tidypopgen_tpg_cluster_pca_ward, 3},
     {NULL, NULL, 0}};
 
+/* Windowed pairwise Fst and PBS by the fused window scan, in a table of its own: the reference computes both in R on top of
+ * pairwise_pop_fst and windows_stats_generic, without a native row. */
+const R_CallMethodDef tpg_rshim_entries_winfst[] = {
+    {"_tidypopgen_tpg_windows_pairwise_pop_fst", (DL_FUNC)&_tidypopgen_tpg_windows_pairwise_pop_fst, 10},
+    {"_tidypopgen_tpg_windows_nwise_pop_pbs", (DL_FUNC)&_tidypopgen_tpg_windows_nwise_pop_pbs, 10},
+    {NULL, NULL, 0}};
+
 #ifdef TPG_RSHIM_STANDALONE
 /* The shim as a package of its own (useDynLib(tpgshim, .registration = TRUE)): used to try the GPU path beside an
  * unmodified tidypopgen by assigning these functions over tidypopgen's internal wrappers. */
 void R_init_tpgshim(DllInfo* dll) {
-  /* R_registerRoutines takes ONE .Call table per DLL: the sixteen tables end to end (the array must outlive the call) */
+  /* R_registerRoutines takes ONE .Call table per DLL: the seventeen tables end to end (the array must outlive the call) */
   static R_CallMethodDef all[sizeof(tpg_rshim_entries) / sizeof(tpg_rshim_entries[0]) +
                              sizeof(tpg_rshim_entries_write) / sizeof(tpg_rshim_entries_write[0]) +
                              sizeof(tpg_rshim_entries_hwe) / sizeof(tpg_rshim_entries_hwe[0]) +
@@ -1913,7 +2106,8 @@ void R_init_tpgshim(DllInfo* dll) {
                              sizeof(tpg_rshim_entries_autosvd) / sizeof(tpg_rshim_entries_autosvd[0]) +
                              sizeof(tpg_rshim_entries_snmf) / sizeof(tpg_rshim_entries_snmf[0]) +
                              sizeof(tpg_rshim_entries_cluster) / sizeof(tpg_rshim_entries_cluster[0]) +
-                             sizeof(tpg_rshim_entries_hclust) / sizeof(tpg_rshim_entries_hclust[0])];
+                             sizeof(tpg_rshim_entries_hclust) / sizeof(tpg_rshim_entries_hclust[0]) +
+                             sizeof(tpg_rshim_entries_winfst) / sizeof(tpg_rshim_entries_winfst[0])];
   size_t k = 0;
   for (const R_CallMethodDef* e = tpg_rshim_entries; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_write; e->name; e++) all[k++] = *e;
@@ -1931,6 +2125,7 @@ void R_init_tpgshim(DllInfo* dll) {
   for (const R_CallMethodDef* e = tpg_rshim_entries_snmf; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_cluster; e->name; e++) all[k++] = *e;
   for (const R_CallMethodDef* e = tpg_rshim_entries_hclust; e->name; e++) all[k++] = *e;
+  for (const R_CallMethodDef* e = tpg_rshim_entries_winfst; e->name; e++) all[k++] = *e;
   all[k].name = NULL;
   all[k].fun = NULL;
   all[k].numArgs = 0;

@@ -137,6 +137,25 @@ tpg_windows_pop_tajimas_d <- function(X, ind.row = bigstatsr::rows_along(X), ind
         as.integer(n_groups), lo, hi, pad_na, as.integer(min_loci))
 }
 
+# Windowed pairwise Fst in one call that never forms the by-locus matrices (pairwise_pop_fst(return_num_dem = TRUE) and the two
+# windows_stats_generic calls of R/windows_pairwise_pop_fst.R:62-107; include/tpg.h "windowed pairwise Fst" is the definition).
+# group_ids0 = dplyr::group_indices(.x) - 1; method 0 = Hudson (what the reference takes here), 1 = Nei87, 2 = WC84; lo / hi /
+# pad_na as tpg_windows_pop_tajimas_d takes them.  Returns the windows x pairs matrix, pairs in utils::combn(n_groups, 2) order.
+tpg_windows_pairwise_pop_fst <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), group_ids0,
+                                         n_groups, method = 0L, lo, hi, pad_na = NULL, min_loci = 1L) {
+  .Call(`_tidypopgen_tpg_windows_pairwise_pop_fst`, X, as.integer(ind.row), as.integer(ind.col), group_ids0,
+        as.integer(n_groups), as.integer(method), lo, hi, pad_na, as.integer(min_loci))
+}
+
+# Windowed PBS of every triplet of populations from that windowed Hudson Fst (R/windows_nwise_pop_pbs.R:78-114); the window Fst
+# stays on the device in between.  Returns list(pbs, fst): pbs windows x 6 per triplet of utils::combn(n_groups, 3) (pbs_1,
+# pbs_2, pbs_3, pbsn1_1, pbsn1_2, pbsn1_3), fst the windows x pairs matrix or NULL unless return_fst.
+tpg_windows_nwise_pop_pbs <- function(X, ind.row = bigstatsr::rows_along(X), ind.col = bigstatsr::cols_along(X), group_ids0,
+                                      n_groups, lo, hi, pad_na = NULL, min_loci = 1L, return_fst = FALSE) {
+  .Call(`_tidypopgen_tpg_windows_nwise_pop_pbs`, X, as.integer(ind.row), as.integer(ind.col), group_ids0,
+        as.integer(n_groups), lo, hi, pad_na, as.integer(min_loci), isTRUE(return_fst))
+}
+
 # Blocked f2 and allele-frequency products in one call (gt_to_aftable, admixtools' discard_from_aftable and afs_to_f2_blocks of
 # R/gt_extract_f2.R:141-189; include/tpg.h "f2 blocks" is the definition).  lo / hi: 0-based half-open ranges of positions in
 # ind.col, one per jackknife block; ploidy = NULL: all diploid; keep: NULL or one logical per locus (transitions, transversions

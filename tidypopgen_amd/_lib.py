@@ -226,6 +226,10 @@ PROTOTYPES = {
     "tpg_pairwise_pop_fst": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp]),
     "tpg_pairwise_pop_fst_sums": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp]),
     "tpg_pairwise_fst_loop": (ci, [vp, ci, vp, ci, i64, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp]),
+    # ---- windowed pairwise Fst
+    "tpg_winfst_chunk_loci": (i64, []),
+    "tpg_windows_fst_scratch_bytes": (i64, [i64, ci, ci, i64]),
+    "tpg_windows_pairwise_pop_fst": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, i64, ci, vp, vp, vp, vp, vp]),
     # ---- pairwise individual matrices
     "tpg_pairwise_buffer_bytes": (sz, [i64]),
     "tpg_pairwise_create": (ci, [vp, i64, vp, vp]),

@@ -1406,10 +1406,14 @@ def windows_stats_generic(x, chromosome, position=None, operator="mean", window_
 
 
 def windows_pairwise_pop_fst(X: FBM, ind_row, ind_col, groupIds, ngroups: int, chromosome, position=None, ploidy=None,
-                             window_size=None, step_size=None, size_unit="snp", min_loci=1, complete=False):
+                             window_size=None, step_size=None, size_unit="snp", min_loci=1, complete=False, route="staged"):
     """R/windows_pairwise_pop_fst.R:49-118 (type = "matrix"): window means of the by-locus Hudson numerators and
-    denominators, then their ratio (the reference always takes Hudson here, whatever `method` says, :62-65).  The two
-    m x P matrices stay in HBM.  -> dict(chromosome, start, end, fst (nw, P))"""
+    denominators, then their ratio (the reference always takes Hudson here, whatever `method` says, :62-65).
+    route = "staged": the two m x P matrices stay in HBM and tpg_window_stats reduces them; route = "fused":
+    tpg_windows_pairwise_pop_fst goes from the count table to the windows and never forms them (windows_fst).
+    -> dict(chromosome, start, end, fst (nw, P))"""
+    if route not in ("staged", "fused"):
+        raise ValueError("route must be 'staged' or 'fused'")
     v = View(X, ind_row, ind_col)
     if len(chromosome) != v.m:
         raise ValueError("loci_table must have the same number of rows as x.")
@@ -1418,6 +1422,9 @@ def windows_pairwise_pop_fst(X: FBM, ind_row, ind_col, groupIds, ngroups: int, c
         raise ValueError("min_loci must be positive.")
     if min_loci > window_size:
         raise ValueError("min_loci must be less than window_size.")
+    if route == "fused":
+        r = windows_fst(v, groupIds, ngroups, wr["lo"], wr["hi"], wr["pad_na"], min_loci, ploidy, "Hudson")
+        return dict(chromosome=wr["chromosome"], start=wr["start"], end=wr["end"], fst=r["fst"])
     pairs_c = np.ascontiguousarray(combn2(ngroups).T)
     P = pairs_c.shape[0]
     gid, pl = _i32(groupIds), _ploidy(v, ploidy)
@@ -1435,6 +1442,111 @@ def windows_pairwise_pop_fst(X: FBM, ind_row, ind_col, groupIds, ngroups: int, c
     with np.errstate(invalid="ignore", divide="ignore"):
         fst = num / den
     return dict(chromosome=wr["chromosome"], start=wr["start"], end=wr["end"], fst=fst)
+
+
+# include/tpg.h "windowed pairwise Fst": loci per chunk partial of the fused window scan (the order of a window's sum is
+# defined in terms of it)
+WINFST_CHUNK_LOCI = int(lib.tpg_winfst_chunk_loci()) if hasattr(lib, "tpg_winfst_chunk_loci") else 0
+
+
+def windows_fst_scratch_bytes(m: int, ngroups: int, P: int, nw: int) -> int:
+    """tpg_windows_fst_scratch_bytes: the device scratch one windows_fst call takes beyond the count table (host only)"""
+    return int(lib.tpg_windows_fst_scratch_bytes(int(m), int(ngroups), int(P), int(nw)))
+
+
+def _window_args(lo, hi, pad_na):
+    lo, hi = np.ascontiguousarray(lo, dtype=np.int64), np.ascontiguousarray(hi, dtype=np.int64)
+    pad = None if pad_na is None else np.ascontiguousarray(pad_na, dtype=np.uint8)
+    if len(hi) != len(lo) or (pad is not None and len(pad) != len(lo)):
+        raise ValueError("lo, hi and pad_na must have one entry per window")
+    return lo, hi, pad
+
+
+def windows_fst(v: View, groupIds, ngroups, lo, hi, pad_na=None, min_loci: int = 1, ploidy=None, method: str = "Hudson",
+                pairwise_combn=None, return_parts: bool = False) -> dict:
+    """tpg_windows_pairwise_pop_fst on explicit 0-based half-open locus ranges (include/tpg.h "windowed pairwise Fst"): from
+    the view's count table to the windows, without the m x P by-locus matrices.  -> dict(fst (nw, P)); return_parts adds
+    mean_num, mean_den (nw, P) and n_num, n_den (nw, P int32, -1 on a pad_na window)."""
+    if method not in FST_METHODS:
+        raise ValueError("'arg' should be one of 'Hudson', 'Nei87', 'WC84'")
+    lo, hi, pad = _window_args(lo, hi, pad_na)
+    nw = len(lo)
+    pairs = combn2(ngroups) if pairwise_combn is None else np.asarray(pairwise_combn, dtype=np.int32)
+    pairs_c = np.ascontiguousarray(pairs.T)  # (P, 2) row-major == 2 x P column-major
+    P = pairs_c.shape[0]
+    gid, pl = _i32(groupIds), _ploidy(v, ploidy)
+    fst = np.zeros((nw, P), order="F")
+    parts = [np.zeros((nw, P), order="F"), np.zeros((nw, P), order="F"), np.zeros((nw, P), dtype=np.int32, order="F"),
+             np.zeros((nw, P), dtype=np.int32, order="F")] if return_parts else [None] * 4
+    check(lib.tpg_windows_pairwise_pop_fst(v.ctx.h, v.h, _ptr(gid), int(ngroups), _ptr(pl), FST_METHODS[method], _ptr(pairs_c), P,
+                                           _ptr(lo), _ptr(hi), _ptr(pad), nw, int(min_loci), _ptr(fst), *[_ptr(a) for a in parts]))
+    out = dict(fst=fst)
+    if return_parts:
+        out.update(mean_num=parts[0], mean_den=parts[1], n_num=parts[2], n_den=parts[3])
+    return out
+
+
+def windows_nwise_pop_pbs(X: FBM, ind_row, ind_col, groupIds, ngroups: int, chromosome, position=None, ploidy=None,
+                          fst_method: str = "Hudson", return_fst: bool = False, window_size=None, step_size=None, size_unit="snp",
+                          min_loci=1, complete=False, triplets=None):
+    """R/windows_nwise_pop_pbs.R:55-126, type = "matrix": the population branch statistic of every triplet of populations
+    from windowed pairwise Fst.  fst_method is validated as nwise_pop_pbs validates it, but the windows are Hudson's: the
+    reference's windows_pairwise_pop_fst sets method = "Hudson" whatever it is given (R/windows_pairwise_pop_fst.R:62-65),
+    and that behaviour is kept.  The nw x P window Fst is written to device memory by the fused window scan and read there by
+    the PBS kernel.  triplets (not in the reference): a list of 1-based (a, b, c) with a < b < c restricts the output to them.
+    -> dict(chromosome, start, end, pbs (nw, 6 * n_triplets), names, [fst (nw, P)]), columns and names as nwise_pop_pbs."""
+    if ngroups < 3:
+        raise ValueError("At least 3 populations are required to compute PBS.")
+    if not isinstance(return_fst, (bool, np.bool_)):
+        raise ValueError("return_fst must be a logical value (TRUE or FALSE)")
+    if fst_method not in FST_METHODS:
+        raise ValueError("'arg' should be one of 'Hudson', 'Nei87', 'WC84'")
+    trips, tcols = _pbs_triplets(ngroups)
+    if triplets is not None:
+        col = {t: k for k, t in enumerate(trips)}
+        want = []
+        for t in triplets:
+            t = tuple(t)
+            if len(t) != 3 or any(not isinstance(x, (int, np.integer)) for x in t) or not 1 <= t[0] < t[1] < t[2] <= ngroups:
+                raise ValueError(f"a triplet must be three 1-based populations (a, b, c) with a < b < c <= {ngroups}, not {t!r}")
+            want.append(tuple(int(x) for x in t))
+        if not want:
+            raise ValueError("triplets must name at least one triplet")
+        tcols = np.ascontiguousarray(tcols[[col[t] for t in want]])
+        trips = want
+    v = View(X, ind_row, ind_col)
+    if len(chromosome) != v.m:
+        raise ValueError("loci_table must have the same number of rows as x.")
+    wr = window_index_ranges(chromosome, position, window_size, step_size, size_unit, complete)
+    if min_loci <= 0:
+        raise ValueError("min_loci must be positive.")
+    if min_loci > window_size:
+        raise ValueError("min_loci must be less than window_size.")
+    pairs_c = np.ascontiguousarray(combn2(ngroups).T)
+    P = pairs_c.shape[0]
+    gid, pl = _i32(groupIds), _ploidy(v, ploidy)
+    lo, hi, pad = _window_args(wr["lo"], wr["hi"], wr["pad_na"])
+    nw = len(lo)
+    ctx = v.ctx
+    res = dict(chromosome=wr["chromosome"], start=wr["start"], end=wr["end"])
+    out = np.zeros((nw, 6 * len(trips)), order="F")
+    f = np.zeros((nw, P), order="F") if return_fst else None
+    if nw > 0:
+        d_fst = ctx.dev_alloc(8 * nw * P)
+        try:
+            check(lib.tpg_windows_pairwise_pop_fst(ctx.h, v.h, _ptr(gid), int(ngroups), _ptr(pl), FST_METHODS["Hudson"],
+                                                   _ptr(pairs_c), P, _ptr(lo), _ptr(hi), _ptr(pad), nw, int(min_loci), d_fst,
+                                                   None, None, None, None))
+            check(lib.tpg_pbs_from_fst(ctx.h, d_fst, nw, P, _ptr(tcols), len(trips), _ptr(out)))
+            if return_fst:
+                check(lib.tpg_dev_to_host(ctx.h, _ptr(f), d_fst, f.nbytes))
+        finally:
+            ctx.dev_free(d_fst)
+    res["pbs"] = out
+    if return_fst:
+        res["fst"] = f
+    res["names"] = _pbs_names(trips)
+    return res
 
 
 # include/tpg.h "Tajima's D": loci per partial sum of pop_tajimas_d (results do not depend on it)
@@ -2408,6 +2520,15 @@ def _pbs_triplets(ngroups):
     return trips, np.ascontiguousarray(cols, dtype=np.int32)
 
 
+def _pbs_names(trips):
+    """the six columns of every triplet, as R/nwise_pop_pbs.R names them"""
+    names = []
+    for (a, b, c) in trips:
+        for stat in ("pbs", "pbsn1"):
+            names += [f"{stat}_{a}.{b}.{c}", f"{stat}_{b}.{a}.{c}", f"{stat}_{c}.{a}.{b}"]
+    return names
+
+
 def nwise_pop_pbs(X: FBM, ind_row, ind_col, groupIds, ngroups: int, ploidy=None, fst_method: str = "Hudson",
                   return_fst: bool = False):
     """R/nwise_pop_pbs.R:36-156, type = "matrix": by-locus PBS and normalised PBS for every triplet of populations.
@@ -2438,11 +2559,7 @@ def nwise_pop_pbs(X: FBM, ind_row, ind_col, groupIds, ngroups: int, ploidy=None,
             res["fst"] = f
     finally:
         ctx.dev_free(d_fst)
-    names = []
-    for (a, b, c) in trips:
-        for stat in ("pbs", "pbsn1"):
-            names += [f"{stat}_{a}.{b}.{c}", f"{stat}_{b}.{a}.{c}", f"{stat}_{c}.{a}.{b}"]
-    res["names"] = names
+    res["names"] = _pbs_names(trips)
     return res
 
 
