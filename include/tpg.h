@@ -1429,7 +1429,10 @@ int tpg_hclust_r_merge(int64_t n, const int32_t* merge_a, const int32_t* merge_b
  *   Rounding (eps as above): var_load(j,a) lies within E = (n_pca + 1) eps sum_p |V_jp| |l_pa| of the exact product; its square
  *   within q = 2 |var_load| E + E^2; c_a within Ec = sum_j q_j + (m + 2) eps c_a; var_contr within q / c_a + var_contr Ec / c_a +
  *   2 eps var_contr.
- * Out of scope: predict() on new individuals, cross-validation of n_pca (xvalDapc), priors other than the group proportions. */
+ * predict() on new individuals is the same arithmetic on their scores x (the first n_pca columns): z = (x - mu)' S[:, :n_da]
+ *   with mu = sum_g pi_g mu_g (g ascending) from the prior and means gt_dapc returns, m_g as above, the posterior and the tie rule
+ *   as above; it is formed in Python (predict_gt_dapc) and needs no entry point here.
+ * Out of scope: cross-validation of n_pca (xvalDapc), priors other than the group proportions. */
 /* host only.  With Lmax = min(d, G - 1): prior[G], means G x d, scaling d x Lmax, svd[Lmax] (columns / entries beyond *n_lda are
  * 0), ind_coord n x Lmax and grp_coord G x Lmax (the first *n_da_out columns are written), posterior n x G, assign[n] (0-based);
  * all column-major host memory; mu_out[d] may be NULL */
@@ -1440,6 +1443,35 @@ int tpg_lda(const double* X, int64_t n, int d, const int32_t* grp0, int G, int n
  * column-major, host or device memory.  1 <= n_pca <= 64, 1 <= n_da <= 64 */
 int tpg_dapc_var_contr(tpg_ctx* ctx, const double* V, int64_t m, int64_t ldv, int n_pca, const double* loadings, int n_da,
                        double* var_load, double* var_contr);
+
+/* ---- OADP projection (predict(pca, new_data, project_method = "OADP"), R/predict_gt_pca.R:177-182 -> bigsnpr::OADP_proj; bigsnpr
+ * is not among the reference's sources, so the projection is defined HERE from first principles, RECALLED FROM Zhang, Dey & Lee
+ * (2020), NOT PINNED) ---------------------------------------------------------------------------------------------------------
+ * Per new individual: l (K) its row of XV, s its X_norm (|z|^2 with missing -> 0), d (K) the singular values of the PCA,
+ * positive and descending.
+ *   1. rho^2 = max(s - sum_k l_k^2, 0).  M is (K+1) x (K+1): the top-left block diag(d), the last row (l_1 .. l_K, rho), the rest
+ *      of the last column 0 -- the reference panel plus the new row in the basis [V, r / rho]; M M' = [[D^2, D l], [l'D, s]].
+ *   2. M = A S B'; the K largest singular values S_K; A1 the top K x K block of their columns of A, a the last row.
+ *   3. Procrustes of the augmented reference scores U A1 S_K onto U D, rotation and scale, no translation (only XV, X_norm and d
+ *      are at hand, as in bigsnpr):  C = S_K A1' D = P Sigma W',  R = P W',  c = tr Sigma / |A1 S_K|_F^2.
+ *   4. The row of the result is c (a S_K) R.
+ * The signs of singular vectors and rotations within repeated singular values cancel.  l = 0 with s < d_K^2 gives exactly 0: an
+ * individual with every genotype missing projects to the origin.  sigma_min(C) <= 2^-40 sigma_max(C): R is not unique, the row
+ * is NaN and counted in *n_degenerate (0 is the expected value); l = 0 with s > d_K^2 is such a row, the new sample's own
+ * direction displacing PC K.
+ * How it is computed (csrc/host/host_oadp.h, one text for host and device): both decompositions are a one-sided Jacobi iteration
+ * in a fixed round-robin order -- on the columns of M, whose limit is A S itself, and on C' = D (A1 S_K) with the row a S_K
+ * carried along, so that neither C'C nor a matrix of singular vectors is formed; a pair of columns is left alone once
+ * |a_i . a_j| <= 2^-52 |a_i| |a_j|, at most 30 sweeps.  A row's bits depend on its own l, s and on d only: not on n, not on
+ * its position.
+ * XV and out are n x K column-major, X_norm[n], sval[K], host or device memory.  1 <= K <= 32, else TPG_EINVAL; sval not positive
+ * or not descending: TPG_EINVAL; a value of XV, X_norm or sval that is not finite: TPG_ENUMERIC. */
+int tpg_oadp_proj(tpg_ctx* ctx, const double* XV, const double* X_norm, int64_t n, int K, const double* sval, double* out,
+                  int64_t* n_degenerate);
+/* the sweep of tpg_fbm256_prod_and_rowSumsSq over the view (V m x K), then the projection, XV and X_norm staying on the device;
+ * out n x K, XV_out n x K (the "simple" projection, may be NULL) */
+int tpg_predict_oadp(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale, const double* V, int K,
+                     const double* sval, double* out, double* XV_out /* may be NULL */, int64_t* n_degenerate);
 
 #ifdef __cplusplus
 }

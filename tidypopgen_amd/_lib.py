@@ -342,6 +342,9 @@ PROTOTYPES = {
     # ---- DAPC
     "tpg_lda": (ci, [vp, i64, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tpg_dapc_var_contr": (ci, [vp, vp, i64, i64, ci, vp, ci, vp, vp]),
+    # ---- OADP projection
+    "tpg_oadp_proj": (ci, [vp, vp, vp, i64, ci, vp, vp, vp]),
+    "tpg_predict_oadp": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
 }
 
 for _name, (_restype, _argtypes) in PROTOTYPES.items():

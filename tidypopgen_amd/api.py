@@ -2507,6 +2507,35 @@ def gt_dapc(x: dict, pop=None, n_pca: Optional[int] = None, n_da: Optional[int] 
     return res
 
 
+def predict_gt_dapc(dapc: dict, scores_new) -> dict:
+    """predict() of a gt_dapc result for new individuals, include/tpg.h "DAPC": scores_new holds their PCA scores (the output of
+    predict_gt_pca / predict_gt_pca_oadp on the PCA the DAPC was built on), of which the first dapc["n.pca"] columns are used
+    -> dict(ind.coord (n x n.da), posterior (n x G), assign (a label of dapc["levels"] per individual)).  Host arithmetic on what
+    gt_dapc returned: mu = sum_g prior_g means_g (g ascending), z = (x - mu) loadings, m_g = (means_g - mu) loadings,
+    q_ig = |z_i - m_g|^2 / 2 - ln prior_g, the posterior exp(-(q_ig - min_g q_ig)) normalised, the smallest q (smaller g on a tie)
+    assigned."""
+    x = np.asarray(scores_new, dtype=np.float64)
+    n_pca = int(dapc["n.pca"])
+    if x.ndim != 2 or x.shape[1] < n_pca:
+        raise ValueError(f"scores_new must be a matrix with at least n.pca = {n_pca} columns")
+    x = x[:, :n_pca]
+    prior, means = np.asarray(dapc["prior"], dtype=np.float64), np.asarray(dapc["means"], dtype=np.float64)
+    S = np.asarray(dapc["loadings"], dtype=np.float64)
+    G = len(prior)
+    if means.shape != (G, n_pca) or S.shape[0] != n_pca:
+        raise ValueError("dapc is not the result of gt_dapc: prior, means and loadings do not fit n.pca")
+    mu = np.zeros(n_pca)
+    for g in range(G):
+        mu += prior[g] * means[g]
+    z = (x - mu[None, :]) @ S
+    mg = (means - mu[None, :]) @ S
+    q = 0.5 * ((z[:, None, :] - mg[None, :, :]) ** 2).sum(axis=2) - np.log(prior)[None, :]
+    best = np.argmin(q, axis=1)  # (the first of equal minima: the smaller g)
+    post = np.exp(-(q - q[np.arange(len(q)), best][:, None])) if len(q) else np.zeros((0, G))
+    post /= post.sum(axis=1, keepdims=True)
+    return {"ind.coord": np.asfortranarray(z), "posterior": np.asfortranarray(post), "assign": np.asarray(dapc["levels"])[best]}
+
+
 def _pbs_triplets(ngroups):
     """utils::combn(levels, 3) order, with the Fst columns of (p1.p2, p1.p3, p2.p3) in combn(levels, 2) order"""
     pairs = combn2(ngroups)  # (2, P), 1-based
@@ -3168,15 +3197,17 @@ def predict_gt_pca(pca: dict, X: Optional[FBM] = None, ind_row=None, ind_col=Non
       "none"           X V on the imputed code table (bigstatsr::big_prodMat, :141-149; missing values are not allowed)
       "simple"         fbm256_prod_and_rowSumsSq, missing genotypes count as 0 (:157-175)
       "least_squares"  per individual, regress its non-missing scaled genotypes on v[, lsq_pcs] (:187-232)
-      "OADP"           XV and the squared norms come from the same device sweep, but the final K x K transform is
-                       bigsnpr's OADP_proj, which is not in the reference checkout: use oadp_inputs() and bigsnpr."""
+      "OADP"           not forwarded from here: predict_gt_pca_oadp() is the projection (the device sweep, then the
+                       per-individual transform of include/tpg.h "OADP projection" in one kernel); bigsnpr's OADP_proj is not in
+                       the reference checkout, and oadp_inputs() returns the XV and X_norm it takes."""
     if project_method not in ("none", "simple", "OADP", "least_squares"):
         raise ValueError("'arg' should be one of 'none', 'simple', 'OADP', 'least_squares'")
     if X is None:
         return np.asfortranarray(pca["u"] * pca["d"])
     if project_method == "OADP":
-        raise NotImplementedError("OADP projection calls bigsnpr::OADP_proj (third-party, not in the reference checkout); "
-                                  "oadp_inputs() returns the XV and X_norm it takes")
+        raise NotImplementedError("project_method = 'OADP' is not forwarded from predict_gt_pca: call predict_gt_pca_oadp() (the "
+                                  "projection of include/tpg.h \"OADP projection\"; bigsnpr::OADP_proj itself is third-party and "
+                                  "not in the reference checkout, oadp_inputs() returns the XV and X_norm it takes)")
     Vl = np.asfortranarray(pca["v"], dtype=float)
     if project_method in ("none", "simple"):
         v = View(X, ind_row, ind_col, code256=code256)
@@ -3215,6 +3246,40 @@ def oadp_inputs(pca: dict, X: FBM, ind_row=None, ind_col=None, code256=CODE_IMPU
     """(XV, X_norm) that predict(project_method = "OADP") hands to bigsnpr::OADP_proj (R/predict_gt_pca.R:157-181)"""
     v = View(X, ind_row, ind_col, code256=code256)
     return _prod_and_rss(v, pca["center"], pca["scale"], np.asfortranarray(pca["v"], dtype=float))
+
+
+def oadp_proj(XV, X_norm, d, ctx: Optional[Context] = None, return_degenerate: bool = False):
+    """tpg_oadp_proj: the OADP projection of include/tpg.h from the "simple" projection XV (n x K), the squared norms X_norm (n)
+    of the new individuals and the K <= 32 singular values d of the PCA -> the projected scores (n x K) [, n_degenerate: the
+    rows whose Procrustes rotation is not unique; they are NaN]"""
+    ctx = ctx or default_context()
+    xv, nrm, sv = _scores(XV), _f64(X_norm), _f64(d)
+    n, K = xv.shape
+    if nrm.shape != (n,) or sv.shape != (K,):
+        raise ValueError(f"XV is {n} x {K}: X_norm must hold {n} values and d {K}")
+    out = np.zeros((n, K), order="F")
+    deg = C.c_int64()
+    check(lib.tpg_oadp_proj(ctx.h, _ptr(xv), _ptr(nrm), n, K, _ptr(sv), _ptr(out), C.byref(deg)))
+    return (out, int(deg.value)) if return_degenerate else out
+
+
+def predict_gt_pca_oadp(pca: dict, X: FBM, ind_row=None, ind_col=None, code256=CODE_IMPUTE_PRED, return_degenerate: bool = False):
+    """predict(pca, new_data, project_method = "OADP") (R/predict_gt_pca.R:153-186) with the transform of include/tpg.h "OADP
+    projection" in place of bigsnpr::OADP_proj: the sweep of fbm256_prod_and_rowSumsSq over the new individuals, then the
+    per-individual projection, without XV or the norms leaving the device (tpg_predict_oadp).  Arguments as predict_gt_pca;
+    the PCA may hold at most 32 components -> the projected scores (n x K) [, n_degenerate]"""
+    v = View(X, ind_row, ind_col, code256=code256)
+    V = np.asfortranarray(pca["v"], dtype=float)
+    if V.shape[0] != v.m:
+        raise ValueError("Incompatibility between dimensions.")  # bigstatsr myassert_size
+    K = V.shape[1]
+    center, scale, sv = _f64(pca["center"]), _f64(pca["scale"]), _f64(pca["d"])
+    if sv.shape != (K,):
+        raise ValueError(f"pca['d'] must hold {K} singular values")
+    out = np.zeros((v.n, K), order="F")
+    deg = C.c_int64()
+    check(lib.tpg_predict_oadp(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(V), K, _ptr(sv), _ptr(out), None, C.byref(deg)))
+    return (out, int(deg.value)) if return_degenerate else out
 
 
 def _prod_and_rss(v: View, center, scale, V):

@@ -403,6 +403,10 @@ int tpg_pca_gram_allreduce(tpg_ctx* ctx, tpg_comm* comm, double* d_K, int64_t n)
 // out[j + k m] = sum_i (g_ij - center[j]) * inv_scale[j] * U[i + k n], a missing genotype adding 0; waits for the stream
 int tpg_sweep_loci_rowscale(tpg_ctx* ctx, const struct tpg_view* v, const double* d_center, const double* d_inv_scale, const double* d_U,
                             int K, double* d_out);
+// pca.hip: the sweep of tpg_fbm256_prod_and_rowSumsSq with every array in device memory (d_scale is the scale, not its inverse):
+// d_XV n x K, d_rss[n]; waits for the stream
+int tpg_sweep_indiv_colscale(tpg_ctx* ctx, const struct tpg_view* v, const double* d_center, const double* d_scale, const double* d_V,
+                             int K, double* d_XV, double* d_rss);
 // stream.hip: a tpg_multi_* analysis of a host FBM with every device streaming its share in blocks under `budget` bytes
 int tpg_multi_stream_host(tpg_multi* mg, const uint8_t* fbm_bytes, int64_t nrow, int64_t ncol, size_t budget, const tpg_stream_job* job);
 int tpg_comm_agree(tpg_comm* comm, int rc);  // all ranks get the same status (the worst any of them passed in)

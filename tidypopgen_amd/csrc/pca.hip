@@ -310,15 +310,20 @@ extern "C" int tpg_fbm256_prod_and_rowSumsSq(tpg_ctx* ctx, const tpg_view* v, co
   OutBuf oxv, orss;
   TPG_TRY(oxv.init(XV, sizeof(double) * (size_t)v->n * (size_t)K));
   TPG_TRY(orss.init(rss, sizeof(double) * (size_t)v->n));
-  DevBuf d_inv;
-  TPG_TRY(d_inv.alloc_n<double>((size_t)v->m));
-  TPG_LAUNCH(ctx, "inv_scale", tpg_inv_kernel, dim3(1024), dim3(256), 0, is.dev<double>(), v->m, d_inv.as<double>());
-  TPG_TRY(tpg_view_need_T(ctx, v));
-  TPG_TRY(run_sweep(ctx, SW_COLSCALE, v->T, v->Q * 4, v->KG, v->n, v->m, ic.dev<double>(), d_inv.as<double>(), iv.dev<double>(),
-                    v->m, K, oxv.dev<double>(), nullptr, orss.dev<double>()));
-  d_inv.free();
+  TPG_TRY(tpg_sweep_indiv_colscale(ctx, v, ic.dev<double>(), is.dev<double>(), iv.dev<double>(), K, oxv.dev<double>(), orss.dev<double>()));
   TPG_TRY(oxv.commit(ctx));
   return orss.commit(ctx);
+}
+
+// common.h: the same sweep for other translation units (oadp.hip), device pointers throughout
+int tpg_sweep_indiv_colscale(tpg_ctx* ctx, const tpg_view* v, const double* d_center, const double* d_scale, const double* d_V, int K,
+                             double* d_XV, double* d_rss) {
+  DevBuf d_inv;
+  TPG_TRY(d_inv.alloc_n<double>((size_t)v->m));
+  TPG_LAUNCH(ctx, "inv_scale", tpg_inv_kernel, dim3(1024), dim3(256), 0, d_scale, v->m, d_inv.as<double>());
+  TPG_TRY(tpg_view_need_T(ctx, v));
+  return run_sweep(ctx, SW_COLSCALE, v->T, v->Q * 4, v->KG, v->n, v->m, d_center, d_inv.as<double>(), d_V, v->m, K, d_XV, nullptr,
+                   d_rss);
 }
 
 // out[i][k] = sum over the loci j where individual i is typed of Tab[j][k]: the per-individual masked sums behind
