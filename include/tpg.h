@@ -1114,7 +1114,8 @@ int tpg_pca_partial_svd(tpg_ctx* ctx, const tpg_view* v, int k, double* d, doubl
                         double* center, double* scale, double* square_frobenius);
 /* gt_pca_randomSVD (R/gt_pca_randomSVD.R:77-135): the same truncated SVD accepted at the
  * relative residual `tol` of the reference's big_randomSVD / RSpectra path (default there 1e-4):
- * |K u_j - d_j^2 u_j| <= tol * d_1^2 for every returned pair. */
+ * |K u_j - d_j^2 u_j| <= tol * d_1^2 for every returned pair.  This entry forms the n x n Gram matrix K = Z Z' (8 n^2
+ * bytes) and iterates on it; tpg_pca_random_svd_op ("PCA by operator products" below) is the same iteration without it. */
 int tpg_pca_random_svd(tpg_ctx* ctx, const tpg_view* v, int k, double tol, double* d, double* u, double* vload,
                        double* center, double* scale, double* square_frobenius);
 /* The pieces of tpg_pca_partial_svd for SNP-block shards on several GPUs: every rank computes the Gram
@@ -1144,6 +1145,51 @@ int tpg_square_frobenius(tpg_ctx* ctx, const tpg_view* v, const double* center, 
 /* out (n x K) [i, k] = sum of Tab[j, k] (m x K) over the loci j at which individual i is typed: the masked sums
  * behind predict(project_method = "least_squares") (R/predict_gt_pca.R:221-228) */
 int tpg_fbm256_valid_prod(tpg_ctx* ctx, const tpg_view* v, const double* Tab, int K, double* out);
+
+/* ---- PCA by operator products (gt_pca_randomSVD, R/gt_pca_randomSVD.R:6-7: "linear in time in all dimensions and very
+ * memory-efficient"; bigstatsr::big_randomSVD only ever multiplies the scaled matrix by vectors) ------------------------------
+ * The scaled matrix Z = (G - 1 center') diag(scale)^-1 of a view (n x m, codes 0 / 1 / 2) as an operator, never as a Gram
+ * matrix: the two products on the int8 matrix cores, and the truncated SVD that needs nothing else.  Memory beyond the view
+ * is linear in n and in m (tpg_pca_op_scratch_bytes), where tpg_pca_random_svd takes 8 n^2 bytes for the Gram matrix.
+ *
+ * tpg_pca_zt_prod: W (m x b) = Z'Q, Q n x b.  tpg_pca_z_prod: Y (n x b) = Z W, W m x b.  Column-major, host or device memory,
+ *   1 <= b <= 64 (else TPG_EINVAL); a missing genotype in the view or a zero in `scale`: TPG_ENUMERIC, as tpg_pca_center_scale;
+ *   n >= 2^24: TPG_EINVAL.
+ *   Arithmetic.  The operand -- Q, or W[j, c] / scale[j] -- is rounded to fixed point with ONE binary exponent per column c
+ *   (the entry's error is at most 2^-40 times the column's largest magnitude amax_c), the integer products and sums are exact,
+ *   the centring term uses the column sums of the ROUNDED operand, and the result is rounded to FP64 once before the centring
+ *   term is subtracted (and, for Z'Q, the quotient by scale[j] taken).  So |W - Z'Q|[j, c] <= 2 n 2^-40 amax_c / scale[j] and
+ *   |Y - Z W|[i, c] <= 2 m 2^-40 amax_c, plus the few FP64 roundings of the last step (tests/pcaop_ref.py spells them out);
+ *   measured, the composition Z (Z'q) is within 2.2e-12 of the FP64 sweeps in norm (1.5e-12 at 5 000 x 1 000 000, 2.1e-12 at
+ *   100 000 x 100 000; DESIGN.md 3.17, profiles/pcaop_probe.txt).  A column of zeros gives a
+ *   column of exact zeros, a column with a NaN or an infinity a column of NaN.  The bits of a result do not depend on how the
+ *   contraction is split over workgroups, and a repeated call returns the same bits.
+ *
+ * tpg_pca_random_svd_op: the outputs and the acceptance contract of tpg_pca_random_svd -- d[k], u n x k, v m x k, center[m],
+ *   scale[m], square_frobenius (may be NULL); |Z Z'u_j - d_j^2 u_j| <= tol d_1^2 for every returned pair, the product taken by
+ *   the operator -- without the n x n matrix.  *n_apply (may be NULL): how many times Z Z' was applied to a block.
+ *   TPG_EINVAL: k > 52 (more components take the Gram route, whose batches deflate the matrix itself), k > n or m, tol outside
+ *   [TPG_PCA_OP_TOL_FLOOR, 1) -- the floor is 100 times the operator's measured relative error (2.1e-10, so 1e-9 as a power of
+ *   ten) and not below the 1e-8 the Gram route is tested at: 1e-8 --, n >= 2^24.
+ *   Measured (one run): one application to 32 columns 4.5 ms at 5 000 x 1 000 000 where the FP64 sweeps take 27.9;
+ *   the whole call at k = 20, tol = 1e-4 75 ms there against the Gram route's 21, and 46 ms against 276 at 40 000 x 100 000.  Not
+ *   measured: any spread, the n at which the routes cross at a fixed m, the Gram route at n = 100 000.  TPG_ENUMERIC as tpg_pca_random_svd.  The random start has
+ *   a fixed seed: the result is a function of the view alone.
+ * tpg_pca_op_scratch_bytes: the device memory a tpg_pca_random_svd_op call plans beyond the view's two layouts (on the 256 CUs
+ *   of an MI355X; host only, no context); 0 for arguments the call would refuse.  Doubling n or m at most doubles it, up to the
+ *   padding of the tiles. */
+#define TPG_PCA_OP_TOL_FLOOR 1e-8
+int tpg_pca_zt_prod(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale, const double* Q, int b,
+                    double* W);
+int tpg_pca_z_prod(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale, const double* W, int b,
+                   double* Y);
+int tpg_pca_random_svd_op(tpg_ctx* ctx, const tpg_view* v, int k, double tol, double* d, double* u, double* vload,
+                          double* center, double* scale, double* square_frobenius, int* n_apply);
+size_t tpg_pca_op_scratch_bytes(int64_t n, int64_t m, int k);
+/* *fits = 1 when the device memory of the Gram route -- the 8 n^2 bytes of the matrix plus the eigen solver's blocks -- is at most
+ * half of the device's free memory at the time of the call, else 0: the rule behind gt_pca_randomSVD(route = "auto"), which takes
+ * the operator route only when this says 0.  A rule about what CAN run, not about which route is faster. */
+int tpg_pca_gram_route_fits(tpg_ctx* ctx, int64_t n, int k, int* fits);
 
 /* ---- pcadapt (gt_pcadapt, R/gt_pcadapt.R:44-86 around bigsnpr::snp_pcadapt; bigsnpr is not among the reference's sources, so
  * the arithmetic is defined HERE.  Recalled from bigsnpr / pcadapt: the statistic is a robust Mahalanobis distance of the

@@ -304,6 +304,12 @@ PROTOTYPES = {
     "tpg_fbm256_prod_and_rowSumsSq": (ci, [vp, vp, vp, vp, vp, ci, vp, vp]),
     "tpg_square_frobenius": (ci, [vp, vp, vp, vp, vp]),
     "tpg_fbm256_valid_prod": (ci, [vp, vp, vp, ci, vp]),
+    # ---- PCA by operator products
+    "tpg_pca_zt_prod": (ci, [vp, vp, vp, vp, vp, ci, vp]),
+    "tpg_pca_z_prod": (ci, [vp, vp, vp, vp, vp, ci, vp]),
+    "tpg_pca_random_svd_op": (ci, [vp, vp, ci, f64, vp, vp, vp, vp, vp, vp, vp]),
+    "tpg_pca_op_scratch_bytes": (sz, [i64, i64, ci]),
+    "tpg_pca_gram_route_fits": (ci, [vp, i64, ci, vp]),
     # ---- pcadapt
     "tpg_select_tile": (i64, []),
     "tpg_col_median_mad": (ci, [vp, vp, i64, ci, i64, vp, vp, vp]),

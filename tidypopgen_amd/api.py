@@ -3167,23 +3167,83 @@ def gt_impute_simple(X: FBM, method: str = "mode", seed: int = 0) -> FBM:
     return X
 
 
+PCA_OP_TOL_FLOOR = 1e-8  # TPG_PCA_OP_TOL_FLOOR of include/tpg.h: the tightest tol the operator route takes
+PCA_ROUTES = ("gram", "operator", "auto")
+
+
+def _pca_op_block(v: View, center, scale, X, rows: int, what: str) -> tuple:
+    center, scale = _f64(center), _f64(scale)
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    if X.ndim != 2 or X.shape[0] != rows:
+        raise ValueError(f"{what} must have {rows} rows, not shape {X.shape}")
+    if center.shape != (v.m,) or scale.shape != (v.m,):
+        raise ValueError(f"center and scale must have {v.m} entries")
+    return center, scale, np.asfortranarray(X)
+
+
+def pca_zt_prod(v: View, center, scale, Q) -> np.ndarray:
+    """tpg_pca_zt_prod: W (m x b) = Z'Q on the int8 matrix cores, Z = (G - 1 center') / scale, Q n x b, 1 <= b <= 64
+    (include/tpg.h "PCA by operator products")"""
+    center, scale, Q = _pca_op_block(v, center, scale, Q, v.n, "Q")
+    b = Q.shape[1]
+    W = np.zeros((v.m, max(b, 1)), order="F")
+    check(lib.tpg_pca_zt_prod(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(Q), b, _ptr(W)))
+    return W
+
+
+def pca_z_prod(v: View, center, scale, W) -> np.ndarray:
+    """tpg_pca_z_prod: Y (n x b) = Z W on the int8 matrix cores, W m x b, 1 <= b <= 64"""
+    center, scale, W = _pca_op_block(v, center, scale, W, v.m, "W")
+    b = W.shape[1]
+    Y = np.zeros((v.n, max(b, 1)), order="F")
+    check(lib.tpg_pca_z_prod(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(W), b, _ptr(Y)))
+    return Y
+
+
+def pca_op_scratch_bytes(n: int, m: int, k: int) -> int:
+    """tpg_pca_op_scratch_bytes: the device memory gt_pca_randomSVD(route="operator") plans beyond the view (host only)"""
+    return int(lib.tpg_pca_op_scratch_bytes(int(n), int(m), int(k)))
+
+
 def gt_pca_randomSVD(X: FBM, ind_row=None, ind_col=None, k: int = 10, tol: float = 1e-4, total_var: bool = True,
-                     code256=CODE_IMPUTE_PRED, impute: Optional[str] = None, impute_seed: int = 0) -> dict:
+                     code256=CODE_IMPUTE_PRED, impute: Optional[str] = None, impute_seed: int = 0,
+                     route: str = "gram") -> dict:
     """R/gt_pca_randomSVD.R:77-135.  The reference reaches the truncated SVD of the scaled matrix through
     bigstatsr::big_randomSVD (RSpectra::svds on the implicit operator), which accepts a singular triplet at the
-    relative residual `tol`; the device path runs the same Gram + subspace iteration as gt_pca_partialSVD and stops
-    at that tolerance: |K u_j - d_j^2 u_j| <= tol * d_1^2."""
+    relative residual `tol`: |Z Z'u_j - d_j^2 u_j| <= tol * d_1^2.  Two routes to it, the same subspace iteration in both:
+      "gram"      (default) the n x n Gram matrix of gt_pca_partialSVD, then the iteration on it: 8 n^2 bytes;
+      "operator"  the iteration on Q -> Z (Z'Q) by the int8 operator products (pca_zt_prod, pca_z_prod): memory linear in n
+                  and in m (pca_op_scratch_bytes), k <= 52, tol >= PCA_OP_TOL_FLOOR; the dict gains n_apply, the number of
+                  operator applications;
+      "auto"      the operator route only when the Gram route's memory does not fit in half of the device's free memory --
+                  a rule about what can run, not about speed.
+    The dict says which one ran: route = "gram" | "operator"."""
     if not (0 < tol < 1):
         raise ValueError("tol must be in (0, 1)")
+    if route not in PCA_ROUTES:
+        raise ValueError(f"route must be one of {PCA_ROUTES}, not {route!r}")
     v = _pca_view(X, ind_row, ind_col, code256, impute, impute_seed)
+    if route == "auto":
+        fits = C.c_int()
+        check(lib.tpg_pca_gram_route_fits(v.ctx.h, v.n, k, C.byref(fits)))
+        route = "gram" if fits.value else "operator"
     d = np.zeros(k)
     u = np.zeros((v.n, k), order="F")
     vl = np.zeros((v.m, k), order="F")
     center, scale = np.zeros(v.m), np.zeros(v.m)
     fro = C.c_double()
-    check(lib.tpg_pca_random_svd(v.ctx.h, v.h, k, tol, _ptr(d), _ptr(u), _ptr(vl), _ptr(center),
-                                 _ptr(scale), C.byref(fro) if total_var else None))
-    out = dict(d=d, u=u, v=vl, center=center, scale=scale, method="randomSVD")
+    napp = C.c_int()
+    if route == "gram":
+        check(lib.tpg_pca_random_svd(v.ctx.h, v.h, k, tol, _ptr(d), _ptr(u), _ptr(vl), _ptr(center),
+                                     _ptr(scale), C.byref(fro) if total_var else None))
+    else:
+        check(lib.tpg_pca_random_svd_op(v.ctx.h, v.h, k, tol, _ptr(d), _ptr(u), _ptr(vl), _ptr(center),
+                                        _ptr(scale), C.byref(fro) if total_var else None, C.byref(napp)))
+    out = dict(d=d, u=u, v=vl, center=center, scale=scale, method="randomSVD", route=route)
+    if route == "operator":
+        out["n_apply"] = napp.value
     if total_var:
         out["square_frobenius"] = fro.value
     return out

@@ -407,6 +407,25 @@ int tpg_sweep_loci_rowscale(tpg_ctx* ctx, const struct tpg_view* v, const double
 // d_XV n x K, d_rss[n]; waits for the stream
 int tpg_sweep_indiv_colscale(tpg_ctx* ctx, const struct tpg_view* v, const double* d_center, const double* d_scale, const double* d_V,
                              int K, double* d_XV, double* d_rss);
+// pcaop.hip: the scaled genotype matrix Z = (G - 1c')S^-1 of a view as an operator on int8 MFMA.  The struct owns the
+// scratch of both halves (tpg_pcaop_work_bytes: digit fragments, int32 partial tiles, the m x bmax block between the
+// halves), all of it linear in n and in m; center and scale stay the caller's (device memory).  The view must hold no
+// missing value and the scale no zero -- the callers' counts check that.  Nothing here waits for the stream.
+struct TpgPcaOp {
+  const struct tpg_view* v = nullptr;
+  const double *d_center = nullptr, *d_scale = nullptr;
+  int bmax = 0;
+  uint4* UD = nullptr;
+  int32_t* part = nullptr;
+  double *W = nullptr, *stat = nullptr;
+  int n_apply = 0;  // applications of Z Z' so far
+  DevArena mem;
+};
+int tpg_pcaop_init(tpg_ctx* ctx, TpgPcaOp* op, const struct tpg_view* v, const double* d_center, const double* d_scale, int bmax);
+size_t tpg_pcaop_work_bytes(int64_t n, int64_t m, int bmax, int num_cu);
+int tpg_pcaop_zt(tpg_ctx* ctx, TpgPcaOp* op, const double* d_Q, int b, double* d_W);     // W (m x b) = Z'Q
+int tpg_pcaop_z(tpg_ctx* ctx, TpgPcaOp* op, const double* d_W, int b, double* d_Y);      // Y (n x b) = Z W
+int tpg_pcaop_apply(tpg_ctx* ctx, TpgPcaOp* op, const double* d_Q, int b, double* d_Y);  // Y = Z (Z'Q), b <= bmax
 // stream.hip: a tpg_multi_* analysis of a host FBM with every device streaming its share in blocks under `budget` bytes
 int tpg_multi_stream_host(tpg_multi* mg, const uint8_t* fbm_bytes, int64_t nrow, int64_t ncol, size_t budget, const tpg_stream_job* job);
 int tpg_comm_agree(tpg_comm* comm, int rc);  // all ranks get the same status (the worst any of them passed in)

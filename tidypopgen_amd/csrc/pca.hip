@@ -1189,6 +1189,9 @@ struct EigWork {
   // tpg_push_small / tpg_fetch_small): no copy engine and no stream synchronisation anywhere in the iteration
   double* xdev = nullptr;
   DevArena mem;  // owns part, gpart, lam_dev, cdev, dtmp and xdev
+  // the second kind of operator: K = Z Z' of a view, never formed -- part = Z (Z'Q) by the int8 halves of pcaop.hip (K is
+  // NULL then); everything else of the iteration works on n x b blocks and is the same for both
+  TpgPcaOp* op = nullptr;
   int init() {
     // K splits: ONE round of workgroups (two fit a CU: 66 KiB of LDS each) -- at n = 5 000, 79 row blocks x 6 splits = 474
     // of 512 places, 89.5 us per product; 16 splits (2.5 rounds, the last half empty) 94.6, 13 splits (two rounds and three
@@ -1197,6 +1200,7 @@ struct EigWork {
     S = 1;
     while (row_blocks * S < 4 * ctx->num_cu && S < 32 && n / (S * 2) >= 64) S *= 2;  // (short ranges: 1 000 rows take 4)
     S = std::max(1, std::min((int)S, 2 * ctx->num_cu / row_blocks));
+    if (op) S = 1;
     // A'B over chunks of rows: a workgroup per 32 (64) rows, so that a product on a few thousand rows is one short round
     // of many workgroups instead of a long loop in a few
     rows_per_chunk = n <= 4096 ? 32 : 64;
@@ -1217,8 +1221,12 @@ struct EigWork {
   }
   // Y = alpha K' Q + beta Y1 + gamma Y0   with K' = K - L diag(lam) L'; no host synchronisation
   int apply(const double* Q, double alpha, const double* Y1, double beta, const double* Y0, double gamma, double* Y) {
-    dim3 grid((unsigned)((n + 63) / 64), (unsigned)S);  // 4 waves x 16 rows per workgroup
-    TPG_LAUNCH(ctx, "eig_symm_apply", tpg_symm_apply_kernel, grid, dim3(256), 0, K, n, Q, b, S, part);
+    if (op) {
+      TPG_TRY(tpg_pcaop_apply(ctx, op, Q, b, part));
+    } else {
+      dim3 grid((unsigned)((n + 63) / 64), (unsigned)S);  // 4 waves x 16 rows per workgroup
+      TPG_LAUNCH(ctx, "eig_symm_apply", tpg_symm_apply_kernel, grid, dim3(256), 0, K, n, Q, b, S, part);
+    }
     const double* Dm = nullptr;
     if (nl > 0) {
       TPG_LAUNCH(ctx, "eig_gram_small", tpg_gram_small_kernel, dim3((unsigned)nchunks), dim3(256), 0, L, nl, Q, b, n,
@@ -1297,8 +1305,9 @@ struct StageTimer {
 // random start, and again after every filter -- and the product K' A of every Rayleigh-Ritz step are projected against
 // d_P, pairs are accepted relative to that lambda_1 and the block is at most the n - np_ dimensions that are left.
 // *lam1_io receives the lambda_1 the pairs were accepted against.  With np_ = 0 nothing of this is reached.
+// op != NULL: the operator route (d_K = NULL, one batch: np_ = 0); op->bmax is at least the block width.
 static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambda_host, double* d_U, double tol = 1e-12,
-                    const double* d_P = nullptr, int np_ = 0, double* lam1_io = nullptr) {
+                    const double* d_P = nullptr, int np_ = 0, double* lam1_io = nullptr, TpgPcaOp* op = nullptr) {
   // block = 2k + 12 (RSpectra, which the reference calls, keeps ncv = 2k + 1 Lanczos vectors): K Q is bound by
   // reading K, so extra columns are nearly free, and a block that reaches past the k wanted values into the
   // bulk of the spectrum converges in far fewer filter / Rayleigh-Ritz rounds than k + 12 columns do
@@ -1307,7 +1316,9 @@ static int eig_topk(tpg_ctx* ctx, const double* d_K, int n, int k, double* lambd
   if (b > 64) b = 64;
   if (b > n - np_) b = n - np_;
   TPG_REQUIRE(k <= b, TPG_EINVAL, "k = %d too large (at most %d components)", k, b);
+  TPG_REQUIRE(!op || b <= op->bmax, TPG_EINVAL, "block of %d columns, operator scratch for %d", b, op->bmax);
   EigWork w{ctx, d_K, n, b, 1};
+  w.op = op;
   TPG_TRY(w.init());
   double *Q = nullptr, *Y = nullptr, *Y0 = nullptr, *Y1 = nullptr;
   for (double** blk : {&Q, &Y, &Y0, &Y1}) TPG_TRY(w.mem.get(blk, (size_t)n * (size_t)b));
@@ -1565,11 +1576,96 @@ extern "C" int tpg_pca_partial_svd_sharded(tpg_ctx* ctx, tpg_comm* comm, const t
 // relative residual at which a singular triplet is accepted (default 1e-4).  Same Gram + subspace iteration here,
 // stopped at that tolerance: residual |K u - d^2 u| <= tol * d_1^2 for every returned pair (the eigenvalue error is
 // then of order tol^2, the vector error of order tol / gap) -- fewer iterations than the partialSVD path's 1e-12.
+// (The Gram route: 8 n^2 bytes.  tpg_pca_random_svd_op below is the route that, like the reference's, only multiplies.)
 extern "C" int tpg_pca_random_svd(tpg_ctx* ctx, const tpg_view* v, int k, double tol, double* d, double* u,
                                   double* vload, double* center, double* scale, double* square_frobenius) {
   TpgEnter _enter(ctx);
   TPG_REQUIRE(tol > 0 && tol < 1, TPG_EINVAL, "tol = %g out of (0, 1)", tol);
   return pca_svd_impl(ctx, nullptr, v, k, tol < 1e-12 ? 1e-12 : tol, d, u, vload, center, scale, square_frobenius);
+}
+
+// ---------------------------------------------------------------------------
+// The same truncated SVD WITHOUT the Gram matrix (include/tpg.h "PCA by operator products"): eig_topk with K = Z Z' as
+// the operator Q -> Z (Z'Q) of pcaop.hip.  What the reference's big_randomSVD promises -- only products of the scaled
+// matrix with vectors, memory linear in n and in m -- and what the Gram route cannot give once 8 n^2 bytes do not fit.
+// One batch of the solver (k <= 52): eig_topk_any's explicit deflation rewrites K and has no operator form.
+static int pca_op_block(int64_t n, int k, bool env) {
+  int b = 2 * k + 12;
+  if (env) b = tpg_env_int("TPG_EIG_BLOCK", b);
+  if (b > 64) b = 64;
+  if (b > n) b = (int)n;
+  return b < 1 ? 1 : b;
+}
+
+extern "C" size_t tpg_pca_op_scratch_bytes(int64_t n, int64_t m, int k) {
+  if (n < 1 || m < 1 || k < 1 || k > 52) return 0;
+  const size_t b = (size_t)pca_op_block(n, k, false), nn = (size_t)n, mm = (size_t)m, kk = (size_t)k;
+  const size_t rows_per_chunk = n <= 4096 ? 32 : 64, nchunks = (nn + rows_per_chunk - 1) / rows_per_chunk;
+  size_t total = tpg_pcaop_work_bytes(n, m, (int)b, 256);                       // the halves (an MI355X: 256 CUs)
+  total += sizeof(double) * (6 * nn * b + nchunks * 64 * 64 + 3 * 64 * 64 + 128);  // eig_topk: four blocks, part, dtmp, the small products
+  total += sizeof(int32_t) * 4 * mm + sizeof(double) * (2 * mm + nn * kk + mm * kk + kk);  // counts; center, scale, u, v, d
+  const size_t CT = (kk * 6 /* LD_TU */ + 31) / 32;                             // the loadings: digit fragments and int32 sums
+  total += (size_t)ceil_div(n, 128) * 4 * CT * 1024 + (size_t)ceil_div(m, 128) * 128 * CT * 32 * sizeof(int32_t);
+  return total;
+}
+
+extern "C" int tpg_pca_gram_route_fits(tpg_ctx* ctx, int64_t n, int k, int* fits) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && fits, TPG_EINVAL, "null argument");
+  TPG_REQUIRE(n >= 1 && k >= 1, TPG_EINVAL, "bad n = %lld / k = %d", (long long)n, k);
+  size_t fr = 0, tot = 0;
+  TPG_HIP(hipMemGetInfo(&fr, &tot));
+  // the matrix; eig_topk: four blocks, dtmp and up to 32 partial products of n x b
+  const double need = 8.0 * (double)n * (double)n + 8.0 * 37.0 * (double)n * (double)pca_op_block(n, std::min(k, 26), false);
+  *fits = need <= 0.5 * (double)fr ? 1 : 0;
+  return TPG_OK;
+}
+
+extern "C" int tpg_pca_random_svd_op(tpg_ctx* ctx, const tpg_view* v, int k, double tol, double* d, double* u, double* vload,
+                                     double* center, double* scale, double* square_frobenius, int* n_apply) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && v && d && u && vload && center && scale, TPG_EINVAL, "null argument");
+  TPG_REQUIRE(tol >= TPG_PCA_OP_TOL_FLOOR && tol < 1, TPG_EINVAL,
+              "tol = %g out of [%g, 1): the operator products are exact to about 1e-11, a tighter tolerance takes the Gram route "
+              "(tpg_pca_random_svd)", tol, (double)TPG_PCA_OP_TOL_FLOOR);
+  TPG_REQUIRE(k >= 1 && k <= v->n && k <= v->m, TPG_EINVAL, "k = %d out of range", k);
+  TPG_REQUIRE(k <= 52, TPG_EINVAL, "k = %d: the operator route takes at most 52 components, more take the Gram route "
+              "(tpg_pca_random_svd)", k);
+  TPG_REQUIRE(v->n <= 2147483647ll, TPG_EINVAL, "n = %lld too large", (long long)v->n);
+  const int64_t n = v->n, m = v->m;
+  OutBuf oc, os, ou, ov;
+  TPG_TRY(oc.init(center, sizeof(double) * (size_t)m));
+  TPG_TRY(os.init(scale, sizeof(double) * (size_t)m));
+  TPG_TRY(ou.init(u, sizeof(double) * (size_t)n * (size_t)k));
+  TPG_TRY(ov.init(vload, sizeof(double) * (size_t)m * (size_t)k));
+  DevBuf b_counts, b_dk;
+  TPG_TRY(b_counts.alloc_n<int32_t>(4 * (size_t)m));
+  TPG_TRY(b_dk.alloc_n<double>((size_t)k));
+  StageTimer st(ctx, "svd_op");
+  TPG_TRY(pca_counts_center_scale(ctx, v, b_counts.as<int32_t>(), oc.dev<double>(), os.dev<double>()));
+  if (square_frobenius)
+    TPG_TRY(frobenius_from_counts(ctx, v, b_counts.as<int32_t>(), oc.dev<double>(), os.dev<double>(), square_frobenius));
+  b_counts.free();
+  st.mark("counts, center, scale, frobenius");
+  std::vector<double> lam((size_t)k), dh((size_t)k);
+  {
+    TpgPcaOp op;
+    TPG_TRY(tpg_pcaop_init(ctx, &op, v, oc.dev<double>(), os.dev<double>(), pca_op_block(n, k, true)));
+    TPG_TRY(eig_topk(ctx, nullptr, (int)n, k, lam.data(), ou.dev<double>(), tol, nullptr, 0, nullptr, &op));
+    if (n_apply) *n_apply = op.n_apply;
+  }
+  st.mark("eig_topk (operator)");
+  for (int j = 0; j < k; j++) dh[(size_t)j] = sqrt(lam[(size_t)j] > 0 ? lam[(size_t)j] : 0.0);
+  TPG_HIP(tpg_push_small(ctx, b_dk.as<double>(), dh.data(), sizeof(double) * (size_t)k));
+  TPG_TRY(pca_loadings_device(ctx, v, oc.dev<double>(), os.dev<double>(), ou.dev<double>(), b_dk.as<double>(), k, ov.dev<double>()));
+  if (tpg_is_device_ptr(d)) TPG_HIP(tpg_push_small(ctx, d, dh.data(), sizeof(double) * (size_t)k));
+  else memcpy(d, dh.data(), sizeof(double) * (size_t)k);
+  TPG_HIP(hipStreamSynchronize(ctx->stream));
+  st.mark("loadings");
+  TPG_TRY(oc.commit(ctx));
+  TPG_TRY(os.commit(ctx));
+  TPG_TRY(ou.commit(ctx));
+  return ov.commit(ctx);
 }
 
 // upper triangle (column k holds rows 0 .. k at k (k + 1) / 2) <-> full symmetric matrix
