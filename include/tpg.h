@@ -1519,6 +1519,41 @@ int tpg_oadp_proj(tpg_ctx* ctx, const double* XV, const double* X_norm, int64_t 
 int tpg_predict_oadp(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale, const double* V, int K,
                      const double* sval, double* out, double* XV_out /* may be NULL */, int64_t* n_degenerate);
 
+/* ---- least-squares projection (predict(pca, new_data, project_method = "least_squares"), R/predict_gt_pca.R:187-228: every
+ * individual is regressed on the loadings over the loci it is typed at, as SMARTPCA's lsqproject does) -------------------------
+ * Inputs: a view (n individuals x m loci), center[m], scale[m], V m x L column-major (the chosen loading columns),
+ * 1 <= L <= TPG_LSQ_MAX_L.  For individual i let T_i be the loci where its code is 0, 1 or 2 and t_i = |T_i|:
+ *   z_ij     = (g_ij - center_j) * (1 / scale_j)            (the arithmetic of tpg_fbm256_prod_and_rowSumsSq)
+ *   A_i[a,b] = sum_{j in T_i} V[j,a] V[j,b]                 b_i[a] = sum_{j in T_i} z_ij V[j,a]
+ *   x_i solves A_i x_i = b_i by Cholesky (A_i = R'R).
+ * A is kept as its packed upper triangle: pair (a, b), a <= b, a-major, P = L (L + 1) / 2 values per individual.
+ * Singular rule, exact and the same on host and device: row i is singular when t_i < L, or a Cholesky pivot p_k fails
+ * p_k > L 2^-52 A_i[k,k], or a pivot is not finite.  A singular row is NaN in every component and counted in *n_singular (0 is
+ * the expected value); the call succeeds all the same.
+ * Rounding, eps = 2^-53.  The sums run on the FP64 matrix cores in an order of the library's choosing, the same on every call
+ * (the split of the locus range may depend on n):
+ *   |dA_i[a,b]| <= (t_i + 2) eps sum_{j in T_i} |V[j,a] V[j,b]|     (one rounding per product, any order of t_i terms)
+ *   |db_i[a]|   <= (t_i + 4) eps sum_{j in T_i} |z_ij V[j,a]|       (z carries three roundings against (g - center) / scale)
+ *   n_typed is exact.
+ * The solve from given (A, b) is backward stable: |x^ - x|_2 <= k e_c / (1 - k e_c) |x|_2 with k = kappa_2(A) and
+ * e_c = 4 L (3 L + 1) eps (the Cholesky backward error of Higham, Accuracy and Stability, Thm 10.4 -- RECALLED, NOT PINNED).
+ * How it is computed (csrc/host/host_lsq.h, one text for host and device): a packed Cholesky row by row and two triangular
+ * solves; every sum is formed by one member of a team in ascending index order and subtracted once, without contraction, so a
+ * row's bits from tpg_lsq_solve depend on its own A, b and t only: not on n, not on its position.
+ * Errors: L outside [1, TPG_LSQ_MAX_L], a null argument, a view without loci: TPG_EINVAL; a value of center, scale, V (or of A, b
+ * handed to tpg_lsq_solve) that is not finite, a scale of zero, a sum that overflows: TPG_ENUMERIC.
+ * All arrays host or device memory, column-major.  Not offered: tpg_stream_* / tpg_multi_* forms, L > 32. */
+#define TPG_LSQ_MAX_L 32
+/* the sweep: A n x P, b n x L, n_typed[n] */
+int tpg_lsq_normal(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale, const double* V, int L, double* A,
+                   double* b, int64_t* n_typed);
+/* the batched solve: A n x P, b n x L, n_typed[n] -> out n x L; n_singular may be NULL */
+int tpg_lsq_solve(tpg_ctx* ctx, const double* A, const double* b, const int64_t* n_typed, int64_t n, int L, double* out,
+                  int64_t* n_singular);
+/* the sweep, then the solve, A and b staying on the device; out n x L, n_typed_out[n] (may be NULL) */
+int tpg_predict_lsq(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale, const double* V, int L, double* out,
+                    int64_t* n_typed_out /* may be NULL */, int64_t* n_singular);
+
 #ifdef __cplusplus
 }
 #endif

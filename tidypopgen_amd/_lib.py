@@ -351,6 +351,10 @@ PROTOTYPES = {
     # ---- OADP projection
     "tpg_oadp_proj": (ci, [vp, vp, vp, i64, ci, vp, vp, vp]),
     "tpg_predict_oadp": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
+    # ---- least-squares projection
+    "tpg_lsq_normal": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    "tpg_lsq_solve": (ci, [vp, vp, vp, vp, i64, ci, vp, vp]),
+    "tpg_predict_lsq": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp]),
 }
 
 for _name, (_restype, _argtypes) in PROTOTYPES.items():

@@ -3256,7 +3256,8 @@ def predict_gt_pca(pca: dict, X: Optional[FBM] = None, ind_row=None, ind_col=Non
     matching locus names, :113-127).  X = None -> the scores U D of the data the PCA was built on (:101-106).
       "none"           X V on the imputed code table (bigstatsr::big_prodMat, :141-149; missing values are not allowed)
       "simple"         fbm256_prod_and_rowSumsSq, missing genotypes count as 0 (:157-175)
-      "least_squares"  per individual, regress its non-missing scaled genotypes on v[, lsq_pcs] (:187-232)
+      "least_squares"  per individual, regress its non-missing scaled genotypes on v[, lsq_pcs] (:187-232); predict_gt_pca_lsq()
+                       is the same projection as one device call, with the singular rows reported
       "OADP"           not forwarded from here: predict_gt_pca_oadp() is the projection (the device sweep, then the
                        per-individual transform of include/tpg.h "OADP projection" in one kernel); bigsnpr's OADP_proj is not in
                        the reference checkout, and oadp_inputs() returns the XV and X_norm it takes."""
@@ -3275,14 +3276,7 @@ def predict_gt_pca(pca: dict, X: Optional[FBM] = None, ind_row=None, ind_col=Non
             raise ValueError("You can't have missing values in 'X'.")  # bigstatsr's check on the code table
         XV, _ = _prod_and_rss(v, pca["center"], pca["scale"], Vl)
         return XV
-    lsq = np.asarray(lsq_pcs)
-    if (len(lsq) == 0 or np.any(np.isnan(lsq.astype(float))) or np.any(lsq < 1) or np.any(lsq > Vl.shape[1])
-            or np.any(lsq != lsq.astype(int))):
-        raise ValueError(f"lsq_pcs should be a vector of valid component indices (positive integers between 1 and "
-                         f"{Vl.shape[1]}), e.g., c(1, 2) or c(1, 2, 3)")
-    if len(set(lsq.tolist())) != len(lsq):
-        raise ValueError("lsq_pcs should not contain duplicate values")
-    lsq = lsq.astype(int) - 1
+    lsq = _lsq_pcs_index(lsq_pcs, Vl.shape[1])
     L = len(lsq)
     v = View(X, ind_row, ind_col, code256=code256)
     Vs = np.asfortranarray(Vl[:, lsq])
@@ -3300,6 +3294,87 @@ def predict_gt_pca(pca: dict, X: Optional[FBM] = None, ind_row=None, ind_col=Non
             A[a, b] = A[b, a] = val
         out[i] = np.linalg.solve(A, rhs[i])  # solve(crossprod(v_sub), crossprod(v_sub, genotypes_scaled)), :228
     return out
+
+
+def _lsq_pcs_index(lsq_pcs, K: int):
+    """the checks of R/predict_gt_pca.R:189-203 on lsq_pcs (1-based) against a PCA of K components -> 0-based indices"""
+    lsq = np.asarray(lsq_pcs)
+    if (len(lsq) == 0 or np.any(np.isnan(lsq.astype(float))) or np.any(lsq < 1) or np.any(lsq > K)
+            or np.any(lsq != lsq.astype(int))):
+        raise ValueError(f"lsq_pcs should be a vector of valid component indices (positive integers between 1 and "
+                         f"{K}), e.g., c(1, 2) or c(1, 2, 3)")
+    if len(set(lsq.tolist())) != len(lsq):
+        raise ValueError("lsq_pcs should not contain duplicate values")
+    return lsq.astype(int) - 1
+
+
+def lsq_normal(v: View, center, scale, V) -> dict:
+    """tpg_lsq_normal: the per-individual normal equations of include/tpg.h "least-squares projection" for the view `v`, from
+    center, scale (m) and the loading columns V (m x L, L <= 32), in one sweep on the FP64 matrix cores -> {"A": n x L x L
+    symmetric, "A_packed": n x L (L + 1) / 2 (pair (a, b), a <= b, a-major), "b": n x L, "n_typed": the typed loci (int64)}"""
+    V = np.asfortranarray(V, dtype=float)
+    center, scale = _f64(center), _f64(scale)
+    if V.ndim != 2 or V.shape[0] != v.m or center.shape != (v.m,) or scale.shape != (v.m,):
+        raise _lib.TpgError(1, f"the view has {v.m} loci: V must have {v.m} rows, center and scale {v.m} values")  # TPG_EINVAL
+    L = V.shape[1]
+    P = L * (L + 1) // 2
+    Ap = np.zeros((v.n, P), order="F")
+    b = np.zeros((v.n, L), order="F")
+    nt = np.zeros(v.n, dtype=np.int64)
+    check(lib.tpg_lsq_normal(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(V), L, _ptr(Ap), _ptr(b), _ptr(nt)))
+    A = np.zeros((v.n, L, L))
+    p = 0
+    for a in range(L):
+        for c in range(a, L):
+            A[:, a, c] = A[:, c, a] = Ap[:, p]
+            p += 1
+    return {"A": A, "A_packed": Ap, "b": b, "n_typed": nt}
+
+
+def lsq_solve(A_packed, b, n_typed, return_singular: bool = False, ctx: Optional[Context] = None):
+    """tpg_lsq_solve: x_i = A_i^-1 b_i for every row by the packed Cholesky of include/tpg.h "least-squares projection"
+    (A_packed n x L (L + 1) / 2, b n x L, n_typed n) -> x (n x L) [, n_singular: the rows the singular rule rejects; they are
+    NaN].  A row's bits depend on that row alone."""
+    ctx = ctx or default_context()
+    Ap = np.asfortranarray(A_packed, dtype=np.float64)
+    bb = np.asfortranarray(b, dtype=np.float64)
+    nt = np.ascontiguousarray(n_typed, dtype=np.int64)
+    if Ap.ndim != 2 or bb.ndim != 2:
+        raise _lib.TpgError(1, "A_packed and b must be matrices")  # TPG_EINVAL: the sizes the C ABI cannot see
+    n, L = bb.shape
+    if Ap.shape != (n, L * (L + 1) // 2) or nt.shape != (n,):
+        raise _lib.TpgError(1, f"b is {n} x {L}: A_packed must be {n} x {L * (L + 1) // 2} and n_typed hold {n} values")
+    out = np.zeros((n, L), order="F")
+    sing = C.c_int64()
+    check(lib.tpg_lsq_solve(ctx.h, _ptr(Ap), _ptr(bb), _ptr(nt), n, L, _ptr(out), C.byref(sing)))
+    return (out, int(sing.value)) if return_singular else out
+
+
+def predict_gt_pca_lsq(pca: dict, X: FBM, ind_row=None, ind_col=None, lsq_pcs=(1, 2), code256=CODE_IMPUTE_PRED,
+                       return_singular: bool = False, return_n_typed: bool = False):
+    """predict(pca, new_data, project_method = "least_squares") (R/predict_gt_pca.R:187-232) as one device call
+    (tpg_predict_lsq): the sweep that forms every individual's normal equations over the loci it is typed at, then the batched
+    Cholesky solve, with nothing but the scores leaving the device.  Arguments and the checks on lsq_pcs as predict_gt_pca; at
+    most 32 components -> the scores (n x len(lsq_pcs)), columns in the order of lsq_pcs (they can go to predict_gt_dapc)
+    [, n_singular: rows typed at fewer loci than components or with a rank-deficient system; they are NaN] [, n_typed]"""
+    Vl = np.asfortranarray(pca["v"], dtype=float)
+    lsq = _lsq_pcs_index(lsq_pcs, Vl.shape[1])
+    L = len(lsq)
+    v = View(X, ind_row, ind_col, code256=code256)
+    Vs = np.asfortranarray(Vl[:, lsq])
+    center, scale = _f64(pca["center"]), _f64(pca["scale"])
+    if Vl.shape[0] != v.m or center.shape != (v.m,) or scale.shape != (v.m,):
+        raise _lib.TpgError(1, f"the view has {v.m} loci: the PCA's v must have {v.m} rows, center and scale {v.m} values")  # TPG_EINVAL
+    out = np.zeros((v.n, L), order="F")
+    nt = np.zeros(v.n, dtype=np.int64)
+    sing = C.c_int64()
+    check(lib.tpg_predict_lsq(v.ctx.h, v.h, _ptr(center), _ptr(scale), _ptr(Vs), L, _ptr(out), _ptr(nt), C.byref(sing)))
+    res = (out,)
+    if return_singular:
+        res += (int(sing.value),)
+    if return_n_typed:
+        res += (nt,)
+    return res if len(res) > 1 else out
 
 
 def oadp_inputs(pca: dict, X: FBM, ind_row=None, ind_col=None, code256=CODE_IMPUTE_PRED):
