@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void tpg_fst_reduce_kernel(const double* __res
 }
 
 // ---------------------------------------------------------------------------
-// Hudson, totals only (no per-locus output), as three masked matrix products over the loci.  With m_g = 1 where the
+// Hudson, totals only (no per-locus output), as masked matrix products over the loci.  With m_g = 1 where the
 // reference keeps the locus for population g (freq and p q / (n - 1) not NaN, src/pairwise_fst_hudson_loop.cpp:43-52 drops a
 // locus for a pair when its numerator or denominator is NaN) and a_g = m_g (p_g^2 - e_g), b_g = m_g, c_g = m_g p_g:
 //     sum_j num = sum_j m_1 m_2 [(p_1 - p_2)^2 - e_1 - e_2] = (A B')[g1,g2] + (A B')[g2,g1] - 2 (C C')[g1,g2]
@@ -122,22 +122,35 @@ __global__ __launch_bounds__(256) void tpg_fst_reduce_kernel(const double* __res
 // workgroup, a 4 x 4 block of (g1, g2) and 48 FP64 sums per thread, operands staged once per chunk of loci in LDS.  The
 // sums are formed in another order than the reference's (and than the by-locus path's, which stays statement for
 // statement): the totals agree to ~1e-14 relative.
+// The mask b is all ones at a locus where no population of the tile's columns is empty: call such a locus clean (k_j = 1,
+// else 0).  Then
+//     (A B')[g1,g2] = S_a[g1] + (A D')[g1,g2],  S_a[g] = sum_j k_j a_g,  D = (1 - k_j) b   (and C, S_c alike)
+// so over clean loci A B' and C B' are one column each, the same for all g2: ONE MFMA per 16 row populations and 4 loci
+// whose second operand is k_j in every column, instead of four.  (Summed by the MFMA, not by the staging threads: the
+// instruction adds its four loci and then the next four in locus order, a chain that a locus contributing exact zeros does
+// not disturb -- a panel and the same panel less a locus at which one population is empty give the same bits, which
+// tests/test_gpu_parity.py::test_fst_scikit_allel_golden asks for and sums per staging thread would not give.)  The staging
+// threads mark the loci at which some column population is masked and raise a workgroup-wide LDS flag for the chunk; only for
+// such a chunk the waves issue A D' and C D' as well.  The final kernel puts A B' and C B' together.
 #define FSTG_T 64   // populations per tile side
 #define FSTG_LB 16  // loci per staged chunk (32 KiB of LDS: four workgroups per CU hide one another's staging)
-// The three products run on the FP64 matrix cores (v_mfma_f64_16x16x4_f64: 16 x 16 pairs x 4 loci in 32 cycles, twice the
-// FP64 VALU rate, and a lane feeds it ONE double per operand where a VALU form read 16 doubles for 48 FMAs -- that form
-// was bound by LDS bandwidth: 27 M ds_read_b128 + 40 M conflict cycles against 1.32 M cycles per launch at 51 populations).
-// A wave owns 16 row populations x all 64 column populations: 4 column tiles x 3 products = 12 accumulators, per 4 loci
-// 2 + 8 ds_read_b64 and 12 MFMAs.  Rows of the staged arrays are FSTG_RS = 80 doubles apart (32 dwords modulo the 64
-// banks), so that the four loci a wave instruction reads fall on disjoint banks.
+// The products run on the FP64 matrix cores (v_mfma_f64_16x16x4_f64: 16 x 16 pairs x 4 loci per instruction, at the FP64
+// VALU's FMA rate on gfx950; what it saves is operand delivery: a lane feeds it ONE double per operand where a
+// VALU form read 16 doubles for 48 FMAs -- that form was bound by LDS bandwidth: 27 M ds_read_b128 + 40 M conflict cycles
+// against 1.32 M cycles per launch at 51 populations).
+// A wave owns 16 row populations x all 64 column populations: 4 column tiles x 3 products + the two column sums = 14
+// accumulators; per 4 loci 2 + 4 ds_read_b64, one ds_read_b32 and 6 MFMAs, in a chunk with a mask 2 + 4 and 8 more.  Rows of
+// the staged arrays are FSTG_RS = 80 doubles apart (32 dwords modulo the 64 banks), so that the four loci a wave instruction
+// reads fall on disjoint banks.
 #define FSTG_RS_MFMA 80
+#define FSTG_TS (3 * FSTG_T * FSTG_T + 2 * FSTG_T)  // doubles per tile of the partials: A D', C D', C C', then S_a, S_c
 __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, int64_t m, int G, int ntile, int kmax,
                                                                   double* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   constexpr int RS = FSTG_RS_MFMA;  // row stride of the staged arrays
   double* ra = sh;                      // [l][RS] a of the row populations
   double* rc = sh + FSTG_LB * RS;       // c of the row populations
-  double* cb = sh + 2 * FSTG_LB * RS;   // b of the column populations
+  double* cb = sh + 2 * FSTG_LB * RS;   // u = 1 - b of the column populations (1: a population that drops out at the locus)
   const int tR = blockIdx.y / ntile, tC = blockIdx.y % ntile;
   const bool diag = tR == tC;
   double* cc = diag ? rc : sh + 3 * FSTG_LB * RS;  // c of the column populations
@@ -146,11 +159,18 @@ __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, in
   // by-locus path, which must be bit-identical to the reference, divides)
   double* inv = sh + 4 * FSTG_LB * RS;
   for (int A = threadIdx.x; A <= kmax; A += 256) { inv[2 * A] = 1.0 / (double)A; inv[2 * A + 1] = 1.0 / ((double)A - 1.0); }
-  double AB[4][4], CB[4][4], CC[4][4];  // [column tile][C/D register]
+  // flag[p][l] != 0: some column population is masked (u = 1) at locus l of the chunk; flag[p][FSTG_LB]: at some locus of
+  // it.  p = the chunk's parity: a chunk's staging clears the other set
+  int* flag = (int*)(inv + 2 * ((size_t)kmax + 1));
+  constexpr int FS = FSTG_LB + 1;
+  if (threadIdx.x < 2 * FS) flag[threadIdx.x] = 0;
+  double AD[4][4], CD[4][4], CC[4][4], SA[4], SC[4];  // [column tile][C/D register]
 #pragma unroll
-  for (int r = 0; r < 4; r++)
+  for (int r = 0; r < 4; r++) {
+    SA[r] = 0.0; SC[r] = 0.0;
 #pragma unroll
-    for (int c = 0; c < 4; c++) { AB[r][c] = 0.0; CB[r][c] = 0.0; CC[r][c] = 0.0; }
+    for (int c = 0; c < 4; c++) { AD[r][c] = 0.0; CD[r][c] = 0.0; CC[r][c] = 0.0; }
+  }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r16 = lane & 15, kq = lane >> 4;
   const int64_t nchunks = (m + FSTG_LB - 1) / FSTG_LB;
   // class counts of diploids (kmax > 0): the three counts of this thread's (locus, population) slots of the NEXT chunk are
@@ -161,7 +181,7 @@ __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, in
   auto fetch = [&](int64_t ch) {
 #pragma unroll
     for (int i = 0; i < NSLOT; i++) {
-      pn1[i] = 0; pn2[i] = 0; pnv[i] = 0;
+      pn1[i] = 0; pn2[i] = 0; pnv[i] = -1;  // -1: a slot past the data, no population there (u = 0)
       if (i < nslot && ch < nchunks) {
         const int idx = threadIdx.x + 256 * i;
         const int side = idx / (FSTG_LB * FSTG_T), rem = idx % (FSTG_LB * FSTG_T);
@@ -175,28 +195,31 @@ __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, in
     }
   };
   if (kmax > 0) fetch(blockIdx.x);
-  for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+  int par = 0;
+  for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x, par ^= 1) {
     const int64_t j0 = ch * FSTG_LB;
     __syncthreads();
+    if (threadIdx.x < FS) flag[(par ^ 1) * FS + threadIdx.x] = 0;  // read last before this barrier, raised next after the one below
     if (kmax > 0) {
 #pragma unroll
       for (int i = 0; i < NSLOT; i++) {
         if (i >= nslot) break;
         const int idx = threadIdx.x + 256 * i;
         const int side = idx / (FSTG_LB * FSTG_T), rem = idx % (FSTG_LB * FSTG_T);
-        double a = 0.0, b = 0.0, c = 0.0;
+        double a = 0.0, u = pnv[i] >= 0 ? 1.0 : 0.0, c = 0.0;
         const int A = min(2 * pnv[i], kmax);
-        if (A > 0) {  // no valid genotype (or a slot past the data): freq is NaN, the population drops out
+        if (A > 0) {  // no valid genotype: freq is NaN, the population drops out
           const double vp = (double)(pn1[i] + 2 * pn2[i]) * inv[2 * A];
           const double e = (vp * (1 - vp)) * inv[2 * A + 1];
-          if (e == e) { a = vp * vp - e; b = 1.0; c = vp; }
+          if (e == e) { a = vp * vp - e; u = 0.0; c = vp; }
         }
         const int srem = (rem / FSTG_T) * RS + rem % FSTG_T;
-        if (side) { cb[srem] = b; cc[srem] = c; }
+        if (side) { cb[srem] = u; cc[srem] = c; }
         else {
           ra[srem] = a; rc[srem] = c;
-          if (diag) cb[srem] = b;
+          if (diag) cb[srem] = u;
         }
+        if ((side || diag) && u != 0.0) { flag[par * FS + rem / FSTG_T] = 1; flag[par * FS + FSTG_LB] = 1; }
       }
     } else {
       // a tile on the diagonal (always, up to 64 populations) stages its populations once: rows and columns are the same
@@ -205,50 +228,74 @@ __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_kernel(FstSrc src, in
         const int l = rem / FSTG_T, gl = rem % FSTG_T;
         const int g = (side ? tC : tR) * FSTG_T + gl;
         const int64_t j = j0 + l;
-        double a = 0.0, b = 0.0, c = 0.0;
+        double a = 0.0, u = 0.0, c = 0.0;
         if (j < m && g < G) {
           double vn, vp, vh;
           fst_stage(src, m, j, g, vn, vp, vh);
           const double e = (vp * (1 - vp)) / (vn - 1);  // src/pairwise_fst_hudson_loop.cpp:28-29
-          if (vp == vp && e == e) { a = vp * vp - e; b = 1.0; c = vp; }
+          if (vp == vp && e == e) { a = vp * vp - e; c = vp; }
+          else u = 1.0;
         }
         const int srem = l * RS + gl;
-        if (side) { cb[srem] = b; cc[srem] = c; }
+        if (side) { cb[srem] = u; cc[srem] = c; }
         else {
           ra[srem] = a; rc[srem] = c;
-          if (diag) cb[srem] = b;
+          if (diag) cb[srem] = u;
         }
+        if ((side || diag) && u != 0.0) { flag[par * FS + l] = 1; flag[par * FS + FSTG_LB] = 1; }
       }
     }
     __syncthreads();
     if (kmax > 0) fetch(ch + gridDim.x);
     // A = x[locus l + kq][row population 16 wv + r16], B = y[locus l + kq][column population 16 ct + r16]
+    const int* dirty = flag + par * FS;
 #pragma unroll
     for (int l = 0; l < FSTG_LB; l += 4) {
       const double av = ra[(l + kq) * RS + 16 * wv + r16], cv = rc[(l + kq) * RS + 16 * wv + r16];
+      const double kv = dirty[l + kq] ? 0.0 : 1.0;
+      *(v4d*)SA = __builtin_amdgcn_mfma_f64_16x16x4f64(av, kv, *(v4d*)SA, 0, 0, 0);
+      *(v4d*)SC = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, kv, *(v4d*)SC, 0, 0, 0);
 #pragma unroll
       for (int ct = 0; ct < 4; ct++) {
-        const double bv = cb[(l + kq) * RS + 16 * ct + r16], dv = cc[(l + kq) * RS + 16 * ct + r16];
-        *(v4d*)AB[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, *(v4d*)AB[ct], 0, 0, 0);
-        *(v4d*)CB[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, bv, *(v4d*)CB[ct], 0, 0, 0);
+        const double dv = cc[(l + kq) * RS + 16 * ct + r16];
         *(v4d*)CC[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, dv, *(v4d*)CC[ct], 0, 0, 0);
+      }
+    }
+    if (dirty[FSTG_LB]) {  // (the same for every thread of the workgroup) some column population is masked in this chunk
+#pragma unroll
+      for (int l = 0; l < FSTG_LB; l += 4) {
+        const double av = ra[(l + kq) * RS + 16 * wv + r16], cv = rc[(l + kq) * RS + 16 * wv + r16];
+        const bool d = dirty[l + kq] != 0;
+#pragma unroll
+        for (int ct = 0; ct < 4; ct++) {
+          const double bv = d ? 1.0 - cb[(l + kq) * RS + 16 * ct + r16] : 0.0;
+          *(v4d*)AD[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, *(v4d*)AD[ct], 0, 0, 0);
+          *(v4d*)CD[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv, bv, *(v4d*)CD[ct], 0, 0, 0);
+        }
       }
     }
   }
   // partial sums of this workgroup: [block x][tile][product][row][col]; C/D: column = lane & 15, row = (lane >> 4) + 4 reg
-  double* o = part + (((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * 3) * FSTG_T * FSTG_T;
+  double* o = part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * FSTG_TS;
 #pragma unroll
   for (int ct = 0; ct < 4; ct++)
 #pragma unroll
     for (int reg = 0; reg < 4; reg++) {
       const int q = (16 * wv + kq + 4 * reg) * FSTG_T + 16 * ct + r16;
-      o[q] = AB[ct][reg];
-      o[FSTG_T * FSTG_T + q] = CB[ct][reg];
+      o[q] = AD[ct][reg];
+      o[FSTG_T * FSTG_T + q] = CD[ct][reg];
       o[2 * FSTG_T * FSTG_T + q] = CC[ct][reg];
+    }
+  // S_a, S_c of the 64 row populations behind the product cells (every column of the 16 x 16 result holds them: column 0)
+  if (r16 == 0)
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++) {
+      o[3 * FSTG_T * FSTG_T + 16 * wv + kq + 4 * reg] = SA[reg];
+      o[3 * FSTG_T * FSTG_T + FSTG_T + 16 * wv + kq + 4 * reg] = SC[reg];
     }
 }
 
-// full[slice][tile][product][row][col] = sum over every FSTG_SL-th workgroup's partials, in workgroup order; the final
+// full[slice][tile][product or column sum][row][col] = sum over every FSTG_SL-th workgroup's partials, in workgroup order; the final
 // kernel adds the FSTG_SL slices in slice order (the same sums on every run)
 #define FSTG_SL 16
 __global__ __launch_bounds__(256) void tpg_fst_hudson_gemm_reduce_kernel(const double* __restrict__ part, int nbx, int64_t cells,
@@ -266,15 +313,23 @@ __global__ void tpg_fst_hudson_gemm_final_kernel(const double* __restrict__ full
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= P) return;
   const int g1 = pairs0[2 * pi], g2 = pairs0[2 * pi + 1];
-  auto at = [&](int prod, int r, int c) {
-    const int t = (r / FSTG_T) * ntile + c / FSTG_T;
-    const int64_t q = (((int64_t)t * 3 + prod) * FSTG_T + r % FSTG_T) * FSTG_T + c % FSTG_T;
+  auto cell = [&](int64_t q) {
     double v = 0.0;
     for (int sl = 0; sl < FSTG_SL; sl++) v += full[(int64_t)sl * cells + q];
     return v;
   };
+  auto at = [&](int prod, int r, int c) {
+    const int t = (r / FSTG_T) * ntile + c / FSTG_T;
+    return cell(((int64_t)t * FSTG_TS + (prod * FSTG_T + r % FSTG_T) * FSTG_T) + c % FSTG_T);
+  };
+  // (A B')[r,c] (k = 0) and (C B')[r,c] (k = 1): the row population's sum over the loci clean for the column tile of c and
+  // the masked product over the others, both from the tile of (r, c)
+  auto masked = [&](int k, int r, int c) {
+    const int t = (r / FSTG_T) * ntile + c / FSTG_T;
+    return cell((int64_t)t * FSTG_TS + 3 * FSTG_T * FSTG_T + k * FSTG_T + r % FSTG_T) + at(k, r, c);
+  };
   const double cc2 = 2 * at(2, g1, g2);
-  const double sn = at(0, g1, g2) + at(0, g2, g1) - cc2, sd = at(1, g1, g2) + at(1, g2, g1) - cc2;
+  const double sn = masked(0, g1, g2) + masked(0, g2, g1) - cc2, sd = masked(1, g1, g2) + masked(1, g2, g1) - cc2;
   if (fst_tot) fst_tot[pi] = sn / sd;
   if (sum_num) { sum_num[pi] = sn; sum_den[pi] = sd; }
 }
@@ -402,52 +457,103 @@ __global__ __launch_bounds__(256) void tpg_fst_wc84_tab_kernel(FstSrc src, int64
 
 // The same for MANY pairs (more than 256) of at most 64 populations: a thread owns a TILE of FSTW_TR x FSTW_TC populations =
 // up to 6 pairs instead of 8 unrelated pairs.  The kernel above is bound by LDS bandwidth AND close to its VALU bound
-// (rocprofv3 --pmc at 51 populations: 1.2e8 ds_read_b128 x 8 cycles / 256 CUs = 3.8 of the kernel's 3.97 million cycles, 7.6e8
-// VALU x 4 / 1 024 SIMDs = 3.0): six 16-byte reads per pair and locus, four of them the pair's two populations, and 38 VALU
-// instructions of which 24 are the FP64 arithmetic.  Here
-//   * a tile reads its 3 + 2 populations ONCE per locus -- 1.67 reads per pair -- and only the two table reads stay per
-//     pair: 3.67 reads instead of 6.  The tiles come from the host (any list of pairs: a tile holds the listed pairs that fall
-//     into it, -1 elsewhere; all pairs of 51 populations: 242 tiles = one workgroup of four full waves, 88 % of their slots
-//     used; 4 x 2 tiles need 194 registers and leave a CU with six waves: 2.4 ms);
+// (rocprofv3 --pmc at 51 populations: 1.2e8 ds_read_b128 against the kernel's 3.97 million cycles, 7.6e8 VALU x 4 / 1 024
+// SIMDs = 3.0; a conflict-free ds_read_b128 of a wave occupies the CU's LDS for 4 cycles, 256 bytes per clock): six 16-byte
+// reads per pair and locus, four of them the pair's two populations, and 38 VALU instructions of which 24 are the FP64
+// arithmetic.  Here
+//   * a tile reads its 3 + 2 populations ONCE per locus and only the table read stays per pair.  The tiles come from the
+//     host (any list of pairs: a tile holds the listed pairs that fall into it, -1 elsewhere; all pairs of 51 populations:
+//     242 tiles = one workgroup of four full waves, 88 % of their slots used; 4 x 2 tiles of the full pair below need 194
+//     registers and leave a CU with six waves: 2.4 ms);
 //   * every LDS address is a per-lane pointer that advances by two loci per iteration + an IMMEDIATE offset (the layout is a
-//     compile-time constant: tables of 512 entries first, 16 loci x 64 populations after them), where the kernel above
+//     compile-time constant: the table of 512 entries first, 16 loci x 64 populations after it), where the kernel above
 //     adds a loop-dependent offset to every one of its addresses in the VALU;
-//   * a population is staged as {32 n, p} and {32 H, 1 / n}: 32 (n_1 + n_2) IS the byte offset of the pair's table entry
-//     (16 bytes per valid allele), and the powers of two cancel exactly against the table's 1 / (32 nt): no doubling, no
-//     shift, the same roundings;
 //   * "is the denominator a number" is decided per WAVE and locus (one ballot of the six comparisons): the common case
 //     adds without v_cndmask (4 per pair).
-// 26 VALU instructions per pair and locus instead of 38.  Per pair the arithmetic, its order, and the order of the loci are
-// those of the kernel above; the staged frequency is a product with the table's 1 / n instead of a quotient (one ulp), so the
-// sums agree with that kernel's to 1e-16, not bit for bit.
+// RED = false, the FULL pair: per pair the arithmetic, its order, and the order of the loci are those of the kernel above
+// (26 VALU instructions per pair and locus instead of 38, 22 sixteen-byte reads per tile and locus).  A population is staged
+// as {32 n, p} and {32 H, 1 / n}: 32 (n_1 + n_2) IS the byte offset of the pair's table entry (16 bytes per valid allele),
+// and the powers of two cancel exactly against the table's 1 / (32 nt).  The staged frequency is a product with the
+// table's 1 / n instead of a quotient (one ulp), so the sums agree with that kernel's to 1e-16, not bit for bit.  It is
+// launched when some group has fewer than three individuals (below).
+// RED = true, the REDUCED pair (DESIGN.md 3 "Fst totals").  With c = n p (1 - p) per (locus, population), cs = c_1 + c_2,
+// hs = H_1 + H_2, d = p_1 - p_2:
+//     p_bar (1 - p_bar) - d^2 n_1 n_2 / nt^2 = cs / nt
+// so "core" above is cs / nt without its cancellation, and with alpha = 1 / (nt - 2), r = 1 / nt the four table values
+// collapse (t2 r = alpha, t3 r / (n_1 n_2) = (alpha / 2)(1 / n_1 + 1 / n_2), r (1 / 2 - t1 t2) = - alpha r / 2):
+//     a   = d^2 / 2 - (alpha / 2) (1 / n_1 + 1 / n_2) (cs - hs / 4)
+//     den = a + alpha (cs - (r / 2) hs)
+// The kernel sums 2 a and 2 den (halved, exactly, when the partials are stored) from {p, 2 c}, {H, 1 / (2 n)} and ONE
+// 16-byte table entry {alpha, r}: d, d^2, cs, hs, the sum of the reciprocals, two FMAs for 2 a with one product, two FMAs
+// for 2 den = 10 FP64 instructions, and the table offset is the sum of two staged INTEGERS 32 n (no FP64 add, no
+// v_cvt): 14 VALU instructions per pair and locus with the two additions to the sums and a comparison per two pairs.
+// Per tile and locus 10 + 6 sixteen-byte reads and 5 four-byte ones (2 cycles each) = 74 LDS cycles against 88.
+// Singular pairs: the table's alpha is NaN where nt <= 2 (there the full pair has 1 / 0 or a negative nt / 2 - 1 and what
+// it gives, +-inf or NaN, decides which loci the sums keep), and an empty population has a NaN frequency, so such a pair
+// fails the wave's ballot like every NaN denominator; the wave then forms that locus again for its six pairs by the FULL
+// pair's statements, with the table values made on the spot by the same IEEE expressions (a rare path: divisions are fine
+// there, a second table in LDS would cost the third workgroup per CU) and adds what that kernel would add.
 // FSTW_TR x FSTW_TC = 3 x 2 populations; a task record = {first row population, first column population, pair index x 6}:
 // host/host_fsttiles.h (fst_wc84_tiles cuts the pair list into them)
-#define FSTT_KMAX 511                            // table entries 0 .. 511 valid alleles of a pair
+#define FSTT_KMAX 511    // table entries 0 .. 511 valid alleles of a pair
 #define FSTT_LB 16
-#define FSTT_TAB2 (512 * 16)
-#define FSTT_SA (2 * 512 * 16)                   // {32 n, p} [locus][population]
-#define FSTT_SB (FSTT_SA + FSTT_LB * 64 * 16)    // {32 H, 1 / n}
-#define FSTT_LDS (FSTT_SB + FSTT_LB * 64 * 16)
+#define FSTT_MIN_GROUP 3  // the reduced pair pays when two full groups are never singular: nt >= 6
+// the four table values of the full pair at A valid alleles of the pair
+__device__ __forceinline__ void fstt_full_table(int A, double& t0, double& t1, double& t2, double& t3) {
+  const double nt = 0.5 * (double)A, nb1 = 0.5 * nt - 1.0;
+  const double r = 1.0 / nt, sv = 1.0 / nb1;  // nb1 = 0 (one individual per population): +inf, as the reference's 1 / 0
+  t0 = r * 0.03125;  // against the staged 32 n, 32 H
+  t1 = (0.5 * (nt - 1.0)) * r;
+  t2 = (0.5 * nt) * sv;
+  t3 = (0.25 * (nt * nt)) * sv;
+}
+// one locus of one pair by the full statements: s = {32 n, p, 32 H, 1 / n}
+__device__ __forceinline__ void fstt_full_pair(const v4d s1, const v4d s2, const v4d t, double& a_out, double& den_out) {
+#pragma clang fp contract(fast)  // (as in the kernel above)
+  const double p_bar = fma(s2[1], s2[0], s1[1] * s1[0]) * t[0], h_bar = (s1[2] + s2[2]) * t[0];
+  const double d = s1[1] - s2[1], d2 = d * d;
+  const double half_s2 = (d2 * (s1[0] * s2[0])) * (t[0] * t[0]);
+  const double core = fma(-p_bar, p_bar, p_bar) - half_s2;
+  const double X = t[3] * (s1[3] * s2[3]);
+  const double a = fma(-X, fma(-0.25, h_bar, core), 0.5 * d2);
+  const double b = t[2] * fma(-t[1], h_bar, core);
+  a_out = a;
+  den_out = fma(0.5, h_bar, a + b);
+}
+template <bool RED>
 __global__ __launch_bounds__(256, 3) void tpg_fst_wc84_tile_kernel(FstSrc src, int64_t m, int G, int kmax,
                                                                    const int32_t* __restrict__ tasks, int ntask, int P,
                                                                    double* __restrict__ part) {
-  __shared__ __attribute__((aligned(16))) char shb[FSTT_LDS];
   constexpr int NPT = FSTW_TR * FSTW_TC, LB = FSTT_LB, GS = 64;
+  // LDS: the table(s) [A], then [locus][population] arrays.  Full: {t0, t1}, {t2, t3}, {32 n, p}, {32 H, 1 / n} = 48 KB;
+  // reduced: {alpha, r}, {p, 2 c}, {H, 1 / (2 n)}, 32 n as int32 = 44 KB.  Three workgroups per CU need <= 53 KB.
+  constexpr int TAB2 = 512 * 16;
+  constexpr int SA = RED ? 512 * 16 : 2 * 512 * 16;
+  constexpr int SB = SA + LB * GS * 16;
+  constexpr int SN = SB + LB * GS * 16;
+  constexpr int LDS = RED ? SN + LB * GS * 4 : SN;
+  static_assert(LDS <= 53 * 1024, "three workgroups per CU");
+  __shared__ __attribute__((aligned(16))) char shb[LDS];
   for (int A = threadIdx.x; A <= kmax; A += 256) {
-    const double nt = 0.5 * (double)A, nb1 = 0.5 * nt - 1.0;
-    const double r = 1.0 / nt, sv = 1.0 / nb1;
-    double* t = (double*)shb + (size_t)A * 2;
-    t[0] = r * 0.03125;  // against the staged 32 n, 32 H
-    t[1] = (0.5 * (nt - 1.0)) * r;
-    double* t2 = (double*)(shb + FSTT_TAB2) + (size_t)A * 2;
-    t2[0] = (0.5 * nt) * sv;
-    t2[1] = (0.25 * (nt * nt)) * sv;
+    if (RED) {
+      const double nt = 0.5 * (double)A;
+      double* t = (double*)shb + (size_t)A * 2;
+      t[0] = A > 4 ? 1.0 / (nt - 2.0) : FST_NAN;  // nt <= 2: the pair is singular, the full statements decide
+      t[1] = 1.0 / nt;
+    } else {
+      double t0, t1, t2, t3;
+      fstt_full_table(A, t0, t1, t2, t3);
+      double* t = (double*)shb + (size_t)A * 2;
+      t[0] = t0; t[1] = t1;
+      double* u = (double*)(shb + TAB2) + (size_t)A * 2;
+      u[0] = t2; u[1] = t3;
+    }
   }
   const int task = blockIdx.y * 256 + threadIdx.x;
   const bool active = task < ntask;
   int pidx[NPT];
   uint32_t ro[FSTW_TR], co[FSTW_TC];  // byte offsets of the tile's populations inside a locus' staged row
-  double sum_num[NPT], sum_den[NPT];
+  double sum_num[NPT], sum_den[NPT];  // reduced: of 2 a and 2 den
   {
     const int r0 = active ? tasks[task * FSTW_TASK_INTS] : 0, c0 = active ? tasks[task * FSTW_TASK_INTS + 1] : 0;
 #pragma unroll
@@ -478,23 +584,28 @@ __global__ __launch_bounds__(256, 3) void tpg_fst_wc84_tile_kernel(FstSrc src, i
       }
     }
   };
-  // one locus of the tile: the row populations at pr[] + OFF, the column populations at pc[] + OFF
+  // one locus of the tile: the row populations at pr[] + OFF, the column populations at pc[] + OFF (reduced: their 32 n at
+  // qr[] + OFF / 4, qc[] + OFF / 4)
   // (LDS pointers by their address space: as generic pointers kept in arrays across the loop they become 64-bit FLAT loads)
   typedef __attribute__((address_space(3))) const char lchar;
   typedef __attribute__((address_space(3))) const v2d lv2d;
-  auto locus = [&](lchar* const* pr, lchar* const* pc, auto off) {
+  typedef __attribute__((address_space(3))) const int lint;
+  auto locus = [&](lchar* const* pr, lchar* const* pc, lchar* const* qr, lchar* const* qc, auto off) {
 #pragma clang fp contract(fast)  // (as in the kernel above)
     constexpr int OFF = decltype(off)::value;
-    v4d R[FSTW_TR], Cc[FSTW_TC];  // {32 n, p, 32 H, 1 / n}
+    v4d R[FSTW_TR], Cc[FSTW_TC];  // full: {32 n, p, 32 H, 1 / n}; reduced: {p, 2 c, H, 1 / (2 n)}
+    int Rn[FSTW_TR], Cn[FSTW_TC];
 #pragma unroll
     for (int i = 0; i < FSTW_TR; i++) {
-      const v2d a = *(lv2d*)(pr[i] + OFF), b = *(lv2d*)(pr[i] + OFF + (FSTT_SB - FSTT_SA));
+      const v2d a = *(lv2d*)(pr[i] + OFF), b = *(lv2d*)(pr[i] + OFF + (SB - SA));
       R[i] = v4d{a[0], a[1], b[0], b[1]};
+      Rn[i] = RED ? *(lint*)(qr[i] + OFF / 4) : 0;
     }
 #pragma unroll
     for (int j = 0; j < FSTW_TC; j++) {
-      const v2d a = *(lv2d*)(pc[j] + OFF), b = *(lv2d*)(pc[j] + OFF + (FSTT_SB - FSTT_SA));
+      const v2d a = *(lv2d*)(pc[j] + OFF), b = *(lv2d*)(pc[j] + OFF + (SB - SA));
       Cc[j] = v4d{a[0], a[1], b[0], b[1]};
+      Cn[j] = RED ? *(lint*)(qc[j] + OFF / 4) : 0;
     }
     double av[NPT], dv[NPT];
     bool ok = true;
@@ -504,24 +615,44 @@ __global__ __launch_bounds__(256, 3) void tpg_fst_wc84_tile_kernel(FstSrc src, i
       for (int j = 0; j < FSTW_TC; j++) {
         const int k = i * FSTW_TC + j;
         const v4d s1 = R[i], s2 = Cc[j];
-        // 16 bytes per valid allele of the pair: 32 (n1 + n2), an exact small integer in FP64
-        const int A16 = __double2int_rz(s1[0] + s2[0]);  // <= 16 kmax (the staging clamps n)
-        const v2d ta = *(const v2d*)(shb + A16), tb = *(const v2d*)(shb + A16 + FSTT_TAB2);
-        const v4d t = v4d{ta[0], ta[1], tb[0], tb[1]};
-        const double p_bar = fma(s2[1], s2[0], s1[1] * s1[0]) * t[0], h_bar = (s1[2] + s2[2]) * t[0];
-        const double d = s1[1] - s2[1], d2 = d * d;
-        const double half_s2 = (d2 * (s1[0] * s2[0])) * (t[0] * t[0]);
-        const double core = fma(-p_bar, p_bar, p_bar) - half_s2;
-        const double X = t[3] * (s1[3] * s2[3]);
-        const double a = fma(-X, fma(-0.25, h_bar, core), 0.5 * d2);
-        const double b = t[2] * fma(-t[1], h_bar, core);
-        const double den = fma(0.5, h_bar, a + b);
-        av[k] = a; dv[k] = den;
-        ok = ok && den == den;
+        if (RED) {
+          // 16 bytes per valid allele of the pair: 32 (n1 + n2) <= 16 kmax (the staging clamps n)
+          const v2d t = *(const v2d*)(shb + (Rn[i] + Cn[j]));  // {alpha, r}
+          const double d = s1[0] - s2[0], d2 = d * d;
+          const double cs = s1[1] + s2[1], hs = s1[2] + s2[2], en = s1[3] + s2[3];
+          const double w = t[0] * en;                   // (alpha / 2) (1 / n1 + 1 / n2)
+          av[k] = fma(-w, fma(-0.5, hs, cs), d2);       // 2 a
+          dv[k] = fma(t[0], fma(-t[1], hs, cs), av[k]);  // 2 den
+        } else {
+          // 16 bytes per valid allele of the pair: 32 (n1 + n2), an exact small integer in FP64
+          const int A16 = __double2int_rz(s1[0] + s2[0]);  // <= 16 kmax (the staging clamps n)
+          const v2d ta = *(const v2d*)(shb + A16), tb = *(const v2d*)(shb + A16 + TAB2);
+          fstt_full_pair(s1, s2, v4d{ta[0], ta[1], tb[0], tb[1]}, av[k], dv[k]);
+        }
+        ok = ok && dv[k] == dv[k];
       }
     if (__all(ok)) {  // (an unused slot of the tile sums what nobody reads)
 #pragma unroll
       for (int k = 0; k < NPT; k++) { sum_num[k] += av[k]; sum_den[k] += dv[k]; }
+    } else if (RED) {
+      // some pair of the wave is singular at this locus, or has an empty population: the whole locus by the full statements
+#pragma unroll
+      for (int i = 0; i < FSTW_TR; i++)
+#pragma unroll
+        for (int j = 0; j < FSTW_TC; j++) {
+          const int k = i * FSTW_TC + j;
+          // (read again: what the common path holds in registers need not live across the divisions)
+          const v2d ra = *(lv2d*)(pr[i] + OFF), rb = *(lv2d*)(pr[i] + OFF + (SB - SA));
+          const v2d ca = *(lv2d*)(pc[j] + OFF), cb = *(lv2d*)(pc[j] + OFF + (SB - SA));
+          const int rn = *(lint*)(qr[i] + OFF / 4), cn = *(lint*)(qc[j] + OFF / 4);
+          const v4d s1 = v4d{(double)rn, ra[0], 32.0 * rb[0], 2.0 * rb[1]};
+          const v4d s2 = v4d{(double)cn, ca[0], 32.0 * cb[0], 2.0 * cb[1]};
+          double t0, t1, t2, t3, a, den;
+          fstt_full_table((rn + cn) >> 4, t0, t1, t2, t3);
+          fstt_full_pair(s1, s2, v4d{t0, t1, t2, t3}, a, den);
+          if (den == den) { sum_num[k] += 2.0 * a; sum_den[k] += 2.0 * den; }  // a NaN numerator makes the denominator NaN too
+          __builtin_amdgcn_sched_barrier(0);  // pair after pair: six interleaved pairs of divisions spill
+        }
     } else {
 #pragma unroll
       for (int k = 0; k < NPT; k++)
@@ -536,44 +667,52 @@ __global__ __launch_bounds__(256, 3) void tpg_fst_wc84_tile_kernel(FstSrc src, i
     for (int i = 0; i < SLOTS; i++) {
       if ((int)(threadIdx.x & 63u) < G) {
         // src/grouped_summaries_dip_pseudo_cpp.cpp:40-56 on the counts (diploids): n = 2 valid, freq, het_obs -- without a
-        // division: 1 / n is the table's own 1 / nt at 2 n valid alleles (32 t[0], exact), freq = alleles * (0.5 / n) (one ulp
+        // division: 1 / n is the table's own 1 / nt at 2 n valid alleles (exact), freq = alleles * (0.5 / n) (one ulp
         // from the quotient: these are the totals, 1e-11 is the contract), and H = het_obs * n IS the heterozygote count
         // (kmax = 4 x the largest population: n <= kmax / 4 whenever the counts belong to these populations; the clamp is what
         // keeps the pair's table offset 32 (n1 + n2) inside the table if they do not, instead of a test per pair and locus)
         const int nv = min(pnv[i], kmax >> 2);
-        const double rn = 32.0 * *(const double*)(shb + (uint32_t)nv * 32u);  // 1 / n; n = 0: inf, and 0 * inf = NaN below, as 0 / 0 was
+        // 1 / n; n = 0: inf, and 0 * inf = NaN below, as 0 / 0 was
+        const double rn = RED ? *(const double*)(shb + (uint32_t)nv * 32u + 8u) : 32.0 * *(const double*)(shb + (uint32_t)nv * 32u);
         const double ni = (double)nv;
         const double vp = (double)(pn1[i] + 2 * pn2[i]) * (0.5 * rn);
         const uint32_t q = threadIdx.x + 256u * (uint32_t)i;
-        *(v2d*)(shb + FSTT_SA + q * 16u) = v2d{32.0 * ni, vp};
-        *(v2d*)(shb + FSTT_SB + q * 16u) = v2d{32.0 * (double)pn1[i], rn};
+        if (RED) {
+          *(v2d*)(shb + SA + q * 16u) = v2d{vp, ((2.0 * ni) * vp) * (1.0 - vp)};
+          *(v2d*)(shb + SB + q * 16u) = v2d{(double)pn1[i], 0.5 * rn};
+          *(int*)(shb + SN + q * 4u) = 32 * nv;
+        } else {
+          *(v2d*)(shb + SA + q * 16u) = v2d{32.0 * ni, vp};
+          *(v2d*)(shb + SB + q * 16u) = v2d{32.0 * (double)pn1[i], rn};
+        }
       }
     }
     __syncthreads();
     fetch(ch + gridDim.x);
     const int lmax = (int)((m - j0) < LB ? (m - j0) : LB);
     if (!active) continue;
-    lchar *pr[FSTW_TR], *pc[FSTW_TC];
+    lchar *pr[FSTW_TR], *pc[FSTW_TC], *qr[FSTW_TR], *qc[FSTW_TC];
 #pragma unroll
-    for (int i = 0; i < FSTW_TR; i++) pr[i] = (lchar*)(shb + FSTT_SA + ro[i]);
+    for (int i = 0; i < FSTW_TR; i++) { pr[i] = (lchar*)(shb + SA + ro[i]); qr[i] = (lchar*)(shb + SN + (ro[i] >> 2)); }
 #pragma unroll
-    for (int j = 0; j < FSTW_TC; j++) pc[j] = (lchar*)(shb + FSTT_SA + co[j]);
+    for (int j = 0; j < FSTW_TC; j++) { pc[j] = (lchar*)(shb + SA + co[j]); qc[j] = (lchar*)(shb + SN + (co[j] >> 2)); }
     int l = 0;
     for (; l + 2 <= lmax; l += 2) {
-      locus(pr, pc, std::integral_constant<int, 0>{});
-      locus(pr, pc, std::integral_constant<int, GS * 16>{});
+      locus(pr, pc, qr, qc, std::integral_constant<int, 0>{});
+      locus(pr, pc, qr, qc, std::integral_constant<int, GS * 16>{});
 #pragma unroll
-      for (int i = 0; i < FSTW_TR; i++) pr[i] += 2 * GS * 16;
+      for (int i = 0; i < FSTW_TR; i++) { pr[i] += 2 * GS * 16; qr[i] += 2 * GS * 4; }
 #pragma unroll
-      for (int j = 0; j < FSTW_TC; j++) pc[j] += 2 * GS * 16;
+      for (int j = 0; j < FSTW_TC; j++) { pc[j] += 2 * GS * 16; qc[j] += 2 * GS * 4; }
     }
-    if (l < lmax) locus(pr, pc, std::integral_constant<int, 0>{});
+    if (l < lmax) locus(pr, pc, qr, qc, std::integral_constant<int, 0>{});
   }
+  const double scale = RED ? 0.5 : 1.0;
 #pragma unroll
   for (int k = 0; k < NPT; k++)
     if (pidx[k] >= 0) {
-      part[((int64_t)blockIdx.x * P + pidx[k]) * 2] = sum_num[k];
-      part[((int64_t)blockIdx.x * P + pidx[k]) * 2 + 1] = sum_den[k];
+      part[((int64_t)blockIdx.x * P + pidx[k]) * 2] = scale * sum_num[k];
+      part[((int64_t)blockIdx.x * P + pidx[k]) * 2 + 1] = scale * sum_den[k];
     }
 }
 
@@ -588,7 +727,8 @@ __global__ void tpg_freq_ref_check_kernel(const double* __restrict__ p, const do
 
 static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const int32_t* pairs1, int P, int by_locus,
                    int return_num_dem, double* fst_tot, double* out_a, double* out_b, double* sum_num = nullptr,
-                   double* sum_den = nullptr, int kmax = 0 /* valid alleles of a pair at most (0: unknown) */) {
+                   double* sum_den = nullptr, int kmax = 0 /* valid alleles of a pair at most (0: unknown) */,
+                   int gmin = 0 /* individuals of the smallest group (0: unknown) */) {
   TPG_REQUIRE(method == TPG_FST_HUDSON || method == TPG_FST_NEI87 || method == TPG_FST_WC84, TPG_EINVAL,
               "unknown Fst method %d", method);
   TPG_REQUIRE(P > 0 && pairs1, TPG_EINVAL, "no population pairs");
@@ -609,9 +749,9 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
   TPG_REQUIRE((size_t)LB * G * 4 * sizeof(double) <= 150 * 1024, TPG_EUNSUPPORTED, "too many populations (%d)", G);
   const size_t shmem = (size_t)LB * G * 4 * sizeof(double);
   const bool fast = !by_locus;  // exact statement order whenever per-locus values are returned
-  if (fast && method == TPG_FST_HUDSON) {  // totals only: three masked matrix products over the loci
+  if (fast && method == TPG_FST_HUDSON) {  // totals only: masked matrix products over the loci
     const int ntile = (int)ceil_div(G, FSTG_T);
-    const int64_t cells = (int64_t)ntile * ntile * 3 * FSTG_T * FSTG_T;
+    const int64_t cells = (int64_t)ntile * ntile * FSTG_TS;
     const int64_t nch = ceil_div(m, FSTG_LB);
     int nbx = (int)std::min<int64_t>(nch, std::max(1, 4 * ctx->num_cu / (ntile * ntile)));
     OutBuf ot, osn, osd;
@@ -623,7 +763,7 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
     double* d_full = d_gp + (size_t)cells * (size_t)nbx;
     // reciprocals by table when the source is the class counts of diploids and the table fits (kmax valid alleles at most)
     const int kq = (src.cnt && !src.has_hap && kmax > 0 && kmax <= 4096) ? kmax : 0;
-    const size_t shg = sizeof(double) * (4 * FSTG_LB * FSTG_RS_MFMA + 2 * ((size_t)kq + 1));
+    const size_t shg = sizeof(double) * (4 * FSTG_LB * FSTG_RS_MFMA + 2 * ((size_t)kq + 1) + FSTG_LB + 1);  // (+ the locus flags)
     (void)hipFuncSetAttribute((const void*)tpg_fst_hudson_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shg);
     TPG_LAUNCH(ctx, "fst_hudson", tpg_fst_hudson_gemm_kernel, dim3((unsigned)nbx, (unsigned)(ntile * ntile)), dim3(256), shg,
                src, m, G, ntile, kq, d_gp);
@@ -674,8 +814,14 @@ static int run_fst(tpg_ctx* ctx, int method, FstSrc src, int64_t m, int G, const
     if (ntask > 0) {
       const int nbt2 = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (int64_t)nblocks));
       dim3 tgrid((unsigned)nbt2, (unsigned)ceil_div(ntask, 256));
-      TPG_LAUNCH(ctx, "fst_wc84", tpg_fst_wc84_tile_kernel, tgrid, dim3(256), 0, src, m, G, kmax, tb.dev<int32_t>(), ntask, P,
-                 d_part);
+      // the reduced pair unless some group is so small that its pairs are singular at every locus (every wave would then
+      // form every locus twice): such panels get the full pair
+      if (gmin >= FSTT_MIN_GROUP)
+        TPG_LAUNCH(ctx, "fst_wc84", tpg_fst_wc84_tile_kernel<true>, tgrid, dim3(256), 0, src, m, G, kmax, tb.dev<int32_t>(), ntask,
+                   P, d_part);
+      else
+        TPG_LAUNCH(ctx, "fst_wc84", tpg_fst_wc84_tile_kernel<false>, tgrid, dim3(256), 0, src, m, G, kmax, tb.dev<int32_t>(), ntask,
+                   P, d_part);
     } else {
 #define FSTW_LAUNCH(PP, GSV)                                                                                                    \
   do {                                                                                                                          \
@@ -768,8 +914,9 @@ static int fused_fst(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, 
   FstSrc src{gc.cnt, gc.Mpad, gc.Cpad, cp.has_hap, nullptr, nullptr, nullptr, nullptr};
   // the valid alleles of a pair of populations never exceed four times the largest group
   const int64_t kmax = 4 * (int64_t)*std::max_element(cp.group_size.begin(), cp.group_size.end());
+  const int64_t gmin = *std::min_element(cp.group_size.begin(), cp.group_size.end());
   return run_fst(ctx, method, src, v->m, ngroups, pairs1, P, by_locus, return_num_dem, fst_tot, out_a, out_b, sum_num,
-                 sum_den, kmax < (1 << 20) ? (int)kmax : 0);
+                 sum_den, kmax < (1 << 20) ? (int)kmax : 0, (int)std::min<int64_t>(gmin, 1 << 20));
 }
 
 extern "C" int tpg_pairwise_pop_fst(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups,
