@@ -243,6 +243,60 @@ typedef struct tpg_ld_report {
 int tpg_ld_clump(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, double thr_r2, const double* S,
                  const uint8_t* exclude, uint8_t* keep, tpg_ld_report* report);
 
+/* ---- LD-kNN imputation (gt_impute_knn; the method of LinkImpute's LD-kNNi, Money et al. 2015, stated here in integers) ------
+ * The reference's second imputation, gt_impute_xgboost, fits boosted trees per locus; this is the published method that does
+ * the same job -- a missing genotype is filled from the individuals that look alike at the loci in strongest LD -- and it can
+ * be pinned to bits.  The definition is this project's own.
+ * Inputs: a raw view v (n individuals, m loci, codes 0 / 1 / 2 / 3 = missing; code256 == NULL or CODE_012); the window hi[m]
+ *   exactly as "LD clumping" takes it (for k > j locus k is a neighbour of j iff k <= hi[j]; for k < j iff j <= hi[k]); l, k and
+ *   min_r2.  1 <= l <= 32, k >= 1, min_r2 >= 0 and finite, n < 2^22, a view with a locus-tiled layout: anything else is
+ *   TPG_EINVAL with nothing written.
+ * Step 1, LD neighbours, on w = tpg_view_impute(v, TPG_IMPUTE_MODE), the fill the PCA uses (a locus typed nowhere stays
+ *   missing there and is never a candidate).  From w's counts, as LD clumping forms them: Sx, Sxx, d = n Sxx - Sx^2 held as a
+ *   double (exact below 2^46).  For a pair of loci num = n Sxy - Sx_j Sx_k in int64, dn = (double)num and
+ *       r2 = (dn * dn) / (d_j * d_k)
+ *   -- three IEEE double operations in this order, no FMA contraction.  The CANDIDATES of j are its neighbours k with d_j > 0,
+ *   d_k > 0 and r2 > min_r2; nbr(j, 0 .. l_j - 1) are the candidates of largest r2, ties to the smaller |k - j|, then to the
+ *   smaller k; l_j = min(l, number of candidates).  Unused slots hold nbr = -1 and r2 = 0.
+ * Step 2, distances, on v itself: D_j(a, b) = sum_t c(v[a, q_t], v[b, q_t]) over q_t = nbr(j, t), with c(x, y) = |x - y| when
+ *   both are typed and 1 otherwise; 0 <= D <= 2 l_j <= 64.
+ * Step 3, the vote, for every (i, j) with v[i, j] == 3: hist[dist][g] counts the individuals b with v[b, j] = g in {0, 1, 2}
+ *   and D_j(i, b) = dist (i is missing at j and never counts itself); T = sum hist.  T = 0: the entry stays 3.  Otherwise
+ *   d* = the smallest dist with sum_{dist' <= dist} sum_g hist[dist'][g] >= min(k, T) -- the whole boundary distance takes
+ *   part, no tie is broken by index, so the result depends on no order -- s_g = sum_{dist <= d*} hist[dist][g] *
+ *   ((1 << 24) / (1 + dist)) with integer division in int64, and the fill is the g of largest s_g, the smaller g on a tie.
+ *   With l_j = 0 every distance is 0 and the fill is the locus's mode over v (tpg_view_impute's TPG_IMPUTE_MODE).
+ * Outputs: a NEW view of v's geometry that holds the fills (what tpg_view_impute returns for the simple methods);
+ *   rep = {imputed, loci_all_missing}; rep_knn (int64[2], may be NULL) = {entries_left: entries that stayed 3 (T = 0),
+ *   loci_without_neighbours: loci with a missing entry and l_j = 0}.
+ * Store form: a byte store (the view is the whole store, raw bytes) receives byte 4 + fill wherever it holds 3, as "simple
+ *   imputation" specifies; a byte above 3 anywhere: TPG_EUNSUPPORTED ("object x is already imputed") before anything is
+ *   written; a .bed-form store: TPG_EUNSUPPORTED, use the view form.
+ * Error estimate (the counterpart of xgboost's imputed_errors): train = tpg_view_holdout_fraction(v, fraction, seed) is
+ *   imputed with the same hi, l, k, min_r2; tpg_view_impute_errors counts per locus the entries typed in `full` and missing
+ *   in `train`, and how many of them `filled` has wrong (an entry left at 3 is wrong): per_locus = m x 2 int64 row-major
+ *   {held, wrong}, totals = their two sums (host memory).  Nothing proportional to n m leaves the device.
+ * flags: 0, or for the tests TPG_KNN_PROFILES_GLOBAL (the vote reads the profiles from global scratch, as it does above
+ *   11 520 individuals where LDS no longer holds them) and TPG_KNN_SMALL_CHUNKS (the band of Sxy values is walked in chunks of a
+ *   few KiB instead of 256 MiB); neither changes a bit of any result.
+ * hi, nbr, r2 and per_locus may be host or device memory. */
+#define TPG_KNN_PROFILES_GLOBAL 1
+#define TPG_KNN_SMALL_CHUNKS 2
+/* step 1 alone on a view in which every locus is typed everywhere or nowhere (a locus typed in part: TPG_ENUMERIC):
+ * nbr = m x l int32 and r2 = m x l doubles, row-major */
+int tpg_ld_top_neighbours(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, int l, double min_r2, int flags, int32_t* nbr,
+                          double* r2);
+int tpg_view_impute_knn(tpg_ctx* ctx, const tpg_view* raw, const int64_t* hi, int l, int k, double min_r2, int flags,
+                        tpg_view** out, tpg_impute_report* rep, int64_t* rep_knn);
+int tpg_fbm_impute_knn(tpg_ctx* ctx, tpg_fbm* fbm, const int64_t* hi, int l, int k, double min_r2, int flags,
+                       tpg_impute_report* rep, int64_t* rep_knn);
+int tpg_view_impute_errors(tpg_ctx* ctx, const tpg_view* full, const tpg_view* train, const tpg_view* filled,
+                           int64_t* per_locus, int64_t* totals);
+/* the device memory a tpg_view_impute_knn call plans beyond the raw view: the mode-filled view and the result, one chunk of
+ * the band (at most 256 MiB, or the 32 loci a chunk cannot go below), nbr and r2, the per-locus tables, and above 11 520
+ * individuals the profiles of two workgroups per CU (256 CUs assumed) */
+size_t tpg_knn_impute_scratch_bytes(int64_t n, int64_t m, int64_t width, int l);
+
 /* ---- Runs of homozygosity (windows_indiv_roh, R/windows_indiv_roh.R:65-150 around detectRUNS::slidingRuns) ---------------
  * detectRUNS is not part of the reference checkout, so the definition below is this project's own.  It is
  * stated in integers; the two places where a double appears are spelled out.

@@ -175,6 +175,12 @@ PROTOTYPES = {
     # ---- LD clumping
     "tpg_ld_band_links": (ci, [vp, vp, vp, f64, vp, i64, vp]),
     "tpg_ld_clump": (ci, [vp, vp, vp, f64, vp, vp, vp, P(LdReport)]),
+    # ---- LD-kNN imputation
+    "tpg_ld_top_neighbours": (ci, [vp, vp, vp, ci, f64, ci, vp, vp]),
+    "tpg_view_impute_knn": (ci, [vp, vp, vp, ci, ci, f64, ci, vp, P(ImputeReport), vp]),
+    "tpg_fbm_impute_knn": (ci, [vp, vp, vp, ci, ci, f64, ci, P(ImputeReport), vp]),
+    "tpg_view_impute_errors": (ci, [vp, vp, vp, vp, vp, vp]),
+    "tpg_knn_impute_scratch_bytes": (sz, [i64, i64, i64, ci]),
     # ---- runs of homozygosity
     "tpg_roh_chunk_loci": (i64, []),
     "tpg_roh_snp_status": (ci, [vp, vp, vp, vp, P(RohParams), vp, i64]),

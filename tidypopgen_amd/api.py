@@ -324,6 +324,23 @@ class View:
         v.n_held = int(held.value)
         return v
 
+    def impute_knn(self, hi, l: int = 10, k: int = 8, min_r2: float = 0.0, _flags: int = 0) -> "View":
+        """a new view of the same rows / columns with the missing genotypes of this (raw) view filled by LD-kNN imputation
+        (tpg_view_impute_knn, include/tpg.h "LD-kNN imputation"): for a missing genotype at locus j the l loci in strongest LD
+        with j inside the window `hi` (ld_window_hi) say which individuals are alike, and the k nearest vote.  The report
+        {"imputed", "loci_all_missing", "entries_left", "loci_without_neighbours"} is left in `.impute_report` of the result."""
+        hi = _ld_hi(self, hi)
+        h = C.c_void_p()
+        rep = _lib.ImputeReport()
+        extra = (C.c_int64 * 2)()
+        check(lib.tpg_view_impute_knn(self.ctx.h, self.h, _ptr(hi), int(l), int(k), float(min_r2), int(_flags), C.byref(h),
+                                      C.byref(rep), extra))
+        v = View.__new__(View)
+        v.X, v.ctx, v.h = self.X, self.ctx, h
+        v.n, v.m = int(lib.tpg_view_n(h)), int(lib.tpg_view_m(h))
+        v.impute_report = _knn_report(rep, extra)
+        return v
+
     def select_loci(self, idx) -> "View":
         """a new view of the loci idx (0-based positions in this view; any order, duplicates allowed) gathered on the device
         (tpg_view_select_loci): also works where the store cannot be packed again, as behind impute()"""
@@ -3163,6 +3180,84 @@ def gt_impute_simple(X: FBM, method: str = "mode", seed: int = 0) -> FBM:
     An error where the reference stops: "object x is already imputed" (a store byte above 3), and a .bed-form store,
     which cannot hold an imputed byte (impute a View of it)."""
     X.impute_report = X.impute_simple(method, seed)
+    X.code256 = CODE_IMPUTE_PRED.copy()
+    return X
+
+
+# ---------------------------------------------------------------------------
+# LD-kNN imputation (include/tpg.h "LD-kNN imputation")
+
+KNN_PROFILES_GLOBAL, KNN_SMALL_CHUNKS = 1, 2  # TPG_KNN_*: the tests' ways into the other paths; no result changes
+
+
+def _knn_report(rep, extra) -> dict:
+    return {"imputed": int(rep.imputed), "loci_all_missing": int(rep.loci_all_missing), "entries_left": int(extra[0]),
+            "loci_without_neighbours": int(extra[1])}
+
+
+def ld_top_neighbours(v: View, hi, l: int = 10, min_r2: float = 0.0, _flags: int = 0):
+    """tpg_ld_top_neighbours on a view without missing genotypes (a locus typed nowhere is allowed and is nobody's neighbour):
+    for every locus the l loci of largest r^2 inside the window hi -> (nbr (m, l) int32, -1 = unused; r2 (m, l) float64)"""
+    hi = _ld_hi(v, hi)
+    l = int(l)
+    nbr = np.full((v.m, max(l, 0)), -1, dtype=np.int32)
+    r2 = np.zeros((v.m, max(l, 0)), dtype=np.float64)
+    check(lib.tpg_ld_top_neighbours(v.ctx.h, v.h, _ptr(hi), l, float(min_r2), int(_flags), _ptr(nbr), _ptr(r2)))
+    return nbr, r2
+
+
+def view_impute_errors(full: View, train: View, filled: View) -> dict:
+    """tpg_view_impute_errors: per locus the entries typed in `full` and missing in `train`, and how many of them `filled` has
+    wrong -> {"per_locus": (2, m) int64 [held; wrong], "held", "wrong"}"""
+    per = np.zeros((full.m, 2), dtype=np.int64)
+    tot = (C.c_int64 * 2)()
+    check(lib.tpg_view_impute_errors(full.ctx.h, full.h, train.h, filled.h, _ptr(per), tot))
+    return {"per_locus": np.ascontiguousarray(per.T), "held": int(tot[0]), "wrong": int(tot[1])}
+
+
+def knn_impute_errors(v: View, hi, l: int = 10, k: int = 8, min_r2: float = 0.0, fraction: float = 0.05, seed: int = 0) -> dict:
+    """the error estimate of LD-kNN imputation on the raw view v (the counterpart of gt_impute_xgboost's imputed_errors): a share
+    `fraction` of the typed genotypes is held out (View.holdout_fraction), the rest imputed with the same hi, l, k and min_r2,
+    and the held-out entries compared with their fills on the device -> view_impute_errors' dict, plus "error" = wrong / held"""
+    train = v.holdout_fraction(fraction, seed)
+    filled = train.impute_knn(hi, l, k, min_r2)
+    out = view_impute_errors(v, train, filled)
+    out["error"] = out["wrong"] / out["held"] if out["held"] else float("nan")
+    train.free()
+    filled.free()
+    return out
+
+
+def knn_impute_scratch_bytes(n: int, m: int, width: int, l: int = 10) -> int:
+    """tpg_knn_impute_scratch_bytes: the device memory a View.impute_knn call plans beyond the raw view"""
+    return int(lib.tpg_knn_impute_scratch_bytes(n, m, width, l))
+
+
+def gt_impute_knn(X: FBM, l: int = 10, k: int = 8, size=100, chromosome=None, position=None, use_positions: bool = False,
+                  min_r2: float = 0.0, append_error: bool = False, error_fraction: float = 0.05, seed: int = 0, _flags: int = 0) -> FBM:
+    """LD-kNN imputation of the store X in place (tpg_fbm_impute_knn), where the reference offers gt_impute_xgboost: a missing
+    byte 3 becomes 4 + fill and X then reads through CODE_IMPUTE_PRED, like gt_impute_simple.  The window comes from
+    ld_window_hi(chromosome, position, size, use_positions): `size` loci either side, or size kb with use_positions.  The
+    report is left in `X.impute_report`; with append_error the (2, m) table [held; wrong] of knn_impute_errors, computed on the
+    store BEFORE it is filled, in `X.impute_errors`.  An error where gt_impute_simple stops: a store that is already imputed
+    (a byte above 3), and a .bed-form store (impute a View of it)."""
+    if use_positions and position is None:
+        raise ValueError("use_positions = TRUE needs positions; pass use_positions=False to count in loci")
+    hi = ld_window_hi(chromosome, position, size, use_positions, m=X.ncol)
+    if len(hi) != X.ncol:
+        raise ValueError("chromosome / position must describe every locus of the store")
+    hi = np.ascontiguousarray(hi, dtype=np.int64)
+    rep = _lib.ImputeReport()
+    extra = (C.c_int64 * 2)()
+    errors = None
+    if append_error:
+        raw = View(X, code256=None)  # (refuses nothing: an imputed store is refused by the call below, before anything is written)
+        errors = knn_impute_errors(raw, hi, l, k, min_r2, error_fraction, seed)
+        raw.free()
+    check(lib.tpg_fbm_impute_knn(X.ctx.h, X.h, _ptr(hi), int(l), int(k), float(min_r2), int(_flags), C.byref(rep), extra))
+    X.impute_report = _knn_report(rep, extra)
+    if errors is not None:
+        X.impute_errors = errors
     X.code256 = CODE_IMPUTE_PRED.copy()
     return X
 
