@@ -1608,6 +1608,70 @@ int tpg_lsq_solve(tpg_ctx* ctx, const double* A, const double* b, const int64_t*
 int tpg_predict_lsq(tpg_ctx* ctx, const tpg_view* v, const double* center, const double* scale, const double* V, int L, double* out,
                     int64_t* n_typed_out /* may be NULL */, int64_t* n_singular);
 
+/* ---- PC-Relate (gt_pcrelate: kinship and inbreeding that stay unbiased under population structure and admixture; Conomos,
+ * Reiner, Weir and Thornton 2016, as GENESIS::pcrelate computes it.  The reference has no pcrelate and GENESIS is not among its
+ * sources, so the arithmetic is defined HERE -- RECALLED, NOT PINNED to any other implementation: every individual's allele
+ * frequency at every locus is modelled from the PCA scores, and kinship is formed from the residuals) ---------------------------
+ * Inputs.  A view of n individuals x m loci, codes 0 / 1 / 2 / missing (missing genotypes are allowed).  V: n x K PCA scores,
+ *   column-major, host or device memory, 0 <= K <= TPG_PCRELATE_MAX_K.  thr: the frequency bound, 0 < thr < 0.5 (0.01 is the
+ *   customary value).  L = K + 1.  eps = 2^-53 below.
+ * 0. Basis (host, csrc/host/host_pcrelate.h).  Q (n x L, column-major) is an orthonormal basis of span[1, V]: column 0 is
+ *   1 / sqrt(n); column j = 1 .. K is V[, j - 1] after modified Gram-Schmidt against the columns before it, APPLIED TWICE, columns
+ *   ascending, every sum ascending in i from +0; nb / na = its norm before / after the projections, Q_ij = w_i / na.  A column with
+ *   na <= n 2^-52 nb (or a norm that is not finite) is a rank-deficient design: TPG_EINVAL.  n < L + 1: TPG_EINVAL.
+ * 1. Coefficients (device).  For locus s: t_s = the number typed, S1 = n1 + 2 n2 (integers), mean_s = S1 / t_s (one division;
+ *   t_s = 0: mean_s = 0), c_sk = sum_{i typed} (g_is - mean_s) Q_ik, k = 0 .. L - 1: the regression of the mean-imputed genotype
+ *   column on [1, V]; as 1 lies in the span, the fitted value is mean_s + sum_k Q_ik c_sk.  t_s = 0 gives c_s = 0, and the locus
+ *   drops out in step 2.  This is the FP64 row-scaled sweep of csrc/pca.hip with a scale of 1, a missing genotype adding 0; the
+ *   order of the sum over i is free.  Outputs mean[m], c (m x L, column-major).  Rounding, as for the beta of "pcadapt":
+ *   |d c_sk| <= n eps sqrt(tot_s) with tot_s = sum_{i typed} (g_is - mean_s)^2 (first order, any order of the sum, fused or
+ *   not), plus eps mean_s sum_{i typed} |Q_ik| <= eps 2 sqrt(n) from the rounding of mean_s.
+ * 2. Frequencies, validity, operands (device, PINNED order, no FMA contraction).  a_is = mean_s + sum_k Q_ik c_sk: starting from
+ *   mean_s, for k = 0 .. L - 1 in turn the product Q_ik c_sk is rounded and then added to the running sum; mu_is = 0.5 a_is.
+ *   valid_is = typed_is and thr <= mu_is <= hi, hi = 1 - thr rounded once.  For a valid cell R_is = g_is - a_is (2 mu is exact),
+ *   S_is = sqrt(mu_is (1 - mu_is)) (1 - mu rounded, the product rounded, the root), M_is = 1; an invalid cell is 0 in all three.
+ *   Given the same mean, c and Q, mu and valid are bit for bit those of the numpy model (tests/pcrelate_ref.py).  A monomorphic
+ *   locus has c_s = 0 and mu = 0 or 1: invalid for everyone.
+ * 3. Grams (device).  Num = R R', Den = S S', Cnt = M M', n x n: the lower triangle is computed on v_mfma_f64_16x16x4_f64 and
+ *   mirrored.  Loci are accumulated in ascending blocks (tpg_pcrelate_block_loci) with no floating-point atomic: the same call
+ *   gives the same bits.  Cnt is an exact integer while m < 2^53.  |d Num_ij| <= (m + 2) eps sum_s |R_is R_js| (one rounding
+ *   per product, any order of the sum) plus the first-order term of the rounding of R itself, 2 eps sum_s |R_is R_js| (R is one
+ *   subtraction of the pinned a_is from 0, 1 or 2: within eps of g - a in relative terms); |d Den_ij| <= (m + 2 + 6) eps sum_s S_is S_js
+ *   (each S is within 3 eps of its value: two roundings under the root, which halves them, and a root within one ulp = 2 eps).
+ *   m here is the number of loci of the view.  tests/test_gpu_pcrelate.py evaluates both per cell
+ *   from the extended-precision route of tests/pcrelate_ref.py.
+ * 4. Epilogue (plain double).  kin_ij = Num_ij / (4 Den_ij); f_i = 2 kin_ii - 1; n_snp = Cnt.  Den_ij = 0 (no jointly valid
+ *   locus) gives NaN (0 / 0): an individual with every genotype missing has a NaN row, a NaN column and a NaN f.
+ * mean and c are INPUTS of steps 2 - 3: a caller may compute them from a training subset of unrelated individuals (the role of
+ * PC-AiR's partition) and hand them to tpg_pcrelate_gram.
+ * No n x m array of doubles exists anywhere: per block of B loci the operands R and S of the block are written once, in the
+ * fragment order of the MFMA, into 16 B bytes per padded row (tpg_pcrelate_scratch_bytes; B <= 1024, csrc/pcrelate.hip).
+ * Errors: a null argument, K or L out of range, thr outside (0, 0.5), an empty view, n < L + 1, a rank-deficient V: TPG_EINVAL;
+ * a value of mean, c or Q that is not finite: TPG_ENUMERIC.  All arrays host or device memory, column-major; the caller's memory
+ * is written at the end only.
+ * Not offered: the IBD-sharing probabilities k0 / k2 (dominance-coded Grams of the same shape: further chains of the same
+ * kernel), GENESIS's `scale` options and its small-sample correction, PC-AiR's choice of an unrelated training set,
+ * tpg_stream_* / tpg_multi_* forms, an R shim entry, K > 32. */
+#define TPG_PCRELATE_MAX_K 32
+/* loci per block for n individuals (a multiple of 128); bytes of operand scratch a call holds: bounded independently of m */
+int64_t tpg_pcrelate_block_loci(int64_t n);
+size_t tpg_pcrelate_scratch_bytes(int64_t n, int64_t m, int K);
+/* the most cells n m that tpg_pcrelate_isaf serves: 2^26 */
+int64_t tpg_pcrelate_isaf_max_cells(void);
+/* step 0, host memory only: V n x K (may be NULL when K = 0) -> Q n x (K + 1) */
+int tpg_pcrelate_basis(const double* V, int64_t n, int K, double* Q);
+/* step 1: Q n x L -> mean[m], c m x L */
+int tpg_pcrelate_coef(tpg_ctx* ctx, const tpg_view* v, const double* Q, int L, double* mean, double* c);
+/* step 2 as a dense result, for tests and small panels (n m <= tpg_pcrelate_isaf_max_cells(), else TPG_EINVAL): mu n x m
+ * doubles, valid n x m bytes 0 / 1 */
+int tpg_pcrelate_isaf(tpg_ctx* ctx, const tpg_view* v, const double* mean, const double* c, const double* Q, int L, double thr,
+                      double* mu, uint8_t* valid);
+/* steps 2 - 3: num, den, cnt n x n doubles, both triangles */
+int tpg_pcrelate_gram(tpg_ctx* ctx, const tpg_view* v, const double* mean, const double* c, const double* Q, int L, double thr,
+                      double* num, double* den, double* cnt);
+/* the whole, bit for bit the staged calls: kin n x n, f[n], n_snp n x n (may be NULL) */
+int tpg_pcrelate(tpg_ctx* ctx, const tpg_view* v, const double* V, int K, double thr, double* kin, double* f, int64_t* n_snp);
+
 #ifdef __cplusplus
 }
 #endif

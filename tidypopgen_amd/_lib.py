@@ -361,6 +361,15 @@ PROTOTYPES = {
     "tpg_lsq_normal": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp]),
     "tpg_lsq_solve": (ci, [vp, vp, vp, vp, i64, ci, vp, vp]),
     "tpg_predict_lsq": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    # ---- PC-Relate
+    "tpg_pcrelate_block_loci": (i64, [i64]),
+    "tpg_pcrelate_scratch_bytes": (sz, [i64, i64, ci]),
+    "tpg_pcrelate_isaf_max_cells": (i64, []),
+    "tpg_pcrelate_basis": (ci, [vp, i64, ci, vp]),
+    "tpg_pcrelate_coef": (ci, [vp, vp, vp, ci, vp, vp]),
+    "tpg_pcrelate_isaf": (ci, [vp, vp, vp, vp, vp, ci, f64, vp, vp]),
+    "tpg_pcrelate_gram": (ci, [vp, vp, vp, vp, vp, ci, f64, vp, vp, vp]),
+    "tpg_pcrelate": (ci, [vp, vp, vp, ci, f64, vp, vp, vp]),
 }
 
 for _name, (_restype, _argtypes) in PROTOTYPES.items():

@@ -3472,6 +3472,102 @@ def predict_gt_pca_lsq(pca: dict, X: FBM, ind_row=None, ind_col=None, lsq_pcs=(1
     return res if len(res) > 1 else out
 
 
+def pcrelate_scratch_bytes(n: int, m: int, k: int) -> int:
+    """tpg_pcrelate_scratch_bytes: the operand scratch a PC-Relate call on n x m holds -- bounded independently of m"""
+    return int(lib.tpg_pcrelate_scratch_bytes(int(n), int(m), int(k)))
+
+
+def pcrelate_block_loci(n: int) -> int:
+    """tpg_pcrelate_block_loci: the loci of one operand block for n individuals"""
+    return int(lib.tpg_pcrelate_block_loci(int(n)))
+
+
+def pcrelate_basis(V, n: Optional[int] = None) -> np.ndarray:
+    """tpg_pcrelate_basis (host only): the orthonormal basis Q (n x (K + 1)) of span[1, V] of include/tpg.h "PC-Relate", step 0.
+    V: n x K scores; K = 0 needs n.  A rank-deficient design and n < K + 2 raise TpgError (TPG_EINVAL)."""
+    V = np.zeros((int(n), 0), order="F") if V is None else np.asfortranarray(V, dtype=np.float64)
+    if V.ndim != 2 or (n is not None and V.shape[0] != int(n)):
+        raise _lib.TpgError(1, "V must be an n x K matrix")  # TPG_EINVAL: the sizes the C ABI cannot see
+    nn, K = V.shape
+    Q = np.zeros((nn, K + 1), order="F")
+    check(lib.tpg_pcrelate_basis(_ptr(V) if K else None, nn, K, _ptr(Q)))
+    return Q
+
+
+def _pcrelate_model(v: View, mean, c, Q):
+    mean = _f64(mean)
+    c, Q = np.asfortranarray(c, dtype=np.float64), np.asfortranarray(Q, dtype=np.float64)
+    if Q.ndim != 2 or c.ndim != 2 or Q.shape[0] != v.n or c.shape != (v.m, Q.shape[1]) or mean.shape != (v.m,):
+        raise _lib.TpgError(1, f"the view is {v.n} x {v.m}: Q must be {v.n} x L, c {v.m} x L and mean hold {v.m} values")  # TPG_EINVAL
+    return mean, c, Q
+
+
+def pcrelate_coef(v: View, Q) -> dict:
+    """tpg_pcrelate_coef, step 1: the regression of every mean-imputed locus of the view on the basis Q (n x L) ->
+    {"mean": m (over the typed genotypes), "c": m x L}"""
+    Q = np.asfortranarray(Q, dtype=np.float64)
+    if Q.ndim != 2 or Q.shape[0] != v.n:
+        raise _lib.TpgError(1, f"the view has {v.n} individuals: Q must have {v.n} rows")  # TPG_EINVAL
+    L = Q.shape[1]
+    mean, c = np.zeros(v.m), np.zeros((v.m, L), order="F")
+    check(lib.tpg_pcrelate_coef(v.ctx.h, v.h, _ptr(Q), L, _ptr(mean), _ptr(c)))
+    return {"mean": mean, "c": c}
+
+
+def pcrelate_isaf(v: View, mean, c, Q, maf_bound: float = 0.01) -> dict:
+    """tpg_pcrelate_isaf, step 2 as a dense result (tests and small panels: TpgError above the cell cap) ->
+    {"mu": n x m individual-specific allele frequencies, "valid": n x m bool}"""
+    mean, c, Q = _pcrelate_model(v, mean, c, Q)
+    mu = np.zeros((v.n, v.m), order="F")
+    valid = np.zeros((v.n, v.m), dtype=np.uint8, order="F")
+    check(lib.tpg_pcrelate_isaf(v.ctx.h, v.h, _ptr(mean), _ptr(c), _ptr(Q), Q.shape[1], float(maf_bound), _ptr(mu), _ptr(valid)))
+    return {"mu": mu, "valid": valid.astype(bool)}
+
+
+def pcrelate_gram(v: View, mean, c, Q, maf_bound: float = 0.01) -> dict:
+    """tpg_pcrelate_gram, steps 2 - 3: {"num": R R', "den": S S', "cnt": M M'} (n x n) from the model (mean, c) -- which may
+    come from a training subset of the individuals -- and the basis rows Q of the view's individuals"""
+    mean, c, Q = _pcrelate_model(v, mean, c, Q)
+    num, den, cnt = (np.zeros((v.n, v.n), order="F") for _ in range(3))
+    check(lib.tpg_pcrelate_gram(v.ctx.h, v.h, _ptr(mean), _ptr(c), _ptr(Q), Q.shape[1], float(maf_bound), _ptr(num), _ptr(den),
+                                _ptr(cnt)))
+    return {"num": num, "den": den, "cnt": cnt}
+
+
+def pcrelate(v: View, V, maf_bound: float = 0.01, return_counts: bool = True) -> dict:
+    """tpg_pcrelate: include/tpg.h "PC-Relate" on the view from the scores V (n x K; None: K = 0) in one call, bit for bit the
+    staged calls -> {"kin": n x n, "inbreeding": n[, "n_snp": n x n int64]}"""
+    V = np.zeros((v.n, 0), order="F") if V is None else np.asfortranarray(V, dtype=np.float64)
+    if V.ndim != 2 or V.shape[0] != v.n:
+        raise _lib.TpgError(1, f"the view has {v.n} individuals: V must have {v.n} rows")  # TPG_EINVAL
+    K = V.shape[1]
+    kin, f = np.zeros((v.n, v.n), order="F"), np.zeros(v.n)
+    ns = np.zeros((v.n, v.n), dtype=np.int64, order="F") if return_counts else None
+    check(lib.tpg_pcrelate(v.ctx.h, v.h, _ptr(V) if K else None, K, float(maf_bound), _ptr(kin), _ptr(f), _ptr(ns)))
+    out = {"kin": kin, "inbreeding": f}
+    if return_counts:
+        out["n_snp"] = ns
+    return out
+
+
+def gt_pcrelate(X: FBM, pca: dict, k: Optional[int] = None, ind_row=None, ind_col=None, maf_bound: float = 0.01,
+                return_counts: bool = True) -> dict:
+    """PC-Relate kinship and inbreeding (Conomos et al. 2016) of the kept rows / columns of X from the first k components of
+    `pca` (a gt_pca_* result of the same individuals; the scores are u * d; k = None: all of them, k = 0: the locus
+    frequencies alone), missing genotypes allowed -> {"kin", "inbreeding"[, "n_snp"]}; "kin" goes as it is into
+    filter_high_relatedness."""
+    u, d = np.asarray(pca["u"], dtype=np.float64), np.asarray(pca["d"], dtype=np.float64)
+    if k is None:
+        k = u.shape[1]
+    if np.ndim(k) != 0 or isinstance(k, (bool, np.bool_)) or int(k) != k or k < 0:
+        raise ValueError("'k' should be a single non-negative integer value")
+    k = int(k)
+    if k > u.shape[1]:
+        raise ValueError("K is too large: 'k' should not be larger than the number of components in 'pca'")
+    v = _raw_view(X, ind_row, ind_col)
+    return pcrelate(v, u[:, :k] * d[:k] if k else None, maf_bound=maf_bound, return_counts=return_counts)
+
+
 def oadp_inputs(pca: dict, X: FBM, ind_row=None, ind_col=None, code256=CODE_IMPUTE_PRED):
     """(XV, X_norm) that predict(project_method = "OADP") hands to bigsnpr::OADP_proj (R/predict_gt_pca.R:157-181)"""
     v = View(X, ind_row, ind_col, code256=code256)
