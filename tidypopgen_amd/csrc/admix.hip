@@ -704,55 +704,11 @@ extern "C" int tpg_admix_squarem_point(tpg_ctx* ctx, int64_t n, int64_t m, int K
 }
 
 // ---- cross-validation (include/tpg.h "admixture cross-validation") -----------------------------------------------------------
-// Two kernels.  admix_holdout_view: L -> the L of a new view with the typed entries of one fold set to code 3; the geometry of
-// tpg_impute_view_kernel (a wave per tile of 32 loci, four tiles per workgroup, lane (r, h) owns locus r), one read and one write of
-// the layout.  The fold of an entry is a hash of (cv_seed, i, j); M(i) of the 128 individuals of a block is the same for the four
-// tiles of a workgroup, so it is staged once per block through LDS (a broadcast read) and an entry costs one tpg_mix64.
+// admix_holdout_view is admix_common.h's hold-out with the fold predicate.
 // admix_holdout_sweep: the likelihood-only pass over the entries typed in `full` and missing in `train`: wave w decodes dword w of
 // BOTH planes at the same offset; the sum shape is that of admix_f_sweep_kernel<KT, false>; the two counts are integers (wave sum,
 // one integer atomic per wave).
 namespace {
-
-__host__ __device__ inline int admix_fold_of(uint64_t locus_key, uint64_t mi, int folds) {
-  const uint64_t h = tpg_mix64(locus_key ^ mi);
-  return (int)(((h >> 32) * (uint64_t)folds) >> 32);
-}
-
-__global__ __launch_bounds__(256) void admix_holdout_view_kernel(const uint4* __restrict__ L, uint4* __restrict__ out, int64_t n_lt,
-                                                                 int64_t Qb, int folds, int fold, uint64_t cv_seed,
-                                                                 unsigned long long* __restrict__ d_held) {
-  __shared__ uint64_t mi[2][128];  // M(i) of the block's individuals; two buffers: one barrier per block
-  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-  const int64_t lt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const bool live = lt < n_lt;  // a wave beyond the last tile still stages and meets the barriers
-  const uint64_t key = tpg_mix64((cv_seed ^ ADM_CV_SALT) ^ tpg_mix64((uint64_t)(lt * 32 + r)));
-  int held = 0;
-  for (int64_t q = 0; q < Qb; q++) {
-    uint64_t* __restrict__ ms = mi[q & 1];
-    if (threadIdx.x < 128) ms[threadIdx.x] = tpg_mix64((uint64_t)(128 * q + threadIdx.x));
-    __syncthreads();
-    if (!live) continue;
-    const uint4 a = L[(lt * Qb + q) * 64 + lane];
-    uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-      // typed entries only: the padding (individuals >= n, loci >= m) is code 3 and stays so
-      uint32_t typed = ~(w[d] & (w[d] >> 1)) & 0x55555555u;
-      while (typed) {
-        const int pos = __ffs(typed) - 1;  // 8 b + 2 k: element 4 k + b
-        typed &= typed - 1;
-        const int e = 4 * ((pos & 7) >> 1) + (pos >> 3);
-        if (admix_fold_of(key, ms[32 * d + 16 * h + e], folds) == fold) {
-          w[d] |= 3u << pos;
-          held++;
-        }
-      }
-    }
-    out[(lt * Qb + q) * 64 + lane] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  for (int o = 32; o > 0; o >>= 1) held += __shfl_xor(held, o);
-  if (lane == 0 && held) atomicAdd(d_held, (unsigned long long)held);
-}
 
 // one workgroup per tile of 32 loci; Lf / Lt: the L planes of the full and the training view (the same geometry).
 // ll_part[lt] = the tile's share of sum ln(p^g pbar^(2 - g)) over the held-out entries; d_cnt[0] += their number, d_cnt[1] += g = 1
@@ -786,7 +742,7 @@ __global__ __launch_bounds__(256) void admix_holdout_sweep_kernel(const uint32_t
     // as many trips as its fullest lane holds entries, not 16 with a share 1 / folds of its lanes active
     uint32_t mine = 0;
 #pragma unroll
-    for (int e = 0; e < 16; e++) mine |= ((ho >> (8 * (e & 3) + 2 * (e >> 2))) & 1u) << e;
+    for (int e = 0; e < 16; e++) mine |= ((ho >> tpg_elem_shift(e)) & 1u) << e;
     while (mine) {
       const int e = __ffs(mine) - 1;
       mine &= mine - 1;
@@ -826,24 +782,7 @@ int admix_check_folds(int folds) {
 int admix_view_holdout(tpg_ctx* ctx, const tpg_view* full, int folds, int fold, uint64_t cv_seed, tpg_view** out, int64_t* n_held) {
   TPG_TRY(admix_check_folds(folds));
   TPG_REQUIRE(fold >= 0 && fold < folds, TPG_EINVAL, "fold = %d out of [0, %d)", fold, folds);
-  TPG_TRY(tpg_view_need_L(ctx, full));
-  const int64_t n_lt = 4 * full->KG;
-  TPG_REQUIRE(ceil_div(n_lt, 4) <= 0x7FFFFFFF, TPG_EUNSUPPORTED, "a hold-out view of %lld loci", (long long)full->m);
-  ViewPtr v(new tpg_view(ctx, full->n, full->m));
-  DevBuf d_held;
-  TPG_HIP(tpg_pmalloc((void**)&v->L, v->bytes_each));
-  TPG_TRY(d_held.alloc(8));
-  TPG_HIP(hipMemsetAsync(d_held.p, 0, 8, ctx->stream));
-  TPG_LAUNCH(ctx, "admix_holdout_view", admix_holdout_view_kernel, dim3((unsigned)ceil_div(n_lt, 4)), dim3(256), 0,
-             (const uint4*)full->L, v->L, n_lt, full->Q, folds, fold, cv_seed, d_held.as<unsigned long long>());
-  TPG_CHECK_LAUNCH();
-  if (n_held) {
-    unsigned long long hh = 0;
-    TPG_HIP(tpg_fetch_small(ctx, &hh, d_held.p, sizeof hh));
-    *n_held = (int64_t)hh;
-  }
-  *out = v.release();
-  return TPG_OK;
+  return admix_holdout_view<HoldoutFold>(ctx, "admix_holdout_view", full, cv_seed, out, n_held != nullptr, n_held, folds, fold);
 }
 
 }  // namespace

@@ -16,6 +16,7 @@
 //     prefix, so the 63 steps need no host round trip: two small fetches per fence (the sorted statistics, the two ratios).
 // Integer atomics only; a result depends on the inputs alone.
 #include "common.h"
+#include "devfrag.h"
 #include "host/host_autosvd.h"
 
 #include <hipcub/hipcub.hpp>
@@ -28,7 +29,6 @@ namespace {
 constexpr int ASV_MAX_RADIUS = 1024;
 constexpr int MC_STEPS = 63;
 
-#define ASV_EXP_MASK 0x7FF0000000000000ull
 
 inline unsigned grid_for(int64_t count) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(count, 256), 4096)); }
 
@@ -119,18 +119,13 @@ int rollmean_device(tpg_ctx* ctx, const double* d_x, int64_t m, const int64_t* h
 }
 
 // ---- the fence ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double asv_unkey(uint64_t key) {
-  const uint64_t u = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-  return __longlong_as_double((long long)u);
-}
-
 // keys[i]: the order-preserving key of x[i] + 0.0; a value that is not finite gets the largest key and is not counted
 __global__ void asv_keys_kernel(const double* __restrict__ x, int64_t count, uint64_t* __restrict__ keys, unsigned long long* __restrict__ n_finite) {
   unsigned long long mine = 0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t u = (uint64_t)__double_as_longlong(x[i] + 0.0);
-    const bool ok = (u & ASV_EXP_MASK) != ASV_EXP_MASK;
-    keys[i] = ok ? ((u >> 63) ? ~u : (u | 0x8000000000000000ull)) : ~0ull;
+    const bool ok = (u & TPG_D_EXP_MASK) != TPG_D_EXP_MASK;
+    keys[i] = ok ? TPG_DKEY(u) : ~0ull;
     mine += ok ? 1ull : 0ull;
   }
   for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
@@ -149,30 +144,30 @@ __global__ void asv_stats_kernel(const uint64_t* __restrict__ s, const unsigned 
   TukeyStats st;
   st.c = c;
   st.pA = st.p0 = 0;
-  st.q1 = st.q3 = st.med = __longlong_as_double(0x7FF8000000000000ll);
+  st.q1 = st.q3 = st.med = TPG_QNAN;
   if (c > 0) {
     const double ps[2] = {0.25, 0.75};
     double q[2];
     for (int i = 0; i < 2; i++) {
       const double h = (double)(c - 1) * ps[i];
       const long long lo = (long long)floor(h), up = lo + 1 < c ? lo + 1 : c - 1;
-      const double a = asv_unkey(s[lo]), b = asv_unkey(s[up]);
+      const double a = tpg_dunkey(s[lo]), b = tpg_dunkey(s[up]);
       q[i] = a + (h - (double)lo) * (b - a);
     }
     st.q1 = q[0];
     st.q3 = q[1];
-    st.med = (c & 1) ? asv_unkey(s[(c - 1) / 2]) : (asv_unkey(s[c / 2 - 1]) + asv_unkey(s[c / 2])) / 2;
+    st.med = (c & 1) ? tpg_dunkey(s[(c - 1) / 2]) : (tpg_dunkey(s[c / 2 - 1]) + tpg_dunkey(s[c / 2])) / 2;
     long long lo = 0, hi = c;  // first index with z > 0
     while (lo < hi) {
       const long long mid = (lo + hi) / 2;
-      if (asv_unkey(s[mid]) - st.med > 0.0) hi = mid;
+      if (tpg_dunkey(s[mid]) - st.med > 0.0) hi = mid;
       else lo = mid + 1;
     }
     st.pA = lo;
     lo = 0, hi = st.pA;  // first index with z >= 0
     while (lo < hi) {
       const long long mid = (lo + hi) / 2;
-      if (asv_unkey(s[mid]) - st.med >= 0.0) hi = mid;
+      if (tpg_dunkey(s[mid]) - st.med >= 0.0) hi = mid;
       else lo = mid + 1;
     }
     st.p0 = lo;
@@ -197,7 +192,7 @@ __device__ __forceinline__ uint64_t asv_mc_prefix(const uint64_t* __restrict__ s
   long long lo = 0, hi = pA;
   while (lo < hi) {
     const long long mid = (lo + hi) / 2;
-    const double b = fabs(asv_unkey(s[pA - 1 - mid]) - med);
+    const double b = fabs(tpg_dunkey(s[pA - 1 - mid]) - med);
     if ((uint64_t)__double_as_longlong(b / a) <= cand) lo = mid + 1;
     else hi = mid;
   }
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(256) void asv_mc_step_kernel(const uint64_t* __rest
   const uint64_t c0 = cand[0], c1 = cand[1];
   unsigned long long mine0 = 0, mine1 = 0;
   for (long long i = pA + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < c; i += (long long)gridDim.x * blockDim.x) {
-    const double a = asv_unkey(s[i]) - med;
+    const double a = tpg_dunkey(s[i]) - med;
     const uint64_t n0 = asv_mc_prefix(s, pA, med, a, c0);
     mine0 += n0;
     mine1 += c1 == c0 ? n0 : asv_mc_prefix(s, pA, med, a, c1);

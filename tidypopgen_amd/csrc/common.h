@@ -376,7 +376,7 @@ static inline int tpg_deliver(tpg_ctx* ctx, T* user, const T* d_src, size_t coun
   else TPG_HIP(tpg_download(ctx, user, d_src, sizeof(T) * count));
   return TPG_OK;
 }
-// kmeans.hip: every entry of a device array finite, else TPG_ENUMERIC naming `what`; `sc` is the call's scratch (it gives the flag)
+// runtime.hip: every entry of a device array finite, else TPG_ENUMERIC naming `what`; `sc` is the call's scratch (it gives the flag)
 int tpg_check_finite(tpg_ctx* ctx, const double* dX, int64_t count, DevArena& sc, const char* what);
 // every [lo[i], hi[i]) inside [0, m], lo / hi in host or device memory; what = "window" | "block" (runtime.hip)
 int tpg_check_ranges(tpg_ctx* ctx, const int64_t* lo, const int64_t* hi, int64_t count, int64_t m, const char* what);

@@ -1,11 +1,111 @@
-// devfrag.h -- device-side helpers for the 2-bit fragment layout (see common.h).
+// devfrag.h -- device-side helpers for the 2-bit fragment layout (see common.h), and the one home of the fragment and wave
+// primitives every kernel file shares: the MFMA vector types and the FP4 scaled-MFMA wrapper, the operand words of an L
+// fragment, tpg_uniform64, tpg_static_for, tpg_wave_sum, the order-preserving key of a double, TPG_QNAN, the NaN-propagating
+// maximum and the team-of-lanes adapter.  A kernel file that needs one of them includes this header; it does not copy it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 typedef double v4d __attribute__((ext_vector_type(4)));
+
+#define TPG_QNAN __longlong_as_double(0x7FF8000000000000ll)
+
+// a wave-uniform value the compiler keeps in SGPRs
+__device__ __forceinline__ int64_t tpg_uniform64(int64_t x) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>), in ascending order
+template <int N, class F>
+__device__ __forceinline__ void tpg_static_for(F&& f) {
+  if constexpr (N > 0) {
+    tpg_static_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
+}
+
+// the sum over the 64 lanes of a wave, on every lane: a butterfly over xor 32, 16, 8, 4, 2, 1.  For the integer counts only.
+// The 64-bit and FP64 wave sums (pcadapt.hip, autosvd.hip, f2.hip, roh.hip, admix.hip, snmf.hip, admix_common.h) stay written
+// out at their sites, in this same order: through a function their kernels came out with reordered instructions, and for the
+// FP64 ones the order IS the result (the files built without FMA contraction state their sums by it).
+__device__ __forceinline__ int tpg_wave_sum(int x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+
+// Order-preserving 64-bit key of a double (u = its bits in an lvalue) and the inverse.  -0 and +0 get different keys: a caller
+// that wants equal values to have equal keys adds 0.0 first (pcadapt.hip, autosvd.hip) or maps 0 to +0 itself (ld.hip).
+// (u & TPG_D_EXP_MASK) == TPG_D_EXP_MASK: not finite.  The forward map is a macro so that its select compiles in place, inside
+// whatever test of the mask the call site makes around it.
+#define TPG_D_EXP_MASK 0x7FF0000000000000ull
+#define TPG_DKEY(u) (((u) >> 63) ? ~(u) : ((u) | 0x8000000000000000ull))
+__device__ __forceinline__ double tpg_dunkey(uint64_t key) {
+  const uint64_t u = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
+  return __longlong_as_double((long long)u);
+}
+
+// max(a, b), NaN if either is; and the same over sh[0 .. N - 1] of a workgroup of N threads (N a power of two), left in sh[0]
+__device__ __forceinline__ double tpg_nanmax(double a, double b) { return (a != a || b != b) ? TPG_QNAN : (a > b ? a : b); }
+template <int N>
+__device__ __forceinline__ void tpg_block_nanmax(double* sh) {
+  __syncthreads();
+  for (int w = N / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] = tpg_nanmax(sh[threadIdx.x], sh[threadIdx.x + w]);
+    __syncthreads();
+  }
+}
+
+// G consecutive lanes of a single-wave workgroup as the team of the row-wise FP64 solvers (host/host_lsq.h, host/host_oadp.h):
+// sync() is the workgroup barrier -- of that one wave -- and any() the barrier's OR
+template <int G>
+struct TpgTeam {
+  __device__ int lane() const { return (int)(threadIdx.x % G); }
+  __device__ int size() const { return G; }
+  __device__ void sync() const { __syncthreads(); }
+  __device__ bool any(bool b) const { return __syncthreads_or(b ? 1 : 0) != 0; }
+};
+
+// FP4 x FP4 (format code 4) scaled MFMA, 32 x 32 x 64: four operand dwords a side, widened to the eight the instruction
+// names, and the two E8M0 block-scale words (one byte per 32 contracted elements; the call sites keep their own constants)
+template <class V>
+__device__ __forceinline__ v8i tpg_w8(const V& a) { return v8i{(int)a[0], (int)a[1], (int)a[2], (int)a[3], 0, 0, 0, 0}; }
+__device__ __forceinline__ v8i tpg_w8(const uint4& a) { return v8i{(int)a.x, (int)a.y, (int)a.z, (int)a.w, 0, 0, 0, 0}; }
+template <class A, class B>
+__device__ __forceinline__ v16f tpg_mfma_f4(const A& a, const B& b, v16f c, int sa, int sb) {
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(tpg_w8(a), tpg_w8(b), c, 4, 4, 0, sa, 0, sb);
+}
+
+// the four FP4 operand dwords of half-group S (64 individuals) of one L fragment: eight codes each, in the low bits of the
+// nibbles (a 2-bit code c there is the FP4 value c / 2).  Which individual lands in which nibble is the same for every locus,
+// which is all a product of L with L needs.
+__device__ __forceinline__ void tpg_l_halfgroup_operand(const uint4& f, int S, uint32_t (&o)[4]) {
+  const uint32_t p0 = S == 0 ? f.x : f.z, p1 = S == 0 ? f.y : f.w;
+  o[0] = p0 & 0x33333333u;
+  o[1] = (p0 >> 2) & 0x33333333u;
+  o[2] = p1 & 0x33333333u;
+  o[3] = (p1 >> 2) & 0x33333333u;
+}
+
+// code 3 -> 0 in the 16 two-bit codes of a dword (the padding individuals of the last group)
+__device__ __forceinline__ uint32_t tpg_clear3(uint32_t w) {
+  const uint32_t miss = w & (w >> 1) & 0x55555555u;
+  return w & ~(miss * 3u);
+}
+__device__ __forceinline__ void tpg_clear3(uint4& f) {
+  f.x = tpg_clear3(f.x);
+  f.y = tpg_clear3(f.y);
+  f.z = tpg_clear3(f.z);
+  f.w = tpg_clear3(f.w);
+}
 
 // v_perm_b32 used as a 4-entry byte lookup: selector bytes 0..3 pick bytes of `lut`.
 // LUT byte c = value for code c (0,1,2 = dosage, 3 = missing).

@@ -24,6 +24,7 @@
 //               same kernel (two products instead of four).  With equal weights ap comes out of the first.
 // No atomics anywhere.
 #include "common.h"
+#include "devfrag.h"
 #include "host/host_f4jack.h"
 
 #include <math.h>
@@ -35,7 +36,6 @@ constexpr int F2_T = 64;                    // groups per tile side
 constexpr int F2_LB = TPG_F2_CHUNK_LOCI;    // loci per staged chunk
 constexpr int F2_RS = 80;                   // row stride of the staged arrays in doubles: 32 dwords modulo the 64 banks, so that the
                                             // loci l and l + 1 a half-wave reads fall on disjoint banks (as FSTG_RS_MFMA)
-#define F2_NAN __longlong_as_double(0x7FF8000000000000ll)
 typedef double f2_v4d __attribute__((ext_vector_type(4)));
 
 struct F2Src {
@@ -209,13 +209,13 @@ __global__ __launch_bounds__(256) void f2_gemm_kernel(F2Src src, int G, int ntil
       const int64_t o = base + g1 + (int64_t)g2 * G, ot = base + g2 + (int64_t)g1 * G;
       const double n = BB[ct][reg], cc = CC[ct][reg];  // n: a sum of ones below 2^53, exact
       if (WITH_A) {
-        double f = F2_NAN;
+        double f = TPG_QNAN;
         if (n > 0.0) f = g1 == g2 ? 0.0 : ((AB[ct][reg] + BA[ct][reg]) - 2.0 * cc) / n;
         if (out_f2) { out_f2[o] = f; if (!diag) out_f2[ot] = f; }
         if (out_cnt) { out_cnt[o] = (int32_t)n; if (!diag) out_cnt[ot] = (int32_t)n; }
       }
       if (out_ap) {
-        const double a = n > 0.0 ? cc / n : F2_NAN;
+        const double a = n > 0.0 ? cc / n : TPG_QNAN;
         out_ap[o] = a;
         if (!diag) out_ap[ot] = a;
       }

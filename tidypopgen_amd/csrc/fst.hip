@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void tpg_fst_kernel(FstSrc src, int64_t m, int
     for (int idx = threadIdx.x; idx < LB * G; idx += 256) {
       const int l = idx / G, g = idx % G;
       const int64_t j = j0 + l;
-      double vn = FST_NAN, vp = FST_NAN, vh = FST_NAN;
+      double vn = TPG_QNAN, vp = TPG_QNAN, vh = TPG_QNAN;
       if (j < m) fst_stage(src, m, j, g, vn, vp, vh);
       sh_n[idx] = vn; sh_p[idx] = vp; sh_h[idx] = vh;
       if (METHOD == TPG_FST_HUDSON) sh_e[idx] = (vp * (1 - vp)) / (vn - 1);  // (p q) / (n - 1), once per population
@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256, 3) void tpg_fst_wc84_tile_kernel(FstSrc src, i
     if (RED) {
       const double nt = 0.5 * (double)A;
       double* t = (double*)shb + (size_t)A * 2;
-      t[0] = A > 4 ? 1.0 / (nt - 2.0) : FST_NAN;  // nt <= 2: the pair is singular, the full statements decide
+      t[0] = A > 4 ? 1.0 / (nt - 2.0) : TPG_QNAN;  // nt <= 2: the pair is singular, the full statements decide
       t[1] = 1.0 / nt;
     } else {
       double t0, t1, t2, t3;

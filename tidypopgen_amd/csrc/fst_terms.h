@@ -4,8 +4,8 @@
 #include <math.h>
 
 #include "common.h"
+#include "devfrag.h"
 
-#define FST_NAN __longlong_as_double(0x7FF8000000000000ll)
 
 // e1 / e2: the per-(locus, population) term staged once per locus chunk -- Hudson: p q / (n - 1), hoisted out of
 // the pair loop with its operation order unchanged (src/pairwise_fst_hudson_loop.cpp:28-29), so values stay
@@ -82,7 +82,7 @@ __device__ __forceinline__ void fst_terms(double n1, double p1, double h1, doubl
     if (np1 == np1) { valid++; ho_sum += h1; nsum += 1.0; inv_nsum += 1.0 / np1; }
     if (np2 == np2) { valid++; ho_sum += h2; nsum += 1.0; inv_nsum += 1.0 / np2; }
     const double np = valid;
-    const double mn = (inv_nsum > 0) ? nsum / inv_nsum : FST_NAN;
+    const double mn = (inv_nsum > 0) ? nsum / inv_nsum : TPG_QNAN;
     const double mHo = ho_sum / valid;
     const double sp2a = p1 * p1 + p2 * p2;
     const double sp2r = q1 * q1 + q2 * q2;

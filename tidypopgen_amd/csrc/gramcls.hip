@@ -43,10 +43,6 @@
 #include "devfrag.h"
 #include "host/host_bits2.h"  // tpg_transpose16_2bit
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
 // This file is compiled with -mllvm -amdgpu-mfma-vgpr-form (csrc/Makefile): the MFMAs of the Gram kernel write their
 // sums to VGPRs and the kernel uses no AGPR at all, so that hipcc gives a two-waves-per-SIMD kernel its whole budget as
 // VGPRs (256 instead of 128 + 128) and a fold is v_cvt_f64_f32 + v_fma_f64 per element, without a v_accvgpr_read.
@@ -316,21 +312,6 @@ __global__ __launch_bounds__(256) void tpg_gcls_gather_kernel(GclsSrc S, int64_t
 }
 
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ v8i tpg_g8(v4u a) { return v8i{(int)a[0], (int)a[1], (int)a[2], (int)a[3], 0, 0, 0, 0}; }
-
-__device__ __forceinline__ int64_t tpg_uniform64(int64_t x) {  // a wave-uniform value the compiler keeps in SGPRs
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-template <int C, class F>
-__device__ __forceinline__ void tpg_static_for(F&& f) {
-  if constexpr (C > 0) {
-    tpg_static_for<C - 1>(f);
-    f(std::integral_constant<int, C - 1>{});
-  }
-}
-
 // ---------------------------------------------------------------------------
 // 3. class Gram.  Unit (I, J): row tiles 2I, 2I+1 against row tiles 2J, 2J+1 (a tile past the data reads the last
 // tile instead; the assemble kernel never looks at its products); one wave = a 64 x 64 tile of pairs over a range of
@@ -347,8 +328,7 @@ __device__ __forceinline__ void tpg_static_for(F&& f) {
 // and folds overlap at all: with one wave per SIMD (64 x 96 tiles, FP4 operands) the same work took 16.4 ms against 12.2.
 // The first MFMA of a class takes the inline constant 0 as C, so nothing is ever zeroed.
 // K split S: each (unit, split) writes its own FP64 slab with plain stores.
-#define MFMA_G4S2(a, b, c) \
-  __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(tpg_g8(a), tpg_g8(b), (c), 4, 4, 0, (int)0x80808080, 0, (int)0x80808080)
+#define GCLS_SC_TWO ((int)0x80808080)  // E8M0 block scale 2^+1, on both sides
 
 // GCLS_D rotating register slots of GA + GB source fragments (two blocks each), filled GCLS_D - 1 pairs ahead of their use;
 // the K loop is unrolled by GCLS_D so that no slot is ever copied.  (Tried and dropped: three slots -- hipcc spills;
@@ -441,10 +421,10 @@ __global__ __launch_bounds__(256, 2) void tpg_gcls_gram_kernel(const uint4* __re
                 if (first) {
                   const v16f z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-                  for (int p = 0; p < GP; p++) acc[p] = MFMA_G4S2(X[p / GB], X[GA + p % GB], z);
+                  for (int p = 0; p < GP; p++) acc[p] = tpg_mfma_f4(X[p / GB], X[GA + p % GB], z, GCLS_SC_TWO, GCLS_SC_TWO);
                 } else {
 #pragma unroll
-                  for (int p = 0; p < GP; p++) acc[p] = MFMA_G4S2(X[p / GB], X[GA + p % GB], acc[p]);
+                  for (int p = 0; p < GP; p++) acc[p] = tpg_mfma_f4(X[p / GB], X[GA + p % GB], acc[p], GCLS_SC_TWO, GCLS_SC_TWO);
                 }
                 first = false;
                 if ((wf & 1ull) || b == bl) {
@@ -498,8 +478,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // registers and ran at 43 ms: at 256 registers the allocator decides, so the existing loop was trimmed instead).
 // CEN: operands in the centred layout of tpg_gcls_gather_kernel<true> (one v_and_b32 per operand word; the odd block of a
 // pair takes the high halves of the nibbles, values +-2, with the block scales 2^-1 where the even block has 2^+1)
-#define MFMA_G4S2_ODD(a, b, c) \
-  __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(tpg_g8(a), tpg_g8(b), (c), 4, 4, 0, (int)0x7E7E7E7E, 0, (int)0x7E7E7E7E)
+#define GCLS_SC_HALF ((int)0x7E7E7E7E)  // E8M0 block scale 2^-1, on both sides
 template <bool CEN>
 __global__ __launch_bounds__(256, 2) void tpg_gcls_gram2_kernel(const uint4* __restrict__ T2g, int64_t nblocks, int64_t rs2, int nrtv,
                                                                 const ulonglong2* __restrict__ wblk,
@@ -619,10 +598,10 @@ __global__ __launch_bounds__(256, 2) void tpg_gcls_gram2_kernel(const uint4* __r
                 }
                 if (CEN && hb == 1) {
 #pragma unroll
-                  for (int p = 0; p < GP; p++) acc[p] = MFMA_G4S2_ODD(X[p / GB], X[GA + p % GB], acc[p]);
+                  for (int p = 0; p < GP; p++) acc[p] = tpg_mfma_f4(X[p / GB], X[GA + p % GB], acc[p], GCLS_SC_HALF, GCLS_SC_HALF);
                 } else {
 #pragma unroll
-                  for (int p = 0; p < GP; p++) acc[p] = MFMA_G4S2(X[p / GB], X[GA + p % GB], acc[p]);
+                  for (int p = 0; p < GP; p++) acc[p] = tpg_mfma_f4(X[p / GB], X[GA + p % GB], acc[p], GCLS_SC_TWO, GCLS_SC_TWO);
                 }
                 st = 0;
                 const uint32_t fl = (uint32_t)wf.x & 3u;

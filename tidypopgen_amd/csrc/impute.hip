@@ -48,12 +48,6 @@ TPG_HD int tpg_impute_draw(uint64_t locus_key, uint64_t i, uint64_t thr) {
   return (int)((h >> 32) < thr) + (int)((h & 0xFFFFFFFFull) < thr);
 }
 
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 // ---------------------------------------------------------------------------
 static constexpr int32_t IMP_ALL_MISSING = -1, IMP_REFUSED = -2;  // a locus's entry of stat[]; >= 0: entries filled
 static constexpr int IMP_PMAX = 8;  // 16-byte pieces a thread keeps in registers
@@ -147,10 +141,10 @@ __global__ __launch_bounds__(WPL >= 4 ? 64 * WPL : 256) void tpg_impute_store_ke
   } else {
     for (int64_t p = tl; p < npieces; p += TPL) imp_count(col.load(p), c1, c2, c3, bad);
   }
-  c1 = wave_sum(c1);
-  c2 = wave_sum(c2);
-  c3 = wave_sum(c3);
-  int nbad = wave_sum(bad ? 1 : 0);
+  c1 = tpg_wave_sum(c1);
+  c2 = tpg_wave_sum(c2);
+  c3 = tpg_wave_sum(c3);
+  int nbad = tpg_wave_sum(bad ? 1 : 0);
   if (WPL > 1) {
     __shared__ int red[WPL > 1 ? WPL : 1][4];
     const int wv = threadIdx.x >> 6;
@@ -199,10 +193,10 @@ __global__ __launch_bounds__(256) void tpg_impute_report_kernel(const int32_t* _
     bad += v == IMP_REFUSED;
   }
   int lo = (int)(imp & 0xFFFFF), hi = (int)(imp >> 20);  // a thread sums far less than 2^51; a wave's sums fit two ints
-  lo = wave_sum(lo);
-  hi = wave_sum(hi);
-  miss = wave_sum(miss);
-  bad = wave_sum(bad);
+  lo = tpg_wave_sum(lo);
+  hi = tpg_wave_sum(hi);
+  miss = tpg_wave_sum(miss);
+  bad = tpg_wave_sum(bad);
   if ((threadIdx.x & 63) == 0) {
     const unsigned long long tot = ((unsigned long long)hi << 20) + (unsigned long long)lo;
     if (tot) atomicAdd(d_rep, tot);
@@ -354,8 +348,8 @@ __global__ __launch_bounds__(256) void tpg_impute_view_kernel(const uint4* __res
   }
   // report: one atomic per wave
   int imp = lane < 32 && fill ? c3 : 0, allmiss = lane < 32 && j < m && t == 0 ? 1 : 0;
-  imp = wave_sum(imp);
-  allmiss = wave_sum(allmiss);
+  imp = tpg_wave_sum(imp);
+  allmiss = tpg_wave_sum(allmiss);
   if (lane == 0) {
     if (imp) atomicAdd(d_rep, (unsigned long long)imp);
     if (allmiss) atomicAdd(d_rep + 1, (unsigned long long)allmiss);

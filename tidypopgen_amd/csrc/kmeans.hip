@@ -31,11 +31,6 @@ constexpr int KM_CHUNK = TPG_KMEANS_CHUNK_DOUBLES;
 static_assert(KM_TILE == 256, "the kernels below are written for workgroups of 256 points");
 static_assert(KM_CHUNK >= TPG_KMEANS_MAX_D, "a chunk holds at least one centre");
 
-__global__ void km_finite_kernel(const double* __restrict__ X, int64_t count, int* __restrict__ flag) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < count && !isfinite(X[t])) *flag = 1;
-}
-
 // start centres: the rows idx[] of X
 __global__ void km_gather_kernel(const double* __restrict__ X, int64_t n, int d, const int32_t* __restrict__ rk,
                                  const int64_t* __restrict__ roff, const int32_t* __restrict__ idx, double* __restrict__ C) {
@@ -390,19 +385,6 @@ int km_check_k(int k, int64_t n) {
 }
 
 }  // namespace
-
-// common.h: every entry of a device array finite, else TPG_ENUMERIC naming `what`; the flag comes out of the caller's arena
-int tpg_check_finite(tpg_ctx* ctx, const double* dX, int64_t count, DevArena& sc, const char* what) {
-  int* d_flag;
-  TPG_TRY(sc.get(&d_flag, 4));
-  TPG_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
-  TPG_LAUNCH(ctx, "km_finite", km_finite_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, dX, count, d_flag);
-  TPG_CHECK_LAUNCH();
-  int flag = 0;
-  TPG_HIP(tpg_fetch_small(ctx, &flag, d_flag, sizeof(int)));
-  TPG_REQUIRE(!flag, TPG_ENUMERIC, "%s holds a value that is not finite", what);
-  return TPG_OK;
-}
 
 extern "C" int64_t tpg_kmeans_chunk_doubles(void) { return KM_CHUNK; }
 

@@ -1,8 +1,9 @@
 // knnimp.hip -- LD-kNN imputation (gt_impute_knn) on the device.  The definition is in include/tpg.h ("LD-kNN imputation");
 // DESIGN.md 3.19 has the mapping and what bounds the kernels.
 //
-//  * tpg_knn_band_kernel: the inner loop of tpg_ld_band_kernel (ld.hip) -- Sxy = sum_i x_j x_k of neighbouring loci as an FP4
-//    MFMA product of the locus-tiled layout L with itself, exact in FP32 for n < 2^22 -- with an epilogue that writes the int32
+//  * tpg_knn_band_kernel: the banded contraction of ldband.h (tpg_band_contract, shared with tpg_ld_band_kernel of ld.hip) --
+//    Sxy = sum_i x_j x_k of neighbouring loci as an FP4 MFMA product of the locus-tiled layout L with itself, exact in FP32 for
+//    n < 2^22; the operand helpers and the wave sum are devfrag.h's -- with an epilogue that writes the int32
 //    sums of the FORWARD band: band[(j - row0) * W + (k - j - 1)] for j < k <= hi[j].  The loci are walked in chunks so that the
 //    band stays under a cap (KNN_BAND_CAP); a chunk's band starts W rows before its first locus, for the backward entries.
 //  * tpg_knn_select_kernel: a wave per locus.  Its forward row is contiguous, its backward entries are strided reads of at most
@@ -19,11 +20,9 @@
 
 #include "common.h"
 #include "devfrag.h"
+#include "ldband.h"
 #include "host/host_knnimp.h"
 
-#define KNN_MAX_N (1ll << 22)
-#define KNN_TK 4                // column tiles per wave and super-chunk (ld.hip: LD_TK)
-#define KNN_SC (4 * KNN_TK)     // column tiles per workgroup and super-chunk
 #define KNN_BAND_CAP (256ull << 20)        // bytes of band per chunk of loci
 #define KNN_BAND_CAP_SMALL (8ull << 10)   // TPG_KNN_SMALL_CHUNKS: the tests' way into the chunk walk
 #define KNN_HIST_STRIDE 196                // 65 x 3 int32, rounded up to a multiple of 4
@@ -34,37 +33,6 @@
 #define KNN_PROFILE_BYTES 13               // thermometer 8 + missing mask 4 + code at the locus 1, as three arrays
 // individuals (padded to 128) whose profiles one workgroup keeps in LDS: 12 672 + 13 * 11 520 = 162 432 <= 163 840
 #define KNN_LDS_MAX_NPAD 11520
-
-typedef int knn_v8i __attribute__((ext_vector_type(8)));
-typedef float knn_v16f __attribute__((ext_vector_type(16)));
-// FP4 x FP4, both block scales 2^1 (ld.hip: LD_MFMA)
-#define KNN_MFMA(a, b, c)                                                                                          \
-  __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4((knn_v8i){(int)(a)[0], (int)(a)[1], (int)(a)[2], (int)(a)[3], 0, 0, 0, 0}, \
-                                                  (knn_v8i){(int)(b)[0], (int)(b)[1], (int)(b)[2], (int)(b)[3], 0, 0, 0, 0}, (c), 4, 4, 0, \
-                                                  (int)0x80808080, 0, (int)0x80808080)
-
-__device__ __forceinline__ void knn_operand(const uint4& f, int S, uint32_t (&o)[4]) {
-  const uint32_t p0 = S == 0 ? f.x : f.z, p1 = S == 0 ? f.y : f.w;
-  o[0] = p0 & 0x33333333u;
-  o[1] = (p0 >> 2) & 0x33333333u;
-  o[2] = p1 & 0x33333333u;
-  o[3] = (p1 >> 2) & 0x33333333u;
-}
-__device__ __forceinline__ uint32_t knn_clear3(uint32_t w) {
-  const uint32_t miss = w & (w >> 1) & 0x55555555u;
-  return w & ~(miss * 3u);
-}
-__device__ __forceinline__ void knn_clear3(uint4& f) {
-  f.x = knn_clear3(f.x);
-  f.y = knn_clear3(f.y);
-  f.z = knn_clear3(f.z);
-  f.w = knn_clear3(f.w);
-}
-__device__ __forceinline__ int knn_wave_sum(int x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 
 // counts (m x 4 {n0, n1, n2, nNA}) of the mode-filled view -> Sx and d = n Sxx - Sx^2, as tpg_ld_prep_kernel forms them.  A
 // locus typed nowhere has d = 0 and is nobody's candidate; a locus typed in part is the caller's mistake (flags bit 0).
@@ -88,66 +56,20 @@ __global__ __launch_bounds__(256) void tpg_knn_band_kernel(const uint4* __restri
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t jt = tile0 + blockIdx.x, j0 = jt * 32, row0 = tile0 * 32;
   if (tid < 32) r_hi[tid] = j0 + tid < m ? hi[j0 + tid] : -1;  // a padding row has no neighbour
-  const int64_t jlast = j0 + 31 < m ? j0 + 31 : m - 1;
-  const int NT = (int)((hi[jlast] >> 5) - jt) + 1;  // column tiles jt .. jt + NT - 1 meet the band of this row tile
-  const int nsc = (NT + KNN_SC - 1) / KNN_SC;
-  const int Qi = (int)Q;
-  const char* pa = (const char*)(L + (jt * Q) * 64);
-  auto LDG = [&](const char* p, int q) {
-    const uint32_t off = (uint32_t)lane * 16u + (uint32_t)q * 1024u;
-    return *(const uint4*)(p + off);
-  };
+  const int NT = tpg_band_tiles(hi, jt, m);
+  const int nsc = (NT + TPG_BAND_SC - 1) / TPG_BAND_SC;
   __syncthreads();
   for (int sc = 0; sc < nsc; sc++) {
-    const int t0 = sc * KNN_SC + wv;
-    const int nt = __builtin_amdgcn_readfirstlane(NT > t0 ? (NT - t0 + 3) / 4 < KNN_TK ? (NT - t0 + 3) / 4 : KNN_TK : 0);
-    knn_v16f acc[KNN_TK];
+    const int t0 = sc * TPG_BAND_SC + wv;
+    v16f acc[TPG_BAND_TK];
 #pragma unroll
-    for (int i = 0; i < KNN_TK; i++)
+    for (int i = 0; i < TPG_BAND_TK; i++)
 #pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][r] = 0.f;
-    if (nt > 0) {
-      const char* pb[KNN_TK];
-#pragma unroll
-      for (int i = 0; i < KNN_TK; i++) pb[i] = (const char*)(L + ((jt + t0 + 4 * (i < nt ? i : 0)) * Q) * 64);
-      uint4 an = LDG(pa, 0), bn[KNN_TK];
-#pragma unroll
-      for (int i = 0; i < KNN_TK; i++)
-        if (i < nt) bn[i] = LDG(pb[i], 0);
-      for (int q = 0; q < Qi; q++) {
-        uint4 a = an;
-        uint4 b[KNN_TK];
-#pragma unroll
-        for (int i = 0; i < KNN_TK; i++)
-          if (i < nt) b[i] = bn[i];
-        if (q == Qi - 1) {  // the group with the padding individuals
-          knn_clear3(a);
-#pragma unroll
-          for (int i = 0; i < KNN_TK; i++)
-            if (i < nt) knn_clear3(b[i]);
-        }
-        const int qn = q + 1 < Qi ? q + 1 : q;
-        an = LDG(pa, qn);
-#pragma unroll
-        for (int i = 0; i < KNN_TK; i++)
-          if (i < nt) bn[i] = LDG(pb[i], qn);
-#pragma unroll
-        for (int S = 0; S < 2; S++) {
-          uint32_t fa[4];
-          knn_operand(a, S, fa);
-#pragma unroll
-          for (int i = 0; i < KNN_TK; i++)
-            if (i < nt) {
-              uint32_t fb[4];
-              knn_operand(b[i], S, fb);
-              acc[i] = KNN_MFMA(fa, fb, acc[i]);
-            }
-        }
-      }
-    }
+      for (int r = 0; r < 16; r++) acc[i][r] = 0.f;  // (all four: zeroing only the tiles inside the band costs 130 more registers)
+    const int nt = tpg_band_contract<TPG_BAND_TK>(L, Q, jt, NT, sc, wv, lane, acc);
     // epilogue: the sums of the forward band, 32 consecutive k of one row per half wave
 #pragma unroll
-    for (int i = 0; i < KNN_TK; i++) {
+    for (int i = 0; i < TPG_BAND_TK; i++) {
       if (i < nt) {
         const int64_t k = (jt + t0 + 4 * i) * 32 + (lane & 31);
 #pragma unroll
@@ -391,8 +313,8 @@ __global__ __launch_bounds__(256) void tpg_knn_vote_kernel(const uint32_t* __res
       }
       if (nw != w) Ow[at] = nw;
     }
-    filled = knn_wave_sum(filled);
-    left = knn_wave_sum(left);
+    filled = tpg_wave_sum(filled);
+    left = tpg_wave_sum(left);
     if (lane == 0) {
       if (filled) atomicAdd(rep, (unsigned long long)filled);
       if (left) atomicAdd(rep + 2, (unsigned long long)left);
@@ -457,7 +379,7 @@ __global__ __launch_bounds__(256) void tpg_knn_errors_kernel(const uint4* __rest
     per_locus[2 * j] = held;
     per_locus[2 * j + 1] = wrong;
   }
-  const int th = knn_wave_sum(mine ? held : 0), tw = knn_wave_sum(mine ? wrong : 0);
+  const int th = tpg_wave_sum(mine ? held : 0), tw = tpg_wave_sum(mine ? wrong : 0);
   if (lane == 0) {
     if (th) atomicAdd(tot, (unsigned long long)th);
     if (tw) atomicAdd(tot + 1, (unsigned long long)tw);
@@ -488,7 +410,7 @@ int knn_check_args(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, int l, in
   TPG_REQUIRE(min_r2 >= 0.0 && min_r2 <= 1.7976931348623157e308, TPG_EINVAL, "min_r2 must be a finite number >= 0");  // (a NaN fails)
   TPG_REQUIRE((flags & ~(TPG_KNN_PROFILES_GLOBAL | TPG_KNN_SMALL_CHUNKS)) == 0, TPG_EINVAL, "unknown flags %d", flags);
   TPG_REQUIRE(v->m >= 1 && v->n >= 1, TPG_EINVAL, "empty view");
-  TPG_REQUIRE(v->n < KNN_MAX_N, TPG_EINVAL, "LD-kNN imputation of 2^22 individuals or more");  // FP32 sums of dosage products
+  TPG_REQUIRE(v->n < TPG_BAND_MAX_N, TPG_EINVAL, "LD-kNN imputation of 2^22 individuals or more");  // FP32 sums of dosage products
   TPG_REQUIRE(v->m < (1ll << 31) - 64, TPG_EINVAL, "LD-kNN imputation of 2^31 loci or more");
   TPG_REQUIRE(v->L || v->LM, TPG_EINVAL, "the view has no locus-tiled layout");
   return TPG_OK;

@@ -3,11 +3,9 @@
 // mapping and what bounds the kernels.
 //
 //  * tpg_ld_band_kernel: r^2 of two loci without missing genotypes follows from integer sums; the only quadratic one,
-//    Sxy = sum_i x_j x_k, is a locus x locus product over the individuals, i.e. over the Q groups of the locus-tiled
-//    layout L, with L as BOTH operands.  A 2-bit code c in the low bits of a nibble is the FP4 (E2M1) value c / 2, so with
-//    a block scale of 2 on either side v_mfma_scale_f32_32x32x64_f8f6f4 adds up the dosage products of 32 x 32 locus pairs
-//    and 64 individuals: products in {0, 1, 2, 4}, sums of at most 4 n, exact in FP32 below 2^24 for every n < 2^22.  The
-//    padding individuals of the last group carry code 3: that group's fragments have their 3s cleared before use.
+//    Sxy = sum_i x_j x_k, is the banded product of the locus-tiled layout L with itself on the FP4 matrix cores that
+//    ldband.h holds (tpg_band_contract, shared with knnimp.hip; its operand helpers are devfrag.h's): exact in FP32 for
+//    every n < 2^22.
 //    A workgroup owns the 32 loci of row tile jt and walks the column tiles jt .. (last neighbour of the tile) / 32 in
 //    super-chunks of 16; wave w of 4 holds the accumulators of tiles w, w + 4, w + 8, w + 12 of the chunk and contracts
 //    them over Q.  In the epilogue every lane forms num and the comparison for its 16 elements; a ballot turns a register
@@ -21,47 +19,15 @@
 //    wave walks what is still undecided after TPG_LD_MAX_ROUNDS in rank order.
 #include "common.h"
 #include "devfrag.h"
+#include "ldband.h"
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
 
-#define TPG_LD_MAX_N (1ll << 22)
 #define TPG_LD_MAX_ROUNDS 32
-#define LD_TK 4                 // column tiles per wave and super-chunk (4 x 16 accumulator registers)
-#define LD_SC (4 * LD_TK)       // column tiles per workgroup and super-chunk
 #define LD_UNDECIDED 0
 #define LD_KEPT 1
 #define LD_FALLEN 2
-
-typedef int ld_v8i __attribute__((ext_vector_type(8)));
-typedef float ld_v16f __attribute__((ext_vector_type(16)));
-// FP4 x FP4, both block scales 2^1: (c_j / 2 * 2) * (c_k / 2 * 2)
-#define LD_MFMA(a, b, c)                                                                                         \
-  __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4((ld_v8i){(int)(a)[0], (int)(a)[1], (int)(a)[2], (int)(a)[3], 0, 0, 0, 0}, \
-                                                  (ld_v8i){(int)(b)[0], (int)(b)[1], (int)(b)[2], (int)(b)[3], 0, 0, 0, 0}, (c), 4, 4, 0, \
-                                                  (int)0x80808080, 0, (int)0x80808080)
-
-// the four FP4 operand dwords of half-group S (64 individuals) of one L fragment: eight codes each, in the low bits of the
-// nibbles.  Which individual lands in which nibble is the same for every locus, which is all a product of L with L needs.
-__device__ __forceinline__ void ld_operand(const uint4& f, int S, uint32_t (&o)[4]) {
-  const uint32_t p0 = S == 0 ? f.x : f.z, p1 = S == 0 ? f.y : f.w;
-  o[0] = p0 & 0x33333333u;
-  o[1] = (p0 >> 2) & 0x33333333u;
-  o[2] = p1 & 0x33333333u;
-  o[3] = (p1 >> 2) & 0x33333333u;
-}
-
-// code 3 -> 0 in the 16 two-bit codes of a dword (the padding individuals of the last group)
-__device__ __forceinline__ uint32_t ld_clear3(uint32_t w) {
-  const uint32_t miss = w & (w >> 1) & 0x55555555u;
-  return w & ~(miss * 3u);
-}
-__device__ __forceinline__ void ld_clear3(uint4& f) {
-  f.x = ld_clear3(f.x);
-  f.y = ld_clear3(f.y);
-  f.z = ld_clear3(f.z);
-  f.w = ld_clear3(f.w);
-}
 
 // counts (m x 4 {n0, n1, n2, nNA}) -> Sx, d = n Sxx - Sx^2 (below 2^46: exact as a double), the default priority
 // (minor allele count) and whether anything is missing
@@ -83,7 +49,7 @@ __global__ __launch_bounds__(256) void tpg_ld_band_kernel(const uint4* __restric
                                                           uint32_t* __restrict__ bits, int64_t stride,
                                                           uint32_t* __restrict__ back, int64_t bstride,
                                                           unsigned long long* __restrict__ links) {
-  __shared__ uint32_t strip[32][LD_SC + 1];  // [row][0: last tile of the super-chunk before | 1 + tile of this one]
+  __shared__ uint32_t strip[32][TPG_BAND_SC + 1];  // [row][0: last tile of the super-chunk before | 1 + tile of this one]
   __shared__ int32_t r_sx[32];
   __shared__ double r_dd[32];
   __shared__ int64_t r_hi[32];
@@ -96,68 +62,21 @@ __global__ __launch_bounds__(256) void tpg_ld_band_kernel(const uint4* __restric
     r_hi[tid] = j < m ? hi[j] : -1;  // a padding row has no neighbour
     strip[tid][0] = 0;
   }
-  const int64_t jlast = j0 + 31 < m ? j0 + 31 : m - 1;
-  const int NT = (int)((hi[jlast] >> 5) - jt) + 1;  // column tiles jt .. jt + NT - 1 meet the band of this row tile
-  const int nsc = NT / LD_SC + 1;                   // the last word of a row needs the tile behind it: one more chunk at a multiple
-  const int Qi = (int)Q;
-  const char* pa = (const char*)(L + (jt * Q) * 64);
-  auto LDG = [&](const char* p, int q) {
-    const uint32_t off = (uint32_t)lane * 16u + (uint32_t)q * 1024u;
-    return *(const uint4*)(p + off);
-  };
+  const int NT = tpg_band_tiles(hi, jt, m);
+  const int nsc = NT / TPG_BAND_SC + 1;  // the last word of a row needs the tile behind it: one more chunk at a multiple
   __syncthreads();
   unsigned cnt = 0;
   for (int sc = 0; sc < nsc; sc++) {
-    // tiles of this wave: offsets sc * LD_SC + wv + 4 i from jt; the first `nt` of them lie inside the band
-    const int t0 = sc * LD_SC + wv;
-    const int nt = __builtin_amdgcn_readfirstlane(NT > t0 ? (NT - t0 + 3) / 4 < LD_TK ? (NT - t0 + 3) / 4 : LD_TK : 0);
-    ld_v16f acc[LD_TK];
+    const int t0 = sc * TPG_BAND_SC + wv;  // tiles of this wave: offsets t0 + 4 i from jt; the first `nt` of them lie inside the band
+    v16f acc[TPG_BAND_TK];
 #pragma unroll
-    for (int i = 0; i < LD_TK; i++)
+    for (int i = 0; i < TPG_BAND_TK; i++)
 #pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][r] = 0.f;  // (all four: zeroing only the first nt costs 130 more registers)
-    if (nt > 0) {
-      const char* pb[LD_TK];
-#pragma unroll
-      for (int i = 0; i < LD_TK; i++) pb[i] = (const char*)(L + ((jt + t0 + 4 * (i < nt ? i : 0)) * Q) * 64);
-      uint4 an = LDG(pa, 0), bn[LD_TK];
-#pragma unroll
-      for (int i = 0; i < LD_TK; i++)
-        if (i < nt) bn[i] = LDG(pb[i], 0);
-      for (int q = 0; q < Qi; q++) {
-        uint4 a = an;
-        uint4 b[LD_TK];
-#pragma unroll
-        for (int i = 0; i < LD_TK; i++)
-          if (i < nt) b[i] = bn[i];
-        if (q == Qi - 1) {  // the group with the padding individuals
-          ld_clear3(a);
-#pragma unroll
-          for (int i = 0; i < LD_TK; i++)
-            if (i < nt) ld_clear3(b[i]);
-        }
-        const int qn = q + 1 < Qi ? q + 1 : q;
-        an = LDG(pa, qn);
-#pragma unroll
-        for (int i = 0; i < LD_TK; i++)
-          if (i < nt) bn[i] = LDG(pb[i], qn);
-#pragma unroll
-        for (int S = 0; S < 2; S++) {
-          uint32_t fa[4];
-          ld_operand(a, S, fa);
-#pragma unroll
-          for (int i = 0; i < LD_TK; i++)
-            if (i < nt) {
-              uint32_t fb[4];
-              ld_operand(b[i], S, fb);
-              acc[i] = LD_MFMA(fa, fb, acc[i]);
-            }
-        }
-      }
-    }
+      for (int r = 0; r < 16; r++) acc[i][r] = 0.f;  // (all four: zeroing only the tiles inside the band costs 130 more registers)
+    const int nt = tpg_band_contract<TPG_BAND_TK>(L, Q, jt, NT, sc, wv, lane, acc);
     // epilogue: link bits of this wave's tiles -> row strips in LDS, column strips to `back`
 #pragma unroll
-    for (int i = 0; i < LD_TK; i++) {
+    for (int i = 0; i < TPG_BAND_TK; i++) {
       const int slot = 1 + wv + 4 * i;
       if (i < nt) {
         const int t = t0 + 4 * i;
@@ -187,9 +106,9 @@ __global__ __launch_bounds__(256) void tpg_ld_band_kernel(const uint4* __restric
     }
     __syncthreads();
     // word w of row j holds the loci j + 1 + 32 w .. j + 32 + 32 w: tiles w and w + 1 from jt, shifted by row + 1
-    for (int idx = tid; idx < 32 * LD_SC; idx += 256) {
-      const int row = idx / LD_SC, wl = idx % LD_SC;
-      const int64_t w = (int64_t)sc * LD_SC - 1 + wl;
+    for (int idx = tid; idx < 32 * TPG_BAND_SC; idx += 256) {
+      const int row = idx / TPG_BAND_SC, wl = idx % TPG_BAND_SC;
+      const int64_t w = (int64_t)sc * TPG_BAND_SC - 1 + wl;
       const unsigned long long both = ((unsigned long long)strip[row][wl + 1] << 32) | strip[row][wl];
       const uint32_t word = (uint32_t)(both >> (row + 1));
       if (w >= 0 && w < stride && j0 + row < m) {
@@ -198,12 +117,11 @@ __global__ __launch_bounds__(256) void tpg_ld_band_kernel(const uint4* __restric
       }
     }
     uint32_t carry = 0;
-    if (tid < 32) carry = strip[tid][LD_SC];
+    if (tid < 32) carry = strip[tid][TPG_BAND_SC];
     __syncthreads();
     if (tid < 32) strip[tid][0] = carry;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor((int)cnt, o);
+  cnt = (unsigned)tpg_wave_sum((int)cnt);
   if (lane == 0 && cnt) atomicAdd(links, (unsigned long long)cnt);
 }
 
@@ -227,9 +145,8 @@ __global__ __launch_bounds__(256) void tpg_ld_key_kernel(const int32_t* __restri
     key[j] = 0;
     return;
   }
-  unsigned long long u = v == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(v);
-  u = (u >> 63) ? ~u : u | 0x8000000000000000ull;
-  key[j] = ~u;
+  const uint64_t u = v == 0.0 ? 0ull : (uint64_t)__double_as_longlong(v);
+  key[j] = ~TPG_DKEY(u);
 }
 
 __global__ __launch_bounds__(256) void tpg_ld_rank_kernel(const uint32_t* __restrict__ order, int64_t m,
@@ -377,7 +294,7 @@ int ld_check_args(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, double thr
   TPG_REQUIRE(ctx && v && hi, TPG_EINVAL, "null argument");
   TPG_REQUIRE(thr_r2 >= 0.0 && thr_r2 <= 1.0, TPG_EINVAL, "thr_r2 must lie in [0, 1]");  // (a NaN fails both)
   TPG_REQUIRE(v->m >= 1 && v->n >= 1, TPG_EINVAL, "empty view");
-  TPG_REQUIRE(v->n < TPG_LD_MAX_N, TPG_EUNSUPPORTED, "LD of 2^22 individuals or more");  // FP32 sums of dosage products
+  TPG_REQUIRE(v->n < TPG_BAND_MAX_N, TPG_EUNSUPPORTED, "LD of 2^22 individuals or more");  // FP32 sums of dosage products
   TPG_REQUIRE(v->m < (1ll << 31) - 64, TPG_EUNSUPPORTED, "LD of 2^31 loci or more");
   return TPG_OK;
 }

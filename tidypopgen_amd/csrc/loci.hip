@@ -266,7 +266,7 @@ __global__ void tpg_pi_kernel(const int4* __restrict__ counts, int64_t m, double
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
     const int4 c = counts[j];
     const double cnt = (double)(c.y + 2 * c.z), valid = (double)(2 * (c.x + c.y + c.z));
-    pi[j] = valid > 0 ? (cnt * (valid - cnt) / (valid * (valid - 1) / 2)) : __longlong_as_double(0x7FF8000000000000ll);
+    pi[j] = valid > 0 ? (cnt * (valid - cnt) / (valid * (valid - 1) / 2)) : TPG_QNAN;
   }
 }
 
@@ -329,22 +329,6 @@ __global__ void tpg_onehot_kernel(const int32_t* __restrict__ cls, int64_t n, in
 // operand dwords for four instructions; het = sum Y - sum W, hom-alt = sum Z - sum W, valid = class size - sum W.
 #define GC_NLT 1
 #define GC_D 4
-template <int C, class F>
-__device__ __forceinline__ void gc_static_for(F&& f) {
-  if constexpr (C > 0) {
-    gc_static_for<C - 1>(f);
-    f(std::integral_constant<int, C - 1>{});
-  }
-}
-typedef int gc_v8i __attribute__((ext_vector_type(8)));
-typedef float gc_v16f __attribute__((ext_vector_type(16)));
-#define GC_MFMA(a, b, c, sa) \
-  __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4((gc_v8i){(int)(a)[0], (int)(a)[1], (int)(a)[2], (int)(a)[3], 0, 0, 0, 0}, \
-                                                  (gc_v8i){(int)(b).x, (int)(b).y, (int)(b).z, (int)(b).w, 0, 0, 0, 0}, (c), 4, 4, 0, (sa), 0, 0x7F7F7F7F)
-__device__ __forceinline__ int64_t tpg_gc_uniform64(int64_t x) {  // a wave-uniform value the compiler keeps in SGPRs
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 template <int GT>
 __global__ __launch_bounds__(256, 3) void tpg_grouped_counts_kernel(const uint4* __restrict__ L,
@@ -356,7 +340,7 @@ __global__ __launch_bounds__(256, 3) void tpg_grouped_counts_kernel(const uint4*
   __shared__ __attribute__((aligned(16))) uint4 ohb[2][2 * GT][64];  // [buffer][step * GT + class tile][lane]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t lt0 = ((int64_t)blockIdx.x * 4 + wv) * GC_NLT;  // may lie past n_lt: the wave still serves the LDS
-  gc_v16f acc[3][GC_NLT][GT];
+  v16f acc[3][GC_NLT][GT];
 #pragma unroll
   for (int p = 0; p < 3; p++)
 #pragma unroll
@@ -367,7 +351,7 @@ __global__ __launch_bounds__(256, 3) void tpg_grouped_counts_kernel(const uint4*
         for (int r = 0; r < 16; r++) acc[p][t][g][r] = 0.f;
   // (wave-uniform bases in SGPRs + a 32-bit lane offset per group: 32-bit group indices, no 64-bit per-lane pointers)
   const int Qi = (int)Q;
-  const int64_t lt0u = tpg_gc_uniform64(lt0);
+  const int64_t lt0u = tpg_uniform64(lt0);
   const char* pa[GC_NLT];
 #pragma unroll
   for (int t = 0; t < GC_NLT; t++) pa[t] = (const char*)(L + ((lt0u + t < n_lt ? lt0u + t : 0) * Q) * 64);  // past the end: a copy
@@ -433,9 +417,9 @@ __global__ __launch_bounds__(256, 3) void tpg_grouped_counts_kernel(const uint4*
         const uint4 b = ohb[cur][S * GT + g][lane];
 #pragma unroll
         for (int t = 0; t < GC_NLT; t++) {
-          acc[0][t][g] = GC_MFMA(fy[t], b, acc[0][t][g], (int)0x80808080);
-          acc[1][t][g] = GC_MFMA(fz[t], b, acc[1][t][g], 0x7F7F7F7F);
-          acc[2][t][g] = GC_MFMA(fw[t], b, acc[2][t][g], (int)0x80808080);
+          acc[0][t][g] = tpg_mfma_f4(fy[t], b, acc[0][t][g], (int)0x80808080, 0x7F7F7F7F);
+          acc[1][t][g] = tpg_mfma_f4(fz[t], b, acc[1][t][g], 0x7F7F7F7F, 0x7F7F7F7F);
+          acc[2][t][g] = tpg_mfma_f4(fw[t], b, acc[2][t][g], (int)0x80808080, 0x7F7F7F7F);
         }
       }
     }
@@ -448,7 +432,7 @@ __global__ __launch_bounds__(256, 3) void tpg_grouped_counts_kernel(const uint4*
     tpg_lds_barrier();
   };
   for (int q = 0; q < Qi; q += GC_D)  // Q is the same for every wave: all of them meet every barrier
-    gc_static_for<GC_D>([&](auto kk) {
+    tpg_static_for<GC_D>([&](auto kk) {
       constexpr int k = decltype(kk)::value;
       if (q + k < Qi) group(std::integral_constant<int, k>{}, std::integral_constant<int, (k + GC_D - 1) % GC_D>{}, q + k);
     });
@@ -723,7 +707,6 @@ extern "C" int tpg_grouped_genotype_counts(tpg_ctx* ctx, const tpg_view* v, cons
 // R/pop_global_stats.R:129-197 (hierfstat::basic.stats arithmetic), one thread per locus; out = m x 10,
 // column-major, columns Ho Hs Ht Dst Htp Dstp Fst Fstp Fis Dest.  np / mn as src/compute_np_mn.cpp:8-34 (n is
 // never NA there: a group with no typed individual has n = 0, counts in np and makes mn = 0).
-#define TPG_GS_NAN __longlong_as_double(0x7FF8000000000000ll)
 __global__ void tpg_global_stats_kernel(const int32_t* __restrict__ cnt, int64_t Mpad, int Cpad, int64_t m, int G,
                                         double* __restrict__ out) {
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
@@ -741,7 +724,7 @@ __global__ void tpg_global_stats_kernel(const int32_t* __restrict__ cnt, int64_t
       sfa += fa;                                      // rowMeans(freq) without na.rm: NaN propagates
       sfr += fr;
     }
-    const double mn = denom > 0.0 ? np / denom : TPG_GS_NAN;
+    const double mn = denom > 0.0 ? np / denom : TPG_QNAN;
     const double mHo = sho / nho, msp2 = ssp2 / nsp2;  // 0 / 0 = NaN, as mean(numeric(0))
     const double mfa = sfa / G, mfr = sfr / G;
     const double mp2 = mfa * mfa + mfr * mfr;
@@ -855,7 +838,7 @@ __global__ __launch_bounds__(64) void tpg_window_stats_kernel(const double* __re
     }
   for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); k += __shfl_xor(k, o); }
   if (lane == 0) {
-    double r = TPG_GS_NAN;
+    double r = TPG_QNAN;
     if (!pad && k > 0 && k >= min_loci) r = op == 0 ? s / k : s;
     stat[w + (int64_t)c * nw] = r;
     if (n_loci) n_loci[w + (int64_t)c * nw] = pad ? -1 : k;  // -1 = NA (incomplete window with complete = TRUE)
@@ -945,7 +928,7 @@ __global__ void tpg_alt_freq_finalize_kernel(const int4* __restrict__ counts, in
     const int4 c = counts[j];
     const double alt = (double)(c.y + 2 * c.z), valid = (double)(2 * (c.x + c.y + c.z));
     double f = alt;
-    if (!as_counts) f = valid > 0 ? alt / valid : __longlong_as_double(0x7FF8000000000000ll);
+    if (!as_counts) f = valid > 0 ? alt / valid : TPG_QNAN;
     out[j] = f;
     out[m + j] = valid;
   }

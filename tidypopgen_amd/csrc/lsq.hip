@@ -161,13 +161,6 @@ __global__ void lsq_reduce_kernel(const double* __restrict__ part, int S, int64_
 }
 
 template <int G>
-struct LsqLanes {
-  __device__ int lane() const { return (int)(threadIdx.x % G); }
-  __device__ int size() const { return G; }
-  __device__ void sync() const { __syncthreads(); }
-};
-
-template <int G>
 __global__ __launch_bounds__(LSQ_WAVE) void lsq_solve_kernel(const double* __restrict__ A, const double* __restrict__ b,
                                                              const int64_t* __restrict__ n_typed, int64_t n, int L, double* __restrict__ out,
                                                              unsigned long long* __restrict__ n_singular) {
@@ -177,7 +170,7 @@ __global__ __launch_bounds__(LSQ_WAVE) void lsq_solve_kernel(const double* __res
   const int64_t i = (int64_t)blockIdx.x * TEAMS + team;
   double* ws = lsq_solve_lds + (size_t)team * host_lsq_ws_doubles(L);
   const bool live = i < n;  // (a team beyond the batch works on a row of zeros and stores nothing: it keeps the barriers whole)
-  const LsqLanes<G> tm;
+  const TpgTeam<G> tm;
   const int singular = host_lsq_solve_row(tm, L, live ? A + i : nullptr, n, live ? b + i : nullptr, n, live ? n_typed[i] : 0, ws,
                                           live ? out + i : nullptr, n);
   if (live && singular && tm.lane() == 0) atomicAdd(n_singular, 1ull);

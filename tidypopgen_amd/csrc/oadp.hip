@@ -11,19 +11,12 @@
 // barrier's OR: the teams of a wave sweep until the last of them has converged, and a sweep over converged columns rotates
 // nothing.  No floating-point atomics; the degenerate rows are counted with one integer atomic per such row.
 #include "common.h"
+#include "devfrag.h"
 #include "host/host_oadp.h"
 
 namespace {
 
 constexpr int OADP_WAVE = 64;
-
-template <int G>
-struct OadpLanes {
-  __device__ int lane() const { return (int)(threadIdx.x % G); }
-  __device__ int size() const { return G; }
-  __device__ void sync() const { __syncthreads(); }
-  __device__ bool any(bool b) const { return __syncthreads_or(b ? 1 : 0) != 0; }
-};
 
 // LDS: 32 doubles of singular values, then 64 / G workspaces
 template <int G>
@@ -39,7 +32,7 @@ __global__ __launch_bounds__(OADP_WAVE) void oadp_kernel(const double* __restric
   if ((int)threadIdx.x < K) d[threadIdx.x] = sval[threadIdx.x];
   __syncthreads();
   const bool live = i < n;  // (a team beyond the batch works on a row of zeros and stores nothing: it keeps the barriers whole)
-  const OadpLanes<G> t;
+  const TpgTeam<G> t;
   const int degenerate = host_oadp_project(t, K, live ? XV + i : nullptr, n, live ? X_norm[i] : 0.0, d, ws, live ? out + i : nullptr, n);
   if (live && degenerate && t.lane() == 0) atomicAdd(n_degenerate, 1ull);
 }

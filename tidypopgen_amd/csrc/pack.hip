@@ -128,10 +128,6 @@ __global__ __launch_bounds__(256) void tpg_pack_kernel(const uint8_t* __restrict
 #ifndef PACK_NSUB
 #define PACK_NSUB 2  // individual chunks per workgroup, all their loads issued up front
 #endif
-__device__ __forceinline__ int64_t tpg_pack_uniform64(int64_t x) {  // a wave-uniform value the compiler keeps in SGPRs
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 typedef uint32_t pk_u4 __attribute__((ext_vector_type(4)));
 typedef pk_u4 pk_u4a8 __attribute__((aligned(8)));
 // BED (round 5): the store is a PLINK .bed payload (tpg_fbm::bed_bpl bytes per SNP, 4 genotypes per byte, `nrow` = bed_bpl).
@@ -334,7 +330,7 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
         }
         if (need_[vw]) *reinterpret_cast<uint4*>(codes + cb[it & 1] + it * 32 * TILE) = make_uint4(c[0], c[1], c[2], c[3]);
         const bool lm = LM1 && vw == 1;
-        gchar* Lb = (gchar*)tpg_pack_uniform64((int64_t)(
+        gchar* Lb = (gchar*)tpg_uniform64((int64_t)(
             lm ? L1 + tpg_lm_piece(bj * TILE + 32 * it, Q, bi, 0) * 4 : (vw ? L1 : L0) + ((bj * 4 + it) * Q + bi) * 256));  // L block (lt = 4 bj + it, bi)
         const uint32_t lw = c[0] | (c[1] << 2) | (c[2] << 4) | (c[3] << 6);
         if (lm && sub == 0 && bi + 1 < Q) {
@@ -345,7 +341,7 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
           typedef __attribute__((address_space(1))) pk_u2 gu2;
           const bool odd = (c16 >> 1) & 1;
           const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(odd ? lmw[it] : lw), 0x4E /* quad_perm [2, 3, 0, 1] */, 0xF, 0xF, true);
-          gchar* Lp = (gchar*)tpg_pack_uniform64((int64_t)(L1 + tpg_lm_piece(bj * TILE + 32 * it, Q, bi0, 0) * 4));
+          gchar* Lp = (gchar*)tpg_uniform64((int64_t)(L1 + tpg_lm_piece(bj * TILE + 32 * it, Q, bi0, 0) * 4));
           *(gu2*)(Lp + loff_lm2) = odd ? pk_u2{got, lw} : pk_u2{lmw[it], got};
         } else {
           *(gu32*)(Lb + (lm ? loff_lm : loff)) = lw;  // (locus-major: the last chunk of an odd Q)
@@ -436,7 +432,7 @@ __global__ __launch_bounds__(256) void tpg_pack_fast_kernel(const uint8_t* __res
         }
       }
       const int sT = g >> 1;
-      gchar2* B4 = (gchar2*)tpg_pack_uniform64((int64_t)(T4v + ((rt * KG + bj) * 2) * 256));  // the two T4 blocks of (rt, kg)
+      gchar2* B4 = (gchar2*)tpg_uniform64((int64_t)(T4v + ((rt * KG + bj) * 2) * 256));  // the two T4 blocks of (rt, kg)
       const uint32_t o4 = (uint32_t)(sT >> 1) * 1024u + (uint32_t)(4 * iqq + 32 * (g & 1)) * 16u + (uint32_t)(sT & 1) * 8u;
 #pragma unroll
       for (int b = 0; b < 4; b++) {

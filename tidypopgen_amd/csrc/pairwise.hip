@@ -56,10 +56,6 @@
 #include <type_traits>
 #include "devfrag.h"
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
 #define TPG_NIB_M (TPG_T4_MM * 0x11111111u)
 #define TPG_NIB_H (TPG_T4_MH * 0x11111111u)
 #define TPG_NIB_D ((TPG_T4_MD | 8u) * 0x11111111u)
@@ -68,11 +64,6 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 #define TPG_SC_ONE TPG_T4_SC(TPG_T4_MM)
 #define TPG_SC_TWO TPG_T4_SC(TPG_T4_MH)
 #define TPG_SC_HALF TPG_T4_SC(TPG_T4_MD)
-
-__device__ __forceinline__ v8i tpg_w8(v4i a) { return v8i{a[0], a[1], a[2], a[3], 0, 0, 0, 0}; }
-// FP4 x FP4 (format code 4), 32 x 32 x 64
-#define MFMA_F4(a, b, c, sa, sb) \
-  __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(tpg_w8(a), tpg_w8(b), (c), 4, 4, 0, (sa), 0, (sb))
 
 // T (2-bit codes) -> T4.  Every lane re-codes its own 16 bytes of a T block (4 dwords x 16 loci) as two 16-byte
 // fragments of 32 nibbles: dwords 0, 1 -> block 2 kg, dwords 2, 3 -> block 2 kg + 1.  Which locus lands on which
@@ -240,15 +231,15 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_kernel(const uint4* __res
           }
           P[nx][TA] = tpg_planes(s == 0 ? RB[C][1] : RB[N][0], TPG_NIB_M, TPG_NIB_D, TPG_NIB_H);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cMM[t] = MFMA_F4(P[cur][t].m, P[cur][TA].m, cMM[t], sc1, sc1);
+          for (int t = 0; t < TA; t++) cMM[t] = tpg_mfma_f4(P[cur][t].m, P[cur][TA].m, cMM[t], sc1, sc1);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cD[t] = MFMA_F4(P[cur][t].d, P[cur][TA].d, cD[t], sch, sch);
+          for (int t = 0; t < TA; t++) cD[t] = tpg_mfma_f4(P[cur][t].d, P[cur][TA].d, cD[t], sch, sch);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cH[t] = MFMA_F4(P[cur][t].h, P[cur][TA].h, cH[t], sc2, sc2);
+          for (int t = 0; t < TA; t++) cH[t] = tpg_mfma_f4(P[cur][t].h, P[cur][TA].h, cH[t], sc2, sc2);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cHM[t] = MFMA_F4(P[cur][t].h, P[cur][TA].m, cHM[t], sc2, sc1);
+          for (int t = 0; t < TA; t++) cHM[t] = tpg_mfma_f4(P[cur][t].h, P[cur][TA].m, cHM[t], sc2, sc1);
 #pragma unroll
-          for (int t = 0; t < TA; t++) cMH[t] = MFMA_F4(P[cur][t].m, P[cur][TA].h, cMH[t], sc1, sc2);
+          for (int t = 0; t < TA; t++) cMH[t] = tpg_mfma_f4(P[cur][t].m, P[cur][TA].h, cMH[t], sc1, sc2);
           // 12 (TA + 1) plane masks and TA + 1 loads spread over the 5 TA MFMAs of the step
 #pragma unroll
           for (int q = 0; q < 5 * TA; q++) {
@@ -425,18 +416,18 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
         for (int a = 0; a < RA; a++)
 #pragma unroll
           for (int b = 0; b < RB; b++) {
-            if constexpr (PS::pV) cMM[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].m, cMM[a][b], sc1, sc1);
-            if constexpr (PS::pD || PS::pS) cD[a][b] = MFMA_F4(P[cur][a].d, P[cur][RA + b].d, cD[a][b], sch, sch);
-            if constexpr (PS::pH) cH[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].h, cH[a][b], sc2, sc2);
-            if constexpr (PS::pA) cHM[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].m, cHM[a][b], sc2, sc1);
-            if constexpr (PS::pA) cMH[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].h, cMH[a][b], sc1, sc2);
+            if constexpr (PS::pV) cMM[a][b] = tpg_mfma_f4(P[cur][a].m, P[cur][RA + b].m, cMM[a][b], sc1, sc1);
+            if constexpr (PS::pD || PS::pS) cD[a][b] = tpg_mfma_f4(P[cur][a].d, P[cur][RA + b].d, cD[a][b], sch, sch);
+            if constexpr (PS::pH) cH[a][b] = tpg_mfma_f4(P[cur][a].h, P[cur][RA + b].h, cH[a][b], sc2, sc2);
+            if constexpr (PS::pA) cHM[a][b] = tpg_mfma_f4(P[cur][a].h, P[cur][RA + b].m, cHM[a][b], sc2, sc1);
+            if constexpr (PS::pA) cMH[a][b] = tpg_mfma_f4(P[cur][a].m, P[cur][RA + b].h, cMH[a][b], sc1, sc2);
           }
         // (the second MFMA into the D + H sums: a pass of its own, 2 RA RB MFMAs behind the first into the same registers)
         if constexpr (PS::pS) {
 #pragma unroll
           for (int a = 0; a < RA; a++)
 #pragma unroll
-            for (int b = 0; b < RB; b++) cD[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].h, cD[a][b], sc2, sc2);
+            for (int b = 0; b < RB; b++) cD[a][b] = tpg_mfma_f4(P[cur][a].h, P[cur][RA + b].h, cD[a][b], sc2, sc2);
         }
         // NV plane masks (+ address arithmetic) and NT loads spread over the NM MFMAs of the step
 #pragma unroll
@@ -484,14 +475,6 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
 // the ring, so that hipcc's wait-count pass can tell the LDS-DMA into one stage from the reads of another (alias scopes per
 // LDS variable): a single array would make every ds_read wait for every DMA in flight, vmcnt(0), i.e. no prefetch at all.
 // Same T4 operands, same slabs, same atomics as the other kernels.
-template <typename F, int... Is>
-__device__ __forceinline__ void tpg_static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void tpg_static_for(F&& f) {
-  tpg_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 // s_waitcnt immediate of gfx9: vmcnt in bits [3:0] and [15:14], expcnt [6:4] and lgkmcnt [11:8] left at "do not wait"
 constexpr int tpg_waitcnt_vm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | (((n >> 4) & 3) << 14); }
 #define SGB_DS_READ 0x100
@@ -614,11 +597,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
         for (int a = 0; a < RA; a++)
 #pragma unroll
           for (int b = 0; b < RB; b++) {
-            if constexpr (PS::pV) cMM[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].m, cMM[a][b], sc1, sc1);
-            if constexpr (PS::pD) cD[a][b] = MFMA_F4(P[cur][a].d, P[cur][RA + b].d, cD[a][b], sch, sch);
-            if constexpr (PS::pH) cH[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].h, cH[a][b], sc2, sc2);
-            if constexpr (PS::pA) cHM[a][b] = MFMA_F4(P[cur][a].h, P[cur][RA + b].m, cHM[a][b], sc2, sc1);
-            if constexpr (PS::pA) cMH[a][b] = MFMA_F4(P[cur][a].m, P[cur][RA + b].h, cMH[a][b], sc1, sc2);
+            if constexpr (PS::pV) cMM[a][b] = tpg_mfma_f4(P[cur][a].m, P[cur][RA + b].m, cMM[a][b], sc1, sc1);
+            if constexpr (PS::pD) cD[a][b] = tpg_mfma_f4(P[cur][a].d, P[cur][RA + b].d, cD[a][b], sch, sch);
+            if constexpr (PS::pH) cH[a][b] = tpg_mfma_f4(P[cur][a].h, P[cur][RA + b].h, cH[a][b], sc2, sc2);
+            if constexpr (PS::pA) cHM[a][b] = tpg_mfma_f4(P[cur][a].h, P[cur][RA + b].m, cHM[a][b], sc2, sc1);
+            if constexpr (PS::pA) cMH[a][b] = tpg_mfma_f4(P[cur][a].m, P[cur][RA + b].h, cMH[a][b], sc1, sc2);
           }
         // the DMAs and the ring reads spread over the first MFMAs, the plane masks between all of them
         __builtin_amdgcn_sched_group_barrier(SGB_VMEM_READ, NLD, 0);
@@ -986,27 +969,41 @@ static int pw_ksplit(int64_t nun, int64_t steps, int64_t min_steps_per_unit, int
   return bestS;
 }
 
+// One launch of `kernel` per chunk of the K groups [kg0, kg1), on one workgroup per CU (a multiple of the 8 XCDs).  FP32
+// accumulators: a unit contracts at most 2^24 loci (131072 groups) per split, so that every count it holds is an exactly
+// represented integer; longer ranges go out in several launches of at most 8 x 2^24 loci.  The `nun` units of `d_order` are
+// shared by `per_wg` takers per workgroup (its 4 waves, or the workgroup as one); the kernel walks K in `ksteps` steps per
+// 128-locus group and a unit keeps at least 8 groups (1024 loci); t_step / t_flush: pw_ksplit's cost model, in us.  what: the head of the TPG_DEBUG line.
+template <class Kernel>
+static int pw_launch_chunks(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1, const char* name,
+                            const char* what, Kernel kernel, const int2* d_order, int64_t nun, int per_wg, int ksteps, double t_step,
+                            double t_flush) {
+  const int64_t max_groups = 131072;
+  int nblk = ctx->num_cu / 8 * 8;
+  if (nblk < 8) nblk = 8;
+  for (int64_t c0 = kg0; c0 < kg1; c0 += 8 * max_groups) {
+    const int64_t c1 = std::min(kg1, c0 + 8 * max_groups);
+    const int64_t kgs = c1 - c0;
+    const int S = pw_ksplit(nun, ksteps * kgs, 8 * ksteps, ceil_div(kgs, max_groups), (int64_t)per_wg * nblk, t_step, t_flush);
+    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] %s%lld units, S = %d\n", what, (long long)nun, S);
+    TPG_LAUNCH(ctx, name, kernel, dim3((unsigned)nblk), dim3(256), 0, (const uint4*)v->T4, v->KG, ksteps * c0, ksteps * c1,
+               (int)pw->nst, (int)ceil_div(pw->n, 32), d_order, nun, S, (const int64_t*)pw->rowpad, pw->acc);
+  }
+  return TPG_OK;
+}
+
+// the wave form: units are (32 RA) x (32 RB) blocks of pairs, one per wave
 template <int RA, int RB, int MASK, int NS>
 static int pw_launch_set(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1, const char* name) {
   const int2* d_order = nullptr;
   int64_t nun = 0;
   TPG_TRY(pw_order_for(ctx, pw, RA, RB, &d_order, &nun));
   constexpr int NM = RA * RB * PwSet<MASK>::NP;
-  const int64_t max_groups = 131072;  // 2^24 loci per wave-unit: FP32 sums of integers stay exact
-  int nblk = ctx->num_cu / 8 * 8;
-  if (nblk < 8) nblk = 8;
-  const int64_t nwaves = 4 * (int64_t)nblk;
-  for (int64_t c0 = kg0; c0 < kg1; c0 += 8 * max_groups) {
-    const int64_t c1 = std::min(kg1, c0 + 8 * max_groups);
-    const int64_t kgs = c1 - c0;
-    // per 64-locus block: NM MFMAs at ~18 ns; flush: 16 atomic wave-instructions per accumulator tile (12 us for 15)
-    int S = pw_ksplit(nun, 2 * kgs, 16, ceil_div(kgs, max_groups), nwaves, 0.0183 * NM, 0.8 * NM);
-    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] %s: %d x %d tiles, %lld units, S = %d\n", name, RA, RB, (long long)nun, S);
-    TPG_LAUNCH(ctx, name, (tpg_pairwise_set_kernel<RA, RB, MASK, NS>), dim3((unsigned)nblk), dim3(256), 0,
-               (const uint4*)v->T4, v->KG, 2 * c0, 2 * c1, (int)pw->nst, (int)ceil_div(pw->n, 32), d_order, nun, S,
-               (const int64_t*)pw->rowpad, pw->acc);
-  }
-  return TPG_OK;
+  char what[80];
+  snprintf(what, sizeof what, "%s: %d x %d tiles, ", name, RA, RB);
+  // per 64-locus block: NM MFMAs at ~18 ns; flush: 16 atomic wave-instructions per accumulator tile (12 us for 15)
+  return pw_launch_chunks(ctx, pw, v, kg0, kg1, name, what, tpg_pairwise_set_kernel<RA, RB, MASK, NS>, d_order, nun, 4, 2,
+                          0.0183 * NM, 0.8 * NM);
 }
 
 // the workgroup form: units are (64 RA) x (64 RB) blocks of pairs, one per workgroup
@@ -1016,19 +1013,10 @@ static int pw_launch_wg(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64
   int64_t nun = 0;
   TPG_TRY(pw_order_for(ctx, pw, 2 * RA, 2 * RB, &d_order, &nun));
   constexpr int NM = RA * RB * PwSet<MASK>::NP;
-  const int64_t max_groups = 131072;  // 2^24 loci per unit: FP32 sums of integers stay exact
-  int nblk = ctx->num_cu / 8 * 8;
-  if (nblk < 8) nblk = 8;
-  for (int64_t c0 = kg0; c0 < kg1; c0 += 8 * max_groups) {
-    const int64_t c1 = std::min(kg1, c0 + 8 * max_groups);
-    const int64_t kgs = c1 - c0;
-    int S = pw_ksplit(nun, 2 * kgs, 16, ceil_div(kgs, max_groups), nblk, 0.0183 * NM, 0.8 * NM);
-    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] %s: workgroups of %d x %d tiles, %lld units, S = %d\n", name, 2 * RA, 2 * RB, (long long)nun, S);
-    TPG_LAUNCH(ctx, name, (tpg_pairwise_wg_kernel<RA, RB, MASK, NST>), dim3((unsigned)nblk), dim3(256), 0,
-               (const uint4*)v->T4, v->KG, 2 * c0, 2 * c1, (int)pw->nst, (int)ceil_div(pw->n, 32), d_order, nun, S,
-               (const int64_t*)pw->rowpad, pw->acc);
-  }
-  return TPG_OK;
+  char what[80];
+  snprintf(what, sizeof what, "%s: workgroups of %d x %d tiles, ", name, 2 * RA, 2 * RB);
+  return pw_launch_chunks(ctx, pw, v, kg0, kg1, name, what, tpg_pairwise_wg_kernel<RA, RB, MASK, NST>, d_order, nun, 1, 2,
+                          0.0183 * NM, 0.8 * NM);
 }
 
 // wave tile and slot count per product set; TPG_PW_VARIANT=<k> picks another instantiation (A/B runs, tools/pw_only.py)
@@ -1037,32 +1025,12 @@ static int pw_variant() {
 }
 
 static int pw_launch_all(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1) {
-  // K split S: units x S wave-units over the resident waves (one workgroup per CU, one wave per SIMD; a multiple of
-  // the 8 XCDs), at least 8 K groups (1024 loci) per unit.  Cost model: rounds(S) = ceil(units S / waves) rounds, a
-  // round costs its K range (about 0.55 us per 128-locus group: 30 MFMAs at ~34 cycles) plus the flush of the
+  // K split S: units x S wave-units over the resident waves (one wave per SIMD).  Cost model: rounds(S) = ceil(units S / waves)
+  // rounds, a round costs its K range (about 0.55 us per 128-locus group: 30 MFMAs at ~34 cycles) plus the flush of the
   // accumulators (240 atomic wave-instructions per wave, all waves at once: ~12 us; S = 5 ... 30 measured within 4 %
   // of each other at 5 000 x 1 000 000, best at 10 - 12).
-  // FP32 accumulators: a wave-unit contracts at most 2^24 loci (131072 groups), so that every count it holds is an
-  // exactly represented integer; longer ranges go out in several launches of at most 8 x 2^24 loci.
-  const int64_t max_groups = 131072;
-  int nblk = ctx->num_cu / 8 * 8;
-  if (nblk < 8) nblk = 8;
-  const int64_t nwaves = 4 * (int64_t)nblk;
-  for (int64_t c0 = kg0; c0 < kg1; c0 += 8 * max_groups) {
-    const int64_t c1 = std::min(kg1, c0 + 8 * max_groups);
-    const int64_t kgs = c1 - c0;
-    int bestS = pw_ksplit(pw->nun, kgs, 8, ceil_div(kgs, max_groups), nwaves, 0.55, 12.0);
-    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] pairwise: %lld units, S = %d\n", (long long)pw->nun, bestS);
-    if (pw_variant() == 2)  // A/B: three groups of prefetch
-      TPG_LAUNCH(ctx, "pairwise_mfma", tpg_pairwise_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, (const uint4*)v->T4, v->KG,
-                 c0, c1, (int)pw->nst, (int)ceil_div(pw->n, 32), (const int2*)pw->order, pw->nun, bestS,
-                 (const int64_t*)pw->rowpad, pw->acc);
-    else
-      TPG_LAUNCH(ctx, "pairwise_mfma", tpg_pairwise_kernel<3>, dim3((unsigned)nblk), dim3(256), 0, (const uint4*)v->T4, v->KG,
-                 c0, c1, (int)pw->nst, (int)ceil_div(pw->n, 32), (const int2*)pw->order, pw->nun, bestS,
-                 (const int64_t*)pw->rowpad, pw->acc);
-  }
-  return TPG_OK;
+  const auto kernel = pw_variant() == 2 ? tpg_pairwise_kernel<4> : tpg_pairwise_kernel<3>;  // (2: A/B, three groups of prefetch)
+  return pw_launch_chunks(ctx, pw, v, kg0, kg1, "pairwise_mfma", "pairwise: ", kernel, (const int2*)pw->order, pw->nun, 4, 1, 0.55, 12.0);
 }
 
 extern "C" int tpg_pairwise_accumulate_products(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t col_begin,
@@ -1173,7 +1141,6 @@ struct PwCounts {
   int V, D, H, Aij, Aji;  // relative to the OUTPUT element (row i, column j): Aij = loci where i is het and j typed
 };
 
-#define TPG_NAN __longlong_as_double(0x7FF8000000000000ll)
 
 // mode: 0 raw counts (six optional outputs), 1 IBS proportion / adjusted counts (scale), 2 KING,
 // 3 allele sharing, 4 IBS + KING + allele sharing together.  Sums of products are formed in 64 bits (a single
@@ -1200,7 +1167,7 @@ __device__ __forceinline__ void tpg_pw_emit(const PwCounts c, int mode, double s
     o0[idx] = K / (2 * mn) + 0.5 - 0.25 * (Ni + Nj) / mn;  // R/snp_king.R:86-89
   } else if (mode == 3) {
     const double num = (double)(D + quirk), den = (double)V;
-    o0[idx] = V == 0 ? TPG_NAN : 0.5 * (1 + num / den);  // R/snp_allele_sharing.R:79-80
+    o0[idx] = V == 0 ? TPG_QNAN : 0.5 * (1 + num / den);  // R/snp_allele_sharing.R:79-80
   } else {
     // mode 4: IBS (o0, scale), KING (o1) and allele sharing (o2) from one fetch
     if (o0) {
@@ -1212,7 +1179,7 @@ __device__ __forceinline__ void tpg_pw_emit(const PwCounts c, int mode, double s
       const double mn = Ni < Nj ? Ni : Nj;
       o1[idx] = K / (2 * mn) + 0.5 - 0.25 * (Ni + Nj) / mn;
     }
-    if (o2) o2[idx] = V == 0 ? TPG_NAN : 0.5 * (1 + (double)(D + quirk) / (double)V);
+    if (o2) o2[idx] = V == 0 ? TPG_QNAN : 0.5 * (1 + (double)(D + quirk) / (double)V);
   }
 }
 

@@ -40,7 +40,6 @@
 #include "devfrag.h"
 
 #define MFMA_I8(a, b, c) __builtin_amdgcn_mfma_i32_32x32x32_i8((a), (b), (c), 0, 0, 0)
-#define PCA_NAN __longlong_as_double(0x7FF8000000000000ll)
 
 // ---------------------------------------------------------------------------
 // center / scale from genotype counts; flags[0] = missing value met, flags[1] = zero scale met
@@ -1862,18 +1861,6 @@ __global__ __launch_bounds__(256) void tpg_uq_colsum_kernel(const double* __rest
 #ifndef LD_WGS
 #define LD_WGS 2  // workgroups per CU the register budget is cut for
 #endif
-__device__ __forceinline__ int64_t tpg_uniform64_pca(int64_t x) {  // a wave-uniform value the compiler keeps in SGPRs
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-template <int C, class F>
-__device__ __forceinline__ void tpg_pca_static_for(F&& f) {
-  if constexpr (C > 0) {
-    tpg_pca_static_for<C - 1>(f);
-    f(std::integral_constant<int, C - 1>{});
-  }
-}
 
 template <int CTP, bool LMV>
 __global__ __launch_bounds__(256, LD_WGS) void tpg_loadings_mfma_kernel(const uint4* __restrict__ L,
@@ -1892,7 +1879,7 @@ __global__ __launch_bounds__(256, LD_WGS) void tpg_loadings_mfma_kernel(const ui
       for (int r = 0; r < 16; r++) acc[t][c][r] = 0;
   // (wave-uniform bases in SGPRs + a 32-bit lane offset per group, 32-bit group indices: no 64-bit per-lane pointers)
   const int Qi = (int)Q;
-  const int64_t lt0u = tpg_uniform64_pca(lt0);
+  const int64_t lt0u = tpg_uniform64(lt0);
   const char* pa[LD_NLT];
 #pragma unroll
   for (int t = 0; t < LD_NLT; t++) pa[t] = (const char*)(L + ((lt0u + t < n_lt ? lt0u + t : 0) * Q) * 64);  // past the end: a copy
@@ -1998,7 +1985,7 @@ __global__ __launch_bounds__(256, LD_WGS) void tpg_loadings_mfma_kernel(const ui
     tpg_lds_barrier();
   };
   for (int q = 0; q < Qi; q += LD_D)  // Q is the same for every wave: all of them meet every barrier
-    tpg_pca_static_for<LD_D>([&](auto kk) {
+    tpg_static_for<LD_D>([&](auto kk) {
       constexpr int k = decltype(kk)::value;
       if (q + k < Qi) group(std::integral_constant<int, k>{}, std::integral_constant<int, (k + LD_D - 1) % LD_D>{}, q + k);
     });
@@ -2042,15 +2029,8 @@ __global__ __launch_bounds__(1024) void tpg_absmax_kernel(const double* __restri
     if (a != a) bad = true;
     mx = a > mx ? a : mx;
   }
-  sh[threadIdx.x] = bad ? __longlong_as_double(0x7FF8000000000000ll) : mx;
-  __syncthreads();
-  for (int w = 512; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      const double a = sh[threadIdx.x], b = sh[threadIdx.x + w];
-      sh[threadIdx.x] = (a != a || b != b) ? __longlong_as_double(0x7FF8000000000000ll) : (a > b ? a : b);
-    }
-    __syncthreads();
-  }
+  sh[threadIdx.x] = bad ? TPG_QNAN : mx;
+  tpg_block_nanmax<1024>(sh);
   if (threadIdx.x == 0) out[0] = sh[0];
 }
 

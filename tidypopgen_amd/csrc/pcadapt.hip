@@ -18,6 +18,7 @@
 // a quarter of them share the exponent of the median absolute deviation), up to 6 for a column of mostly equal values.
 // NaN and infinite entries never enter a count or a rank.  Integer LDS atomics only; the result does not depend on their order.
 #include "common.h"
+#include "devfrag.h"
 #include "host/host_pcadapt.h"
 
 #include <math.h>
@@ -38,8 +39,6 @@ struct SelDesc {
   int32_t cidx;   // the centre of an ABSDEV kind: cvals[cidx]
 };
 
-#define PCD_NAN __longlong_as_double(0x7FF8000000000000ll)
-#define PCD_EXP_MASK 0x7FF0000000000000ull
 
 // the value of virtual column `d` at `row` as its sort key; false: not finite.  -0 is read as +0 (x + 0.0), so that equal
 // values have equal keys
@@ -52,13 +51,9 @@ __device__ __forceinline__ bool sel_key(const double* __restrict__ X, int64_t ld
   if (d.kind == SEL_ABSDEV || d.kind >= SEL_SUM_ABSDEV) x = fabs(x - c);
   x = x + 0.0;
   const uint64_t u = (uint64_t)__double_as_longlong(x);
-  if ((u & PCD_EXP_MASK) == PCD_EXP_MASK) return false;
-  key = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  if ((u & TPG_D_EXP_MASK) == TPG_D_EXP_MASK) return false;
+  key = TPG_DKEY(u);
   return true;
-}
-__device__ __forceinline__ double sel_unkey(uint64_t key) {
-  const uint64_t u = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-  return __longlong_as_double((long long)u);
 }
 
 // which bins hold the elements of (0-based) ranks rank0 (in h0) and rank1 (in h1, which may be h0): res[s] = {bin, rank inside
@@ -183,7 +178,7 @@ __global__ __launch_bounds__(SEL_THREADS) void pcadapt_select_kernel(const doubl
       count = s_count;
       if (count == 0) {
         if (t == 0) {
-          out[col] = PCD_NAN;
+          out[col] = TPG_QNAN;
           if (cnt_out) cnt_out[col] = 0;
         }
         return;
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(SEL_THREADS) void pcadapt_select_kernel(const doubl
     __syncthreads();  // res is read by all before it is written again
   }
   if (t == 0) {
-    const double lo = sel_unkey(prefix[0]), hi = sel_unkey(prefix[1]);
+    const double lo = tpg_dunkey(prefix[0]), hi = tpg_dunkey(prefix[1]);
     out[col] = ns == 1 ? lo : (lo + hi) / 2;
     if (cnt_out) cnt_out[col] = (int64_t)count;
   }
@@ -233,7 +228,7 @@ __global__ void pcadapt_finalize_kernel(const int4* __restrict__ counts, int64_t
     }
     const bool ok = tot != 0.0 && rss > 0.0;
     const double den = sqrt(rss / dof);
-    for (int k = 0; k < K; k++) z[j + (int64_t)k * m] = ok ? z[j + (int64_t)k * m] / den : PCD_NAN;
+    for (int k = 0; k < K; k++) z[j + (int64_t)k * m] = ok ? z[j + (int64_t)k * m] / den : TPG_QNAN;
     mine += ok ? 1ull : 0ull;
   }
   for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
@@ -248,7 +243,7 @@ __global__ void pcadapt_mask_kernel(const double* __restrict__ Z, int64_t m, int
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
     bool ok = true;
     for (int k = 0; k < K; k++) ok = ok && fabs(Z[j + (int64_t)k * ldz]) <= 1.79769313486231570815e308;
-    for (int k = 0; k < K; k++) X[j + (int64_t)k * m] = ok ? Z[j + (int64_t)k * ldz] : PCD_NAN;
+    for (int k = 0; k < K; k++) X[j + (int64_t)k * m] = ok ? Z[j + (int64_t)k * ldz] : TPG_QNAN;
     mine += ok ? 1ull : 0ull;
   }
   for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);

@@ -33,13 +33,8 @@
 #define MFMA_I8(a, b, c) __builtin_amdgcn_mfma_i32_32x32x32_i8((a), (b), (c), 0, 0, 0)
 #define OP_TU 6        // digits per column (LD_TU of pca.hip)
 #define OP_BMAX 64     // columns per block
-#define OP_NAN __longlong_as_double(0x7FF8000000000000ll)
 
 #define OP_NG 64       // workgroups per column in the column statistics: OP_NG * 256 strided partial results
-
-__device__ __forceinline__ double tpg_pcaop_nanmax(double a, double b) {
-  return (a != a || b != b) ? OP_NAN : (a > b ? a : b);
-}
 
 // pmax[c * OP_NG + g] = max |x_ic| over the rows i = g * 256 + t (mod OP_NG * 256) (x = X / rdiv where rdiv is given),
 // NaN if one of them is not finite or too large to scale.  grid (b, OP_NG)
@@ -56,12 +51,8 @@ __global__ __launch_bounds__(256) void tpg_pcaop_colmax_kernel(const double* __r
     if (!(a < 1e300)) bad = true;  // NaN, infinity, or too large to scale
     mx = a > mx ? a : mx;
   }
-  sh[threadIdx.x] = bad ? OP_NAN : mx;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] = tpg_pcaop_nanmax(sh[threadIdx.x], sh[threadIdx.x + w]);
-    __syncthreads();
-  }
+  sh[threadIdx.x] = bad ? TPG_QNAN : mx;
+  tpg_block_nanmax<256>(sh);
   if (threadIdx.x == 0) pmax[c * OP_NG + blockIdx.y] = sh[0];
 }
 
@@ -72,11 +63,7 @@ __global__ __launch_bounds__(OP_NG) void tpg_pcaop_exponent_kernel(const double*
   __shared__ double sh[OP_NG];
   const int c = blockIdx.x;
   sh[threadIdx.x] = pmax[c * OP_NG + threadIdx.x];
-  __syncthreads();
-  for (int w = OP_NG / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] = tpg_pcaop_nanmax(sh[threadIdx.x], sh[threadIdx.x + w]);
-    __syncthreads();
-  }
+  tpg_block_nanmax<OP_NG>(sh);
   if (threadIdx.x == 0) {
     const double a = sh[0];
     int ex = 0;
@@ -202,7 +189,7 @@ __global__ __launch_bounds__(OP_NG) void tpg_pcaop_colsum2_kernel(const double* 
   const int c = blockIdx.x;
   const double am = amax[c];
   if (!(am > 0)) {
-    if (threadIdx.x == 0) out[c] = am == 0 ? 0.0 : OP_NAN;
+    if (threadIdx.x == 0) out[c] = am == 0 ? 0.0 : TPG_QNAN;
     return;
   }
   sh[threadIdx.x] = psum[c * OP_NG + threadIdx.x];
@@ -312,7 +299,7 @@ __global__ void tpg_pcaop_finalize_zt_kernel(const int32_t* __restrict__ part, i
     const double am = amax[c];
     double out;
     if (am == 0) out = 0.0;
-    else if (!(am > 0)) out = OP_NAN;
+    else if (!(am > 0)) out = TPG_QNAN;
     else {
       const double gu = ldexp(tpg_pcaop_recombine(part, S, rows_pad, Cpad, j, c), -FU[c]);
       const double p = center[j] * qsum[c];
@@ -334,7 +321,7 @@ __global__ void tpg_pcaop_finalize_z_kernel(const int32_t* __restrict__ part, in
     const double am = amax[c];
     double out;
     if (am == 0) out = 0.0;
-    else if (!(am > 0)) out = OP_NAN;
+    else if (!(am > 0)) out = TPG_QNAN;
     else out = ldexp(tpg_pcaop_recombine(part, S, rows_pad, Cpad, i, c), -FU[c]) - csum[c];
     Y[i + (int64_t)c * n] = out;
   }

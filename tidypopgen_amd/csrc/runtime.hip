@@ -578,6 +578,25 @@ InBuf::~InBuf() {
   if (owned_ptr) tpg_pfree(owned_ptr);
 }
 
+__global__ void tpg_finite_kernel(const double* __restrict__ X, int64_t count, int* __restrict__ flag) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < count && !isfinite(X[t])) *flag = 1;
+}
+
+// common.h: every entry of a device array finite, else TPG_ENUMERIC naming `what`; the flag comes out of the caller's arena.
+// (The launch keeps the name it had when only the k-means called it.)
+int tpg_check_finite(tpg_ctx* ctx, const double* dX, int64_t count, DevArena& sc, const char* what) {
+  int* d_flag;
+  TPG_TRY(sc.get(&d_flag, 4));
+  TPG_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
+  TPG_LAUNCH(ctx, "km_finite", tpg_finite_kernel, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, dX, count, d_flag);
+  TPG_CHECK_LAUNCH();
+  int flag = 0;
+  TPG_HIP(tpg_fetch_small(ctx, &flag, d_flag, sizeof(int)));
+  TPG_REQUIRE(!flag, TPG_ENUMERIC, "%s holds a value that is not finite", what);
+  return TPG_OK;
+}
+
 int tpg_check_ranges(tpg_ctx* ctx, const int64_t* lo, const int64_t* hi, int64_t count, int64_t m, const char* what) {
   HostIn<int64_t> hlo, hhi;
   TPG_TRY(hlo.init(ctx, lo, count));

@@ -142,7 +142,7 @@ __global__ void snmf_q_combine_kernel(const double* __restrict__ part, const int
 
 // ---- NNLS: the solver itself is host/host_nnls.h (one thread per system; also built for the host by tests/host/nnls_san.cpp) ----
 __device__ __forceinline__ void snmf_count_unsolved(int bad, unsigned long long* __restrict__ unsolved) {
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  bad = tpg_wave_sum(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(unsolved, (unsigned long long)bad);
 }
 
@@ -590,46 +590,10 @@ extern "C" int tpg_nnls_shared(tpg_ctx* ctx, int K, const double* A, const doubl
 }
 
 // ---- hold-out by fraction and the cross-entropy (include/tpg.h "sNMF") ---------------------------------------------------------
-// Siblings of admix_holdout_view_kernel and admix_holdout_sweep_kernel (admix.hip): the same geometry, the same hash, the same sum
-// shapes.  The view kernel compares the high half of the hash with a threshold instead of mapping it to a fold; the sweep decodes
-// both planes and adds -ln max(p, floor) to one of two sums: typed in `train`, or typed in `full` alone.
+// The view is admix_common.h's hold-out with the high half of the hash against a threshold instead of a fold.  The sweep is a
+// sibling of admix_holdout_sweep_kernel (admix.hip): the same geometry, the same sum shapes; it decodes both planes and adds
+// -ln max(p, floor) to one of two sums: typed in `train`, or typed in `full` alone.
 namespace {
-
-__global__ __launch_bounds__(256) void snmf_holdout_view_kernel(const uint4* __restrict__ L, uint4* __restrict__ out, int64_t n_lt,
-                                                                int64_t Qb, uint64_t thr, uint64_t seed,
-                                                                unsigned long long* __restrict__ d_held) {
-  __shared__ uint64_t mi[2][128];  // M(i) of the block's individuals; two buffers: one barrier per block
-  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-  const int64_t lt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const bool live = lt < n_lt;  // a wave beyond the last tile still stages and meets the barriers
-  const uint64_t key = tpg_mix64((seed ^ ADM_CV_SALT) ^ tpg_mix64((uint64_t)(lt * 32 + r)));
-  int held = 0;
-  for (int64_t q = 0; q < Qb; q++) {
-    uint64_t* __restrict__ ms = mi[q & 1];
-    if (threadIdx.x < 128) ms[threadIdx.x] = tpg_mix64((uint64_t)(128 * q + threadIdx.x));
-    __syncthreads();
-    if (!live) continue;
-    const uint4 a = L[(lt * Qb + q) * 64 + lane];
-    uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-      // typed entries only: the padding (individuals >= n, loci >= m) is code 3 and stays so
-      uint32_t typed = ~(w[d] & (w[d] >> 1)) & 0x55555555u;
-      while (typed) {
-        const int pos = __ffs(typed) - 1;  // 8 b + 2 k: element 4 k + b
-        typed &= typed - 1;
-        const int e = 4 * ((pos & 7) >> 1) + (pos >> 3);
-        if ((tpg_mix64(key ^ ms[32 * d + 16 * h + e]) >> 32) < thr) {
-          w[d] |= 3u << pos;
-          held++;
-        }
-      }
-    }
-    out[(lt * Qb + q) * 64 + lane] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  for (int o = 32; o > 0; o >>= 1) held += __shfl_xor(held, o);
-  if (lane == 0 && held) atomicAdd(d_held, (unsigned long long)held);
-}
 
 // one workgroup per tile of 32 loci.  part_m[lt] / part_a[lt] = the tile's share of the masked / all sum; d_cnt[0] / d_cnt[1] += the
 // number of their entries
@@ -707,23 +671,8 @@ extern "C" int tpg_view_holdout_fraction(tpg_ctx* ctx, const tpg_view* full, dou
   TpgEnter _enter(ctx);
   TPG_REQUIRE(ctx && full && out, TPG_EINVAL, "null argument");
   TPG_REQUIRE(fraction > 0.0 && fraction < 1.0, TPG_EINVAL, "fraction = %g out of (0, 1)", fraction);
-  TPG_TRY(tpg_view_need_L(ctx, full));
-  const int64_t n_lt = 4 * full->KG;
-  TPG_REQUIRE(ceil_div(n_lt, 4) <= 0x7FFFFFFF, TPG_EUNSUPPORTED, "a hold-out view of %lld loci", (long long)full->m);
   const uint64_t thr = (uint64_t)floor(fraction * 4294967296.0);
-  ViewPtr v(new tpg_view(ctx, full->n, full->m));
-  DevBuf d_held;
-  TPG_HIP(tpg_pmalloc((void**)&v->L, v->bytes_each));
-  TPG_TRY(d_held.alloc(8));
-  TPG_HIP(hipMemsetAsync(d_held.p, 0, 8, ctx->stream));
-  TPG_LAUNCH(ctx, "snmf_holdout_view", snmf_holdout_view_kernel, dim3((unsigned)ceil_div(n_lt, 4)), dim3(256), 0, (const uint4*)full->L,
-             v->L, n_lt, full->Q, thr, seed, d_held.as<unsigned long long>());
-  TPG_CHECK_LAUNCH();
-  unsigned long long hh = 0;
-  TPG_HIP(tpg_fetch_small(ctx, &hh, d_held.p, sizeof hh));
-  if (n_held) *n_held = (int64_t)hh;
-  *out = v.release();
-  return TPG_OK;
+  return admix_holdout_view<HoldoutBelow>(ctx, "snmf_holdout_view", full, seed, out, true, n_held, thr);
 }
 
 extern "C" int tpg_snmf_cross_entropy_sums(tpg_ctx* ctx, const tpg_view* full, const tpg_view* train, int K, const double* Q,

@@ -19,6 +19,7 @@
 // Every sum has a fixed shape that depends on (lo, hi) or on m alone: per-thread strided partials, a butterfly over the wave,
 // the waves of a workgroup in order.  No atomics.
 #include "common.h"
+#include "devfrag.h"
 
 #include <math.h>
 #include <string.h>
@@ -26,7 +27,6 @@
 namespace {
 
 constexpr int TAJ_CHUNK = TPG_TAJIMA_CHUNK_LOCI;
-#define TAJ_NAN __longlong_as_double(0x7FF8000000000000ll)
 
 // a1, e1, e2 of n sampled alleles (R/pop_tajimas_d.R:158-163), in double, a1 and a2 summed in ascending order of i
 void tajima_consts(int64_t n, double* a1, double* e1, double* e2) {
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(64) void tajima_combine_kernel(const double* __rest
   }
   tajima_wave_sum(a);
   if (threadIdx.x == 0) {
-    out_k[g] = a.cnt == m ? a.k : TAJ_NAN;
+    out_k[g] = a.cnt == m ? a.k : TPG_QNAN;
     out_seg[g] = a.seg;
   }
 }
@@ -157,8 +157,8 @@ __global__ __launch_bounds__(256) void tajima_windows_kernel(const double* __res
   for (int t = 1; t < 4; t++) { a.k += sk[t]; a.seg += sseg[t]; a.cnt += scnt[t]; }
   const int64_t o = w + (int64_t)g * nw;
   const double a1 = consts[3 * g];  // NaN for a group nobody belongs to: k_hat is NaN there even over an empty window
-  const double k = (pad || a.cnt != j1 - j0 || a1 != a1) ? TAJ_NAN : a.k;
-  double r = TAJ_NAN;
+  const double k = (pad || a.cnt != j1 - j0 || a1 != a1) ? TPG_QNAN : a.k;
+  double r = TPG_QNAN;
   if (!pad && a.cnt >= min_loci) r = tajima_d(k, a.seg, a1, consts[3 * g + 1], consts[3 * g + 2]);
   d[o] = r;
   if (seg) seg[o] = a.seg;

@@ -181,8 +181,8 @@ __global__ __launch_bounds__(256) void winfst_window_kernel(WfSrc wsrc, int64_t 
   for (int k = 0; k < PPT; k++) {
     if (!pr.has(k)) continue;
     const int64_t o = w + (int64_t)pr.pidx(k) * nw;
-    const double mn = (pad || a.cn[k] == 0 || a.cn[k] < min_loci) ? FST_NAN : a.sn[k] / (double)a.cn[k];
-    const double md = (pad || a.cd[k] == 0 || a.cd[k] < min_loci) ? FST_NAN : a.sd[k] / (double)a.cd[k];
+    const double mn = (pad || a.cn[k] == 0 || a.cn[k] < min_loci) ? TPG_QNAN : a.sn[k] / (double)a.cn[k];
+    const double md = (pad || a.cd[k] == 0 || a.cd[k] < min_loci) ? TPG_QNAN : a.sd[k] / (double)a.cd[k];
     fst[o] = mn / md;
     if (mean_num) mean_num[o] = mn;
     if (mean_den) mean_den[o] = md;
