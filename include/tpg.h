@@ -297,6 +297,49 @@ int tpg_view_impute_errors(tpg_ctx* ctx, const tpg_view* full, const tpg_view* t
  * individuals the profiles of two workgroups per CU (256 CUs assumed) */
 size_t tpg_knn_impute_scratch_bytes(int64_t n, int64_t m, int64_t width, int l);
 
+/* ---- LD statistics (loci_ld_score, ld_decay, ld_region_r2: how much LD there is inside the window; no counterpart in the
+ * reference, whose LD functions only search the window) ---------------------------------------------------------------------
+ * The definition is this project's own.  Everything below is integers but r2 itself.
+ * Input: a view of n individuals x m loci in which every code is 0, 1 or 2.  A missing genotype: TPG_ENUMERIC (impute the view
+ *   first).  n >= 2^22: TPG_EUNSUPPORTED.
+ * Window: hi[m] exactly as "LD clumping" takes it and checks it.  The PAIRS are all (j, k) with j < k <= hi[j]; the PARTNERS of
+ *   locus j are the k > j with k <= hi[j] and the k < j with j <= hi[k], as in "LD-kNN imputation".
+ *   sum_j (hi[j] - j) >= 2^33: TPG_EUNSUPPORTED (so that no sum below passes 2^63).
+ * r2 of a pair: Sx, Sxx and d = n Sxx - Sx^2 from the counts, d held as a double; num = n Sxy - Sx_j Sx_k in int64,
+ *   dn = (double)num and
+ *       r2 = (dn * dn) / (d_j * d_k)
+ *   -- three IEEE double operations in this order, no FMA contraction: the bits tpg_ld_top_neighbours returns for the pair.
+ *   A pair is VALID iff d_j > 0 and d_k > 0: a monomorphic locus has no valid pair.
+ * Fixed point: q = (uint64) floor(r2 * 2^30 + 0.5).  Every sum of r2 below is a uint64 sum of q, which depends on no order; the
+ *   rounding is at most 2^-31 per pair, far below the sampling error 1 / n of an r2.  No sum reaches 2^63, so the prototypes
+ *   spell the arrays int64_t like every other 64-bit output of this header: the bits are those of the uint64 sum.
+ * Per locus (score_q and n_partners are NULL together): score_q[m], uint64 = sum of q over the valid pairs of j with its
+ *   partners on both sides; n_partners[m], int32 = the number of those pairs.  The self term is not included.
+ * Decay (bin_pairs, bin_sum_q and bin_sum_dist are NULL together; bin_size and nbins are read only with them): pos is
+ *   int64[m], or NULL.  dist = pos[k] - pos[j], or k - j without pos.  pos[j + 1] < pos[j] for neighbours j, j + 1, or a
+ *   |pos| of 2^61 or more: TPG_EINVAL (a decrease across a window border is allowed).  bin_size >= 1 and
+ *   1 <= nbins <= 4096, else TPG_EINVAL.  bin = dist / bin_size by integer division; over the valid pairs with bin < nbins:
+ *   bin_pairs[nbins] int64 their number, bin_sum_q[nbins] uint64 the sum of q, bin_sum_dist[nbins] int64 the sum of dist
+ *   (distances so large that this sum could pass 2^63: TPG_EUNSUPPORTED).  Valid pairs with bin >= nbins are counted in
+ *   pairs_beyond.
+ * A NULL group does not change a bit of the other group.  hi, pos and all outputs may be host or device memory.  On any error
+ *   nothing is written. */
+typedef struct tpg_ldstat_report {
+  int64_t pairs;        /* sum_j (hi[j] - j) */
+  int64_t pairs_valid;  /* pairs of two polymorphic loci */
+  int64_t pairs_beyond; /* valid pairs behind the last bin (0 without the decay group) */
+  int64_t band_tiles;   /* 32 x 32 tiles of Sxy the call contracted */
+} tpg_ldstat_report;
+/* one call, one pass over the band.  report (host memory, may be NULL): a tpg_ldstat_report, taken as the four int64_t it
+ * consists of */
+int tpg_ld_stats(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, const int64_t* pos, int64_t bin_size, int nbins,
+                 int64_t* score_q, int32_t* n_partners, int64_t* bin_pairs, int64_t* bin_sum_q, int64_t* bin_sum_dist,
+                 int64_t* report);
+/* the values of a region, for heatmaps, tests and small panels: r2[(j - j0) * stride + b] = r2 of the pair (j, j + 1 + b) for
+ * j0 <= j < j1 and b < hi[j] - j; NaN outside the window and for a pair that is not valid.  0 <= j0 < j1 <= m,
+ * stride >= max(1, hi[j] - j) over the region and (j1 - j0) * stride <= 2^26, else TPG_EINVAL. */
+int tpg_ld_band_r2(tpg_ctx* ctx, const tpg_view* v, const int64_t* hi, int64_t j0, int64_t j1, double* r2, int64_t stride);
+
 /* ---- Runs of homozygosity (windows_indiv_roh, R/windows_indiv_roh.R:65-150 around detectRUNS::slidingRuns) ---------------
  * detectRUNS is not part of the reference checkout, so the definition below is this project's own.  It is
  * stated in integers; the two places where a double appears are spelled out.

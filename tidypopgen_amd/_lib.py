@@ -87,6 +87,11 @@ class LdReport(C.Structure):
                 ("band_bytes", C.c_int64)]
 
 
+class LdStatReport(C.Structure):
+    """tpg_ldstat_report of include/tpg.h (tpg_ld_stats takes it as the four int64_t it consists of)"""
+    _fields_ = [("pairs", C.c_int64), ("pairs_valid", C.c_int64), ("pairs_beyond", C.c_int64), ("band_tiles", C.c_int64)]
+
+
 class RohParams(C.Structure):
     """tpg_roh_params of include/tpg.h, field for field"""
     _fields_ = [("window_size", C.c_int32), ("threshold", C.c_double), ("min_snp", C.c_int32), ("heterozygosity", C.c_int32),
@@ -181,6 +186,9 @@ PROTOTYPES = {
     "tpg_fbm_impute_knn": (ci, [vp, vp, vp, ci, ci, f64, ci, P(ImputeReport), vp]),
     "tpg_view_impute_errors": (ci, [vp, vp, vp, vp, vp, vp]),
     "tpg_knn_impute_scratch_bytes": (sz, [i64, i64, i64, ci]),
+    # ---- LD statistics
+    "tpg_ld_stats": (ci, [vp, vp, vp, vp, i64, ci, vp, vp, vp, vp, vp, vp]),
+    "tpg_ld_band_r2": (ci, [vp, vp, vp, i64, i64, vp, i64]),
     # ---- runs of homozygosity
     "tpg_roh_chunk_loci": (i64, []),
     "tpg_roh_snp_status": (ci, [vp, vp, vp, vp, P(RohParams), vp, i64]),

@@ -2909,6 +2909,172 @@ def loci_ld_clump(X: FBM, ind_row=None, ind_col=None, S=None, thr_r2: float = 0.
 
 
 # ---------------------------------------------------------------------------
+# LD statistics (include/tpg.h "LD statistics")
+
+LD_Q_ONE = 1 << 30          # the fixed point of every sum of r^2: q = floor(r2 * 2^30 + 0.5)
+LD_MAX_BINS = 4096          # HOST_LDSTAT_MAX_BINS
+LD_REGION_MAX_LOCI = 4096   # ld_region_r2: 4096 x 4095 values stay under the 2^26 of tpg_ld_band_r2
+
+
+def _ld_positions(v: View, position):
+    """positions as the int64 the library takes (None stays None); a fractional position is an error, not a rounding"""
+    if position is None:
+        return None
+    p = np.asarray(position)
+    if p.shape != (v.m,):
+        raise ValueError("position must have one entry per locus of the view")
+    if p.dtype.kind == "f":
+        if not np.all(np.isfinite(p)) or np.any(p != np.floor(p)):
+            raise ValueError("positions must be whole numbers")
+    elif p.dtype.kind not in "iu":
+        raise ValueError("positions must be numbers")
+    return np.ascontiguousarray(p, dtype=np.int64)
+
+
+def ld_stats(v: View, hi, position=None, bin_size: int = 1, n_bins: int = 0, scores: bool = True) -> dict:
+    """tpg_ld_stats on a view without missing genotypes, the raw integers: with scores "score_q" (m,) uint64 and "n_partners"
+    (m,) int32; with n_bins != 0 "bin_pairs" (n_bins,) int64, "bin_sum_q" uint64 and "bin_sum_dist" int64 over the distances
+    position[k] - position[j] (k - j without positions); always "report" = {pairs, pairs_valid, pairs_beyond, band_tiles}.
+    r^2 sums are score_q / LD_Q_ONE."""
+    hi = _ld_hi(v, hi)
+    n_bins = int(n_bins)
+    pos = _ld_positions(v, position) if n_bins != 0 else None
+    out = {}
+    sq = npart = bp = bq = bd = None
+    if scores:
+        sq, npart = np.zeros(v.m, dtype=np.uint64), np.zeros(v.m, dtype=np.int32)
+    if n_bins != 0:  # (a count the library refuses still reaches it: the arrays only have to exist)
+        bp, bq, bd = (np.zeros(max(n_bins, 1), dtype=t) for t in (np.int64, np.uint64, np.int64))
+    rep = _lib.LdStatReport()
+    check(lib.tpg_ld_stats(v.ctx.h, v.h, _ptr(hi), _ptr(pos), int(bin_size), n_bins, _ptr(sq), _ptr(npart), _ptr(bp), _ptr(bq),
+                           _ptr(bd), C.byref(rep)))
+    if scores:
+        out.update(score_q=sq, n_partners=npart)
+    if n_bins != 0:
+        out.update(bin_pairs=bp, bin_sum_q=bq, bin_sum_dist=bd)
+    out["report"] = {f: int(getattr(rep, f)) for f, _ in _lib.LdStatReport._fields_}
+    return out
+
+
+def ld_band_r2(v: View, hi, j0: int, j1: int) -> np.ndarray:
+    """tpg_ld_band_r2: r^2 of the loci j0 <= j < j1 (0-based) with the loci behind them in the window, (j1 - j0, stride)
+    float64 with entry [j - j0, b] = r^2 of (j, j + 1 + b); NaN outside the window and for a pair with a monomorphic locus;
+    stride = the widest window of the region (at least 1)"""
+    hi = _ld_hi(v, hi)
+    j0, j1 = int(j0), int(j1)
+    if not 0 <= j0 < j1 <= v.m:
+        raise ValueError("[j0, j1) must be a range of the loci of the view")
+    stride = max(1, int((hi[j0:j1] - np.arange(j0, j1)).max()))
+    r2 = np.zeros((j1 - j0, stride), dtype=np.float64)
+    check(lib.tpg_ld_band_r2(v.ctx.h, v.h, _ptr(hi), j0, j1, _ptr(r2), stride))
+    return r2
+
+
+def ld_region_r2(X: FBM, j0: int, j1: int, ind_row=None, ind_col=None, impute: Optional[str] = None, impute_seed: int = 0) -> np.ndarray:
+    """the r^2 matrix of the loci j0 <= j < j1 (0-based positions in ind_col; at most LD_REGION_MAX_LOCI of them) for a
+    heatmap: symmetric (j1 - j0, j1 - j0) float64, diagonal 1; the row and column of a monomorphic locus are NaN, diagonal
+    included.  A missing genotype is an error unless impute = "mode" | "mean0" | "random" fills the view first."""
+    v = _pca_view(X, ind_row, ind_col, "fbm", impute, impute_seed)
+    j0, j1 = int(j0), int(j1)
+    if not 0 <= j0 < j1 <= v.m:
+        raise ValueError("[j0, j1) must be a range of the loci of ind_col")
+    r = j1 - j0
+    if r > LD_REGION_MAX_LOCI:
+        raise ValueError(f"a region of {r} loci: at most {LD_REGION_MAX_LOCI}")
+    sub = v.select_loci(np.arange(j0, j1))
+    band = ld_band_r2(sub, np.full(r, r - 1, dtype=np.int64), 0, r)
+    poly = loci_counts(sub)[:, :3].max(axis=1) < sub.n
+    sub.free()
+    out = np.full((r, r), np.nan)
+    a, b = np.triu_indices(r, 1)
+    out[a, b] = band[a, b - a - 1]
+    out[b, a] = out[a, b]
+    out[np.arange(r), np.arange(r)] = np.where(poly, 1.0, np.nan)
+    return out
+
+
+def _ld_stat_view(X, ind_row, ind_col, size, chromosome, position, use_positions, impute, impute_seed):
+    """the view and its window, as loci_ld_clump makes them"""
+    v = _pca_view(X, ind_row, ind_col, "fbm", impute, impute_seed)
+    if use_positions and position is None:
+        raise ValueError("use_positions = TRUE needs positions; pass use_positions=False to count in loci")
+    hi = ld_window_hi(chromosome, position, size, use_positions, m=v.m)
+    if len(hi) != v.m:
+        raise ValueError("chromosome / position must describe every locus of ind_col")
+    return v, hi
+
+
+def loci_ld_score(X: FBM, ind_row=None, ind_col=None, size=500.0, chromosome=None, position=None, use_positions: bool = True,
+                  adjusted: bool = True, include_self: bool = True, impute: Optional[str] = None, impute_seed: int = 0) -> np.ndarray:
+    """the LD score of every locus: the sum of r^2 with the loci of its window (ld_window_hi: size kb either side, or size
+    loci with use_positions = False), (m,) float64.  adjusted: every r^2 in its bias-corrected form r^2 - (1 - r^2) / (n - 2),
+    the form of LD score regression (Bulik-Sullivan et al. 2015); n < 3 is then an error.  include_self adds the locus's own
+    r^2 = 1.  A monomorphic locus has no r^2 with anybody: NaN.  Missing genotypes as in loci_ld_clump."""
+    v, hi = _ld_stat_view(X, ind_row, ind_col, size, chromosome, position, use_positions, impute, impute_seed)
+    if adjusted and v.n < 3:
+        raise ValueError("the adjusted LD score needs at least 3 individuals")
+    r = ld_stats(v, hi)
+    S = r["score_q"].astype(np.float64) / LD_Q_ONE
+    c = r["n_partners"].astype(np.float64)
+    score = S - (c - S) / (v.n - 2) if adjusted else S
+    if include_self:
+        score = score + 1.0
+    score[loci_counts(v)[:, :3].max(axis=1) >= v.n] = np.nan
+    return score
+
+
+def _ld_decay_one(v, hi, pos, bin_size, n_bins, adjusted) -> dict:
+    r = ld_stats(v, hi, pos, bin_size, n_bins, scores=False)
+    npairs = r["bin_pairs"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_r2 = np.where(npairs > 0, r["bin_sum_q"].astype(np.float64) / LD_Q_ONE / npairs, np.nan)
+        mean_dist = np.where(npairs > 0, r["bin_sum_dist"].astype(np.float64) / npairs, np.nan)
+    if adjusted:
+        mean_r2 = mean_r2 - (1.0 - mean_r2) / (v.n - 2)
+    lo = np.arange(n_bins, dtype=np.int64) * int(bin_size)
+    return dict(distance_lo=lo, distance_hi=lo + int(bin_size), mean_distance=mean_dist, n_pairs=npairs, mean_r2=mean_r2,
+                pairs_beyond=r["report"]["pairs_beyond"])
+
+
+def ld_decay(X: FBM, ind_row=None, ind_col=None, size=500.0, chromosome=None, position=None, use_positions: bool = True,
+             bin_size: Optional[int] = None, n_bins: Optional[int] = None, by_chromosome: bool = False, adjusted: bool = False,
+             impute: Optional[str] = None, impute_seed: int = 0) -> dict:
+    """the LD decay curve: mean r^2 of the pairs of loci inside the window (as loci_ld_score takes it) by distance -- in
+    positions with use_positions, else in loci.  Bin b holds the distances [b bin_size, (b + 1) bin_size); bin_size defaults
+    to 1000 positions or 1 locus, n_bins to what the window reaches (at most LD_MAX_BINS).  Returns "distance_lo",
+    "distance_hi" (exclusive), "mean_distance", "n_pairs", "mean_r2" (NaN for an empty bin; adjusted: in the bias-corrected form
+    of loci_ld_score) and "pairs_beyond", the pairs behind the last bin.  by_chromosome: one curve per chromosome, the arrays
+    stacked as rows in the order of "chromosome"."""
+    v, hi = _ld_stat_view(X, ind_row, ind_col, size, chromosome, position, use_positions, impute, impute_seed)
+    if adjusted and v.n < 3:
+        raise ValueError("the adjusted r^2 needs at least 3 individuals")
+    if bin_size is None:
+        bin_size = 1000 if use_positions else 1
+    bin_size = int(bin_size)
+    if bin_size < 1:
+        raise ValueError("bin_size must be at least 1")
+    if n_bins is None:
+        reach = int(math.floor(float(size) * 1000.0)) if use_positions else int(math.floor(size))
+        n_bins = min(LD_MAX_BINS, reach // bin_size + 1)
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= LD_MAX_BINS:
+        raise ValueError(f"n_bins must lie in [1, {LD_MAX_BINS}]")
+    pos = _ld_positions(v, position) if use_positions else None
+    if not by_chromosome:
+        return _ld_decay_one(v, hi, pos, bin_size, n_bins, adjusted)
+    chrom = np.zeros(v.m, dtype=np.int64) if chromosome is None else np.asarray(chromosome)
+    starts = np.r_[0, np.flatnonzero(chrom[1:] != chrom[:-1]) + 1, v.m]
+    curves = []
+    for a, b in zip(starts[:-1], starts[1:]):
+        sub = v.select_loci(np.arange(a, b))
+        curves.append(_ld_decay_one(sub, hi[a:b] - a, None if pos is None else pos[a:b], bin_size, n_bins, adjusted))
+        sub.free()
+    out = {k: np.stack([c[k] for c in curves]) for k in curves[0]}
+    out["chromosome"] = chrom[starts[:-1]]
+    return out
+
+
+# ---------------------------------------------------------------------------
 # autoSVD (include/tpg.h "autoSVD")
 
 TUKEY_REPORT_FIELDS = ("n_finite", "q1", "q3", "med", "mc", "coef", "thr")

@@ -1,5 +1,5 @@
-// ldband.h -- the banded L x L' contraction that LD clumping (ld.hip) and LD-kNN imputation (knnimp.hip) share; included by
-// those two files only.
+// ldband.h -- the banded L x L' contraction that LD clumping (ld.hip), LD-kNN imputation (knnimp.hip) and the LD statistics
+// (ldstat.hip) share; included by those three files only.
 //
 // Sxy = sum_i x_j x_k of two neighbouring loci is a locus x locus product over the individuals, i.e. over the Q groups of the
 // locus-tiled layout L, with L as BOTH operands.  A 2-bit code c in the low bits of a nibble is the FP4 (E2M1) value c / 2, so
