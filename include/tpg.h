@@ -395,6 +395,46 @@ int tpg_roh_indiv_summary(tpg_ctx* ctx, const tpg_roh* r, int64_t* n_runs, int64
 int tpg_roh_locus_counts(tpg_ctx* ctx, const tpg_roh* r, int32_t* counts);
 void tpg_roh_free(tpg_roh* r);
 
+/* ---- IBD segments (where two individuals share DNA: the stretches over which a pair shares at least one haplotype, IBD1, or
+ * both, IBD2; the output of `king --ibdseg` / IBIS; no counterpart in the reference) -----------------------------------------
+ * The definition is this project's own, recalled from Seidman et al. 2020 (IBIS) and KING, not pinned.
+ * Everything is an integer.
+ * Input: a view of n individuals x m loci (codes 0, 1, 2, and 3 = missing), chrom (int32[m]) and pos (int64[m]) of its loci,
+ *   host or device memory -- pos in any ordered integer unit: bp, or cM scaled to integers -- and the scalars below.
+ * Per unordered pair (a, b), a < b, and per locus j: typed[j] = both codes != 3.  bad[j] for kind = 1: typed and the codes are
+ *   {0, 2} in either order (opposite homozygotes cannot share a haplotype); for kind = 2: typed and the codes differ (they
+ *   cannot share both).  A missing genotype is neither bad nor typed.
+ *   1. brk[j], 0 <= j < m - 1, exactly as step 2 of "Runs of homozygosity": a chromosome change, or pos[j + 1] - pos[j] >
+ *      max_gap.  A position that decreases inside a chromosome: TPG_EINVAL ("not ordered"); equal positions are allowed.
+ *   2. A CLEAN STRETCH is a maximal [s, e] with no bad locus in it and no brk[j] for s <= j < e; its count c = the typed loci
+ *      in it.
+ *   3. Bridging (bridge_min_snp > 0): two consecutive clean stretches [s1, e1], [s2, e2] are JOINED iff s2 = e1 + 2 (exactly
+ *      one bad locus lies between them), brk[e1] and brk[e1 + 1] are both false, c1 >= bridge_min_snp and c2 >=
+ *      bridge_min_snp.  A joint depends on its two stretches only, so the order of evaluation does not matter.  A SEGMENT is
+ *      a maximal chain of joined stretches [first, last]; n_err = its bridged bad loci, n_typed = the typed loci in
+ *      [first, last].  With bridge_min_snp = 0 every clean stretch is its own segment and n_err = 0.
+ *   4. A segment is REPORTED iff n_typed >= min_snp, pos[last] - pos[first] >= min_length, and n_err <= max_err where
+ *      max_err >= 0 (a negative max_err: no limit).
+ * TPG_EINVAL: min_snp < 1 (with min_snp >= 1 a pair with a wholly missing individual reports nothing), min_length < 0,
+ *   max_gap < 0, bridge_min_snp < 0, kind not 1 or 2, cap < 0, cap > 0 with a NULL segment array.  m >= 2^31 - 64, or more
+ *   than 65536 individuals (2^31 pairs): TPG_EUNSUPPORTED.  n = 1: TPG_OK, no segment.
+ * Output: the reported segments of all pairs, ordered by (a, b, first), 0-based; per pair their number and the sum of their
+ *   lengths pos[last] - pos[first].  Deterministic, independent of chunking, tile shape and launch geometry. */
+/* loci per chunk of the scan (results do not depend on it) */
+#define TPG_IBD_CHUNK_LOCI 1024
+int64_t tpg_ibd_chunk_loci(void);
+/* the sum over the break-free regions of pos[last] - pos[first]: what a pair that shares everything adds up to.  Host only:
+ * chrom and pos are host memory.  m < 1, max_gap < 0, not ordered: TPG_EINVAL */
+int tpg_ibd_genome_length(const int32_t* chrom, const int64_t* pos, int64_t m, int64_t max_gap, int64_t* length);
+/* *count = the number of reported segments, whatever cap is.  count <= cap: the six arrays hold count entries each in the
+ * stated order; otherwise they are not written and the caller calls again (cap = 0 with NULL arrays is the counting call).
+ * pair_n_seg (int32) and pair_sum_length (int64): n x n, symmetric, zero diagonal; either may be NULL; complete whatever cap
+ * is.  Every output may be host or device memory.  On any error the caller's outputs are untouched. */
+int tpg_ibd_segments(tpg_ctx* ctx, const tpg_view* v, const int32_t* chrom, const int64_t* pos, int kind, int64_t min_snp,
+                     int64_t min_length, int64_t max_gap, int64_t bridge_min_snp, int64_t max_err, int64_t cap, int32_t* ind_a,
+                     int32_t* ind_b, int64_t* first0, int64_t* last0, int32_t* n_typed, int32_t* n_err, int64_t* count,
+                     int32_t* pair_n_seg, int64_t* pair_sum_length);
+
 /* ---- Tajima's D (pop_tajimas_d, R/pop_tajimas_d.R:151-166; windows_pop_tajimas_d, R/windows_pop_tajimas_d.R:69-102 over
  * R/windows_stats_generic.R:113-176; pi as src/gt_pi_diploid.cpp:22-35 and src/gt_grouped_pi_diploid.cpp:24-38) -----------
  * Group g has N_g individuals in the view and n = 2 N_g sampled alleles: the group's size, not its typed count.  J is a set

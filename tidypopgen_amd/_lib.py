@@ -198,6 +198,10 @@ PROTOTYPES = {
     "tpg_roh_indiv_summary": (ci, [vp, vp, vp, vp]),
     "tpg_roh_locus_counts": (ci, [vp, vp, vp]),
     "tpg_roh_free": (None, [vp]),
+    # ---- IBD segments
+    "tpg_ibd_chunk_loci": (i64, []),
+    "tpg_ibd_genome_length": (ci, [vp, vp, i64, i64, vp]),
+    "tpg_ibd_segments": (ci, [vp, vp, vp, vp, ci, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     # ---- Tajima's D
     "tpg_tajimas_d_from_sums": (ci, [i64, i64, f64, vp]),
     "tpg_tajima_chunk_loci": (i64, []),

@@ -3340,6 +3340,84 @@ def windows_indiv_roh(X: FBM, ind_row=None, ind_col=None, chromosome=None, posit
     return out
 
 
+# ---------------------------------------------------------------------------
+# IBD segments (include/tpg.h "IBD segments")
+
+# loci per chunk of the scan (results do not depend on it; the seam tests do)
+IBD_CHUNK_LOCI = int(lib.tpg_ibd_chunk_loci()) if hasattr(lib, "tpg_ibd_chunk_loci") else 0
+
+
+def ibd_genome_length(chromosome, position, max_gap: int = 10**6) -> int:
+    """tpg_ibd_genome_length: the sum over the break-free regions of pos[last] - pos[first], what a pair that shares everything
+    adds up to (host only)"""
+    chrom, pos = _roh_loci(len(np.asarray(position)), chromosome, position)
+    out = C.c_int64()
+    check(lib.tpg_ibd_genome_length(_ptr(chrom), _ptr(pos), len(pos), int(max_gap), C.byref(out)))
+    return int(out.value)
+
+
+def ibd_segments(X_or_view, chromosome, position, kind: int = 1, min_snp: int = 200, min_length: int = 0, max_gap: int = 10**6,
+                 bridge_min_snp: int = 50, max_err: int = -1, summary: bool = True, ind_row=None, ind_col=None, cap: Optional[int] = None) -> dict:
+    """tpg_ibd_segments: where the pairs of individuals share DNA (include/tpg.h "IBD segments"; the output of `king --ibdseg` /
+    IBIS on unphased genotypes).  kind 1: at least one haplotype shared (no opposite homozygotes), kind 2: both (equal
+    genotypes).  X_or_view: a View, or an FBM with ind_row / ind_col (1-based; ind_row is the hook for a subset of individuals).
+    chromosome / position describe the loci of the view, in order; position in any ordered integer unit.  The defaults are
+    this project's own: segments of at least 200 typed loci, single bad loci bridged between stretches of at least 50, any
+    number of them (max_err < 0: no limit).
+    cap: the segments the first call has room for.  The library walks the panel to count and again to write; a call whose arrays
+    are too short has counted for nothing and is repeated with room for all, which costs one more counting walk.  The default,
+    one segment per pair up to 2^24, is no bound but is rarely passed (the arrays are untouched memory until written); a caller
+    who knows better passes its own.
+    -> {ind_a, ind_b, first, last (0-based), length (pos[last] - pos[first]), n_typed, n_err}, ordered by (ind_a, ind_b, first);
+    with summary also n_seg and sum_length, (n, n), symmetric."""
+    if position is None:
+        raise ValueError("IBD segments need the positions of the loci")
+    v = X_or_view if isinstance(X_or_view, View) else View(X_or_view, ind_row, ind_col)
+    chrom, pos = _roh_loci(v.m, chromosome, position)
+    n = v.n
+    n_seg = np.zeros((n, n), dtype=np.int32) if summary else None
+    total = np.zeros((n, n), dtype=np.int64) if summary else None
+    cap = max(4096, min(n * (n - 1) // 2, 1 << 24)) if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("cap below 0")
+    count = C.c_int64()
+    while True:
+        seg = dict(ind_a=np.empty(cap, dtype=np.int32), ind_b=np.empty(cap, dtype=np.int32), first=np.empty(cap, dtype=np.int64),
+                   last=np.empty(cap, dtype=np.int64), n_typed=np.empty(cap, dtype=np.int32), n_err=np.empty(cap, dtype=np.int32))
+        check(lib.tpg_ibd_segments(v.ctx.h, v.h, _ptr(chrom), _ptr(pos), int(kind), int(min_snp), int(min_length), int(max_gap),
+                                   int(bridge_min_snp), int(max_err), cap, *(_ptr(seg[k]) if cap else None for k in
+                                   ("ind_a", "ind_b", "first", "last", "n_typed", "n_err")), C.byref(count), _ptr(n_seg), _ptr(total)))
+        if count.value <= cap:
+            break
+        cap = int(count.value)  # the arrays were too short and are untouched: once more with room for all
+    c = int(count.value)
+    out = {k: a[:c].copy() for k, a in seg.items()}  # (the arrays of cap entries go back)
+    out["length"] = pos[out["last"]] - pos[out["first"]]
+    if summary:
+        out["n_seg"], out["sum_length"] = n_seg, total
+    return out
+
+
+def pairwise_ibd(X, chromosome, position, ind_row=None, ind_col=None, **params) -> dict:
+    """IBD sharing of every pair from both kinds of segment (ibd_segments takes **params).  With L1 and L2 the per-pair sums of
+    the kind-1 and kind-2 segment lengths and Lg the genome length: ibd1_prop = (L1 - L2) / Lg and ibd2_prop = L2 / Lg (IBD2
+    lies inside IBD1), kin = (L1 + L2) / (4 Lg) -- a kinship estimate that uses no allele frequency and goes into
+    filter_high_relatedness as it is.  -> {ibd1_prop, ibd2_prop, kin (n, n), genome_length, segments1, segments2}"""
+    if "kind" in params or "summary" in params:
+        raise ValueError("pairwise_ibd runs both kinds with the summary: kind / summary are not its parameters")
+    if position is None:
+        raise ValueError("IBD segments need the positions of the loci")
+    Lg = ibd_genome_length(chromosome, position, params.get("max_gap", 10**6))  # (host only: before anything is packed or walked)
+    if Lg <= 0:
+        raise ValueError("the loci span no length: every break-free region holds one position")
+    v = X if isinstance(X, View) else View(X, ind_row, ind_col)
+    s1 = ibd_segments(v, chromosome, position, kind=1, summary=True, **params)
+    s2 = ibd_segments(v, chromosome, position, kind=2, summary=True, **params)
+    L1, L2 = s1.pop("sum_length").astype(np.float64), s2.pop("sum_length").astype(np.float64)
+    return {"ibd1_prop": (L1 - L2) / Lg, "ibd2_prop": L2 / Lg, "kin": (L1 + L2) / (4.0 * Lg), "genome_length": Lg,
+            "segments1": s1, "segments2": s2}
+
+
 def gt_impute_simple(X: FBM, method: str = "mode", seed: int = 0) -> FBM:
     """R/gt_impute_simple.R:54-93: the missing genotypes of X are filled in place (FBM.impute_simple) and X then reads
     through CODE_IMPUTE_PRED, as the reference leaves the gen_tibble's FBM; the report is left in `X.impute_report`.

@@ -3,8 +3,8 @@
 //
 //  * tpg_roh_status_kernel: a workgroup owns the 32 individuals of one row tile of T and a chunk of TPG_ROH_CHUNK_LOCI loci
 //    with a halo of HB = ceil((W - 1) / 128) blocks on either side.  Every 1-KiB block is read whole, 16 B per lane; the
-//    two-bit codes of a dword are turned into locus-ordered `opp` and `miss` masks by a fixed bit shuffle (even bits
-//    together, then a 4 x 4 bit transpose) and lanes r and r + 32 exchange halves, so that LDS holds 32 loci per word.
+//    two-bit codes of a dword are turned into locus-ordered `opp` and `miss` masks by a fixed bit shuffle (locusbits.h: even
+//    bits together, then a 4 x 4 bit transpose) and lanes r and r + 32 exchange halves, so that LDS holds 32 loci per word.
 //    Word-level prefix popcounts give the sums of the first window of a word, the other 31 follow by sliding (one bit in,
 //    one bit out): nothing loops over W.  The same once more over the window-ok bits gives `hits` per locus.  What does
 //    not depend on the individual -- which windows exist and cross no break -- comes up once as a bit vector.
@@ -14,6 +14,7 @@
 //  * tpg_roh_filter_kernel counts nOpp / nMiss of a segment from T and applies the run filters; a scan over the flags
 //    compacts the runs.  Only the two counts (segments, runs) cross to the host.
 #include "common.h"
+#include "locusbits.h"
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
@@ -31,32 +32,6 @@ struct tpg_roh {
   DevBuf pos;                              // int64[m]
 };
 
-// bits 0, 2, .., 30 of x -> bits 0 .. 15
-__device__ __forceinline__ uint32_t roh_even_bits(uint32_t x) {
-  x &= 0x55555555u;
-  x = (x | (x >> 1)) & 0x33333333u;
-  x = (x | (x >> 2)) & 0x0f0f0f0fu;
-  x = (x | (x >> 4)) & 0x00ff00ffu;
-  x = (x | (x >> 8)) & 0x0000ffffu;
-  return x;
-}
-// in either half: bit 4 b + k -> bit 4 k + b (element e = 4 k + b of a dword sits at bits 8 b + 2 k, common.h)
-__device__ __forceinline__ uint32_t roh_transpose4(uint32_t x) {
-  uint32_t t = (x ^ (x >> 3)) & 0x0a0a0a0au;
-  x ^= t ^ (t << 3);
-  t = (x ^ (x >> 6)) & 0x00cc00ccu;
-  x ^= t ^ (t << 6);
-  return x;
-}
-// the 16 codes of two dwords -> locus-ordered masks, dword a in the low half: opposite (code 1; with het: codes 0 and 2)
-// and missing (code 3)
-__device__ __forceinline__ void roh_masks(uint32_t a, uint32_t b, int het, uint32_t& opp, uint32_t& miss) {
-  const uint32_t la = a & 0x55555555u, ha = (a >> 1) & 0x55555555u;
-  const uint32_t lb = b & 0x55555555u, hb = (b >> 1) & 0x55555555u;
-  const uint32_t oa = het ? la ^ 0x55555555u : la & ~ha, ob = het ? lb ^ 0x55555555u : lb & ~hb;
-  opp = roh_transpose4(roh_even_bits(oa) | (roh_even_bits(ob) << 16));
-  miss = roh_transpose4(roh_even_bits(la & ha) | (roh_even_bits(lb & hb) << 16));
-}
 // bits [sh, sh + 32) of hi:lo
 __device__ __forceinline__ uint32_t roh_funnel(uint32_t lo, uint32_t hi, int sh) {
   return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
@@ -113,11 +88,13 @@ __global__ __launch_bounds__(256) void tpg_roh_status_kernel(const uint4* __rest
       if (kg < 0 || kg >= KG) continue;  // (the whole wave alike)
       const uint4 f = T[(rt * KG + kg) * 64 + lane];
       uint32_t o01, m01, o23, m23;
-      roh_masks(f.x, f.y, het, o01, m01);
-      roh_masks(f.z, f.w, het, o23, m23);
+      tpg_lb_opp_miss(f.x, f.y, het, o01, m01);
+      tpg_lb_opp_miss(f.z, f.w, het, o23, m23);
       const uint32_t po01 = (uint32_t)__shfl_xor((int)o01, 32), pm01 = (uint32_t)__shfl_xor((int)m01, 32);
       const uint32_t po23 = (uint32_t)__shfl_xor((int)o23, 32), pm23 = (uint32_t)__shfl_xor((int)m23, 32);
       // word s = loci 32 s .. 32 s + 31 of the block: low half from lane r, high half from lane r + 32
+      // (the exchange of locusbits.h's tpg_lb_words, written out: through that function the kernel compiles to other
+      // instructions, and this kernel's code stays as it was measured)
       uint32_t* ro = sopp + r * NWp + 4 * b;
       uint32_t* rm = smiss + r * NWp + 4 * b;
       if (h == 0) {
@@ -286,7 +263,7 @@ __global__ __launch_bounds__(256) void tpg_roh_filter_kernel(const uint32_t* __r
     const int off = (int)(lg & 127), s = off >> 5, h = (off >> 4) & 1;
     const uint32_t w = T32[(((rt * KG + kg) * 64) + r + 32 * h) * 4 + s];
     uint32_t o, ms;
-    roh_masks(w, 0u, het, o, ms);
+    tpg_lb_opp_miss(w, 0u, het, o, ms);
     const int lo = a > lg ? (int)(a - lg) : 0, hi = b < lg + 15 ? (int)(b - lg) : 15;
     const uint32_t mask = ((2u << hi) - 1u) & ~((1u << lo) - 1u) & 0xffffu;
     co += __popc(o & mask);
