@@ -540,6 +540,74 @@ int tpg_f2_blocks(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int
 int tpg_f4_jackknife(const double* f2, int G, int64_t nb, const int64_t* block_len, const int32_t* quads0, int64_t nq,
                      double* est, double* se, int32_t* n_used);
 
+/* ---- site frequency spectra (pop_sfs, pairwise_pop_jsfs; the reference has no SFS code and nothing pins it: the arithmetic
+ * is defined HERE, recalled, not pinned, from Marth et al. 2004 (the hypergeometric projection of a sample with missing data)
+ * and Gutenkunst et al. 2009 (dadi's projection and folding conventions)) -------------------------------------------------
+ * A view of N individuals in G groups, diploid only as for Tajima's D: ploidy may be NULL; anything other than 2 in it is
+ * TPG_EINVAL.  groupIds0 == NULL: one group of everybody.  A group nobody belongs to: TPG_EINVAL.
+ * Per locus j and group g:
+ *   v(j,g) = twice the typed individuals of g at j;  x(j,g) = alternate alleles among them.
+ *   flip:  uint8[m], host or device memory, may be NULL: where flip[j] != 0, x is replaced by v - x (the counted allele is
+ *          then the reference allele: how a caller supplies ancestral states).
+ *   keep:  uint8[m], host or device memory, may be NULL: 0 drops the locus everywhere.
+ * Projection size: proj (int32[G], host memory, may be NULL = all 0); n_g = proj[g] in [1, 2 N_g], 0 means 2 N_g; anything
+ *   else: TPG_EINVAL.  Offsets o_g = sum_{g' < g} (n_g' + 1), W = o_G; W > TPG_SFS_MAX_WIDTH: TPG_EINVAL.
+ * Usability: t(j,g) = [keep[j] and v(j,g) >= n_g]: a locus typed at fewer than n_g alleles in g is not usable for g.
+ * Weights: h(j,g,k) = C(x,k) C(v - x, n_g - k) / C(v, n_g), k = 0 .. n_g: the hypergeometric probability that a sample of n_g of
+ *   the v typed alleles holds k counted ones.  Outside max(0, n_g - (v - x)) <= k <= min(n_g, x) the weight is the exact double
+ *   +0.0; where v = n_g the row is exactly the indicator of k = x (1.0 there, no rounding).  The evaluation is pinned in
+ *   csrc/host/host_sfs.h (the same text runs on the device and on the host, without FMA contraction): a recurrence outwards
+ *   from the mode, normalised by the sum of the support added in ascending k.  With u = 2^-53, an entry whose exact value is at
+ *   least 2^-1000 is within (9 n_g + 4) u of it, relatively (the header counts the roundings); a smaller one is a non-negative
+ *   double below 2^-999, possibly +0.0, without a relative bound (the recurrence may have passed through subnormal values).
+ * Blocks: block b covers the loci lo[b] .. hi[b]-1, the contract of tpg_window_stats and tpg_f2_blocks: a block may be empty,
+ *   blocks need not be disjoint; lo > hi or a block outside [0, m]: TPG_EINVAL; nb == 0: TPG_OK, nothing written; nb >
+ *   TPG_SFS_MAX_BLOCKS: TPG_EINVAL (split the list).  The whole view is the block (0, m).
+ * Outputs, each may be NULL, host or device memory:
+ *   sfs     (double, W x nb, column-major)       sfs[o_g + k, b] = sum_{j in b} t(j,g) h(j,g,k)
+ *   n_used1 (int64, G x nb)                      sum_{j in b} t(j,g)
+ *   jsfs    (double, W x W x nb, column-major)   J[o_g1 + a, o_g2 + c, b] = sum_{j in b} t(j,g1) t(j,g2) h(j,g1,a) h(j,g2,c)
+ *           for ALL g1, g2: block (g1, g2) is the joint spectrum of the pair over the loci usable in both; the diagonal blocks
+ *           hold the same sum with g1 = g2 (defined, though not a spectrum).  J is symmetric bit for bit.
+ *   n_used2 (int64, G x G x nb)                  sum_{j in b} t(j,g1) t(j,g2)
+ * Accuracy: the integer outputs are exact.  Every term of sfs and jsfs is non-negative and the sums run on the FP64 matrix
+ *   cores as chains over the block's loci, cut into tpg_sfs_segments(hi - lo, W) <= 64 partial sums that are added in ascending
+ *   order.  Whatever order the matrix core adds the four products of a step in, a term passes through at most
+ *   L = hi - lo additions of its chain and 63 of the partial sums, one rounding for its product and 2 (9 n + 4) for its two
+ *   weights, n = max n_g.  So a cell whose exact value is at least 2^-900 is within
+ *       TPG_SFS_CELL_ROUNDINGS(n, L) u = (18 n + L + 80) 2^-53, relatively,
+ *   of the exact rational value of the definition (8 + 64 + 1 + L roundings, the rest for second-order terms and for terms
+ *   below 2^-1000, which add at most L 2^-999 absolutely).  Where every usable locus of a cell has v = n_g -- complete data, or
+ *   proj = 0 with any pattern of missingness -- every term is 0 or 1 and the cell is the exact integer count as a double,
+ *   whatever the order of the sum.
+ * Determinism: a cell depends on (lo, hi, g1, g2, proj, keep, flip) alone -- not on nb, on the block's place in the list or on
+ *   launch geometry -- and two calls give the same bits.  No floating-point atomics (n_used adds integers).
+ * Scratch: the staged operand (at most 128 MiB, or one chunk of TPG_SFS_CHUNK_LOCI loci x the padded width if that is more:
+ *   2.1 MiB at W = 4096) plus the partial tiles (32 KiB each: at most 2048 of them, or one block's if that is more: 2145 at
+ *   W = 4096) plus tables of a few hundred KiB: under 200 MiB whatever m and nb are.  On any error the caller's outputs are
+ *   untouched. */
+#define TPG_SFS_MAX_WIDTH 4096
+#define TPG_SFS_MAX_BLOCKS 16777215
+#define TPG_SFS_CELL_ROUNDINGS(n, L) (18 * (int64_t)(n) + (int64_t)(L) + 80)
+/* loci staged at a time per partial sum, in ascending order from the start of its segment (results do not depend on it; the
+ * tests put block lengths around it) */
+#define TPG_SFS_CHUNK_LOCI 64
+int64_t tpg_sfs_chunk_loci(void);
+/* the split rule: how many partial sums a block of that length is cut into at width W (a function of the two alone):
+ * min(max(1, ceil(block_len / 1024)), min(64, max(1, 1024 / T))), T = the 64 x 64 tiles of the upper triangle of the
+ * (W + 1)-wide operand; segments are equal multiples of TPG_SFS_CHUNK_LOCI loci, the last ones shorter or empty.
+ * block_len < 0 or W outside [2, TPG_SFS_MAX_WIDTH]: -1 */
+int64_t tpg_sfs_segments(int64_t block_len, int64_t W);
+/* host only, no context: the bytes tpg_sfs_blocks takes from the device pool as scratch (beyond the view's count table and
+ * the device copies of arguments and outputs the caller keeps in host memory); the call checks its own allocations against
+ * it.  want_joint = jsfs is asked for.  A bad size: -1 */
+int64_t tpg_sfs_scratch_bytes(int64_t m, int ngroups, int64_t W, int64_t nb, int want_joint);
+/* host only, no context: csrc/host/host_sfs.h on one (x, v, n): h[0 .. n].  Not 0 <= x <= v, 1 <= n <= v, v < 2^31: TPG_EINVAL */
+int tpg_sfs_project_row(int64_t x, int64_t v, int64_t n, double* h);
+int tpg_sfs_blocks(tpg_ctx* ctx, const tpg_view* v, const int32_t* groupIds0, int ngroups, const double* ploidy,
+                   const int32_t* proj, const uint8_t* keep, const uint8_t* flip, const int64_t* lo, const int64_t* hi, int64_t nb,
+                   double* sfs, int64_t* n_used1, double* jsfs, int64_t* n_used2);
+
 /* ---- admixture (gt_admixture, R/gt_admixture.R:62-100: the reference exports the panel to PLINK, runs an outside `admixture`
  * binary and reads its .Q / .P files back; ADMIXTURE is not part of the reference's sources and nothing pins it, so the model
  * and the algorithm are defined HERE: the plain EM of Tang et al. 2005 (FRAPPE), the fixed-point map that Alexander, Novembre

@@ -212,6 +212,12 @@ PROTOTYPES = {
     "tpg_f2_chunk_loci": (i64, []),
     "tpg_f2_blocks": (ci, [vp, vp, vp, ci, vp, P(F2Params), vp, vp, i64, vp, vp, vp, vp, vp]),
     "tpg_f4_jackknife": (ci, [vp, ci, i64, vp, vp, i64, vp, vp, vp]),
+    # ---- site frequency spectra
+    "tpg_sfs_chunk_loci": (i64, []),
+    "tpg_sfs_segments": (i64, [i64, i64]),
+    "tpg_sfs_scratch_bytes": (i64, [i64, ci, i64, i64, ci]),
+    "tpg_sfs_project_row": (ci, [i64, i64, i64, vp]),
+    "tpg_sfs_blocks": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
     # ---- admixture
     "tpg_admix_params_default": (ci, [P(AdmixParams)]),
     "tpg_admix_chunk_loci": (i64, []),

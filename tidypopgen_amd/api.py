@@ -1806,6 +1806,194 @@ def f3_from_f2_blocks(f2, block_lengths, triples) -> dict:
     return f4_from_f2_blocks(f2, block_lengths, np.stack([t[:, 0], t[:, 1], t[:, 0], t[:, 2]], axis=1))
 
 
+# include/tpg.h "site frequency spectra": loci staged at a time (results do not depend on it) and the widest operand
+SFS_CHUNK_LOCI = int(lib.tpg_sfs_chunk_loci()) if hasattr(lib, "tpg_sfs_chunk_loci") else 0
+SFS_MAX_WIDTH = 4096  # TPG_SFS_MAX_WIDTH
+
+
+def sfs_segments(block_len: int, W: int) -> int:
+    """tpg_sfs_segments: the partial sums a block of block_len loci is cut into at width W (-1: a bad size)"""
+    return int(lib.tpg_sfs_segments(int(block_len), int(W)))
+
+
+def sfs_scratch_bytes(m: int, ngroups: int, W: int, nb: int, joint: bool = True) -> int:
+    """tpg_sfs_scratch_bytes: the device scratch of one sfs_blocks call (-1: a bad size)"""
+    return int(lib.tpg_sfs_scratch_bytes(int(m), int(ngroups), int(W), int(nb), int(bool(joint))))
+
+
+def sfs_project_row(x: int, v: int, n: int) -> np.ndarray:
+    """tpg_sfs_project_row (host arithmetic, no device): the hypergeometric weights h[0 .. n] of x counted alleles among v typed
+    ones projected to n, by the routine the device runs (csrc/host/host_sfs.h)"""
+    h = np.full(max(int(n), 0) + 1, np.nan)
+    check(lib.tpg_sfs_project_row(int(x), int(v), int(n), _ptr(h)))
+    return h
+
+
+def _sfs_mask(x, m, name):
+    if x is None or isinstance(x, (int, np.integer)):
+        return x  # nothing, or a device pointer
+    a = np.ascontiguousarray(np.asarray(x) != 0, dtype=np.uint8)
+    if a.shape != (m,):
+        raise ValueError(f"{name} must have one entry per locus of the view")
+    return a
+
+
+def sfs_blocks(v: View, groupIds, ngroups, lo, hi, proj=None, keep=None, flip=None, joint=True, ploidy=None) -> dict:
+    """tpg_sfs_blocks (include/tpg.h "site frequency spectra") on explicit 0-based half-open locus ranges -> dict(sfs (W, nb),
+    n_used1 (G, nb), and with joint jsfs (W, W, nb), n_used2 (G, G, nb); n (G): the projection sizes, offsets (G + 1): o_g and
+    W).  groupIds=None: one group.  proj: n_g per group, 0 or None = the group's 2 N_g."""
+    if groupIds is None:
+        gid, G = None, 1
+        sizes = np.array([v.n], dtype=np.int64)
+    else:
+        gid, G = _i32(groupIds), int(ngroups)
+        if len(gid) != v.n:
+            raise ValueError("groupIds must have one entry per individual of ind_row")
+        ok = (gid >= 0) & (gid < max(G, 1))
+        sizes = np.bincount(gid[ok], minlength=max(G, 1))[:max(G, 1)].astype(np.int64)
+    pj = None if proj is None else np.ascontiguousarray(np.broadcast_to(np.asarray(proj, dtype=np.int32), (max(G, 1),)))
+    n = 2 * sizes if pj is None else np.where(pj == 0, 2 * sizes, pj.astype(np.int64))
+    offsets = np.r_[0, np.cumsum(np.maximum(n, 0) + 1)].astype(np.int64)
+    W = int(min(offsets[-1], SFS_MAX_WIDTH))  # (a wider request is refused by the library before it writes anything)
+    lo, hi = np.ascontiguousarray(lo, dtype=np.int64), np.ascontiguousarray(hi, dtype=np.int64)
+    nb = len(lo)
+    if lo.ndim != 1 or hi.shape != lo.shape:
+        raise ValueError("lo and hi must have one entry per block")
+    kp, fl = _sfs_mask(keep, v.m, "keep"), _sfs_mask(flip, v.m, "flip")
+    pl = _f64(ploidy)
+    if pl is not None and len(pl) != v.n:
+        raise ValueError("ploidy must have one entry per individual of ind_row")
+    Gd = max(G, 1)
+    out = dict(sfs=np.zeros((W, nb), order="F"), n_used1=np.zeros((Gd, nb), dtype=np.int64, order="F"))
+    if joint:
+        out.update(jsfs=np.zeros((W, W, nb), order="F"), n_used2=np.zeros((Gd, Gd, nb), dtype=np.int64, order="F"))
+    check(lib.tpg_sfs_blocks(v.ctx.h, v.h, _ptr(gid), G, _ptr(pl), _ptr(pj), _ptr(kp), _ptr(fl), _ptr(lo), _ptr(hi), nb,
+                             _ptr(out["sfs"]), _ptr(out["n_used1"]), _ptr(out.get("jsfs")), _ptr(out.get("n_used2"))))
+    out.update(n=n.astype(np.int64), offsets=offsets)
+    return out
+
+
+def sfs_fold(sfs) -> np.ndarray:
+    """Fold a 1-D spectrum of n + 1 entries (host): folded[k] = sfs[k] + sfs[n - k] for k < n / 2, the middle entry (n even)
+    stays once, the entries above are 0"""
+    s = np.asarray(sfs, dtype=np.float64)
+    if s.ndim != 1 or len(s) < 2:
+        raise ValueError("sfs must be a vector of n + 1 >= 2 entries")
+    n = len(s) - 1
+    out = np.zeros_like(s)
+    for k in range(n // 2 + 1):
+        out[k] = s[k] + s[n - k] if 2 * k < n else s[k]
+    return out
+
+
+def jsfs_fold(J) -> np.ndarray:
+    """Fold a joint spectrum (n1 + 1) x (n2 + 1) (host; dadi's convention, recalled): an entry with a + c > (n1 + n2) / 2 is
+    added to (n1 - a, n2 - c) and set to 0; the entries on the line a + c = (n1 + n2) / 2 become the mean of the two mirror
+    cells"""
+    J = np.asarray(J, dtype=np.float64)
+    if J.ndim != 2 or min(J.shape) < 2:
+        raise ValueError("J must be (n1 + 1) x (n2 + 1)")
+    n1, n2 = J.shape[0] - 1, J.shape[1] - 1
+    a, c = np.meshgrid(np.arange(n1 + 1), np.arange(n2 + 1), indexing="ij")
+    mirror = J[::-1, ::-1]
+    tot2 = 2 * (a + c)
+    return np.where(tot2 < n1 + n2, J + mirror, np.where(tot2 == n1 + n2, (J + mirror) / 2.0, 0.0))
+
+
+def sfs_stats(sfs) -> dict:
+    """Summary statistics of a real-valued unfolded spectrum of n + 1 entries (host, plain double, every sum in ascending k in
+    the order written): S = sum_{0<k<n} sfs[k], theta_w = S / a1, theta_pi = sum k (n - k) sfs[k] / C(n, 2), theta_h =
+    sum k^2 sfs[k] / C(n, 2), fay_wu_h = theta_pi - theta_h, tajimas_d with the constants of the Tajima section of include/tpg.h"""
+    s = np.asarray(sfs, dtype=np.float64)
+    if s.ndim != 1 or len(s) < 3:
+        raise ValueError("sfs must be a vector of n + 1 >= 3 entries")
+    n = len(s) - 1
+    S = pi = th = 0.0
+    for k in range(1, n):
+        x = float(s[k])
+        S = S + x
+        pi = pi + float(k * (n - k)) * x
+        th = th + float(k * k) * x
+    c2 = float(n * (n - 1) // 2)
+    a1 = a2 = 0.0
+    for i in range(1, n):
+        a1 += 1.0 / float(i)
+        a2 += 1.0 / (float(i) * float(i))
+    nd = float(n)
+    e1 = ((nd + 1) / (3 * (nd - 1)) - 1 / a1) / a1
+    e2 = (2 * (nd * nd + nd + 3) / (9 * nd * (nd - 1)) - (nd + 2) / (nd * a1) + a2 / (a1 * a1)) / (a1 * a1 + a2)
+    theta_pi, theta_h = pi / c2, th / c2
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = (np.float64(theta_pi) - np.float64(S) / a1) / np.sqrt(np.float64(e1 * S + e2 * S * (S - 1)))
+    return dict(n=n, S=S, theta_w=S / a1, theta_pi=theta_pi, theta_h=theta_h, fay_wu_h=theta_pi - theta_h, tajimas_d=float(d))
+
+
+def _sfs_cut(r, G):
+    return [[r["sfs"][r["offsets"][g]:r["offsets"][g + 1], b] for g in range(G)] for b in range(r["sfs"].shape[1])]
+
+
+def pop_sfs(X: FBM, ind_row=None, ind_col=None, groupIds=None, ngroups: int = 0, proj=None, flip=None, keep=None,
+            folded: bool = False, ploidy=None) -> dict:
+    """The site frequency spectrum of every group over the whole view, projected to proj[g] alleles (None or 0: the group's
+    2 N_g; loci typed at fewer alleles are left out of that group).  flip marks the loci whose REFERENCE allele is the derived
+    one.  -> dict(sfs: one vector of n_g + 1 entries per group, n_used: loci used per group, n: the projection sizes)"""
+    v = View(X, ind_row, ind_col)
+    G = 1 if groupIds is None else int(ngroups)
+    r = sfs_blocks(v, groupIds, ngroups, [0], [v.m], proj, keep, flip, joint=False, ploidy=ploidy)
+    spectra = _sfs_cut(r, G)[0]
+    if folded:
+        spectra = [sfs_fold(s) for s in spectra]
+    return dict(sfs=[np.array(s) for s in spectra], n_used=r["n_used1"][:, 0].copy(), n=r["n"])
+
+
+def sfs_block_ranges(chromosome, block_size: int):
+    """Bootstrap blocks of block_size consecutive loci that do not cross a chromosome border, as 0-based half-open (lo, hi)"""
+    chrom = np.asarray(chromosome)
+    if chrom.ndim != 1 or int(block_size) < 1:
+        raise ValueError("chromosome must be a vector and block_size positive")
+    m, bs = len(chrom), int(block_size)
+    starts = np.flatnonzero(np.r_[True, chrom[1:] != chrom[:-1]]) if m else np.zeros(0, dtype=np.int64)
+    lo, hi = [], []
+    for a, b in zip(starts, np.r_[starts[1:], m]):
+        for s in range(int(a), int(b), bs):
+            lo.append(s)
+            hi.append(min(s + bs, int(b)))
+    return np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
+
+
+def pairwise_pop_jsfs(X: FBM, ind_row, ind_col, groupIds, ngroups: int, proj=None, flip=None, keep=None, folded: bool = False,
+                      blocks=None, chromosome=None, block_size=None, ploidy=None) -> dict:
+    """The joint site frequency spectrum of every pair of groups g1 < g2 (combn2 order) over the loci usable in both, each
+    projected to its proj[g].  -> dict(pairs (2 x P, 1-based), jsfs: one (n_g1 + 1) x (n_g2 + 1) array per pair, n_used: loci
+    per pair, n).  With blocks=(lo, hi), or chromosome and block_size (sfs_block_ranges), the arrays are per block -- (n_g1 + 1)
+    x (n_g2 + 1) x nb and n_used (P, nb), with lo and hi -- for a block bootstrap."""
+    v = View(X, ind_row, ind_col)
+    G = int(ngroups)
+    per_block = blocks is not None or chromosome is not None
+    if blocks is not None:
+        lo, hi = blocks
+    elif chromosome is not None:
+        if block_size is None or len(chromosome) != v.m:
+            raise ValueError("chromosome needs one entry per locus of ind_col and a block_size")
+        lo, hi = sfs_block_ranges(chromosome, block_size)
+    else:
+        lo, hi = [0], [v.m]
+    r = sfs_blocks(v, groupIds, G, lo, hi, proj, keep, flip, joint=True, ploidy=ploidy)
+    o, pairs = r["offsets"], combn2(G)
+    js, used = [], []
+    for a, b in pairs.T - 1:
+        J = r["jsfs"][o[a]:o[a + 1], o[b]:o[b + 1], :]
+        if folded:
+            J = np.stack([jsfs_fold(J[:, :, k]) for k in range(J.shape[2])], axis=2) if J.shape[2] else J
+        js.append(np.array(J) if per_block else np.array(J[:, :, 0]))
+        used.append(r["n_used2"][a, b, :] if per_block else r["n_used2"][a, b, 0])
+    out = dict(pairs=pairs, jsfs=js, n_used=np.array(used, dtype=np.int64).reshape((pairs.shape[1], -1) if per_block else (-1,)),
+               n=r["n"])
+    if per_block:
+        out.update(lo=np.asarray(lo, dtype=np.int64), hi=np.asarray(hi, dtype=np.int64))
+    return out
+
+
 # include/tpg.h "admixture": loci per partial sum of the Q update (results do not depend on launch geometry)
 ADMIX_CHUNK_LOCI = int(lib.tpg_admix_chunk_loci()) if hasattr(lib, "tpg_admix_chunk_loci") else 0
 
