@@ -979,6 +979,52 @@ int tpg_windows_pairwise_pop_fst(tpg_ctx* ctx, const tpg_view* v, const int32_t*
                                  const uint8_t* pad_na, int64_t nw, int min_loci, double* fst, double* mean_num,
                                  double* mean_den, int32_t* n_num, int32_t* n_den);
 
+/* ---- Fst under relabelings (pairwise_pop_fst_test: is a pairwise Fst different from zero?  The permutation test of Arlequin,
+ * hierfstat and StAMPP: shuffle the individuals between the populations, recompute Fst, see where the observed value falls.  The
+ * reference has nothing of the kind, so everything is defined HERE) --------------------------------------------------------------
+ * Labels: labels is R x n row-major in host memory; labels[r][i] in {-1, 0 .. ngroups-1} is the group of individual i under
+ *        relabeling r, -1 = the individual is outside relabeling r.  A relabeling may leave a group empty.
+ * Per-locus terms: for relabeling r, pair (g1, g2) and locus j, num and den are exactly the doubles tpg_pairwise_pop_fst(...,
+ *        return_num_dem = 1) writes for that method on the view that keeps only the individuals with label >= 0, grouped by those
+ *        labels: integer counts per (locus, group), then the statements of fst_stage and fst_terms<METHOD, false>
+ *        (csrc/fst_terms.h) in IEEE double without FMA contraction; for Hudson e = (p (1 - p)) / (n - 1) as tpg_fst_kernel stages
+ *        it.  A locus is KEPT for a pair when num and den are both non-NaN; n_kept counts those loci.  (An empty group has
+ *        p = 0 / 0: none of its loci is kept, its sums are +0.0, n_kept = 0 and the ratio is NaN.)
+ * Sums:  with U = TPG_FSTPERM_UNIT_LOCI (a divisor of 32) and S = TPG_FSTPERM_SPAN_LOCI (a multiple of 128): the kept terms of
+ *        unit k, loci k U .. k U + U - 1, are added in ascending locus order from 0.0; the unit sums of span s, loci s S ..
+ *        s S + S - 1, are added in ascending order from 0.0 (a unit without kept terms adds its 0.0); the span sums are added in
+ *        ascending order from 0.0.  sum_num and sum_den are added separately over the same kept set.  No floating-point atomics.
+ *        A sum is within m 2^-52 sum |x_j| of the exact sum of its kept doubles.
+ * Determinism: the outputs of a relabeling depend on the view, its label row, ngroups, the pair list and the method alone: not on
+ *        R, on its place in the list, on the other rows, on the library's internal batching or on launch geometry.  Two calls
+ *        give the same bits.
+ * Limits and errors: diploid codes only (there is no ploidy argument).  2 <= ngroups <= TPG_FSTPERM_MAX_GROUPS, because the
+ *        classes of a relabeling live in the accumulators of one workgroup; above it TPG_EINVAL with a message that points to the
+ *        pairwise scheme (two groups per relabeling).  A label outside [-1, ngroups), a pair outside [1, ngroups] or with
+ *        g1 == g2, P < 1, R < 0, an unknown method: TPG_EINVAL, nothing written.  R == 0: TPG_OK, nothing written.
+ *        n >= 2^24: TPG_EUNSUPPORTED, as for the grouped counts.  The library walks R in internal batches, so its device scratch is
+ *        bounded independently of R: tpg_fst_relabel_scratch_bytes (host only; a bad size: -1).
+ * Outputs: sum_num, sum_den (doubles) and n_kept (may be NULL), each R x P row-major, host memory.
+ * tpg_fst_perm_labels (host only, no context, no GPU) is the r-th relabeling as a pure function of its arguments.  With
+ *        M = tpg_mix64 (see "simple imputation") and 64-bit unsigned arithmetic: the eligible set E is e_0 < e_1 < ... in ascending
+ *        index -- scheme 0 "pairwise": the individuals of groups a and b (0-based ids, a != b); scheme 1 "global": everybody.
+ *        key(i) = M(seed ^ M((r << 32) + i)); sigma is E sorted by (key, index); individual sigma_t receives the group of e_t.
+ *        r = 0 is the identity and is not hashed.  Scheme 0 writes a -> 0, b -> 1 and everybody else -> -1 (use it with
+ *        ngroups = 2 and the pair (1, 2)); scheme 1 writes the groups as they are.  0 <= r < 2^31, n < 2^31; a bad argument:
+ *        TPG_EINVAL.
+ * Not offered: block-bootstrap confidence intervals over loci (the span sums are the hook), pseudohaploids, tpg_stream_* /
+ *        tpg_multi_* forms, an R shim entry. */
+#define TPG_FSTPERM_UNIT_LOCI 8
+#define TPG_FSTPERM_SPAN_LOCI 512
+#define TPG_FSTPERM_MAX_GROUPS 64
+int tpg_fst_relabel_sums(tpg_ctx* ctx, const tpg_view* v, const int32_t* labels, int64_t R, int ngroups, int method,
+                         const int32_t* pairs1, int P, double* sum_num, double* sum_den, int64_t* n_kept);
+int64_t tpg_fstperm_unit_loci(void);
+int64_t tpg_fstperm_span_loci(void);
+int64_t tpg_fst_relabel_scratch_bytes(int64_t n, int64_t m, int ngroups, int P);
+int tpg_fst_perm_labels(int64_t n, const int32_t* groupIds0, int ngroups, int scheme, int a, int b, uint64_t seed, int64_t r,
+                        int32_t* out);
+
 /* ---- pairwise individual matrices (IBS / KING / allele sharing / GRM) ---- */
 /* Accumulators for the four integer cross-products V=vv', D=dd', H=hh', A=hv'
  * (v valid, d = dosage-1, h heterozygous), from which every count matrix of

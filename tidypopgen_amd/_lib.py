@@ -254,6 +254,12 @@ PROTOTYPES = {
     "tpg_winfst_chunk_loci": (i64, []),
     "tpg_windows_fst_scratch_bytes": (i64, [i64, ci, ci, i64]),
     "tpg_windows_pairwise_pop_fst": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, i64, ci, vp, vp, vp, vp, vp]),
+    # ---- Fst under relabelings
+    "tpg_fst_relabel_sums": (ci, [vp, vp, vp, i64, ci, ci, vp, ci, vp, vp, vp]),
+    "tpg_fstperm_unit_loci": (i64, []),
+    "tpg_fstperm_span_loci": (i64, []),
+    "tpg_fst_relabel_scratch_bytes": (i64, [i64, i64, ci, ci]),
+    "tpg_fst_perm_labels": (ci, [i64, vp, ci, ci, ci, ci, u64, i64, vp]),
     # ---- pairwise individual matrices
     "tpg_pairwise_buffer_bytes": (sz, [i64]),
     "tpg_pairwise_create": (ci, [vp, i64, vp, vp]),

@@ -1503,6 +1503,95 @@ def windows_fst(v: View, groupIds, ngroups, lo, hi, pad_na=None, min_loci: int =
     return out
 
 
+def fst_relabel_sums(v: View, labels, ngroups: int, pairs=None, method: str = "Hudson") -> dict:
+    """tpg_fst_relabel_sums (include/tpg.h "Fst under relabelings"): labels is R x n, -1 = outside the relabeling; pairs is
+    2 x P, 1-based (default: every pair).  -> dict(sum_num, sum_den (R, P), n_kept (R, P int64), fst = sum_num / sum_den)."""
+    if method not in FST_METHODS:
+        raise ValueError("'arg' should be one of 'Hudson', 'Nei87', 'WC84'")
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim == 1:
+        lab = lab.reshape(1, -1)
+    if lab.ndim != 2 or lab.shape[1] != v.n:
+        raise ValueError("labels must have one column per individual of the view")
+    R = lab.shape[0]
+    pairs = combn2(ngroups) if pairs is None else np.asarray(pairs, dtype=np.int32)
+    pairs_c = np.ascontiguousarray(pairs.T)  # (P, 2) row-major == 2 x P column-major
+    P = pairs_c.shape[0]
+    sn, sd, nk = np.zeros((R, P)), np.zeros((R, P)), np.zeros((R, P), dtype=np.int64)
+    check(lib.tpg_fst_relabel_sums(v.ctx.h, v.h, _ptr(lab), R, int(ngroups), FST_METHODS[method], _ptr(pairs_c), P, _ptr(sn), _ptr(sd),
+                                   _ptr(nk)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return dict(sum_num=sn, sum_den=sd, n_kept=nk, fst=sn / sd)
+
+
+FST_PERM_SCHEMES = {"pairwise": 0, "global": 1}
+
+
+def fst_perm_labels(n: int, groupIds, ngroups: int, scheme, a: int, b: int, seed: int, r: int) -> np.ndarray:
+    """tpg_fst_perm_labels: the r-th relabeling of the scheme ("pairwise" / 0: groups a and b, 0-based, become labels 0 and 1,
+    everybody else -1; "global" / 1: everybody keeps a group); r = 0 is the identity.  Host only."""
+    gid = _i32(groupIds)
+    if gid is None or gid.shape != (n,):
+        raise ValueError("groupIds must have one entry per individual")
+    out = np.zeros(n, dtype=np.int32)
+    sch = FST_PERM_SCHEMES[scheme] if isinstance(scheme, str) else int(scheme)
+    check(lib.tpg_fst_perm_labels(int(n), _ptr(gid), int(ngroups), sch, int(a), int(b), int(seed) & 0xFFFFFFFFFFFFFFFF, int(r), _ptr(out)))
+    return out
+
+
+def fst_perm_pvalue(fst_obs, fst_perm):
+    """the permutation p-value (host): fst_obs (P), fst_perm (n_perm, P) -> (p, n_valid); n_valid = the number of finite permuted
+    values, p = (1 + #{finite permuted >= observed}) / (1 + n_valid), NaN where the observed value is not finite"""
+    obs = np.atleast_1d(np.asarray(fst_obs, dtype=np.float64))
+    perm = np.asarray(fst_perm, dtype=np.float64).reshape(-1, obs.shape[0])
+    fin = np.isfinite(perm)
+    n_valid = fin.sum(axis=0).astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        ge = (fin & (perm >= obs[None, :])).sum(axis=0)
+    p = (1.0 + ge) / (1.0 + n_valid)
+    return np.where(np.isfinite(obs), p, np.nan), n_valid
+
+
+def pairwise_pop_fst_test(X: FBM, ind_row, ind_col, groupIds, ngroups: int, method: str = "Hudson", n_perm: int = 999, seed: int = 0,
+                          scheme: str = "pairwise", pairwise_combn=None, return_perm: bool = False, max_rows: int = 4096) -> dict:
+    """Permutation test of pairwise Fst (no counterpart in the reference).  scheme = "pairwise": for every pair the individuals
+    of its two populations are shuffled between them (rows r = 0 .. n_perm of tpg_fst_perm_labels scheme 0, two groups per
+    relabeling), all pairs' rows going down in batches of at most max_rows; "global": everybody is shuffled, one label matrix of
+    1 + n_perm rows with ngroups groups (at most 64).  -> dict(fst_tot, p_value, n_valid (P)), with return_perm also perm_fst
+    (n_perm, P).  fst_tot is row 0, the identity, through the same kernel, so that ties compare like with like."""
+    if method not in FST_METHODS:
+        raise ValueError("'arg' should be one of 'Hudson', 'Nei87', 'WC84'")
+    if scheme not in FST_PERM_SCHEMES:
+        raise ValueError("scheme must be 'pairwise' or 'global'")
+    if n_perm < 1 or max_rows < 1:
+        raise ValueError("n_perm and max_rows must be positive")
+    v = View(X, ind_row, ind_col)
+    gid = _i32(groupIds)
+    pairs = combn2(ngroups) if pairwise_combn is None else np.asarray(pairwise_combn, dtype=np.int32).reshape(2, -1)
+    P, nr = pairs.shape[1], 1 + int(n_perm)
+    fst = np.zeros((nr, P))
+    if scheme == "global":
+        if ngroups > 64:
+            raise ValueError("scheme = 'global' holds at most 64 groups in one relabeling: use scheme = 'pairwise'")
+        for r0 in range(0, nr, max_rows):
+            lab = np.stack([fst_perm_labels(v.n, gid, ngroups, 1, 0, 0, seed, r) for r in range(r0, min(nr, r0 + max_rows))])
+            fst[r0:r0 + len(lab)] = fst_relabel_sums(v, lab, ngroups, pairs, method)["fst"]
+    else:
+        one = np.array([[1], [2]], dtype=np.int32)
+        todo = [(k, r) for k in range(P) for r in range(nr)]
+        for t0 in range(0, len(todo), max_rows):
+            part = todo[t0:t0 + max_rows]
+            lab = np.stack([fst_perm_labels(v.n, gid, ngroups, 0, int(pairs[0, k]) - 1, int(pairs[1, k]) - 1, seed, r) for k, r in part])
+            f = fst_relabel_sums(v, lab, 2, one, method)["fst"][:, 0]
+            for (k, r), x in zip(part, f):
+                fst[r, k] = x
+    p, n_valid = fst_perm_pvalue(fst[0], fst[1:])
+    out = dict(fst_tot=fst[0].copy(), p_value=p, n_valid=n_valid)
+    if return_perm:
+        out["perm_fst"] = fst[1:].copy()
+    return out
+
+
 def windows_nwise_pop_pbs(X: FBM, ind_row, ind_col, groupIds, ngroups: int, chromosome, position=None, ploidy=None,
                           fst_method: str = "Hudson", return_fst: bool = False, window_size=None, step_size=None, size_unit="snp",
                           min_loci=1, complete=False, triplets=None):
