@@ -5,9 +5,10 @@
 //    owns locus r and popcounts its own dwords, so the only cross-lane step is one lane^32
 //    exchange at the end.  HBM-bound: n/4 bytes per locus in, 16 B out.  (A view made by the fast pack kernel carries
 //    per-chunk counts from the pack itself: tpg_loci_counts_sum_kernel adds those up and L is not read.)
-//  * tpg_grouped_counts_kernel: per locus x class counts as an int8 MFMA contraction over
+//  * tpg_grouped_counts_kernel: per locus x class counts as an FP4 MFMA contraction over
 //    individuals, D[locus][class] = sum_i plane[i][locus] * onehot[i][class] for the planes
-//    {het, hom-alt, valid}.  Exact in int32, arbitrary class assignment, no atomics.
+//    {bit 0, bit 1, both} of the 2-bit code (het, hom-alt and valid follow by subtraction).  The products are
+//    0 / 1 and the sums FP32: exact below 2^24 individuals.  Arbitrary class assignment, no atomics.
 //  * finalize kernels turn counts into the doubles the reference returns
 //    (src/alt_freq_dip_pseudo_cpp.cpp:43-57, src/grouped_alt_freq_dip_pseudo_cpp.cpp:46-55,
 //    src/grouped_missingness_cpp.cpp:23-31, src/grouped_summaries_dip_pseudo_cpp.cpp:50-57).
