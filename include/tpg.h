@@ -1134,6 +1134,79 @@ int tpg_resident_drop(tpg_ctx* ctx);
  * pending, at once otherwise */
 int tpg_increment_as_note_narrow_block(tpg_ctx* ctx, double* K, int64_t n);
 
+/* ---- AMOVA (gt_amova: the analysis of molecular variance of Excoffier, Smouse & Quattro 1992 as Arlequin, pegas, poppr and ade4
+ * run it: the squared genotype distances between individuals are partitioned among regions, among populations within regions and
+ * within populations, and each Phi is tested by its own permutation scheme.  The reference has nothing of the kind, so everything
+ * is defined HERE; the formulas are recalled from Excoffier et al. 1992, not pinned by a run of Arlequin) -------------------------
+ * Squared distance, tpg_pairwise_sqdist: with d = dosage - 1, h = heterozygous, v = typed and the accumulators V = vv', D = dd',
+ *        A = hv': raw_ij = sum over the loci both i and j are typed at of (d_i - d_j)^2 = 2 V_ij - A_ij - A_ji - 2 D_ij (sum d_i^2 v_j
+ *        = V_ij - A_ij), an exact integer, 0 on the diagonal.  type TPG_SQDIST_RAW: raw (m is ignored).  TPG_SQDIST_ADJUSTED:
+ *        (raw m) / V_ij -- the product as a 64-bit integer, converted to double, then one IEEE division by (double)V_ij -- NaN
+ *        where V_ij = 0; 1 <= m <= 2^30.  Needs TPG_PW_V | TPG_PW_D | TPG_PW_A (TPG_PW_FOR_KING), else TPG_EINVAL.  out: n x n
+ *        column-major doubles, host or device memory.
+ * Class sums, tpg_class_sums: A is n x n column-major doubles in host or device memory, symmetric or not.  labels is R x n
+ *        row-major in host memory, labels[r][i] in {-1, 0 .. nclasses-1}; -1 = individual i is outside labeling r; a class may be
+ *        empty.  sums is R x nclasses row-major in host memory: sums[r][c] = sum of A[i + j n] over all ordered pairs (i, j) with
+ *        labels[r][i] = labels[r][j] = c, the diagonal included.
+ * Order: with C = TPG_CLASSSUM_CHUNK: the partial of row i over chunk k (columns k C .. k C + C - 1) adds the included A[i + j n]
+ *        in ascending j from 0.0; t(r, i) adds the chunk partials of row i in ascending k from 0.0 (a chunk without an included
+ *        column adds its 0.0); sums[r][c] adds t(r, i) over the rows i of class c in ascending i from 0.0.  IEEE double, no FMA, no
+ *        floating-point atomics.  A NaN in A reaches exactly the classes that contain that pair; an empty class gives +0.0.
+ *        If A holds integers and every partial sum stays below 2^53, every order gives the exact integer: for raw distances of m
+ *        loci that holds when 4 m n^2 < 2^53.  Otherwise a sum is within k 2^-52 sum |x| of the exact sum of its k terms.
+ * Determinism: a row of sums depends on A, its own label row and nclasses alone: not on R, on its place in the list, on the
+ *        library's internal passes and batches or on launch geometry.  Two calls give the same bits.
+ * Limits and errors: 1 <= nclasses <= TPG_CLASSSUM_MAX_CLASSES, 1 <= n <= 2^20, a label outside [-1, nclasses), R < 0:
+ *        TPG_EINVAL, nothing written.  R == 0: TPG_OK, nothing written.  The library walks R in internal passes, so its device
+ *        scratch (A itself, when it comes from the host, not counted) is bounded independently of R:
+ *        tpg_class_sums_scratch_bytes (host only; a bad size: -1).  tpg_classsum_chunk / _tile_rows / _batch: the columns of a
+ *        chunk, the rows of a workgroup and the labelings a workgroup carries (TPG_CLASSSUM_*), for tests that place borders.
+ * tpg_amova_perm_labels (host only, no context, no GPU): the r-th relabeling as a pure function of its arguments.  pop0[n] in
+ *        {-1, 0 .. npop-1} (-1 = outside: stays outside), region_of_pop0[npop] in {0 .. nregion-1}; nregion = 0: no regions, only
+ *        scheme 0, region_of_pop0 and region_of_pop_out may be NULL.  With M = tpg_mix64 and 64-bit unsigned arithmetic,
+ *        key(u) = M(seed ^ M((r << 32) + u)); a shuffle of a set E = e_0 < e_1 < ... of units: sigma = E sorted by (key, index),
+ *        unit sigma_t receives what unit e_t held.  Scheme 0 (tests Phi_ST): E = the individuals with a population, which are
+ *        shuffled among the populations -- the rule and, without -1 labels, the bits of tpg_fst_perm_labels scheme 1.  Scheme 1
+ *        (Phi_SC): the same inside every region separately, E = that region's individuals: nobody leaves a region.  Scheme 2
+ *        (Phi_CT): the populations are the units (u = the population index): population sigma_t receives the region of population
+ *        e_t; pop_out = pop0 and region_of_pop_out changes, so region sizes change.  Schemes 0 and 1 copy region_of_pop0.  r = 0
+ *        is the identity and is not hashed.  Population sizes are preserved.  An empty population, an empty region, an id out of
+ *        range, 0 <= r < 2^31 or n < 2^31 violated: TPG_EINVAL.
+ * tpg_amova_from_sums (host only): one relabeling's numbers -> out[21] = df[4], ssd[4], msd[3], ncoef[3], sigma2[4], phi[3], in
+ *        IEEE double in the statement order below, without FMA contraction.  n_p = pop_size[p] >= 1, W_p = pop_sum[p] and
+ *        R_g = region_sum[g] the class sums, T = total_sum the sum over all ordered included pairs; N = sum n_p, N_g = the
+ *        individuals of region g, P = npop, G = nregion; integer sums (N, N_g, sum n_p^2, sum N_g^2) are exact and converted once.
+ *        SSD_T = T / (2 N); SSD_WP = W_p / (2 n_p) added over p ascending from 0.0; SSD_WR = R_g / (2 N_g) over g ascending.
+ *        x / df is NaN when df = 0.  Rows are (among regions, among populations within regions, within populations, total).
+ *        With regions: df = (G - 1, P - G, N - P, N - 1); ssd = (SSD_T - SSD_WR, SSD_WR - SSD_WP, SSD_WP, SSD_T); msd = ssd / df;
+ *        S1 = n_p^2 / N_g(p) added over p ascending; ncoef = (n, n', n'') = ((N - S1) / (P - G), (S1 - (sum n_p^2) / N) / (G - 1),
+ *        (N - (sum N_g^2) / N) / (G - 1)); s_c = msd_WP; s_b = (msd_AP - s_c) / n; s_a = ((msd_AR - s_c) - n' s_b) / n'';
+ *        s_T = (s_a + s_b) + s_c; sigma2 = (s_a, s_b, s_c, s_T); phi = (Phi_CT, Phi_SC, Phi_ST) = (s_a / s_T, s_b / (s_b + s_c),
+ *        (s_a + s_b) / s_T).
+ *        Without regions (nregion = 0): df = (NaN, P - 1, N - P, N - 1); ssd = (NaN, SSD_T - SSD_WP, SSD_WP, SSD_T);
+ *        ncoef = (n_0, NaN, NaN), n_0 = (N - (sum n_p^2) / N) / (P - 1); s_b = (msd_AP - s_c) / n_0; s_T = s_b + s_c;
+ *        sigma2 = (NaN, s_b, s_c, s_T); phi = (NaN, NaN, Phi_ST = s_b / s_T).
+ *        Negative components and Phi are reported as they come, as Arlequin does.  npop < 1, a population size < 1, a region id
+ *        out of range or an empty region: TPG_EINVAL, nothing written.
+ * Not offered: Mantel tests and PERMANOVA drivers (tpg_class_sums is their kernel), a within-individual level, more than three
+ *        levels, tpg_stream_* / tpg_multi_* forms, an R shim entry, distances other than the squared Euclidean one. */
+#define TPG_SQDIST_RAW 0
+#define TPG_SQDIST_ADJUSTED 1
+#define TPG_CLASSSUM_CHUNK 512
+#define TPG_CLASSSUM_TILE_ROWS 256
+#define TPG_CLASSSUM_BATCH 32
+#define TPG_CLASSSUM_MAX_CLASSES 1024
+int tpg_pairwise_sqdist(tpg_ctx* ctx, const tpg_pairwise* pw, int type, int64_t m, double* out);
+int tpg_class_sums(tpg_ctx* ctx, const double* A, int64_t n, const int32_t* labels, int64_t R, int nclasses, double* sums);
+int64_t tpg_class_sums_scratch_bytes(int64_t n, int64_t R, int nclasses);
+int64_t tpg_classsum_chunk(void);
+int64_t tpg_classsum_tile_rows(void);
+int64_t tpg_classsum_batch(void);
+int tpg_amova_perm_labels(int64_t n, const int32_t* pop0, int npop, const int32_t* region_of_pop0, int nregion, int scheme,
+                          uint64_t seed, int64_t r, int32_t* pop_out, int32_t* region_of_pop_out);
+int tpg_amova_from_sums(int npop, const int64_t* pop_size, const double* pop_sum, int nregion, const int32_t* region_of_pop0,
+                        const double* region_sum, double total_sum, double* out);
+
 /* ---- SNP-block shards over the GPUs of one node -------------------------------------------------
  * The locus axis is the reference's own block axis (R/snp_ibs.R:59-82): a shard is a contiguous range of loci.
  * Per-locus outputs are disjoint slices (no exchange).  What is additive over loci is exchanged by the LIBRARY, over

@@ -8,3 +8,4 @@ from .api import *  # noqa: F401,F403
 from .api import (CODE_012, CODE_IMPUTE_PRED, FBM, Comm, Context, Multi, Pairwise, Roh, ShardedPairwise, View, default_context)  # noqa: F401
 from .api import ibd_genome_length, ibd_segments, pairwise_ibd  # noqa: F401
 from .api import fst_perm_labels, fst_perm_pvalue, fst_relabel_sums, pairwise_pop_fst_test  # noqa: F401
+from .api import DeviceMatrix, amova_from_sums, amova_perm_labels, class_sums, gt_amova, pairwise_sqdist  # noqa: F401

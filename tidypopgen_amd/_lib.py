@@ -285,6 +285,15 @@ PROTOTYPES = {
     "tpg_increment_flush": (ci, [vp]),
     "tpg_resident_drop": (ci, [vp]),
     "tpg_increment_as_note_narrow_block": (ci, [vp, vp, i64]),
+    # ---- AMOVA
+    "tpg_pairwise_sqdist": (ci, [vp, vp, ci, i64, vp]),
+    "tpg_class_sums": (ci, [vp, vp, i64, vp, i64, ci, vp]),
+    "tpg_class_sums_scratch_bytes": (i64, [i64, i64, ci]),
+    "tpg_classsum_chunk": (i64, []),
+    "tpg_classsum_tile_rows": (i64, []),
+    "tpg_classsum_batch": (i64, []),
+    "tpg_amova_perm_labels": (ci, [i64, vp, ci, vp, ci, ci, u64, i64, vp, vp]),
+    "tpg_amova_from_sums": (ci, [ci, vp, vp, ci, vp, vp, f64, vp]),
     # ---- SNP-block shards over the GPUs of one node
     "tpg_comm_unique_id": (ci, [vp]),
     "tpg_comm_init_rank": (ci, [vp, ci, ci, vp, vp]),

@@ -430,6 +430,17 @@ class Pairwise:
         check(lib.tpg_pairwise_grm(self.ctx.h, self.h, _ptr(out)))
         return out
 
+    def sqdist(self, type: str = "raw", m: int = 0, out=None):
+        """tpg_pairwise_sqdist (include/tpg.h "AMOVA"): the squared Euclidean distance of the dosages over the loci both
+        individuals are typed at, "raw" or "adjusted" (raw * m / typed loci).  out: None (a new host matrix), a host matrix or a
+        DeviceMatrix."""
+        if type not in SQDIST_TYPES:
+            raise ValueError("type must be 'raw' or 'adjusted'")
+        if out is None:
+            out = self._mat()
+        check(lib.tpg_pairwise_sqdist(self.ctx.h, self.h, SQDIST_TYPES[type], int(m), out.p if isinstance(out, DeviceMatrix) else _ptr(out)))
+        return out
+
     def epilogues(self, which=("ibs", "king", "allele_sharing", "grm"), ibs_type: str = "proportion", m: int = 0) -> dict:
         """IBS, KING, allele sharing and GRM from one pass over the accumulators"""
         names = ("ibs", "king", "allele_sharing", "grm")
@@ -1589,6 +1600,175 @@ def pairwise_pop_fst_test(X: FBM, ind_row, ind_col, groupIds, ngroups: int, meth
     out = dict(fst_tot=fst[0].copy(), p_value=p, n_valid=n_valid)
     if return_perm:
         out["perm_fst"] = fst[1:].copy()
+    return out
+
+
+class DeviceMatrix:
+    """An n x n column-major matrix of doubles that stays in HBM between two library calls (tpg_dev_alloc): what
+    pairwise_sqdist(device=True) returns and class_sums / gt_amova accept."""
+
+    def __init__(self, ctx: Context, n: int):
+        self.ctx, self.n = ctx, int(n)
+        self.p = ctx.dev_alloc(8 * self.n * self.n)
+
+    @classmethod
+    def from_numpy(cls, A, ctx: Optional[Context] = None) -> "DeviceMatrix":
+        a = np.asfortranarray(A, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("A must be a square matrix")
+        d = cls(ctx or default_context(), a.shape[0])
+        check(lib.tpg_dev_from_host(d.ctx.h, d.p, _ptr(a), a.nbytes))
+        return d
+
+    def to_numpy(self) -> np.ndarray:
+        out = np.zeros((self.n, self.n), order="F")
+        check(lib.tpg_dev_to_host(self.ctx.h, _ptr(out), self.p, out.nbytes))
+        return out
+
+    def free(self):
+        if self.p is not None:
+            lib.tpg_dev_free(self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+SQDIST_TYPES = {"raw": 0, "adjusted": 1}
+
+
+def pairwise_sqdist(X: FBM, ind_row=None, ind_col=None, type: str = "raw", device: bool = False):
+    """Squared genotype distances between individuals from one pairwise pass with the KING set of products.  device = True:
+    the matrix stays in HBM (a DeviceMatrix, which class_sums and gt_amova accept)."""
+    if type not in SQDIST_TYPES:
+        raise ValueError("type must be 'raw' or 'adjusted'")
+    v, pw = _pairwise_pass(X, ind_row, ind_col, PW_FOR_KING)
+    return pw.sqdist(type, v.m, DeviceMatrix(X.ctx, v.n) if device else None)
+
+
+def class_sums(A, labels, nclasses: int, ctx: Optional[Context] = None) -> np.ndarray:
+    """tpg_class_sums: A is n x n (a numpy array or a DeviceMatrix), labels is R x n with -1 = outside the labeling ->
+    (R, nclasses) sums of A[i, j] over the ordered pairs of each class, in the order include/tpg.h "AMOVA" defines."""
+    if isinstance(A, DeviceMatrix):
+        ctx, n, pa, keep = A.ctx, A.n, A.p, A
+    else:
+        ctx = ctx or default_context()
+        keep = np.asfortranarray(A, dtype=np.float64)
+        if keep.ndim != 2 or keep.shape[0] != keep.shape[1]:
+            raise ValueError("A must be a square matrix")
+        n, pa = keep.shape[0], _ptr(keep)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim == 1:
+        lab = lab.reshape(1, -1)
+    if lab.ndim != 2 or lab.shape[1] != n:
+        raise ValueError("labels must have one column per row of A")
+    sums = np.zeros((lab.shape[0], max(int(nclasses), 0)))
+    check(lib.tpg_class_sums(ctx.h, pa, n, _ptr(lab), lab.shape[0], int(nclasses), _ptr(sums)))
+    return sums
+
+
+AMOVA_SCHEMES = {"ST": 0, "SC": 1, "CT": 2}
+
+
+def amova_perm_labels(n: int, pop, npop: int, region_of_pop, nregion: int, scheme, seed: int, r: int):
+    """tpg_amova_perm_labels: the r-th relabeling of scheme "ST" / 0 (individuals among all populations), "SC" / 1 (inside every
+    region) or "CT" / 2 (whole populations among the regions); r = 0 is the identity.  -> (pop (n), region_of_pop (npop) or None).
+    Host only."""
+    p0 = _i32(pop)
+    if p0 is None or p0.shape != (n,):
+        raise ValueError("pop must have one entry per individual")
+    g0 = _i32(region_of_pop) if nregion > 0 else None
+    if g0 is not None and g0.shape != (npop,):
+        raise ValueError("region_of_pop must have one entry per population")
+    sch = AMOVA_SCHEMES[scheme] if isinstance(scheme, str) else int(scheme)
+    po, go = np.zeros(n, dtype=np.int32), (np.zeros(npop, dtype=np.int32) if g0 is not None else None)
+    check(lib.tpg_amova_perm_labels(int(n), _ptr(p0), int(npop), _ptr(g0), int(nregion), sch, int(seed) & 0xFFFFFFFFFFFFFFFF, int(r),
+                                    _ptr(po), _ptr(go)))
+    return po, go
+
+
+def amova_from_sums(pop_size, pop_sum, total_sum: float, region_of_pop=None, region_sum=None) -> dict:
+    """tpg_amova_from_sums: one relabeling's class sums -> dict(df (4), ssd (4), msd (3), ncoef (3), sigma2 (4), phi (3)); rows
+    (among regions, among populations within regions, within populations, total), phi = (CT, SC, ST).  Host only."""
+    ps, pw = np.ascontiguousarray(pop_size, dtype=np.int64), _f64(pop_sum)
+    if ps.ndim != 1 or pw.shape != ps.shape:
+        raise ValueError("pop_size and pop_sum must have one entry per population")
+    g0, rs = (_i32(region_of_pop), _f64(region_sum)) if region_of_pop is not None else (None, None)
+    if g0 is not None and (g0.shape != ps.shape or rs is None or rs.ndim != 1 or (len(g0) and rs.shape[0] <= int(g0.max()))):
+        raise ValueError("region_of_pop needs one entry per population and region_sum one per region")
+    out = np.zeros(21)
+    check(lib.tpg_amova_from_sums(len(ps), _ptr(ps), _ptr(pw), 0 if g0 is None else len(rs), _ptr(g0), _ptr(rs), float(total_sum), _ptr(out)))
+    return dict(df=out[0:4].copy(), ssd=out[4:8].copy(), msd=out[8:11].copy(), ncoef=out[11:14].copy(), sigma2=out[14:18].copy(),
+                phi=out[18:21].copy())
+
+
+def gt_amova(X: Optional[FBM] = None, ind_row=None, ind_col=None, pop=None, npop: int = 0, region_of_pop=None, dist=None,
+             dist_type: str = "raw", n_perm: int = 999, seed: int = 0, return_perm: bool = False) -> dict:
+    """Analysis of molecular variance with permutation tests (no counterpart in the reference; include/tpg.h "AMOVA").  pop (n,
+    0-based, -1 = left out) and region_of_pop (npop, 0-based; None: two levels) give the hierarchy.  The squared distances come
+    from X by one pairwise pass (dist_type "raw" or "adjusted") and stay in HBM, or from dist (any n x n matrix or DeviceMatrix).
+    One class_sums call per kind of labeling -- the all-zero row (T), the population rows, the region rows -- each holding the
+    identity and the relabelings of the schemes that change it: "ST" shuffles individuals among all populations, "SC" inside
+    every region (the region sums stay), "CT" whole populations among the regions (the population sums stay).
+    -> dict(table = dict(source, df, ssd, msd, sigma2, percent), ncoef, phi, p_value, n_valid (each (CT, SC, ST))), with
+    return_perm also perm = {scheme: dict(phi (n_perm, 3), sigma2 (n_perm, 4))}."""
+    if pop is None or npop < 1:
+        raise ValueError("pop and npop are required")
+    if n_perm < 1:
+        raise ValueError("n_perm must be positive")
+    if (X is None) == (dist is None):
+        raise ValueError("give either X or dist")
+    A = pairwise_sqdist(X, ind_row, ind_col, dist_type, device=True) if dist is None else dist
+    if not isinstance(A, DeviceMatrix):
+        A = np.asfortranarray(A, dtype=np.float64)
+    n = A.n if isinstance(A, DeviceMatrix) else A.shape[0]
+    ctx = A.ctx if isinstance(A, DeviceMatrix) else (X.ctx if X is not None else None)
+    p0 = _i32(pop)
+    if p0.shape != (n,):
+        raise ValueError("pop must have one entry per individual")
+    g0 = _i32(region_of_pop) if region_of_pop is not None else None
+    G = 0 if g0 is None else int(g0.max()) + 1 if len(g0) else 0
+    amova_perm_labels(n, p0, npop, g0, G, 0, seed, 0)  # the checks of the design: an empty population, a bad id
+    size = np.bincount(p0[p0 >= 0], minlength=npop).astype(np.int64)
+    schemes = ["ST"] + (["SC", "CT"] if G else [])
+    rel = {s: [amova_perm_labels(n, p0, npop, g0, G, s, seed, r) for r in range(1, n_perm + 1)] for s in schemes}
+    T = class_sums(A, np.where(p0 >= 0, 0, -1), 1, ctx)[0, 0]
+    W = class_sums(A, np.stack([p0] + [p for s in ("ST", "SC") if s in rel for p, _ in rel[s]]), npop, ctx)
+    W_of = {"ST": W[1:1 + n_perm], "SC": W[1 + n_perm:1 + 2 * n_perm]}
+    if G:
+        def induced(p, g):  # the region of everybody's population, -1 staying outside
+            return np.where(p >= 0, g[np.maximum(p, 0)], -1).astype(np.int32)
+
+        Rg = class_sums(A, np.stack([induced(p0, g0)] + [induced(p, g0) for p, _ in rel["ST"]] + [induced(p0, g) for _, g in rel["CT"]]), G,
+                        ctx)
+        R_of = {"ST": Rg[1:1 + n_perm], "CT": Rg[1 + n_perm:1 + 2 * n_perm]}
+    obs = amova_from_sums(size, W[0], T, g0, Rg[0] if G else None)
+    perm = {}
+    for s in schemes:
+        rows = []
+        for k in range(n_perm):
+            w = W_of[s][k] if s != "CT" else W[0]
+            rg = None if not G else R_of[s][k] if s != "SC" else Rg[0]
+            rows.append(amova_from_sums(size, w, T, rel[s][k][1] if s == "CT" else g0, rg))
+        perm[s] = dict(phi=np.stack([x["phi"] for x in rows]), sigma2=np.stack([x["sigma2"] for x in rows]))
+    col = {"CT": 0, "SC": 1, "ST": 2}
+    p_value, n_valid = np.full(3, np.nan), np.zeros(3, dtype=np.int64)
+    for s in schemes:
+        p, nv = fst_perm_pvalue(obs["phi"][col[s]], perm[s]["phi"][:, col[s]])
+        p_value[col[s]], n_valid[col[s]] = p[0], nv[0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        percent = 100.0 * obs["sigma2"] / obs["sigma2"][3]
+    keep = slice(0, 4) if G else slice(1, 4)
+    table = dict(source=["among regions", "among populations within regions", "within populations", "total"][keep] if G
+                 else ["among populations", "within populations", "total"],
+                 df=obs["df"][keep], ssd=obs["ssd"][keep], msd=np.append(obs["msd"], np.nan)[keep], sigma2=obs["sigma2"][keep],
+                 percent=percent[keep])
+    out = dict(table=table, ncoef=obs["ncoef"], phi=obs["phi"], p_value=p_value, n_valid=n_valid)
+    if return_perm:
+        out["perm"] = perm
     return out
 
 

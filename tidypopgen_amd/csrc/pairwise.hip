@@ -1168,6 +1168,12 @@ __device__ __forceinline__ void tpg_pw_emit(const PwCounts c, int mode, double s
   } else if (mode == 3) {
     const double num = (double)(D + quirk), den = (double)V;
     o0[idx] = V == 0 ? TPG_QNAN : 0.5 * (1 + num / den);  // R/snp_allele_sharing.R:79-80
+  } else if (mode == 5) {
+    // squared Euclidean distance of the dosages over the loci both are typed at (include/tpg.h "AMOVA"): sum d_i^2 v_j = V - Aij.
+    // scale = 0: raw; scale = m: the product as an integer (|raw| <= 4 L < 2^33, m <= 2^30), then one division
+    const long long raw = 2 * V - Aij - Aji - 2 * D;
+    if (scale == 0.0) o0[idx] = (double)raw;
+    else o0[idx] = V == 0 ? TPG_QNAN : (double)(raw * (long long)scale) / (double)V;
   } else {
     // mode 4: IBS (o0, scale), KING (o1) and allele sharing (o2) from one fetch
     if (o0) {
@@ -1361,6 +1367,16 @@ extern "C" int tpg_pairwise_allele_sharing(tpg_ctx* ctx, const tpg_pairwise* pw,
   TPG_TRY(pw_need(pw, TPG_PW_FOR_AS, "allele sharing"));
   double* outs[6] = {out, nullptr, nullptr, nullptr, nullptr, nullptr};
   return run_epilogue(ctx, pw, 3, 1.0, outs);
+}
+
+extern "C" int tpg_pairwise_sqdist(tpg_ctx* ctx, const tpg_pairwise* pw, int type, int64_t m, double* out) {
+  TpgEnter _enter(ctx);
+  TPG_REQUIRE(ctx && pw && out, TPG_EINVAL, "null argument");
+  TPG_REQUIRE(type == TPG_SQDIST_RAW || type == TPG_SQDIST_ADJUSTED, TPG_EINVAL, "bad squared-distance type %d", type);
+  TPG_REQUIRE(type == TPG_SQDIST_RAW || (m >= 1 && m <= (1ll << 30)), TPG_EINVAL, "m = %lld out of [1, 2^30]", (long long)m);
+  TPG_TRY(pw_need(pw, TPG_PW_FOR_KING, "the squared distance"));
+  double* outs[6] = {out, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return run_epilogue(ctx, pw, 5, type == TPG_SQDIST_RAW ? 0.0 : (double)m, outs);
 }
 
 static int grm_from_as_band(tpg_ctx* ctx, tpg_comm* comm, int n, const PwBand& band, double* d_M);
