@@ -5,6 +5,11 @@ launch: how many launches of which width depends on k alone, CT = ceil(6 k / 32)
 give CT = 1, 1, 2, 3, 3, 4, 5, 6, 7, 9, 12 -- every arm of the launch chain (1, 2, 3, 4, 4 + 1, 4 + 2, 4 + 3, 4 + 4 + 1,
 4 + 4 + 4) -- and from k = 6 on components whose six digits straddle two tiles.  Both layouts of a view: rows (View) and
 locus-major (the second member of View.pair when n is a multiple of 8).
+
+What the 1e-9 bound below does NOT see: n = 130 and 136 are both Q = ceil(n / 128) = 2, one depth of the kernel's pipeline, and a
+slip in a few rows -- a wrong lowest digit in one individual or in the 16 of one lane's piece, a dropped carry, a digit without its
+sign in one byte position -- moves a result by a few 2^-33 max |u|, far below 1e-9.  tests/test_gpu_loadings_exact.py holds the
+same kernels to integer sums bit for bit at every depth, and tests/test_loadings_host.py shows which slips pass here.
 """
 import numpy as np
 import pytest
@@ -65,8 +70,8 @@ def _views(tpg, n):
 @pytest.mark.parametrize("layout,n", [("rows", 130), ("locus_major", 136)])
 def test_loadings_against_fp64(tpg, layout, n, k):
     """max |got - want| <= 1e-9 max |want|, the suite's bound for this entry point.  The 2^-40 fixed point of the digits
-    costs at most 2 n 2^-40 ~ 2.4e-10 at these n, so the bound has no slack to hide a lost or misplaced digit in (2^-35 of
-    max |u| at the least, in every row that loses it)."""
+    costs at most 2 n 2^-40 ~ 2.4e-10 at these n, so the bound has no slack to hide a digit lost or misplaced in EVERY row
+    (2^-35 of max |u| at the least, per row).  A digit lost in a few rows it does hide: see the module docstring."""
     g, v_rows, v_lm = _views(tpg, n)
     v = v_rows if layout == "rows" else v_lm
     center, scale = tpg.pca_center_scale(v)
