@@ -1188,7 +1188,7 @@ int tpg_increment_as_note_narrow_block(tpg_ctx* ctx, double* K, int64_t n);
  *        sigma2 = (NaN, s_b, s_c, s_T); phi = (NaN, NaN, Phi_ST = s_b / s_T).
  *        Negative components and Phi are reported as they come, as Arlequin does.  npop < 1, a population size < 1, a region id
  *        out of range or an empty region: TPG_EINVAL, nothing written.
- * Not offered: Mantel tests and PERMANOVA drivers (tpg_class_sums is their kernel), a within-individual level, more than three
+ * Not offered: PERMANOVA drivers (tpg_class_sums is their kernel), a within-individual level, more than three
  *        levels, tpg_stream_* / tpg_multi_* forms, an R shim entry, distances other than the squared Euclidean one. */
 #define TPG_SQDIST_RAW 0
 #define TPG_SQDIST_ADJUSTED 1
@@ -1206,6 +1206,67 @@ int tpg_amova_perm_labels(int64_t n, const int32_t* pop0, int npop, const int32_
                           uint64_t seed, int64_t r, int32_t* pop_out, int32_t* region_of_pop_out);
 int tpg_amova_from_sums(int npop, const int64_t* pop_size, const double* pop_sum, int nregion, const int32_t* region_of_pop0,
                         const double* region_sum, double total_sum, double* out);
+
+/* ---- Mantel tests (gt_mantel: does genetic distance grow with geographic distance?  The correlation of two distance matrices,
+ * tested by permuting the individuals of one of them; the partial test "after controlling for a third matrix"; permutations
+ * restricted to strata.  The reference carries coordinates for every individual and has no test that uses them, so everything is
+ * defined HERE; it is recalled from Mantel 1967, Smouse, Long & Sokal 1986 and vegan's mantel / mantel.partial, not pinned by a
+ * run of vegan) -------------------------------------------------------------------------------------------------------------------
+ * The conventions are those of "AMOVA": n x n column-major doubles in host or device memory, IEEE double, no FMA contraction, no
+ * floating-point atomics, errors leave the outputs untouched.
+ * Cross sums, tpg_mantel_sums: A and the Q matrices B[0 .. Q-1] are n x n, symmetric or not.  perms is R x n row-major in host
+ *        memory, every row a permutation pi of 0 .. n-1.  sums is R x Q row-major in host memory: sums[r][q] = the sum over the
+ *        ordered pairs i != j of A[pi(i) + pi(j) n] * B_q[i + j n].  The diagonals are never read into a sum: a NaN on a diagonal
+ *        changes nothing.  A NaN off the diagonal of A makes every sum NaN, one off the diagonal of B_q makes column q NaN and
+ *        no other column.
+ * Order: with L = TPG_MANTEL_LANES, the column term c(r, q, j): partial t (0 <= t < L) adds the products for i = t, t + L,
+ *        t + 2 L, ... in ascending i from +0.0, each product rounded to double before it is added, i = j skipped; then for
+ *        h = L/2, L/4, .., 1: s[t] += s[t + h] for t < h; c = s[0].  sums[r][q] adds c(r, q, j) in ascending j from +0.0.  If A and
+ *        B_q hold integers and every partial sum stays below 2^53 every order gives the exact integer; otherwise a sum is
+ *        within k 2^-52 sum |x| of the exact sum of its k rounded products.
+ * Determinism: sums[r][q] depends on A, B_q and row r of perms alone: not on R, Q, the other matrices, the row's place in the
+ *        list, the library's internal passes and batches or launch geometry.  Two calls give the same bits.
+ * Limits and errors: 1 <= n <= TPG_MANTEL_MAX_N (a column of A is kept in LDS), 1 <= Q <= TPG_MANTEL_MAX_Q, R >= 0, every
+ *        row of perms a bijection (no duplicate, no value out of range; checked on the host before any launch), else TPG_EINVAL
+ *        with nothing written.  R == 0: TPG_OK, nothing written.  The library walks R in internal passes, so its device scratch
+ *        (the matrices themselves, when they come from the host, not counted) is bounded independently of R:
+ *        tpg_mantel_scratch_bytes (host only; a bad size: -1).  tpg_mantel_lanes: L, and tpg_mantel_pass_rows: the permutations
+ *        of one internal pass at (n, Q), and tpg_mantel_strides: the strides of L rows a thread of the kernel keeps in flight per
+ *        trip of its loop at Q (a bad size: -1 from both), for tests that place borders.  None of them is in the order.  B is declared const double** and not
+ *        const double* const*, because the binding's prototype check reads one level of const: nothing is written through
+ *        it, and a C caller that holds a const double* const* passes it with a cast.
+ * tpg_offdiag_moments: out[0] = S = the sum of a_ij over i != j, out[1] = SS = the sum of a_ij * a_ij, both in the order above
+ *        under the identity permutation with b = 1.0 (the product a * 1.0 is a) and b = a.  out is host memory.
+ * tpg_offdiag_center: out_ij = a_ij - mean off the diagonal, +0.0 on it; out may be A (in place) or a second matrix, host or
+ *        device memory.  A driver centres both matrices by S / N, N = n (n - 1), before it forms the cross sums, so that the
+ *        correlation does not cancel on matrices whose entries are all large and positive.
+ * tpg_mantel_perms (host only, no context, no GPU): rows r0 .. r0 + R - 1 of the permutation list in ONE call, out R x n; every
+ *        row is a pure function of (n, strata, seed, r).  strata0[n] in {0 .. nstrata-1}, or NULL = one stratum.  With M =
+ *        tpg_mix64 and 64-bit unsigned arithmetic, key(u) = M(seed ^ M((r << 32) + u)) (the key of tpg_amova_perm_labels); within
+ *        a stratum with members e_0 < e_1 < ..., sigma = the members sorted by (key, index) and pi(sigma_t) = e_t: individual
+ *        sigma_t takes the row and column that e_t held.  Nobody leaves a stratum.  r = 0 is the identity and is not hashed.
+ *        0 <= r < 2^31 violated, a stratum id out of range, R < 0 or n outside the limits: TPG_EINVAL, nothing written.
+ * tpg_mantel_from_sums (host only): with N the number of pairs and the moments of both matrices, in IEEE double in this
+ *        statement order, without FMA contraction: c = Sab - (Sa * Sb) / N; va = Saa - (Sa * Sa) / N; vb = Sbb - (Sb * Sb) / N;
+ *        *out = c / sqrt(va * vb); NaN where va > 0 or vb > 0 does not hold, or N < 1.  Under a permutation of A only Sab changes.
+ * tpg_mantel_partial (host only): fa = 1 - r_ac * r_ac; fb = 1 - r_bc * r_bc; (r_ab - r_ac * r_bc) / sqrt(fa * fb); NaN where
+ *        fa > 0 or fb > 0 does not hold.  Under a permutation of A r_ab and r_ac change (Q = 2 in one tpg_mantel_sums call) and
+ *        r_bc stays.
+ * Not offered: n > TPG_MANTEL_MAX_N, Mantel correlograms, PERMANOVA, Kendall's tau, tpg_stream_* / tpg_multi_* forms, an R shim
+ *        entry, a rank transform on the device (Spearman's form ranks on the host). */
+#define TPG_MANTEL_LANES 256
+#define TPG_MANTEL_MAX_N 16384
+#define TPG_MANTEL_MAX_Q 4
+int tpg_mantel_sums(tpg_ctx* ctx, const double* A, const double** B, int Q, int64_t n, const int32_t* perms, int64_t R, double* sums);
+int64_t tpg_mantel_scratch_bytes(int64_t n, int64_t R, int Q);
+int64_t tpg_mantel_lanes(void);
+int64_t tpg_mantel_pass_rows(int64_t n, int Q);
+int64_t tpg_mantel_strides(int Q);
+int tpg_offdiag_moments(tpg_ctx* ctx, const double* A, int64_t n, double* out);
+int tpg_offdiag_center(tpg_ctx* ctx, const double* A, int64_t n, double mean, double* out);
+int tpg_mantel_perms(int64_t n, const int32_t* strata0, int nstrata, uint64_t seed, int64_t r0, int64_t R, int32_t* out);
+int tpg_mantel_from_sums(int64_t N, double Sa, double Saa, double Sb, double Sbb, double Sab, double* out);
+double tpg_mantel_partial(double r_ab, double r_ac, double r_bc);
 
 /* ---- SNP-block shards over the GPUs of one node -------------------------------------------------
  * The locus axis is the reference's own block axis (R/snp_ibs.R:59-82): a shard is a contiguous range of loci.

@@ -294,6 +294,16 @@ PROTOTYPES = {
     "tpg_classsum_batch": (i64, []),
     "tpg_amova_perm_labels": (ci, [i64, vp, ci, vp, ci, ci, u64, i64, vp, vp]),
     "tpg_amova_from_sums": (ci, [ci, vp, vp, ci, vp, vp, f64, vp]),
+    "tpg_mantel_sums": (ci, [vp, vp, vp, ci, i64, vp, i64, vp]),
+    "tpg_mantel_scratch_bytes": (i64, [i64, i64, ci]),
+    "tpg_mantel_lanes": (i64, []),
+    "tpg_mantel_pass_rows": (i64, [i64, ci]),
+    "tpg_mantel_strides": (i64, [ci]),
+    "tpg_offdiag_moments": (ci, [vp, vp, i64, vp]),
+    "tpg_offdiag_center": (ci, [vp, vp, i64, f64, vp]),
+    "tpg_mantel_perms": (ci, [i64, vp, ci, u64, i64, i64, vp]),
+    "tpg_mantel_from_sums": (ci, [i64, f64, f64, f64, f64, f64, vp]),
+    "tpg_mantel_partial": (f64, [f64, f64, f64]),
     # ---- SNP-block shards over the GPUs of one node
     "tpg_comm_unique_id": (ci, [vp]),
     "tpg_comm_init_rank": (ci, [vp, ci, ci, vp, vp]),

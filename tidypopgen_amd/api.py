@@ -1772,6 +1772,227 @@ def gt_amova(X: Optional[FBM] = None, ind_row=None, ind_col=None, pop=None, npop
     return out
 
 
+def _square(A, ctx):
+    """a numpy array or a DeviceMatrix -> (ctx, n, pointer, the object that keeps the memory alive)"""
+    if isinstance(A, DeviceMatrix):
+        return A.ctx, A.n, A.p, A
+    keep = np.asfortranarray(A, dtype=np.float64)
+    if keep.ndim != 2 or keep.shape[0] != keep.shape[1]:
+        raise ValueError("a square matrix is required")
+    return ctx, keep.shape[0], _ptr(keep), keep
+
+
+def mantel_sums(A, Bs, perms, ctx: Optional[Context] = None) -> np.ndarray:
+    """tpg_mantel_sums: A and every B of the list Bs are n x n (numpy arrays or DeviceMatrix), perms is R x n, every row a
+    permutation of 0 .. n-1 -> (R, Q) sums over i != j of A[perm[i], perm[j]] * B_q[i, j], in the order include/tpg.h "Mantel
+    tests" defines."""
+    if isinstance(Bs, (np.ndarray, DeviceMatrix)):
+        Bs = [Bs]
+    for M in [A, *Bs]:
+        if isinstance(M, DeviceMatrix):
+            ctx = M.ctx
+    ctx = ctx or default_context()
+    _, n, pa, keep_a = _square(A, ctx)
+    mats = [_square(B, ctx) for B in Bs]
+    if any(m[1] != n for m in mats):
+        raise ValueError("every matrix must be n x n")
+    pm = np.ascontiguousarray(perms, dtype=np.int32)
+    if pm.ndim == 1:
+        pm = pm.reshape(1, -1)
+    if pm.ndim != 2 or pm.shape[1] != n:
+        raise ValueError("perms must have one column per row of A")
+    Q = len(mats)
+    pb = (C.c_void_p * max(Q, 1))(*[m[2] for m in mats])
+    sums = np.zeros((pm.shape[0], Q))
+    check(lib.tpg_mantel_sums(ctx.h, pa, pb, Q, n, _ptr(pm), pm.shape[0], _ptr(sums)))
+    return sums
+
+
+def mantel_pass_rows(n: int, Q: int) -> int:
+    """tpg_mantel_pass_rows: the permutations of one internal pass of mantel_sums at (n, Q); -1 on a bad size"""
+    return int(lib.tpg_mantel_pass_rows(int(n), int(Q)))
+
+
+def mantel_scratch_bytes(n: int, R: int, Q: int) -> int:
+    """tpg_mantel_scratch_bytes: the device scratch of a mantel_sums call, bounded independently of R; -1 on a bad size"""
+    return int(lib.tpg_mantel_scratch_bytes(int(n), int(R), int(Q)))
+
+
+def offdiag_moments(A, ctx: Optional[Context] = None):
+    """tpg_offdiag_moments: -> (S, SS), the sums of a_ij and of a_ij^2 over i != j in the order of mantel_sums"""
+    ctx, n, pa, keep = _square(A, ctx or (None if isinstance(A, DeviceMatrix) else default_context()))
+    out = np.zeros(2)
+    check(lib.tpg_offdiag_moments(ctx.h, pa, n, _ptr(out)))
+    return float(out[0]), float(out[1])
+
+
+def offdiag_center(A, mean: float, out=None, ctx: Optional[Context] = None):
+    """tpg_offdiag_center: a_ij - mean off the diagonal, +0.0 on it.  A DeviceMatrix gives a DeviceMatrix (out=A: in place), a
+    numpy array a new numpy array."""
+    if isinstance(A, DeviceMatrix):
+        out = DeviceMatrix(A.ctx, A.n) if out is None else out
+        check(lib.tpg_offdiag_center(A.ctx.h, A.p, A.n, float(mean), out.p))
+        return out
+    ctx, n, pa, keep = _square(A, ctx or default_context())
+    res = np.zeros((n, n), order="F")
+    check(lib.tpg_offdiag_center(ctx.h, pa, n, float(mean), _ptr(res)))
+    return res
+
+
+def mantel_perms(n: int, seed: int, r0: int, R: int, strata=None, nstrata: int = 0) -> np.ndarray:
+    """tpg_mantel_perms: rows r0 .. r0 + R - 1 of the permutation list in one call -> (R, n) int32; row r = 0 is the identity;
+    strata (n, 0-based ids below nstrata): nobody leaves a stratum.  Host only."""
+    st = _i32(strata)
+    if st is not None and st.shape != (n,):
+        raise ValueError("strata must have one entry per individual")
+    out = np.zeros((max(int(R), 0), max(int(n), 0)), dtype=np.int32)
+    check(lib.tpg_mantel_perms(int(n), _ptr(st), int(nstrata), int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), int(R), _ptr(out)))
+    return out
+
+
+def mantel_from_sums(N: int, Sa: float, Saa: float, Sb: float, Sbb: float, Sab: float) -> float:
+    """tpg_mantel_from_sums: the correlation from the number of pairs, the moments of both matrices and the cross sum.  Host only."""
+    out = np.zeros(1)
+    check(lib.tpg_mantel_from_sums(int(N), float(Sa), float(Saa), float(Sb), float(Sbb), float(Sab), _ptr(out)))
+    return float(out[0])
+
+
+def mantel_partial(r_ab: float, r_ac: float, r_bc: float) -> float:
+    """tpg_mantel_partial: the partial correlation of a and b given c.  Host only."""
+    return float(lib.tpg_mantel_partial(float(r_ab), float(r_ac), float(r_bc)))
+
+
+def great_circle_dist(lon, lat, radius_km: float = 6371.0088) -> np.ndarray:
+    """Haversine distances in km between points given by longitude and latitude in degrees -> n x n, symmetric, zero diagonal.
+    numpy on the host, not a device kernel: its bits are numpy's."""
+    lon, lat = np.radians(np.asarray(lon, dtype=np.float64)), np.radians(np.asarray(lat, dtype=np.float64))
+    if lon.ndim != 1 or lon.shape != lat.shape:
+        raise ValueError("lon and lat must be vectors of one length")
+    sdlat = np.sin((lat[:, None] - lat[None, :]) / 2.0)
+    sdlon = np.sin((lon[:, None] - lon[None, :]) / 2.0)
+    h = sdlat * sdlat + np.cos(lat)[:, None] * np.cos(lat)[None, :] * (sdlon * sdlon)
+    d = 2.0 * radius_km * np.arcsin(np.sqrt(np.minimum(h, 1.0)))
+    d = np.maximum(d, d.T)  # (h is symmetric up to the order of the two cosines: make it so)
+    np.fill_diagonal(d, 0.0)
+    return np.asfortranarray(d)
+
+
+def offdiag_midranks(M) -> np.ndarray:
+    """Spearman's transform of a symmetric matrix: the entries of the strict lower triangle replaced by their mid-ranks (1-based,
+    ties share the mean of their ranks), mirrored; the diagonal +0.0.  numpy on the host."""
+    M = np.asarray(M, dtype=np.float64)
+    n = M.shape[0]
+    il = np.tril_indices(n, -1)
+    x = M[il]
+    if not np.array_equal(x, M.T[il], equal_nan=True):
+        raise ValueError("method='spearman' needs symmetric matrices")
+    order = np.argsort(x, kind="stable")
+    xs = x[order]
+    first = np.concatenate(([True], xs[1:] != xs[:-1])) if len(xs) else np.zeros(0, dtype=bool)
+    start = np.flatnonzero(first)
+    count = np.diff(np.append(start, len(xs)))
+    mid = start + (count + 1) / 2.0  # ranks start + 1 .. start + count: their mean
+    ranks = np.empty(len(xs))
+    ranks[order] = np.repeat(mid, count)
+    ranks[np.isnan(x)] = np.nan
+    out = np.zeros((n, n), order="F")
+    out[il] = ranks
+    out.T[il] = ranks
+    return out
+
+
+def _mantel_r(N, Sa, Saa, Sb, Sbb, Sab):
+    """tpg_mantel_from_sums statement for statement on a vector of cross sums"""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        Nd = np.float64(N)
+        mab = np.float64(Sa) * np.float64(Sb)
+        cab = np.asarray(Sab, dtype=np.float64) - mab / Nd
+        maa = np.float64(Sa) * np.float64(Sa)
+        va = np.float64(Saa) - maa / Nd
+        mbb = np.float64(Sb) * np.float64(Sb)
+        vb = np.float64(Sbb) - mbb / Nd
+        if N < 1 or not (va > 0.0) or not (vb > 0.0):
+            return np.full(np.shape(cab), np.nan)
+        den = np.sqrt(va * vb)
+        return cab / den
+
+
+def _mantel_partial_r(r_ab, r_ac, r_bc):
+    """tpg_mantel_partial statement for statement on vectors r_ab, r_ac"""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        fa = 1.0 - r_ac * r_ac
+        fb = np.float64(1.0) - np.float64(r_bc) * np.float64(r_bc)
+        num = r_ab - r_ac * np.float64(r_bc)
+        den = np.sqrt(fa * fb)
+        return np.where((fa > 0.0) & (fb > 0.0), num / den, np.nan)
+
+
+def gt_mantel(X: Optional[FBM] = None, ind_row=None, ind_col=None, dist=None, dist_type: str = "raw", y=None, z=None, coords=None,
+              method: str = "pearson", strata=None, n_perm: int = 999, seed: int = 0, return_perm: bool = False) -> dict:
+    """Mantel test of isolation by distance (no counterpart in the reference; include/tpg.h "Mantel tests"): the correlation of
+    the genetic distances A -- from X by one pairwise pass (dist_type "raw" or "adjusted"), kept in HBM, or dist (n x n matrix
+    or DeviceMatrix) -- with y (n x n) or the great-circle distances of coords = (lon, lat), tested by n_perm permutations of
+    the individuals of A (inside strata, 0-based ids, when given).  z (n x n): the partial test of A and y given z.  method
+    "spearman" replaces the entries of every matrix by mid-ranks on the host first (symmetric matrices only).  Population level:
+    gt_mantel(dist=F / (1 - F), y=np.log(geo)) with F the fst_tot matrix of pairwise_pop_fst.
+    -> dict(statistic, p_value (one-sided, permuted >= observed), n_valid, n_perm), for the partial test also r_ab, r_ac, r_bc;
+    with return_perm also perm (n_perm,) the permuted statistics."""
+    if method not in ("pearson", "spearman"):
+        raise ValueError("method must be 'pearson' or 'spearman'")
+    if n_perm < 1:
+        raise ValueError("n_perm must be positive")
+    if (X is None) == (dist is None):
+        raise ValueError("give either X or dist")
+    if (y is None) == (coords is None):
+        raise ValueError("give either y or coords")
+    A = pairwise_sqdist(X, ind_row, ind_col, dist_type, device=True) if dist is None else dist
+    ctx = A.ctx if isinstance(A, DeviceMatrix) else (X.ctx if X is not None else default_context())
+    n = A.n if isinstance(A, DeviceMatrix) else np.shape(A)[0]
+    mats = [A, great_circle_dist(*coords) if y is None else y] + ([z] if z is not None else [])
+    ours = [dist is None, False, False]  # a DeviceMatrix of the caller's is centred into a new one, never in place
+    for k, M in enumerate(mats):
+        if not isinstance(M, DeviceMatrix):
+            M = np.asfortranarray(M, dtype=np.float64)
+            if M.shape != (n, n):
+                raise ValueError("every matrix must be n x n")
+        elif M.n != n:
+            raise ValueError("every matrix must be n x n")
+        if method == "spearman":
+            M = offdiag_midranks(M.to_numpy() if isinstance(M, DeviceMatrix) else M)
+        if not isinstance(M, DeviceMatrix):
+            M, ours[k] = DeviceMatrix.from_numpy(M, ctx), True
+        mats[k] = M
+    N = n * (n - 1)
+    mom = []
+    for k, M in enumerate(mats):  # centre by S / N, then the moments of what the cross sums see
+        S, _ = offdiag_moments(M)
+        mean = S / np.float64(N) if N > 0 else 0.0
+        mats[k] = offdiag_center(M, mean, out=M if ours[k] else None)
+        mom.append(offdiag_moments(mats[k]))
+    st = _i32(strata)
+    perms = mantel_perms(n, seed, 0, n_perm + 1, st, 0 if st is None else (int(st.max()) + 1 if len(st) else 0))
+    sums = mantel_sums(mats[0], mats[1:], perms)
+    if np.isnan(sums[0]).any() or np.isnan(np.array(mom)).any():
+        raise _lib.TpgError(4, "gt_mantel: a matrix holds a missing value off its diagonal")  # TPG_ENUMERIC
+    (Sa, Saa), (Sb, Sbb) = mom[0], mom[1]
+    r_ab = _mantel_r(N, Sa, Saa, Sb, Sbb, sums[:, 0])
+    out = {}
+    if z is None:
+        stat = r_ab
+    else:
+        Sc, Scc = mom[2]
+        r_ac = _mantel_r(N, Sa, Saa, Sc, Scc, sums[:, 1])
+        Sbc = mantel_sums(mats[1], [mats[2]], perms[:1])[0, 0]
+        r_bc = mantel_from_sums(N, Sb, Sbb, Sc, Scc, Sbc)
+        stat = _mantel_partial_r(r_ab, r_ac, r_bc)
+        out.update(r_ab=float(r_ab[0]), r_ac=float(r_ac[0]), r_bc=r_bc)
+    p, nv = fst_perm_pvalue(stat[:1], stat[1:].reshape(-1, 1))
+    out.update(statistic=float(stat[0]), p_value=float(p[0]), n_valid=int(nv[0]), n_perm=int(n_perm))
+    if return_perm:
+        out["perm"] = stat[1:].copy()
+    return out
+
+
 def windows_nwise_pop_pbs(X: FBM, ind_row, ind_col, groupIds, ngroups: int, chromosome, position=None, ploidy=None,
                           fst_method: str = "Hudson", return_fst: bool = False, window_size=None, step_size=None, size_unit="snp",
                           min_loci=1, complete=False, triplets=None):
