@@ -46,11 +46,13 @@ class Meta:
         return float(self.nruns) < 0.15 * float(self.nblocks)
 
 
-def describe(scale):
+def describe(scale, w_max=W_MAX):
+    """w_max: the largest weight the caller expects (the overflow cases of tests/gramdig_ref.py reach the class route with
+    weights of 1e6 and more; nothing in the table depends on it)"""
     scale = np.ascontiguousarray(scale, dtype=np.float64)
     me = Meta()
     me.w = 1.0 / (scale * scale)
-    assert np.all(me.w > 0) and me.w.max() <= W_MAX
+    assert np.all(me.w > 0) and me.w.max() <= w_max
     bits = me.w.view(np.uint64)
     key = (bits + np.uint64(16)) & ~np.uint64(31)
     order = np.argsort(key, kind="stable")

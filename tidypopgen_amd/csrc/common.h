@@ -95,8 +95,10 @@ int tpg_prof_resolve(tpg_ctx* ctx);
 // actually used for every locus (its class representative, within 2^-47 of w_j)
 // centred_ok: the caller applies the double centring H K H afterwards, so terms r_i + r_k + const may be left out of S'
 // (gramcls.hip: the centred operand layout of the mixed-fold kernel)
+// force: take this route whatever the cost model says (the digit route cannot hold these weights in int64); *done is still
+// false where the route cannot run at all (TPG_GRAM_DIGITS, m >= 2^31 - 64)
 int tpg_gram_classes(tpg_ctx* ctx, const struct tpg_view* v, const double* d_w, double* d_what, double* d_K, bool* done,
-                     bool centred_ok);
+                     bool centred_ok, bool force = false);
 // The same over the ranks of a communicator, with whole weight classes per rank: `v` holds this rank's loci (counts: its
 // m x 4 genotype counts, scale: its binomial scales), the packed columns are exchanged so that rank r ends up with ALL loci
 // of the allele-count range it owns, and d_K receives S' of those classes (the sum over the ranks is S' of the panel).

@@ -902,9 +902,9 @@ __global__ __launch_bounds__(256) void tpg_gcls_l2lm_kernel(const uint4* __restr
 // A view that was packed locus-major (the imputed view of tpg_view_create_pair) is the gather's source as it is; any other
 // view is copied first.
 int tpg_gram_classes(tpg_ctx* ctx, const tpg_view* v, const double* d_w, double* d_what, double* d_K, bool* done,
-                     bool centred_ok) {
+                     bool centred_ok, bool force) {
   *done = false;
-  if (tpg_env_set("TPG_GRAM_DIGITS")) return TPG_OK;
+  if (tpg_env_set("TPG_GRAM_DIGITS")) return TPG_OK;  // (also when forced: the caller refuses what the digits cannot hold)
   const int64_t n_lt = 4 * v->KG;
   DevBuf d_LM;
   if (!v->LM) {
@@ -914,7 +914,7 @@ int tpg_gram_classes(tpg_ctx* ctx, const tpg_view* v, const double* d_w, double*
                dim3(256), 0, (const uint4*)v->L, v->Q, n_lt, d_LM.as<uint4>());
   }
   const GclsSrc src{v->LM ? v->LM : d_LM.as<uint4>(), 0, 2 * v->Q, 0, 0, 2, 1};
-  const int rc = gram_classes_core(ctx, v->n, v->Q, v->m, src, d_w, d_what, d_K, false, done, centred_ok);
+  const int rc = gram_classes_core(ctx, v->n, v->Q, v->m, src, d_w, d_what, d_K, force, done, centred_ok);
   d_LM.free();  // stream-ordered
   return rc;
 }

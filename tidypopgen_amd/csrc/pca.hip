@@ -580,7 +580,7 @@ __global__ __launch_bounds__(256, 1) void tpg_pca_gram_kernel(const uint4* __res
         long long c = 0;
 #pragma unroll
         for (int t = 0; t < TD; t++) c += (long long)acc[t][tb][q] << (7 * t);
-        c <<= 7 * t0;  // wrapping shift is fine: two's complement, |c| stays far below 2^62
+        c <<= 7 * t0;  // two's complement; pca_gram_device launches this route only where 4 sum_j W_j < 2^63, so no sum wraps
         atomicAdd((unsigned long long*)(slab + (tb * 16 + q) * 64), (unsigned long long)c);
       }
   }
@@ -697,23 +697,38 @@ __global__ __launch_bounds__(256) void tpg_dot_kernel(const double* __restrict__
 // own_center: center_j is the column mean over the view's own individuals (big_SVD's case) -> double centering;
 // otherwise the general form K = S' - r 1' - 1 r' + C with r_i = sum_j w_j c_j g_ij, C = sum_j w_j c_j^2.
 // out[0] = bit pattern of the smallest scale (positive doubles order like their bit patterns), out[1] = 1 + index
-// of some locus whose scale is not a positive number (0 if none)
-__global__ void tpg_scale_range_kernel(const double* __restrict__ scale, int64_t m, unsigned long long* __restrict__ out) {
+// of some locus whose scale is not a positive number (0 if none), out[2 + block] = the bits of the block's sum of the
+// weights 1 / scale^2 over the positive scales.  The launch is SCALE_RANGE_BLOCKS x 256 whatever m is, a thread adds its
+// loci in ascending order, a wave by the xor tree, thread 0 the four waves in order, and the host the blocks in order: the
+// sum has the same bits on every call, so the overflow guard of pca_gram_device decides the same way every time.
+#define SCALE_RANGE_BLOCKS 512
+__global__ __launch_bounds__(256) void tpg_scale_range_kernel(const double* __restrict__ scale, int64_t m,
+                                                              unsigned long long* __restrict__ out) {
+  __shared__ double wsh[4];
   unsigned long long mn = 0x7FF0000000000000ull, bad = 0;
+  double sw = 0;
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
     const double sc = scale[j];
     if (!(sc > 0)) bad = (unsigned long long)j + 1;
-    else { const unsigned long long b = (unsigned long long)__double_as_longlong(sc); mn = b < mn ? b : mn; }
+    else {
+      const unsigned long long b = (unsigned long long)__double_as_longlong(sc);
+      mn = b < mn ? b : mn;
+      sw += 1.0 / (sc * sc);
+    }
   }
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned long long omn = __shfl_xor(mn, o), obad = __shfl_xor(bad, o);
     mn = omn < mn ? omn : mn;
     bad = obad > bad ? obad : bad;
+    sw += __shfl_xor(sw, o);
   }
   if ((threadIdx.x & 63) == 0) {
     atomicMin(out, mn);
     if (bad) atomicMax(out + 1, bad);
+    wsh[threadIdx.x >> 6] = sw;
   }
+  __syncthreads();
+  if (threadIdx.x == 0) out[2 + blockIdx.x] = (unsigned long long)__double_as_longlong(((wsh[0] + wsh[1]) + wsh[2]) + wsh[3]);
 }
 
 __global__ void tpg_pca_weights_kernel(const double* __restrict__ scale, int64_t m, double* __restrict__ w) {
@@ -729,14 +744,15 @@ __global__ void tpg_pca_wc_kernel(const double* __restrict__ what, const double*
 static int pca_gram_device(tpg_ctx* ctx, const tpg_view* v, const double* d_center, const double* d_scale,
                            double* d_K, bool own_center) {
   const int64_t n = v->n, m = v->m;
-  // weight range decides the number of digits: smallest scale by a device reduction (16 bytes come back)
+  // weight range decides the number of digits: smallest scale, and the sum of the weights, by a device reduction (4 KiB come back)
   DevBuf d_rng;
-  TPG_TRY(d_rng.alloc_n<unsigned long long>(2));
-  const unsigned long long rng_init[2] = {0x7FF0000000000000ull, 0ull};  // +inf, no bad entry
-  unsigned long long rng[2];
+  TPG_TRY(d_rng.alloc_n<unsigned long long>(2 + SCALE_RANGE_BLOCKS));
+  const unsigned long long rng_init[2] = {0x7FF0000000000000ull, 0ull};  // +inf, no bad entry (every block writes its sum)
+  std::vector<unsigned long long> rng(2 + SCALE_RANGE_BLOCKS);
   TPG_HIP(tpg_push_small(ctx, d_rng.p, rng_init, sizeof(rng_init)));
-  hipLaunchKernelGGL(tpg_scale_range_kernel, dim3(512), dim3(256), 0, ctx->stream, d_scale, m, d_rng.as<unsigned long long>());
-  TPG_HIP(tpg_fetch_small(ctx, rng, d_rng.p, sizeof(rng)));
+  hipLaunchKernelGGL(tpg_scale_range_kernel, dim3(SCALE_RANGE_BLOCKS), dim3(256), 0, ctx->stream, d_scale, m,
+                     d_rng.as<unsigned long long>());
+  TPG_HIP(tpg_fetch_small(ctx, rng.data(), d_rng.p, sizeof(unsigned long long) * rng.size()));
   d_rng.free();
   TPG_REQUIRE(rng[1] == 0, TPG_ENUMERIC, "zero or negative scale at locus %lld", (long long)(rng[1] - 1));
   double smin;
@@ -746,8 +762,32 @@ static int pca_gram_device(tpg_ctx* ctx, const tpg_view* v, const double* d_cent
   int T = (wbits + ctx->pca_digit_fbits + 1 + 6) / 7;
   if (T > 8 && ctx->pca_digit_fbits > 22) T = std::max(8, (wbits + 22 + 1 + 6) / 7);  // (extra bits are a wish, 22 the requirement)
   if (T < 4) T = 4;
+  int F = 7 * T - 1 - wbits;
+  // T balanced digits (-64 .. 63) reach 63 (128^T - 1) / 127, which is 1 / 127 short of 2^(7 T - 1): a largest weight in
+  // the top 1 / 127 of its binade (127 with wbits = 7; n + 1/2 of a singleton for n = 4 064 .. 4 095) would lose the carry
+  // out of its top digit and come out 2^(7 T - F) too small.  Give up a fractional bit where one is spare, else add a digit.
   TPG_REQUIRE(T <= 8, TPG_ENUMERIC, "per-locus weight range too wide (max 1/scale^2 = %g)", wmax);
-  const int F = 7 * T - 1 - wbits;
+  bool ninth_digit = false;  // the carry asks for a ninth digit, which the kernel does not have: the class route, as for may_wrap
+  if (llrint(ldexp(wmax, F)) > 63 * ((1ll << (7 * T)) - 1) / 127) {
+    if (F > 22) F--;
+    else if (T < 8) T++;
+    else ninth_digit = true;
+  }
+  // The digit route sums S_ik = sum_j g_ij g_kj W_j, W_j = llrint(2^F / scale_j^2), in wrapping int64.  F makes the largest
+  // W_j use all 7 T - 1 bits whatever the absolute scale, so nothing but the panel keeps S below 2^63: g <= 2 and
+  // W_j <= 2^F w_j + 1/2 give S_ik <= 4 sum_j W_j <= 4 (2^F sum_j w_j + m / 2), and the route is safe when that stays below
+  // 2^63 (sufficient, not necessary: every partial sum of the non-negative terms then fits as well).  The sum of the
+  // weights comes back with the smallest scale (in a fixed order); 1 + 2^-20 covers the rounding of its additions many times over.
+  // Under the binomial scaling (w <= n, a handful of loci near it) this never binds; a caller's own scale can make it
+  // bind within a few hundred loci (every scale = 1e-4: T = 8, W of 55 bits).  Then the class route forms S' in FP64
+  // for any weights and is taken whatever its cost model says; where it cannot run, the call is refused.
+  double wsum = 0;
+  for (int b = 0; b < SCALE_RANGE_BLOCKS; b++) {
+    double part;
+    memcpy(&part, &rng[2 + (size_t)b], sizeof(double));
+    wsum += part;
+  }
+  const bool may_wrap = !(4.0 * (ldexp(wsum * (1.0 + 0x1p-20), F) + 0.5 * (double)m) < 0x1p63);
 
   // units: see tpg_gram_locate.  nrtv row tiles hold data, nsbf full super-tiles, rem remainder tiles
   const int nrt = (int)(v->Q * 4);
@@ -778,7 +818,13 @@ static int pca_gram_device(tpg_ctx* ctx, const tpg_view* v, const double* d_cent
     DevBuf d_w;
     TPG_TRY(d_w.alloc_n<double>((size_t)m));
     TPG_LAUNCH(ctx, "pca_weights", tpg_pca_weights_kernel, dim3(1024), dim3(256), 0, d_scale, m, d_w.as<double>());
-    TPG_TRY(tpg_gram_classes(ctx, v, d_w.as<double>(), d_what, d_K, &by_classes, own_center));
+    TPG_TRY(tpg_gram_classes(ctx, v, d_w.as<double>(), d_what, d_K, &by_classes, own_center, may_wrap || ninth_digit));
+    TPG_REQUIRE(by_classes || !ninth_digit, TPG_ENUMERIC,
+                "digit-split Gram needs a ninth digit for the largest weight (max 1/scale^2 = %g is in the top 1/127 below 2^%d) "
+                "and the class route is not available", wmax, wbits);
+    TPG_REQUIRE(by_classes || !may_wrap, TPG_ENUMERIC,
+                "digit-split Gram would overflow int64: 4 * sum of the fixed-point weights (2^%d * %g + %lld / 2) is not below 2^63 "
+                "and the class route is not available", F, wsum, (long long)m);
     if (by_classes)
       TPG_LAUNCH(ctx, "pca_weights", tpg_pca_wc_kernel, dim3(1024), dim3(256), 0, (const double*)d_what, d_center, m, d_wc);
   }  // (d_w goes back before the digit buffers are asked for: stream-ordered)
