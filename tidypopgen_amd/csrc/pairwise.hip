@@ -55,6 +55,7 @@
 #include "common.h"
 #include <type_traits>
 #include "devfrag.h"
+#include "host/host_pwplan.h"  // pwplan_make, pwplan_piece, pwplan_ksplit: how the kernels deal their work
 
 #define TPG_NIB_M (TPG_T4_MM * 0x11111111u)
 #define TPG_NIB_H (TPG_T4_MH * 0x11111111u)
@@ -111,6 +112,26 @@ __host__ __device__ __forceinline__ int64_t tpg_pw_unit_index(int nst, int I, in
   return TA * ((int64_t)I * nst - ((int64_t)I * (I - 1)) / 2) + (jt - TA * I);
 }
 
+// Index of a taker (a wave, or a workgroup) in a round -> its entry of `order` and its K range [k0, k1), in the kernel's own K
+// steps (groups or blocks).  The plan is host/host_pwplan.h's: the indices below `full` are the wave-units of the full rounds
+// (unit un % nun on cut un / nun of S), the L c after them the pieces of the tail round.  `un` is wave-uniform, so is every
+// result: they are pinned into SGPRs here (32-bit step indices: a view has fewer than 2^26 blocks).
+struct PwTake {
+  int I, J, k0, k1;
+};
+__device__ __forceinline__ PwTake tpg_pw_decode(int64_t un, int64_t nun, int S, int64_t full, int64_t L, int c, int64_t kg_begin,
+                                                int64_t kgs, const int2* __restrict__ order) {
+  int64_t unit, r0, r1;
+  pwplan_piece(un, nun, S, full, L, c, kgs, &unit, &r0, &r1);
+  const int2 ij = order[unit];
+  PwTake t;
+  t.I = __builtin_amdgcn_readfirstlane(ij.x);
+  t.J = __builtin_amdgcn_readfirstlane(ij.y);
+  t.k0 = __builtin_amdgcn_readfirstlane((int)(kg_begin + r0));
+  t.k1 = __builtin_amdgcn_readfirstlane((int)(kg_begin + r1));
+  return t;
+}
+
 // The pairwise kernel.  One wave = one (I, jt) unit: a (32 TA) x 32 tile of pairs, five products, 5 TA accumulator
 // tiles (240 AGPRs at TA = 3), one wave per SIMD.  Per 64 loci: TA + 1 fragments of four dwords -> 12 v_and_b32 each
 // -> 5 TA MFMAs, i.e. 3.2 VALU per MFMA: at ~8 + 5.2 x (VALU per MFMA) cycles of issue per MFMA the
@@ -129,6 +150,7 @@ template <int NG>  // rotating load slots of one 128-locus group each: NG - 1 gr
 __global__ __launch_bounds__(256, 1) void tpg_pairwise_kernel(const uint4* __restrict__ T4, int64_t KG,
                                                                  int64_t kg_begin, int64_t kg_end, int nst, int nct,
                                                                  const int2* __restrict__ order, int64_t nun, int S,
+                                                                 int64_t full, int64_t L, int c,
                                                                  const int64_t* __restrict__ rowpad,
                                                                  int32_t* __restrict__ acc_out) {
   const int lane = threadIdx.x & 63;
@@ -145,14 +167,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_kernel(const uint4* __res
   const int sc1 = TPG_SC_ONE, sc2 = TPG_SC_TWO, sch = TPG_SC_HALF;
   for (int64_t round = 0;; round++) {
     const int64_t un = ((round * 8 + xcd) * cpx + cidx) * 4 + wv;
-    if (un >= nun * S) break;
-    const int ks = (int)(un / nun);
-    const int2 ijt = order[un % nun];
-    const int I = __builtin_amdgcn_readfirstlane(ijt.x), jt = __builtin_amdgcn_readfirstlane(ijt.y);
-    const int64_t tp0 = tpg_pw_unit_index(nst, I, jt) + rowpad[I];
+    if (un >= full + L * c) break;
     // 32-bit group indices (a view has fewer than 2^25 groups): scalar range tests, one s_add_i32 per step
-    const int k0 = __builtin_amdgcn_readfirstlane((int)(kg_begin + (kgs * ks) / S));
-    const int k1 = __builtin_amdgcn_readfirstlane((int)(kg_begin + (kgs * (ks + 1)) / S));
+    const PwTake tk = tpg_pw_decode(un, nun, S, full, L, c, kg_begin, kgs, order);
+    const int I = tk.I, jt = tk.J, k0 = tk.k0, k1 = tk.k1;
+    const int64_t tp0 = tpg_pw_unit_index(nst, I, jt) + rowpad[I];
 
     // A row tiles past the last one with data (the last super-tile may be partial; the view holds 4 ceil(n / 128)
     // row tiles) read tile 0 instead and get zero plane masks: zero products
@@ -343,6 +362,7 @@ template <int RA, int RB, int MASK, int NS>
 __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* __restrict__ T4, int64_t KG,
                                                                      int64_t kb_begin, int64_t kb_end, int nst, int nct,
                                                                      const int2* __restrict__ order, int64_t nun, int S,
+                                                                     int64_t full, int64_t L, int c,
                                                                      const int64_t* __restrict__ rowpad,
                                                                      int32_t* __restrict__ acc_out) {
   using PS = PwSet<MASK>;
@@ -357,14 +377,11 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_set_kernel(const uint4* _
   const int sc1 = TPG_SC_ONE, sc2 = TPG_SC_TWO, sch = TPG_SC_HALF;
   for (int64_t round = 0;; round++) {
     const int64_t un = ((round * 8 + xcd) * cpx + cidx) * 4 + wv;
-    if (un >= nun * S) break;
-    const int ks = (int)(un / nun);
-    const int2 ij = order[un % nun];
-    const int I = __builtin_amdgcn_readfirstlane(ij.x), J = __builtin_amdgcn_readfirstlane(ij.y);
+    if (un >= full + L * c) break;
     // 32-bit block indices (a view has fewer than 2^26 blocks): the range tests of the loop are scalar compares, not VALU
     // compares of two uniform 64-bit values, and an index step is one s_add_i32
-    const int kb0 = __builtin_amdgcn_readfirstlane((int)(kb_begin + (kbs * ks) / S));
-    const int kb1 = __builtin_amdgcn_readfirstlane((int)(kb_begin + (kbs * (ks + 1)) / S));
+    const PwTake tk = tpg_pw_decode(un, nun, S, full, L, c, kb_begin, kbs, order);
+    const int I = tk.I, J = tk.J, kb0 = tk.k0, kb1 = tk.k1;
     // row tiles of the wave: RA A tiles (rows of the output), RB B tiles (columns).  A tile past the last one with data
     // reads tile 0 instead; what it yields is never stored
     // (fixed bases at block kb0 in SGPRs; a block is one 32-bit lane offset: a wave-unit never spans 2^22 blocks)
@@ -482,7 +499,8 @@ constexpr int tpg_waitcnt_vm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | (
 template <int RA, int RB, int MASK, int NST>
 __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __restrict__ T4, int64_t KG, int64_t kb_begin,
                                                                     int64_t kb_end, int nst, int nct, const int2* __restrict__ order,
-                                                                    int64_t nun, int S, const int64_t* __restrict__ rowpad,
+                                                                    int64_t nun, int S, int64_t full, int64_t L, int c,
+                                                                    const int64_t* __restrict__ rowpad,
                                                                     int32_t* __restrict__ acc_out) {
   using PS = PwSet<MASK>;
   constexpr int NFW = 2 * RA + 2 * RB;           // fragments of the workgroup per 64 loci
@@ -515,12 +533,9 @@ __global__ __launch_bounds__(256, 1) void tpg_pairwise_wg_kernel(const uint4* __
   const int sc1 = TPG_SC_ONE, sc2 = TPG_SC_TWO, sch = TPG_SC_HALF;
   for (int64_t round = 0;; round++) {
     const int64_t un = (round * 8 + xcd) * cpx + cidx;  // one unit per WORKGROUP
-    if (un >= nun * S) break;
-    const int ks = (int)(un / nun);
-    const int2 ij = order[un % nun];
-    const int I = __builtin_amdgcn_readfirstlane(ij.x), J = __builtin_amdgcn_readfirstlane(ij.y);
-    const int kb0 = __builtin_amdgcn_readfirstlane((int)(kb_begin + (kbs * ks) / S));
-    const int kb1 = __builtin_amdgcn_readfirstlane((int)(kb_begin + (kbs * (ks + 1)) / S));
+    if (un >= full + L * c) break;
+    const PwTake tk = tpg_pw_decode(un, nun, S, full, L, c, kb_begin, kbs, order);
+    const int I = tk.I, J = tk.J, kb0 = tk.k0, kb1 = tk.k1;
     // fragment f of the workgroup: f < 2 RA: A row tile 2 RA I + f; else B row tile 2 RB J + (f - 2 RA).  A tile past the last
     // one with data reads tile 0 instead; what it yields is never stored.  Wave wv fetches fragments NLD wv .. NLD wv + NLD - 1.
     glb_t src[NLD];
@@ -953,27 +968,28 @@ static int pw_order_for(tpg_ctx* ctx, tpg_pairwise* pw, int RA, int RB, const in
   return TPG_OK;
 }
 
-// K split of units x S wave-units over the resident waves: a round costs its K range plus the flush of the
-// accumulators; t_step in us per K step, t_flush in us
-static int pw_ksplit(int64_t nun, int64_t steps, int64_t min_steps_per_unit, int64_t minS, int64_t nwaves, double t_step,
-                     double t_flush) {
-  int bestS = (int)minS;
-  double best = -1;
-  const int64_t cap = steps / min_steps_per_unit;
-  const int64_t maxS = std::max<int64_t>(minS, cap > 0 ? std::min<int64_t>(cap, 96) : 1);
-  for (int64_t S = minS; S <= maxS; S++) {
-    const int64_t rounds = ceil_div(nun * S, nwaves);
-    const double cost = (double)rounds * ((double)ceil_div(steps, S) * t_step + t_flush);
-    if (best < 0 || cost < best * 0.995) { best = cost; bestS = (int)S; }
-  }
-  return bestS;
+// TPG_PW_PLAN="S[,c[,nblk]]", read at every call (A/B runs and tests only): forces the K split S, caps the pieces c of a tail
+// wave-unit (1: no tail cut, 0: no cap) and launches nblk workgroups instead of one per CU.  0 where a field is not given.
+struct PwForced {
+  int S = 0, c = 0, nblk = 0;
+};
+static int pw_forced_plan(tpg_ctx* ctx, PwForced* f) {
+  const char* e = getenv("TPG_PW_PLAN");
+  if (!e || !*e) return TPG_OK;
+  const int got = sscanf(e, "%d,%d,%d", &f->S, &f->c, &f->nblk);
+  TPG_REQUIRE(got >= 1 && f->S >= 1 && f->S <= 96 && f->c >= 0 && (got < 3 || (f->nblk >= 8 && f->nblk % 8 == 0)), TPG_EINVAL,
+              "TPG_PW_PLAN=\"%s\": S[,c[,nblk]] with 1 <= S <= 96, c >= 0 (0: no cap), nblk a multiple of 8", e);
+  return TPG_OK;
 }
 
 // One launch of `kernel` per chunk of the K groups [kg0, kg1), on one workgroup per CU (a multiple of the 8 XCDs).  FP32
 // accumulators: a unit contracts at most 2^24 loci (131072 groups) per split, so that every count it holds is an exactly
 // represented integer; longer ranges go out in several launches of at most 8 x 2^24 loci.  The `nun` units of `d_order` are
 // shared by `per_wg` takers per workgroup (its 4 waves, or the workgroup as one); the kernel walks K in `ksteps` steps per
-// 128-locus group and a unit keeps at least 8 groups (1024 loci); t_step / t_flush: pw_ksplit's cost model, in us.  what: the head of the TPG_DEBUG line.
+// 128-locus group and a piece keeps at least 8 groups (1024 loci).  The dealing is host/host_pwplan.h's (DESIGN.md 3.1 "Dealing"): full
+// rounds of nun x S wave-units, what is left over in one more round cut into c pieces each; S is the cheapest under its cost
+// model, a round costing its K range plus the flush of the accumulators (t_step in us per K step, t_flush in us).
+// what: the head of the TPG_DEBUG line.
 template <class Kernel>
 static int pw_launch_chunks(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1, const char* name,
                             const char* what, Kernel kernel, const int2* d_order, int64_t nun, int per_wg, int ksteps, double t_step,
@@ -981,13 +997,29 @@ static int pw_launch_chunks(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, i
   const int64_t max_groups = 131072;
   int nblk = ctx->num_cu / 8 * 8;
   if (nblk < 8) nblk = 8;
+  PwForced forced;
+  TPG_TRY(pw_forced_plan(ctx, &forced));
+  if (forced.nblk) {
+    TPG_REQUIRE(forced.nblk <= nblk, TPG_EINVAL, "TPG_PW_PLAN: %d workgroups on %d CUs", forced.nblk, ctx->num_cu);
+    nblk = forced.nblk;
+  }
+  const int64_t W = (int64_t)per_wg * nblk;
   for (int64_t c0 = kg0; c0 < kg1; c0 += 8 * max_groups) {
     const int64_t c1 = std::min(kg1, c0 + 8 * max_groups);
-    const int64_t kgs = c1 - c0;
-    const int S = pw_ksplit(nun, ksteps * kgs, 8 * ksteps, ceil_div(kgs, max_groups), (int64_t)per_wg * nblk, t_step, t_flush);
-    if (tpg_env_set("TPG_DEBUG")) fprintf(stderr, "[tpg] %s%lld units, S = %d\n", what, (long long)nun, S);
+    const int64_t kgs = c1 - c0, minS = ceil_div(kgs, max_groups);
+    int64_t S = pwplan_ksplit(nun, ksteps * kgs, 8 * ksteps, minS, W, t_step, t_flush);
+    if (forced.S) {
+      TPG_REQUIRE(forced.S >= minS, TPG_EINVAL, "TPG_PW_PLAN: S = %d leaves more than 2^24 loci to a wave-unit of %lld groups",
+                  forced.S, (long long)kgs);
+      S = forced.S;
+    }
+    const PwPlan p = pwplan_make(nun, S, W, ksteps * kgs, 8 * ksteps, forced.c);
+    if (tpg_env_set("TPG_DEBUG"))
+      fprintf(stderr, "[tpg] %s%lld units, S = %d, %lld full rounds of %lld, tail %lld x %d\n", what, (long long)nun, (int)S,
+              (long long)(p.full / W), (long long)W, (long long)p.L, (int)p.c);
     TPG_LAUNCH(ctx, name, kernel, dim3((unsigned)nblk), dim3(256), 0, (const uint4*)v->T4, v->KG, ksteps * c0, ksteps * c1,
-               (int)pw->nst, (int)ceil_div(pw->n, 32), d_order, nun, S, (const int64_t*)pw->rowpad, pw->acc);
+               (int)pw->nst, (int)ceil_div(pw->n, 32), d_order, nun, (int)S, p.full, p.L, (int)p.c, (const int64_t*)pw->rowpad,
+               pw->acc);
   }
   return TPG_OK;
 }
@@ -1025,12 +1057,14 @@ static int pw_variant() {
 }
 
 static int pw_launch_all(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t kg0, int64_t kg1) {
-  // K split S: units x S wave-units over the resident waves (one wave per SIMD).  Cost model: rounds(S) = ceil(units S / waves)
-  // rounds, a round costs its K range (about 0.55 us per 128-locus group: 30 MFMAs at ~34 cycles) plus the flush of the
-  // accumulators (240 atomic wave-instructions per wave, all waves at once: ~12 us; S = 5 ... 30 measured within 4 %
-  // of each other at 5 000 x 1 000 000, best at 10 - 12).
+  // K split S: units x S wave-units over the resident waves (one wave per SIMD), full rounds plus one tail round of cut
+  // wave-units (host/host_pwplan.h).  Cost model: a round costs its K range (0.548 us per 128-locus group: 30 MFMAs at ~34
+  // cycles) plus the flush of the accumulators (240 atomic wave-instructions per wave, all waves at once: 10.1 us) -- fitted
+  // to the sweep S = 1 ... 14 with the tail on at 5 000 x 1 000 000 (profiles/pwtail_ksplit.txt: within 0.15 ms of every
+  // measured time; S = 1, four full rounds and a tail of 91 x 11, is the fastest there, 17.4 ms against 17.95 at S = 10).
   const auto kernel = pw_variant() == 2 ? tpg_pairwise_kernel<4> : tpg_pairwise_kernel<3>;  // (2: A/B, three groups of prefetch)
-  return pw_launch_chunks(ctx, pw, v, kg0, kg1, "pairwise_mfma", "pairwise: ", kernel, (const int2*)pw->order, pw->nun, 4, 1, 0.55, 12.0);
+  return pw_launch_chunks(ctx, pw, v, kg0, kg1, "pairwise_mfma", "pairwise: ", kernel, (const int2*)pw->order, pw->nun, 4, 1, 0.548,
+                          10.1);
 }
 
 extern "C" int tpg_pairwise_accumulate_products(tpg_ctx* ctx, tpg_pairwise* pw, const tpg_view* v, int64_t col_begin,
