@@ -1816,9 +1816,10 @@ int tpg_cluster_wss(tpg_ctx* ctx, const double* X, int64_t n, int d, int R, cons
  * WSS of a labelling: tpg_cluster_wss above.
  * Relation to R.  hclust$height = sqrt(height).  hclust$merge (tpg_hclust_r_merge): -(i + 1) for point i on its own, the 1-based
  *   step number for a cluster, a singleton before a cluster, of two singletons the smaller point and of two clusters the earlier
- *   step first.  hclust$order is not produced.
+ *   step first.  hclust$order: tpg_hclust_order below.
  * No random generator, no floating-point atomic: the result is a pure function of (X, power), two calls give the same bits.
- * Out of scope: other linkages, a distance matrix as input, order and plots, Ward inside tpg_stream_* / tpg_multi_*. */
+ * Other linkages, a distance matrix as input and order: "Trees from a pairwise matrix" below.
+ * Out of scope: plots, Ward inside tpg_stream_* / tpg_multi_*. */
 #define TPG_HCLUST_MAX_N 32768
 /* merge_a, merge_b (int32) and height: n - 1 entries each (0-based slots), host or device memory; n = 1 writes nothing */
 int tpg_hclust_ward(tpg_ctx* ctx, const double* X, int64_t n, int d, int power, int32_t* merge_a, int32_t* merge_b, double* height);
@@ -1832,6 +1833,66 @@ int tpg_hclust_ward_trace(tpg_ctx* ctx, const double* X, int64_t n, int d, int p
 int tpg_hclust_cut(int64_t n, const int32_t* merge_a, const int32_t* merge_b, int R, const int32_t* k, int32_t* labels);
 /* host only: merge (n - 1) x 2 int32 column-major, R's convention */
 int tpg_hclust_r_merge(int64_t n, const int32_t* merge_a, const int32_t* merge_b, int32_t* merge);
+
+/* ---- Trees from a pairwise matrix (the order function of the reference's heatmap_pairwise() and heatmap_add_dendro(),
+ * function(x) stats::hclust(stats::as.dist(x)), and the neighbour-joining tree users draw from the same matrices;
+ * stats::hclust and ape are not among the reference's sources, so the arithmetic is defined HERE, RECALLED, NOT PINNED BY AN R
+ * RUN) ------------------------------------------------------------------------------------------------------------------------
+ * Input, common to tpg_hclust_dist and tpg_nj.  D is n x n doubles, column-major, host or device memory.  The value of the pair
+ *   {i, j}, i < j, is D[j + i n]: the strict lower triangle, as as.dist reads it.  The diagonal and the upper triangle are never
+ *   read (diag(m) <- NA is harmless, an asymmetric matrix is accepted).  Every entry of the strict lower triangle is finite, else
+ *   TPG_ENUMERIC and nothing is written; negative values are allowed.  1 <= n <= TPG_HCLUST_MAX_N, else TPG_EINVAL before
+ *   anything is allocated.  D is never modified: the working matrix S is a scratch copy, full and symmetric, 8 n^2 bytes.
+ * tpg_hclust_dist.  Slots, outputs and tie rule as tpg_hclust_ward: 0-based slots, a < b at every step, slot a survives (a
+ *   cluster's slot is its smallest member), n - 1 entries, n = 1 writes nothing.  At each step the merged pair is the
+ *   lexicographic minimum of (S(a,b), a, b) over the live pairs a < b; height[s] is that S, no root taken.  Then for every other
+ *   live c, with x = S(a,c), y = S(b,c) and the sizes n_a, n_b, n_c from before the merge converted to double, in FP64, every
+ *   operation rounded once, nothing fused:
+ *     TPG_LINK_SINGLE   0                      S(a,c) = y where y < x, else x
+ *     TPG_LINK_COMPLETE 1 (hclust's default)   S(a,c) = y where y > x, else x
+ *     TPG_LINK_AVERAGE  2 (UPGMA)              p = n_a x,  q = n_b y,  S(a,c) = (p + q) / (n_a + n_b)
+ *     TPG_LINK_MCQUITTY 3 (WPGMA)              S(a,c) = (x + y) 0.5
+ *     TPG_LINK_WARD     4 (ward.D on D as given)   the recurrence of "Ward clustering on PCA scores" above, unchanged
+ *   and S(c,a) = S(a,c); n_a += n_b and b is dead.  Any other method: TPG_EINVAL.  ward.D2 is the caller's business: square the
+ *   input, take the root of the heights.
+ * tpg_hclust_order (host only): hclust$order, 0-based, recalled from hcass2, not pinned.  With R's merge matrix as
+ *   tpg_hclust_r_merge makes it, leaves(row) = leaves(first column) followed by leaves(second column), a negative entry is that
+ *   single point, order = leaves(last row).  n = 1 gives [0].  A merge list that tpg_hclust_cut would refuse: TPG_EINVAL, nothing
+ *   written.
+ * tpg_nj: neighbour-joining (Saitou & Nei 1987 in Studier & Keppler's form; recalled, not pinned by a run of ape).
+ *   State: the live slots, r of them; S; one row sum R_i per live slot.
+ *   Start: R_i = sum of S(i,j) over j != i, ascending j, from +0.0, one addition per j.
+ *   While r > 2 (join s = 0 .. n - 3), every operator one rounded FP64 operation, left to right:
+ *     q(a,b) = ((double)(r - 2) S(a,b) - R_a) - R_b for the live a < b; the join is the lexicographic minimum of (q, a, b); a
+ *       NaN q never wins.
+ *     d = S(a,b);  len_a[s] = 0.5 d + (R_a - R_b) / (2.0 (double)(r - 2));  len_b[s] = d - len_a[s].
+ *     For every other live c, x = S(a,c), y = S(b,c):  t = ((x + y) - d) 0.5;  R_c = ((R_c - x) - y) + t;  S(a,c) = S(c,a) = t.
+ *     R_a = ((R_a + R_b) - (double)r d) 0.5 with the R_a, R_b and r of before the join: the exact algebraic identity for the sum
+ *       of the t, so that no reduction and no summation order enters.  Slot a holds the new node, slot b is dead, r -= 1.
+ *   End: the two slots left are x < y; last = (x, y, S(x,y)), three doubles.  join_a, join_b, len_a, len_b: n - 2 entries; n = 2
+ *     writes only last; n = 1 writes nothing.  Branch lengths may come out negative and are returned as they are.
+ *   The row sums are UPDATED, not recomputed: in the numpy restatement they drift from recomputed sums by 3e-13 relative at
+ *     n = 301.  The definition is the updated sums.
+ *   A step that finds no pair (every q NaN after an overflow): TPG_ENUMERIC, nothing written.
+ * tpg_nj_edges (host only): the tree in ape's phylo layout, recalled, not pinned; n >= 3, else TPG_EINVAL.  Tips are 1 .. n, the
+ *   node of join s is 2n - 2 - s, so the last join is the root n + 1 and Nnode = n - 2.  The root has three children: its a-child,
+ *   its b-child and the node of the other slot left (one of the two slots left is always the last join's), at length last[2].
+ *   2n - 3 edges; edge is (2n - 3) x 2 int32 column-major (parent, child), in preorder from the root, a-child before b-child
+ *   before the third; edge_length alike.  A join list that names a dead slot, a pair outside 0 <= a < b < n, or a last that does
+ *   not name the two slots left: TPG_EINVAL, nothing written.
+ * No random generator, no floating-point atomic: every result is a pure function of the lower triangle (and method).
+ * Out of scope: an R shim entry, the forwarding of gt_cluster_pca(method = "ward"), centroid and median linkage (not monotone),
+ *   bootstrap support of a tree over locus blocks, BIONJ / FastME, rooting and plotting, trees inside tpg_stream_* / tpg_multi_*. */
+#define TPG_LINK_SINGLE 0
+#define TPG_LINK_COMPLETE 1
+#define TPG_LINK_AVERAGE 2
+#define TPG_LINK_MCQUITTY 3
+#define TPG_LINK_WARD 4
+int tpg_hclust_dist(tpg_ctx* ctx, const double* D, int64_t n, int method, int32_t* merge_a, int32_t* merge_b, double* height);
+int tpg_hclust_order(int64_t n, const int32_t* merge_a, const int32_t* merge_b, int32_t* order);
+int tpg_nj(tpg_ctx* ctx, const double* D, int64_t n, int32_t* join_a, int32_t* join_b, double* len_a, double* len_b, double* last);
+int tpg_nj_edges(int64_t n, const int32_t* join_a, const int32_t* join_b, const double* len_a, const double* len_b, const double* last,
+                 int32_t* edge, double* edge_length);
 
 /* ---- DAPC (gt_dapc, R/gt_dapc.R:137-255 around MASS::lda(XU, pop, tol = 1e-30) and predict(); MASS is not among the
  * reference's sources, so the discriminant analysis is defined HERE, RECALLED FROM MASS, NOT PINNED) ---------------------------

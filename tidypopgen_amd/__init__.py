@@ -11,3 +11,4 @@ from .api import fst_perm_labels, fst_perm_pvalue, fst_relabel_sums, pairwise_po
 from .api import DeviceMatrix, amova_from_sums, amova_perm_labels, class_sums, gt_amova, pairwise_sqdist  # noqa: F401
 from .api import (great_circle_dist, gt_mantel, mantel_from_sums, mantel_partial, mantel_pass_rows, mantel_perms, mantel_scratch_bytes,  # noqa: F401
                   mantel_sums, offdiag_center, offdiag_midranks, offdiag_moments)
+from .api import gt_hclust, gt_nj, hclust_dist, hclust_order, nj, nj_edges, nj_newick  # noqa: F401

@@ -394,6 +394,11 @@ PROTOTYPES = {
     "tpg_hclust_ward_trace": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp]),
     "tpg_hclust_cut": (ci, [i64, vp, vp, ci, vp, vp]),
     "tpg_hclust_r_merge": (ci, [i64, vp, vp, vp]),
+    # ---- trees from a pairwise matrix
+    "tpg_hclust_dist": (ci, [vp, vp, i64, ci, vp, vp, vp]),
+    "tpg_hclust_order": (ci, [i64, vp, vp, vp]),
+    "tpg_nj": (ci, [vp, vp, i64, vp, vp, vp, vp, vp]),
+    "tpg_nj_edges": (ci, [i64, vp, vp, vp, vp, vp, vp, vp]),
     # ---- DAPC
     "tpg_lda": (ci, [vp, i64, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tpg_dapc_var_contr": (ci, [vp, vp, i64, i64, ci, vp, ci, vp, vp]),

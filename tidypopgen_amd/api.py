@@ -2981,6 +2981,114 @@ def hclust_cut(tree: dict, k) -> np.ndarray:
     return labels[:n]
 
 
+# ---- trees from a pairwise matrix (include/tpg.h "Trees from a pairwise matrix")
+
+LINKAGES = {"single": 0, "complete": 1, "average": 2, "mcquitty": 3, "ward.D": 4, "ward.D2": 4}  # TPG_LINK_*
+
+
+def _tree_operand(D, ctx):
+    """D (numpy n x n or DeviceMatrix) -> (ctx, n, pointer, the object that keeps the pointer alive)"""
+    if isinstance(D, DeviceMatrix):
+        return D.ctx, D.n, D.p, D
+    keep = np.asfortranarray(D, dtype=np.float64)
+    if keep.ndim != 2 or keep.shape[0] != keep.shape[1]:
+        raise ValueError("D must be a square matrix")
+    return ctx or default_context(), keep.shape[0], _ptr(keep), keep
+
+
+def hclust_order(tree: dict) -> np.ndarray:
+    """tpg_hclust_order (host only): hclust$order of a tree of hclust_ward / hclust_dist, 1-based as R"""
+    n = int(tree["n"])
+    ma, mb = _i32(tree["merge_a"]), _i32(tree["merge_b"])
+    if len(ma) != n - 1 or len(mb) != n - 1:
+        raise ValueError(f"a tree of {n} points has {n - 1} merges")
+    order = np.zeros(max(n, 1), dtype=np.int32)
+    check(lib.tpg_hclust_order(n, _ptr(ma if n > 1 else None), _ptr(mb if n > 1 else None), _ptr(order)))
+    return order[:n] + 1
+
+
+def hclust_dist(D, method: str = "complete", ctx: Optional[Context] = None) -> dict:
+    """tpg_hclust_dist: stats::hclust(as.dist(D), method) on the strict lower triangle of D (a numpy array or a DeviceMatrix,
+    never modified).  method: single, complete, average, mcquitty, ward.D, ward.D2 (the recurrence of ward.D on the squared
+    matrix, the root of its heights).  -> the dict of hclust_ward (n, merge_a, merge_b, height, merge) plus order (1-based, as R)
+    and method; hclust_cut works on it unchanged."""
+    if method not in LINKAGES:
+        raise ValueError(f"method must be one of {', '.join(LINKAGES)}")
+    ctx, n, p, keep = _tree_operand(D, ctx)
+    if method == "ward.D2":  # squared on the host: the caller's matrix stays as it is
+        keep = np.asfortranarray(keep.to_numpy() if isinstance(keep, DeviceMatrix) else keep) ** 2
+        p = _ptr(keep)
+    m = max(n - 1, 0)
+    ma, mb, h = np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1))
+    check(lib.tpg_hclust_dist(ctx.h, p, n, LINKAGES[method], _ptr(ma), _ptr(mb), _ptr(h)))
+    merge = np.zeros((m, 2), dtype=np.int32, order="F")
+    check(lib.tpg_hclust_r_merge(n, _ptr(ma), _ptr(mb), _ptr(merge if m else None)))
+    out = dict(n=n, merge_a=ma[:m], merge_b=mb[:m], height=np.sqrt(h[:m]) if method == "ward.D2" else h[:m], merge=merge, method=method)
+    out["order"] = hclust_order(out)
+    return out
+
+
+def nj(D, ctx: Optional[Context] = None) -> dict:
+    """tpg_nj: the neighbour-joining tree of the strict lower triangle of D (a numpy array or a DeviceMatrix, never modified).
+    -> dict(n, join_a, join_b (0-based slots, n - 2 joins), len_a, len_b (the branch of either slot to the new node), last
+    (x, y, S(x, y)) of the two slots left; empty for n = 1)"""
+    ctx, n, p, keep = _tree_operand(D, ctx)
+    j = max(n - 2, 0)
+    ja, jb = np.zeros(max(j, 1), dtype=np.int32), np.zeros(max(j, 1), dtype=np.int32)
+    la, lb, last = np.zeros(max(j, 1)), np.zeros(max(j, 1)), np.zeros(3)
+    check(lib.tpg_nj(ctx.h, p, n, _ptr(ja), _ptr(jb), _ptr(la), _ptr(lb), _ptr(last)))
+    return dict(n=n, join_a=ja[:j], join_b=jb[:j], len_a=la[:j], len_b=lb[:j], last=last if n >= 2 else last[:0])
+
+
+def nj_edges(tree: dict) -> dict:
+    """tpg_nj_edges (host only): a tree of nj() in ape's phylo layout -> dict(edge ((2n - 3) x 2, parent and child, tips 1 .. n,
+    root n + 1, preorder), edge_length, Nnode = n - 2); n >= 3"""
+    n = int(tree["n"])
+    ja, jb, la, lb, last = _i32(tree["join_a"]), _i32(tree["join_b"]), _f64(tree["len_a"]), _f64(tree["len_b"]), _f64(tree["last"])
+    if n >= 3 and (any(len(v) != n - 2 for v in (ja, jb, la, lb)) or len(last) != 3):
+        raise ValueError(f"a tree of {n} tips has {n - 2} joins and a last of 3")
+    e = max(2 * n - 3, 1)
+    edge, length = np.zeros((e, 2), dtype=np.int32, order="F"), np.zeros(e)
+    check(lib.tpg_nj_edges(n, _ptr(ja), _ptr(jb), _ptr(la), _ptr(lb), _ptr(last), _ptr(edge), _ptr(length)))
+    return dict(edge=edge, edge_length=length, Nnode=n - 2)
+
+
+def nj_newick(tree: dict, labels=None, fmt: str = "%.17g") -> str:
+    """The tree of nj() as Newick text, unrooted with a trifurcation at the root; labels default "1" .. "n" """
+    n = int(tree["n"])
+    labels = [str(i + 1) for i in range(n)] if labels is None else [str(v) for v in labels]
+    if len(labels) != n:
+        raise ValueError("labels must name every tip")
+    e = nj_edges(tree)
+    kids = {}
+    # preorder: the edges below a node follow its own, so going backwards every child is complete when its edge comes up
+    for (parent, child), length in zip(e["edge"][::-1].tolist(), e["edge_length"][::-1].tolist()):
+        text = labels[child - 1] if child <= n else "(" + ",".join(reversed(kids.pop(child))) + ")"
+        kids.setdefault(parent, []).append(text + ":" + fmt % length)
+    return "(" + ",".join(reversed(kids[n + 1])) + ");"
+
+
+def _gt_tree_matrix(X, ind_row, ind_col, dist, dist_type):
+    if (X is None) == (dist is None):
+        raise ValueError("give either X or dist")
+    return pairwise_sqdist(X, ind_row, ind_col, dist_type, device=True) if dist is None else dist
+
+
+def gt_hclust(X: Optional[FBM] = None, ind_row=None, ind_col=None, dist=None, dist_type: str = "raw", method: str = "complete") -> dict:
+    """The tree the reference's heatmaps order by, stats::hclust(as.dist(.), method): of the squared genotype distances of X (one
+    pairwise pass, dist_type "raw" or "adjusted", kept in HBM), or of dist (n x n matrix or DeviceMatrix), e.g. 1 - snp_ibs(X)
+    for individuals or the fst_tot matrix of pairwise_pop_fst for populations.  -> hclust_dist's dict."""
+    if method not in LINKAGES:
+        raise ValueError(f"method must be one of {', '.join(LINKAGES)}")
+    return hclust_dist(_gt_tree_matrix(X, ind_row, ind_col, dist, dist_type), method, ctx=X.ctx if X is not None else None)
+
+
+def gt_nj(X: Optional[FBM] = None, ind_row=None, ind_col=None, dist=None, dist_type: str = "raw") -> dict:
+    """The neighbour-joining tree of the squared genotype distances of X (kept in HBM) or of dist, as gt_hclust takes them.
+    -> nj's dict; nj_edges and nj_newick turn it into ape's layout and into text."""
+    return nj(_gt_tree_matrix(X, ind_row, ind_col, dist, dist_type), ctx=X.ctx if X is not None else None)
+
+
 def cluster_wss(X, labels, k, return_counts: bool = False, ctx: Optional[Context] = None):
     """tpg_cluster_wss: the within-group sum of squares of every column of labels (n x R, 0-based, column r in [0, k[r])) in one
     call, by the kernels a run of kmeans_batch ends in -> wss (R)[, counts: a list of k_r points per label]"""

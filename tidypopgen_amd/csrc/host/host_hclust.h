@@ -82,3 +82,36 @@ static inline int host_hclust_r_merge(int64_t n, const int32_t* merge_a, const i
   }
   return HOST_HCLUST_OK;
 }
+
+// order[n], 0-based, as R's hclust$order (recalled from hcass2, not pinned): with R's merge matrix above, the leaves of a row are
+// the leaves of its first column followed by those of its second, a negative entry is that single point, and order is the leaves
+// of the last row.  n = 1 gives [0].  Nothing is written unless the merge list passes host_hclust_check.
+static inline int host_hclust_order(int64_t n, const int32_t* merge_a, const int32_t* merge_b, int32_t* order, const char** why) {
+  if (n < 1) {
+    *why = "n < 1";
+    return HOST_HCLUST_EINVAL;
+  }
+  const int64_t rows = n - 1;
+  std::vector<int32_t> merge((size_t)(2 * rows));
+  const int rc = host_hclust_r_merge(n, merge_a, merge_b, merge.data(), why);
+  if (rc != HOST_HCLUST_OK) return rc;
+  if (n == 1) {
+    order[0] = 0;
+    return HOST_HCLUST_OK;
+  }
+  // a stack in place of the recursion (a chain of n - 1 merges is n - 1 deep): the second column goes on first, so the first
+  // comes off first
+  std::vector<int32_t> todo;
+  todo.push_back((int32_t)rows);
+  int64_t at = 0;
+  while (!todo.empty()) {
+    const int32_t e = todo.back();
+    todo.pop_back();
+    if (e < 0) order[at++] = -e - 1;
+    else {
+      todo.push_back(merge[(size_t)(rows + e - 1)]);
+      todo.push_back(merge[(size_t)(e - 1)]);
+    }
+  }
+  return HOST_HCLUST_OK;
+}
